@@ -6,10 +6,15 @@ UNet_light (874 864 params) + fused softmax-Dice + Adam, one step = zero_grad / 
 [flat-bucket gradient all-reduce] / Adam over a batch of 2 synthetic volumes per GPU (weak scaling: per-GPU batch fixed).
 Inputs are resident in HBM before the timed region.  One JSON line on rank 0.
 
-After the headline the default run also times configs[2] (reg-only) and configs[3]'s per-GPU shape (joint alternating step,
-1 pair per GPU) for the same --steps / --warmup and reports them under "extra" (north_star's target is quoted on the joint step).
+A plain run sets up, warms up, times the K steps of the headline workload and prints the line (`value`, `ms_per_step`).  --full adds
+everything else the benchmark measures: per-call HIP-event timing of the convolutions and the roofline block, the same K steps with a
+host read of the loss per step, the all-reduce timed on its own (N > 1), configs[2] (reg-only) and configs[3]'s per-GPU shape (joint
+alternating step, 1 pair per GPU) for the same --steps / --warmup under "extra" (north_star's target is quoted on the joint step), the
+fp32-matrix A/B, configs[4]'s shape and precisions, and the CPU baseline with the full-size parity block.  --dump-outputs DIR writes what
+the last timed step computed (its loss and the parameters it updated) as DIR/<name>.npy.
 
-  python bench.py --gpus N --steps K --warmup W          (N > 1 without a launcher: re-executes itself under torch.distributed.run)
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+                                                          (N > 1 without a launcher: re-executes itself under torch.distributed.run)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 import argparse
@@ -21,6 +26,7 @@ import socket
 import subprocess
 import sys
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
@@ -255,9 +261,35 @@ def self_spawn(n):
 class Workload:
     """One timed configuration: step() closure + what one step amounts to."""
 
-    def __init__(self, name, step, units, unit, flops_per_step, loss_of, optimizers=()):
+    def __init__(self, name, step, units, unit, flops_per_step, loss_of, optimizers=(), models=()):
         self.name, self.step, self.units, self.unit, self.flops_per_step, self.loss_of = name, step, units, unit, flops_per_step, loss_of
         self.optimizers = list(optimizers)          # the FlatAdam buckets this step all-reduces (one collective each)
+        self.models = list(models)                  # (prefix, module): the networks whose parameters / buffers the step updates
+
+
+DUMP_BUDGET_BYTES = 60 << 20        # --dump-outputs: under 64 MB in all, .npy headers included
+
+
+def dump_outputs(out_dir, loss, wl):
+    """--dump-outputs: what a caller of the timed step holds after its last step -- the returned loss and every floating-point parameter /
+    buffer of the networks it trained -- as out_dir/<name>.npy (float32; float64 stays float64).  Past DUMP_BUDGET_BYTES every array is cut
+    to the same fraction of its elements, drawn (flattened, in index order) by a generator seeded with the array's name."""
+    import numpy as np
+    arrays = {'loss': np.array([loss], dtype=np.float32)}
+    for prefix, m in wl.models:
+        for k, v in m.state_dict().items():
+            if v.dtype.is_floating_point:
+                arrays['%s.%s' % (prefix, k)] = v.detach().to('cpu', torch.float64 if v.dtype == torch.float64 else torch.float32).contiguous().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    frac = min(1.0, DUMP_BUDGET_BYTES / float(total))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if frac < 1.0 and a.size > 1:
+            a = a.reshape(-1)
+            idx = np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, max(1, int(a.size * frac)), replace=False)
+            a = a[np.sort(idx)]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return len(arrays)
 
 
 def make_workloads(args, dev, rank, which):
@@ -322,7 +354,7 @@ def make_workloads(args, dev, rank, which):
             nm = 'seg-only full UNet (32-512 ch) + softmax-Dice + Adam training step, batch %d/GPU, %dx%dx%d %s (SURVEY row f3, not a BASELINE config)' % (
                 args.batch, shape[0], shape[1], shape[2], prec)
             fl = None
-        out['seg'] = Workload(nm, seg_step, args.batch, 'volumes/s', fl, lambda r: r, [opt])
+        out['seg'] = Workload(nm, seg_step, args.batch, 'volumes/s', fl, lambda r: r, [opt], [('seg', model)])
     if 'joint_smooth' in which:
         which = list(which) + ['joint']
     if 'reg' in which or 'joint' in which:
@@ -355,14 +387,15 @@ def make_workloads(args, dev, rank, which):
             rstep = RegistrationStep(reg, ropt)
             reg_fn = (lambda: rstep(im_m, im_t)[0]) if not args.graph else graphed(*rstep.segments(im_m, im_t), 'loss')
             out['reg'] = Workload('reg-only VoxelMorph + trilinear warp + NCC + bending + Adam, 1 pair/GPU, %dx%dx%d %s (BASELINE configs[2])'
-                                  % (shape + (prec,)), reg_fn, 1, 'pairs/s', REG_TRAIN_FLOP_PER_VOXEL * V, lambda r: r, [ropt])
+                                  % (shape + (prec,)), reg_fn, 1, 'pairs/s', REG_TRAIN_FLOP_PER_VOXEL * V, lambda r: r, [ropt], [('reg', reg)])
         if 'joint' in which:
             jstep = DeepAtlasJointStep(model, opt, reg, ropt, n_classes)
             joint_fn = (lambda: jstep(im_m, im_t, sm, st_)['loss_seg']) if not args.graph else graphed(*jstep.segments(im_m, im_t, sm, st_), 'loss_seg')
             out['joint'] = Workload('joint DeepAtlas alternating step (reg phase + seg phase, 32-ch seg warp), 1 pair/GPU, %dx%dx%d %s '
                                     '(BASELINE configs[3] per-GPU shape)' % (shape + (prec,)),
                                     joint_fn, 1, 'pairs/s',
-                                    (SEG_TRAIN_FLOP_PER_VOXEL + REG_TRAIN_FLOP_PER_VOXEL) * V if args.net == 'UNet_light' else None, lambda r: r, [ropt, opt])
+                                    (SEG_TRAIN_FLOP_PER_VOXEL + REG_TRAIN_FLOP_PER_VOXEL) * V if args.net == 'UNet_light' else None, lambda r: r, [ropt, opt],
+                                    [('seg', model), ('reg', reg)])
             if smooth:
                 out['joint_smooth'] = out.pop('joint')
                 out['joint_smooth'].name += ' -- on registration-like inputs: blocky label maps and a smooth field (shift of 1 - 2 voxels + 0.05 voxels of texture) instead of iid labels and the untrained net\'s 8-voxel noise'
@@ -513,7 +546,7 @@ def main():
     ap.add_argument('--precision', default='fp32_split', choices=['fp32_split', 'fp32', 'bf16', 'bf16_storage'],
                     help="matrix arithmetic of the 3x3x3 convolutions.  'fp32_split' (headline): fp32 operands scaled per tile and split into two fp16 "
                          "terms, three partial products per multiply on the fp16 pipe, fp32 accumulate -- 22-bit products (per product narrower than fp32); 'fp32': the fp32 matrix "
-                         "instructions (one fmaf per product; also timed by the default run, under extra.native_fp32_mfma); 'bf16': operands "
+                         "instructions (one fmaf per product; also timed by --full, under extra.native_fp32_mfma); 'bf16': operands "
                          "ROUNDED to bf16 (BASELINE configs[4]'s mixed precision; never the headline)")
     ap.add_argument('--graph', action='store_true', help='capture each step once as HIP graph(s) and replay it (one host call per step; per-call '
                     'HIP-event timing is then taken in the eager post-run pass only)')
@@ -523,7 +556,15 @@ def main():
                     help="segmentation network of the 'seg' workload; 'UNet' = the fixed 19 M-parameter net (SURVEY.md row f3), not the headline config")
     ap.add_argument('--workload', default='seg', choices=['seg', 'reg', 'joint', 'joint_smooth'],
                     help="headline leg: 'seg' = BASELINE configs[1] (the metric); 'reg' / 'joint' = configs[2] / [3] per-GPU shapes (1 pair / GPU)")
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: per-call timing + roofline, the loss-read pass, the all-reduce leg, the reg / joint / fp32-matrix / '
+                         "configs[4] legs, the CPU baseline and the full-size parity block (--no-cpu-baseline / --no-profile / --no-extra "
+                         'drop parts of it).  Without it only the headline workload is set up, warmed up and timed')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the loss of the last one and the parameters / buffers it left (float32) as DIR/<name>.npy')
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_extra = args.no_profile = True
 
     want = max(args.gpus, 1)
     if 'WORLD_SIZE' not in os.environ and want > 1:
@@ -590,6 +631,8 @@ def main():
     head = wls[args.workload]
     dt, per_rank, final_loss, prof, launches = time_workload(head, args, world, dev, None if (args.no_profile or args.graph) else CONV_FWD_CALLS)
     head_res = result_of(head, dt, per_rank, world, args, launches)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, final_loss, head)
     # the same K steps with the host reading the loss every step, as SegmentationExperiment.train_one_epoch does (models/segmentation.py:160
     # of the reference: `loss.item()` per iteration): one device synchronisation per step
     sync_ms = None
@@ -602,7 +645,7 @@ def main():
         sync_ms = round((time.perf_counter() - t0) / args.steps * 1e3, 3)
 
     allreduce = None
-    if world > 1:
+    if world > 1 and args.full:
         # the step's only collective, timed on its own: the flat-bucket gradient all-reduce(s) of one step (seg 3.5 MB; reg 1.0 MB),
         # 20 back-to-back calls between device synchronisations, maximum over the ranks
         buckets = head.optimizers

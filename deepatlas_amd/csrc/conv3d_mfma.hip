@@ -101,7 +101,7 @@ __global__ void __launch_bounds__(256, WPE) conv3_mfma_fwd_kernel(FwdP p) {
         return;
     }
     // DYN: this workgroup's XCD range [xlo, xhi) of the brick order, its counter, and the ring of drawn positions.  (Out-of-range
-    // buffer ATOMICS fault on gfx950 -- tools/ubench/buffer_atomic_oob.hip -- so the draw sits in an exec-mask branch of thread 0.)
+    // buffer ATOMICS fault on gfx950, so the draw sits in an exec-mask branch of thread 0.)
     int xlo = 0, xhi = 0;
     int* sp = reinterpret_cast<int*>(reinterpret_cast<char*>(lds) + (size_t)StageGeom<CK, HZ>::TOTAL * 4 * EB * NP);
     int* ctr = nullptr;

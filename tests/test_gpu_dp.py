@@ -190,7 +190,7 @@ def test_bench_multi_rank_code_path_on_a_shared_device():
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
     env['DA_BENCH_SHARE_DEVICE'] = '1'
     out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--shape', '32', '32', '32',
-                          '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=900)
+                          '--full', '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith('{"metric"')][-1])
     assert line['n_gpus'] == 2 and line['scaling'] == 'weak' and line['config']['parallelism'] == 'dp2' and line['config']['global_batch'] == 4

@@ -212,8 +212,8 @@ def test_two_term_fp16_split_bounds_and_sums_are_fp32_accurate():
 
 
 def test_asan_build_recipe_and_roctx_ranges(tmp_path):
-    """SURVEY.md section 5 build notes: the -fsanitize=address variant compiles (one small source: host + device instrumentation for
-    gfx950:xnack+), and the roctx range helper is inert when disabled and pushes / pops through the ROCm roctx library when enabled."""
+    """SURVEY.md section 5 build notes: the -fsanitize=address variant compiles (one small source: host instrumentation, device code for
+    plain gfx950), and the roctx range helper is inert when disabled and pushes / pops through the ROCm roctx library when enabled."""
     import subprocess
     import __graft_entry__ as g
     lib = g.build_asan(sources=['optim.hip'])

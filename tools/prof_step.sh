@@ -5,7 +5,7 @@ w=$1; tag=$2
 cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/${ROUND:-r04}; mkdir -p $O
-timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_$tag -- python bench.py --workload $w --steps 6 --warmup 2 --no-cpu-baseline --no-extra > $O/prof_$tag.log 2>&1 < /dev/null
+timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_$tag -- python bench.py --full --workload $w --steps 6 --warmup 2 --no-cpu-baseline --no-extra > $O/prof_$tag.log 2>&1 < /dev/null
 f=$(ls $O/prof_$tag/*/*.db 2>/dev/null | head -1)
 if [ -n "$f" ]; then
   python tools/rocpd_summary.py "$f" --top 60 > $O/${tag}_kernel_stats.txt 2>&1 < /dev/null

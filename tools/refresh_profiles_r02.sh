@@ -6,24 +6,24 @@ cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r02; rm -rf $O; mkdir -p $O
 git rev-parse --short HEAD > $O/commit.txt 2>/dev/null || true
-timeout 900 python bench.py > $O/bench_default.log 2>&1 < /dev/null
+timeout 900 python bench.py --full > $O/bench_default.log 2>&1 < /dev/null
 grep '"metric"' $O/bench_default.log | tail -1 > $O/bench_default.json
-timeout 600 python bench.py --no-cpu-baseline --graph > $O/bench_graph.log 2>&1 < /dev/null
+timeout 600 python bench.py --full --no-cpu-baseline --graph > $O/bench_graph.log 2>&1 < /dev/null
 grep '"metric"' $O/bench_graph.log | tail -1 > $O/bench_graph.json
-timeout 600 python bench.py --no-cpu-baseline --shape 192 224 192 > $O/bench_192x224x192.log 2>&1 < /dev/null
+timeout 600 python bench.py --full --no-cpu-baseline --shape 192 224 192 > $O/bench_192x224x192.log 2>&1 < /dev/null
 grep '"metric"' $O/bench_192x224x192.log | tail -1 > $O/bench_192x224x192.json
-timeout 600 python bench.py --no-cpu-baseline --precision fp32 > $O/bench_fp32_mfma.log 2>&1 < /dev/null
+timeout 600 python bench.py --full --no-cpu-baseline --precision fp32 > $O/bench_fp32_mfma.log 2>&1 < /dev/null
 grep '"metric"' $O/bench_fp32_mfma.log | tail -1 > $O/bench_fp32_mfma.json
-timeout 600 python bench.py --no-cpu-baseline --precision bf16 > $O/bench_bf16.log 2>&1 < /dev/null
+timeout 600 python bench.py --full --no-cpu-baseline --precision bf16 > $O/bench_bf16.log 2>&1 < /dev/null
 grep '"metric"' $O/bench_bf16.log | tail -1 > $O/bench_bf16.json
-timeout 600 python bench.py --no-cpu-baseline --precision bf16 --shape 192 224 192 > $O/bench_bf16_192x224x192.log 2>&1 < /dev/null
+timeout 600 python bench.py --full --no-cpu-baseline --precision bf16 --shape 192 224 192 > $O/bench_bf16_192x224x192.log 2>&1 < /dev/null
 grep '"metric"' $O/bench_bf16_192x224x192.log | tail -1 > $O/bench_bf16_192x224x192.json
-timeout 600 python bench.py --no-cpu-baseline --shape 32 32 32 --steps 20 --warmup 5 --no-profile > $O/bench_host_floor_32.log 2>&1 < /dev/null
+timeout 600 python bench.py --full --no-cpu-baseline --shape 32 32 32 --steps 20 --warmup 5 --no-profile > $O/bench_host_floor_32.log 2>&1 < /dev/null
 grep '"metric"' $O/bench_host_floor_32.log | tail -1 > $O/bench_host_floor_32.json
-timeout 600 python bench.py --no-cpu-baseline --shape 32 32 32 --steps 20 --warmup 5 --graph > $O/bench_host_floor_32_graph.log 2>&1 < /dev/null
+timeout 600 python bench.py --full --no-cpu-baseline --shape 32 32 32 --steps 20 --warmup 5 --graph > $O/bench_host_floor_32_graph.log 2>&1 < /dev/null
 grep '"metric"' $O/bench_host_floor_32_graph.log | tail -1 > $O/bench_host_floor_32_graph.json
 for w in seg reg joint; do
-  timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_$w -- python bench.py --workload $w --steps 6 --warmup 2 --no-cpu-baseline --no-extra > $O/prof_$w.log 2>&1 < /dev/null
+  timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_$w -- python bench.py --full --workload $w --steps 6 --warmup 2 --no-cpu-baseline --no-extra > $O/prof_$w.log 2>&1 < /dev/null
   f=$(ls $O/prof_$w/*/*.db 2>/dev/null | head -1)
   if [ -n "$f" ]; then
     python tools/rocpd_summary.py "$f" --top 60 > $O/${w}_kernel_stats.txt 2>&1 < /dev/null

@@ -5,16 +5,16 @@
 cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r05p; rm -rf $O; mkdir -p $O
-timeout 1500 python bench.py > $O/bench_default.log 2>&1 < /dev/null
+timeout 1500 python bench.py --full > $O/bench_default.log 2>&1 < /dev/null
 grep '"metric"' $O/bench_default.log | tail -1 > $O/bench_default.json
-timeout 1200 python bench.py --steps 20 --warmup 5 > $O/bench_driver_style.log 2>&1 < /dev/null
+timeout 1200 python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_style.log 2>&1 < /dev/null
 grep '"metric"' $O/bench_driver_style.log | tail -1 > $O/bench_driver_style_steps20.json
-timeout 600 python bench.py --no-cpu-baseline --no-extra --precision fp32 > $O/bench_fp32_mfma.log 2>&1 < /dev/null
+timeout 600 python bench.py --full --no-cpu-baseline --no-extra --precision fp32 > $O/bench_fp32_mfma.log 2>&1 < /dev/null
 grep '"metric"' $O/bench_fp32_mfma.log | tail -1 > $O/bench_fp32_mfma.json
-timeout 600 python bench.py --no-cpu-baseline --precision bf16_storage > $O/bench_bf16_storage.log 2>&1 < /dev/null
+timeout 600 python bench.py --full --no-cpu-baseline --precision bf16_storage > $O/bench_bf16_storage.log 2>&1 < /dev/null
 grep '"metric"' $O/bench_bf16_storage.log | tail -1 > $O/bench_bf16_storage.json
 for w in seg reg joint; do
-  timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_$w -- python bench.py --workload $w --steps 6 --warmup 2 --no-cpu-baseline --no-extra > $O/prof_$w.log 2>&1 < /dev/null
+  timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_$w -- python bench.py --full --workload $w --steps 6 --warmup 2 --no-cpu-baseline --no-extra > $O/prof_$w.log 2>&1 < /dev/null
   f=$(ls $O/prof_$w/*/*.db 2>/dev/null | head -1)
   if [ -n "$f" ]; then
     python tools/rocpd_summary.py "$f" --top 60 > $O/${w}_kernel_stats.txt 2>&1 < /dev/null
