@@ -226,12 +226,9 @@ constexpr int YROW = TX * 2;                                             // byte
 constexpr int NDY = (HVOX * 3 + 255) / 256;                              // dword loads per thread for the dy halo tile, Cout <= 3 (9)
 }
 
-// W8: eight waves -- wave pairs (w, w + 4) share the K-steps and take half of the M-tiles each: half the accumulators and half the staging registers per thread, so that
-// two 512-thread workgroups fit a CU (<= 128 registers) and twice as many loads are in flight
-template <int MT, bool TWO, int S1, bool W8>
-__global__ void __launch_bounds__(W8 ? 512 : 256, W8 ? 4 : 2) flow_wgrad_split_kernel(FlowWgP p) {
-    constexpr int NTHR = W8 ? 512 : 256, MTW = W8 ? MT / 2 : MT;
-    static_assert(!W8 || MT % 2 == 0, "M-tiles split over wave pairs");
+template <int MT, bool TWO, int S1>
+__global__ void __launch_bounds__(256, 2) flow_wgrad_split_kernel(FlowWgP p) {
+    constexpr int NTHR = 256;
     constexpr int TZ = sp::TZ, TY = sp::TY, TX = sp::TX, TVOX = sp::TVOX, HZ = sp::HZ, HY = sp::HY, HX = sp::HX, HVOX = sp::HVOX, CHS = sp::CHS, YROW = sp::YROW, NDY = (sp::HVOX * 3 + NTHR - 1) / NTHR;
     (void)TZ;
     constexpr int NTT = TWO ? 2 : 1;
@@ -255,20 +252,19 @@ __global__ void __launch_bounds__(W8 ? 512 : 256, W8 ? 4 : 2) flow_wgrad_split_k
     __syncthreads();
 
     // A rows of this lane: m = 16 mt + i -> (tap, co); byte offset of the row's window in the dy copies for K-step row pair (z, y): + (z * HY + y) * YROW
-    const int mt0 = W8 ? (wave >> 2) * MTW : 0;               // this wave's first M-tile
-    int offA[MTW];
+    int offA[MT];
 #pragma unroll
-    for (int mt = 0; mt < MTW; ++mt) {
-        const int m = 16 * (mt0 + mt) + i;
+    for (int mt = 0; mt < MT; ++mt) {
+        const int m = 16 * mt + i;
         const bool ok = m < 27 * Cout;
         const int tap = ok ? m / Cout : 13, co = ok ? m % Cout : 0;
         const int tz = tap / 9, ty = (tap / 3) % 3, tx = tap % 3;
         // dy[p - (tap - 1)]: halo row (z + 2 - tz, y + 2 - ty), x window starting at x + 2 - tx -> copy (2 - tx)
         offA[mt] = ok ? ((((2 - tx) * 3 + co) * HZ + (2 - tz)) * HY + (2 - ty)) * YROW + (g & 1) * 16 + (g >> 1) * YROW : -1;
     }
-    f32x4 acc[MTW][NTT];
+    f32x4 acc[MT][NTT];
 #pragma unroll
-    for (int mt = 0; mt < MTW; ++mt)
+    for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
         for (int nt = 0; nt < NTT; ++nt) acc[mt][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
@@ -442,7 +438,7 @@ __global__ void __launch_bounds__(W8 ? 512 : 256, W8 ? 4 : 2) flow_wgrad_split_k
     int Ecur = 0;
     if (t_begin < t_end) { issue(t_begin); Ecur = stage(); }
     __syncthreads();
-    const int zw = (wave & 3) >> 1, yw = (wave & 1) * 4;
+    const int zw = wave >> 1, yw = (wave & 1) * 4;
 #pragma unroll 1
     for (int tile = t_begin; tile < t_end; ++tile) {
         const bool has_next = tile + 1 < t_end;
@@ -450,7 +446,7 @@ __global__ void __launch_bounds__(W8 ? 512 : 256, W8 ? 4 : 2) flow_wgrad_split_k
         {
             const float f = da_acc_factor(Ecur - Eacc);          // the running sums into this tile's unit (exact)
 #pragma unroll
-            for (int mt = 0; mt < MTW; ++mt)
+            for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
                 for (int nt = 0; nt < NTT; ++nt) acc[mt][nt] = acc[mt][nt] * f;
             Eacc = Ecur;
@@ -467,7 +463,7 @@ __global__ void __launch_bounds__(W8 ? 512 : 256, W8 ? 4 : 2) flow_wgrad_split_k
                 if (TWO) B[NTT - 1][pl] = *reinterpret_cast<const f16x8*>(xh + pl * XPL + (16 + (i & (S1 - 1))) * CHS + vrow);
             }
 #pragma unroll
-            for (int mt = 0; mt < MTW; ++mt) {
+            for (int mt = 0; mt < MT; ++mt) {
                 const unsigned char* ap = offA[mt] >= 0 ? yh + offA[mt] + rowoff : zrow;
                 const f16x8 Ah = *reinterpret_cast<const f16x8*>(ap);
                 const f16x8 Al = *reinterpret_cast<const f16x8*>(offA[mt] >= 0 ? ap + YPL : zrow);
@@ -493,12 +489,12 @@ __global__ void __launch_bounds__(W8 ? 512 : 256, W8 ? 4 : 2) flow_wgrad_split_k
     __syncthreads();
     float4* red = reinterpret_cast<float4*>(lds8);
     for (int w = 0; w < 4; ++w) {
-        if ((wave & 3) == w) {
+        if (wave == w) {
 #pragma unroll
-            for (int mt = 0; mt < MTW; ++mt)
+            for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
                 for (int nt = 0; nt < NTT; ++nt) {
-                    float4* slot = red + ((mt0 + mt) * NTT + nt) * 64 + lane;
+                    float4* slot = red + (mt * NTT + nt) * 64 + lane;
                     float4 cur = (w == 0) ? make_float4(0.f, 0.f, 0.f, 0.f) : *slot;
                     cur.x += acc[mt][nt][0] * inv1 * inv2; cur.y += acc[mt][nt][1] * inv1 * inv2; cur.z += acc[mt][nt][2] * inv1 * inv2; cur.w += acc[mt][nt][3] * inv1 * inv2;
                     *slot = cur;
@@ -545,20 +541,15 @@ static int flow_launch_t(const FlowWgP& p, int nb, hipStream_t st) {
     return 0;
 }
 
-template <int MTT, bool TWO, int S1, bool W8>
-static int flow_launch_split_t(const FlowWgP& p, int nb, hipStream_t st) {
-    const size_t shm = (size_t)2 * (16 + (TWO ? S1 : 0)) * sp::CHS + (size_t)2 * 3 * 3 * sp::HZ * sp::HY * sp::YROW + 80;
-    auto kern = flow_wgrad_split_kernel<MTT, TWO, S1, W8>;
-    static bool attr_set = false;
-    if (!attr_set) { hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024); if (e != hipSuccess) return (int)e; attr_set = true; }
-    hipLaunchKernelGGL(kern, dim3(nb), dim3(W8 ? 512 : 256), shm, st, p);
-    DA_LAUNCH_CHECK();
-    return 0;
-}
 template <int MTT, bool TWO, int S1>
 static int flow_launch_split(const FlowWgP& p, int nb, hipStream_t st) {
-    static const bool w8 = [] { const char* e = getenv("DA_FLOW_WGRAD_W8"); return e && atoi(e) != 0; }();      // A/B: 1 = eight waves per workgroup (measured slower: 0.29 vs 0.24 ms)
-    return w8 ? flow_launch_split_t<MTT, TWO, S1, true>(p, nb, st) : flow_launch_split_t<MTT, TWO, S1, false>(p, nb, st);
+    const size_t shm = (size_t)2 * (16 + (TWO ? S1 : 0)) * sp::CHS + (size_t)2 * 3 * 3 * sp::HZ * sp::HY * sp::YROW + 80;
+    auto kern = flow_wgrad_split_kernel<MTT, TWO, S1>;
+    static bool attr_set = false;
+    if (!attr_set) { hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024); if (e != hipSuccess) return (int)e; attr_set = true; }
+    hipLaunchKernelGGL(kern, dim3(nb), dim3(256), shm, st, p);
+    DA_LAUNCH_CHECK();
+    return 0;
 }
 
 // split matrix mode, fp32 tensors: the two-term fp16 kernel (its tile is 2 x 8 x 16: the geometry is re-derived); DA_NO_FLOW_WGRAD_SPLIT=1: the exact-fp32 kernel
@@ -575,8 +566,7 @@ static void flow_geom_split(FlowWgP& p, int* nb) {
 template <int MTT, bool TWO, int S1>
 static int flow_launch(const FlowWgP& p0, int& nb, hipStream_t st, int x_bf16) {      // nb: in = the fp32 kernel's workgroups, out = the number of partial rows written
     // (two window tensors -- the registration net's first layer, 1 + 1 -> 16, roles exchanged -- stay on the fp32 kernel: 0.225 ms there, 0.246 here with two loads per element)
-    static const bool two_win = [] { const char* e = getenv("DA_FLOW_WGRAD_SPLIT_2WIN"); return e && atoi(e) != 0; }();
-    if (flow_use_split(x_bf16) && (p0.Cd1 == p0.Cout || two_win)) {
+    if (flow_use_split(x_bf16) && p0.Cd1 == p0.Cout) {
         FlowWgP p = p0;
         flow_geom_split(p, &nb);
         return flow_launch_split<MTT, TWO, S1>(p, nb, st);
@@ -753,11 +743,7 @@ int da_conv3_fewcin_wgrad(const float* in1, int C1, const float* in2, int C2, co
         if (!off) {
             if (Cin == 1 && Cout == 8) return fewcin_valu_launch<1, 2>(in1, C1, in2, dy, dw_tio, N, D, H, W, ws, st);
             if (Cin == 1 && Cout == 16) return fewcin_valu_launch<1, 4>(in1, C1, in2, dy, dw_tio, N, D, H, W, ws, st);
-            // (two input channels: 8 lanes per voxel leave 8 voxels per wave-wide load -- reg 1 + 1 -> 16: 0.22 ms on the matrix form, slower here;
-            //  the instantiations stay for A/B builds)
-            static int two = -1; if (two < 0) { const char* e = getenv("DA_FEWCIN_VALU2"); two = (e && atoi(e)) ? 1 : 0; }
-            if (two && Cin == 2 && Cout == 8) return fewcin_valu_launch<2, 2>(in1, C1, in2, dy, dw_tio, N, D, H, W, ws, st);
-            if (two && Cin == 2 && Cout == 16) return fewcin_valu_launch<2, 4>(in1, C1, in2, dy, dw_tio, N, D, H, W, ws, st);
+            // (two input channels stay on the matrix form: 8 lanes per voxel leave 8 voxels per wave-wide load -- reg 1 + 1 -> 16: 0.22 ms there, slower here)
         }
     }
     FlowWgP p;

@@ -47,10 +47,6 @@ namespace {
 // BF: bf16 matrix mode (da_set_matrix_bf16): tensors stay fp32 in HBM, the staged tile and the packed weights are bf16 and one
 // v_mfma_f32_16x16x16_bf16 (fp32 accumulate) replaces the four v_mfma_f32_16x16x4_f32 of a K-step -- same lane <-> (voxel, cin)
 // mapping, so everything around the K loop is shared.  The kernel is then bound by HBM / LDS instead of the matrix pipe.
-// DYN (experiment, DA_DYN_TILES=1): work-stealing tile walk.  Instead of a static share of its XCD's tile range a workgroup draws the
-// next position from that XCD's counter (one atomic per tile by thread 0, two tiles ahead, handed to the other waves through a
-// 4-entry LDS ring), so a kernel whose workgroups start at different times -- behind another persistent kernel on the other stream
-// -- still finishes together.  Not for the STATS variant: its per-workgroup partial sums would then depend on the draw order.
 // SP: split mode (da_set_matrix_mode(2)) -- fp32 products on the fp16 matrix pipe (da_split2).  Both operands are scaled by a power of two
 // and split into two fp16 terms (activations while they are staged, at the scale of their (tile, channel chunk); weights in the pack kernel,
 // at the scale of their channel chunk) and a K-step of an (M-tile, N-tile) pair is three v_mfma_f32_16x16x32_f16: a.h b.l + a.l b.h + a.h b.h,
@@ -59,9 +55,9 @@ namespace {
 // 2^(E - E_previous) (exact), in the epilogue by 2^-E.  E of a later chunk is capped at 40 above the smallest E the tile has seen, so the
 // rescaled sums cannot overflow (a chunk 2^40 below its neighbours does not reach the fp32 sum anyway).  LDS holds the two planes (CK = 8:
 // 2 x 17 KB); fragments of the next two rows are read while the current two rows' 6 MFMAs issue.
-template <int CK, int NREP, bool MASKED = false, int STATS = 0, bool BF = false, bool PRO = false, bool DYN = false, bool SP = false, int S2F = 0, bool PAIR = false, bool HB = false, int WPE = 2>   // MASKED: sparse tap sets (stride-2 via space-to-depth); STATS: 1 BN partial sums of the output, 2 (data gradient) BatchNorm-BACKWARD sums of the layer that produced the input this gradient belongs to; PRO: input prologue; S2F: 1 virtual space-to-depth input, 2 depth-to-space stores; HB: bf16 activation storage; WPE: waves per SIMD the register allocation must leave room for
-__global__ void __launch_bounds__(256, WPE) conv3_mfma_fwd_kernel(FwdP p) {
-    static_assert(!HB || (BF && !SP && !DYN), "bf16 activation storage: bf16 matrix mode only");
+template <int CK, int NREP, bool MASKED = false, int STATS = 0, bool BF = false, bool PRO = false, bool SP = false, int S2F = 0, bool PAIR = false, bool HB = false>   // MASKED: sparse tap sets (stride-2 via space-to-depth); STATS: 1 BN partial sums of the output, 2 (data gradient) BatchNorm-BACKWARD sums of the layer that produced the input this gradient belongs to; PRO: input prologue; S2F: 1 virtual space-to-depth input, 2 depth-to-space stores; HB: bf16 activation storage
+__global__ void __launch_bounds__(256, 2) conv3_mfma_fwd_kernel(FwdP p) {
+    static_assert(!HB || (BF && !SP), "bf16 activation storage: bf16 matrix mode only");
     static_assert(STATS != 2 || (SP && NREP == 1 && !PRO), "BatchNorm-backward sums: the split mode's one-N-tile data gradient");
     static_assert(S2F == 0 || MASKED, "fused space-to-depth addressing belongs to the tap-masked (stride-2) variants");
     // PAIR (split mode, one N-tile): two consecutive 8-channel chunks share every 64-byte sector of their input.  Staged one work item apart
@@ -69,8 +65,7 @@ __global__ void __launch_bounds__(256, WPE) conv3_mfma_fwd_kernel(FwdP p) {
     // loads of BOTH chunks are issued together during the odd item of a pair; the second chunk's data waits in registers (pre2) through the
     // even item.  The item loop is unrolled by two (lambda instantiated per phase) so that the even phase contains no load instructions.
     static_assert(!PAIR || (SP && NREP == 1 && !PRO), "paired staging: split mode, one N-tile, no input prologue");
-    static_assert(!DYN || (!STATS && !MASKED && !PRO), "dynamic tile walk: plain forward / data-gradient variants only");
-    static_assert(!SP || (BF && !MASKED && !DYN && CK == 8), "split mode: dense bf16 K = 32 kernels on 8-channel chunks");
+    static_assert(!SP || (BF && !MASKED && CK == 8), "split mode: dense bf16 K = 32 kernels on 8-channel chunks");
     constexpr int NP = SP ? 2 : 1;                                  // operand planes
     constexpr bool RAW = HB && BF && !SP && !PRO && !MASKED && S2F == 0;       // bf16 tensors copied straight into the bf16 LDS image (da_buf_loadq)
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -95,33 +90,16 @@ __global__ void __launch_bounds__(256, WPE) conv3_mfma_fwd_kernel(FwdP p) {
     const int nchunks = (p.C1 + p.C2) / CK;
     // persistent: this workgroup walks its share of the brick-ordered tile list; work item = (tile, channel chunk)
     const TileWalk tw = tile_walk(p.ntiles);
-    const int nitems = DYN ? 0x7FFFFFFF : tw.cnt * nchunks;
-    if (!DYN && nitems <= 0) {
+    const int nitems = tw.cnt * nchunks;
+    if (nitems <= 0) {
         if (STATS) for (int c = threadIdx.x; c < NREP * 16; c += 256) { const int co = blockIdx.y * NREP * 16 + c; if (co < p.Cout) { p.stats_partial[((size_t)blockIdx.x * 2) * p.Cout + co] = 0.0; p.stats_partial[((size_t)blockIdx.x * 2 + 1) * p.Cout + co] = 0.0; } }
         return;
     }
-    // DYN: this workgroup's XCD range [xlo, xhi) of the brick order, its counter, and the ring of drawn positions.  (Out-of-range
-    // buffer ATOMICS fault on gfx950, so the draw sits in an exec-mask branch of thread 0.)
-    int xlo = 0, xhi = 0;
-    int* sp = reinterpret_cast<int*>(reinterpret_cast<char*>(lds) + (size_t)StageGeom<CK, HZ>::TOTAL * 4 * EB * NP);
-    int* ctr = nullptr;
-    if constexpr (DYN) {
-        const int G = gridDim.x, X = (G % 8 == 0) ? 8 : 1, xcd = blockIdx.x % X;
-        xlo = (int)((long long)p.ntiles * xcd / X); xhi = (int)((long long)p.ntiles * (xcd + 1) / X);
-        ctr = p.dyn_ctr + blockIdx.y * 8 + xcd;
-        if (threadIdx.x == 0) { sp[0] = xlo + atomicAdd(ctr, 1); sp[1] = xlo + atomicAdd(ctr, 1); }
-        __syncthreads();
-        if (sp[0] >= xhi) return;
-    }
-    auto tile_pos = [&](int k) -> int {
-        if constexpr (DYN) return __builtin_amdgcn_readfirstlane(sp[k & 3]);
-        else return tw.lo + k * tw.J;
-    };
 
     // work item = (k-th tile of this workgroup's walk, channel chunk): the current and the next item's coordinates are kept in SGPRs
     int cK = 0, cCh = 0, cN, cZ, cY, cX, nK, nCh, nN, nZ, nY, nX;
     auto tile_at = [&](int k, int& n, int& z0, int& y0, int& x0) {
-        int pos = tile_pos(k); pos = pos < p.ntiles ? pos : p.ntiles - 1;               // (past the walk: any valid entry; never used)
+        int pos = tw.lo + k * tw.J; pos = pos < p.ntiles ? pos : p.ntiles - 1;               // (past the walk: any valid entry; never used)
         const int4 t = p.tiles[__builtin_amdgcn_readfirstlane(pos)];
         n = t.x; z0 = t.y; y0 = t.z; x0 = t.w;
     };
@@ -343,15 +321,13 @@ __global__ void __launch_bounds__(256, WPE) conv3_mfma_fwd_kernel(FwdP p) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) { const int co = (nt0 + nn) * 16 + 4 * a4 + j; bvv[nn][j] = (p.bias && co < p.Cout) ? p.bias[co] : 0.f; }
 
-    const int prio_rank = (int)((blockIdx.x + gridDim.x * blockIdx.y) / 256u);
     // one work item; PH: 0 = unpaired, 1 = even item of a pair (no staging loads: the next item's tile is in pre2), 2 = odd item (loads both
-    // chunks of the next pair).  Returns false when the walk is over (DYN).
-    auto item_body = [&](int item, auto PHC) -> bool {
+    // chunks of the next pair)
+    auto item_body = [&](int item, auto PHC) {
         constexpr int PH = decltype(PHC)::value;
-        if (p.prio_ranks > 1) da_setprio((prio_rank + item) % p.prio_ranks);
         int n, z0, y0, x0, ch;
         item_coords(0, n, z0, y0, x0, ch);
-        const bool has_next = PH == 1 ? true : DYN ? ((ch + 1 < nchunks) || tile_pos(cK + 1) < xhi) : (item + 1 < nitems);
+        const bool has_next = PH == 1 ? true : (item + 1 < nitems);
         const bool last = (ch == nchunks - 1);
         if constexpr (SP) {          // bring the running sums into this item's unit (exact: a power of two; zero sums on a tile's first chunk)
             if (Ecur != Eacc) {
@@ -364,9 +340,6 @@ __global__ void __launch_bounds__(256, WPE) conv3_mfma_fwd_kernel(FwdP p) {
                 }
                 Eacc = Ecur;
             }
-        }
-        if constexpr (DYN) {       // on a tile's first chunk: draw the position of the tile after next; published below, before the barriers
-            if (threadIdx.x == 0 && ch == 0) sp[(cK + 2) & 3] = xlo + atomicAdd(ctr, 1);
         }
 
         if constexpr (MASKED) {
@@ -450,7 +423,7 @@ __global__ void __launch_bounds__(256, WPE) conv3_mfma_fwd_kernel(FwdP p) {
         constexpr int PLANE_E = StageGeom<CK, HZ>::TOTAL * 4;             // elements per operand plane (SP)
         // SP: rows per block of MFMAs -- a block issues its products plane pair by plane pair over RPB x NREP accumulators, so two MFMAs on the same
         // accumulator are four apart (two apart, one N-tile and row pairs, cost 2 - 5 wait states per MFMA: its latency is two issue slots)
-        constexpr int RPB = (SP && NREP == 1 && WPE == 2 && DA_RPB4) ? 4 : 2;
+        constexpr int RPB = (SP && NREP == 1 && DA_RPB4) ? 4 : 2;
         Frag AC[NP][RPB];                                                   // SP: fragments of the current row block
         if constexpr (SP) {
             const AElem* ap = step_ptr(0);
@@ -668,9 +641,7 @@ __global__ void __launch_bounds__(256, WPE) conv3_mfma_fwd_kernel(FwdP p) {
         }
         if (STATS && last && ((++tiles_done) & 1) == 0) stats_flush();
         if constexpr (PRO && !PRO_IN) load_pro(has_next ? 1 : 0);      // outside the branch: no vector memory in branches
-        if constexpr (DYN) { if (!has_next) return false; }
         if (has_next && !(p.ablate & 4)) {
-            if (p.prio_ranks == -1) __builtin_amdgcn_s_setprio(0);       // DA_PHASE_PRIO: the staging phase yields to the co-resident workgroup's K loop
             if constexpr (SP) {                    // the next tile's largest magnitude (after its prologue), one value per wave
                 if constexpr (PRO && !PRO_IN) stage_pro_apply<0, PRE>(pre, vm, psc, psf, pslope);
                 sp_publish(PH == 1 ? pre2 : pre);
@@ -684,23 +655,20 @@ __global__ void __launch_bounds__(256, WPE) conv3_mfma_fwd_kernel(FwdP p) {
             else stage_write<CK, HZ, 0, PRE, BF, SP, 0, RAW>(lds, pre);     // (PRO_IN: already transformed inside the K loop)
             if constexpr (!PRO) stage_rest(1);
             __syncthreads();
-            if (p.prio_ranks == -1) __builtin_amdgcn_s_setprio(2);
         }
         cK = nK; cCh = nCh; cN = nN; cZ = nZ; cY = nY; cX = nX;
         if constexpr (SP) Ecur = Enext;
         advance();
-        return true;
     };
     if constexpr (PAIR) {
 #pragma unroll 1
         for (int item = 0; item < nitems; item += 2) {
-            if (!item_body(item, IntC<1>{})) break;
-            if (!item_body(item + 1, IntC<2>{})) break;
+            item_body(item, IntC<1>{});
+            item_body(item + 1, IntC<2>{});
         }
     } else {
 #pragma unroll 1
-        for (int item = 0; item < nitems; ++item)
-            if (!item_body(item, IntC<0>{})) break;
+        for (int item = 0; item < nitems; ++item) item_body(item, IntC<0>{});
     }
     if (p.clk && threadIdx.x == 0) {      // DA_CLK: block 17's cycles / wall time, and the span of block lifetimes over the whole grid
         const unsigned long long rt1 = __builtin_amdgcn_s_memrealtime();
@@ -893,10 +861,9 @@ __global__ void __launch_bounds__(256) conv3_thin_kernel(ThinP p) {
 
 // packed B operand: wp[chunk][step][ntile][lane][m]
 __global__ void pack_fwd_weights_kernel(const float* __restrict__ w, float* __restrict__ wp, int Cin, int Cout,
-                                        int CK, int NSTEPS, int NTpad, int flipped, long long total, int bf, int* zero_ctr, int nctr,
+                                        int CK, int NSTEPS, int NTpad, int flipped, long long total, int bf,
                                         int4* __restrict__ tiles, int ntiles, int ntx, int nty, int ntz, int cout0, int CoutW) {
     // (cout0, CoutW: this launch covers output channels [cout0, cout0 + Cout) of a weight tensor with CoutW output channels)
-    if (zero_ctr && blockIdx.x == 0 && (int)threadIdx.x < nctr) zero_ctr[threadIdx.x] = 0;      // DYN tile counters of the launch that follows
     // tile table of the launch that follows: brick-order position -> (sample, z0, y0, x0)
     for (int pos = blockIdx.x * blockDim.x + threadIdx.x; pos < ntiles; pos += gridDim.x * blockDim.x) {
         int n, tx, ty, tz;
@@ -1015,7 +982,6 @@ struct WgP {
     unsigned masks[16]; int maskmode;   // per channel chunk tap masks (0 = all taps)
     const float* ps1; const float* pt1; const float* ps2; const float* pt2; float pslope1, pslope2;   // PRO: see FwdP
     const int4* tiles;                  // split kernel: (n, z0, y0, x0) per brick-order position (wgrad_tiles_kernel)
-    int prio_ranks;                     // see da_setprio
     int ablate;                         // diagnostic only (env DA_WG_ABLATE, split kernel): 1 no staging loads, 2 no fragment reads + MFMAs, 4 no maxima / LDS writes / barriers, 16 no accumulator rescale
     S2dSrc s2in;                        // MASKED: in1 is the original tensor of a stride-2 layer, read as its space-to-depth view (cin > 0)
 };
@@ -1157,10 +1123,8 @@ __global__ void __launch_bounds__(256, 2) conv3_mfma_wgrad_kernel(WgP p) {
     };
     if (tile_begin < tile_end) { issue_loads(tile_begin); write_lds(); }
     __syncthreads();
-    const int prio_rank = (int)((blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z)) / 256u);
 #pragma unroll 1
     for (int tile = tile_begin; tile < tile_end; ++tile) {
-        if (p.prio_ranks > 1) da_setprio((prio_rank + tile) % p.prio_ranks);
         const bool has_next = tile + 1 < tile_end;
         if (has_next) issue_loads(tile + 1);                 // next tile's global loads fly during this tile's MFMAs
         // K loop: 16 rows (vz, vy) x 4 K-steps (4 voxels along x each).  Per row one base address per operand; the four
@@ -1459,10 +1423,8 @@ __global__ void __launch_bounds__(256, 2) conv3_split_wgrad_kernel(WgP p) {
     __syncthreads();
     constexpr int NPR = SPL ? 3 : 1;
     constexpr int PA[3] = {0, SPL ? 1 : 0, 0}, PB[3] = {SPL ? 1 : 0, 0, 0};      // (x, dY) plane pairs, small terms first (one plane: the single product)
-    const int prio_rank = (int)((blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z)) / 256u);
 #pragma unroll 1
     for (int tile = 0; tile < tw.cnt; ++tile) {
-        if (p.prio_ranks > 1) da_setprio((prio_rank + tile) % p.prio_ranks);
         const bool has_next = tile + 1 < tw.cnt;
         if (has_next && !(p.ablate & 1)) issue_loads(tnext);    // next tile's global loads fly during this tile's MFMAs
         tnext = fetch_tile(tile + 2);
@@ -1518,12 +1480,10 @@ __global__ void __launch_bounds__(256, 2) conv3_split_wgrad_kernel(WgP p) {
         }
         }
         if (has_next && !(p.ablate & 4)) {
-            if (p.prio_ranks == -1) __builtin_amdgcn_s_setprio(0);
             publish_max();
             __syncthreads();
             write_lds();
             __syncthreads();
-            if (p.prio_ranks == -1) __builtin_amdgcn_s_setprio(2);
         }
     }
     if constexpr (SPL) {                                        // back to the true unit (two exact factors: |E| may exceed 127)
@@ -2085,7 +2045,7 @@ static int pick_ck(int C1, int C2) {
 // one-item-ahead prefetch hides).
 static int pick_nrep(int NT) { return NT <= 3 ? NT : (NT % 2 == 0 ? 2 : (NT % 3 == 0 ? 3 : 2)); }
 
-static const int kDynCtrInts = 256;          // tile counters [<= 32 cout groups][8 XCDs] behind the packed weights; split mode: the chunks' weight exponents (<= 256 chunks)
+static const int kWexpInts = 256;            // behind the packed weights; split mode: the chunks' weight exponents (<= 256 chunks)
 static size_t packed_bytes(int Cin, int Cout, int CK) {
     const int NT = (Cout + 15) / 16, NREP = pick_nrep(NT);
     const int NTpad = ((NT + NREP - 1) / NREP * NREP + 1) & ~1;      // (even: the bf16 / split modes use <= 2 N-tiles per workgroup)
@@ -2093,7 +2053,7 @@ static size_t packed_bytes(int Cin, int Cout, int CK) {
     size_t b = (size_t)(Cin / CK) * NSTEPS * NTpad * 256 * sizeof(float);
     const size_t sp = (size_t)(Cin / 8) * 7 * NTpad * 2048;           // split mode: 8-channel chunks, 7 K-steps of 32, two 1 KiB planes
     if (Cin % 8 == 0 && sp > b) b = sp;
-    return da_align(b) + da_align(kDynCtrInts * sizeof(int));
+    return da_align(b) + da_align(kWexpInts * sizeof(int));
 }
 
 struct WgPlan { int CK, NREP, ngroups, nchunks, ntz, nty, ntx, ntiles, nslabs, tps; size_t partial_bytes; int w16; };      // w16: 1 conv3_split_wgrad16_kernel (16-channel chunks, one 8-wave workgroup per CU), 2 its ring form conv3_split_wgrad16r_kernel
@@ -2122,10 +2082,6 @@ static WgPlan wgrad_plan(int N, int D, int H, int W, int C1, int C2, int Cout, b
         static int ring = -1; if (ring < 0) { const char* e = getenv("DA_WG16R"); ring = (e && !atoi(e)) ? 0 : 1; }
         if (q.w16 && ring && allow_ring) {
             q.w16 = 2;
-            // DA_WG16R_SLABMUL=k: k times as many (k times shorter) workgroups than CUs can hold at once, so that workgroups of a kernel queued later
-            // on a higher-priority stream get CUs as these retire (experiment: the persistent form holds every CU until its slab is done)
-            static int mul = -1; if (mul < 0) { const char* e = getenv("DA_WG16R_SLABMUL"); mul = e ? atoi(e) : 1; if (mul < 1) mul = 1; }
-            slabs *= mul; if (slabs > cap) slabs = cap;
             if (slabs > q.ntiles) slabs = q.ntiles;
             q.tps = (int)da_cdiv(q.ntiles, slabs);
             q.nslabs = (int)da_cdiv(q.ntiles, q.tps);           // (every slab non-empty)
@@ -2175,17 +2131,17 @@ bool da_conv3_mfma_fwd_supported(int C1, int C2, int Cout, int stride, int Cs1, 
     return true;
 }
 
-template <int CK, int NREP, bool MASKED = false, int STATS = 0, bool BF = false, bool PRO = false, bool DYN = false, bool SP = false, int S2F = 0, bool PAIR = false, bool HB = false, int WPE = 2>
+template <int CK, int NREP, bool MASKED = false, int STATS = 0, bool BF = false, bool PRO = false, bool SP = false, int S2F = 0, bool PAIR = false, bool HB = false>
 static int launch_fwd_mfma(const FwdP& p, int gy, hipStream_t st) {
-    const size_t shm = (size_t)6 * HY * HX * CK * (BF ? 2 : 4) * (SP ? 2 : 1) + (STATS ? (size_t)4 * 2 * NREP * 16 * sizeof(double) : 0) + ((DYN || SP) ? 16 : 0);
-    auto kern = conv3_mfma_fwd_kernel<CK, NREP, MASKED, STATS, BF, PRO, DYN, SP, S2F, PAIR, HB, WPE>;
+    const size_t shm = (size_t)6 * HY * HX * CK * (BF ? 2 : 4) * (SP ? 2 : 1) + (STATS ? (size_t)4 * 2 * NREP * 16 * sizeof(double) : 0) + (SP ? 16 : 0);
+    auto kern = conv3_mfma_fwd_kernel<CK, NREP, MASKED, STATS, BF, PRO, SP, S2F, PAIR, HB>;
     static bool attr_set = false;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
         if (e != hipSuccess) return (int)e;
         attr_set = true;
     }
-    { static int occ = -1; if (occ < 0) { occ = getenv("DA_OCC") ? 1 : 0; if (occ) { int nb = 0; (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, shm); fprintf(stderr, "[occ] <%d,%d,M%d,S%d,BF%d,PRO%d,DYN%d,SP%d> lds %zu B -> %d workgroups per CU\n", CK, NREP, (int)MASKED, (int)STATS, (int)BF, (int)PRO, (int)DYN, (int)SP, shm, nb); } } }
+    { static int occ = -1; if (occ < 0) { occ = getenv("DA_OCC") ? 1 : 0; if (occ) { int nb = 0; (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, shm); fprintf(stderr, "[occ] <%d,%d,M%d,S%d,BF%d,PRO%d,SP%d> lds %zu B -> %d workgroups per CU\n", CK, NREP, (int)MASKED, (int)STATS, (int)BF, (int)PRO, (int)SP, shm, nb); } } }
     static unsigned long long* dclk = nullptr; static int want = -1;
     if (want < 0) { want = getenv("DA_CLK") ? 1 : 0; if (want) (void)hipMalloc(&dclk, 64 + 1024 * 16); }
     FwdP q = p; q.clk = want ? dclk : nullptr;
@@ -2327,25 +2283,23 @@ static int conv3_mfma_fwd_impl(const float* in1, int C1, const float* in2, int C
     float* wp = reinterpret_cast<float*>(opbase);
     int4* tiles = reinterpret_cast<int4*>(opbase + pk);
     const long long total = (long long)(Cin / CK) * NSTEPS * NTpad * 256;
-    int* dyn_ctr = reinterpret_cast<int*>(opbase + pk - da_align(kDynCtrInts * sizeof(int)));
-    static int dyn_env = -1; if (dyn_env < 0) { const char* e = getenv("DA_DYN_TILES"); dyn_env = (e && atoi(e)) ? 1 : 0; }
-    const bool dyn = dyn_env && !bf && !split && !pro && s2d_cin == 0 && !stats_partial && gy * 8 <= kDynCtrInts;
+    int* wexp = reinterpret_cast<int*>(opbase + pk - da_align(kWexpInts * sizeof(int)));
     FwdP p;
     p.bst_y = nullptr; p.bst_par = nullptr; p.bst_slope = -1.f;
     p.ntz = (D + 3) / 4; p.nty = (H + TY - 1) / TY; p.ntx = (W + TX - 1) / TX;
     p.ntiles = N * p.ntz * p.nty * p.ntx;
     if (split) {
-        if (Cin / 8 > kDynCtrInts) return DA_ERR_UNSUPPORTED;
+        if (Cin / 8 > kWexpInts) return DA_ERR_UNSUPPORTED;
         if (pp_mode == 2 && g_pp_collect) {
             if (g_pp_ncollect >= kPackJobsMax) return DA_ERR_WS_SMALL;
-            g_pp_collect->j[g_pp_ncollect++] = PackJob{w_tio, reinterpret_cast<unsigned short*>(wp), dyn_ctr, tiles, Cin, Cout, NTpad, w_is_flipped_tr, p.ntiles, p.ntx, p.nty, p.ntz, cout0, CoutW};
+            g_pp_collect->j[g_pp_ncollect++] = PackJob{w_tio, reinterpret_cast<unsigned short*>(wp), wexp, tiles, Cin, Cout, NTpad, w_is_flipped_tr, p.ntiles, p.ntx, p.nty, p.ntz, cout0, CoutW};
         } else if (pp_mode != 1)
-        hipLaunchKernelGGL(pack_split_weights_kernel, dim3(Cin / 8, 8), dim3(256), 0, st, w_tio, reinterpret_cast<unsigned short*>(wp), dyn_ctr, Cin, Cout, NTpad, w_is_flipped_tr,
+        hipLaunchKernelGGL(pack_split_weights_kernel, dim3(Cin / 8, 8), dim3(256), 0, st, w_tio, reinterpret_cast<unsigned short*>(wp), wexp, Cin, Cout, NTpad, w_is_flipped_tr,
                            tiles, p.ntiles, p.ntx, p.nty, p.ntz, cout0, CoutW);
         if (pp_mode == 2) { DA_LAUNCH_CHECK(); g_pp.used++; return 0; }
     } else
     hipLaunchKernelGGL(pack_fwd_weights_kernel, dim3(da_grid(total > p.ntiles ? total : p.ntiles, 256, 1024)), dim3(256), 0, st, w_tio, wp, Cin, Cout, CK, NSTEPS, NTpad, w_is_flipped_tr, total, pkmode,
-                       dyn ? dyn_ctr : nullptr, gy * 8, tiles, p.ntiles, p.ntx, p.nty, p.ntz, cout0, CoutW);
+                       tiles, p.ntiles, p.ntx, p.nty, p.ntz, cout0, CoutW);
     DA_LAUNCH_CHECK();
     p.tiles = tiles;
     p.in1 = in1; p.in2 = in2; p.C1 = C1; p.C2 = C2; p.wp = wp; p.bias = bias;
@@ -2364,14 +2318,10 @@ static int conv3_mfma_fwd_impl(const float* in1, int C1, const float* in2, int C
         // (a third workgroup per CU for the split kernels -- 168 VGPRs, 3 x 52 KB of LDS -- was measured and dropped: in split mode the
         // matrix pipe is already busy ~100 % of the shader cycles and the clock is set by the power limit)
         static int nres = -1; if (nres < 0) { const char* e = getenv("DA_FWD_BLOCKS"); nres = e ? atoi(e) : 512; }
-        static int wg3 = -1; if (wg3 < 0) { const char* e = getenv("DA_FWD_WG3"); wg3 = (e && atoi(e)) ? 1 : 0; }
-        int nblk = ((wg3 && split && NREP == 1) ? 768 : nres) / gy; if (nblk < 1) nblk = 1; if (nblk > p.ntiles) nblk = p.ntiles;
+        int nblk = nres / gy; if (nblk < 1) nblk = 1; if (nblk > p.ntiles) nblk = p.ntiles;
         if (nblk >= 8) nblk &= ~7;                           // multiple of 8: blockIdx.x % 8 is then the XCD (tile_walk)
         p.nblocks = nblk;
     }
-    { static int norot = -1; if (norot < 0) { const char* e = getenv("DA_PRIO_ROT"); norot = (e && atoi(e)) ? 0 : 1; }
-      const int resident = (p.nblocks * gy + 255) / 256; p.prio_ranks = (norot || resident < 2) ? 0 : (resident > 4 ? 4 : resident);
-      static int phase = -1; if (phase < 0) { const char* e = getenv("DA_PHASE_PRIO"); phase = (e && atoi(e)) ? 1 : 0; } if (phase) p.prio_ranks = -1; }
     p.s2in = S2dSrc{0, 0, 0, 0}; p.s2out = S2dSrc{0, 0, 0, 0};
     if (s2f && s2d_cin > 0) {
         if (s2f->fuse_in && !w_is_flipped_tr) p.s2in = S2dSrc{s2d_cin, s2f->D0, s2f->H0, s2f->W0};
@@ -2380,7 +2330,7 @@ static int conv3_mfma_fwd_impl(const float* in1, int C1, const float* in2, int C
     p.stats_partial = stats_partial;
     if (stats_nparts) *stats_nparts = 0;
     p.ps1 = p.pt1 = p.ps2 = p.pt2 = nullptr; p.pslope1 = p.pslope2 = -1.f;
-    p.dyn_ctr = dyn_ctr; p.wexp = dyn_ctr;
+    p.wexp = wexp;
     if (pro) {
         const float *ones, *zeros;
         if (const int rc = pro_identity(&ones, &zeros)) return rc;
@@ -2392,60 +2342,42 @@ static int conv3_mfma_fwd_impl(const float* in1, int C1, const float* in2, int C
         if (stats_partial && stats_nparts) *stats_nparts = p.nblocks;
         // paired staging (one sector fetch per two chunks): one N-tile, an even number of 8-channel chunks that pair up inside in1 / in2
         static int nopair = -1; if (nopair < 0) { const char* e = getenv("DA_NO_PAIR"); nopair = (e && atoi(e)) ? 1 : 0; }
-        static int wg3s = -1; if (wg3s < 0) { const char* e = getenv("DA_FWD_WG3"); wg3s = (e && atoi(e)) ? 1 : 0; }
-        if (wg3s && NREP == 1 && !da_conv3_fwdsp_enabled())      // experiment: three workgroups per CU (<= 168 VGPRs), no paired staging
-            return stats_partial ? (pro ? launch_fwd_mfma<8, 1, false, true, true, true, false, true, 0, false, false, 3>(p, gy, st) : launch_fwd_mfma<8, 1, false, true, true, false, false, true, 0, false, false, 3>(p, gy, st))
-                                 : (pro ? launch_fwd_mfma<8, 1, false, false, true, true, false, true, 0, false, false, 3>(p, gy, st) : launch_fwd_mfma<8, 1, false, false, true, false, false, true, 0, false, false, 3>(p, gy, st));
-        p.bst_y = nullptr; p.bst_par = nullptr; p.bst_slope = -1.f;
-        if (da_conv3_fwdsp_enabled()) {     // weights in LDS, staging loads a whole item ahead (conv3d_fwdsp.hip); DA_FWDSP=0: the kernels below
-            const bool pair = !nopair && NREP == 1 && !pro && !want_bst && C1 % 16 == 0 && C2 % 16 == 0;
-            if (want_bst) {
-                if (!(NREP == 1 && !pro && Cs2 == 0 && gy <= 2)) return DA_ERR_UNSUPPORTED;
-                p.bst_y = g_bst.y; p.bst_par = g_bst.par; p.bst_slope = g_bst.slope;
-            }
-            return da_conv3_fwdsp_launch(p, gy, NREP, want_bst ? 2 : (stats_partial ? 1 : 0), pro ? 1 : 0, pair ? 1 : 0, st);
-        }
         if (want_bst) {                                      // (da_conv3d_k3_dgrad_bst checked the shape: one output tensor of <= 32 channels, no prologue)
             if (!(NREP == 1 && !pro && Cs2 == 0 && gy <= 2)) return DA_ERR_UNSUPPORTED;
             p.bst_y = g_bst.y; p.bst_par = g_bst.par; p.bst_slope = g_bst.slope;
-            return launch_fwd_mfma<8, 1, false, 2, true, false, false, true>(p, gy, st);      // (unpaired staging: with the pair's second parked chunk the eight y quads of the epilogue spill)
+            return launch_fwd_mfma<8, 1, false, 2, true, false, true>(p, gy, st);      // (unpaired staging: with the pair's second parked chunk the eight y quads of the epilogue spill)
         }
         if (!nopair && NREP == 1 && !pro && C1 % 16 == 0 && C2 % 16 == 0)
-            return stats_partial ? launch_fwd_mfma<8, 1, false, true, true, false, false, true, 0, true>(p, gy, st)
-                                 : launch_fwd_mfma<8, 1, false, false, true, false, false, true, 0, true>(p, gy, st);
-#define DA_SP_CASE(nr) if (NREP == nr) return stats_partial ? (pro ? launch_fwd_mfma<8, nr, false, true, true, true, false, true>(p, gy, st) : launch_fwd_mfma<8, nr, false, true, true, false, false, true>(p, gy, st)) \
-                                                              : (pro ? launch_fwd_mfma<8, nr, false, false, true, true, false, true>(p, gy, st) : launch_fwd_mfma<8, nr, false, false, true, false, false, true>(p, gy, st))
+            return stats_partial ? launch_fwd_mfma<8, 1, false, true, true, false, true, 0, true>(p, gy, st)
+                                 : launch_fwd_mfma<8, 1, false, false, true, false, true, 0, true>(p, gy, st);
+#define DA_SP_CASE(nr) if (NREP == nr) return stats_partial ? (pro ? launch_fwd_mfma<8, nr, false, true, true, true, true>(p, gy, st) : launch_fwd_mfma<8, nr, false, true, true, false, true>(p, gy, st)) \
+                                                              : (pro ? launch_fwd_mfma<8, nr, false, false, true, true, true>(p, gy, st) : launch_fwd_mfma<8, nr, false, false, true, false, true>(p, gy, st))
         DA_SP_CASE(1); DA_SP_CASE(2);
 #undef DA_SP_CASE
         return DA_ERR_UNSUPPORTED;
     }
     if (stats_partial && p.maskmode == 0 && (CK == 16 || CK == 8) && NREP <= 2) {
         if (stats_nparts) *stats_nparts = p.nblocks;
-#define DA_ST_CASE(ck, nr) if (CK == ck && NREP == nr) return pro ? (hb ? launch_fwd_mfma<ck, nr, false, true, true, true, false, false, 0, false, true>(p, gy, st) : bf ? launch_fwd_mfma<ck, nr, false, true, true, true>(p, gy, st) : launch_fwd_mfma<ck, nr, false, true, false, true>(p, gy, st)) \
-                                                                  : (hb ? launch_fwd_mfma<ck, nr, false, true, true, false, false, false, 0, false, true>(p, gy, st) : bf ? launch_fwd_mfma<ck, nr, false, true, true>(p, gy, st) : launch_fwd_mfma<ck, nr, false, true>(p, gy, st))
+#define DA_ST_CASE(ck, nr) if (CK == ck && NREP == nr) return pro ? (hb ? launch_fwd_mfma<ck, nr, false, true, true, true, false, 0, false, true>(p, gy, st) : bf ? launch_fwd_mfma<ck, nr, false, true, true, true>(p, gy, st) : launch_fwd_mfma<ck, nr, false, true, false, true>(p, gy, st)) \
+                                                                  : (hb ? launch_fwd_mfma<ck, nr, false, true, true, false, false, 0, false, true>(p, gy, st) : bf ? launch_fwd_mfma<ck, nr, false, true, true>(p, gy, st) : launch_fwd_mfma<ck, nr, false, true>(p, gy, st))
         DA_ST_CASE(16, 1); DA_ST_CASE(16, 2); DA_ST_CASE(8, 1); DA_ST_CASE(8, 2);
 #undef DA_ST_CASE
     }
     if (pro) {
-#define DA_PRO_CASE(ck, nr) if (CK == ck && NREP == nr) return hb ? launch_fwd_mfma<ck, nr, false, false, true, true, false, false, 0, false, true>(p, gy, st) : bf ? launch_fwd_mfma<ck, nr, false, false, true, true>(p, gy, st) : launch_fwd_mfma<ck, nr, false, false, false, true>(p, gy, st)
+#define DA_PRO_CASE(ck, nr) if (CK == ck && NREP == nr) return hb ? launch_fwd_mfma<ck, nr, false, false, true, true, false, 0, false, true>(p, gy, st) : bf ? launch_fwd_mfma<ck, nr, false, false, true, true>(p, gy, st) : launch_fwd_mfma<ck, nr, false, false, false, true>(p, gy, st)
         DA_PRO_CASE(16, 1); DA_PRO_CASE(16, 2); DA_PRO_CASE(8, 1); DA_PRO_CASE(8, 2);
 #undef DA_PRO_CASE
         return DA_ERR_UNSUPPORTED;
     }
     if (p.maskmode != 0) {
         const int s2f = p.s2in.cin > 0 ? 1 : (p.s2out.cin > 0 ? 2 : 0);
-#define DA_M_CASE(nr, f) if (NREP == nr && s2f == f) return hb ? launch_fwd_mfma<16, nr, true, false, true, false, false, false, f, false, true>(p, gy, st) : bf ? launch_fwd_mfma<16, nr, true, false, true, false, false, false, f>(p, gy, st) : launch_fwd_mfma<16, nr, true, false, false, false, false, false, f>(p, gy, st)
+#define DA_M_CASE(nr, f) if (NREP == nr && s2f == f) return hb ? launch_fwd_mfma<16, nr, true, false, true, false, false, f, false, true>(p, gy, st) : bf ? launch_fwd_mfma<16, nr, true, false, true, false, false, f>(p, gy, st) : launch_fwd_mfma<16, nr, true, false, false, false, false, f>(p, gy, st)
         DA_M_CASE(1, 0); DA_M_CASE(1, 1); DA_M_CASE(1, 2); DA_M_CASE(2, 0); DA_M_CASE(2, 1); DA_M_CASE(2, 2);
 #undef DA_M_CASE
         return DA_ERR_UNSUPPORTED;
     }
-    if (dyn) {       // experiment (DA_DYN_TILES=1): work-stealing tile walk for the plain fp32 forward / data-gradient kernels
-#define DA_DYN_CASE(ck, nr) if (CK == ck && NREP == nr) return launch_fwd_mfma<ck, nr, false, false, false, false, true>(p, gy, st)
-        DA_DYN_CASE(16, 1); DA_DYN_CASE(16, 2); DA_DYN_CASE(16, 3); DA_DYN_CASE(8, 1); DA_DYN_CASE(8, 2);
-#undef DA_DYN_CASE
-    }
 #define DA_FWD_CASE(ck, nr) if (CK == ck && NREP == nr) return bf ? launch_fwd_mfma<ck, nr, false, false, true>(p, gy, st) : launch_fwd_mfma<ck, nr>(p, gy, st)
-#define DA_FWD_CASE_HB(ck, nr) if (hb && CK == ck && NREP == nr) return launch_fwd_mfma<ck, nr, false, false, true, false, false, false, 0, false, true>(p, gy, st)
+#define DA_FWD_CASE_HB(ck, nr) if (hb && CK == ck && NREP == nr) return launch_fwd_mfma<ck, nr, false, false, true, false, false, 0, false, true>(p, gy, st)
     DA_FWD_CASE_HB(16, 1); DA_FWD_CASE_HB(16, 2); DA_FWD_CASE_HB(8, 1); DA_FWD_CASE_HB(8, 2);      // (bf16 mode: at most two N-tiles)
 #undef DA_FWD_CASE_HB
     DA_FWD_CASE(16, 1); DA_FWD_CASE(16, 2); DA_FWD_CASE(16, 3);          // pick_nrep never asks for more than 3 N-tiles
@@ -2482,7 +2414,6 @@ bool da_conv3_thin_supported(int C1, int C2, int Cout, int stride) {
     return false;
 }
 
-static thread_local int g_thin_pack = 1, g_thin_only = 0;      // kept packed weights (da_pp_lookup in da_conv3_thin_fwd): pack at all / stop after the pack
 static const size_t kThinPackBytes = 65536;        // padded weights [27][CinP][CT]: <= 27.6 KB (Cin <= 64, CT = 4) / 13.8 KB (Cin <= 4, CT <= 32)
 
 template <int CL, int CT, int VPT, int JR = CT, int CR = CL>
@@ -2490,8 +2421,7 @@ static int thin_launch(ThinP& p, const float* w_src, float* wq, hipStream_t st, 
     const int Cin = p.C1 + p.C2;
     const int CinP = (Cin + CL - 1) / CL * CL;
     if ((size_t)27 * CinP * CT * sizeof(float) > kThinPackBytes / 2) return DA_ERR_UNSUPPORTED;
-    if (g_thin_pack) hipLaunchKernelGGL(thin_pack_kernel, dim3(da_grid(27 * CinP * CT, 256, 64)), dim3(256), 0, st, w_src, wq, Cin, CinP, p.Cout, CT, p.flip_tr, j0, Cw < 0 ? p.Cout : Cw);
-    if (g_thin_only) return 0;
+    hipLaunchKernelGGL(thin_pack_kernel, dim3(da_grid(27 * CinP * CT, 256, 64)), dim3(256), 0, st, w_src, wq, Cin, CinP, p.Cout, CT, p.flip_tr, j0, Cw < 0 ? p.Cout : Cw);
     p.w = wq;
     const size_t ldsb = ((size_t)(2 * VPT + 2) * HY * HX * CL + (CT <= 16 ? 0 : (size_t)27 * CinP * CT)) * sizeof(float);
     p.ntz = (p.D + 2 * VPT - 1) / (2 * VPT);
@@ -2526,13 +2456,7 @@ int da_conv3_thin_fwd(const float* in1, int C1, const float* in2, int C2, const 
                       void* ws, size_t ws_bytes, hipStream_t st, int in_bf16, int out_bf16) {
     if ((unsigned long long)D * H * W * (C1 > C2 ? C1 : C2) * 4ull >= 0xFFFFFFF0ull) return DA_ERR_UNSUPPORTED;
     if (!ws || ws_bytes < kThinPackBytes) return DA_ERR_WS_SMALL;
-    const int Cin_ = C1 + C2;
-    if (!(Cout <= 4 || Cin_ == 1 || (Cin_ <= 4 && C2 > 0) || (Cin_ <= 4 && C2 == 0))) return DA_ERR_UNSUPPORTED;      // (the cases below; decided before the kept-pack lookup)
-    // the padded weights: in the workspace, or in the caller's kept buffer (conv3d_internal.h: da_pp_lookup; fp32 tensors only -- the bf16 twins pack per call)
-    const DaKeptPack kp = (in_bf16 || out_bf16) ? DaKeptPack{nullptr, 0, 0} : da_pp_lookup(w, kThinPackBytes, flip_tr ? DA_PP_THIN_FLIP : DA_PP_THIN);
-    if (kp.only && !kp.buf) return 0;
-    float* wq = kp.buf ? (float*)kp.buf : (float*)ws;
-    struct ThinFlags { ThinFlags(int pack, int only) { g_thin_pack = pack; g_thin_only = only; } ~ThinFlags() { g_thin_pack = 1; g_thin_only = 0; } } thin_flags((!kp.buf || kp.fill) ? 1 : 0, kp.only);
+    float* wq = (float*)ws;
     ThinP p;
     p.in1 = in1; p.in2 = in2; p.C1 = C1; p.C2 = C2; p.w = w; p.bias = bias; p.out1 = out1; p.out2 = out2; p.Cs1 = Cs1; p.Cs2 = Cs2;
     p.N = N; p.D = D; p.H = H; p.W = W; p.Cout = Cout; p.flip_tr = flip_tr; p.slope = slope;
@@ -2724,9 +2648,6 @@ int da_conv3_mfma_wgrad(const float* in1, int C1, const float* in2, int C2, cons
     WgP p;
     p.tiles = nullptr;
     p.s2in = (s2f && s2d_cin > 0 && s2f->fuse_in) ? S2dSrc{s2d_cin, s2f->D0, s2f->H0, s2f->W0} : S2dSrc{0, 0, 0, 0};
-    { static int norot = -1; if (norot < 0) { const char* e = getenv("DA_PRIO_ROT"); norot = (e && atoi(e)) ? 0 : 1; }
-      const int resident = (q.nslabs * q.nchunks * q.ngroups + 255) / 256; p.prio_ranks = (norot || resident < 2) ? 0 : (resident > 4 ? 4 : resident);
-      static int phase = -1; if (phase < 0) { const char* e = getenv("DA_PHASE_PRIO"); phase = (e && atoi(e)) ? 1 : 0; } if (phase) p.prio_ranks = -1; }
     { static int abl = -1; if (abl < 0) { const char* e = getenv("DA_WG_ABLATE"); abl = e ? atoi(e) : 0; } p.ablate = abl; }
     if (split || rows1) {
         int4* tiles = reinterpret_cast<int4*>(reinterpret_cast<char*>(ws) + q.partial_bytes);

@@ -1,6 +1,5 @@
-// Staging helpers, tile walk and the launch parameter block shared by the stride-1 3x3x3 implicit-GEMM kernels (conv3d_mfma.hip: every matrix
-// mode; conv3d_fwdsp.hip: the split mode's forward / data-gradient kernel with the weights in LDS).  Everything device-side lives in an anonymous
-// namespace (one copy per translation unit); the two plain structs that cross translation units have external names.
+// Staging helpers, tile walk and the launch parameter block of the stride-1 3x3x3 implicit-GEMM kernels (conv3d_mfma.hip, every matrix mode).
+// Everything device-side lives in an anonymous namespace.
 #pragma once
 #include "common.h"
 #include "split_f16.h"
@@ -20,10 +19,8 @@ struct DaC3FwdP {
     double* stats_partial;              // optional [gridDim.x][2][Cout]: per-workgroup sum / sum of squares of the (pre-activation) output
     unsigned long long* clk;
     const float* ps1; const float* pt1; const float* ps2; const float* pt2; float pslope1, pslope2;   // PRO: per-channel scale / shift / act slope still to be applied to in1 / in2
-    int* dyn_ctr;    // DYN: tile counters [gridDim.y][8 XCDs], zeroed by the pack kernel of the same call
     const int4* tiles;   // (n, z0, y0, x0) of every tile in brick order, written by the pack kernel of the same call: the persistent loop
                          // reads one entry per item through the scalar cache instead of decomposing the position (~10 integer divisions)
-    int prio_ranks;  // co-resident workgroups per CU taking turns at the top wave priority (0: off)
     DaC3S2dSrc s2in;     // MASKED forward: in1 is the ORIGINAL tensor of a stride-2 layer, read as its space-to-depth view (cin > 0)
     const int* wexp; // SP: power-of-two exponent of every channel chunk of the packed weights (pack_split_weights_kernel)
     DaC3S2dSrc s2out;    // MASKED data gradient: the 8 * cin output channels are scattered to the original-resolution gradient (cin > 0)
@@ -32,10 +29,6 @@ struct DaC3FwdP {
     // bst_par = its statistics rows [mean | rstd | scale | shift][Cs1]; stats_partial then receives (sum dz, sum dz (y - mean)), dz = dx act'(y scale + shift)
     const float* bst_y; const float* bst_par; float bst_slope;
 };
-// conv3d_fwdsp.hip: split mode, fp32 tensors, 8-channel chunks.  nrep: N-tiles per workgroup (1 | 2); stats: 0 none, 1 BatchNorm sums of the output,
-// 2 BatchNorm-backward sums (data gradient); pro: input prologue; pair: paired staging of chunk pairs (nrep 1, no prologue, stats != 2)
-bool da_conv3_fwdsp_enabled();
-int da_conv3_fwdsp_launch(const DaC3FwdP& p, int gy, int nrep, int stats, int pro, int pair, hipStream_t st);
 
 namespace {
 
@@ -319,18 +312,6 @@ template <bool HB> __device__ __forceinline__ void da_buf_storeq(__amdgpu_buffer
 }
 template <bool B> struct BoolC { static constexpr bool value = B; };
 template <int V> struct IntC { static constexpr int value = V; };
-// Wave priority rotation (experiment, DA_PRIO_ROT=1; off by default).  The persistent kernels keep 2 - 3 workgroups per CU alive for the
-// whole launch, and the CU arbitrates instruction issue between their waves by priority, then by AGE: with equal priorities the
-// first-dispatched workgroup of a CU runs ~20 % faster than the last one for the whole kernel (DA_CLK=1 DA_CLK_DUMP=1: lifetimes 1.39 /
-// 1.67 / 1.91 ms on every CU for equal work, split-mode 48 -> 16 forward).  Rotating s_setprio over the co-resident workgroups once per work
-// item (rank = dispatch round, 256 workgroups per round) halves the spread of the finish times (508 -> 253 us) and changes the kernel time
-// by nothing (2.27 -> 2.28 ms): the kernel is power-bound, the early finishers' CUs were not wasted -- the survivors ran at a higher clock.
-__device__ __forceinline__ void da_setprio(int p) {
-    if (p == 0) __builtin_amdgcn_s_setprio(0);
-    else if (p == 1) __builtin_amdgcn_s_setprio(1);
-    else if (p == 2) __builtin_amdgcn_s_setprio(2);
-    else __builtin_amdgcn_s_setprio(3);
-}
 // lane ^ 1 / lane ^ 2 exchanges inside a lane quad as DPP quad_perm moves (VALU, no trip through the LDS crossbar like __shfl_xor)
 __device__ __forceinline__ float da_quad_xor1(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true)); }   // quad_perm [1,0,3,2]
 __device__ __forceinline__ float da_quad_xor2(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true)); }   // quad_perm [2,3,0,1]

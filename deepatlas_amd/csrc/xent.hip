@@ -249,7 +249,7 @@ __global__ void __launch_bounds__(256) xent_bwd_quad_kernel(const float* __restr
 }
 
 static int xe_lanes(int C, const float* a, const float* b, const float* c) {      // lanes per voxel of the quad kernels, 0: thread-per-voxel form
-    if (C % 4 != 0 || getenv("DA_XENT_V1")) return 0;
+    if (C % 4 != 0) return 0;
     const int L = C / 4;
     if (L != 1 && L != 2 && L != 4 && L != 8 && L != 16) return 0;
     if (((size_t)a | (size_t)b | (size_t)c) & 15) return 0;

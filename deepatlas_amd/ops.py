@@ -268,23 +268,16 @@ def enable_async_wgrad(flag=True):
 
 LAST_WGRAD_ON_MAIN = os.environ.get('DA_LAST_WGRAD_ON_MAIN', '1') == '1'      # see Conv3dFn.backward
 LAST_WGRAD_ON_MAIN_BN = os.environ.get('DA_LAST_WGRAD_ON_MAIN_BN', '0') == '1'
-_N_SIDE = max(1, int(os.environ.get('DA_SIDE_STREAMS', '1')))      # > 1: weight gradients alternate between that many side streams (experiment)
 _SIDE_PRIO = int(os.environ.get('DA_SIDE_PRIO', '0'))      # HIP stream priority of the side stream (lower number = higher priority; out-of-range values clamp)
-_side_streams = []
-_side_rr = 0
 
 
 def side_stream():
-    """The second HIP stream (round-robin over DA_SIDE_STREAMS of them); every caller is about to queue work on it."""
-    global _side_stream, _side_dirty, _side_rr
+    """The second HIP stream; every caller is about to queue work on it."""
+    global _side_stream, _side_dirty
     if _side_stream is None:
         _side_stream = torch.cuda.Stream(priority=_SIDE_PRIO)
-        _side_streams.append(_side_stream)
-        for _ in range(_N_SIDE - 1):
-            _side_streams.append(torch.cuda.Stream(priority=_SIDE_PRIO))
     _side_dirty = True
-    _side_rr = (_side_rr + 1) % len(_side_streams)
-    return _side_streams[_side_rr]
+    return _side_stream
 
 
 _side_dirty = False      # work has been queued on the side stream since the last join
@@ -295,8 +288,7 @@ def join_side_stream():
     dependency at all (inside a HIP-graph capture a wait on work from before the capture would be illegal)."""
     global _side_dirty
     if _side_stream is not None and (_side_dirty or _side_keep):
-        for s_ in _side_streams:
-            torch.cuda.current_stream().wait_stream(s_)
+        torch.cuda.current_stream().wait_stream(_side_stream)
     _side_keep.clear()
     _side_dirty = False
 
@@ -316,8 +308,7 @@ def _serialize_matrix_kernels(flops, voxels):
     tails and waiting costs 10 % (268 vs 300 ms per step), and equally long kernels are left to overlap too."""
     if (ASYNC_WGRAD and _side_stream is not None and _side_dirty and flops >= _SERIALIZE_MIN_FLOPS and voxels >= _SERIALIZE_MIN_VOXELS
             and _last_side_flops <= _SERIALIZE_MAX_RATIO * flops):
-        for s_ in _side_streams:
-            torch.cuda.current_stream().wait_stream(s_)
+        torch.cuda.current_stream().wait_stream(_side_stream)
 
 
 _SERIALIZE_MIN_FLOPS = float(os.environ.get('DA_MFMA_SERIALIZE_MIN_FLOPS', '3e11'))      # 'inf' disables the rule
@@ -417,7 +408,7 @@ _pack_entries = {}
 
 
 class _Pack(object):
-    __slots__ = ('bufs', 'stamp', 'event', 'base', 'view', 'args', 'disabled', 'storage', 'pversion', 'used', 'any', 'tag')
+    __slots__ = ('bufs', 'stamp', 'event', 'base', 'view', 'args', 'disabled', 'storage', 'pversion', 'used')
 
 
 def _pack_stamp(e):
@@ -428,23 +419,8 @@ def _pack_stamp(e):
     return (_other_bumps, _bucket_epoch.get(e.storage, 0), e.pversion, b._version if b is not None else -1)
 
 
-def _pack_any(w_tio, C1, C2, Cout, dgrad, stride, up2, N, D, H, W, buf, st):
-    """da_conv3d_k3_prepack_any: (bytes such a pack needs, tag, filled).  buf None: size query."""
-    import ctypes
-    need, tag, filled = ctypes.c_size_t(0), ctypes.c_int(0), ctypes.c_int(0)
-    wsb = nat.lib().da_upconv3d_k3_ws_bytes(N, D, H, W, C1 + C2, Cout) if up2 else nat.lib().da_conv3d_k3_ws_bytes(N, D, H, W, C1 + C2, Cout, stride)
-    wp, wn = _ws(wsb, w_tio)
-    call('da_conv3d_k3_prepack_any', ptr(w_tio), C1, C2, Cout, dgrad, stride, 1 if up2 else 0, N, D, H, W, ptr(buf), buf.numel() if buf is not None else 0,
-         ctypes.byref(need), ctypes.byref(tag), ctypes.byref(filled), wp, wn, st)
-    return need.value, tag.value, filled.value
-
-
 def _pack_fill(e, w_tio, st):
     import ctypes
-    if e.any is not None:                                # the families outside the split matrix kernels: one region, filled by the family's own pack kernel
-        C1, C2, Cout, dgrad, N, D, H, W = e.args
-        stride, up2 = e.any
-        return _pack_any(w_tio, C1, C2, Cout, dgrad, stride, up2, N, D, H, W, e.bufs[0], st)[2]
     C1, C2, Cout, dgrad, N, D, H, W = e.args
     used = ctypes.c_int(0)
     b1 = e.bufs[1]
@@ -453,21 +429,13 @@ def _pack_fill(e, w_tio, st):
     return used.value
 
 
-# Kept packs ALSO for the folded up-sampling / native stride-2 / flow / thin kernels (da_conv3d_k3_prepack_any).  OFF by default: measured on the registration step
-# (22 such packs of 5 - 20 us) it is 0.07 - 0.09 ms SLOWER than packing per call (4.25 vs 4.33 ms; backward packs only: 4.32) -- a kept pack costs the host a dictionary
-# lookup, a stamp, an event wait and a hand-over call per layer plus a re-fill call per layer behind the optimiser step, more than the 3-us launch it removes, and the
-# reg step's forward runs 10 - 20 us kernels that leave the host no slack.  DA_PACK_CACHE_ANY=1 switches it on (tests/test_gpu_nets.py exercises it).
-_PACK_ANY_BWD_ONLY = os.environ.get('DA_PACK_CACHE_ANY_BWD_ONLY') == '1'
-PACK_CACHE_ANY = os.environ.get('DA_PACK_CACHE_ANY') == '1'
-
-
 def use_pack(w_tio, dgrad, C1, C2, Cout, N, D, H, W, stride=1, up2=False):
-    """Right before a da_conv3d_k3_{fwd,fwd_bnstats,fwd_pro,dgrad} or da_upconv3d_k3_{fwd,dgrad} call (up2: D, H, W = the coarse extents): hand it the kept
-    packed operand of these weights (filling it now if it is new or stale).  No-op outside the split matrix mode, for weights that are not views of a live base
-    tensor, and inside graph capture."""
-    if not PACK_CACHE or _matrix_mode != 'fp32_split' or w_tio.dtype != torch.float32 or torch.cuda.is_current_stream_capturing():
+    """Right before a da_conv3d_k3_{fwd,fwd_bnstats,fwd_pro,dgrad} or da_upconv3d_k3_{fwd,dgrad} call: hand it the kept packed operand of these weights
+    (filling it now if it is new or stale).  Only stride-1 layers keep packs (the split matrix kernels); no-op for stride 2 and the folded up-sampling, outside
+    the split matrix mode, for weights that are not views of a live base tensor, and inside graph capture."""
+    if stride != 1 or up2 or not PACK_CACHE or _matrix_mode != 'fp32_split' or w_tio.dtype != torch.float32 or torch.cuda.is_current_stream_capturing():
         return
-    key = (w_tio.data_ptr(), dgrad, C1, C2, Cout, N, D, H, W, stride, bool(up2))
+    key = (w_tio.data_ptr(), dgrad, C1, C2, Cout, N, D, H, W)
     e = _pack_entries.get(key)
     sp = w_tio.untyped_storage().data_ptr()
     if e is not None and (e.base() is None or e.storage != sp):
@@ -477,13 +445,8 @@ def use_pack(w_tio, dgrad, C1, C2, Cout, N, D, H, W, stride=1, up2=False):
         base = next((r for r in _flat_param_buckets if r() is not None and r().untyped_storage().data_ptr() == sp), None)
         if base is None:
             return
-        nbytes = nat.lib().da_conv3d_k3_pack_bytes(N, D, H, W, C1 + C2, Cout) if (stride == 1 and not up2) else 0
+        nbytes = nat.lib().da_conv3d_k3_pack_bytes(N, D, H, W, C1 + C2, Cout)
         e = _Pack()
-        e.any, e.tag = None, 0
-        if nbytes == 0 and PACK_CACHE_ANY and (dgrad or not _PACK_ANY_BWD_ONLY):                # not a split matrix-kernel layer: one of the other families may keep its pack
-            nbytes, e.tag, _ = _pack_any(w_tio, C1, C2, Cout, dgrad, stride, up2, N, D, H, W, None, stream())
-            if nbytes:
-                e.any = (stride, bool(up2))
         e.args, e.event, e.stamp, e.disabled, e.used = (C1, C2, Cout, dgrad, N, D, H, W), None, None, nbytes == 0, True
         e.base = base
         e.storage = sp
@@ -491,7 +454,7 @@ def use_pack(w_tio, dgrad, C1, C2, Cout, N, D, H, W, stride=1, up2=False):
         e.bufs = [None, None]
         if not e.disabled:
             e.bufs[0] = torch.empty((nbytes,), dtype=torch.uint8, device=w_tio.device)
-            if dgrad and C2 > 0 and e.any is None:
+            if dgrad and C2 > 0:
                 e.bufs[1] = torch.empty((nbytes,), dtype=torch.uint8, device=w_tio.device)
         _pack_entries[key] = e
     if e.disabled:
@@ -509,9 +472,6 @@ def use_pack(w_tio, dgrad, C1, C2, Cout, N, D, H, W, stride=1, up2=False):
         e.stamp, e.event = stamp, None
     elif e.event is not None:
         torch.cuda.current_stream().wait_event(e.event)
-    if e.any is not None:
-        nat.lib().da_conv3d_k3_use_prepacked_any(ptr(w_tio), ptr(e.bufs[0]), e.bufs[0].numel(), e.tag)
-        return
     b1 = e.bufs[1]
     nat.lib().da_conv3d_k3_use_prepacked(ptr(w_tio), ptr(e.bufs[0]), e.bufs[0].numel(), ptr(b1), b1.numel() if b1 is not None else 0)
 
@@ -539,24 +499,6 @@ def repack_after_step(flat_p):
     if not mine:
         return
     import ctypes
-    others = [e for e in mine if e.any is not None]
-    mine = [e for e in mine if e.any is None]
-    if others:                                          # the other families: one small pack launch each, on the side stream like the batched ones
-        side = side_stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            sst = stream()
-            for e in others:
-                v = torch.as_strided(e.base(), e.view[0], e.view[1], e.view[2])
-                if _pack_fill(e, v, sst) == 0:
-                    e.disabled = True
-            ev = torch.cuda.Event()
-            ev.record(side)
-        for e in others:
-            if not e.disabled:
-                e.stamp, e.event = _pack_stamp(e), ev
-    if not mine:
-        return
     n = len(mine)
     views = [torch.as_strided(e.base(), e.view[0], e.view[1], e.view[2]) for e in mine]
     PA, IA, SA = ctypes.c_void_p * n, ctypes.c_int * n, ctypes.c_size_t * n
