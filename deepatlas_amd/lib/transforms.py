@@ -1,8 +1,10 @@
 """Tensor-level transforms (lib/transforms.py) on the device: mask_to_one_hot / SegMaskToOneHot (:652-689), and the data path of
 SURVEY.md row f4 -- SitkToTensor's clamp + cast (:71-92), CropTensor (:124-158), Partition's overlap tiling with reflect padding
-and both assemble modes (:508-649).  The SimpleITK read / resample / crop filters themselves are host I/O and stay out of scope;
-these classes take numpy arrays (what sitk.GetArrayFromImage returns) or tensors and hand back DEVICE tensors, so a loader
-thread only uploads the raw volume once.
+and both assemble modes (:508-649), and the two random spatial augmentations RandomRigidTransform (:202-259) and
+RandomBSplineTransform (:161-199) as device resamples.  The SimpleITK read / crop / filter transforms (GaussianBlur, BilateralFilter,
+Resample to a voxel size, Normalization, LeftToRight, RandomCrop, BalancedRandomCrop, SegmentationLabelFilter) are host I/O and stay
+out of scope; these classes take numpy arrays (what sitk.GetArrayFromImage returns) or tensors and hand back DEVICE tensors, so a
+loader thread only uploads the raw volume once.
 """
 import ctypes
 
@@ -176,3 +178,219 @@ class Partition(object):
             keep[sl] = out[sl]
             out = keep
         return out
+
+
+# ---- random spatial augmentation (lib/transforms.py:161-290) ----------------------------------------------------------------------
+# Device tensors carry no geometry: they follow SitkToTensor's convention (image C x D x H x W float32, segmentation D x H x W), axes in
+# SimpleITK order x = W, y = H, z = D, origin 0, identity direction, spacing sample.get('spacing', (1, 1, 1)) given as (x, y, z).  The
+# parameter draws and the host-side geometry are the small pure functions below; ops.spatial_resample does the resample on the device.
+
+def _rotation_zxy(angles):
+    """sitk.Euler3DTransform with ComputeZYX off: R = Rz Rx Ry (right-handed), angles (x, y, z) in radians."""
+    ax, ay, az = (float(a) for a in angles)
+    cx, sx, cy, sy, cz, sz = np.cos(ax), np.sin(ax), np.cos(ay), np.sin(ay), np.cos(az), np.sin(az)
+    Rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]])
+    Ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
+    Rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
+    return Rz @ Rx @ Ry
+
+
+def rigid_index_affine(angles, translation, spacing, rotation_center):
+    """3 x 4 fp64 index-space matrix A of the rigid map, q = A[:, :3] i + A[:, 3] for an output index i = (x, y, z).
+    Physical point p = S i maps to R (p - c) + c + t (sitk.Euler3DTransform about c with translation t), c = S rotation_center (an
+    index, (x, y, z)), S = diag(spacing); dividing by S gives the input index: A = [S^-1 R S | S^-1 (c + t - R c)]."""
+    S = np.asarray(spacing, dtype=np.float64)
+    R = _rotation_zxy(angles)
+    c = S * np.asarray(rotation_center, dtype=np.float64)
+    t = np.asarray(translation, dtype=np.float64)
+    A = np.empty((3, 4))
+    A[:, :3] = R * S[None, :] / S[:, None]
+    A[:, 3] = (c + t - R @ c) / S
+    return A
+
+
+def draw_rigid(ratio, rotation_angles, translation, spacing):
+    """One sample's draws, in the reference's order (:224-242): the coin np.random.rand(1) against `ratio`, then normal(0, angle / 2)
+    for x, y, z (degrees -> radians), then normal(0, translation / 2) * spacing for x, y, z.  Returns None when the coin fails (nothing
+    more is drawn), else (angles in radians, translation in physical units), both (x, y, z)."""
+    if not np.random.rand(1)[0] < ratio:
+        return None
+    angles = [np.random.normal(0, rotation_angles[k] / 2) * np.pi / 180 for k in range(3)]
+    trans = [np.random.normal(0, translation[k] / 2) * spacing[k] for k in range(3)]
+    return np.array(angles), np.array(trans)
+
+
+def bspline_grid(size, mesh_size, order):
+    """Control grid (gx, gy, gz) = mesh_size + order of sitk.BSplineTransformInitializer(img, mesh_size, order) on a volume of `size`
+    voxels, both (x, y, z).  Orders 1, 2, 3; every axis needs >= 2 voxels (the domain spans the voxel centres [0, size - 1])."""
+    if order not in (1, 2, 3):
+        raise ValueError('bspline_order %r: orders 1, 2 and 3 are supported' % (order,))
+    if len(mesh_size) != 3 or min(int(m) for m in mesh_size) < 1:
+        raise ValueError('mesh_size must be three positive integers (x, y, z)')
+    if min(int(s) for s in size) < 2:
+        raise ValueError('a B-spline transform needs >= 2 voxels per axis, got size %s' % (tuple(size),))
+    return tuple(int(m) + order for m in mesh_size)
+
+
+def bspline_kernel(u, order):
+    """Centred uniform B-spline of `order` (1 hat, 2 quadratic, 3 cubic) at u, fp64."""
+    a = np.abs(np.asarray(u, dtype=np.float64))
+    if order == 1:
+        return np.where(a < 1, 1 - a, 0.0)
+    if order == 2:
+        return np.where(a < 0.5, 0.75 - a * a, np.where(a < 1.5, 0.5 * (1.5 - a) ** 2, 0.0))
+    return np.where(a < 1, (4 - 6 * a * a + 3 * a ** 3) / 6, np.where(a < 2, (2 - a) ** 3 / 6, 0.0))
+
+
+def bspline_support(i, size, mesh, order):
+    """Support of output index i along one axis: grid coordinate g = i M / (size - 1) + (order - 1) / 2, start = floor(g - (order - 1) / 2)
+    clamped to <= M - 1 (the limit from inside at the upper face: ITK's InsideValidRegion nudge), weights B(g - start - k), k = 0..order."""
+    g = i * mesh / (size - 1) + (order - 1) / 2
+    start = np.minimum(np.floor(g - (order - 1) / 2).astype(np.int64), mesh - 1)
+    k = np.arange(order + 1)
+    w = bspline_kernel(np.asarray(g)[..., None] - (np.asarray(start)[..., None] + k), order)
+    return start, w
+
+
+def draw_bspline(ratio, n_params, deform_scale, random_mode):
+    """One sample's draws, in the reference's order (:178-188): the coin np.random.rand(1), then ONE vector of all n_params parameters,
+    normal(0, deform_scale / 2, n) ('Normal') or random(n) * deform_scale ('Uniform').  Then, as the reference's code does, the first third
+    is set to 0.  The reference's comment calls that third the z displacement; in ITK's parameter layout it is the X component (all x
+    coefficients, then y, then z), so x is the axis that stays undeformed.  Returns None when the coin fails."""
+    if not np.random.rand(1)[0] < ratio:
+        return None
+    if random_mode == 'Normal':
+        p = np.random.normal(0, deform_scale / 2, n_params)
+    elif random_mode == 'Uniform':
+        p = np.random.random(n_params) * deform_scale
+    else:
+        raise ValueError("random_mode %r: 'Normal' or 'Uniform'" % (random_mode,))
+    p[0:int(len(p) / 3)] = 0
+    return p
+
+
+def bspline_coefficients(params, grid):
+    """Flat ITK parameter vector -> 3 x gz x gy x gx array (component x, y, z; each grid flattened with x fastest), physical units."""
+    gx, gy, gz = grid
+    return np.asarray(params, dtype=np.float64).reshape(3, gz, gy, gx)
+
+
+_IDENTITY_3x4 = np.eye(3, 4)
+
+
+def _as_batch(sample):
+    img = sample['image']
+    seg = sample.get('segmentation')
+    single = img.dim() == 4
+    if img.dim() not in (4, 5):
+        raise ValueError('image must be C x D x H x W or N x C x D x H x W')
+    imgs = img.unsqueeze(0) if single else img
+    segs = None if seg is None else (seg.unsqueeze(0) if single else seg)
+    return imgs, segs, single
+
+
+def _store(sample, img, seg, single):
+    if img is not None:
+        sample['image'] = img[0] if single else img
+    if seg is not None:
+        sample['segmentation'] = seg[0] if single else seg
+    return sample
+
+
+def _check_interpolator(interpolator):
+    if interpolator not in ops.AUG_INTERPOLATORS:
+        raise NotImplementedError("interpolator %r: the device resample implements 'linear' and 'nearest' (no sitkBSpline)" % (interpolator,))
+    return interpolator
+
+
+class RandomBSplineTransform(object):
+    """lib/transforms.py:161-199 on the device: random B-spline deformation of an image and its segmentation.
+    sample['image'] C x D x H x W float32 (or a batch N x C x D x H x W), sample['segmentation'] D x H x W (or N x D x H x W) uint8 / int64.
+    Per sample: the coin against `ratio`, then the draws of draw_bspline.  Geometry of sitk.BSplineTransformInitializer(img, mesh_size,
+    bspline_order) (mesh_size (x, y, z)): per axis M + order control points over the voxel centres [0, size - 1] (bspline_support); the
+    displacement is in physical units, input index = i + d(i) / spacing.  Resample as sitk.Resample onto the image's own grid: inside
+    (-0.5 <= q < size - 0.5) the image is trilinear with neighbours clamped to the volume ('linear') or nearest ('nearest'), labels
+    nearest floor(q + 0.5); outside 0.1 for the image, 0 for labels.  Samples whose coin fails are copied unchanged in the same launch;
+    when every coin fails the sample is returned untouched with no device call.  Returns fresh device tensors otherwise."""
+
+    def __init__(self, mesh_size=(3, 3, 3), bspline_order=2, deform_scale=1.0, ratio=0.5, interpolator='linear', random_mode='Normal'):
+        if bspline_order not in (1, 2, 3):
+            raise ValueError('bspline_order %r: orders 1, 2 and 3 are supported' % (bspline_order,))
+        self.mesh_size = mesh_size
+        self.bspline_order = bspline_order
+        self.deform_scale = deform_scale
+        self.ratio = ratio  # control the probability of conduct transform
+        self.interpolator = _check_interpolator(interpolator)
+        self.random_mode = random_mode
+
+    def draw(self, n, size):
+        """The draws of n samples of `size` (x, y, z) voxels, sample after sample: a list of flat parameter vectors or None."""
+        grid = bspline_grid(size, self.mesh_size, self.bspline_order)
+        n_params = 3 * grid[0] * grid[1] * grid[2]
+        return [draw_bspline(self.ratio, n_params, self.deform_scale, self.random_mode) for _ in range(n)]
+
+    def __call__(self, sample):
+        imgs, segs, single = _as_batch(sample)
+        D, H, W = (int(s) for s in imgs.shape[-3:])
+        grid = bspline_grid((W, H, D), self.mesh_size, self.bspline_order)
+        params = self.draw(imgs.shape[0], (W, H, D))
+        if all(p is None for p in params):
+            return sample
+        spacing = np.asarray(sample.get('spacing', (1.0, 1.0, 1.0)), dtype=np.float64)
+        coef = np.zeros((len(params), 3, grid[2], grid[1], grid[0]))
+        for k, p in enumerate(params):
+            if p is not None:
+                coef[k] = bspline_coefficients(p, grid) / spacing[:, None, None, None]
+        affine = np.broadcast_to(_IDENTITY_3x4, (len(params), 3, 4))
+        img, seg = ops.spatial_resample(imgs, segs, affine, coef, self.bspline_order, self.interpolator)
+        return _store(sample, img, seg, single)
+
+
+class RandomRigidTransform(object):
+    """lib/transforms.py:202-259 on the device: random rigid (sitk.Euler3DTransform) transform of an image and / or its segmentation.
+    Tensors as RandomBSplineTransform.  Per sample: the coin against `ratio`, then the draws of draw_rigid.  The rotation R = Rz Rx Ry
+    (ComputeZYX off) acts about c = spacing * rotation_center, an index (x, y, z) defaulting to (W, H, D) // 2; output point p = S i reads
+    the input at R (p - c) + c + t, composed on the host in fp64 into one index-space 3 x 4 matrix per sample (rigid_index_affine).
+    Resample rules as RandomBSplineTransform.  mode 'both', 'img' or 'seg' (the other tensor is left as it is); anything else raises
+    ValueError."""
+
+    def __init__(self, ratio=1.0, rotation_center=None, rotation_angles=(0.0, 0.0, 0.0), translation=(0.0, 0.0, 0.0),
+                 interpolator='linear', mode='both'):
+        if mode not in ('both', 'img', 'seg'):
+            raise ValueError('Wrong rigid transformation mode :{}!'.format(mode))
+        self.rotation_center = rotation_center
+        self.rotation_angles = rotation_angles
+        self.translation = translation
+        self.interpolator = _check_interpolator(interpolator)
+        self.ratio = ratio
+        self.mode = mode
+
+    def draw(self, n, spacing=(1.0, 1.0, 1.0)):
+        """The draws of n samples, sample after sample: a list of (angles, translation) or None."""
+        return [draw_rigid(self.ratio, self.rotation_angles, self.translation, spacing) for _ in range(n)]
+
+    def __call__(self, sample):
+        imgs, segs, single = _as_batch(sample)
+        D, H, W = (int(s) for s in imgs.shape[-3:])
+        spacing = tuple(float(s) for s in sample.get('spacing', (1.0, 1.0, 1.0)))
+        params = self.draw(imgs.shape[0], spacing)
+        if all(p is None for p in params):
+            return sample
+        center = self.rotation_center if self.rotation_center else (np.array((W, H, D)) // 2).tolist()
+        affine = np.stack([_IDENTITY_3x4 if p is None else rigid_index_affine(p[0], p[1], spacing, center) for p in params])
+        img, seg = ops.spatial_resample(imgs if self.mode in ('both', 'img') else None,
+                                        segs if self.mode in ('both', 'seg') else None, affine, interpolator=self.interpolator)
+        return _store(sample, img, seg, single)
+
+
+AUGMENTATIONS = {'rigid': RandomRigidTransform, 'bspline': RandomBSplineTransform}
+
+
+def make_augmentation(spec):
+    """SegmentationExperiment's config['augment']: [[name, kwargs], ...] with name 'rigid' or 'bspline' -> the transforms, in order."""
+    out = []
+    for name, kwargs in (spec or []):
+        if name not in AUGMENTATIONS:
+            raise ValueError("augmentation %r: one of %s" % (name, sorted(AUGMENTATIONS)))
+        out.append(AUGMENTATIONS[name](**dict(kwargs or {})))
+    return out

@@ -20,6 +20,7 @@ from torch.utils.data import DataLoader
 from .base import BaseExperiment
 from ..lib import datasets as med_data
 from ..lib import evalMetrics as metrics
+from ..lib import transforms as med_transforms
 from ..lib.loss import get_loss_function
 from ..lib.network_factory import get_network
 from ..lib.param_dict import save_dict_to_json
@@ -51,6 +52,8 @@ class SegmentationExperiment(BaseExperiment):
         self.global_step = 0
         self.training_data_loader = self.config.get('training_data_loader')
         self.validation_data_loader = self.config.get('validation_data_loader')
+        # optional training-batch augmentation, config['augment'] = [['rigid', {...}], ['bspline', {...}]] (lib/transforms.py:161-259)
+        self.augment = med_transforms.make_augmentation(self.config.get('augment'))
         print("Init experiment {} seed {}".format(self.exp_name, self.config['random_seed']))
 
     @staticmethod
@@ -164,6 +167,14 @@ class SegmentationExperiment(BaseExperiment):
             self.optimizer.step()
         return loss, output
 
+    def augment_batch(self, images, truths):
+        """config['augment']'s transforms, in order, on the device, to one training batch (N x 1 x D x H x W, N x D x H x W).  Validation
+        and test batches are never augmented."""
+        sample = {'image': images.to(self.device, non_blocking=True), 'segmentation': truths.to(self.device, non_blocking=True)}
+        for t in self.augment:
+            sample = t(sample)
+        return sample['image'], sample['segmentation']
+
     def train_one_epoch(self):
         running_loss = 0.0
         iters_per_epoch = max(self.config['samples_per_epoch'] // (self.config['batch_size'] * parallel.world_size()), 1)
@@ -175,6 +186,8 @@ class SegmentationExperiment(BaseExperiment):
                 train_data_iter = iter(self.training_data_loader)
                 images, truths, name = next(train_data_iter)
             self.global_step = (self.current_epoch - 1) * iters_per_epoch + (i + 1) * self.config['batch_size']
+            if self.augment:
+                images, truths = self.augment_batch(images, truths)
             loss, output = self.train_step(images, truths)
             running_loss += loss.item()
             if i % self.config['print_batch_period'] == self.config['print_batch_period'] - 1:

@@ -2189,3 +2189,57 @@ def label_overlap_counts(pred, truth, n_class):
     counts = torch.zeros((N, n_class, 3), dtype=torch.int64, device=pl.device)
     call('da_label_overlap_counts', ptr(pl), pb, ptr(tl), tb, N, pl.shape[1], n_class, ptr(counts), stream())
     return counts
+
+
+AUG_INTERPOLATORS = {'linear': 0, 'nearest': 1}
+_LABEL_BYTES = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}
+
+
+def spatial_resample(image, labels, affine, coef=None, order=0, interpolator='linear'):
+    """The resample behind lib/transforms.py's random rigid / B-spline transforms (:161-290), one da_spatial_resample launch per batch.
+    image: N x C x D x H x W float32 or None; labels: N x D x H x W uint8 / int32 / int64 or None (not both None); both on the GPU.
+    affine: N x 3 x 4 host array, the index-space map q = A[:, :3] i + A[:, 3] with i = (x, y, z) = (w, h, d).  coef: None (order 0) or
+    an N x 3 x gz x gy x gx host array of (x, y, z) displacements in INDEX units on the control grid of a B-spline of `order` 1..3,
+    added to q.  Image `interpolator` 'linear' or 'nearest', labels nearest; outside the volume 0.1 / 0.
+    Returns (image_out, labels_out): fresh tensors, None where the input is None."""
+    import numpy as np
+    if interpolator not in AUG_INTERPOLATORS:
+        raise NotImplementedError("interpolator %r: the device resample implements 'linear' and 'nearest'" % (interpolator,))
+    ref = image if image is not None else labels
+    if ref is None:
+        raise ValueError('spatial_resample needs an image or labels')
+    nat.require_cuda(image, labels)
+    N = ref.shape[0]
+    D, H, W = (int(s) for s in ref.shape[-3:])
+    if image is not None:
+        if image.dim() != 5 or image.dtype != torch.float32:
+            raise ValueError('image must be N x C x D x H x W float32')
+        image = image.contiguous()
+    if labels is not None:
+        if labels.dtype not in _LABEL_BYTES:
+            raise ValueError('labels must be uint8, int32 or int64')
+        if tuple(labels.shape) != (N, D, H, W):
+            raise ValueError('labels must be N x D x H x W matching the image')
+        labels = labels.contiguous()
+    A = np.asarray(affine, dtype=np.float64).reshape(N, 3, 4)
+    # the kernel applies the matrix about o = (W/2, H/2, D/2): q = M (i - o) + (M o + b), which keeps the fp32 terms small
+    o = np.array([W // 2, H // 2, D // 2], dtype=np.float64)
+    kern = np.concatenate([A[:, :, :3], (A[:, :, :3] @ o + A[:, :, 3])[:, :, None]], axis=2)
+    dev = ref.device
+    aff = torch.from_numpy(np.ascontiguousarray(kern, dtype=np.float32)).to(dev)
+    if order:
+        cf = np.ascontiguousarray(coef, dtype=np.float32)
+        if cf.ndim != 5 or cf.shape[:2] != (N, 3):
+            raise ValueError('coef must be N x 3 x gz x gy x gx')
+        gz, gy, gx = cf.shape[2:]
+        cft = torch.from_numpy(cf).to(dev)
+    else:
+        gz = gy = gx = 0
+        cft = None
+    img_out = torch.empty_like(image) if image is not None else None
+    lab_out = torch.empty_like(labels) if labels is not None else None
+    with torch.cuda.device(dev):
+        call('da_spatial_resample', ptr(image), ptr(img_out), int(image.shape[1]) if image is not None else 0, AUG_INTERPOLATORS[interpolator],
+             ptr(labels), ptr(lab_out), _LABEL_BYTES[labels.dtype] if labels is not None else 1,
+             ptr(aff), ptr(cft), int(order), int(gx), int(gy), int(gz), N, D, H, W, stream())
+    return img_out, lab_out

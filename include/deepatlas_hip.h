@@ -454,6 +454,22 @@ int da_assemble_tiles(const void* tiles, void* vol, int elem_bytes, int D, int H
 int da_synth_volume(float* img, unsigned char* labels, int N, int D, int H, int W, int n_classes, int mode, float noise,
                     unsigned int seed, int sample0, void* stream);
 
+/* ---- random spatial augmentation (lib/transforms.py:161-290: RandomBSplineTransform, RandomRigidTransform, resample) --------
+ * sitk.Resample with the image as its own reference grid, for a batch of N samples in one launch.  img / img_out [N][C][D][H][W] fp32,
+ * labels / labels_out [N][D][H][W] of label_bytes (1, 4 or 8) bytes; either pair may be NULL (not both).  Output voxel i = (x, y, z) =
+ * (w, h, d) reads the input at the continuous index q = A[n][:, :3] (i - o) + A[n][:, 3] (+ the B-spline displacement), with
+ * o = (W/2, H/2, D/2) (integer division) and affine A [N][3][4] fp32 on the device.  Inside (-0.5 <= q < size - 0.5 on every axis):
+ * image trilinear with neighbours clamped to the volume (interp 0) or nearest (interp 1), labels nearest floor(q + 0.5); outside:
+ * 0.1 for the image, 0 for labels.  order 0: no displacement (coef unused).  order 1..3: coef [N][3][gz][gy][gx] fp32 on the device,
+ * the (x, y, z) displacement components in INDEX units over a control grid of g = M + order points per axis, M mesh cells spanning
+ * the voxel centres [0, size - 1] (ITK BSplineTransformInitializer); every axis needs >= 2 voxels and g >= order + 1.
+ * DA_ERR_UNSUPPORTED for gx gy gz > DA_AUG_MAX_GRID_POINTS (the coefficients are staged in LDS) or volumes of >= 2^31 voxels. */
+#define DA_AUG_MAX_GRID_POINTS 2048
+int da_spatial_resample(const float* img, float* img_out, int C, int interp,
+                        const void* labels, void* labels_out, int label_bytes,
+                        const float* affine, const float* coef, int order, int gx, int gy, int gz,
+                        int N, int D, int H, int W, void* stream);
+
 /* ---- LNCC similarity (lib/loss.py:589-617 VoxelMorphLNCC = registry 'lncc', and :512-586 LNCCLoss) -----
  * I, J: [N][D][H][W] fp32 (single channel); all-ones F^3 window with dilation `dil` and stride `stride` (1, 1 for VoxelMorphLNCC),
  * valid padding; loss = 1 - mean(cross^2 / (Ivar Jvar + eps)).  Output extent per axis: (L - dil (F-1) - 1) / stride + 1.

@@ -41,6 +41,16 @@ def build_config(args):
     config['valid_data_dir'] = config['data_dir']
     config['log_dir'] = './{}/{}'.format(args.log_root, config['data'])
     config['device'] = 'cuda:{}'.format(args.device) if args.device.isdigit() else args.device
+    # opt-in device augmentation (lib/transforms.py:161-259), every other argument at the reference's default
+    augment = []
+    aug_rigid = config.pop('aug_rigid', None)
+    aug_bspline = config.pop('aug_bspline', None)
+    if aug_rigid:
+        augment.append(['rigid', {'rotation_angles': list(aug_rigid[:3]), 'translation': list(aug_rigid[3:])}])
+    if aug_bspline is not None:
+        augment.append(['bspline', {'deform_scale': aug_bspline}])
+    if augment:
+        config['augment'] = augment
     if not config.get('matrix_precision'):                # (--matrix-precision; not a key of the reference's config: absent = the package default, 'fp32_split')
         config.pop('matrix_precision', None)
     return config
@@ -64,6 +74,10 @@ def main(argv=None):
                              "7e-7, NARROWER than an fp32 multiply; sums of >= ~100 terms are as close to double as fp32's; elements > 2^15..2^18 below "
                              "their tile's maximum keep only an absolute 2^-40 of it -- csrc/split_f16.h); 'fp32' the fp32 matrix instructions = the "
                              "reference's arithmetic (~1.7x slower steps); 'bf16' operands rounded to bf16")
+    parser.add_argument('--aug-rigid', nargs=6, type=float, default=None, metavar=('RX', 'RY', 'RZ', 'TX', 'TY', 'TZ'),
+                        help='augment training batches with RandomRigidTransform: rotation_angles (degrees) and translation (voxels), (x, y, z)')
+    parser.add_argument('--aug-bspline', type=float, default=None, metavar='DEFORM_SCALE',
+                        help='augment training batches with RandomBSplineTransform(deform_scale=DEFORM_SCALE), after the rigid one')
     args = parser.parse_args(argv)
     exp = SegmentationExperiment(build_config(args))
     if not args.test_only:
