@@ -314,23 +314,12 @@ extern "C" size_t da_conv3d_k3_ws_bytes(int N, int D, int H, int W, int Cin, int
     return packed + (direct > mfma ? direct : mfma) + da_bn_ws_bytes(0, Cm) + 4096;
 }
 
-static int g_force_direct = -1;
-static bool force_direct() {
-    if (g_force_direct < 0) { const char* e = getenv("DA_CONV_DIRECT"); g_force_direct = (e && e[0] == '1') ? 1 : 0; }
-    return g_force_direct == 1;
-}
-extern "C" int da_set_conv_direct(int on) { const int prev = force_direct() ? 1 : 0; g_force_direct = on ? 1 : 0; return prev; }
+// da_set_conv_direct(1): every 3x3x3 call on the direct kernels (the tests' cross-check of the other routes)
+static bool g_force_direct = false;
+extern "C" int da_set_conv_direct(int on) { const int prev = g_force_direct ? 1 : 0; g_force_direct = on != 0; return prev; }
 
-// Coarse stride-2 layers (the registration encoder below 40^3) are latency-bound on the space-to-depth route (a chain of four launches,
-// 16 channel chunks per tile walked one after the other: 0.15 - 0.28 ms for 0.05 - 0.4 GFLOP).  Measured alternative: the direct
-// kernels are 2 - 8x SLOWER there (forward 0.33 vs 0.15 ms, data gradient 0.52 vs 0.05, weight gradient 0.58 vs 0.07 at 40^3 -> 20^3),
-// so the switch stays off: DA_S2_DIRECT_MAX_OUT_VOX = largest output-voxel count that takes the direct kernels (default 0 = never).
-static bool s2_prefers_direct(int N, int D, int H, int W) {
-    static long long thr = -1;
-    if (thr < 0) { const char* e = getenv("DA_S2_DIRECT_MAX_OUT_VOX"); thr = e ? atoll(e) : 0; }
-    const long long out = (long long)N * ((D - 1) / 2 + 1) * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1);
-    return out <= thr;
-}
+// Coarse stride-2 layers (the registration encoder below 40^3) stay on the space-to-depth route: the direct kernels were measured
+// 2 - 8x SLOWER there (forward 0.33 vs 0.15 ms, data gradient 0.52 vs 0.05, weight gradient 0.58 vs 0.07 at 40^3 -> 20^3).
 
 extern "C" int da_conv3d_k3_fwd(const float* in1, int C1, const float* in2, int C2,
                                 const float* w_tio, const float* bias, float* out,
@@ -339,26 +328,26 @@ extern "C" int da_conv3d_k3_fwd(const float* in1, int C1, const float* in2, int 
     if (!in1 || !w_tio || !out || C1 <= 0 || C2 < 0 || (C2 > 0 && !in2) || N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cout <= 0 || (stride != 1 && stride != 2))
         return DA_ERR_BADARG;
     hipStream_t st = da_stream(stream);
-    if (!force_direct() && stride == 2 && da_conv3_s2_supported(C1, C2, Cout) && !s2_prefers_direct(N, D, H, W)) {
+    if (!g_force_direct && stride == 2 && da_conv3_s2_supported(C1, C2, Cout)) {
         if (ws_bytes < da_conv3d_k3_ws_bytes(N, D, H, W, C1 + C2, Cout, stride)) return DA_ERR_WS_SMALL;
         return da_conv3_s2_fwd(in1, C1, w_tio, bias, out, N, D, H, W, Cout, act_slope, ws, ws_bytes - da_bn_ws_bytes(0, Cout) - 4096, st);
     }
-    if (!force_direct() && da_conv3_mfma_fwd_supported(C1, C2, Cout, stride)) {
+    if (!g_force_direct && da_conv3_mfma_fwd_supported(C1, C2, Cout, stride)) {
         if (ws_bytes < da_conv3d_k3_ws_bytes(N, D, H, W, C1 + C2, Cout, stride)) return DA_ERR_WS_SMALL;
         const int rc = da_conv3_mfma_fwd(in1, C1, in2, C2, w_tio, /*w_is_flipped_tr=*/0, bias, out, Cout, nullptr, 0,
                                          N, D, H, W, Cout, stride, act_slope, ws, ws_bytes, st);
         if (rc != DA_ERR_UNSUPPORTED) return rc;           // e.g. a per-sample tensor beyond 32-bit byte offsets: direct kernels below
     }
-    if (!force_direct() && stride == 1 && da_conv3_flowmm_supported(C1, C2, Cout, N, D, H, W)) {      // <= 3 outputs, split mode: (dy, cout) columns on the matrix cores
+    if (!g_force_direct && stride == 1 && da_conv3_flowmm_supported(C1, C2, Cout, N, D, H, W)) {      // <= 3 outputs, split mode: (dy, cout) columns on the matrix cores
         const int rc = da_conv3_flowmm_fwd(in1, C1, in2, C2, w_tio, bias, out, N, D, H, W, Cout, act_slope, ws, ws_bytes, st);
         if (rc != DA_ERR_UNSUPPORTED) return rc;
     }
-    if (!force_direct() && da_conv3_thin_supported(C1, C2, Cout, stride) && !getenv("DA_NO_THIN")) {
+    if (!g_force_direct && da_conv3_thin_supported(C1, C2, Cout, stride)) {
         const int rc = da_conv3_thin_fwd(in1, C1, in2, C2, w_tio, 0, bias, out, Cout, nullptr, 0, N, D, H, W, Cout, act_slope, ws, ws_bytes, st);
         if (rc != DA_ERR_UNSUPPORTED) return rc;
     }
     // tiny Cin, full-quad Cout, single output pointer, 32-bit addressable
-    const bool tiny = !force_direct() && stride == 1 && ((C2 == 0 && (C1 == 1 || C1 == 2)) || (C1 == 1 && C2 == 1)) && (Cout == 8 || Cout == 16) &&
+    const bool tiny = !g_force_direct && stride == 1 && ((C2 == 0 && (C1 == 1 || C1 == 2)) || (C1 == 1 && C2 == 1)) && (Cout == 8 || Cout == 16) &&
                       (unsigned long long)N * D * H * W * 2ull * 4ull < 0xFFFFFFF0ull;
     if (tiny) {
         const long long nvox = (long long)N * D * H * W;
@@ -378,7 +367,7 @@ extern "C" int da_conv3d_k3_fwd_bnstats(const float* in1, int C1, const float* i
     if (stats_nparts) *stats_nparts = 0;
     if (!in1 || !w_tio || !out || C1 <= 0 || C2 < 0 || (C2 > 0 && !in2) || N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cout <= 0 || (stride != 1 && stride != 2))
         return DA_ERR_BADARG;
-    if (stats_partial && stats_capacity >= 512 && !force_direct() && stride == 1 && da_conv3_mfma_fwd_supported(C1, C2, Cout, stride)) {
+    if (stats_partial && stats_capacity >= 512 && !g_force_direct && stride == 1 && da_conv3_mfma_fwd_supported(C1, C2, Cout, stride)) {
         if (ws_bytes < da_conv3d_k3_ws_bytes(N, D, H, W, C1 + C2, Cout, stride)) return DA_ERR_WS_SMALL;
         const int rc = da_conv3_mfma_fwd(in1, C1, in2, C2, w_tio, 0, bias, out, Cout, nullptr, 0, N, D, H, W, Cout, stride, -1.f,
                                          ws, ws_bytes, da_stream(stream), 0, stats_partial, stats_nparts);
@@ -401,7 +390,7 @@ extern "C" int da_conv3d_k3_fwd_pro(const float* in1, int C1, const float* pro1_
     if (!in1 || !w_tio || !out || C1 <= 0 || C2 < 0 || (C2 > 0 && !in2) || N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cout <= 0 ||
         (pro1_scale && !pro1_shift) || (pro2_scale && !pro2_shift))
         return DA_ERR_BADARG;
-    if (force_direct() || !da_conv3_mfma_fwd_supported(C1, C2, Cout, 1)) return DA_ERR_UNSUPPORTED;
+    if (g_force_direct || !da_conv3_mfma_fwd_supported(C1, C2, Cout, 1)) return DA_ERR_UNSUPPORTED;
     if (ws_bytes < da_conv3d_k3_ws_bytes(N, D, H, W, C1 + C2, Cout, 1)) return DA_ERR_WS_SMALL;
     const DaPro pro = {pro1_scale, pro1_shift, pro1_slope, pro2_scale, pro2_shift, pro2_slope};
     const bool stats = stats_partial && stats_capacity >= 512;
@@ -417,7 +406,7 @@ extern "C" int da_conv3d_k3_wgrad_pro(const float* in1, int C1, const float* pro
     if (!in1 || !dy || !dw_tio || C1 <= 0 || C2 < 0 || (C2 > 0 && !in2) || N <= 0 || Cout <= 0 ||
         (pro1_scale && !pro1_shift) || (pro2_scale && !pro2_shift))
         return DA_ERR_BADARG;
-    if (force_direct() || !da_conv3_mfma_wgrad_supported(C1, C2, Cout, 1)) return DA_ERR_UNSUPPORTED;
+    if (g_force_direct || !da_conv3_mfma_wgrad_supported(C1, C2, Cout, 1)) return DA_ERR_UNSUPPORTED;
     if (ws_bytes < da_conv3d_k3_ws_bytes(N, D, H, W, C1 + C2, Cout, 1)) return DA_ERR_WS_SMALL;
     const DaPro pro = {pro1_scale, pro1_shift, pro1_slope, pro2_scale, pro2_shift, pro2_slope};
     return da_conv3_mfma_wgrad(in1, C1, in2, C2, dy, dw_tio, N, D, H, W, Cout, 1, ws, ws_bytes, da_stream(stream), 0, &pro);
@@ -432,16 +421,16 @@ extern "C" int da_conv3d_k3_dgrad(const float* dy, const float* w_tio, float* dx
     if (ws_bytes < da_conv3d_k3_ws_bytes(N, D, H, W, Cin, Cout, stride)) return DA_ERR_WS_SMALL;
     if (stride == 1) {
         // dX = conv(dY, flip/transpose(W)) : Cin' = Cout, Cout' = Cin, output split over (dx1, dx2)
-        if (!force_direct() && da_conv3_mfma_fwd_supported(Cout, 0, Cin, 1, C1, C2)) {
+        if (!g_force_direct && da_conv3_mfma_fwd_supported(Cout, 0, Cin, 1, C1, C2)) {
             const int rc = da_conv3_mfma_fwd(dy, Cout, nullptr, 0, w_tio, /*w_is_flipped_tr=*/1, nullptr, dx1, C1, dx2, C2,
                                              N, D, H, W, Cin, 1, -1.f, ws, ws_bytes, st);
             if (rc != DA_ERR_UNSUPPORTED) return rc;
         }
-        if (!force_direct() && da_conv3_flowmm_supported(C1, C2, Cout, N, D, H, W)) {
+        if (!g_force_direct && da_conv3_flowmm_supported(C1, C2, Cout, N, D, H, W)) {
             const int rc = da_conv3_flowmm_dgrad(dy, w_tio, dx1, C1, dx2, C2, N, D, H, W, Cout, ws, ws_bytes, st);
             if (rc != DA_ERR_UNSUPPORTED) return rc;
         }
-        if (!force_direct() && da_conv3_thin_supported(Cout, 0, Cin, 1)) {
+        if (!g_force_direct && da_conv3_thin_supported(Cout, 0, Cin, 1)) {
             const int rc = da_conv3_thin_fwd(dy, Cout, nullptr, 0, w_tio, 1, nullptr, dx1, C1, dx2, C2, N, D, H, W, Cin, -1.f, ws, ws_bytes, st);
             if (rc != DA_ERR_UNSUPPORTED) return rc;
         }
@@ -450,7 +439,7 @@ extern "C" int da_conv3d_k3_dgrad(const float* dy, const float* w_tio, float* dx
         DA_LAUNCH_CHECK();
         return da_conv3_direct_fwd(dy, Cout, nullptr, 0, wf, nullptr, dx1, C1, dx2, C2, N, D, H, W, Cin, 1, -1.f, st);
     }
-    if (!force_direct() && da_conv3_s2_supported(C1, C2, Cout) && !s2_prefers_direct(N, D, H, W))
+    if (!g_force_direct && da_conv3_s2_supported(C1, C2, Cout))
         return da_conv3_s2_dgrad(dy, w_tio, dx1, C1, N, D, H, W, Cout, ws, ws_bytes - da_bn_ws_bytes(0, Cout) - 4096, st);
     const int Do = (D - 1) / 2 + 1, Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     const long long nvox = (long long)N * D * H * W;
@@ -471,9 +460,9 @@ extern "C" int da_conv3d_k3_wgrad(const float* in1, int C1, const float* in2, in
     const int Do = (D - 1) / stride + 1, Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
     const int O = 27 * Cin * Cout;
     int rc = 0;
-    if (!force_direct() && stride == 2 && da_conv3_s2_supported(C1, C2, Cout) && !s2_prefers_direct(N, D, H, W)) {
+    if (!g_force_direct && stride == 2 && da_conv3_s2_supported(C1, C2, Cout)) {
         rc = da_conv3_s2_wgrad(in1, C1, dy, dw_tio, N, D, H, W, Cout, ws, ws_bytes - da_bn_ws_bytes(0, Cout) - 4096, st);
-    } else if (!force_direct() && stride == 1 && da_conv3_mfma_wgrad_supported(C1, C2, Cout, stride)) {
+    } else if (!g_force_direct && stride == 1 && da_conv3_mfma_wgrad_supported(C1, C2, Cout, stride)) {
         rc = da_conv3_mfma_wgrad(in1, C1, in2, C2, dy, dw_tio, N, D, H, W, Cout, stride, ws, ws_bytes, st);
     } else {
         rc = DA_ERR_UNSUPPORTED;
@@ -511,11 +500,11 @@ extern "C" int da_conv3d_k3_fwd_bf16(const void* in1, int C1, const void* in2, i
     if (!in1 || !w_tio || !out || C1 <= 0 || C2 < 0 || (C2 > 0 && !in2) || N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cout <= 0 || (stride != 1 && stride != 2))
         return DA_ERR_BADARG;
     const unsigned want = 1u | (C2 > 0 ? 2u : 0u) | 4u;
-    if (force_direct()) return DA_ERR_UNSUPPORTED;
+    if (g_force_direct) return DA_ERR_UNSUPPORTED;
     if (ws_bytes < da_conv3d_k3_ws_bytes(N, D, H, W, C1 + C2, Cout, stride)) return DA_ERR_WS_SMALL;
     {   // thin layers on the VALU kernel: fp32 network inputs -> bf16 (first layers), bf16 -> fp32 displacement field (flow conv)
         const unsigned inm = 1u | (C2 > 0 ? 2u : 0u), in_bits = bf16_mask & inm;
-        if (stride == 1 && (in_bits == 0 || in_bits == inm) && !da_conv3_mfma_fwd_supported(C1, C2, Cout, stride) && da_conv3_thin_supported(C1, C2, Cout, stride) && !getenv("DA_NO_THIN")) {
+        if (stride == 1 && (in_bits == 0 || in_bits == inm) && !da_conv3_mfma_fwd_supported(C1, C2, Cout, stride) && da_conv3_thin_supported(C1, C2, Cout, stride)) {
             const int rc = da_conv3_thin_fwd((const float*)in1, C1, (const float*)in2, C2, w_tio, 0, bias, (float*)out, Cout, nullptr, 0, N, D, H, W, Cout, act_slope,
                                              ws, ws_bytes, da_stream(stream), in_bits != 0, (bf16_mask & 4u) != 0);
             if (rc != DA_ERR_UNSUPPORTED) return rc;
@@ -523,7 +512,7 @@ extern "C" int da_conv3d_k3_fwd_bf16(const void* in1, int C1, const void* in2, i
     }
     if ((bf16_mask & want) != want) return DA_ERR_UNSUPPORTED;
     if (stride == 2) {
-        if (!da_conv3_s2_supported(C1, C2, Cout) || s2_prefers_direct(N, D, H, W)) return DA_ERR_UNSUPPORTED;
+        if (!da_conv3_s2_supported(C1, C2, Cout)) return DA_ERR_UNSUPPORTED;
         return da_conv3_s2_fwd((const float*)in1, C1, w_tio, bias, (float*)out, N, D, H, W, Cout, act_slope, ws, ws_bytes - da_bn_ws_bytes(0, Cout) - 4096, da_stream(stream), 1);
     }
     if (!da_conv3_mfma_fwd_supported(C1, C2, Cout, stride)) return DA_ERR_UNSUPPORTED;
@@ -540,7 +529,7 @@ extern "C" int da_conv3d_k3_fwd_bnstats_bf16(const void* in1, int C1, const void
     if (!in1 || !w_tio || !out || C1 <= 0 || C2 < 0 || (C2 > 0 && !in2) || N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cout <= 0 || (stride != 1 && stride != 2))
         return DA_ERR_BADARG;
     const unsigned want = 1u | (C2 > 0 ? 2u : 0u) | 4u;
-    if (force_direct()) return DA_ERR_UNSUPPORTED;
+    if (g_force_direct) return DA_ERR_UNSUPPORTED;
     if ((bf16_mask & want) != want || stride != 1 || !da_conv3_mfma_fwd_supported(C1, C2, Cout, stride))      // no fused statistics (*stats_nparts = 0): thin / stride-2 routes
         return da_conv3d_k3_fwd_bf16(in1, C1, in2, C2, w_tio, bias, out, N, D, H, W, Cout, stride, -1.f, ws, ws_bytes, stream, bf16_mask);
     if (ws_bytes < da_conv3d_k3_ws_bytes(N, D, H, W, C1 + C2, Cout, stride)) return DA_ERR_WS_SMALL;
@@ -560,7 +549,7 @@ extern "C" int da_conv3d_k3_fwd_pro_bf16(const void* in1, int C1, const float* p
         (pro1_scale && !pro1_shift) || (pro2_scale && !pro2_shift))
         return DA_ERR_BADARG;
     const unsigned want = 1u | (C2 > 0 ? 2u : 0u) | 4u;
-    if ((bf16_mask & want) != want || force_direct() || !da_conv3_mfma_fwd_supported(C1, C2, Cout, 1)) return DA_ERR_UNSUPPORTED;
+    if ((bf16_mask & want) != want || g_force_direct || !da_conv3_mfma_fwd_supported(C1, C2, Cout, 1)) return DA_ERR_UNSUPPORTED;
     if (ws_bytes < da_conv3d_k3_ws_bytes(N, D, H, W, C1 + C2, Cout, 1)) return DA_ERR_WS_SMALL;
     const DaPro pro = {pro1_scale, pro1_shift, pro1_slope, pro2_scale, pro2_shift, pro2_slope};
     const bool stats = stats_partial && stats_capacity >= 512;
@@ -577,7 +566,7 @@ extern "C" int da_conv3d_k3_wgrad_pro_bf16(const void* in1, int C1, const float*
         (pro1_scale && !pro1_shift) || (pro2_scale && !pro2_shift))
         return DA_ERR_BADARG;
     const unsigned want = 1u | (C2 > 0 ? 2u : 0u) | 4u;
-    if ((bf16_mask & want) != want || force_direct() || !da_conv3_mfma_wgrad_supported(C1, C2, Cout, 1)) return DA_ERR_UNSUPPORTED;
+    if ((bf16_mask & want) != want || g_force_direct || !da_conv3_mfma_wgrad_supported(C1, C2, Cout, 1)) return DA_ERR_UNSUPPORTED;
     if (ws_bytes < da_conv3d_k3_ws_bytes(N, D, H, W, C1 + C2, Cout, 1)) return DA_ERR_WS_SMALL;
     const DaPro pro = {pro1_scale, pro1_shift, pro1_slope, pro2_scale, pro2_shift, pro2_slope};
     return da_conv3_mfma_wgrad((const float*)in1, C1, (const float*)in2, C2, (const float*)dy, dw_tio, N, D, H, W, Cout, 1, ws, ws_bytes, da_stream(stream), 0, &pro, nullptr, 1);
@@ -589,7 +578,7 @@ extern "C" int da_conv3d_k3_dgrad_bf16(const void* dy, const float* w_tio, void*
     if (!dy || !w_tio || !dx1 || C1 <= 0 || C2 < 0 || (C2 > 0 && !dx2) || N <= 0 || Cout <= 0 || (stride != 1 && stride != 2)) return DA_ERR_BADARG;
     const int Cin = C1 + C2;
     const unsigned want = 1u | 2u | (C2 > 0 ? 4u : 0u);
-    if (force_direct()) return DA_ERR_UNSUPPORTED;
+    if (g_force_direct) return DA_ERR_UNSUPPORTED;
     if (ws_bytes < da_conv3d_k3_ws_bytes(N, D, H, W, Cin, Cout, stride)) return DA_ERR_WS_SMALL;
     {   // data gradient of the flow conv: fp32 gradient of the displacement field -> bf16 gradients of its two inputs
         const unsigned outm = 2u | (C2 > 0 ? 4u : 0u), out_bits = bf16_mask & outm;
@@ -601,7 +590,7 @@ extern "C" int da_conv3d_k3_dgrad_bf16(const void* dy, const float* w_tio, void*
     }
     if ((bf16_mask & want) != want) return DA_ERR_UNSUPPORTED;
     if (stride == 2) {
-        if (!da_conv3_s2_supported(C1, C2, Cout) || s2_prefers_direct(N, D, H, W)) return DA_ERR_UNSUPPORTED;
+        if (!da_conv3_s2_supported(C1, C2, Cout)) return DA_ERR_UNSUPPORTED;
         return da_conv3_s2_dgrad((const float*)dy, w_tio, (float*)dx1, C1, N, D, H, W, Cout, ws, ws_bytes - da_bn_ws_bytes(0, Cout) - 4096, da_stream(stream), 1);
     }
     if (!da_conv3_mfma_fwd_supported(Cout, 0, Cin, 1, C1, C2)) return DA_ERR_UNSUPPORTED;
@@ -615,7 +604,7 @@ extern "C" int da_conv3d_k3_wgrad_bf16(const void* in1, int C1, const void* in2,
                                        void* ws, size_t ws_bytes, void* stream, unsigned bf16_mask) {
     if (!in1 || !dy || !dw_tio || C1 <= 0 || C2 < 0 || (C2 > 0 && !in2) || N <= 0 || Cout <= 0 || (stride != 1 && stride != 2)) return DA_ERR_BADARG;
     const unsigned want = 1u | (C2 > 0 ? 2u : 0u) | 4u;
-    if (force_direct() || dbias) return DA_ERR_UNSUPPORTED;
+    if (g_force_direct || dbias) return DA_ERR_UNSUPPORTED;
     if (ws_bytes < da_conv3d_k3_ws_bytes(N, D, H, W, C1 + C2, Cout, stride)) return DA_ERR_WS_SMALL;
     {   // thin layers: first layers (fp32 network input, bf16 output gradient) and the flow conv (bf16 inputs, fp32 gradient of the field)
         const unsigned inm = 1u | (C2 > 0 ? 2u : 0u), in_bits = bf16_mask & inm;
@@ -627,7 +616,7 @@ extern "C" int da_conv3d_k3_wgrad_bf16(const void* in1, int C1, const void* in2,
     }
     if ((bf16_mask & want) != want) return DA_ERR_UNSUPPORTED;
     if (stride == 2) {
-        if (!da_conv3_s2_supported(C1, C2, Cout) || s2_prefers_direct(N, D, H, W)) return DA_ERR_UNSUPPORTED;
+        if (!da_conv3_s2_supported(C1, C2, Cout)) return DA_ERR_UNSUPPORTED;
         return da_conv3_s2_wgrad((const float*)in1, C1, (const float*)dy, dw_tio, N, D, H, W, Cout, ws, ws_bytes - da_bn_ws_bytes(0, Cout) - 4096, da_stream(stream), 1);
     }
     if (!da_conv3_mfma_wgrad_supported(C1, C2, Cout, stride)) return DA_ERR_UNSUPPORTED;

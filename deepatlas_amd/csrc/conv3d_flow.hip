@@ -552,11 +552,8 @@ static int flow_launch_split(const FlowWgP& p, int nb, hipStream_t st) {
     return 0;
 }
 
-// split matrix mode, fp32 tensors: the two-term fp16 kernel (its tile is 2 x 8 x 16: the geometry is re-derived); DA_NO_FLOW_WGRAD_SPLIT=1: the exact-fp32 kernel
-static bool flow_use_split(int x_bf16) {
-    static const bool off = [] { const char* e = getenv("DA_NO_FLOW_WGRAD_SPLIT"); return e && atoi(e) != 0; }();
-    return !off && !x_bf16 && da_matrix_mode() == 2;
-}
+// split matrix mode, fp32 tensors: the two-term fp16 kernel (its tile is 2 x 8 x 16: the geometry is re-derived); otherwise the exact-fp32 kernel
+static bool flow_use_split(int x_bf16) { return !x_bf16 && da_matrix_mode() == 2; }
 static void flow_geom_split(FlowWgP& p, int* nb) {
     p.ntz = (p.D + sp::TZ - 1) / sp::TZ; p.nty = (p.H + sp::TY - 1) / sp::TY; p.ntx = (p.W + sp::TX - 1) / sp::TX;
     p.ntiles = p.N * p.ntz * p.nty * p.ntx;
@@ -578,8 +575,7 @@ static void flow_geom(FlowWgP& p, int N, int D, int H, int W, int* nb) {
     p.N = N; p.D = D; p.H = H; p.W = W;
     p.ntz = (D + TZ - 1) / TZ; p.nty = (H + TY - 1) / TY; p.ntx = (W + TX - 1) / TX;
     p.ntiles = N * p.ntz * p.nty * p.ntx;
-    static const int cap = [] { const char* e = getenv("DA_FLOW_BLOCKS"); const int v = e ? atoi(e) : 0; return v > 0 && v < kFlowBlocks ? v : kFlowBlocks; }();   // A/B: 256 = one workgroup per CU
-    *nb = p.ntiles < cap ? p.ntiles : cap;
+    *nb = p.ntiles < kFlowBlocks ? p.ntiles : kFlowBlocks;
 }
 
 int da_conv3_flow_wgrad(const float* in1, int C1, const float* in2, int C2, const float* dy, float* dw_tio,
@@ -739,12 +735,9 @@ int da_conv3_fewcin_wgrad(const float* in1, int C1, const float* in2, int C2, co
     if (ws_bytes < da_align((size_t)kFlowBlocks * O * sizeof(float)) + da_align((size_t)O * sizeof(float))) return DA_ERR_WS_SMALL;
     if ((unsigned long long)D * H * W * 16ull * 4ull >= 0xFFFFFFF0ull) return DA_ERR_UNSUPPORTED;
     if (!dy_bf16 && (unsigned long long)N * D * H * W * (unsigned long long)Cout * 4ull < 0xFFFFFFF0ull && (Cout == 8 || Cout == 16) && (C2 == 0 || (C1 == 1 && C2 == 1))) {
-        static int off = -1; if (off < 0) { const char* e = getenv("DA_NO_FEWCIN_VALU"); off = (e && atoi(e)) ? 1 : 0; }
-        if (!off) {
-            if (Cin == 1 && Cout == 8) return fewcin_valu_launch<1, 2>(in1, C1, in2, dy, dw_tio, N, D, H, W, ws, st);
-            if (Cin == 1 && Cout == 16) return fewcin_valu_launch<1, 4>(in1, C1, in2, dy, dw_tio, N, D, H, W, ws, st);
-            // (two input channels stay on the matrix form: 8 lanes per voxel leave 8 voxels per wave-wide load -- reg 1 + 1 -> 16: 0.22 ms there, slower here)
-        }
+        if (Cin == 1 && Cout == 8) return fewcin_valu_launch<1, 2>(in1, C1, in2, dy, dw_tio, N, D, H, W, ws, st);
+        if (Cin == 1 && Cout == 16) return fewcin_valu_launch<1, 4>(in1, C1, in2, dy, dw_tio, N, D, H, W, ws, st);
+        // (two input channels stay on the matrix form: 8 lanes per voxel leave 8 voxels per wave-wide load -- reg 1 + 1 -> 16: 0.22 ms there, slower here)
     }
     FlowWgP p;
     p.in1 = nullptr; p.C1 = 0; p.in2 = dy; p.C2 = Cout;                   // "X" = dy

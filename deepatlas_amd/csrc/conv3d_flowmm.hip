@@ -412,7 +412,7 @@ Plan fm_plan(int N, int D, int H, int W) {
 
 // Shapes: split matrix mode, <= 3 output channels, the input channel splits instantiated below, samples below 4 GiB.
 bool da_conv3_flowmm_supported(int C1, int C2, int Cout, int N, int D, int H, int W) {
-    if (da_matrix_mode() != 2 || getenv("DA_NO_FLOWMM")) return false;
+    if (da_matrix_mode() != 2) return false;
     if (Cout < 1 || Cout > 3) return false;
     if (!((C1 == 8 && C2 == 16) || (C1 == 16 && C2 == 16) || (C1 == 16 && C2 == 0) || (C1 == 8 && C2 == 8) || (C1 == 8 && C2 == 0))) return false;
     const long long vox = (long long)D * H * W;

@@ -59,7 +59,7 @@ template <int CK, int NREP, bool MASKED = false, int STATS = 0, bool BF = false,
 __global__ void __launch_bounds__(256, 2) conv3_mfma_fwd_kernel(FwdP p) {
     static_assert(!HB || (BF && !SP), "bf16 activation storage: bf16 matrix mode only");
     static_assert(STATS != 2 || (SP && NREP == 1 && !PRO), "BatchNorm-backward sums: the split mode's one-N-tile data gradient");
-    static_assert(S2F == 0 || MASKED, "fused space-to-depth addressing belongs to the tap-masked (stride-2) variants");
+    static_assert((S2F != 0) == MASKED, "the tap-masked (stride-2) variants and only they address X / dX through the space-to-depth view");
     // PAIR (split mode, one N-tile): two consecutive 8-channel chunks share every 64-byte sector of their input.  Staged one work item apart
     // the second one misses L2 (the launch turns its L2 over in about one item time): FETCH_SIZE 1.8x the algorithmic bytes.  With PAIR the
     // loads of BOTH chunks are issued together during the odd item of a pair; the second chunk's data waits in registers (pre2) through the
@@ -2075,12 +2075,10 @@ static WgPlan wgrad_plan(int N, int D, int H, int W, int C1, int C2, int Cout, b
         static int on = -1; if (on < 0) { const char* e = getenv("DA_WG16"); on = (e && !atoi(e)) ? 0 : 1; }
         const int combos = ((C1 + C2) / 16) * q.ngroups;
         long long s16 = (256 / combos) & ~7ll;               // one workgroup per CU, a multiple of 8 slabs (XCD grouping) ...
-        { static int any = -1; if (any < 0) { const char* e = getenv("DA_WG16_ANY"); any = (e && !atoi(e)) ? 0 : 1; }
-          if (any && s16 * combos < 224) s16 = 256 / combos; }  // ... or any slab count that fills the chip (tile_walk then walks one list): 192 -> 64 0.65 -> 0.60 ms, 96 -> 32 unchanged
+        if (s16 * combos < 224) s16 = 256 / combos;          // ... or any slab count that fills the chip (tile_walk then walks one list): 192 -> 64 0.65 -> 0.60 ms, 96 -> 32 unchanged
         if (on && s16 >= 1 && s16 * combos >= 224 && s16 <= cap && s16 <= q.ntiles) { q.w16 = 1; q.nchunks = (C1 + C2) / 16; slabs = s16; }
         // the ring form (conv3d_wgring.h): fp32 tensors in split mode only; contiguous tile ranges per slab, so no multiple-of-8 rounding below
-        static int ring = -1; if (ring < 0) { const char* e = getenv("DA_WG16R"); ring = (e && !atoi(e)) ? 0 : 1; }
-        if (q.w16 && ring && allow_ring) {
+        if (q.w16 && allow_ring) {
             q.w16 = 2;
             if (slabs > q.ntiles) slabs = q.ntiles;
             q.tps = (int)da_cdiv(q.ntiles, slabs);
@@ -2218,8 +2216,7 @@ int da_conv3_mfma_fwd(const float* in1, int C1, const float* in2, int C2, const 
     // tensor, one N-tile (paired staging) for the second -- stage it twice and write each output tensor from its own launch.
     struct PpReset { ~PpReset() { if (g_pp.mode == 1) g_pp.mode = 0; } } pp_reset;      // a handed-over pack serves exactly one call
     if (g_pp.mode && g_pp.w != w_tio) g_pp.mode = 0;                                      // (it belongs to other weights: a call in between went elsewhere)
-    static int no2 = -1; if (no2 < 0) { const char* e = getenv("DA_NO_DGRAD_SPLIT_LAUNCH"); no2 = (e && atoi(e)) ? 1 : 0; }
-    if (!no2 && da_matrix_mode() == 2 && w_is_flipped_tr && s2d_cin == 0 && !stats_partial && !pro && Cs2 > 0 && Cs1 == 32 && Cs2 == 16 && Cout == 48 &&
+    if (da_matrix_mode() == 2 && w_is_flipped_tr && s2d_cin == 0 && !stats_partial && !pro && Cs2 > 0 && Cs1 == 32 && Cs2 == 16 && Cout == 48 &&
         pick_ck(C1, C2) != 0) {
         int rc = conv3_mfma_fwd_impl(in1, C1, in2, C2, w_tio, 1, bias, out1, 32, nullptr, 0, N, D, H, W, 32, stride, slope, ws, ws_bytes, st, 0, nullptr, nullptr,
                                      nullptr, nullptr, 0, Cout, false);
@@ -2241,6 +2238,7 @@ static int conv3_mfma_fwd_impl(const float* in1, int C1, const float* in2, int C
     int CK = pick_ck(C1, C2);
     if (!CK) return DA_ERR_UNSUPPORTED;
     if (pro && (s2d_cin > 0 || w_is_flipped_tr || Cin > kProMaxC)) return DA_ERR_UNSUPPORTED;
+    if (s2d_cin > 0 && !s2f) return DA_ERR_UNSUPPORTED;          // (the sparse-tap route reads / writes through the space-to-depth view only)
     const bool split = da_matrix_mode() == 2 && s2d_cin == 0;      // (the sparse-tap stride-2 route keeps the native fp32 kernels)
     const bool bf = da_matrix_mode() == 1;
     if (split) CK = 8;
@@ -2257,9 +2255,8 @@ static int conv3_mfma_fwd_impl(const float* in1, int C1, const float* in2, int C
     {   // Coarse levels have few tiles (30 per volume at 20x24x20, 180 at 40x48x40): the persistent grid then runs one or two
         // uneven rounds.  Makespan model: a workgroup walks ceil(tiles / nblk) tiles, each costing ~NREP (one N-tile per
         // workgroup is ~8 % less efficient per FLOP but quadruples / doubles the number of work items); take the cheaper.
-        static int adapt = -1; if (adapt < 0) { const char* e = getenv("DA_NREP_ADAPT"); adapt = e ? atoi(e) : 1; }
         const long long tiles = (long long)N * ((D + 3) / 4) * ((H + TY - 1) / TY) * ((W + TX - 1) / TX);
-        if (adapt && s2d_cin == 0 && NREP > 1 && !want_bst) {
+        if (s2d_cin == 0 && NREP > 1 && !want_bst) {
             auto cost = [&](int nrep) {
                 const int g = (NT + nrep - 1) / nrep;
                 long long nb = 512 / g; if (nb < 1) nb = 1; if (nb > tiles) nb = tiles;
@@ -2317,16 +2314,12 @@ static int conv3_mfma_fwd_impl(const float* in1, int C1, const float* in2, int C
     {   // one resident round: 2 workgroups per CU x 256 CUs, split over the cout groups
         // (a third workgroup per CU for the split kernels -- 168 VGPRs, 3 x 52 KB of LDS -- was measured and dropped: in split mode the
         // matrix pipe is already busy ~100 % of the shader cycles and the clock is set by the power limit)
-        static int nres = -1; if (nres < 0) { const char* e = getenv("DA_FWD_BLOCKS"); nres = e ? atoi(e) : 512; }
-        int nblk = nres / gy; if (nblk < 1) nblk = 1; if (nblk > p.ntiles) nblk = p.ntiles;
+        int nblk = 512 / gy; if (nblk < 1) nblk = 1; if (nblk > p.ntiles) nblk = p.ntiles;
         if (nblk >= 8) nblk &= ~7;                           // multiple of 8: blockIdx.x % 8 is then the XCD (tile_walk)
         p.nblocks = nblk;
     }
     p.s2in = S2dSrc{0, 0, 0, 0}; p.s2out = S2dSrc{0, 0, 0, 0};
-    if (s2f && s2d_cin > 0) {
-        if (s2f->fuse_in && !w_is_flipped_tr) p.s2in = S2dSrc{s2d_cin, s2f->D0, s2f->H0, s2f->W0};
-        if (s2f->fuse_out && w_is_flipped_tr) p.s2out = S2dSrc{s2d_cin, s2f->D0, s2f->H0, s2f->W0};
-    }
+    if (s2d_cin > 0) (w_is_flipped_tr ? p.s2out : p.s2in) = S2dSrc{s2d_cin, s2f->D0, s2f->H0, s2f->W0};
     p.stats_partial = stats_partial;
     if (stats_nparts) *stats_nparts = 0;
     p.ps1 = p.pt1 = p.ps2 = p.pt2 = nullptr; p.pslope1 = p.pslope2 = -1.f;
@@ -2341,13 +2334,12 @@ static int conv3_mfma_fwd_impl(const float* in1, int C1, const float* in2, int C
     if (split) {
         if (stats_partial && stats_nparts) *stats_nparts = p.nblocks;
         // paired staging (one sector fetch per two chunks): one N-tile, an even number of 8-channel chunks that pair up inside in1 / in2
-        static int nopair = -1; if (nopair < 0) { const char* e = getenv("DA_NO_PAIR"); nopair = (e && atoi(e)) ? 1 : 0; }
         if (want_bst) {                                      // (da_conv3d_k3_dgrad_bst checked the shape: one output tensor of <= 32 channels, no prologue)
             if (!(NREP == 1 && !pro && Cs2 == 0 && gy <= 2)) return DA_ERR_UNSUPPORTED;
             p.bst_y = g_bst.y; p.bst_par = g_bst.par; p.bst_slope = g_bst.slope;
             return launch_fwd_mfma<8, 1, false, 2, true, false, true>(p, gy, st);      // (unpaired staging: with the pair's second parked chunk the eight y quads of the epilogue spill)
         }
-        if (!nopair && NREP == 1 && !pro && C1 % 16 == 0 && C2 % 16 == 0)
+        if (NREP == 1 && !pro && C1 % 16 == 0 && C2 % 16 == 0)
             return stats_partial ? launch_fwd_mfma<8, 1, false, true, true, false, true, 0, true>(p, gy, st)
                                  : launch_fwd_mfma<8, 1, false, false, true, false, true, 0, true>(p, gy, st);
 #define DA_SP_CASE(nr) if (NREP == nr) return stats_partial ? (pro ? launch_fwd_mfma<8, nr, false, true, true, true, true>(p, gy, st) : launch_fwd_mfma<8, nr, false, true, true, false, true>(p, gy, st)) \
@@ -2370,9 +2362,9 @@ static int conv3_mfma_fwd_impl(const float* in1, int C1, const float* in2, int C
         return DA_ERR_UNSUPPORTED;
     }
     if (p.maskmode != 0) {
-        const int s2f = p.s2in.cin > 0 ? 1 : (p.s2out.cin > 0 ? 2 : 0);
-#define DA_M_CASE(nr, f) if (NREP == nr && s2f == f) return hb ? launch_fwd_mfma<16, nr, true, false, true, false, false, f, false, true>(p, gy, st) : bf ? launch_fwd_mfma<16, nr, true, false, true, false, false, f>(p, gy, st) : launch_fwd_mfma<16, nr, true, false, false, false, false, f>(p, gy, st)
-        DA_M_CASE(1, 0); DA_M_CASE(1, 1); DA_M_CASE(1, 2); DA_M_CASE(2, 0); DA_M_CASE(2, 1); DA_M_CASE(2, 2);
+        const int view = p.maskmode;                         // 1: the forward stages X through the view, 2: the data gradient stores dX through it
+#define DA_M_CASE(nr, f) if (NREP == nr && view == f) return hb ? launch_fwd_mfma<16, nr, true, false, true, false, false, f, false, true>(p, gy, st) : bf ? launch_fwd_mfma<16, nr, true, false, true, false, false, f>(p, gy, st) : launch_fwd_mfma<16, nr, true, false, false, false, false, f>(p, gy, st)
+        DA_M_CASE(1, 1); DA_M_CASE(1, 2); DA_M_CASE(2, 1); DA_M_CASE(2, 2);
 #undef DA_M_CASE
         return DA_ERR_UNSUPPORTED;
     }
@@ -2390,11 +2382,11 @@ static int conv3_mfma_fwd_impl(const float* in1, int C1, const float* in2, int C
 //   0  fp32 operands on v_mfma_f32_16x16x4_f32 (an fmaf chain)
 //   1  operands ROUNDED to bf16 (BASELINE configs[4]'s precision; not fp32-accurate)
 //   2  fp32 operands scaled per tile and split into two fp16 terms, three partial products per multiply on the fp16 pipe, fp32 accumulate
-static int g_matrix_mode = -1;          // -1: not decided yet (env DA_MATRIX_MODE=0|1|2, or the older DA_MATRIX_BF16=1, for tools)
+static int g_matrix_mode = -1;          // -1: not decided yet (env DA_MATRIX_MODE=0|1|2, for tools)
 int da_matrix_mode() {
     if (g_matrix_mode < 0) {
-        const char* m = getenv("DA_MATRIX_MODE"); const char* e = getenv("DA_MATRIX_BF16");
-        g_matrix_mode = m ? atoi(m) : ((e && atoi(e) != 0) ? 1 : 0);
+        const char* m = getenv("DA_MATRIX_MODE");
+        g_matrix_mode = m ? atoi(m) : 0;
         if (g_matrix_mode < 0 || g_matrix_mode > 2) g_matrix_mode = 0;
     }
     return g_matrix_mode;
@@ -2434,8 +2426,7 @@ template <int CL, int CR = CL>
 static int thin_few_inputs(ThinP& p, const float* w_src, float* wq, hipStream_t st) {
     if (p.Cout <= 8) return thin_launch<CL, 8, 4, 8, CR>(p, w_src, wq, st);
     if (p.Cout <= 16) return thin_launch<CL, 16, 4, 16, CR>(p, w_src, wq, st);
-    static int split = -1; if (split < 0) { const char* e = getenv("DA_NO_THIN_SPLIT"); split = (e && atoi(e)) ? 0 : 1; }
-    if (split && p.Cs2 > 0 && p.Cs1 <= 16 && p.Cs2 <= 16 && p.Cs1 % 4 == 0 && p.Cs2 % 4 == 0) {
+    if (p.Cs2 > 0 && p.Cs1 <= 16 && p.Cs2 <= 16 && p.Cs1 % 4 == 0 && p.Cs2 % 4 == 0) {
         // split output (data gradient of a concat conv, e.g. the flow conv's 3 -> 16 + 8): one launch per output tensor, each with few
         // enough outputs per thread for scalar-cache weights; the (tiny) input is simply read twice
         ThinP a = p, b = p;
@@ -2579,12 +2570,10 @@ int da_conv3_mfma_wgrad(const float* in1, int C1, const float* in2, int C2, cons
     if (hb && (da_matrix_mode() != 1 || pick_ck(C1, C2) == 0 || Cout % 4 != 0 || Cout <= 4 || smallcin_ok(C1, C2, Cout, stride) ||
                da_conv3_fewcin_wgrad_supported(C1, C2, Cout, stride))) return DA_ERR_UNSUPPORTED;
     if (pro && (stride != 1 || s2d_cin > 0 || C1 + C2 > kProMaxC || pick_ck(C1, C2) == 0 || Cout % 4 != 0 || Cout <= 4)) return DA_ERR_UNSUPPORTED;
+    if (s2d_cin > 0 && !s2f) return DA_ERR_UNSUPPORTED;
     if (!pro && s2d_cin == 0 && da_conv3_fewcin_wgrad_supported(C1, C2, Cout, stride)) {
-        static int off = -1; if (off < 0) { const char* e = getenv("DA_NO_FLOW_WGRAD"); off = (e && atoi(e)) ? 1 : 0; }
-        if (!off) {
-            const int rc = da_conv3_fewcin_wgrad(in1, C1, in2, C2, dy, dw_tio, N, D, H, W, Cout, ws, ws_bytes, st);
-            if (rc != DA_ERR_UNSUPPORTED && rc != DA_ERR_WS_SMALL) return rc;
-        }
+        const int rc = da_conv3_fewcin_wgrad(in1, C1, in2, C2, dy, dw_tio, N, D, H, W, Cout, ws, ws_bytes, st);
+        if (rc != DA_ERR_UNSUPPORTED && rc != DA_ERR_WS_SMALL) return rc;
     }
     if (smallcin_ok(C1, C2, Cout, stride)) {
         const int Cin = C1 + C2, O = 27 * Cin * Cout;
@@ -2604,11 +2593,8 @@ int da_conv3_mfma_wgrad(const float* in1, int C1, const float* in2, int C2, cons
         return 0;
     }
     if (s2d_cin == 0 && !pro && da_conv3_flow_wgrad_supported(C1, C2, Cout, stride) && ws_bytes >= da_conv3_flow_wgrad_ws_bytes(C1 + C2, Cout)) {
-        static int off = -1; if (off < 0) { const char* e = getenv("DA_NO_FLOW_WGRAD"); off = (e && atoi(e)) ? 1 : 0; }
-        if (!off) {
-            const int rc = da_conv3_flow_wgrad(in1, C1, in2, C2, dy, dw_tio, N, D, H, W, Cout, ws, ws_bytes, st);
-            if (rc != DA_ERR_UNSUPPORTED) return rc;
-        }
+        const int rc = da_conv3_flow_wgrad(in1, C1, in2, C2, dy, dw_tio, N, D, H, W, Cout, ws, ws_bytes, st);
+        if (rc != DA_ERR_UNSUPPORTED) return rc;
     }
     if (stride == 1 && s2d_cin == 0 && Cout <= 4 && C1 + C2 <= 32 && (unsigned long long)D * H * W * (C1 > C2 ? C1 : C2) * 4ull < 0xFFFFFFF0ull) {
         // Very few OUTPUT channels (the 24 -> 3 flow conv, voxel_morph.py:57): swap the operands.  dW[tap][ci][co] =
@@ -2634,12 +2620,11 @@ int da_conv3_mfma_wgrad(const float* in1, int C1, const float* in2, int C2, cons
         return 0;
     }
     const bool split = da_matrix_mode() == 2 && s2d_cin == 0 && Cout % 4 == 0 && pick_ck(C1, C2) != 0;
-    // bf16 matrix mode: the row-owner kernel with one operand plane (K = 32 MFMAs, a sixth of the split mode's matrix work); DA_BF16_WGRAD_V1=1
-    // keeps the older tap-owner kernel (v_mfma_f32_16x16x16_bf16) for A/B
-    static int bfv1 = -1; if (bfv1 < 0) { const char* e = getenv("DA_BF16_WGRAD_V1"); bfv1 = (e && atoi(e)) ? 1 : 0; }
+    // bf16 activation storage: the row-owner kernel with one operand plane (K = 32 MFMAs, a sixth of the split mode's matrix work) instead of
+    // the tap-owner kernel (v_mfma_f32_16x16x16_bf16)
     // (measured, 2 x 160 x 192 x 160: bf16 storage 48 -> 16 1.23 -> 1.09 ms, 16 -> 16 0.42 -> 0.38; NOT for more than one cout tile -- 96 -> 32: 0.44 ->
     // 0.70 ms, the kernel re-stages x per 16-cout group -- and not with fp32 tensors, 1.21 -> 1.94 ms: there the staging conversions dominate)
-    const bool rows1 = !bfv1 && hb && da_matrix_mode() == 1 && s2d_cin == 0 && Cout % 4 == 0 && Cout <= 16 && pick_ck(C1, C2) != 0;
+    const bool rows1 = hb && da_matrix_mode() == 1 && s2d_cin == 0 && Cout % 4 == 0 && Cout <= 16 && pick_ck(C1, C2) != 0;
     const WgPlan q = wgrad_plan(N, D, H, W, C1, C2, Cout, split || rows1, split || rows1, (split && !hb) || rows1);
     if (!q.CK) return DA_ERR_UNSUPPORTED;
     const bool bf = da_matrix_bf16();      // (Cout % 4 != 0 keeps the exact kernel: its dY staging is scalar)
@@ -2647,7 +2632,7 @@ int da_conv3_mfma_wgrad(const float* in1, int C1, const float* in2, int C2, cons
     if (ws_bytes < q.partial_bytes + ((split || rows1) ? wg_tile_table_bytes(N, D, H, W) : 0)) return DA_ERR_WS_SMALL;
     WgP p;
     p.tiles = nullptr;
-    p.s2in = (s2f && s2d_cin > 0 && s2f->fuse_in) ? S2dSrc{s2d_cin, s2f->D0, s2f->H0, s2f->W0} : S2dSrc{0, 0, 0, 0};
+    p.s2in = s2d_cin > 0 ? S2dSrc{s2d_cin, s2f->D0, s2f->H0, s2f->W0} : S2dSrc{0, 0, 0, 0};
     { static int abl = -1; if (abl < 0) { const char* e = getenv("DA_WG_ABLATE"); abl = e ? atoi(e) : 0; } p.ablate = abl; }
     if (split || rows1) {
         int4* tiles = reinterpret_cast<int4*>(reinterpret_cast<char*>(ws) + q.partial_bytes);

@@ -417,8 +417,7 @@ struct MarchGeom { int ntx, nty, nch, ZC; bool ok; };
 // writes the marching form's five backward terms into `sums` where the separable form keeps raw window sums, and the workspace is sized per form.
 // (Both walks address at most (D + F)(H + F)(W + F) elements per sample with 32-bit byte offsets.)  The tiling below is per walk direction.
 static bool lncc_march_ok(int D, int H, int W, int F, int dil, int stride) {
-    static const int off = [] { const char* e = getenv("DA_LNCC_MARCH"); return (e && e[0] == '0') ? 1 : 0; }();
-    return !off && dil == 1 && stride == 1 && (F == 9 || F == 5) && (long long)(D + F) * (H + F) * (W + F) * 4 < (1ll << 31);
+    return dil == 1 && stride == 1 && (F == 9 || F == 5) && (long long)(D + F) * (H + F) * (W + F) * 4 < (1ll << 31);
 }
 static MarchGeom lncc_march_geom(int N, int Lz, int Ly, int Lx, int F, bool ok) {
     MarchGeom g{};

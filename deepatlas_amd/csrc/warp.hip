@@ -939,8 +939,7 @@ extern "C" int da_warp_fwd(const float* src, const float* disp, float* deform, f
     if (!src || !disp || !out || N <= 0 || D < 2 || H < 2 || W < 2 || C <= 0) return DA_ERR_BADARG;
     int lpv; const bool v4 = vec_ok(C, &lpv);
     const long long total = (long long)N * D * H * W * lpv;
-    static const bool grouped = [] { const char* e = getenv("DA_WARP_GROUPED"); return !(e && atoi(e) == 0); }();      // A/B: 0 = the per-lane-group kernels
-    if (v4 && grouped && lpv >= 2 && gather_grouped_ok(D, H, W, C, lpv) && N <= 65535) {
+    if (v4 && lpv >= 2 && gather_grouped_ok(D, H, W, C, lpv) && N <= 65535) {
         int nb = (int)da_cdiv((long long)D * H * W, 512); if (nb > 4096) nb = 4096; if (nb < 1) nb = 1;
         hipLaunchKernelGGL(warp_fwd_grouped_kernel, dim3(nb, N), dim3(256), (size_t)4 * 64 * lpv * sizeof(float4), da_stream(stream), src, disp, deform, out, D, H, W, C, lpv);
     } else if (v4) hipLaunchKernelGGL((warp_fwd_kernel<4>), dim3(da_grid(total, 256)), dim3(256), 0, da_stream(stream), src, disp, deform, out, N, D, H, W, C, lpv);
@@ -1060,8 +1059,7 @@ extern "C" int da_warp_dice_fwd(const float* src, const float* disp, const void*
     const long long V = (long long)D * H * W;
     const int slots = 256 / lpv;
     int nblocks = (int)da_cdiv(V, (long long)slots * 4); if (nblocks > kLwdBlocks) nblocks = kLwdBlocks; if (nblocks < 1) nblocks = 1;
-    static const bool grouped = [] { const char* e = getenv("DA_WARP_GROUPED"); return !(e && atoi(e) == 0); }();
-    if (grouped && lpv >= 2 && gather_grouped_ok(D, H, W, C, lpv))
+    if (lpv >= 2 && gather_grouped_ok(D, H, W, C, lpv))
         hipLaunchKernelGGL(warp_dice_grouped_kernel, dim3(nblocks, N), dim3(256), (size_t)3 * slots * C * sizeof(float), st,
                            src, disp, lab_t, lab_t_bytes, D, H, W, C, lpv, partial);
     else
@@ -1090,24 +1088,21 @@ extern "C" int da_warp_adjoint_labels(const void* lab_t, int lab_t_bytes, const 
     hipError_t e = hipMemsetAsync(B, 0, (size_t)nvox * C * sizeof(float), st);
     if (e != hipSuccess) return (int)e;
     if (A) { e = hipMemsetAsync(A, 0, (size_t)nvox * sizeof(float), st); if (e != hipSuccess) return (int)e; }
-    static const int use_box = [] { const char* e = getenv("DA_ADJ_BOX"); return (e && e[0] == '0') ? 0 : 1; }();
-    if (use_box) {
-        constexpr int BX = 32, BY = 8, BZ = 4, M = 2, K = 3;
-        constexpr size_t shm = (size_t)K * (BX + 2 * M + 1) * (BY + 2 * M + 1) * (BZ + 2 * M + 1) * sizeof(float);
-        auto kern = warp_adjoint_labels_box_kernel<BX, BY, BZ, M, K>;
-        static bool attr_set = false;
-        if (!attr_set) {
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-            if (e != hipSuccess) return (int)e;
-            attr_set = true;
-        }
-        const int nbx = (W + BX - 1) / BX, nby = (H + BY - 1) / BY, nbz = (D + BZ - 1) / BZ;
-        const long long nb = (long long)nbx * nby * nbz * N;
-        if (nb < (1ll << 31)) {
-            hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(256), shm, st, lab_t, lab_t_bytes, disp, A, B, N, D, H, W, C, nbx, nby, nbz);
-            DA_LAUNCH_CHECK();
-            return 0;
-        }
+    constexpr int BX = 32, BY = 8, BZ = 4, M = 2, K = 3;
+    constexpr size_t shm = (size_t)K * (BX + 2 * M + 1) * (BY + 2 * M + 1) * (BZ + 2 * M + 1) * sizeof(float);
+    auto kern = warp_adjoint_labels_box_kernel<BX, BY, BZ, M, K>;
+    static bool attr_set = false;
+    if (!attr_set) {
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+        if (e != hipSuccess) return (int)e;
+        attr_set = true;
+    }
+    const int nbx = (W + BX - 1) / BX, nby = (H + BY - 1) / BY, nbz = (D + BZ - 1) / BZ;
+    const long long nb = (long long)nbx * nby * nbz * N;
+    if (nb < (1ll << 31)) {                    // (larger grids: the plain kernel below)
+        hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(256), shm, st, lab_t, lab_t_bytes, disp, A, B, N, D, H, W, C, nbx, nby, nbz);
+        DA_LAUNCH_CHECK();
+        return 0;
     }
     hipLaunchKernelGGL(warp_adjoint_labels_kernel, dim3(da_grid(nvox, 256)), dim3(256), 0, st, lab_t, lab_t_bytes, disp, A, B, N, D, H, W, C);
     DA_LAUNCH_CHECK();
@@ -1120,7 +1115,7 @@ extern "C" int da_seg_anat_dlogits(const float* prob, const void* lab_m, int lab
     if (!prob || !B || !dlogits || !coef_anat || !dloss_anat || N <= 0 || V <= 0 || C <= 0) return DA_ERR_BADARG;
     if (coef_sup && (!lab_m || !dloss_sup || (lab_m_bytes != 1 && lab_m_bytes != 8))) return DA_ERR_BADARG;
     int lpv; if (!vec_ok(C, &lpv)) return DA_ERR_UNSUPPORTED;
-    if (C == 32 && !getenv("DA_DLOGITS_TILE")) {
+    if (C == 32) {
         const long long nb = ((V + 255) / 256) * N;
         hipLaunchKernelGGL((seg_anat_dlogits_lane_kernel<32>), dim3(da_grid(nb * 256, 256)), dim3(256), 0, da_stream(stream), prob, lab_m, lab_m_bytes, A, B, dlogits,
                            coef_sup, coef_anat, dloss_sup, dloss_anat, N, V);

@@ -11,7 +11,6 @@ compare against:
   Sm = None (moving image without a manual segmentation): the reg phase warps softmax(S(Im)).detach() (segmentation net in eval
   mode under no_grad: no state change) instead of onehot(Sm), and the seg phase drops its supervised term.
 """
-import os
 
 import torch
 
@@ -70,15 +69,15 @@ class DeepAtlasJointStep:
     # The segmentation net's FORWARD pass does not depend on the registration phase (with a manual segmentation of the moving image: the registration phase warps
     # one-hot(seg_m), and the deformation is only needed by the segmentation phase's LOSS).  It is issued first, on its own stream, and runs beside the registration
     # phase -- a chain of small latency-bound kernels that leaves most of the GPU idle -- instead of after it.  Same kernels, same order inside either network:
-    # results are those of the sequential step.  DA_JOINT_OVERLAP=0 (or overlap_phases=False) runs the phases one after the other.
-    overlap_phases = os.environ.get('DA_JOINT_OVERLAP', '1') == '1'
+    # results are those of the sequential step.  overlap_phases = False runs the phases one after the other.
+    overlap_phases = True
     _phase_stream = None
     _ev_disp = None
 
     def _seg_forward_ahead(self, im_m):
         main = torch.cuda.current_stream()
         if self._phase_stream is None:
-            self._phase_stream = torch.cuda.Stream(priority=int(os.environ.get('DA_JOINT_PS_PRIO', '-1')))      # high priority: the segmentation phase is the step's long chain (-0.14 ms; 0 = normal)
+            self._phase_stream = torch.cuda.Stream(priority=-1)      # high priority: the segmentation phase is the step's long chain (-0.14 ms against 0)
         ps = self._phase_stream
         ps.wait_stream(main)                       # (the previous step's segmentation update, the input)
         with torch.cuda.stream(ps):

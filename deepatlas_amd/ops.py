@@ -54,9 +54,8 @@ def set_activation_storage(mode):
     if mode not in ACT_STORAGE_MODES:
         raise ValueError("activation storage must be one of %r, got %r" % (ACT_STORAGE_MODES, mode))
     prev, ACT_STORAGE = ACT_STORAGE, mode
-    if _LAZY_UP_ENV is None:
-        global LAZY_BN_UPSAMPLER
-        LAZY_BN_UPSAMPLER = mode == 'bf16'
+    global LAZY_BN_UPSAMPLER
+    LAZY_BN_UPSAMPLER = mode == 'bf16'
     return prev
 
 
@@ -245,7 +244,7 @@ def init_into(param, init_fn):
     weights are strided views of FlatAdam's tap-major buckets once an optimiser exists; a random fill of the view itself would walk
     memory order and hand the same random stream to different elements than the reference's contiguous parameter gets
     (lib/network_factory/unets.py:61-67): same seed, different weights.  Drawing into a contiguous temporary and copying keeps
-    seed-for-seed reproducibility against the reference and against DA_NO_NATIVE_TIO=1."""
+    seed-for-seed reproducibility against the reference and against NATIVE_TIO = False."""
     with torch.no_grad():
         if param.data.is_contiguous():
             init_fn(param.data)
@@ -266,16 +265,11 @@ def enable_async_wgrad(flag=True):
     ASYNC_WGRAD = bool(flag)
 
 
-LAST_WGRAD_ON_MAIN = os.environ.get('DA_LAST_WGRAD_ON_MAIN', '1') == '1'      # see Conv3dFn.backward
-LAST_WGRAD_ON_MAIN_BN = os.environ.get('DA_LAST_WGRAD_ON_MAIN_BN', '0') == '1'
-_SIDE_PRIO = int(os.environ.get('DA_SIDE_PRIO', '0'))      # HIP stream priority of the side stream (lower number = higher priority; out-of-range values clamp)
-
-
 def side_stream():
     """The second HIP stream; every caller is about to queue work on it."""
     global _side_stream, _side_dirty
     if _side_stream is None:
-        _side_stream = torch.cuda.Stream(priority=_SIDE_PRIO)
+        _side_stream = torch.cuda.Stream(priority=0)
     _side_dirty = True
     return _side_stream
 
@@ -311,9 +305,9 @@ def _serialize_matrix_kernels(flops, voxels):
         torch.cuda.current_stream().wait_stream(_side_stream)
 
 
-_SERIALIZE_MIN_FLOPS = float(os.environ.get('DA_MFMA_SERIALIZE_MIN_FLOPS', '3e11'))      # 'inf' disables the rule
-_SERIALIZE_MAX_RATIO = float(os.environ.get('DA_MFMA_SERIALIZE_MAX_RATIO', '0.4'))
-_SERIALIZE_MIN_VOXELS = float(os.environ.get('DA_MFMA_SERIALIZE_MIN_VOXELS', '4e6'))
+_SERIALIZE_MIN_FLOPS = 3e11
+_SERIALIZE_MAX_RATIO = 0.4
+_SERIALIZE_MIN_VOXELS = 4e6
 
 
 def _run_on_side(fn, keep_alive):
@@ -402,8 +396,8 @@ def register_flat_params(flat_p):
 # kept per (weights, direction, shape): filled in-chain the first time, and from then on re-filled for ALL layers of an optimiser right after its
 # step -- on the side stream, beside the start of the next forward pass -- with one event per entry that the consuming call waits for.
 # An entry is valid while its stamp (weights epoch, version counters: the one of weight_tio) matches and the weights' base tensor is alive; it holds
-# a weak reference to that base only.  Not inside a HIP-graph capture.  DA_NO_PACK_CACHE=1 switches it off.
-PACK_CACHE = os.environ.get('DA_NO_PACK_CACHE') != '1'
+# a weak reference to that base only.  Not inside a HIP-graph capture.  PACK_CACHE = False (tests) switches it off.
+PACK_CACHE = True
 _pack_entries = {}
 
 
@@ -536,7 +530,7 @@ _TIO_BACK = {'oik': 'da_w_tio_to_oik', 'iok': 'da_w_tio_to_iok', 'iok_flip': 'da
 # state_dict keys, shapes and values are the reference's, Adam is elementwise (layout-agnostic), and the per-step layout conversions
 # (one launch per weight each way) do not exist.  A parameter's kind comes from tag_conv_layouts(); a parameter without an optimiser
 # (or with another one) stays contiguous in the reference layout and takes the conversion kernels + cache below.
-NATIVE_TIO = os.environ.get('DA_NO_NATIVE_TIO') != '1'
+NATIVE_TIO = True         # (tests: False keeps every conv weight contiguous in the reference layout)
 
 
 def tag_conv_layouts(module):
@@ -598,7 +592,7 @@ class WgradTarget(object):
         self.kind, self.like, self.direct, self.view, self.tmp = kind, w_tio, False, None, None
         if self.gw is not None:
             self.view = _tio_native(self.gw, kind)
-            if self.view is not None and getattr(param, '_da_gz', False) and os.environ.get('DA_NO_DIRECT_WGRAD') != '1':
+            if self.view is not None and getattr(param, '_da_gz', False):
                 param._da_gz = False
                 self.direct = True
 
@@ -642,7 +636,7 @@ def weight_tio(weight, kind):
         return nv
     capturing = torch.cuda.is_current_stream_capturing()
     stamp = None
-    if not capturing and os.environ.get('DA_NO_WEIGHT_CACHE') != '1':
+    if not capturing:
         stamp = (_weights_epoch, weight._version, weight.data_ptr(), kind,
                  tuple(r()._version for r in _flat_param_buckets if r() is not None))
         ent = getattr(weight, '_da_tio', None)
@@ -681,13 +675,12 @@ def grad_from_tio(dw_tio, kind, shape, acc=None):
 # (tests/test_gpu_nets.py::test_lazy_batchnorm_matches_materialised_activations).
 # Measured at 160x192x160, batch 2.  In the HBM-bound head kernels the prologue is free; in the MFMA-bound 3x3x3
 # kernels its 4 VALU operations per staged element are not: 16 -> 16 forward 1.17 -> 1.20 ms, weight gradient 1.22 -> 1.29 ms; 48 -> 16
-# forward 3.26 -> 3.40 ms, weight gradient 3.69 -> 3.93 ms.  Conv -> conv and conv -> head links (on by default, DA_LAZY_BN=0 turns them
-# off): 39.15 -> 38.6 ms/step, and the activated tensors of those links are never allocated.  The up-sampler -> concat-conv link
-# (DA_LAZY_BN_UPSAMPLER=1; off by default) saves another 0.2 ms/step but moves the bench's roofline call onto the prologue variant of
-# the 48 -> 16 forward (0.757 instead of 0.778 of the fp32 matrix peak for the same algorithmic FLOPs).
-LAZY_BN = os.environ.get('DA_LAZY_BN', '1') != '0'
-_LAZY_UP_ENV = os.environ.get('DA_LAZY_BN_UPSAMPLER')          # '1' / '0' force the up-sampler link on / off; unset: on with bf16 activation storage
-LAZY_BN_UPSAMPLER = _LAZY_UP_ENV == '1'                         # (bf16 storage: the prologue is cheaper there -- seg step 13.04 -> 12.61 ms; fp32: 27.70 -> 27.70 - 27.78)
+# forward 3.26 -> 3.40 ms, weight gradient 3.69 -> 3.93 ms.  Conv -> conv and conv -> head links (LAZY_BN; tests turn it off):
+# 39.15 -> 38.6 ms/step, and the activated tensors of those links are never allocated.  The up-sampler -> concat-conv link
+# (LAZY_BN_UPSAMPLER; set_activation_storage turns it on with bf16 storage only) saves another 0.2 ms/step but moves the bench's
+# roofline call onto the prologue variant of the 48 -> 16 forward (0.757 instead of 0.778 of the fp32 matrix peak for the same algorithmic FLOPs).
+LAZY_BN = True
+LAZY_BN_UPSAMPLER = False       # (bf16 storage: the prologue is cheaper there -- seg step 13.04 -> 12.61 ms; fp32: 27.70 -> 27.70 - 27.78)
 
 
 class LazyAct(object):
@@ -881,7 +874,7 @@ class Conv3dK3Fn(Function):
                 db = None
             # a layer whose inputs want no gradient is the net's first: nothing follows it on the main chain, while the side stream still has the weight
             # gradients of the layers before it queued up -- its own weight gradient runs on the main stream (reg step: the side stream's backlog was the step's tail)
-            on_main = LAST_WGRAD_ON_MAIN and dx1 is None and dx2 is None
+            on_main = dx1 is None and dx2 is None
             side = torch.cuda.current_stream() if on_main else side_stream()
             if not on_main:
                 side.wait_stream(torch.cuda.current_stream())
@@ -913,7 +906,7 @@ class Conv3dK3Fn(Function):
 def upconv_supported(C1, C2, Cout):
     """Can `conv3x3x3(F.interpolate(cat(x1, x2), scale 2, nearest))` run with the up-sampling folded in (conv3d_up2.hip)?  Channel counts
     as da_upconv3d_k3_supported documents; only in split matrix mode (the kernels' arithmetic)."""
-    return bool(nat.lib().da_upconv3d_k3_supported(int(C1), int(C2), int(Cout))) and os.environ.get('DA_NO_UPCONV') != '1'
+    return bool(nat.lib().da_upconv3d_k3_supported(int(C1), int(C2), int(Cout)))
 
 
 class Conv1x1Fn(Function):
@@ -1157,17 +1150,13 @@ def _bn_forward(a, gamma, beta, running_mean, running_var, training, momentum, e
 # (_bn_backward of the layer whose output that gradient belongs to) pops its entry; FlatAdam.zero_grad / step drop whatever was never consumed.
 _bwd_stats = {}
 # one-input layers whose data gradient carries the producer's sums: <= 16 input channels.  The entry also takes 32 (two N-tiles, one per workgroup), measured
-# slower in the step: 20.46 - 20.56 -> 20.59 - 20.67 ms (DA_DGRAD_BST_MAXC=32)
-_DGRAD_BST_MAXC = int(os.environ.get('DA_DGRAD_BST_MAXC', '16'))
-FUSE_BN_BWD_STATS = os.environ.get('DA_NO_BN_BWD_FUSE') != '1'
-_DGRAD_BST_CONCAT = os.environ.get('DA_NO_DGRAD_BST_CONCAT') != '1'      # the 32 + 16 concat layer's data gradient with the producer's sums (only reached with DA_LAZY_BN_UPSAMPLER=1)
+# slower in the step: 20.46 - 20.56 -> 20.59 - 20.67 ms.  The 32 + 16 concat layer's data gradient also carries them (reached with LAZY_BN_UPSAMPLER only).
+_DGRAD_BST_MAXC = 16
+FUSE_BN_BWD_STATS = True        # (tests: False takes every BatchNorm-backward sum by the stand-alone pass)
 
 
 def drop_bwd_stats(*_):
     _bwd_stats.clear()
-
-
-DIRECT_SMALL_GRADS = os.environ.get('DA_NO_DIRECT_SMALL_GRADS') != '1'
 
 
 def _direct_small_target(small_params, C, want_dbias):
@@ -1175,7 +1164,7 @@ def _direct_small_target(small_params, C, want_dbias):
     results straight into it: all three gradients are views of a registered bucket, consecutive there (conv.bias, BN.weight, BN.bias are consecutive
     parameters), and still all zeros since zero_grad (`_da_gz`, the mark the direct weight gradients use).  Saves the (3, C) scratch tensor and one
     torch add per block (19 launches on the dependent chain of a seg step).  None: take the scratch tensor + _accumulate_small_grads."""
-    if not DIRECT_SMALL_GRADS or small_params is None or not want_dbias or False:
+    if small_params is None or not want_dbias:
         return None
     bias, gamma, beta = small_params
     if bias is None or gamma is None or beta is None:
@@ -1215,7 +1204,7 @@ def _accumulate_small_grads(bias, gamma, beta, db, dgamma, dbeta):
     each other in the bucket (they do: conv.bias, BN.weight, BN.bias are consecutive parameters) their three gradients -- one (3, C)
     tensor, see _bn_backward -- are added with ONE kernel instead of three autograd accumulations.  Returns the gradients still to
     be handed to autograd (None where already accumulated)."""
-    if db is None or dgamma is None or dbeta is None or os.environ.get('DA_NO_SMALL_GRAD_FUSE') == '1':
+    if db is None or dgamma is None or dbeta is None:
         return db, dgamma, dbeta
     gb, gg, gbt = _async_target(bias), _async_target(gamma), _async_target(beta)
     if gb is None or gg is None or gbt is None:
@@ -1275,7 +1264,7 @@ class ConvBNActFn(Function):
         train_stats = bool(training or running_mean is None)
         pbuf = torch.empty((512, 2, Cout), dtype=torch.float64, device=a1.device) if train_stats else None
         npar = ctypes.c_int(0)
-        cap = 512 if (train_stats and os.environ.get('DA_NO_FUSED_STATS') != '1') else 0
+        cap = 512 if train_stats else 0
         done = False
         if pro1 is not None or pro2 is not None:
             s1, t1, sl1 = _pro_args(pro1)
@@ -1328,7 +1317,7 @@ class ConvBNActFn(Function):
             _serialize_matrix_kernels(54.0 * (C1 + C2) * Cout * N * D * H * W, N * D * H * W)
             use_pack(w_tio, 1, C1, C2, Cout, N, D, H, W)
             done = False
-            if (FUSE_BN_BWD_STATS and pro1 is not None and ((a2 is None and C1 <= _DGRAD_BST_MAXC) or (a2 is not None and C1 == 32 and C2 == 16 and a2.dtype == torch.float32 and _DGRAD_BST_CONCAT))
+            if (FUSE_BN_BWD_STATS and pro1 is not None and ((a2 is None and C1 <= _DGRAD_BST_MAXC) or (a2 is not None and C1 == 32 and C2 == 16 and a2.dtype == torch.float32))
                     and _matrix_mode == 'fp32_split' and dy.dtype == torch.float32
                     and a1.dtype == torch.float32 and p1s.data_ptr() - 8 * C1 == p1t.data_ptr() - 12 * C1 and p1s.untyped_storage().data_ptr() <= p1s.data_ptr() - 8 * C1):
                 # (also while a HIP graph is being captured: whether the route exists is decided on the host, and a graphed step must run the same kernels --
@@ -1354,10 +1343,8 @@ class ConvBNActFn(Function):
         elif gw is not None:
             global _last_side_flops
             _last_side_flops = 54.0 * (C1 + C2) * Cout * N * D * H * W
-            on_main = LAST_WGRAD_ON_MAIN_BN and dx1 is None and dx2 is None      # the net's first layer: see Conv3dFn.backward (A/B switch; off: no gain measured on the seg step)
-            side = torch.cuda.current_stream() if on_main else side_stream()
-            if not on_main:
-                side.wait_stream(torch.cuda.current_stream())
+            side = side_stream()                       # (also for the net's first layer: its weight gradient on the main stream, as in Conv3dFn.backward, gained nothing here)
+            side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
                 sst = stream()
                 swp, swn = _ws(wsb, a1)
@@ -1374,7 +1361,7 @@ class ConvBNActFn(Function):
                 None, None, None, None, None, None) + (None,) * ctx.n_extra
 
 
-FUSE_DECONV_BN_BWD = os.environ.get('DA_NO_DECONV_BN_BWD_FUSE') != '1'
+FUSE_DECONV_BN_BWD = True      # (tests: False runs the up-sampler block's backward as three calls)
 
 
 def _deconv_bn_bwd_fused(ctx, go, a, w_tio, y, stats, N, D, H, W, Cin, Cout, st):
@@ -1435,7 +1422,7 @@ class DeconvBNActFn(Function):
         b = bias.detach().contiguous() if bias is not None else None
         wp, wn = _ws(nat.lib().da_pointwise_ws_bytes(8, Cin, Cout), a)
         partials = None
-        if (training or running_mean is None) and os.environ.get('DA_NO_FUSED_STATS') != '1' and os.environ.get('DA_NO_FUSED_DECONV_STATS') != '1':
+        if training or running_mean is None:
             # the matrix-core epilogue accumulates the BatchNorm partial sums (one set per 256 coarse voxels): no statistics pass over y
             import ctypes
             nblk = (N * D * H * W + 255) // 256
@@ -1563,7 +1550,7 @@ class MaxPool2SkipFn(Function):
                 act = _apply_pro(a, extra, st)
                 call_act('da_maxpool2_fwd', A(act), O(out), N, D, H, W, C, st)
             ps, pt = extra[0], extra[1]
-            if (FUSE_BN_BWD_STATS and os.environ.get('DA_NO_POOL_BST') != '1' and a.dtype == torch.float32 and ps.data_ptr() - 8 * C == pt.data_ptr() - 12 * C
+            if (FUSE_BN_BWD_STATS and a.dtype == torch.float32 and ps.data_ptr() - 8 * C == pt.data_ptr() - 12 * C
                     and ps.untyped_storage().data_ptr() <= ps.data_ptr() - 8 * C):
                 # (scale, shift) are rows of the producer's [mean | rstd | scale | shift] buffer: its BatchNorm-backward sums can ride on this node's backward
                 raw, ctx.pro_slope = a, float(extra[2])
@@ -1704,7 +1691,7 @@ class WarpLabelsFn(Function):
 # set (SegmentationExperiment and bench.py do, for the softmax-Dice criterion) the network's 1x1x1 output convolution is not run on
 # its own: forward() returns a LazyLogits, and DiceLossMultiClass evaluates head + softmax + Dice in one kernel pair (da_head_dice_*)
 # that never writes the 629 MB-per-volume logits.  Anything else that touches the object gets real logits via .materialize().
-FUSE_HEAD_DICE = os.environ.get('DA_FUSE_HEAD_DICE', '1') != '0'
+FUSE_HEAD_DICE = True
 
 
 def head_dice_supported(cin, n_classes):
@@ -1860,13 +1847,12 @@ class SegPhaseLossFn(Function):
         # ONE workspace for both Dice entries (a second, larger _ws request on the same stream would replace -- and free -- the first)
         wp, wn = _ws(max(nat.lib().da_dice_ws_bytes(N, V, C), nat.lib().da_warp_dice_ws_bytes(N, C)), a)
         prob = torch.empty_like(a)
-        fused_fwd = os.environ.get('DA_NO_FUSED_SEGPHASE_FWD') != '1'
         if labels_m is not None:
             lm, bm = _labels(labels_m.reshape(N, -1))
             coef_s = _empty((2, N, C), a)
             # supervised Dice sums and softmax(logits) from ONE pass over the logits (da_softmax_dice_fwd) ...
-            if not (fused_fwd and call_supported('da_softmax_dice_fwd', ptr(a), ptr(lm), bm, ptr(prob), N, V, C, wt, nb, float(eps),
-                                                 ptr(loss_s), ptr(coef_s), wp, wn, st)):
+            if not call_supported('da_softmax_dice_fwd', ptr(a), ptr(lm), bm, ptr(prob), N, V, C, wt, nb, float(eps),
+                                  ptr(loss_s), ptr(coef_s), wp, wn, st):
                 call('da_dice_fwd', ptr(a), ptr(lm), bm, None, N, V, C, 1, wt, nb, float(eps), ptr(loss_s), ptr(coef_s), wp, wn, st)
                 call('da_softmax_fwd', ptr(a), ptr(prob), N * V, C, st)
         else:
@@ -1876,8 +1862,8 @@ class SegPhaseLossFn(Function):
         # ... and the anatomy Dice of the WARPED probabilities without writing the warped tensor (da_warp_dice_fwd)
         wp2, wn2 = wp, wn
         warped = None
-        if not (fused_fwd and call_supported('da_warp_dice_fwd', ptr(prob), ptr(u), ptr(lt), bt, N, D, H, W, C, wt, nb, float(eps),
-                                             ptr(loss_a), ptr(coef_a), wp2, wn2, st)):
+        if not call_supported('da_warp_dice_fwd', ptr(prob), ptr(u), ptr(lt), bt, N, D, H, W, C, wt, nb, float(eps),
+                              ptr(loss_a), ptr(coef_a), wp2, wn2, st):
             warped = torch.empty_like(a)
             call('da_warp_fwd', ptr(prob), ptr(u), None, ptr(warped), N, D, H, W, C, st)
             call('da_dice_fwd', ptr(warped), ptr(lt), bt, None, N, V, C, 0, wt, nb, float(eps), ptr(loss_a), ptr(coef_a), wp, wn, st)

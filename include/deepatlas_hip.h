@@ -117,8 +117,8 @@ int da_upconv3d_k3_dgrad(const float* dy, const float* w_tio, float* dx1, int C1
 int da_upconv3d_k3_wgrad(const float* s1, int C1, const float* s2, int C2, const float* dy, float* dw_tio,
                          int N, int Dc, int Hc, int Wc, int Cout, void* ws, size_t ws_bytes, void* stream);
 
-/* test/diagnostic knob: force the direct (VALU) kernels instead of the MFMA implicit-GEMM path (also env
- * DA_CONV_DIRECT=1); returns the previous setting.  Used by the GPU tests to A/B the two implementations. */
+/* test/diagnostic knob: force the direct (VALU) kernels instead of the MFMA implicit-GEMM path; returns the previous setting.
+ * Used by the GPU tests to A/B the two implementations. */
 int da_set_conv_direct(int on);
 
 /* bf16 matrix mode (BASELINE config 5; the reference itself is fp32-only, train_seg.py has no autocast): when on, the 3x3x3
@@ -475,7 +475,7 @@ int da_spatial_resample(const float* img, float* img_out, int C, int interp,
  * valid padding; loss = 1 - mean(cross^2 / (Ivar Jvar + eps)).  Output extent per axis: (L - dil (F-1) - 1) / stride + 1.
  * sums: [5][N][Do][Ho][Wo] floats written by fwd and consumed by bwd of the SAME geometry, opaque to the caller: the five window
  * sums (I, J, I^2, J^2, IJ) in the separable form; in the z-marching form (dil = stride = 1, F = 5 or 9: one fused kernel per
- * direction, reglosses.hip) the five per-window backward terms A', B', C', E1', E2'.  DA_LNCC_MARCH=0 keeps the separable form. */
+ * direction, reglosses.hip) the five per-window backward terms A', B', C', E1', E2'. */
 size_t da_lncc_ws_bytes(int N, int D, int H, int W, int F, int dil, int stride);
 int da_lncc_fwd(const float* I, const float* J, int N, int D, int H, int W, int F, int dil, int stride, float eps,
                 float* loss, float* sums, void* ws, size_t ws_bytes, void* stream);

@@ -1,12 +1,15 @@
 """(debug helper, not collected by pytest) per-parameter gradient difference between the bf16 twins and the conversion route."""
-import os, sys
+import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch
 from deepatlas_amd import ops
 import test_gpu_bf16_storage as T
+ap = argparse.ArgumentParser(description=__doc__)
+ap.add_argument('--no-lazy-bn', action='store_true', help='BatchNorm + activation materialised between the layers (ops.LAZY_BN off)')
+args = ap.parse_args()
 ops.set_matrix_precision('bf16'); ops.set_activation_storage('bf16')
-ops.LAZY_BN = os.environ.get('DA_LAZY_BN', '1') != '0'
+ops.LAZY_BN = not args.no_lazy_bn
 fused = os.environ.get('FUSED', '1') == '1'
 res = []
 for force in (False, True):

@@ -1,5 +1,5 @@
 """(debug helper, not collected by pytest) Per-module comparison of a UNet_light forward in bf16 storage mode: `_bf16` twins vs the conversion route (ops.BF16_FORCE_BRIDGE)."""
-import os, sys
+import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from deepatlas_amd import ops
@@ -7,8 +7,11 @@ from oracle import nets
 from deepatlas_amd.lib.network_factory import get_network
 
 dev = torch.device('cuda:0')
+ap = argparse.ArgumentParser(description=__doc__)
+ap.add_argument('--no-lazy-bn', action='store_true', help='BatchNorm + activation materialised between the layers (ops.LAZY_BN off)')
+args = ap.parse_args()
 ops.set_matrix_precision('bf16'); ops.set_activation_storage('bf16')
-ops.LAZY_BN = os.environ.get('DA_LAZY_BN', '1') != '0'
+ops.LAZY_BN = not args.no_lazy_bn
 spec = nets.UNET_LIGHT
 sd = nets.closed_form_fill(nets.unet_param_shapes(1, 32, spec['encoders'], spec['decoders']), seed=1)
 x = nets.closed_form_volume((2, 1, 32, 32, 32), seed=2).to(dev)

@@ -13,6 +13,6 @@ f=$(ls $O/prof/*/*.db 2>/dev/null | head -1)
 if [ -n "$f" ]; then python tools/rocpd_summary.py "$f" > $O/seg_bf16_kernel_stats.txt 2>&1 < /dev/null; python tools/rocpd_timeline.py "$f" --top 16 > $O/seg_bf16_timeline.txt 2>&1 < /dev/null; fi
 rm -rf $O/prof
 for l in 32,16,16,2,160,192,160 16,0,16,2,160,192,160 64,32,32,2,80,96,80 8,0,16,2,160,192,160; do
-  DA_MATRIX_BF16=1 python tools/bench_conv.py --layer $l --what fwd,dgrad,wgrad --iters 10 2>&1 | grep -v amdgpu.ids >> $O/conv3d_layers_bf16.txt
+  DA_MATRIX_MODE=1 python tools/bench_conv.py --layer $l --what fwd,dgrad,wgrad --iters 10 2>&1 | grep -v amdgpu.ids >> $O/conv3d_layers_bf16.txt
 done
 cat $O/bench_*.json | cut -c1-260
