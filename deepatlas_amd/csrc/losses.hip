@@ -331,18 +331,38 @@ static int lpv_for(int C) {
 // ------------------------------------------------------------------------------------------------
 // NCC
 // ------------------------------------------------------------------------------------------------
+// ALIGNED: every sample's base is 16-byte aligned (both tensors, and V % 4 == 0 when N > 1): float4 body from element 0, scalar tail.
+// Otherwise a sample's base may sit anywhere on a 4-byte boundary (N > 1 with V % 4 != 0, or a view into a larger buffer): a scalar head of
+// 0 - 3 elements up to the next 16-byte boundary, the float4 body from there, the scalar tail; when x and y have no common float4 phase the
+// whole sample goes through the scalar loop.  The scalar elements are strided over the whole grid and flushed like the body.
+// All five sums are of x - x[0] and y - y[0] (the sample's first elements as pivots; the finalize kernel adds them back to the means): the one-pass
+// var = E[x^2] - E[x]^2 then cancels terms of the size of the variance, not of mean^2 -- with the raw values an image with mean 6 and variance 0.75
+// lost a factor 50 of the products' fp32 rounding, which no double accumulation recovers.  The pivot helps as far as x[0] is representative: the
+// conditioning is (x[0] - mean)^2 / var instead of mean^2 / var, so a first voxel at 0 (a background corner) under intensities in [0, 1] is the raw
+// sum again, a first voxel far outside the intensity range is worse than the raw sum, and a NaN / inf there makes the sample's result NaN (as any
+// non-finite voxel does in the reference).  tests/test_gpu_loss_shapes.py test_ncc_unrepresentative_pivot holds the bound for x[0] = 0, mean 6.5.
+template <bool ALIGNED>
 __global__ void ncc_partial_kernel(const float* __restrict__ x, const float* __restrict__ y, long long V,
                                    double* __restrict__ partial /* [N][blocks][5] */) {
     __shared__ double red[5][4];
     const int n = blockIdx.y;
     const float* xs = x + (long long)n * V; const float* ys = y + (long long)n * V;
+    const float px = xs[0], py = ys[0];
     float a[5] = {0, 0, 0, 0, 0};
     double acc[5] = {0, 0, 0, 0, 0};
-    const long long V4 = V / 4;
+    long long head = 0;
+    if (!ALIGNED) {
+        head = (long long)(((16 - ((size_t)xs & 15)) & 15) >> 2);
+        if ((((size_t)xs ^ (size_t)ys) & 15) != 0 || head > V) head = V;
+    }
+    const long long V4 = (V - head) / 4;
+    const float* xb = xs + head; const float* yb = ys + head;
     int cnt = 0;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < V4; i += (long long)gridDim.x * blockDim.x) {
-        const float4 p = reinterpret_cast<const float4*>(xs)[i];
-        const float4 q = reinterpret_cast<const float4*>(ys)[i];
+        float4 p = reinterpret_cast<const float4*>(xb)[i];
+        float4 q = reinterpret_cast<const float4*>(yb)[i];
+        p.x -= px; p.y -= px; p.z -= px; p.w -= px;
+        q.x -= py; q.y -= py; q.z -= py; q.w -= py;
         a[0] += (p.x + p.y) + (p.z + p.w);
         a[1] += (q.x + q.y) + (q.z + q.w);
         a[2] += (p.x * q.x + p.y * q.y) + (p.z * q.z + p.w * q.w);
@@ -354,9 +374,25 @@ __global__ void ncc_partial_kernel(const float* __restrict__ x, const float* __r
             cnt = 0;
         }
     }
-    if (blockIdx.x == 0) for (long long i = V4 * 4 + threadIdx.x; i < V; i += blockDim.x) {
-        const float p = xs[i], q = ys[i];
-        a[0] += p; a[1] += q; a[2] += p * q; a[3] += p * p; a[4] += q * q;
+    if (ALIGNED) {
+        if (blockIdx.x == 0) for (long long i = V4 * 4 + threadIdx.x; i < V; i += blockDim.x) {
+            const float p = xs[i] - px, q = ys[i] - py;
+            a[0] += p; a[1] += q; a[2] += p * q; a[3] += p * p; a[4] += q * q;
+        }
+    } else {
+        // head [0, head) and tail [head + 4 V4, V) as one index range j, skipping the body
+        const long long nscalar = V - V4 * 4;
+        cnt = 0;
+        for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < nscalar; j += (long long)gridDim.x * blockDim.x) {
+            const long long i = j < head ? j : j + V4 * 4;
+            const float p = xs[i] - px, q = ys[i] - py;
+            a[0] += p; a[1] += q; a[2] += p * q; a[3] += p * p; a[4] += q * q;
+            if (++cnt == 64) {
+#pragma unroll
+                for (int k = 0; k < 5; ++k) { acc[k] += (double)a[k]; a[k] = 0.f; }
+                cnt = 0;
+            }
+        }
     }
 #pragma unroll
     for (int k = 0; k < 5; ++k) acc[k] += (double)a[k];
@@ -371,8 +407,9 @@ __global__ void ncc_partial_kernel(const float* __restrict__ x, const float* __r
     }
 }
 
-// stats[n] = {mean_x, mean_y, cov, var_x, var_y, ncc, M, 0}
+// stats[n] = {mean_x, mean_y, cov, var_x, var_y, ncc, M, 0}; the partial sums are of x - x[n][0], y - y[n][0]
 __global__ void ncc_finalize_kernel(const double* __restrict__ partial, int nblocks, int nsum, int N, long long V,
+                                    const float* __restrict__ x, const float* __restrict__ y,
                                     float* __restrict__ loss, double* __restrict__ stats) {
     __shared__ double sncc[64];
     const int n = threadIdx.x;
@@ -386,7 +423,7 @@ __global__ void ncc_finalize_kernel(const double* __restrict__ partial, int nblo
         double vx = s[3] / M - mx * mx, vy = s[4] / M - my * my;
         const double ncc = cov / (sqrt(vx) * sqrt(vy));
         double* o = stats + (size_t)n * 8;
-        o[0] = mx; o[1] = my; o[2] = cov; o[3] = vx; o[4] = vy; o[5] = ncc; o[6] = M; o[7] = 0.0;
+        o[0] = mx + (double)x[(long long)n * V]; o[1] = my + (double)y[(long long)n * V]; o[2] = cov; o[3] = vx; o[4] = vy; o[5] = ncc; o[6] = M; o[7] = 0.0;
         sncc[n] = ncc;
     }
     __syncthreads();
@@ -780,14 +817,16 @@ extern "C" int da_ncc_fwd(const float* x, const float* y, int N, long long V, fl
                           void* ws, size_t ws_bytes, void* stream) {
     if (!x || !y || !loss || !stats || N <= 0 || N > 64 || V <= 0) return DA_ERR_BADARG;
     if (ws_bytes < da_ncc_ws_bytes(N, V)) return DA_ERR_WS_SMALL;
-    if ((V % 4) != 0 && N > 1) return DA_ERR_UNSUPPORTED;   // per-sample base must stay 16-byte aligned
     hipStream_t st = da_stream(stream);
     int nblocks = (int)da_cdiv(V / 4 + 1, 256 * 4); if (nblocks > kBlocks) nblocks = kBlocks; if (nblocks < 1) nblocks = 1;
-    hipLaunchKernelGGL(ncc_partial_kernel, dim3(nblocks, N), dim3(256), 0, st, x, y, V, (double*)ws);
+    // float4 loads from element 0 of every sample need each sample's base 16-byte aligned; any other layout takes the head / body / tail form
+    const bool aligned = ((((size_t)x | (size_t)y) & 15) == 0) && (N == 1 || (V % 4) == 0);
+    if (aligned) hipLaunchKernelGGL(ncc_partial_kernel<true>, dim3(nblocks, N), dim3(256), 0, st, x, y, V, (double*)ws);
+    else hipLaunchKernelGGL(ncc_partial_kernel<false>, dim3(nblocks, N), dim3(256), 0, st, x, y, V, (double*)ws);
     DA_LAUNCH_CHECK();
     hipLaunchKernelGGL(colreduce_inplace_kernel, dim3((unsigned)da_cdiv((long long)N * 5 * 64, 256)), dim3(256), 0, st, (double*)ws, N, nblocks, 5);
     DA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ncc_finalize_kernel, dim3(1), dim3(64), 0, st, (const double*)ws, nblocks, 1, N, V, loss, stats);
+    hipLaunchKernelGGL(ncc_finalize_kernel, dim3(1), dim3(64), 0, st, (const double*)ws, nblocks, 1, N, V, x, y, loss, stats);
     DA_LAUNCH_CHECK();
     return 0;
 }

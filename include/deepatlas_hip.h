@@ -394,6 +394,8 @@ int da_conv3d_k3_prepack_many(int n, const float* const* w_tio, const int* C1, c
                               void* const* b0, const size_t* n0, void* const* b1, const size_t* n1, int* used, void* stream);
 
 /* ---- NCC loss (row a12; lib/loss.py:493-501) -------------------------------------------------- */
+/* x, y: [N][V] fp32, any N <= 64 and any V >= 1; the bases need only float alignment (16-byte aligned samples take the float4-from-0 form,
+ * every other layout a scalar head up to the next 16-byte boundary, the float4 body and a scalar tail). */
 size_t da_ncc_ws_bytes(int N, long long V);
 int da_ncc_fwd(const float* x, const float* y, int N, long long V, float* loss, double* stats /*[N][8]*/,
                void* ws, size_t ws_bytes, void* stream);
