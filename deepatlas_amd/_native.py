@@ -122,6 +122,9 @@ SIGNATURES = {
     'da_xent_bwd': (I, [P, P, I, P, P, P, P, P, LL, I, I, I, F, LL, P]),
     'da_argmax_dice_counts': (I, [P, P, I, I, LL, I, P, P, P]),
     'da_label_overlap_counts': (I, [P, I, P, I, I, LL, I, P, P]),
+    'da_warp_labels_nearest_counts': (I, [P, I, P, I, P, I, I, I, I, I, P, P, P]),
+    'da_jacobian_det_ws_bytes': (SZ, [I, I, I, I]),
+    'da_jacobian_det': (I, [P, I, I, I, I, P, P, P, SZ, P]),
     'da_conv_k2s2_fwd': (I, [P, P, P, P, I, I, I, I, I, I, P, SZ, P]),
     'da_conv_k2s2_dgrad': (I, [P, P, P, I, I, I, I, I, I, P, SZ, P]),
     'da_conv_k2s2_wgrad_ws_bytes': (SZ, [I, I, I, I, I, I]),

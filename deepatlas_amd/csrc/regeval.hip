@@ -1,0 +1,254 @@
+// Registration evaluation: nearest-neighbour label warp fused with the integer overlap counts (the DeepAtlas registration Dice: warp the moving
+// segmentation with the predicted deformation, overlap it with the target segmentation), and the Jacobian determinant of the deformation with
+// its per-sample statistics (folding fraction).  The reference has neither metric (README.md:15-19 lists registration as TODO); the deformation
+// is the one its registration net builds: deform = disp + identity, sampled with align_corners=True (voxel_morph.py:85-91, lib/utils.py:89-102).
+// NDHWC: disp[N][D][H][W][3], channel order (x, y, z) = (W, H, D) axis, normalised units, identity generated in-kernel.
+#include "common.h"
+
+namespace {
+
+constexpr int kJacBlocks = 2048;   // Jacobian partial blocks per sample (multiple of 8: XCD-contiguous split)
+constexpr int kJacStats = 5;       // per-block partials: sum(det - 1), sum((det - 1)^2), min, max, #(det <= 0)
+
+__device__ __forceinline__ long long load_label(const void* labels, int label_bytes, long long i) {
+    return label_bytes == 1 ? (long long)((const unsigned char*)labels)[i] : ((const long long*)labels)[i];
+}
+
+// the fp32 expressions of warp.hip (id_coord / make_taps), so that the training warp and this evaluation sample the same coordinate
+__device__ __forceinline__ float id_coord(int k, int size) { return (float)k / (float)(size - 1) * 2.0f - 1.0f; }
+__device__ __forceinline__ float unnormalize(float g, int size) { return ((g + 1.f) / 2.f) * (float)(size - 1); }
+
+// index of the moving voxel the target voxel (d, h, w) reads, or -1 (outside the volume, or a non-finite coordinate): every axis rounded
+// half-to-even (rintf in the default rounding mode = ATen's nearbyint), then the bounds test of padding_mode='zeros'
+__device__ __forceinline__ int nearest_source(float ux, float uy, float uz, int d, int h, int w, int D, int H, int W) {
+    const float gx = ux + id_coord(w, W), gy = uy + id_coord(h, H), gz = uz + id_coord(d, D);
+    if (!(fabsf(gx) < 1e9f && fabsf(gy) < 1e9f && fabsf(gz) < 1e9f)) return -1;      // NaN / inf: reads 0
+    const float x = rintf(unnormalize(gx, W)), y = rintf(unnormalize(gy, H)), z = rintf(unnormalize(gz, D));
+    if (!(x >= 0.f && x <= (float)(W - 1) && y >= 0.f && y <= (float)(H - 1) && z >= 0.f && z <= (float)(D - 1))) return -1;
+    return ((int)z * H + (int)y) * W + (int)x;
+}
+
+// Each thread takes RUN consecutive target voxels: their displacement is 3 x 16 bytes, their target labels and warped labels 4 bytes when the
+// layout allows (VEC), and runs of equal (warped, target) pairs are merged in registers before the per-wave LDS histograms are touched, as in
+// label_overlap_counts_kernel (losses.hip).  One 64-bit global atomic per (workgroup, class, kind) at the end: integer counts, exact and
+// independent of the order.  The runs are dealt out XCD-contiguously (da_xcd_loop): a target neighbourhood gathers its moving labels through one L2.
+template <bool VEC, bool COUNTS>
+__global__ void __launch_bounds__(256)
+warp_nearest_counts_kernel(const void* __restrict__ lab_m, int m_bytes, const void* __restrict__ lab_t, int t_bytes,
+                           const float* __restrict__ disp, int D, int H, int W, int C,
+                           unsigned long long* __restrict__ counts, unsigned char* __restrict__ warped) {
+    extern __shared__ unsigned int shc[];   // [4 waves][3][C]
+    constexpr int RUN = 4;
+    const int n = blockIdx.y;
+    const int V = D * H * W;
+    if (COUNTS) {
+        for (int c = threadIdx.x; c < 4 * 3 * C; c += blockDim.x) shc[c] = 0u;
+        __syncthreads();
+    }
+    unsigned int* hist = shc + (threadIdx.x >> 6) * 3 * C;
+    auto flush = [&](int pl, int tl, unsigned int len) {
+        if (len == 0u) return;
+        if (pl >= 0 && pl < C) atomicAdd(&hist[pl], len);
+        if (tl >= 0 && tl < C) atomicAdd(&hist[C + tl], len);
+        if (pl == tl && pl >= 0 && pl < C) atomicAdd(&hist[2 * C + pl], len);
+    };
+    const long long sample = (long long)n * V;
+    const float* u = disp + sample * 3;
+    const int nruns = (V + RUN - 1) / RUN;
+    for (DaXcdLoop L = da_xcd_loop(nruns, 64); L.i < L.end; L.i += L.step) {
+        const int v0 = (int)L.i * RUN;
+        const int cnt = (V - v0) < RUN ? (V - v0) : RUN;
+        float uu[RUN * 3];
+        if (VEC) {
+            const float4* q = reinterpret_cast<const float4*>(u + (long long)v0 * 3);
+            const float4 a = q[0], b = q[1], c = q[2];
+            uu[0] = a.x; uu[1] = a.y; uu[2] = a.z; uu[3] = a.w; uu[4] = b.x; uu[5] = b.y; uu[6] = b.z; uu[7] = b.w;
+            uu[8] = c.x; uu[9] = c.y; uu[10] = c.z; uu[11] = c.w;
+        } else {
+#pragma unroll
+            for (int k = 0; k < RUN * 3; ++k) uu[k] = (k < cnt * 3) ? u[(long long)v0 * 3 + k] : 0.f;
+        }
+        int d, h, w; da_vox3(v0, H, W, d, h, w);
+        int src[RUN];
+#pragma unroll
+        for (int k = 0; k < RUN; ++k) {
+            src[k] = (k < cnt) ? nearest_source(uu[3 * k], uu[3 * k + 1], uu[3 * k + 2], d, h, w, D, H, W) : -1;
+            if (++w == W) { w = 0; if (++h == H) { h = 0; ++d; } }
+        }
+        unsigned char m[RUN];
+#pragma unroll
+        for (int k = 0; k < RUN; ++k)      // (the RUN gathers are independent: issued back to back)
+            m[k] = src[k] >= 0 ? (unsigned char)load_label(lab_m, m_bytes, sample + src[k]) : (unsigned char)0;
+        if (warped) {
+            if (VEC) {
+                *reinterpret_cast<uchar4*>(warped + sample + v0) = make_uchar4(m[0], m[1], m[2], m[3]);
+            } else {
+#pragma unroll
+                for (int k = 0; k < RUN; ++k) if (k < cnt) warped[sample + v0 + k] = m[k];
+            }
+        }
+        if (COUNTS) {
+            int t[RUN];
+            if (VEC && t_bytes == 1) {
+                const uchar4 tt = *reinterpret_cast<const uchar4*>((const unsigned char*)lab_t + sample + v0);
+                t[0] = tt.x; t[1] = tt.y; t[2] = tt.z; t[3] = tt.w;
+            } else {
+#pragma unroll
+                for (int k = 0; k < RUN; ++k) t[k] = (k < cnt) ? (int)load_label(lab_t, t_bytes, sample + v0 + k) : -1;
+            }
+            int pl = -1, tl = -1; unsigned int len = 0u;
+#pragma unroll
+            for (int k = 0; k < RUN; ++k) {
+                if (k < cnt) {
+                    const int a = (int)m[k], b = t[k];
+                    if (a != pl || b != tl) { flush(pl, tl, len); pl = a; tl = b; len = 0u; }
+                    ++len;
+                }
+            }
+            flush(pl, tl, len);
+        }
+    }
+    if (COUNTS) {
+        __syncthreads();
+        for (int c = threadIdx.x; c < 3 * C; c += blockDim.x) {
+            const unsigned int s = shc[c] + shc[3 * C + c] + shc[6 * C + c] + shc[9 * C + c];
+            const int k = c / C, cc = c % C;
+            if (s) atomicAdd(&counts[((size_t)n * C + cc) * 3 + k], (unsigned long long)s);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Jacobian determinant of x -> x + u(x), u_c = disp_c (size_c - 1) / 2 in voxels; numpy.gradient differences with unit spacing (central
+// inside, one-sided on the faces), determinant by cofactor expansion in fp32.  A direct 6-neighbour gather like bending_bwd_kernel: the
+// voxels are dealt out XCD-contiguously so that the +-1 plane neighbours are found in the XCD's own L2.  Statistics: per-thread doubles ->
+// wave butterfly -> the four waves in order -> one partial row per workgroup; jacobian_finalize_kernel adds the rows in index order.
+// No atomics anywhere: two runs are bit-identical.  The sums are taken of det - 1 (exact in double), so that the variance of a
+// nearly-rigid field does not cancel.
+// ------------------------------------------------------------------------------------------------
+struct F3 { float x, y, z; };
+__device__ __forceinline__ F3 ld3(const float* __restrict__ p, float sx, float sy, float sz) { F3 r; r.x = p[0] * sx; r.y = p[1] * sy; r.z = p[2] * sz; return r; }
+
+__global__ void __launch_bounds__(256)
+jacobian_det_kernel(const float* __restrict__ disp, int D, int H, int W, float* __restrict__ det_out, double* __restrict__ partial) {
+    __shared__ double red[4][kJacStats];
+    const int n = blockIdx.y;
+    const int V = D * H * W;
+    const float* u = disp + (long long)n * V * 3;
+    const float sx = (float)(W - 1) / 2.f, sy = (float)(H - 1) / 2.f, sz = (float)(D - 1) / 2.f;
+    const long long sW = 3, sH = (long long)W * 3, sD = (long long)H * W * 3;
+    double s1 = 0.0, s2 = 0.0, cnt = 0.0;
+    float mn = INFINITY, mx = -INFINITY;
+    for (DaXcdLoop L = da_xcd_loop(V, 256); L.i < L.end; L.i += L.step) {
+        const int v = (int)L.i;
+        int d, h, w; da_vox3(v, H, W, d, h, w);
+        const float* q = u + (long long)v * 3;
+        const int wl = w > 0 ? -1 : 0, wh = w < W - 1 ? 1 : 0;
+        const int hl = h > 0 ? -1 : 0, hh = h < H - 1 ? 1 : 0;
+        const int dl = d > 0 ? -1 : 0, dh = d < D - 1 ? 1 : 0;
+        const F3 xa = ld3(q + wl * sW, sx, sy, sz), xb = ld3(q + wh * sW, sx, sy, sz);
+        const F3 ya = ld3(q + hl * sH, sx, sy, sz), yb = ld3(q + hh * sH, sx, sy, sz);
+        const F3 za = ld3(q + dl * sD, sx, sy, sz), zb = ld3(q + dh * sD, sx, sy, sz);
+        const float kx = (wh - wl == 2) ? 0.5f : 1.f, ky = (hh - hl == 2) ? 0.5f : 1.f, kz = (dh - dl == 2) ? 0.5f : 1.f;
+        // J[c][a] = delta_ca + d u_c / d a, (c, a) in (x, y, z)
+        const float j00 = 1.f + (xb.x - xa.x) * kx, j01 = (yb.x - ya.x) * ky, j02 = (zb.x - za.x) * kz;
+        const float j10 = (xb.y - xa.y) * kx, j11 = 1.f + (yb.y - ya.y) * ky, j12 = (zb.y - za.y) * kz;
+        const float j20 = (xb.z - xa.z) * kx, j21 = (yb.z - ya.z) * ky, j22 = 1.f + (zb.z - za.z) * kz;
+        const float det = j00 * (j11 * j22 - j12 * j21) - j01 * (j10 * j22 - j12 * j20) + j02 * (j10 * j21 - j11 * j20);
+        if (det_out) det_out[(long long)n * V + v] = det;
+        const double e = (double)det - 1.0;
+        s1 += e; s2 += e * e;
+        mn = fminf(mn, det); mx = fmaxf(mx, det);
+        if (det <= 0.f) cnt += 1.0;
+    }
+    s1 = da_wave_sum(s1); s2 = da_wave_sum(s2); cnt = da_wave_sum(cnt);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { mn = fminf(mn, __shfl_xor(mn, o)); mx = fmaxf(mx, __shfl_xor(mx, o)); }
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    if (lane == 0) { red[wid][0] = s1; red[wid][1] = s2; red[wid][2] = (double)mn; red[wid][3] = (double)mx; red[wid][4] = cnt; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double* p = partial + ((size_t)n * gridDim.x + blockIdx.x) * kJacStats;
+        p[0] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
+        p[1] = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
+        p[2] = fmin(fmin(red[0][2], red[1][2]), fmin(red[2][2], red[3][2]));
+        p[3] = fmax(fmax(red[0][3], red[1][3]), fmax(red[2][3], red[3][3]));
+        p[4] = ((red[0][4] + red[1][4]) + red[2][4]) + red[3][4];
+    }
+}
+
+// one wave per sample: lane l adds rows l, l + 64, ... in that order, then the fixed butterfly.  stats[n][8] =
+// (sum det, sum det^2, min, max, #(det <= 0), mean, population variance, 0)
+__global__ void jacobian_finalize_kernel(const double* __restrict__ partial, int nblocks, long long V, double* __restrict__ stats) {
+    const int n = blockIdx.x, lane = threadIdx.x;
+    double s1 = 0.0, s2 = 0.0, cnt = 0.0, mn = INFINITY, mx = -INFINITY;
+    for (int b = lane; b < nblocks; b += 64) {
+        const double* p = partial + ((size_t)n * nblocks + b) * kJacStats;
+        s1 += p[0]; s2 += p[1]; mn = fmin(mn, p[2]); mx = fmax(mx, p[3]); cnt += p[4];
+    }
+    s1 = da_wave_sum(s1); s2 = da_wave_sum(s2); cnt = da_wave_sum(cnt);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { mn = fmin(mn, __shfl_xor(mn, o)); mx = fmax(mx, __shfl_xor(mx, o)); }
+    if (lane == 0) {
+        const double v = (double)V, m1 = s1 / v;
+        double var = s2 / v - m1 * m1;
+        if (var < 0.0) var = 0.0;
+        double* o = stats + (size_t)n * 8;
+        o[0] = s1 + v; o[1] = s2 + 2.0 * s1 + v; o[2] = mn; o[3] = mx; o[4] = cnt; o[5] = 1.0 + m1; o[6] = var; o[7] = 0.0;
+    }
+}
+
+int jac_blocks(long long V) {
+    long long g = da_cdiv(V, 256);
+    if (g > kJacBlocks) g = kJacBlocks;
+    if (g >= 8) g = g / 8 * 8;          // a multiple of 8 takes the XCD-contiguous split
+    return (int)(g < 1 ? 1 : g);
+}
+
+}  // namespace
+
+extern "C" int da_warp_labels_nearest_counts(const void* lab_m, int m_bytes, const void* lab_t, int t_bytes, const float* disp,
+                                             int N, int D, int H, int W, int C, unsigned long long* counts, unsigned char* warped, void* stream) {
+    if (!lab_m || !disp || (!counts && !warped) || N < 1 || D < 1 || H < 1 || W < 1 || (m_bytes != 1 && m_bytes != 8)) return DA_ERR_BADARG;
+    if (counts && (!lab_t || C < 1 || C > 1024 || (t_bytes != 1 && t_bytes != 8))) return DA_ERR_BADARG;
+    const long long V = (long long)D * H * W;
+    if (V >= 0x7FFFFFFFLL / 4) return DA_ERR_UNSUPPORTED;                  // 32-bit voxel and element offsets inside a sample
+    hipStream_t st = da_stream(stream);
+    const long long nruns = (V + 3) / 4;
+    int g = da_grid(da_cdiv(nruns, 2), 256, 2048);                          // two runs (8 voxels) per thread where the volume is large enough
+    if (g >= 8) g = g / 8 * 8;
+    // the 16-byte / 4-byte forms need every sample's first voxel aligned
+    const bool vec = (V % 4 == 0) && (((size_t)disp & 15) == 0) && (!warped || ((size_t)warped & 3) == 0) &&
+                     (!counts || t_bytes != 1 || ((size_t)lab_t & 3) == 0);
+    const dim3 grid(g, N), block(256);
+    if (counts) {
+        const size_t lds = (size_t)4 * 3 * C * sizeof(unsigned int);
+        if (vec) hipLaunchKernelGGL((warp_nearest_counts_kernel<true, true>), grid, block, lds, st, lab_m, m_bytes, lab_t, t_bytes, disp, D, H, W, C, counts, warped);
+        else hipLaunchKernelGGL((warp_nearest_counts_kernel<false, true>), grid, block, lds, st, lab_m, m_bytes, lab_t, t_bytes, disp, D, H, W, C, counts, warped);
+    } else {
+        if (vec) hipLaunchKernelGGL((warp_nearest_counts_kernel<true, false>), grid, block, 0, st, lab_m, m_bytes, lab_t, t_bytes, disp, D, H, W, 0, counts, warped);
+        else hipLaunchKernelGGL((warp_nearest_counts_kernel<false, false>), grid, block, 0, st, lab_m, m_bytes, lab_t, t_bytes, disp, D, H, W, 0, counts, warped);
+    }
+    DA_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t da_jacobian_det_ws_bytes(int N, int D, int H, int W) {
+    (void)D; (void)H; (void)W;
+    return da_align((size_t)(N > 0 ? N : 1) * kJacBlocks * kJacStats * sizeof(double));
+}
+
+extern "C" int da_jacobian_det(const float* disp, int N, int D, int H, int W, double* stats, float* det_out,
+                               void* ws, size_t ws_bytes, void* stream) {
+    if (!disp || !stats || !ws || N < 1 || D < 2 || H < 2 || W < 2) return DA_ERR_BADARG;
+    if (ws_bytes < da_jacobian_det_ws_bytes(N, D, H, W)) return DA_ERR_WS_SMALL;
+    const long long V = (long long)D * H * W;
+    if (V >= 0x7FFFFFFFLL / 4) return DA_ERR_UNSUPPORTED;
+    hipStream_t st = da_stream(stream);
+    const int nblocks = jac_blocks(V);
+    hipLaunchKernelGGL(jacobian_det_kernel, dim3(nblocks, N), dim3(256), 0, st, disp, D, H, W, det_out, (double*)ws);
+    DA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(jacobian_finalize_kernel, dim3(N), dim3(64), 0, st, (const double*)ws, nblocks, V, stats);
+    DA_LAUNCH_CHECK();
+    return 0;
+}

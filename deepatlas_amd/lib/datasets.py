@@ -69,3 +69,48 @@ def get_seg_dataset(name):
     if name == 'synthetic':
         return SyntheticSegDataset
     raise KeyError("dataset '%s': only 'synthetic' is available (NIfTI datasets need SimpleITK, out of scope)" % name)
+
+
+class SyntheticRegDataset(Dataset):
+    """Ordered (moving, fixed) pairs over the volumes of a SyntheticSegDataset, enumerated as the reference's pairwise datasets do
+    (lib/datasets.py:344-359): pair id -> fixed = id // (n - 1), moving = id % (n - 1), plus one when >= fixed; n (n - 1) pairs, no
+    self-pairs.  Sample: (moving image, fixed image, moving segmentation, fixed segmentation, has_moving_seg, name).
+
+    labeled: the volume indices that have a manual segmentation (None: all).  For an unlabelled MOVING volume the segmentation slot
+    holds zeros and has_moving_seg is False (a flag, because default collation cannot batch None); the experiment turns it into
+    seg_m=None.  Pairs whose FIXED volume is unlabelled are left out of the enumeration: the joint step and the registration Dice
+    both need the fixed segmentation (an unlabelled fixed image is not supported)."""
+
+    def __init__(self, n_volumes, shape, n_classes, seed=230, labeled=None):
+        if n_volumes < 2:
+            raise ValueError('a pairwise dataset needs at least two volumes')
+        self.seg = SyntheticSegDataset(n_volumes, shape, n_classes, seed)
+        self.n = n_volumes
+        self.labeled = set(range(n_volumes)) if labeled is None else set(int(i) for i in labeled)
+        self.pairs = [p for p in (self.pair_of(i, n_volumes) for i in range(n_volumes * (n_volumes - 1))) if p[1] in self.labeled]
+
+    @staticmethod
+    def pair_of(pair_id, n):
+        """(moving, fixed) volume indices of pair `pair_id` among n volumes."""
+        fixed, moving = pair_id // (n - 1), pair_id % (n - 1)
+        if moving >= fixed:
+            moving += 1
+        return moving, fixed
+
+    def __len__(self):
+        return len(self.pairs)
+
+    def __getitem__(self, i):
+        m, f = self.pairs[i]
+        im, sm, name_m = self.seg[m]
+        it, st_, name_f = self.seg[f]
+        has = m in self.labeled
+        if not has:
+            sm = torch.zeros_like(sm)
+        return im, it, sm, st_, has, '%s_to_%s' % (name_m, name_f)
+
+
+def get_reg_dataset(name):
+    if name == 'synthetic':
+        return SyntheticRegDataset
+    raise KeyError("dataset '%s': only 'synthetic' is available (NIfTI datasets need SimpleITK, out of scope)" % name)

@@ -150,3 +150,20 @@ def get_multi_metric(pred, gt, eval_label_list=None, rm_bg=False):
                 batch_avg_res[m][:, l] = float(np.mean(col[np.where(col != -1)]))
     return {'multi_metric_res': multi_metric_res, 'label_avg_res': label_avg_res, 'batch_avg_res': batch_avg_res,
             'label_list': label_list}
+
+
+def registration_dice(seg_m, seg_t, disp, n_class):
+    """Hard-label registration Dice (the DeepAtlas registration metric): the moving segmentation warped with the predicted deformation
+    (nearest neighbour, ops.warp_labels_nearest) against the target segmentation, classes 1..n_class-1, for every pair of the batch:
+    float64 ndarray [N][n_class-1], NaN where a class is absent from both maps (the convention of metricEval('dice', ...)).
+    seg_m / seg_t: N x D x H x W label maps, disp: N x 3 x D x H x W; one kernel, exact integer counts."""
+    return dice_from_counts(ops.reg_label_counts(seg_m, seg_t, disp, n_class))[:, 1:]
+
+
+def jacobian_stats(disp):
+    """Regularity of the deformation x -> x + u(x): per-sample float64 arrays `mean`, `std` (population), `min`, `max` of det J,
+    `n_nonpos` = number of voxels with det J <= 0 (folding) and `nonpos_frac` = that number over the voxel count."""
+    s = ops.jacobian_det(disp).cpu().numpy()
+    n_vox = float(np.prod(disp.shape[2:]))
+    return {'mean': s[:, 5].copy(), 'std': np.sqrt(s[:, 6]), 'min': s[:, 2].copy(), 'max': s[:, 3].copy(),
+            'n_nonpos': s[:, 4].copy(), 'nonpos_frac': s[:, 4] / n_vox}

@@ -1,0 +1,227 @@
+"""RegistrationExperiment: the experiment the reference lists as TODO (README.md:15-19), on the skeleton of SegmentationExperiment.
+
+Model = the registration net (lib/network_factory/voxel_morph.py), step = models/joint.py RegistrationStep (NCC + lambda_reg * bending
+energy, unchanged), data = ordered (moving, fixed) pairs (lib/datasets.py:331-451).  Validation scores what a registration is for: the
+hard-label registration Dice -- the moving segmentation warped with the predicted deformation (nearest neighbour) against the fixed
+segmentation -- next to the same Dice for the identity deformation on the same pairs, and the regularity of the deformation (det J:
+mean, standard deviation, folding fraction), all from exact device kernels (lib/evalMetrics.py registration_dice / jacobian_stats).
+Checkpoints carry the keys of SegmentationExperiment's ({'epoch', 'model_state_dict', 'optimizer_state_dict', 'best_score'}).
+"""
+import datetime
+import os
+import time
+import warnings
+
+import numpy as np
+import torch
+from torch.utils.data import DataLoader
+
+from .base import BaseExperiment
+from .joint import RegistrationStep
+from .segmentation import SegmentationExperiment
+from ..lib import datasets as med_data
+from ..lib import evalMetrics as metrics
+from ..lib.network_factory import get_network
+from ..lib.param_dict import save_dict_to_json
+from ..optim import FlatAdam
+from .. import ops
+from .. import parallel
+
+try:
+    from tensorboardX import SummaryWriter
+except Exception:                                             # tensorboardX is optional here
+    SummaryWriter = None
+
+
+def _nanmean(a, axis=None):
+    """numpy.nanmean without its warning for an all-NaN slice (a class that occurs in no pair stays NaN)."""
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore', category=RuntimeWarning)
+        return np.nanmean(a, axis=axis)
+
+
+def eval_registration(model, dataloader, n_classes, device):
+    """Registration metrics of `model` over a loader of (moving image, fixed image, moving seg, fixed seg, has_moving_seg, name) batches.
+    Pairs without a moving segmentation have no registration Dice and are skipped for it; every pair counts for the Jacobian statistics.
+    Returns a dict: dice_per_class [C-1] (mean over the pairs that have the class: nanmean), dice_avg (mean over the classes that occur),
+    identity_dice_per_class / identity_dice_avg (the same for disp = 0 on the same pairs: what registration bought), nonpos_frac (mean
+    folding fraction), det_mean / det_std (means over the pairs of the per-pair mean / standard deviation of det J), n_pairs, n_dice_pairs."""
+    dice, dice_id, jac = [], [], {'nonpos_frac': [], 'mean': [], 'std': []}
+    with torch.no_grad():
+        model.eval()
+        for im_m, im_t, seg_m, seg_t, has, _name in dataloader:
+            im_m, im_t = im_m.to(device), im_t.to(device)
+            disp = model(im_m, im_t)[0]
+            js = metrics.jacobian_stats(disp)
+            for k in jac:
+                jac[k].append(js[k])
+            keep = torch.as_tensor(has).reshape(-1).bool()
+            if bool(keep.any()):
+                sm, st_, dk = seg_m[keep].to(device), seg_t[keep].to(device), disp[keep.to(device)]
+                dice.append(metrics.registration_dice(sm, st_, dk, n_classes))
+                dice_id.append(metrics.registration_dice(sm, st_, torch.zeros_like(dk), n_classes))
+    out = {}
+    for key, rows in (('dice', dice), ('identity_dice', dice_id)):
+        per = _nanmean(np.concatenate(rows, 0), axis=0) if rows else np.full(n_classes - 1, np.nan)
+        out[key + '_per_class'] = per
+        out[key + '_avg'] = float(_nanmean(per)) if np.isfinite(per).any() else float('nan')
+    for k, name in (('nonpos_frac', 'nonpos_frac'), ('mean', 'det_mean'), ('std', 'det_std')):
+        out[name] = float(np.mean(np.concatenate(jac[k]))) if jac[k] else float('nan')
+    out['n_pairs'] = int(sum(len(a) for a in jac['mean']))
+    out['n_dice_pairs'] = int(sum(len(a) for a in dice))
+    return out
+
+
+class RegistrationExperiment(BaseExperiment):
+    def __init__(self, config):
+        super(RegistrationExperiment, self).__init__(config)
+        self.device = torch.device(self.config.get('device', 'cuda'))
+        cfg = self.config
+        if cfg['debug_mode']:
+            print("Debug mode")
+            cfg['print_batch_period'] = cfg['valid_epoch_period'] = 2
+        self.exp_name = self.experiment_name(cfg)
+        run_dir = "debug_reg" if cfg['debug_mode'] else self.exp_name
+        self.ckpoint_dir = os.path.join(cfg['log_dir'], run_dir, str(cfg['random_seed']))
+        self.writer = None
+        self.global_step = 0
+        self.best_score = 0
+        self.current_epoch = 1
+        self.training_data_loader = self.config.get('training_data_loader')
+        self.validation_data_loader = self.config.get('validation_data_loader')
+        print("Init experiment {} seed {}".format(self.exp_name, self.config['random_seed']))
+
+    @staticmethod
+    def experiment_name(cfg):
+        """Reg_<model>_<data dir name>_<n>samples_batch_<b>_<e>epochs_ncc_bending_<lambda_reg>_lr_<lr>[_scheduler_<mode>]"""
+        parts = ['Reg_', cfg['model'], '_', os.path.basename(cfg['data_dir']), '_%ssamples' % cfg['num_samples'], '_batch_%s' % cfg['batch_size'],
+                 '_%sepochs' % cfg['n_epochs'], '_ncc_bending_%s' % cfg['lambda_reg'], '_lr_%s' % cfg['learning_rate']]
+        if cfg['lr_mode'] != 'const':
+            parts.append('_scheduler_%s' % cfg['lr_mode'])
+        return ''.join(str(v) for v in parts)
+
+    # ---- setup ---------------------------------------------------------------------------------
+    def setup_log(self):
+        if parallel.rank() != 0:
+            return
+        if not os.path.isdir(self.ckpoint_dir):
+            os.makedirs(self.ckpoint_dir)
+        save_dict_to_json(self.config, os.path.join(self.ckpoint_dir, "train_config.json"))
+        if SummaryWriter is not None:
+            self.writer = SummaryWriter(self.ckpoint_dir)
+
+    def setup_train_data(self):
+        if self.training_data_loader is not None:
+            return
+        dataset = med_data.get_reg_dataset(self.config['data'])
+        shape = self.config['synthetic_shape']
+        training_data = dataset(max(self.config['num_samples'], 2), shape, self.config['n_classes'], seed=self.config['random_seed'])
+        sampler = parallel.distributed_sampler(training_data, shuffle=True, seed=self.config['random_seed'])
+        self.training_data_loader = DataLoader(training_data, batch_size=self.config['batch_size'], shuffle=sampler is None,
+                                               sampler=sampler, num_workers=0)
+        validation_data = dataset(max(self.config.get('num_valid_samples', 2), 2), shape, self.config['n_classes'],
+                                  seed=self.config['random_seed'] + 1000)
+        self.validation_data_loader = DataLoader(validation_data, batch_size=1, shuffle=False, num_workers=0)
+
+    def setup_model(self):
+        self.model = get_network(self.config['model'])(**self.config.get('model_settings', {}))
+        self.model.to(self.device)
+
+    def setup_optimizer(self):
+        self.optimizer = FlatAdam(self.model.parameters(), lr=self.config['learning_rate'])
+        ops.enable_async_wgrad(bool(self.config.get('async_wgrad', True)))
+        ops.set_matrix_precision(self.config.get('matrix_precision') or ops.DEFAULT_MATRIX_PRECISION)
+        self.scheduler = SegmentationExperiment.make_scheduler(self.optimizer, self.config)
+        self.step = RegistrationStep(self.model, self.optimizer, lam_reg=self.config['lambda_reg'])
+
+    # ---- training ------------------------------------------------------------------------------
+    def train(self):
+        self.setup_train()
+        print("Training {}".format(self.exp_name))
+        finished_epoch, self.best_score = self.initialize_model(self.model, self.optimizer, self.config['resume_dir'])
+        parallel.broadcast_parameters(self.optimizer, model=self.model)
+        parallel.pin_host_resources()
+        self.current_epoch = finished_epoch + 1
+        for epoch in range(self.current_epoch, self.config['n_epochs'] + 1):
+            self.train_one_epoch()
+            self.validate()
+            self.current_epoch += 1
+        if self.writer is not None:
+            self.writer.close()
+        print('Finished Training: {}'.format(self.exp_name))
+
+    def train_step(self, im_m, im_t):
+        """One RegistrationStep on a batch of pairs: (loss, (disp, warped, deform), (similarity, bending))."""
+        return self.step(im_m.to(self.device, non_blocking=True), im_t.to(self.device, non_blocking=True))
+
+    def train_one_epoch(self):
+        running_loss = 0.0
+        iters_per_epoch = max(self.config['samples_per_epoch'] // (self.config['batch_size'] * parallel.world_size()), 1)
+        train_data_iter = None
+        period = self.config['print_batch_period']
+        for i in range(iters_per_epoch):
+            try:
+                batch = next(train_data_iter)
+            except (StopIteration, TypeError):
+                train_data_iter = iter(self.training_data_loader)
+                batch = next(train_data_iter)
+            self.global_step = (self.current_epoch - 1) * iters_per_epoch + (i + 1) * self.config['batch_size']
+            loss, _, _ = self.train_step(batch[0], batch[1])
+            running_loss += loss.item()
+            if i % period == period - 1:
+                if parallel.rank() == 0:
+                    print('Epoch[{}/{}] it {} loss: {:.3f} lr:{} {}'.format(
+                        self.current_epoch, self.config['n_epochs'], i + 1, running_loss / period if i > 0 else running_loss,
+                        self.optimizer.param_groups[0]['lr'], datetime.datetime.now().strftime("%D %H:%M:%S")))
+                    if self.writer is not None:
+                        self.writer.add_scalar('loss/training', running_loss / period, global_step=self.global_step)
+                        self.writer.add_scalar('learning_rate', self.optimizer.param_groups[0]['lr'], global_step=self.global_step)
+                running_loss = 0.0
+
+    def eval(self, dataloader):
+        return eval_registration(self.model, dataloader, self.config['n_classes'], self.device)
+
+    def validate(self):
+        if self.current_epoch % self.config['valid_epoch_period'] != 0:
+            return
+        start_time = time.time()
+        res = self.last_validation = self.eval(self.validation_data_loader)
+        score = res['dice_avg']
+        if self.scheduler is not None:
+            if self.config['lr_mode'] == 'plateau':
+                self.scheduler.step(score)
+            else:
+                self.scheduler.step()
+        # (the first validation of a run always leaves a best file, also when its score is 0 or NaN: test() reloads it)
+        is_best = not os.path.isfile(os.path.join(self.ckpoint_dir, 'model_best.pth.tar'))
+        if score > self.best_score:
+            is_best = True
+            self.best_score = score
+        if parallel.rank() != 0:
+            return
+        if self.writer is not None:
+            tag = 'validation_{}/'.format(self.config['data'])
+            for k in ('dice_avg', 'identity_dice_avg', 'nonpos_frac', 'det_mean', 'det_std'):
+                self.writer.add_scalar(tag + k, res[k], global_step=self.global_step)
+        print("Validation: registration Dice Avg: {:.4f} (identity {:.4f})  det J {:.4f} +- {:.4f}, folding {:.3%} ({:.3f} sec) {}".format(
+            score, res['identity_dice_avg'], res['det_mean'], res['det_std'], res['nonpos_frac'], time.time() - start_time,
+            datetime.datetime.now().strftime("%D %H:%M:%S")))
+        if self.current_epoch % self.config['save_ckpts_epoch_period'] == 0:
+            self.save_checkpoint({'epoch': self.current_epoch,
+                                  'model_state_dict': self.model.state_dict(),
+                                  'optimizer_state_dict': self.optimizer.state_dict(),
+                                  'best_score': self.best_score},
+                                 is_best, self.ckpoint_dir)
+
+    def test(self, best=True, if_log=True):
+        """Reload the best (or the last) checkpoint and report the registration metrics on the test loader."""
+        self.setup_model()
+        if self.validation_data_loader is None:
+            self.setup_train_data()
+        ckpoint_file = os.path.join(self.ckpoint_dir, 'model_best.pth.tar' if best else 'checkpoint.pth.tar')
+        last_epoch, best_score = self.initialize_model(self.model, optimizer=None, ckpoint_path=ckpoint_file)
+        loader = self.config.get('testing_data_loader') or self.validation_data_loader
+        res = self.eval(loader)
+        print('Testing Model: {} ({} epochs)  registration Dice_avg: {} (identity {})  folding fraction: {}'.format(
+            ckpoint_file, last_epoch, res['dice_avg'], res['identity_dice_avg'], res['nonpos_frac']))
+        return res

@@ -2229,3 +2229,65 @@ def spatial_resample(image, labels, affine, coef=None, order=0, interpolator='li
              ptr(labels), ptr(lab_out), _LABEL_BYTES[labels.dtype] if labels is not None else 1,
              ptr(aff), ptr(cft), int(order), int(gx), int(gy), int(gz), N, D, H, W, stream())
     return img_out, lab_out
+
+
+# ------------------------------------------------------------------------------------------------
+# registration evaluation (csrc/regeval.hip): hard-label warp + overlap counts, Jacobian determinant.  No autograd.
+# ------------------------------------------------------------------------------------------------
+def _eval_disp(disp):
+    u = ndhwc(disp.detach())
+    if u.dim() != 5 or u.shape[-1] != 3 or u.dtype != torch.float32:
+        raise ValueError('displacement field must be N x 3 x D x H x W float32')
+    return u
+
+
+def _warp_nearest_counts(seg_m, seg_t, disp, n_class, want_counts, want_warped):
+    u = _eval_disp(disp)
+    N, D, H, W, _ = u.shape
+    ml, mb = _labels(seg_m.reshape(seg_m.shape[0], -1))
+    if tuple(ml.shape) != (N, D * H * W):
+        raise ValueError('label map must be N x D x H x W matching the displacement field')
+    tl, tb = None, 1
+    counts = warped = None
+    if want_counts:
+        tl, tb = _labels(seg_t.reshape(seg_t.shape[0], -1))
+        if tl.shape != ml.shape:
+            raise ValueError('moving and target label maps must have the same shape')
+        counts = torch.zeros((N, int(n_class), 3), dtype=torch.int64, device=u.device)
+    if want_warped:
+        warped = torch.empty((N, D, H, W), dtype=torch.uint8, device=u.device)
+    with torch.cuda.device(u.device):
+        call('da_warp_labels_nearest_counts', ptr(ml), mb, ptr(tl), tb, ptr(u), N, D, H, W, int(n_class) if want_counts else 0,
+             ptr(counts), ptr(warped), stream())
+    return counts, warped
+
+
+def warp_labels_nearest(labels, disp):
+    """F.grid_sample(labels, disp + identity, mode='nearest', padding_mode='zeros', align_corners=True) for a label map N x D x H x W
+    (uint8 or int64) and a displacement field N x 3 x D x H x W in the layout of WarpFn: the warped map, uint8 N x D x H x W."""
+    return _warp_nearest_counts(labels, None, disp, 0, False, True)[1]
+
+
+def reg_label_counts(seg_m, seg_t, disp, n_class, return_warped=False):
+    """Overlap counts of the registration Dice in one pass: counts[N][n_class][3] int64 = (|warp(seg_m)==c|, |seg_t==c|, |both|) with the
+    nearest-neighbour warp of warp_labels_nearest; labels outside [0, n_class) are ignored.  Bit-equal to
+    label_overlap_counts(warp_labels_nearest(seg_m, disp), seg_t, n_class).  return_warped: (counts, warped uint8 map)."""
+    counts, warped = _warp_nearest_counts(seg_m, seg_t, disp, n_class, True, bool(return_warped))
+    return (counts, warped) if return_warped else counts
+
+
+JACOBIAN_STATS = ('sum', 'sumsq', 'min', 'max', 'n_nonpos', 'mean', 'var')
+
+
+def jacobian_det(disp, return_map=False):
+    """Jacobian determinant of x -> x + u(x) for a displacement field N x 3 x D x H x W (normalised units, as WarpFn takes it), u in
+    voxels, numpy.gradient differences.  Returns stats, a float64 N x 8 device tensor whose columns are JACOBIAN_STATS (+ one unused);
+    return_map: (stats, det N x D x H x W float32)."""
+    u = _eval_disp(disp)
+    N, D, H, W, _ = u.shape
+    stats = torch.empty((N, 8), dtype=torch.float64, device=u.device)
+    det = torch.empty((N, D, H, W), dtype=torch.float32, device=u.device) if return_map else None
+    with torch.cuda.device(u.device):
+        wp, wn = _ws(nat.lib().da_jacobian_det_ws_bytes(N, D, H, W), u)
+        call('da_jacobian_det', ptr(u), N, D, H, W, ptr(stats), ptr(det), wp, wn, stream())
+    return (stats, det) if return_map else stats

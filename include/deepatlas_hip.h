@@ -503,6 +503,28 @@ int da_argmax_dice_counts(const float* logits, const void* truth, int label_byte
 int da_label_overlap_counts(const void* pred, int pred_bytes, const void* truth, int truth_bytes, int N, long long V, int C,
                             unsigned long long* counts, void* stream);
 
+/* ---- registration evaluation (regeval.hip).  The reference lists registration / joint training as TODO (README.md:15-19) and has no
+ *      registration metric; these serve the deformation its registration net builds -- deform = disp + identity (voxel_morph.py:85-88,
+ *      lib/utils.py:89-102) sampled by F.grid_sample(..., align_corners=True) (voxel_morph.py:90-91) -- and the pairwise datasets it
+ *      left as hooks (lib/datasets.py:331-451).  disp [N][D][H][W][3] fp32, channels (x, y, z) = (W, H, D) axis, normalised units. ---- */
+/* Nearest-neighbour warp of a label map fused with the overlap counts of the registration Dice: warped = F.grid_sample(lab_m, deform,
+ * mode='nearest', padding_mode='zeros', align_corners=True).  The sampling coordinate is computed with the fp32 expressions of da_warp_fwd's
+ * kernel, each axis rounded half-to-even; the moving label is read where all three indices are in range, else 0; a non-finite coordinate
+ * gives 0.  lab_m / lab_t: uint8 (1) or int64 (8) maps [N][D][H][W].  warped (may be NULL) uint8 [N][D][H][W]: moving labels are stored
+ * as uint8 (an int64 label outside [0, 255] wraps) and counted as stored.  counts (may be NULL; not both) [N][C][3] uint64 =
+ * (|warped==c|, |lab_t==c|, |both|), zero-filled by the caller, labels outside [0, C) ignored, C <= 1024; lab_t is only read with counts.
+ * Exact integers, independent of the order.  DA_ERR_UNSUPPORTED for volumes of >= 2^29 voxels. */
+int da_warp_labels_nearest_counts(const void* lab_m, int m_bytes, const void* lab_t, int t_bytes, const float* disp,
+                                  int N, int D, int H, int W, int C, unsigned long long* counts, unsigned char* warped, void* stream);
+/* Jacobian determinant of x -> x + u(x) with u_c = disp_c (size_c - 1) / 2 voxels, size = (W, H, D): J[c][a] = delta_ca + d u_c / d a,
+ * numpy.gradient's differences at unit spacing (central inside, one-sided on the faces), determinant by cofactor expansion in fp32.
+ * Every extent >= 2.  stats [N][8] doubles = (sum det, sum det^2, min, max, number of voxels with det <= 0, mean, population variance, 0),
+ * accumulated in double from per-workgroup partials added in index order (no atomics: two runs are bit-identical); mean and variance come
+ * from the sums of det - 1, which do not cancel for a nearly rigid field.  det_out (may be NULL) [N][D][H][W] fp32. */
+size_t da_jacobian_det_ws_bytes(int N, int D, int H, int W);
+int da_jacobian_det(const float* disp, int N, int D, int H, int W, double* stats /*[N][8]*/, float* det_out,
+                    void* ws, size_t ws_bytes, void* stream);
+
 /* ---- optimiser (models/segmentation.py:91 torch.optim.Adam defaults) -------------------------- */
 int da_adam_step(float* p, const float* g, float* m, float* v, long long n,
                  float lr, float beta1, float beta2, float eps, int step, float grad_scale, void* stream);

@@ -1,0 +1,71 @@
+"""Train the registration net (VoxelMorph) alone: the registration counterpart of train_seg.py, which the reference lists as TODO
+(README.md:15-19).  Same flag style as train_seg.py; the step is NCC + lambda_reg * bending energy (models/joint.py RegistrationStep),
+the data are ordered pairs of synthetic volumes, validation reports the hard-label registration Dice (against the identity
+deformation's) and the Jacobian statistics of the predicted deformation."""
+import argparse
+import os
+
+from deepatlas_amd.models.registration import RegistrationExperiment
+
+
+def build_config(args):
+    n_classes = 32
+    config = dict(
+        debug_mode=args.debug,
+        resume_dir='',
+        random_seed=230,
+        data='synthetic',
+        n_epochs=args.num_epochs,
+        samples_per_epoch=args.num_samples * max(args.num_samples - 1, 1),    # every ordered pair once
+        batch_size=1,
+        valid_batch_size=1,
+        print_batch_period=50,
+        valid_epoch_period=1,
+        save_ckpts_epoch_period=1,
+        model='voxel_morph_cvpr',
+        model_settings={},
+        n_classes=n_classes,
+        lambda_reg=1.0,
+        learning_rate=1e-3,
+        lr_mode='multiStep',
+        milestones=[0.5, 1],
+        gamma=0.2,
+    )
+    config.update(args.__dict__)
+    config['learning_rate'] = args.lr
+    config['synthetic_shape'] = tuple(args.shape)
+    config['data_dir'] = os.path.join(args.data_root, "synthetic")
+    config['valid_data_dir'] = config['data_dir']
+    config['log_dir'] = './{}/{}'.format(args.log_root, config['data'])
+    config['device'] = 'cuda:{}'.format(args.device) if args.device.isdigit() else args.device
+    if not config.get('matrix_precision'):                # absent = the package default, 'fp32_split'
+        config.pop('matrix_precision', None)
+    return config
+
+
+def add_common_arguments(parser):
+    parser.add_argument('--device', '-g', default='0', type=str, help='index of used GPU')
+    parser.add_argument('--debug', '-d', action='store_true', help='if debug mode')
+    parser.add_argument('--num-samples', '-ns', default=21, type=int, help='number of volumes for training (pairs: n (n - 1))')
+    parser.add_argument('--num-epochs', '-ne', default=100, type=int, help='number of epochs for training')
+    parser.add_argument('--lr', default=1e-3, type=float, help='learning rate')
+    parser.add_argument('--test_only', '-t', action='store_true', help='only test model')
+    parser.add_argument('--data-root', '-root', default='./data', type=str, help='root of the data folder')
+    parser.add_argument('--log-root', '-log', default='./logs', type=str, help='root of the log folders')
+    parser.add_argument('--shape', nargs=3, type=int, default=[64, 64, 64], help='synthetic volume size D H W (multiples of 16)')
+    parser.add_argument('--matrix-precision', default=None, choices=['fp32', 'fp32_split', 'bf16'],
+                        help="arithmetic of the 3x3x3 convolutions, as in train_seg.py ('fp32_split' when absent)")
+    parser.add_argument('--lambda-reg', default=1.0, type=float, help='weight of the bending-energy regulariser')
+    return parser
+
+
+def main(argv=None):
+    args = add_common_arguments(argparse.ArgumentParser()).parse_args(argv)
+    exp = RegistrationExperiment(build_config(args))
+    if not args.test_only:
+        exp.train()
+    return exp.test()
+
+
+if __name__ == '__main__':
+    main()
