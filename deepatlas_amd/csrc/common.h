@@ -13,6 +13,19 @@
         if (e__ != hipSuccess) return (int)e__;             \
     } while (0)
 
+// Launch of a kernel whose dynamic LDS exceeds the default limit: hipFuncAttributeMaxDynamicSharedMemorySize is set once per kernel (the
+// function-local static: one per instantiation, initialised thread-safely), then the launch and its check.  The attribute is LdsBound bytes,
+// or, by default, the first launch's `lds`: a kernel whose LDS size varies from call to call passes the largest size it can ask for.
+//   return da_launch_lds<my_kernel<8, 2>>(dim3(nb), dim3(256), lds, st, params);
+template <auto Kern, int LdsBound = 0, typename... Args>
+static inline int da_launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, LdsBound ? LdsBound : (int)lds);
+    if (attr != hipSuccess) return (int)attr;
+    hipLaunchKernelGGL(Kern, grid, block, lds, st, args...);
+    DA_LAUNCH_CHECK();
+    return 0;
+}
+
 static inline hipStream_t da_stream(void* s) { return (hipStream_t)s; }
 __host__ __device__ static inline long long da_cdiv(long long a, long long b) { return (a + b - 1) / b; }
 static inline size_t da_align(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }

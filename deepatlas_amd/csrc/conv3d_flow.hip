@@ -533,23 +533,13 @@ static int flow_launch_t(const FlowWgP& p, int nb, hipStream_t st) {
     const size_t red_bytes = (size_t)MTT * (TWO ? 2 : 1) * 64 * sizeof(float4);
     size_t shm = ((size_t)TVOX * 16 + (TWO ? (size_t)TVOX * S1 : 0) + (size_t)HVOX * p.Cout) * sizeof(float);
     if (shm < red_bytes) shm = red_bytes;
-    auto kern = flow_wgrad_kernel<MTT, TWO, S1, XB>;
-    static bool attr_set = false;
-    if (!attr_set) { hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); if (e != hipSuccess) return (int)e; attr_set = true; }
-    hipLaunchKernelGGL(kern, dim3(nb), dim3(256), shm, st, p);
-    DA_LAUNCH_CHECK();
-    return 0;
+    return da_launch_lds<flow_wgrad_kernel<MTT, TWO, S1, XB>, 80 * 1024>(dim3(nb), dim3(256), shm, st, p);      // (shm grows with Cout: the attribute is a fixed bound)
 }
 
 template <int MTT, bool TWO, int S1>
 static int flow_launch_split(const FlowWgP& p, int nb, hipStream_t st) {
     const size_t shm = (size_t)2 * (16 + (TWO ? S1 : 0)) * sp::CHS + (size_t)2 * 3 * 3 * sp::HZ * sp::HY * sp::YROW + 80;
-    auto kern = flow_wgrad_split_kernel<MTT, TWO, S1>;
-    static bool attr_set = false;
-    if (!attr_set) { hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024); if (e != hipSuccess) return (int)e; attr_set = true; }
-    hipLaunchKernelGGL(kern, dim3(nb), dim3(256), shm, st, p);
-    DA_LAUNCH_CHECK();
-    return 0;
+    return da_launch_lds<flow_wgrad_split_kernel<MTT, TWO, S1>, 64 * 1024>(dim3(nb), dim3(256), shm, st, p);
 }
 
 // split matrix mode, fp32 tensors: the two-term fp16 kernel (its tile is 2 x 8 x 16: the geometry is re-derived); otherwise the exact-fp32 kernel

@@ -397,9 +397,6 @@ __global__ void __launch_bounds__(256, 2) fm_dgrad_kernel(DgP p) {
     }
 }
 
-template <typename K> int fm_set_lds(K kern, size_t bytes) {
-    return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
 struct Plan { int ntz, nty, ntx, ntiles; };
 Plan fm_plan(int N, int D, int H, int W) {
     Plan q;
@@ -435,11 +432,9 @@ int da_conv3_flowmm_fwd(const float* in1, int C1, const float* in2, int C2, cons
     DA_LAUNCH_CHECK();
     const int grid = q.ntiles < 512 ? q.ntiles : 512;
     const size_t shm = (size_t)2 * HV * Cin * 2 + 16;
-#define X(a, b) if (C1 == a && C2 == b) { static bool set = false; if (!set) { const int e = fm_set_lds(fm_fwd_kernel<a, b>, shm); if (e) return e; set = true; } \
-        hipLaunchKernelGGL((fm_fwd_kernel<a, b>), dim3(grid), dim3(256), shm, st, p); }
+#define X(a, b) if (C1 == a && C2 == b) return da_launch_lds<fm_fwd_kernel<a, b>>(dim3(grid), dim3(256), shm, st, p);
     FM_CASES(X)
 #undef X
-    DA_LAUNCH_CHECK();
     return 0;
 }
 

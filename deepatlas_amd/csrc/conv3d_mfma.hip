@@ -25,21 +25,6 @@
 #include "split_f16.h"      // da_split2, da_absmax4, da_wave_max_nonneg, da_scale_exp, da_pow2: the two-term fp16 split of the SP kernels
 
 #include "conv3d_stage.h"
-#ifndef DA_BF16_SMAP
-#ifndef DA_BF16_SMAP2
-#define DA_BF16_SMAP2 0  // ... also in the two-N-tile kernels when the tensors are bf16 (raw staging: half the parked registers): 96 -> 32 forward 0.316 -> 0.308 ms but + statistics 0.262 -> 0.317; off
-#endif
-#define DA_BF16_SMAP 1   // bf16 matrix-mode forward kernels: staging offsets from the per-thread halo map (0: the cursor; A/B builds)
-#endif
-#ifndef DA_SP_LB
-#define DA_SP_LB 1   // split mode, one N-tile: K-steps of weight-fragment lookahead
-#endif
-#ifndef DA_RPB4
-#define DA_RPB4 0   // split mode, one N-tile: row blocks of four instead of two (no gain measured: 48 -> 16 forward 1.60 -> 1.62 ms, +16 registers)
-#endif
-#ifndef DA_PIN
-#define DA_PIN 1   // pin the m-outer MFMA order (keeps hipcc from chaining 4 dependent MFMAs on one accumulator)
-#endif
 
 namespace {
 
@@ -254,7 +239,7 @@ __global__ void __launch_bounds__(256, 2) conv3_mfma_fwd_kernel(FwdP p) {
     // carry-stepping cursor with its per-load bounds checks (~20).  Split mode always; the bf16 matrix-mode kernels too when the whole next
     // tile is parked in registers (PRE == NIT): their 8 MFMAs per K-step leave the VALU as the busiest pipe (SQ counters: 7 VALU instructions
     // per MFMA with the cursor, profiles/r03_pmc_sq_conv3d_48to16.txt)
-    constexpr bool SMAP = SP || (K32 && PRE == NIT && (NREP == 1 || (RAW && DA_BF16_SMAP2)) && DA_BF16_SMAP);      // (two N-tiles with fp32 tensors: measured 10 % slower with the map's 17 extra registers; raw bf16 staging parks half the registers)
+    constexpr bool SMAP = SP || (K32 && PRE == NIT && NREP == 1);      // (two N-tiles: measured slower with the map's 17 extra registers)
     constexpr bool SMVO = SP && !(NREP == 2 && STATS);            // the launch-constant voxel offsets cost NIT registers
     StageMap<CK, HZ, SMVO> smap; if constexpr (SMAP) smap.init(p.H, p.W);
     const bool hi = (g >> 1) != 0;
@@ -296,7 +281,7 @@ __global__ void __launch_bounds__(256, 2) conv3_mfma_fwd_kernel(FwdP p) {
         else if constexpr (BF) return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(b, a, c, 0, 0, 0);
         else return c;
     };
-    constexpr int LB = SP ? (NREP == 1 ? DA_SP_LB : 1) : (NREP == 1) ? 4 : ((NREP == 2 && !STATS) ? 2 : 1);   // B lookahead in K-steps (the statistics variant of NREP = 2 would spill at 2; a split-mode K-step is 6 x 8 MFMAs long)
+    constexpr int LB = SP ? 1 : (NREP == 1) ? 4 : ((NREP == 2 && !STATS) ? 2 : 1);   // B lookahead in K-steps (the statistics variant of NREP = 2 would spill at 2; a split-mode K-step is 6 x 8 MFMAs long)
     constexpr int RB = LB + 1;                          // ring slots
     constexpr int TAIL = SP ? 2 : 5;                    // K-steps at the end of an item without staging loads (they must land before stage_write)
     constexpr int PRO_DELAY = SP ? 1 : 3;               // K-steps between a staging load and its prologue arithmetic (< TAIL)
@@ -423,7 +408,7 @@ __global__ void __launch_bounds__(256, 2) conv3_mfma_fwd_kernel(FwdP p) {
         constexpr int PLANE_E = StageGeom<CK, HZ>::TOTAL * 4;             // elements per operand plane (SP)
         // SP: rows per block of MFMAs -- a block issues its products plane pair by plane pair over RPB x NREP accumulators, so two MFMAs on the same
         // accumulator are four apart (two apart, one N-tile and row pairs, cost 2 - 5 wait states per MFMA: its latency is two issue slots)
-        constexpr int RPB = (SP && NREP == 1 && DA_RPB4) ? 4 : 2;
+        constexpr int RPB = 2;
         Frag AC[NP][RPB];                                                   // SP: fragments of the current row block
         if constexpr (SP) {
             const AElem* ap = step_ptr(0);
@@ -513,7 +498,7 @@ __global__ void __launch_bounds__(256, 2) conv3_mfma_fwd_kernel(FwdP p) {
 #pragma unroll
                     for (int r = 0; r < HALF; ++r)
                         acc[r][nn] = __builtin_amdgcn_mfma_f32_16x16x4f32(bq[s % RB][nn][0][m], A0[r][m], acc[r][nn], 0, 0, 0);
-                if (DA_PIN) __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_sched_barrier(0);      // pin the m-outer order (keeps hipcc from chaining 4 dependent MFMAs on one accumulator)
             }
             }
             {   // first half of the next K-step (the last step re-reads its own, harmlessly)
@@ -534,7 +519,7 @@ __global__ void __launch_bounds__(256, 2) conv3_mfma_fwd_kernel(FwdP p) {
 #pragma unroll
                     for (int r = 0; r < HALF; ++r)
                         acc[HALF + r][nn] = __builtin_amdgcn_mfma_f32_16x16x4f32(bq[s % RB][nn][0][m], A1[r][m], acc[HALF + r][nn], 0, 0, 0);
-                if (DA_PIN) __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_sched_barrier(0);      // pin the m-outer order (keeps hipcc from chaining 4 dependent MFMAs on one accumulator)
             }
             }
         }
@@ -1238,9 +1223,6 @@ __global__ void __launch_bounds__(256, 2) conv3_mfma_wgrad_kernel(WgP p) {
 #ifndef DA_WG_ZPAD
 #define DA_WG_ZPAD 4
 #endif
-#ifndef DA_WG_TZ
-#define DA_WG_TZ 2      // z planes per tile of the split weight gradient (4: two z-plane pairs per staged tile -- measured 48 -> 16 2.01 -> 1.85 ms but 16 -> 16 0.64 -> 0.70: spills at 256 VGPRs; kept for A/B builds)
-#endif
 // (Tried: a 1-D launch that gives the two workgroups of a CU -- blocks L and L + 256, tools/ubench/wg_placement.hip -- neighbouring chunks of
 // one slab so that the one behind finds the other's lines in L1.  No effect, 2.008 vs 2.017 ms on 48 -> 16 on one box: a tile's lines, 92 KB,
 // pass through the 32 KB L1 long before the partner asks for them.)
@@ -1253,8 +1235,7 @@ __global__ void __launch_bounds__(256, 2) conv3_split_wgrad_kernel(WgP p) {
     constexpr bool RAWA = HB && !SPL && !PRO, RAWY = HB && !SPL;       // bf16 tensors copied straight into the bf16 LDS image (da_buf_loadq)
     constexpr unsigned ES = HbEl<HB>::ES;
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int CK = 8, CG = 16, TZ = DA_WG_TZ, HZ = TZ + 2, TVOX = TZ * TY * TX;      // tile 4 x 8 x 16: two z-plane pairs per staged tile (half the barriers and tile-table reads per MFMA, halo 2.1x instead of 2.8x)
-    static_assert(TZ == 2 || TZ == 4, "one or two z-plane pairs per tile");
+    constexpr int CK = 8, CG = 16, TZ = 2, HZ = TZ + 2, TVOX = TZ * TY * TX;      // tile 2 x 8 x 16: one z-plane pair per staged tile (a 4-plane tile spills)
     constexpr int ZPQ = DA_WG_ZPAD, ZPE = 4 * ZPQ;                         // padding after every z plane of the x tile: quads / elements
     constexpr int PLA = HZ * (HY * HX * CK + ZPE), PLY = TVOX * CG;        // elements per plane
     float* ldsA = lds;
@@ -1538,347 +1519,10 @@ __global__ void __launch_bounds__(256, 2) conv3_split_wgrad_kernel(WgP p) {
     }
 }
 
-// ---------------------------------------------------------------------------------------------------
-// Weight gradient in split mode, third form: 16-channel chunks, eight waves.
-// The staging loads of the row-owner kernel above fetch 32 bytes (8 channels) of every voxel while the L1 asks the L2 for 64-byte
-// sectors, and the kernel is bound by exactly that stream: with everything but the loads removed it runs 1.91 of 1.98 ms (48 -> 16,
-// DA_WG_ABLATE=6); the counters show 167 M sector requests per launch at 387 cycles of latency and the L1 stalled on its outstanding
-// requests 35 % of the time -- ~64 sectors in flight x 64 B / 387 cycles = the observed ~10 B / clk / CU (profiles/r04_wgrad_memory_path.txt).
-// Here a workgroup stages 16 channels = one whole sector per voxel (half the requests for the same data, and half as many passes over
-// the dY tile), as EIGHT waves: waves 0 - 3 own the chunk's first 8 channels, waves 4 - 7 the second 8, each exactly the row-owner
-// kernel's per-wave program (two output rows, all 27 taps, 14 accumulators) on the shared dY tile -- so the register budget per wave is
-// unchanged, and per thread the staging shrinks (6 x quads as before, 2 dY quads instead of 4).  One workgroup per CU (62 KB of LDS,
-// 2 waves per SIMD as before); chosen when C1 and C2 are multiples of 16 and slabs x chunks x cout groups fills >= 224 of the 256 CUs.
-// ---------------------------------------------------------------------------------------------------
+// quads of padding after every z plane of a half image in the ring kernels of conv3d_wgring.h (as DA_WG_ZPAD above)
 #ifndef DA_WG16_ZPAD
 #define DA_WG16_ZPAD 4
 #endif
-// Phases as in the row-owner kernel (MFMAs | barrier | convert + write | barrier), ~205 registers and 62 KB of LDS.  A two-buffer form (one
-// barrier per tile, the next tile converted between the MFMAs, loads two tiles ahead: 254 registers, 125 KB) is faster alone (48 -> 16:
-// 1.72 vs 1.85 ms) but slower in the training step (seg 22.8 vs 21.65 ms): it fills the register file, and the BatchNorm-backward kernels
-// of the main stream -- HBM-bound, the natural partners of a matrix-bound weight gradient on the side stream -- then wait for it to end
-// instead of running beside it in the 2 x 48 registers per SIMD and 98 KB of LDS this form leaves free.
-// NPL = 2: split mode (fp32 tensors, two fp16 planes, three products).  NPL = 1 with HB: bf16 activation storage in the bf16 matrix mode -- one
-// bf16 plane, one product, no scales; a 16-channel chunk is then 32 bytes of a voxel (the row-owner form stages 16: a quarter of a sector).
-template <bool PRO, int NPL = 2, bool HB = false>
-__global__ void __launch_bounds__(512, 1) conv3_split_wgrad16_kernel(WgP p) {
-    static_assert(NPL == 2 || (NPL == 1 && HB), "two fp16 planes of fp32 tensors, or one bf16 plane of bf16 tensors");
-    constexpr bool SPL = NPL == 2;
-    using WFrag = std::conditional_t<SPL, f16x8, bf16x8>;
-    constexpr bool RAWA = HB && !SPL && !PRO, RAWY = HB && !SPL;       // bf16 tensors copied straight into the bf16 LDS image
-    constexpr unsigned ES = HbEl<HB>::ES;
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int CK = 16, CG = 16, TZ = 2, HZ = TZ + 2, TVOX = TZ * TY * TX, NT = 512;
-    constexpr int ZPQ = DA_WG16_ZPAD, ZPE = 4 * ZPQ;
-    constexpr int QA = CK / 4, HV = HZ * HY * HX, TOTA = HV * QA, NITA = (TOTA + NT - 1) / NT;
-    constexpr int PLH = HZ * (HY * HX * 8 + ZPE), PLA = 2 * PLH, PLY = TVOX * CG;      // elements per half image / per plane (x tile: the chunk's two 8-channel halves as two images of 16-byte voxel records -- the row-owner kernel's layout, 1.2 LDS cycles per half-wave fragment read; 32-byte records with the halves side by side: 2.8, lanes 8 voxels apart are then exactly 64 banks apart)
-    constexpr int QY = CG / 4, NITY = (TVOX * QY + NT - 1) / NT;
-    float* ldsA = lds;
-    float* ldsY = lds + PLA / 2 * NPL;                                     // NPL planes of PLA two-byte elements
-    float* smax = ldsY + PLY / 2 * NPL;                                    // [2][8]
-    typedef s16x4 __attribute__((address_space(3))) * lds_frag_ptr;
-    const short* ldsAh = reinterpret_cast<const short*>(ldsA);
-    const short* ldsYh = reinterpret_cast<const short*>(ldsY);
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int wr = wave & 3, wh = wave >> 2;                               // row pair, channel half
-    const int i = lane & 15, g = lane >> 4, q = i & 3, vq = i >> 2;
-    const int slab = blockIdx.x, nsl = gridDim.x, ch = blockIdx.y, cg = blockIdx.z;
-    const int cbase = ch * CK;
-    const float* src; int Cs, choff;
-    if (cbase < p.C1) { src = p.in1; Cs = p.C1; choff = cbase; } else { src = p.in2; Cs = p.C2; choff = cbase - p.C1; }
-    const int c4 = (int)threadIdx.x % QA;
-    unsigned vmA = 0;
-    float4 psc = make_float4(1.f, 1.f, 1.f, 1.f), psf = make_float4(0.f, 0.f, 0.f, 0.f); float pslope = -1.f;
-    if constexpr (PRO) {
-        const int cofs = choff + c4 * 4;
-        psc = *reinterpret_cast<const float4*>((cbase < p.C1 ? p.ps1 : p.ps2) + cofs);
-        psf = *reinterpret_cast<const float4*>((cbase < p.C1 ? p.pt1 : p.pt2) + cofs);
-        pslope = cbase < p.C1 ? p.pslope1 : p.pslope2;
-    }
-    // fragment sources exactly as in conv3_split_wgrad_kernel, in this wave's half image
-    const int laneA = ((((g >> 1) * HY) + 2 * wr) * HX + 8 * (g & 1) + vq) * 8 + (q & 1) * 4 + (g >> 1) * ZPE + wh * PLH;
-    int offC[5];
-#pragma unroll
-    for (int c = 0; c < 5; ++c) {
-        const int combo = (c < 4) ? 2 * c + (q >> 1) : 8;
-        offC[c] = ((combo / 3) * HY * HX + combo % 3) * 8 + (combo / 3) * ZPE;
-    }
-    const int laneY = ((((g >> 1) * TY) + 2 * wr) * TX + 8 * (g & 1) + vq) * CG + q * 4;
-    auto tr8 = [&](const short* a, int step) -> WFrag {
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_frag_ptr)a);
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_frag_ptr)(a + step));
-        return __builtin_bit_cast(WFrag, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-    };
-    auto mma = [&](f32x4 c, const WFrag& a, const WFrag& b) -> f32x4 {
-        if constexpr (SPL) return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-        else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-    };
-    struct F3 { WFrag p[NPL]; };
-    auto loadF = [&](int c, int h) -> F3 {
-        F3 f; const short* a = ldsAh + laneA + offC[c] + h * (HX * 8);
-#pragma unroll
-        for (int pl = 0; pl < NPL; ++pl) f.p[pl] = tr8(a + pl * PLA, 4 * 8);
-        return f;
-    };
-    auto loadG = [&](int h) -> F3 {
-        F3 f; const short* a = ldsAh + laneA + offC[4] + (h + (q >> 1)) * (HX * 8);
-#pragma unroll
-        for (int pl = 0; pl < NPL; ++pl) f.p[pl] = tr8(a + pl * PLA, 4 * 8);
-        return f;
-    };
-    auto loadY = [&](int r) -> F3 {
-        F3 f; const short* a = ldsYh + laneY + r * (TX * CG);
-#pragma unroll
-        for (int pl = 0; pl < NPL; ++pl) f.p[pl] = tr8(a + pl * PLY, 4 * CG);
-        return f;
-    };
-    f32x4 acc[5][3];
-#pragma unroll
-    for (int c = 0; c < 5; ++c)
-#pragma unroll
-        for (int d = 0; d < 3; ++d) acc[c][d] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-    const TileWalk tw = tile_walk(p.ntiles, nsl, slab);
-    float4 preA[NITA], preY[NITY];
-    // staging maps (launch constants): x halo quad idx = threadIdx.x + 512 it -> halo voxel idx / 4; dY quad idx -> voxel idx / 4
-    int voA[NITA]; unsigned pkA[NITA];
-#pragma unroll
-    for (int it = 0; it < NITA; ++it) {
-        const int hv = ((int)threadIdx.x + it * NT) / QA;
-        const int hx = hv % HX, t = hv / HX, hy = t % HY, hz = t / HY;
-        pkA[it] = (hv < HV) ? ((unsigned)hz << 16 | (unsigned)hy << 8 | (unsigned)hx) : 0xFFFF0000u;
-        voA[it] = (hv < HV) ? (hz * p.H + hy) * p.W + hx : 0;
-    }
-    const bool smallA = (long long)HZ * p.H * p.W < (1ll << 24) && (long long)Cs * ES < (1ll << 24);
-    const int yq4 = cg * CG + ((int)threadIdx.x % QY) * 4;
-    const int yv0 = (int)threadIdx.x / QY;
-    int voY[NITY];
-    const bool smallY = (long long)TZ * p.H * p.W < (1ll << 24) && (long long)p.Cout * ES < (1ll << 24);
-#pragma unroll
-    for (int it = 0; it < NITY; ++it) { const int v = yv0 + it * (NT / QY); voY[it] = ((v >> 7) * p.H + ((v >> 4) & 7)) * p.W + (v & 15); }
-    auto fetch_tile = [&](int tile) -> int4 {
-        int pos = tw.lo + tile * tw.J; pos = pos < p.ntiles ? pos : p.ntiles - 1;
-        return p.tiles[__builtin_amdgcn_readfirstlane(pos)];
-    };
-    auto issue_loads = [&](const int4 tv) {
-        const int n = __builtin_amdgcn_readfirstlane(tv.x), z0 = __builtin_amdgcn_readfirstlane(tv.y), y0 = __builtin_amdgcn_readfirstlane(tv.z), x0 = __builtin_amdgcn_readfirstlane(tv.w);
-        {
-            const long long sample = (long long)p.D * p.H * p.W * Cs;
-            const __amdgpu_buffer_rsrc_t rs = da_rsrc_n<HB>(src, n, sample);
-            const bool interior = smallA && z0 >= 1 && z0 + HZ - 2 < p.D && y0 >= 1 && y0 + HY - 2 < p.H && x0 >= 1 && x0 + HX - 2 < p.W;
-            const unsigned Cs4 = (unsigned)Cs * ES, cofs4 = (unsigned)(choff + c4 * 4) * ES;      // (bytes per voxel record / of this thread's quad)
-            const unsigned base = (unsigned)(((z0 - 1) * p.H + (y0 - 1)) * p.W + (x0 - 1)) * Cs4 + cofs4;
-            if constexpr (PRO) vmA = 0;
-#pragma unroll
-            for (int it = 0; it < NITA; ++it) {
-                const int hz = (int)(pkA[it] >> 16), hy = (int)((pkA[it] >> 8) & 255u), hx = (int)(pkA[it] & 255u);
-                unsigned so;
-                if (interior) so = ((it + 1) * NT <= TOTA || hz != 0xFFFF) ? __umul24((unsigned)voA[it], Cs4) + base : 0xFFFFFFFFu;
-                else {
-                    const int z = z0 - 1 + hz, y = y0 - 1 + hy, x = x0 - 1 + hx;
-                    const bool inb = (unsigned)z < (unsigned)p.D && (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W;
-                    so = inb ? (unsigned)(((z * p.H + y) * p.W + x)) * Cs4 + cofs4 : 0xFFFFFFFFu;
-                }
-                preA[it] = da_buf_loadq<HB, RAWA>(rs, so);
-                if constexpr (PRO) vmA |= (so != 0xFFFFFFFFu ? 1u : 0u) << it;
-            }
-        }
-        const long long sampleY = (long long)p.D * p.H * p.W * p.Cout;
-        const __amdgpu_buffer_rsrc_t ry = da_rsrc_n<HB>(p.dy, n, sampleY);
-        const bool inside = smallY && z0 + TZ <= p.D && y0 + TY <= p.H && x0 + TX <= p.W && cg * CG + CG <= p.Cout;
-        const int basev = (z0 * p.H + y0) * p.W + x0;
-        const unsigned baseY = ((unsigned)basev * (unsigned)p.Cout + (unsigned)yq4) * ES;
-#pragma unroll
-        for (int it = 0; it < NITY; ++it) {
-            const int v = yv0 + it * (NT / QY);
-            const int vx = v & 15, vy = (v >> 4) & 7, vz = v >> 7;
-            unsigned off;
-            if (inside) off = __umul24((unsigned)voY[it], (unsigned)p.Cout * ES) + baseY;
-            else {
-                const int x = x0 + vx, y = y0 + vy, z = z0 + vz;
-                const bool vin = z < p.D && y < p.H && x < p.W && yq4 < p.Cout;
-                off = vin ? (unsigned)((((z * p.H + y) * p.W + x) * p.Cout + yq4) * ES) : 0xFFFFFFFFu;
-            }
-            preY[it] = da_buf_loadq<HB, RAWY>(ry, off);
-        }
-    };
-    int Eacc = 0, Emin = 0, Enext = 0; bool first_tile = true;
-    auto publish_max = [&]() {
-        if constexpr (PRO) stage_pro_apply<0, NITA>(preA, vmA, psc, psf, pslope);
-        if constexpr (SPL) {
-            const float ma = da_wave_max_nonneg(stage_absmax<NITA>(preA)), my = da_wave_max_nonneg(stage_absmax<NITY>(preY));
-            if (lane == 0) { smax[wave] = ma; smax[8 + wave] = my; }
-        }
-    };
-    auto pack_bf16 = [&](const float4 v, bool raw) -> uint2 {             // one parked quad as four bf16 (raw: it already is, in .x / .y)
-        return raw ? make_uint2(__float_as_uint(v.x), __float_as_uint(v.y)) : make_uint2(da_bf16x2(v.x, v.y), da_bf16x2(v.z, v.w));
-    };
-    auto write_lds = [&]() {
-        if constexpr (!SPL) {
-#pragma unroll
-            for (int it = 0; it < NITA; ++it) {
-                const int idx0 = threadIdx.x + it * NT;
-                if (idx0 < TOTA) {
-                    const int hv = idx0 >> 2;
-                    reinterpret_cast<uint2*>(ldsA)[(c4 >> 1) * (PLH / 4) + hv * 2 + (c4 & 1) + ZPQ * (hv / (HY * HX))] = pack_bf16(preA[it], RAWA);
-                }
-            }
-#pragma unroll
-            for (int it = 0; it < NITY; ++it) {
-                const int idx = threadIdx.x + it * NT;
-                if (idx < TVOX * QY) reinterpret_cast<uint2*>(ldsY)[idx] = pack_bf16(preY[it], RAWY);
-            }
-            return;
-        }
-        const float4 ma0 = *reinterpret_cast<const float4*>(smax), ma1 = *reinterpret_cast<const float4*>(smax + 4);
-        const float4 my0 = *reinterpret_cast<const float4*>(smax + 8), my1 = *reinterpret_cast<const float4*>(smax + 12);
-        const float mA = fmaxf(fmaxf(fmaxf(ma0.x, ma0.y), fmaxf(ma0.z, ma0.w)), fmaxf(fmaxf(ma1.x, ma1.y), fmaxf(ma1.z, ma1.w)));
-        const float mY = fmaxf(fmaxf(fmaxf(my0.x, my0.y), fmaxf(my0.z, my0.w)), fmaxf(fmaxf(my1.x, my1.y), fmaxf(my1.z, my1.w)));
-        const int ea = da_scale_exp(__int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(mA))));
-        const int ey = da_scale_exp(__int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(mY))));
-        int E = ea + ey;
-        if (!first_tile) E = min(E, Emin + 40);
-        if (!first_tile && E >= Eacc && E <= Eacc + 3) E = Eacc;           // (keep the accumulators' unit: see conv3_split_wgrad_kernel)
-        Emin = first_tile ? E : min(Emin, E);
-        first_tile = false;
-        Enext = E;
-        const float sy = da_pow2(ey), sa = da_pow2(E - ey);
-#pragma unroll
-        for (int it = 0; it < NITA; ++it) {
-            const int idx0 = threadIdx.x + it * NT;
-            if (idx0 < TOTA) {
-                const int hv = idx0 >> 2;
-                const int idx = (c4 >> 1) * (PLH / 4) + hv * 2 + (c4 & 1) + ZPQ * (hv / (HY * HX));
-                uint2 h, l; da_split2(preA[it], sa, h, l);
-                reinterpret_cast<uint2*>(ldsA)[idx] = h; reinterpret_cast<uint2*>(ldsA)[idx + PLA / 4] = l;
-            }
-        }
-#pragma unroll
-        for (int it = 0; it < NITY; ++it) {
-            const int idx = threadIdx.x + it * NT;
-            if (idx < TVOX * QY) {
-                uint2 h, l; da_split2(preY[it], sy, h, l);
-                reinterpret_cast<uint2*>(ldsY)[idx] = h; reinterpret_cast<uint2*>(ldsY)[idx + PLY / 4] = l;
-            }
-        }
-    };
-    int4 tnext = fetch_tile(1);
-    if (tw.cnt > 0) { issue_loads(fetch_tile(0)); publish_max(); __syncthreads(); write_lds(); }
-    __syncthreads();
-    constexpr int NPR = SPL ? 3 : 1;
-    constexpr int PA[3] = {0, SPL ? 1 : 0, 0}, PB[3] = {SPL ? 1 : 0, 0, 0};      // (x, dY) plane pairs, small terms first (one plane: the single product)
-#pragma unroll 1
-    for (int tile = 0; tile < tw.cnt; ++tile) {
-        const bool has_next = tile + 1 < tw.cnt;
-        if (has_next && !(p.ablate & 1)) issue_loads(tnext);
-        tnext = fetch_tile(tile + 2);
-        if (SPL && Enext != Eacc) {
-            const float f = da_acc_factor(Enext - Eacc);
-#pragma unroll
-            for (int c = 0; c < 5; ++c)
-#pragma unroll
-                for (int d = 0; d < 3; ++d) acc[c][d] = acc[c][d] * f;
-            Eacc = Enext;
-        }
-        if (!(p.ablate & 2)) {
-        F3 Y0 = loadY(0), Y1 = loadY(1);
-        F3 Fa = loadF(0, 0), Fb = loadF(0, 1), Fc = loadF(0, 2), Fd, Na, Nb, Nc;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            Fd = loadF(c, 3);
-            Na = (c < 3) ? loadF(c + 1, 0) : loadG(0);
-#pragma unroll
-            for (int pr = 0; pr < NPR; ++pr) {
-                acc[c][0] = mma(acc[c][0], Fa.p[PA[pr]], Y0.p[PB[pr]]);
-                acc[c][1] = mma(acc[c][1], Fb.p[PA[pr]], Y0.p[PB[pr]]);
-                acc[c][2] = mma(acc[c][2], Fc.p[PA[pr]], Y0.p[PB[pr]]);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            if (c < 3) { Nb = loadF(c + 1, 1); Nc = loadF(c + 1, 2); } else { Nb = loadG(1); Nc = loadF(4, 2); }
-#pragma unroll
-            for (int pr = 0; pr < NPR; ++pr) {
-                acc[c][0] = mma(acc[c][0], Fb.p[PA[pr]], Y1.p[PB[pr]]);
-                acc[c][1] = mma(acc[c][1], Fc.p[PA[pr]], Y1.p[PB[pr]]);
-                acc[c][2] = mma(acc[c][2], Fd.p[PA[pr]], Y1.p[PB[pr]]);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            Fa = Na; Fb = Nb; Fc = Nc;
-        }
-        {
-            Fd = loadF(4, 3);
-#pragma unroll
-            for (int pr = 0; pr < NPR; ++pr) {
-                acc[4][0] = mma(acc[4][0], Fa.p[PA[pr]], Y0.p[PB[pr]]);
-                acc[4][1] = mma(acc[4][1], Fc.p[PA[pr]], Y0.p[PB[pr]]);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int pr = 0; pr < NPR; ++pr) {
-                acc[4][0] = mma(acc[4][0], Fb.p[PA[pr]], Y1.p[PB[pr]]);
-                acc[4][1] = mma(acc[4][1], Fd.p[PA[pr]], Y1.p[PB[pr]]);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        }
-        if (has_next && !(p.ablate & 4)) {
-            publish_max();
-            __syncthreads();
-            write_lds();
-            __syncthreads();
-        }
-    }
-    if constexpr (SPL) {
-        const float inv1 = da_pow2(-(Eacc / 2)), inv2 = da_pow2(-(Eacc - Eacc / 2));
-#pragma unroll
-        for (int c = 0; c < 5; ++c)
-#pragma unroll
-            for (int d = 0; d < 3; ++d) acc[c][d] = acc[c][d] * inv1 * inv2;
-    }
-    // reduce the four row-pair waves of each channel half through LDS (two rounds; 4 x 15 KB), then waves 0 and 4 write the slab's partial dW
-    __syncthreads();
-    float4* red = reinterpret_cast<float4*>(lds);
-    auto put = [&](int slot) {
-#pragma unroll
-        for (int c = 0; c < 5; ++c)
-#pragma unroll
-            for (int d = 0; d < 3; ++d) red[((slot * 15) + c * 3 + d) * 64 + lane] = make_float4(acc[c][d][0], acc[c][d][1], acc[c][d][2], acc[c][d][3]);
-    };
-    auto add = [&](int slot) {
-#pragma unroll
-        for (int c = 0; c < 5; ++c)
-#pragma unroll
-            for (int d = 0; d < 3; ++d) {
-                const float4 v = red[((slot * 15) + c * 3 + d) * 64 + lane];
-                acc[c][d][0] += v.x; acc[c][d][1] += v.y; acc[c][d][2] += v.z; acc[c][d][3] += v.w;
-            }
-    };
-    if (wr >= 2) put(2 * wh + wr - 2);
-    __syncthreads();
-    if (wr < 2) add(2 * wh + wr);
-    __syncthreads();
-    if (wr == 1) put(wh);
-    __syncthreads();
-    if (wr == 0) {
-        add(wh);
-        float* part = p.partial + (size_t)slab * p.O;
-        const int Cin = p.C1 + p.C2;
-        const int co = cg * CG + i;
-#pragma unroll
-        for (int c = 0; c < 5; ++c)
-#pragma unroll
-            for (int d = 0; d < 3; ++d)
-#pragma unroll
-                for (int reg = 0; reg < 4; ++reg) {
-                    const int row = 4 * g + reg;
-                    const int combo = c < 4 ? 2 * c + (row >> 3) : 8;
-                    const int dyt = c < 4 ? d : 2 * d + (row >> 3);
-                    const int tap = (combo / 3) * 9 + dyt * 3 + combo % 3, ci = wh * 8 + (row & 7);
-                    if (dyt < 3 && (c < 4 || d < 2) && co < p.Cout) part[((size_t)tap * Cin + cbase + ci) * p.Cout + co] = acc[c][d][reg];
-                }
-    }
-}
-
 #include "conv3d_wgring.h"      // conv3_split_wgrad16r_kernel: the eight-wave form walking z columns with the x planes in an LDS ring
 
 __global__ void slab_reduce_kernel(const float* __restrict__ partial, int nparts, int O, float* __restrict__ out) {
@@ -2056,8 +1700,8 @@ static size_t packed_bytes(int Cin, int Cout, int CK) {
     return da_align(b) + da_align(kWexpInts * sizeof(int));
 }
 
-struct WgPlan { int CK, NREP, ngroups, nchunks, ntz, nty, ntx, ntiles, nslabs, tps; size_t partial_bytes; int w16; };      // w16: 1 conv3_split_wgrad16_kernel (16-channel chunks, one 8-wave workgroup per CU), 2 its ring form conv3_split_wgrad16r_kernel
-static WgPlan wgrad_plan(int N, int D, int H, int W, int C1, int C2, int Cout, bool split = false, bool allow16 = false, bool allow_ring = false) {
+struct WgPlan { int CK, NREP, ngroups, nchunks, ntz, nty, ntx, ntiles, nslabs, tps; size_t partial_bytes; bool ring; };      // ring: the eight-wave ring form of conv3d_wgring.h (16-channel chunks, one workgroup per CU) instead of the four-wave row-owner kernel
+static WgPlan wgrad_plan(int N, int D, int H, int W, int C1, int C2, int Cout, bool split = false, bool allow_ring = false) {
     WgPlan q;
     q.CK = pick_ck(C1, C2);
     const int NT = (Cout + 15) / 16;
@@ -2065,22 +1709,20 @@ static WgPlan wgrad_plan(int N, int D, int H, int W, int C1, int C2, int Cout, b
     if (split && q.CK) { q.CK = 8; q.NREP = 1; }             // split mode: two fp16 planes of x and dY in LDS -> 8-channel chunks, one cout tile
     q.ngroups = (NT + q.NREP - 1) / q.NREP;
     q.nchunks = q.CK ? (C1 + C2) / q.CK : 1;
-    q.ntz = (split && q.CK) ? (D + DA_WG_TZ - 1) / DA_WG_TZ : (D + 1) / 2; q.nty = (H + TY - 1) / TY; q.ntx = (W + TX - 1) / TX;      // (the row-owner kernel: DA_WG_TZ planes per tile)
+    q.ntz = (D + 1) / 2; q.nty = (H + TY - 1) / TY; q.ntx = (W + TX - 1) / TX;      // (every weight-gradient kernel: two z planes per tile)
     q.ntiles = N * q.ntz * q.nty * q.ntx;
     const size_t O = (size_t)27 * (C1 + C2) * Cout;
     long long slabs = 512 / (q.nchunks * q.ngroups); if (slabs < 1) slabs = 1;      // one resident round: 2 workgroups / CU
     const long long cap = (long long)((96ull << 20) / (O * 4)); if (slabs > cap) slabs = cap < 1 ? 1 : cap;
-    q.w16 = 0;
-    if (allow16 && split && q.CK && C1 % 16 == 0 && C2 % 16 == 0 && DA_WG_TZ == 2) {
+    q.ring = false;
+    if (allow_ring && split && q.CK && C1 % 16 == 0 && C2 % 16 == 0) {
         static int on = -1; if (on < 0) { const char* e = getenv("DA_WG16"); on = (e && !atoi(e)) ? 0 : 1; }
         const int combos = ((C1 + C2) / 16) * q.ngroups;
         long long s16 = (256 / combos) & ~7ll;               // one workgroup per CU, a multiple of 8 slabs (XCD grouping) ...
         if (s16 * combos < 224) s16 = 256 / combos;          // ... or any slab count that fills the chip (tile_walk then walks one list): 192 -> 64 0.65 -> 0.60 ms, 96 -> 32 unchanged
-        if (on && s16 >= 1 && s16 * combos >= 224 && s16 <= cap && s16 <= q.ntiles) { q.w16 = 1; q.nchunks = (C1 + C2) / 16; slabs = s16; }
-        // the ring form (conv3d_wgring.h): fp32 tensors in split mode only; contiguous tile ranges per slab, so no multiple-of-8 rounding below
-        if (q.w16 && allow_ring) {
-            q.w16 = 2;
-            if (slabs > q.ntiles) slabs = q.ntiles;
+        if (on && s16 >= 1 && s16 * combos >= 224 && s16 <= cap && s16 <= q.ntiles) {
+            // the ring form (conv3d_wgring.h): contiguous tile ranges per slab, so no multiple-of-8 rounding below
+            q.ring = true; q.nchunks = (C1 + C2) / 16; slabs = s16;
             q.tps = (int)da_cdiv(q.ntiles, slabs);
             q.nslabs = (int)da_cdiv(q.ntiles, q.tps);           // (every slab non-empty)
             q.partial_bytes = da_align((size_t)q.nslabs * O * sizeof(float));
@@ -2111,7 +1753,7 @@ size_t da_conv3_mfma_ws_bytes(int N, int D, int H, int W, int Cin, int Cout, int
     if (Cin % 8 == 0) { const size_t a = packed_bytes(Cin, Cout, Cin % 16 == 0 ? 16 : 8); if (a > pk) pk = a; const size_t b = packed_bytes(Cin, Cout, 8); if (b > pk) pk = b; }
     if (Cout % 8 == 0) { const size_t a = packed_bytes(Cout, Cin, Cout % 16 == 0 ? 16 : 8); if (a > pk) pk = a; }
     size_t part = 0;
-    if (Cin % 8 == 0) { part = wgrad_plan(N, D, H, W, Cin, 0, Cout).partial_bytes; const size_t pr = wgrad_plan(N, D, H, W, Cin, 0, Cout, true, true, true).partial_bytes; if (pr > part) part = pr; }
+    if (Cin % 8 == 0) { part = wgrad_plan(N, D, H, W, Cin, 0, Cout).partial_bytes; const size_t pr = wgrad_plan(N, D, H, W, Cin, 0, Cout, true, true).partial_bytes; if (pr > part) part = pr; }
     if (Cin <= 4 && Cout <= 32) part = da_align((size_t)kScBlocksFwd * 27 * Cin * Cout * sizeof(float));
     if (Cout <= 4 && Cin <= 32) { const size_t sw = da_align((size_t)(kScBlocksFwd + 1) * 27 * Cin * Cout * sizeof(float)); if (sw > part) part = sw; }   // swapped-operand weight gradient
     return pk + tile_table_bytes(N, D, H, W) + part + wg_tile_table_bytes(N, D, H, W);
@@ -2129,22 +1771,36 @@ bool da_conv3_mfma_fwd_supported(int C1, int C2, int Cout, int stride, int Cs1, 
     return true;
 }
 
-template <int CK, int NREP, bool MASKED = false, int STATS = 0, bool BF = false, bool PRO = false, bool SP = false, int S2F = 0, bool PAIR = false, bool HB = false>
+// What a launcher's call site turns on in its kernel.  Each launcher maps its flag set onto the kernel template's positional parameters, in
+// one place; a combination the kernel does not support fails that kernel's static_asserts.
+enum : unsigned {
+    kStats = 1u << 0,       // forward: BatchNorm partial sums of the output
+    kBst = 1u << 1,         // forward (as the data gradient): BatchNorm-backward sums of the layer that produced the input
+    kBf16 = 1u << 2,        // bf16 matrix mode, fp32 tensors
+    kHb = 1u << 3,          // bf16 matrix mode, bf16 tensors (bf16 activation storage)
+    kSplit = 1u << 4,       // split mode (two fp16 planes)
+    kPro = 1u << 5,         // input prologue
+    kPair = 1u << 6,        // forward, split mode: paired staging
+    kS2dIn = 1u << 7,       // forward, sparse taps: X staged through the space-to-depth view
+    kD2sOut = 1u << 8,      // forward, sparse taps (data gradient): dX stored through the view
+    kMasked = 1u << 9,      // weight gradient: sparse taps
+    kScalarDy = 1u << 10,   // weight gradient: dY staged with dword loads (Cout % 4 != 0)
+};
+
+template <int CK, int NREP, unsigned F = 0>
 static int launch_fwd_mfma(const FwdP& p, int gy, hipStream_t st) {
+    static_assert((F & ~(kStats | kBst | kBf16 | kHb | kSplit | kPro | kPair | kS2dIn | kD2sOut)) == 0, "a flag the forward kernel does not have");
+    constexpr bool SP = (F & kSplit) != 0, HB = (F & kHb) != 0, BF = SP || HB || (F & kBf16) != 0, PRO = (F & kPro) != 0, PAIR = (F & kPair) != 0;
+    constexpr int STATS = (F & kBst) ? 2 : (F & kStats) ? 1 : 0, S2F = (F & kS2dIn) ? 1 : (F & kD2sOut) ? 2 : 0;
+    constexpr bool MASKED = S2F != 0;
+    constexpr auto kern = conv3_mfma_fwd_kernel<CK, NREP, MASKED, STATS, BF, PRO, SP, S2F, PAIR, HB>;
     const size_t shm = (size_t)6 * HY * HX * CK * (BF ? 2 : 4) * (SP ? 2 : 1) + (STATS ? (size_t)4 * 2 * NREP * 16 * sizeof(double) : 0) + (SP ? 16 : 0);
-    auto kern = conv3_mfma_fwd_kernel<CK, NREP, MASKED, STATS, BF, PRO, SP, S2F, PAIR, HB>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
-    { static int occ = -1; if (occ < 0) { occ = getenv("DA_OCC") ? 1 : 0; if (occ) { int nb = 0; (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, shm); fprintf(stderr, "[occ] <%d,%d,M%d,S%d,BF%d,PRO%d,SP%d> lds %zu B -> %d workgroups per CU\n", CK, NREP, (int)MASKED, (int)STATS, (int)BF, (int)PRO, (int)SP, shm, nb); } } }
     static unsigned long long* dclk = nullptr; static int want = -1;
     if (want < 0) { want = getenv("DA_CLK") ? 1 : 0; if (want) (void)hipMalloc(&dclk, 64 + 1024 * 16); }
     FwdP q = p; q.clk = want ? dclk : nullptr;
     if (want) { const unsigned long long init[6] = {0, 0, ~0ull, 0, ~0ull, 0}; (void)hipMemcpyAsync(dclk, init, 48, hipMemcpyHostToDevice, st); (void)hipStreamSynchronize(st); }
-    hipLaunchKernelGGL(kern, dim3(p.nblocks, gy), dim3(256), shm, st, q);
+    if (const int rc = da_launch_lds<kern>(dim3(p.nblocks, gy), dim3(256), shm, st, q)) return rc;
+    { static int occ = -1; if (occ < 0) { occ = getenv("DA_OCC") ? 1 : 0; if (occ) { int nb = 0; (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, shm); fprintf(stderr, "[occ] <%d,%d,M%d,S%d,BF%d,PRO%d,SP%d> lds %zu B -> %d workgroups per CU\n", CK, NREP, (int)MASKED, (int)STATS, (int)BF, (int)PRO, (int)SP, shm, nb); } } }
     if (want) {
         unsigned long long h[6]; (void)hipStreamSynchronize(st); (void)hipMemcpy(h, dclk, 48, hipMemcpyDeviceToHost);
         fprintf(stderr, "[clk] cycles %llu realtime %llu -> %.0f MHz; grid %d x %d: starts span %.1f us, ends span %.1f us, first start -> last end %.1f us\n", h[0], h[1],
@@ -2156,8 +1812,28 @@ static int launch_fwd_mfma(const FwdP& p, int gy, hipStream_t st) {
             for (int b = 0; b < nb; ++b) fprintf(stderr, "[blk] %d xcc %llu hwid %08llx life_us %.1f\n", b, (rec[2 * b] >> 32) & 15, rec[2 * b] & 0xffffffffull, rec[2 * b + 1] * 0.01);
         }
     }
-    DA_LAUNCH_CHECK();
     return 0;
+}
+
+// the three precisions of the matrix modes 0 and 1: fp32, bf16 operands of fp32 tensors, bf16 operands of bf16 tensors
+template <int CK, int NREP, unsigned F>
+static int launch_fwd_prec(bool bf, bool hb, const FwdP& p, int gy, hipStream_t st) {
+    return hb ? launch_fwd_mfma<CK, NREP, F | kHb>(p, gy, st) : bf ? launch_fwd_mfma<CK, NREP, F | kBf16>(p, gy, st) : launch_fwd_mfma<CK, NREP, F>(p, gy, st);
+}
+// ... of the dense kernels, 16- or 8-channel chunks and one or two N-tiles
+template <unsigned F>
+static int launch_fwd_dense(int CK, int NREP, bool bf, bool hb, const FwdP& p, int gy, hipStream_t st) {
+    if (CK == 16 && NREP == 1) return launch_fwd_prec<16, 1, F>(bf, hb, p, gy, st);
+    if (CK == 16 && NREP == 2) return launch_fwd_prec<16, 2, F>(bf, hb, p, gy, st);
+    if (CK == 8 && NREP == 1) return launch_fwd_prec<8, 1, F>(bf, hb, p, gy, st);
+    if (CK == 8 && NREP == 2) return launch_fwd_prec<8, 2, F>(bf, hb, p, gy, st);
+    return DA_ERR_UNSUPPORTED;
+}
+// the split mode's unpaired kernels
+template <int NREP>
+static int launch_fwd_split(bool stats, bool pro, const FwdP& p, int gy, hipStream_t st) {
+    return stats ? (pro ? launch_fwd_mfma<8, NREP, kSplit | kStats | kPro>(p, gy, st) : launch_fwd_mfma<8, NREP, kSplit | kStats>(p, gy, st))
+                 : (pro ? launch_fwd_mfma<8, NREP, kSplit | kPro>(p, gy, st) : launch_fwd_mfma<8, NREP, kSplit>(p, gy, st));
 }
 
 // identity scale / shift for an input without a prologue (the kernels load the constants unconditionally); one device per process
@@ -2337,45 +2013,29 @@ static int conv3_mfma_fwd_impl(const float* in1, int C1, const float* in2, int C
         if (want_bst) {                                      // (da_conv3d_k3_dgrad_bst checked the shape: one output tensor of <= 32 channels, no prologue)
             if (!(NREP == 1 && !pro && Cs2 == 0 && gy <= 2)) return DA_ERR_UNSUPPORTED;
             p.bst_y = g_bst.y; p.bst_par = g_bst.par; p.bst_slope = g_bst.slope;
-            return launch_fwd_mfma<8, 1, false, 2, true, false, true>(p, gy, st);      // (unpaired staging: with the pair's second parked chunk the eight y quads of the epilogue spill)
+            return launch_fwd_mfma<8, 1, kSplit | kBst>(p, gy, st);      // (unpaired staging: with the pair's second parked chunk the eight y quads of the epilogue spill)
         }
         if (NREP == 1 && !pro && C1 % 16 == 0 && C2 % 16 == 0)
-            return stats_partial ? launch_fwd_mfma<8, 1, false, true, true, false, true, 0, true>(p, gy, st)
-                                 : launch_fwd_mfma<8, 1, false, false, true, false, true, 0, true>(p, gy, st);
-#define DA_SP_CASE(nr) if (NREP == nr) return stats_partial ? (pro ? launch_fwd_mfma<8, nr, false, true, true, true, true>(p, gy, st) : launch_fwd_mfma<8, nr, false, true, true, false, true>(p, gy, st)) \
-                                                              : (pro ? launch_fwd_mfma<8, nr, false, false, true, true, true>(p, gy, st) : launch_fwd_mfma<8, nr, false, false, true, false, true>(p, gy, st))
-        DA_SP_CASE(1); DA_SP_CASE(2);
-#undef DA_SP_CASE
+            return stats_partial ? launch_fwd_mfma<8, 1, kSplit | kStats | kPair>(p, gy, st) : launch_fwd_mfma<8, 1, kSplit | kPair>(p, gy, st);
+        if (NREP == 1) return launch_fwd_split<1>(stats_partial != nullptr, pro != nullptr, p, gy, st);
+        if (NREP == 2) return launch_fwd_split<2>(stats_partial != nullptr, pro != nullptr, p, gy, st);
         return DA_ERR_UNSUPPORTED;
     }
     if (stats_partial && p.maskmode == 0 && (CK == 16 || CK == 8) && NREP <= 2) {
         if (stats_nparts) *stats_nparts = p.nblocks;
-#define DA_ST_CASE(ck, nr) if (CK == ck && NREP == nr) return pro ? (hb ? launch_fwd_mfma<ck, nr, false, true, true, true, false, 0, false, true>(p, gy, st) : bf ? launch_fwd_mfma<ck, nr, false, true, true, true>(p, gy, st) : launch_fwd_mfma<ck, nr, false, true, false, true>(p, gy, st)) \
-                                                                  : (hb ? launch_fwd_mfma<ck, nr, false, true, true, false, false, 0, false, true>(p, gy, st) : bf ? launch_fwd_mfma<ck, nr, false, true, true>(p, gy, st) : launch_fwd_mfma<ck, nr, false, true>(p, gy, st))
-        DA_ST_CASE(16, 1); DA_ST_CASE(16, 2); DA_ST_CASE(8, 1); DA_ST_CASE(8, 2);
-#undef DA_ST_CASE
+        return pro ? launch_fwd_dense<kStats | kPro>(CK, NREP, bf, hb, p, gy, st) : launch_fwd_dense<kStats>(CK, NREP, bf, hb, p, gy, st);
     }
-    if (pro) {
-#define DA_PRO_CASE(ck, nr) if (CK == ck && NREP == nr) return hb ? launch_fwd_mfma<ck, nr, false, false, true, true, false, 0, false, true>(p, gy, st) : bf ? launch_fwd_mfma<ck, nr, false, false, true, true>(p, gy, st) : launch_fwd_mfma<ck, nr, false, false, false, true>(p, gy, st)
-        DA_PRO_CASE(16, 1); DA_PRO_CASE(16, 2); DA_PRO_CASE(8, 1); DA_PRO_CASE(8, 2);
-#undef DA_PRO_CASE
+    if (pro) return launch_fwd_dense<kPro>(CK, NREP, bf, hb, p, gy, st);
+    if (p.maskmode != 0) {                                   // (CK == 16) 1: the forward stages X through the view, 2: the data gradient stores dX through it
+        if (NREP == 1) return p.maskmode == 1 ? launch_fwd_prec<16, 1, kS2dIn>(bf, hb, p, gy, st) : launch_fwd_prec<16, 1, kD2sOut>(bf, hb, p, gy, st);
+        if (NREP == 2) return p.maskmode == 1 ? launch_fwd_prec<16, 2, kS2dIn>(bf, hb, p, gy, st) : launch_fwd_prec<16, 2, kD2sOut>(bf, hb, p, gy, st);
         return DA_ERR_UNSUPPORTED;
     }
-    if (p.maskmode != 0) {
-        const int view = p.maskmode;                         // 1: the forward stages X through the view, 2: the data gradient stores dX through it
-#define DA_M_CASE(nr, f) if (NREP == nr && view == f) return hb ? launch_fwd_mfma<16, nr, true, false, true, false, false, f, false, true>(p, gy, st) : bf ? launch_fwd_mfma<16, nr, true, false, true, false, false, f>(p, gy, st) : launch_fwd_mfma<16, nr, true, false, false, false, false, f>(p, gy, st)
-        DA_M_CASE(1, 1); DA_M_CASE(1, 2); DA_M_CASE(2, 1); DA_M_CASE(2, 2);
-#undef DA_M_CASE
-        return DA_ERR_UNSUPPORTED;
+    if (NREP == 3 && !bf) {                                  // three N-tiles: the fp32 matrix mode only (NREP is capped at 2 above otherwise)
+        if (CK == 16) return launch_fwd_mfma<16, 3>(p, gy, st);
+        if (CK == 8) return launch_fwd_mfma<8, 3>(p, gy, st);
     }
-#define DA_FWD_CASE(ck, nr) if (CK == ck && NREP == nr) return bf ? launch_fwd_mfma<ck, nr, false, false, true>(p, gy, st) : launch_fwd_mfma<ck, nr>(p, gy, st)
-#define DA_FWD_CASE_HB(ck, nr) if (hb && CK == ck && NREP == nr) return launch_fwd_mfma<ck, nr, false, false, true, false, false, 0, false, true>(p, gy, st)
-    DA_FWD_CASE_HB(16, 1); DA_FWD_CASE_HB(16, 2); DA_FWD_CASE_HB(8, 1); DA_FWD_CASE_HB(8, 2);      // (bf16 mode: at most two N-tiles)
-#undef DA_FWD_CASE_HB
-    DA_FWD_CASE(16, 1); DA_FWD_CASE(16, 2); DA_FWD_CASE(16, 3);          // pick_nrep never asks for more than 3 N-tiles
-    DA_FWD_CASE(8, 1); DA_FWD_CASE(8, 2); DA_FWD_CASE(8, 3);
-#undef DA_FWD_CASE
-    return DA_ERR_UNSUPPORTED;
+    return launch_fwd_dense<0>(CK, NREP, bf, hb, p, gy, st);
 }
 
 // matrix mode of the 3x3x3 convolutions: process-wide switch (like da_set_conv_direct); the setters return the previous setting.
@@ -2483,82 +2143,71 @@ __global__ void swapped_wgrad_place_kernel(const float* __restrict__ tmp, float*
     }
 }
 
-template <int CK, int NREP, bool YS = false, bool MASKED = false, bool BF = false, bool PRO = false, bool SP = false, bool HB = false>
+template <int CK, int NREP, unsigned F = 0>
 static int launch_wgrad_mfma(const WgP& p, const WgPlan& q, hipStream_t st) {
+    static_assert((F & ~(kScalarDy | kMasked | kBf16 | kHb | kPro)) == 0, "a flag the tap-owner weight-gradient kernel does not have");
+    constexpr bool HB = (F & kHb) != 0, BF = HB || (F & kBf16) != 0;
+    constexpr auto kern = conv3_mfma_wgrad_kernel<CK, NREP, (F & kScalarDy) != 0, (F & kMasked) != 0, BF, (F & kPro) != 0, false, HB>;
     const size_t shm = (size_t)(4 * HY * HX * CK + 2 * TY * TX * NREP * 16) * (BF ? 2 : 4);
-    auto kern = conv3_mfma_wgrad_kernel<CK, NREP, YS, MASKED, BF, PRO, SP, HB>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(q.nslabs, q.nchunks, q.ngroups), dim3(256), shm, st, p);
-    DA_LAUNCH_CHECK();
-    return 0;
+    return da_launch_lds<kern>(dim3(q.nslabs, q.nchunks, q.ngroups), dim3(256), shm, st, p);
+}
+// its three precisions (see launch_fwd_prec), and the dense kernels' chunk widths and N-tile counts
+template <int CK, int NREP, unsigned F>
+static int launch_wgrad_prec(bool bf, bool hb, const WgP& p, const WgPlan& q, hipStream_t st) {
+    // (bf16 tensors, dense taps, one cout tile: da_conv3_mfma_wgrad sends them to the row-owner / ring kernels -- rows1 -- so no tap-owner kernel exists for them)
+    if constexpr (NREP == 1 && !(F & kMasked)) { if (hb) return DA_ERR_UNSUPPORTED; }
+    else if (hb) return launch_wgrad_mfma<CK, NREP, F | kHb>(p, q, st);
+    return bf ? launch_wgrad_mfma<CK, NREP, F | kBf16>(p, q, st) : launch_wgrad_mfma<CK, NREP, F>(p, q, st);
+}
+template <unsigned F>
+static int launch_wgrad_dense(bool bf, bool hb, const WgP& p, const WgPlan& q, hipStream_t st) {
+    if (q.CK == 16 && q.NREP == 1) return launch_wgrad_prec<16, 1, F>(bf, hb, p, q, st);
+    if (q.CK == 16 && q.NREP == 2) return launch_wgrad_prec<16, 2, F>(bf, hb, p, q, st);
+    if (q.CK == 8 && q.NREP == 1) return launch_wgrad_prec<8, 1, F>(bf, hb, p, q, st);
+    if (q.CK == 8 && q.NREP == 2) return launch_wgrad_prec<8, 2, F>(bf, hb, p, q, st);
+    return DA_ERR_UNSUPPORTED;
 }
 
-template <bool PRO, int NPL = 2, bool HB = false>
+// Row-owner kernel: kHb = the one-plane bf16 form on bf16 tensors, else the split mode's two fp16 planes of fp32 tensors
+template <unsigned F>
 static int launch_split_wgrad(const WgP& p, const WgPlan& q, hipStream_t st) {
-    size_t shm = (size_t)((DA_WG_TZ + 2) * (HY * HX * 8 + 4 * DA_WG_ZPAD) + DA_WG_TZ * TY * TX * 16) * 2 * NPL + 32;      // + the waves' tile maxima (split mode)
+    static_assert((F & ~(kPro | kHb)) == 0, "a flag the row-owner weight-gradient kernel does not have");
+    constexpr bool HB = (F & kHb) != 0;
+    constexpr int NPL = HB ? 1 : 2;
+    size_t shm = (size_t)(4 * (HY * HX * 8 + 4 * DA_WG_ZPAD) + 2 * TY * TX * 16) * 2 * NPL + 32;      // + the waves' tile maxima (split mode)
     if (shm < (size_t)2 * 15 * 64 * sizeof(float4)) shm = (size_t)2 * 15 * 64 * sizeof(float4);      // the cross-wave reduction at the end reuses the tiles' LDS
-    auto kern = conv3_split_wgrad_kernel<PRO, NPL, HB>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(q.nslabs, q.nchunks, q.ngroups), dim3(256), shm, st, p);
-    DA_LAUNCH_CHECK();
-    return 0;
+    return da_launch_lds<conv3_split_wgrad_kernel<(F & kPro) != 0, NPL, HB>>(dim3(q.nslabs, q.nchunks, q.ngroups), dim3(256), shm, st, p);
 }
-
-template <bool PRO, int NPL = 2, bool HB = false>
-static int launch_split_wgrad16(const WgP& p, const WgPlan& q, hipStream_t st) {
-    size_t shm = (size_t)(2 * 4 * (HY * HX * 8 + 4 * DA_WG16_ZPAD) + 2 * TY * TX * 16) * 2 * NPL + 128;      // the tile's planes + the waves' maxima
-    if (shm < (size_t)4 * 15 * 64 * sizeof(float4)) shm = (size_t)4 * 15 * 64 * sizeof(float4);      // the cross-wave reduction at the end reuses the tile's LDS
-    auto kern = conv3_split_wgrad16_kernel<PRO, NPL, HB>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(q.nslabs, q.nchunks, q.ngroups), dim3(512), shm, st, p);
-    DA_LAUNCH_CHECK();
-    return 0;
-}
-
-template <bool PRO>
+// Ring form (conv3d_wgring.h), split mode
+template <unsigned F>
 static int launch_split_wgrad16r(const WgP& p, const WgPlan& q, hipStream_t st) {
+    static_assert((F & ~kPro) == 0, "a flag the ring weight-gradient kernel does not have");
     // six plane slots x two half images x two fp16 planes + two dY buffers of two planes + the waves' maxima (2 parities x 3 x 8 floats)
     size_t shm = (size_t)(2 * 2 * 6 * (HY * HX * 8 + 4 * DA_WG16_ZPAD)) * 2 + (size_t)(2 * 2 * 2 * TY * TX * 16) * 2 + 2 * 24 * sizeof(float) + 8 * sizeof(float4);      // (+ the prologue's scale / shift quads)
     if (shm < (size_t)4 * 15 * 64 * sizeof(float4)) shm = (size_t)4 * 15 * 64 * sizeof(float4);
-    auto kern = conv3_split_wgrad16r_kernel<PRO>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(q.nslabs, q.nchunks, q.ngroups), dim3(512), shm, st, p);
-    DA_LAUNCH_CHECK();
-    return 0;
+    return da_launch_lds<conv3_split_wgrad16r_kernel<(F & kPro) != 0>>(dim3(q.nslabs, q.nchunks, q.ngroups), dim3(512), shm, st, p);
 }
-
-template <bool PRO>
+// ... and bf16 storage (one bf16 plane)
+template <unsigned F>
 static int launch_bf16_wgrad16r(const WgP& p, const WgPlan& q, hipStream_t st) {
+    static_assert((F & ~kPro) == 0, "a flag the ring weight-gradient kernel does not have");
     size_t shm = (size_t)(2 * 6 * (HY * HX * 8 + 4 * DA_WG16_ZPAD)) * 2 + (size_t)(2 * 2 * TY * TX * 16) * 2 + 8 * sizeof(float4);
     if (shm < (size_t)4 * 15 * 64 * sizeof(float4)) shm = (size_t)4 * 15 * 64 * sizeof(float4);
-    auto kern = conv3_bf16_wgrad16r_kernel<PRO>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(q.nslabs, q.nchunks, q.ngroups), dim3(512), shm, st, p);
+    return da_launch_lds<conv3_bf16_wgrad16r_kernel<(F & kPro) != 0>>(dim3(q.nslabs, q.nchunks, q.ngroups), dim3(512), shm, st, p);
+}
+// the row-owner / ring kernels of the split mode, or (rows1) of bf16 storage
+template <unsigned F>
+static int launch_rows_wgrad(bool rows1, const WgP& p, const WgPlan& q, hipStream_t st) {
+    if (rows1) return q.ring ? launch_bf16_wgrad16r<F>(p, q, st) : launch_split_wgrad<F | kHb>(p, q, st);
+    return q.ring ? launch_split_wgrad16r<F>(p, q, st) : launch_split_wgrad<F>(p, q, st);
+}
+
+// the small-Cin weight gradient's MT x NT kernels (also the swapped-operand route of very few output channels)
+static int launch_smallcin_wgrad(int MT, int NT, int nb, const ScP& sp, hipStream_t st) {
+#define DA_SC_CASE(mt, nt) if (MT == mt && NT == nt) hipLaunchKernelGGL((conv3_smallcin_wgrad_kernel<mt, nt>), dim3(nb), dim3(256), 0, st, sp)
+    DA_SC_CASE(2, 1); else DA_SC_CASE(2, 2); else DA_SC_CASE(4, 1); else DA_SC_CASE(4, 2); else DA_SC_CASE(6, 1); else DA_SC_CASE(6, 2);
+    else DA_SC_CASE(7, 1); else DA_SC_CASE(7, 2); else return DA_ERR_UNSUPPORTED;
+#undef DA_SC_CASE
     DA_LAUNCH_CHECK();
     return 0;
 }
@@ -2584,11 +2233,7 @@ int da_conv3_mfma_wgrad(const float* in1, int C1, const float* in2, int C2, cons
         sp.N = N; sp.D = D; sp.H = H; sp.W = W; sp.Cout = Cout; sp.nrows = (long long)N * D * H; sp.dyb = nullptr; sp.Cd1 = Cout;
         int nb = (int)da_cdiv(sp.nrows, 4); if (nb > kScBlocks) nb = kScBlocks;
         const int MT = (27 * Cin + 15) / 16, NT = (Cout + 15) / 16;
-#define DA_SC_CASE(mt, nt) if (MT == mt && NT == nt) hipLaunchKernelGGL((conv3_smallcin_wgrad_kernel<mt, nt>), dim3(nb), dim3(256), 0, st, sp)
-        DA_SC_CASE(2, 1); else DA_SC_CASE(2, 2); else DA_SC_CASE(4, 1); else DA_SC_CASE(4, 2); else DA_SC_CASE(6, 1); else DA_SC_CASE(6, 2);
-        else DA_SC_CASE(7, 1); else DA_SC_CASE(7, 2); else return DA_ERR_UNSUPPORTED;
-#undef DA_SC_CASE
-        DA_LAUNCH_CHECK();
+        if (const int rcs = launch_smallcin_wgrad(MT, NT, nb, sp, st)) return rcs;
         { const int rc2 = da_reduce_partials(sp.partial, nb, O, dw_tio, st); if (rc2) return rc2; }
         return 0;
     }
@@ -2608,11 +2253,7 @@ int da_conv3_mfma_wgrad(const float* in1, int C1, const float* in2, int C2, cons
         sp.partial = (float*)ws; sp.N = N; sp.D = D; sp.H = H; sp.W = W; sp.nrows = (long long)N * D * H;
         int nb = (int)da_cdiv(sp.nrows, 4); if (nb > kScBlocks) nb = kScBlocks;
         const int MT = (27 * Cout + 15) / 16, NT = (Cin + 15) / 16;
-#define DA_SC_CASE(mt, nt) if (MT == mt && NT == nt) hipLaunchKernelGGL((conv3_smallcin_wgrad_kernel<mt, nt>), dim3(nb), dim3(256), 0, st, sp)
-        DA_SC_CASE(2, 1); else DA_SC_CASE(2, 2); else DA_SC_CASE(4, 1); else DA_SC_CASE(4, 2); else DA_SC_CASE(6, 1); else DA_SC_CASE(6, 2);
-        else DA_SC_CASE(7, 1); else DA_SC_CASE(7, 2); else return DA_ERR_UNSUPPORTED;
-#undef DA_SC_CASE
-        DA_LAUNCH_CHECK();
+        if (const int rcs = launch_smallcin_wgrad(MT, NT, nb, sp, st)) return rcs;
         float* tmp = (float*)ws + (size_t)kScBlocks * O;
         { const int rc2 = da_reduce_partials(sp.partial, nb, O, tmp, st); if (rc2) return rc2; }
         hipLaunchKernelGGL(swapped_wgrad_place_kernel, dim3(da_grid(O, 256, 64)), dim3(256), 0, st, tmp, dw_tio, Cin, Cout);
@@ -2625,7 +2266,7 @@ int da_conv3_mfma_wgrad(const float* in1, int C1, const float* in2, int C2, cons
     // (measured, 2 x 160 x 192 x 160: bf16 storage 48 -> 16 1.23 -> 1.09 ms, 16 -> 16 0.42 -> 0.38; NOT for more than one cout tile -- 96 -> 32: 0.44 ->
     // 0.70 ms, the kernel re-stages x per 16-cout group -- and not with fp32 tensors, 1.21 -> 1.94 ms: there the staging conversions dominate)
     const bool rows1 = hb && da_matrix_mode() == 1 && s2d_cin == 0 && Cout % 4 == 0 && Cout <= 16 && pick_ck(C1, C2) != 0;
-    const WgPlan q = wgrad_plan(N, D, H, W, C1, C2, Cout, split || rows1, split || rows1, (split && !hb) || rows1);
+    const WgPlan q = wgrad_plan(N, D, H, W, C1, C2, Cout, split || rows1, split || rows1);
     if (!q.CK) return DA_ERR_UNSUPPORTED;
     const bool bf = da_matrix_bf16();      // (Cout % 4 != 0 keeps the exact kernel: its dY staging is scalar)
     if ((unsigned long long)D * H * W * 4ull * (unsigned long long)((C1 > C2 ? C1 : C2) > Cout ? (C1 > C2 ? C1 : C2) : Cout) >= 0xFFFFFFF0ull) return DA_ERR_UNSUPPORTED;
@@ -2636,8 +2277,8 @@ int da_conv3_mfma_wgrad(const float* in1, int C1, const float* in2, int C2, cons
     { static int abl = -1; if (abl < 0) { const char* e = getenv("DA_WG_ABLATE"); abl = e ? atoi(e) : 0; } p.ablate = abl; }
     if (split || rows1) {
         int4* tiles = reinterpret_cast<int4*>(reinterpret_cast<char*>(ws) + q.partial_bytes);
-        if (q.w16 >= 2) tiles = nullptr;           // (the ring form derives its tiles from the position: no table, no launch)
-        else hipLaunchKernelGGL(wgrad_tiles_kernel, dim3(da_grid(q.ntiles, 256, 256)), dim3(256), 0, st, tiles, q.ntiles, q.ntx, q.nty, q.ntz, DA_WG_TZ);
+        if (q.ring) tiles = nullptr;               // (the ring form derives its tiles from the position: no table, no launch)
+        else hipLaunchKernelGGL(wgrad_tiles_kernel, dim3(da_grid(q.ntiles, 256, 256)), dim3(256), 0, st, tiles, q.ntiles, q.ntx, q.nty, q.ntz, 2);
         DA_LAUNCH_CHECK();
         p.tiles = tiles;
     }
@@ -2657,34 +2298,19 @@ int da_conv3_mfma_wgrad(const float* in1, int C1, const float* in2, int C2, cons
         if (pro_slopes(pro, C2, &p.pslope1, &p.pslope2)) return DA_ERR_UNSUPPORTED;
         p.ps1 = pro->s1 ? pro->s1 : ones; p.pt1 = pro->s1 ? pro->t1 : zeros;
         p.ps2 = (C2 > 0 && pro->s2) ? pro->s2 : ones; p.pt2 = (C2 > 0 && pro->s2) ? pro->t2 : zeros;
-        int rcp = DA_ERR_UNSUPPORTED;
-        if (split) rcp = q.w16 >= 2 ? launch_split_wgrad16r<true>(p, q, st) : q.w16 ? launch_split_wgrad16<true>(p, q, st) : launch_split_wgrad<true>(p, q, st);
-        else if (rows1) rcp = q.w16 >= 2 ? launch_bf16_wgrad16r<true>(p, q, st) : q.w16 ? launch_split_wgrad16<true, 1, true>(p, q, st) : launch_split_wgrad<true, 1, true>(p, q, st);
-        else
-#define DA_WP_CASE(ck, nr) if (q.CK == ck && q.NREP == nr) rcp = hb ? launch_wgrad_mfma<ck, nr, false, false, true, true, false, true>(p, q, st) : bf ? launch_wgrad_mfma<ck, nr, false, false, true, true>(p, q, st) : launch_wgrad_mfma<ck, nr, false, false, false, true>(p, q, st)
-        { DA_WP_CASE(16, 1); DA_WP_CASE(16, 2); DA_WP_CASE(8, 1); DA_WP_CASE(8, 2); }
-#undef DA_WP_CASE
-        if (rcp) return rcp;
-        return da_reduce_partials(p.partial, q.nslabs, p.O, dw_tio, st);
     }
     int rc = DA_ERR_UNSUPPORTED;
-    if (split) rc = q.w16 >= 2 ? launch_split_wgrad16r<false>(p, q, st) : q.w16 ? launch_split_wgrad16<false>(p, q, st) : launch_split_wgrad<false>(p, q, st);
-    else if (rows1) rc = q.w16 >= 2 ? launch_bf16_wgrad16r<false>(p, q, st) : q.w16 ? launch_split_wgrad16<false, 1, true>(p, q, st) : launch_split_wgrad<false, 1, true>(p, q, st);
+    if (split || rows1) rc = pro ? launch_rows_wgrad<kPro>(rows1, p, q, st) : launch_rows_wgrad<0>(rows1, p, q, st);
+    else if (pro) rc = launch_wgrad_dense<kPro>(bf, hb, p, q, st);
     else if (p.maskmode != 0) {
         if (Cout % 4 != 0) return DA_ERR_UNSUPPORTED;
-        if (hb) rc = (q.NREP == 1) ? launch_wgrad_mfma<16, 1, false, true, true, false, false, true>(p, q, st) : launch_wgrad_mfma<16, 2, false, true, true, false, false, true>(p, q, st);
-        else if (bf) rc = (q.NREP == 1) ? launch_wgrad_mfma<16, 1, false, true, true>(p, q, st) : launch_wgrad_mfma<16, 2, false, true, true>(p, q, st);
-        else rc = (q.NREP == 1) ? launch_wgrad_mfma<16, 1, false, true>(p, q, st) : launch_wgrad_mfma<16, 2, false, true>(p, q, st);
+        rc = (q.NREP == 1) ? launch_wgrad_prec<16, 1, kMasked>(bf, hb, p, q, st) : launch_wgrad_prec<16, 2, kMasked>(bf, hb, p, q, st);
     }
-    else if (Cout % 4 != 0 && q.CK == 16) rc = launch_wgrad_mfma<16, 1, true>(p, q, st);
-    else if (Cout % 4 != 0 && q.CK == 8) rc = launch_wgrad_mfma<8, 1, true>(p, q, st);
-    else if (q.CK == 16 && q.NREP == 1) rc = hb ? launch_wgrad_mfma<16, 1, false, false, true, false, false, true>(p, q, st) : bf ? launch_wgrad_mfma<16, 1, false, false, true>(p, q, st) : launch_wgrad_mfma<16, 1>(p, q, st);
-    else if (q.CK == 16 && q.NREP == 2) rc = hb ? launch_wgrad_mfma<16, 2, false, false, true, false, false, true>(p, q, st) : bf ? launch_wgrad_mfma<16, 2, false, false, true>(p, q, st) : launch_wgrad_mfma<16, 2>(p, q, st);
-    else if (q.CK == 8 && q.NREP == 1) rc = hb ? launch_wgrad_mfma<8, 1, false, false, true, false, false, true>(p, q, st) : bf ? launch_wgrad_mfma<8, 1, false, false, true>(p, q, st) : launch_wgrad_mfma<8, 1>(p, q, st);
-    else if (q.CK == 8 && q.NREP == 2) rc = hb ? launch_wgrad_mfma<8, 2, false, false, true, false, false, true>(p, q, st) : bf ? launch_wgrad_mfma<8, 2, false, false, true>(p, q, st) : launch_wgrad_mfma<8, 2>(p, q, st);
+    else if (Cout % 4 != 0 && q.CK == 16) rc = launch_wgrad_mfma<16, 1, kScalarDy>(p, q, st);
+    else if (Cout % 4 != 0 && q.CK == 8) rc = launch_wgrad_mfma<8, 1, kScalarDy>(p, q, st);
+    else rc = launch_wgrad_dense<0>(bf, hb, p, q, st);
     if (rc) return rc;
-    { const int rc2 = da_reduce_partials(p.partial, q.nslabs, p.O, dw_tio, st); if (rc2) return rc2; }
-    return 0;
+    return da_reduce_partials(p.partial, q.nslabs, p.O, dw_tio, st);
 }
 
 // ---- C ABI of the kept packs (see PrepackState) --------------------------------------------------------------------------------------------

@@ -670,9 +670,6 @@ int s2n_wgrad_slabs(int ntiles, int nchunks, int ngroups) {
     if (s > ntiles) s = ntiles;
     return s < 1 ? 1 : s;
 }
-template <typename K> int s2n_set_lds(K kern, size_t bytes) {
-    return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
 
 }  // namespace
 
@@ -704,11 +701,7 @@ int da_conv3_s2n_fwd(const float* in, int Cin, const float* w_tio, const float* 
     p.ntz = q.ntz; p.nty = q.nty; p.ntx = q.ntx; p.nchunks = Cin / 8; p.NT = Cout / 16; p.slope = slope;
     hipLaunchKernelGGL(s2n_pack_fwd_kernel, dim3(p.nchunks, 4), dim3(256), 0, st, w_tio, (unsigned short*)((unsigned char*)ws + 256), (int*)ws, Cin, Cout, p.NT);
     DA_LAUNCH_CHECK();
-    static bool attr = false;
-    if (!attr) { const int e = s2n_set_lds(s2n_fwd_kernel, NPLN * PLANE_B + 16); if (e) return e; attr = true; }
-    hipLaunchKernelGGL(s2n_fwd_kernel, dim3(q.ntiles, Cout / 32), dim3(256), NPLN * PLANE_B + 16, st, p);
-    DA_LAUNCH_CHECK();
-    return 0;
+    return da_launch_lds<s2n_fwd_kernel>(dim3(q.ntiles, Cout / 32), dim3(256), NPLN * PLANE_B + 16, st, p);
 }
 
 int da_conv3_s2n_dgrad(const float* dy, const float* w_tio, float* dx, int Cin, int N, int D, int H, int W, int Cout,
@@ -722,17 +715,11 @@ int da_conv3_s2n_dgrad(const float* dy, const float* w_tio, float* dx, int Cin, 
     hipLaunchKernelGGL(s2n_pack_dgrad_kernel, dim3(da_grid((long long)27 * p.KS * p.NTN * 64, 256, 32)), dim3(256), 0, st, w_tio, (unsigned short*)((unsigned char*)ws + 256), (int*)ws, Cin, Cout, p.KS, p.NTN);
     DA_LAUNCH_CHECK();
     const size_t shm = (size_t)NPLN * (Cout / 8) * GV * 16 + 16;
-    static bool attr[3] = {false, false, false};
-    int e = 0;
-    switch (p.NTN) {
-        case 1: if (!attr[1]) { e = s2n_set_lds(s2n_dgrad_kernel<1>, 98304); if (e) return e; attr[1] = true; }
-                hipLaunchKernelGGL(s2n_dgrad_kernel<1>, dim3(q.ntiles), dim3(256), shm, st, p); break;
-        case 2: if (!attr[2]) { e = s2n_set_lds(s2n_dgrad_kernel<2>, 98304); if (e) return e; attr[2] = true; }
-                hipLaunchKernelGGL(s2n_dgrad_kernel<2>, dim3(q.ntiles), dim3(256), shm, st, p); break;
+    switch (p.NTN) {      // (shm grows with Cout: the attribute is the bound of Cout = 64)
+        case 1: return da_launch_lds<s2n_dgrad_kernel<1>, 98304>(dim3(q.ntiles), dim3(256), shm, st, p);
+        case 2: return da_launch_lds<s2n_dgrad_kernel<2>, 98304>(dim3(q.ntiles), dim3(256), shm, st, p);
         default: return DA_ERR_UNSUPPORTED;
     }
-    DA_LAUNCH_CHECK();
-    return 0;
 }
 
 int da_conv3_s2n_wgrad(const float* in, int Cin, const float* dy, float* dw_tio, int N, int D, int H, int W, int Cout,
@@ -748,9 +735,6 @@ int da_conv3_s2n_wgrad(const float* in, int Cin, const float* dy, float* dw_tio,
     // every (chunk, group) workgroup of a slab writes its own (tap, cin chunk, cout group) block of the slab's partial: the blocks are
     // disjoint and together cover all O entries, so the partial needs no zero fill
     const size_t shm = (size_t)NPLN * PLANE_B + NPLN * YPLANE_B + 32;
-    static bool attr = false;
-    if (!attr) { const int e = s2n_set_lds(s2n_wgrad_kernel, shm); if (e) return e; attr = true; }
-    hipLaunchKernelGGL(s2n_wgrad_kernel, dim3(p.nslabs, nchunks, ngroups), dim3(256), shm, st, p);
-    DA_LAUNCH_CHECK();
+    if (const int rc = da_launch_lds<s2n_wgrad_kernel>(dim3(p.nslabs, nchunks, ngroups), dim3(256), shm, st, p)) return rc;
     return da_reduce_partials(p.partial, p.nslabs, p.O, dw_tio, st);
 }

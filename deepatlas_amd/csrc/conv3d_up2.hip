@@ -733,9 +733,6 @@ int up_wgrad_slabs(int ntiles, int nchunks) {
     if (s > ntiles) s = ntiles;
     return s < 1 ? 1 : s;
 }
-template <typename K> int up_set_lds(K kern, size_t bytes) {
-    return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
 
 }  // namespace
 
@@ -779,16 +776,8 @@ extern "C" int da_upconv3d_k3_fwd(const float* s1, int C1, const float* s2, int 
     hipLaunchKernelGGL(up_pack_fwd_kernel, dim3(p.nchunks, 4 * p.NTall), dim3(256), 0, st, w_tio, (unsigned short*)((unsigned char*)ws + 256), (int*)ws, Cin, Cout, p.NTall);
     DA_LAUNCH_CHECK();
     const size_t shm = NPLN * SPLANE_B + 16;
-    static bool a1 = false, a2 = false;
-    if (p.NTall == 1) {
-        if (!a1) { const int e = up_set_lds(up_fwd_kernel<1>, shm); if (e) return e; a1 = true; }
-        hipLaunchKernelGGL(up_fwd_kernel<1>, dim3(q.ntiles, 1), dim3(256), shm, st, p);
-    } else {
-        if (!a2) { const int e = up_set_lds(up_fwd_kernel<2>, shm); if (e) return e; a2 = true; }
-        hipLaunchKernelGGL(up_fwd_kernel<2>, dim3(q.ntiles, 1), dim3(256), shm, st, p);
-    }
-    DA_LAUNCH_CHECK();
-    return 0;
+    if (p.NTall == 1) return da_launch_lds<up_fwd_kernel<1>>(dim3(q.ntiles, 1), dim3(256), shm, st, p);
+    return da_launch_lds<up_fwd_kernel<2>>(dim3(q.ntiles, 1), dim3(256), shm, st, p);
 }
 
 extern "C" int da_upconv3d_k3_dgrad(const float* dy, const float* w_tio, float* dx1, int C1, float* dx2, int C2,
@@ -808,19 +797,12 @@ extern "C" int da_upconv3d_k3_dgrad(const float* dy, const float* w_tio, float* 
     hipLaunchKernelGGL(up_pack_dgrad_kernel, dim3(p.nchunks, 4 * NTN), dim3(256), 0, st, w_tio, (unsigned short*)((unsigned char*)ws + 256), (int*)ws, Cin, Cout, NTN);
     DA_LAUNCH_CHECK();
     const size_t shm = NPLN * FPLANE_B + 16;
-    static bool a[5] = {false, false, false, false, false};
-    int e = 0;
     switch (NTN) {
-        case 1: if (!a[1]) { e = up_set_lds(up_dgrad_kernel<1>, shm); if (e) return e; a[1] = true; }
-                hipLaunchKernelGGL(up_dgrad_kernel<1>, dim3(q.ntiles), dim3(256), shm, st, p); break;
-        case 2: if (!a[2]) { e = up_set_lds(up_dgrad_kernel<2>, shm); if (e) return e; a[2] = true; }
-                hipLaunchKernelGGL(up_dgrad_kernel<2>, dim3(q.ntiles), dim3(256), shm, st, p); break;
-        case 4: if (!a[4]) { e = up_set_lds(up_dgrad_kernel<4>, shm); if (e) return e; a[4] = true; }
-                hipLaunchKernelGGL(up_dgrad_kernel<4>, dim3(q.ntiles), dim3(256), shm, st, p); break;
+        case 1: return da_launch_lds<up_dgrad_kernel<1>>(dim3(q.ntiles), dim3(256), shm, st, p);
+        case 2: return da_launch_lds<up_dgrad_kernel<2>>(dim3(q.ntiles), dim3(256), shm, st, p);
+        case 4: return da_launch_lds<up_dgrad_kernel<4>>(dim3(q.ntiles), dim3(256), shm, st, p);
         default: return DA_ERR_UNSUPPORTED;
     }
-    DA_LAUNCH_CHECK();
-    return 0;
 }
 
 extern "C" int da_upconv3d_k3_wgrad(const float* s1, int C1, const float* s2, int C2, const float* dy, float* dw_tio,
@@ -837,10 +819,7 @@ extern "C" int da_upconv3d_k3_wgrad(const float* s1, int C1, const float* s2, in
     const int nchunks = Cin / 8;
     p.nslabs = up_wgrad_slabs(q.ntiles, nchunks); p.O = 64 * Cin * Cout;
     const size_t shm = (size_t)NPLN * SPLANE_B + NPLN * YPLANE_B + 32;
-    static bool attr = false;
-    if (!attr) { const int e = up_set_lds(up_wgrad_kernel, shm); if (e) return e; attr = true; }
-    hipLaunchKernelGGL(up_wgrad_kernel, dim3(p.nslabs, nchunks, 8), dim3(256), shm, st, p);
-    DA_LAUNCH_CHECK();
+    if (const int rc = da_launch_lds<up_wgrad_kernel>(dim3(p.nslabs, nchunks, 8), dim3(256), shm, st, p)) return rc;
     hipLaunchKernelGGL(up_wgrad_reduce_kernel, dim3(da_grid((long long)27 * Cin * Cout * 8, 256, 2048)), dim3(256), 0, st, p.partial, p.nslabs, Cin, Cout, dw_tio);
     DA_LAUNCH_CHECK();
     return 0;

@@ -1,7 +1,10 @@
-// Split-mode weight gradient, fourth form: the eight-wave 16-channel kernel of conv3d_mfma.hip (conv3_split_wgrad16_kernel) walking z COLUMNS
-// with the x halo planes in an LDS RING.  Included by conv3d_mfma.hip inside its anonymous namespace (WgP, the staging helpers, split_f16.h).
+// Split-mode weight gradient, ring form: eight waves on 16-channel chunks walking z COLUMNS with the x halo planes in an LDS RING.
+// Included by conv3d_mfma.hip inside its anonymous namespace (WgP, the staging helpers, split_f16.h).
 //
-// Why.  conv3_split_wgrad16_kernel stages a 4 x 10 x 18 halo box for every 2 x 8 x 16 output tile: 2.81 x the tile's voxels, every tile, through the
+// Why.  A chunk of 16 channels is one whole 64-byte sector per voxel (the row-owner kernel's 8-channel chunks use half of every sector they ask
+// for); waves 0 - 3 own the chunk's first 8 channels, waves 4 - 7 the second 8, each with the row-owner kernel's per-wave program (two output rows,
+// all 27 taps) on a shared dY tile; one workgroup per CU.  Staging a 4 x 10 x 18 halo box for every 2 x 8 x 16 output tile, as the row-owner kernel
+// does, loads 2.81 x the tile's voxels, every tile, through the
 // L1 -- 7.1 GB per launch of the 48 -> 16 layer against 2.5 GB of tensors, at the ~10 B / clk / CU an L1 sustains on 64-byte sector requests
 // (profiles/r04_wgrad_memory_path.txt: the staging loads ALONE take the row-owner kernel's whole time).  A weight gradient keeps its sums per
 // (tap, cin, cout) and only walks voxels, so a workgroup can walk a z column: consecutive tiles (z0, z0 + 2, ...) share two of their four halo
@@ -18,7 +21,7 @@
 // tiles; a run ends at the end of a column, at the end of the workgroup's range, or when the incoming slab does not fit the scale: it would
 // overflow fp16 (its ideal exponent e_new < ea) or the tile's own window {upper slab, new slab} would sit more than 2^3 below the ideal scale
 // (ea < min(e_up, e_new) - 3).  The next run starts with a whole-tile load and a fresh scale.  What a tile's x operands get is therefore the
-// same as in the row-owner / eight-wave kernels, whose accumulator-unit hysteresis also stages x up to 2^3 below its box's ideal scale.  dY has
+// same as in the row-owner kernel, whose accumulator-unit hysteresis also stages x up to 2^3 below its box's ideal scale.  dY has
 // no halo: its scale is per tile, 2^(E - ea) with E the accumulators' unit (kept while the ideal unit lies within [E, E + 3]).
 template <bool PRO>
 __global__ void __launch_bounds__(512, 1) conv3_split_wgrad16r_kernel(WgP p) {
@@ -62,7 +65,7 @@ __global__ void __launch_bounds__(512, 1) conv3_split_wgrad16r_kernel(WgP p) {
         pslope = cbase < p.C1 ? p.pslope1 : p.pslope2;
         __syncthreads();
     }
-    // fragment sources: the eight-wave kernel's, with the z plane of a read resolved through the ring (offC, per tile)
+    // fragment sources: the row-owner kernel's per wave, with the z plane of a read resolved through the ring (offC, per tile)
     const int laneA0 = ((2 * wr) * HX + 8 * (g & 1) + vq) * 8 + (q & 1) * 4 + wh * PLH;
     const int laneY = ((((g >> 1) * TY) + 2 * wr) * TX + 8 * (g & 1) + vq) * CG + q * 4;
     int offC[5];

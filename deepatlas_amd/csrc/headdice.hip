@@ -459,16 +459,7 @@ static int hd_launch_fwd(const HdP& p, int nblocks, hipStream_t st) {
 template <int KC, int NT, typename T>
 static int hd_launch_bwd(const HdP& p, int nblocks, hipStream_t st) {
     const size_t shm = (size_t)4 * (64 * (KC * 16 + 4) + 64 * (NT * 16 + 4)) * sizeof(float);
-    auto kern = head_dice_bwd_kernel<KC, NT, T>;
-    static bool attr_set = false;
-    if (!attr_set && shm > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(256), shm, st, p);
-    DA_LAUNCH_CHECK();
-    return 0;
+    return da_launch_lds<head_dice_bwd_kernel<KC, NT, T>>(dim3(nblocks), dim3(256), shm, st, p);
 }
 
 template <typename T>

@@ -789,16 +789,7 @@ static int g_wg_in_bf = 0, g_wg_dy_bf = 0;      // storage types of the weight-g
 template <int CIT, int COT, int TPB, typename TI, typename TY>
 static int launch_pw_wgrad_t(const PwWgP& p, int nblocks, hipStream_t st) {
     const size_t shm = (size_t)CIT * TPB * COT * 64 * 4 * sizeof(float);
-    auto kern = pw_mfma_wgrad_kernel<CIT, COT, TPB, TI, TY>;
-    static bool attr_set = false;
-    if (!attr_set && shm > 65536) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(nblocks, p.ntaps / TPB), dim3(256), shm, st, p);
-    DA_LAUNCH_CHECK();
-    return 0;
+    return da_launch_lds<pw_mfma_wgrad_kernel<CIT, COT, TPB, TI, TY>>(dim3(nblocks, p.ntaps / TPB), dim3(256), shm, st, p);
 }
 template <int CIT, int COT, int TPB>
 static int launch_pw_wgrad(const PwWgP& p, int nblocks, hipStream_t st) {
@@ -849,7 +840,6 @@ static int pw_wgrad_slice(const float* in, const float* dy, float* dw, long long
     const int CIT = Cin / 16, COT = Cout / 16;
     int rc = DA_ERR_UNSUPPORTED;
     // taps per block chosen so that CIT*COT*TPB*4 accumulator registers <= 128
-#define DA_WG_CASE(a, c, t) if (CIT == a && COT == c && ((ntaps == 8 && t > 0) || (ntaps == 1 && t == 0))) rc = launch_pw_wgrad<a, c, (t > 0 ? t : 1)>(p, nb, st)
     if (ntaps == 8) {
         if (CIT * COT <= 4) {
             if (CIT == 1 && COT == 1) rc = launch_pw_wgrad<1, 1, 8>(p, nb, st);
@@ -882,7 +872,6 @@ static int pw_wgrad_slice(const float* in, const float* dy, float* dw, long long
         else if (CIT == 1 && COT == 4) rc = launch_pw_wgrad<1, 4, 1>(p, nb, st);
         else if (CIT == 4 && COT == 1) rc = launch_pw_wgrad<4, 1, 1>(p, nb, st);
     }
-#undef DA_WG_CASE
     if (rc) return rc;
     { const int rc2 = da_reduce_partials(p.partial, nb, (int)O, dw, st); if (rc2) return rc2; }
     return 0;

@@ -1090,20 +1090,10 @@ extern "C" int da_warp_adjoint_labels(const void* lab_t, int lab_t_bytes, const 
     if (A) { e = hipMemsetAsync(A, 0, (size_t)nvox * sizeof(float), st); if (e != hipSuccess) return (int)e; }
     constexpr int BX = 32, BY = 8, BZ = 4, M = 2, K = 3;
     constexpr size_t shm = (size_t)K * (BX + 2 * M + 1) * (BY + 2 * M + 1) * (BZ + 2 * M + 1) * sizeof(float);
-    auto kern = warp_adjoint_labels_box_kernel<BX, BY, BZ, M, K>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
     const int nbx = (W + BX - 1) / BX, nby = (H + BY - 1) / BY, nbz = (D + BZ - 1) / BZ;
     const long long nb = (long long)nbx * nby * nbz * N;
-    if (nb < (1ll << 31)) {                    // (larger grids: the plain kernel below)
-        hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(256), shm, st, lab_t, lab_t_bytes, disp, A, B, N, D, H, W, C, nbx, nby, nbz);
-        DA_LAUNCH_CHECK();
-        return 0;
-    }
+    if (nb < (1ll << 31))                      // (larger grids: the plain kernel below)
+        return da_launch_lds<warp_adjoint_labels_box_kernel<BX, BY, BZ, M, K>>(dim3((unsigned)nb), dim3(256), shm, st, lab_t, lab_t_bytes, disp, A, B, N, D, H, W, C, nbx, nby, nbz);
     hipLaunchKernelGGL(warp_adjoint_labels_kernel, dim3(da_grid(nvox, 256)), dim3(256), 0, st, lab_t, lab_t_bytes, disp, A, B, N, D, H, W, C);
     DA_LAUNCH_CHECK();
     return 0;

@@ -61,7 +61,7 @@ CASES = [
     (8, 16, 3, (1, 5, 9, 18)),         # the flow conv 24 -> 3 (conv3d_flowmm.hip: (dy, cout) columns), ragged tiles in every axis
     (16, 0, 3, (2, 4, 8, 16)),         # one source tensor, two samples, exact tiles
     (8, 8, 2, (1, 3, 7, 20)),          # two output channels
-    # enough tiles for the weight gradient's 16-channel / eight-wave form (conv3_split_wgrad16_kernel: slabs x chunks x groups >= 224)
+    # enough tiles for the weight gradient's 16-channel / eight-wave ring form (conv3_split_wgrad16r_kernel: slabs x chunks x groups >= 224)
     (32, 16, 16, (1, 15, 41, 50)),     # 48 -> 16: three 16-channel chunks over two tensors, ragged tiles in every axis, odd tile count per slab
     (16, 0, 16, (2, 16, 40, 64)),      # one chunk, 256 slabs, two samples
     (32, 0, 32, (1, 12, 36, 40)),      # two chunks x two cout groups

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Weight gradient of a list of layer shapes through the C ABI (split mode), written to an .npz: run once with DA_WG16=1 and once with
-DA_WG16=0 and compare (tools/ab/exp_w16cmp.sh) -- the eight-wave kernel against the row-owner kernel on shapes the unit tests do not reach."""
+DA_WG16=0 and compare (tools/ab/exp_w16cmp.sh) -- the eight-wave ring kernel (conv3d_wgring.h) against the row-owner kernel on shapes the unit tests do not reach."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np
