@@ -924,6 +924,218 @@ __global__ void __launch_bounds__(256) seg_anat_dlogits_lane_kernel(const float*
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Dice between a WARPED LABEL MAP and a DENSE tensor (joint step on a pair whose fixed image has no manual segmentation): the warped one-hot
+// W = warp(onehot(lab_m), phi) has at most 8 non-zero classes per voxel and is never written.  Per sample and class the three sums
+//   I_c = sum_v W_c(v) X_c(v),   SW_c = sum_v W_c(v),   SX_c = sum_v X_c(v)
+// in two roles: ROLE 0 (registration phase) X = probabilities, W is Dice's SOURCE (partials I, SW, SX); ROLE 1 (segmentation phase) X = softmax of
+// the logits, formed per voxel here, is the source and W the target (partials I, SX, SW).  Taps, bounds and label rules are those of
+// label_warp_dice_partial_kernel.  A wave takes 64 consecutive voxels: every lane derives ONE voxel's eight (weight, label) pairs into the wave's
+// LDS rows -- the C / 4 lanes of a voxel do not each repeat the divisions, the floor and the eight label reads -- and the wave then walks the
+// 64 x C dense block in LPV coalesced 1 KB pieces (16 bytes per lane, issued before the taps are derived), lane (voxel, channel quad) forming
+// its four W_c from the voxel's row.  No atomics: per-lane fp32 sums, combined in double in a fixed order per workgroup.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void softwarp_softmax4(float (&x)[4], int lpv) {      // group_softmax4 of losses.hip: the same expressions
+    float m = fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3]));
+    for (int o = 1; o < lpv; o <<= 1) m = fmaxf(m, __shfl_xor(m, o));
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { x[j] = expf(x[j] - m); s += x[j]; }
+    for (int o = 1; o < lpv; o <<= 1) s += __shfl_xor(s, o);
+    const float inv = 1.f / s;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) x[j] *= inv;
+}
+
+struct alignas(16) SoftwarpRows { float w[4][64][8]; unsigned char l[4][64][8]; };      // per wave: 64 voxels x 8 corners (label 255: counts for no class)
+
+// voxel v of sample n (first voxel sb = n V) -> its row: corner weights (0 where the corner is outside the volume) and corner labels
+__device__ __forceinline__ void softwarp_plan(const void* __restrict__ lab_m, int bm, const float* __restrict__ disp, long long sb, long long v, bool live,
+                                              int D, int H, int W, int C, float* __restrict__ wrow, unsigned char* __restrict__ lrow) {
+    int d, h, w; da_vox3(v, H, W, d, h, w);
+    const float* u = disp + (sb + v) * 3;
+    const float gx = u[0] + id_coord(w, W), gy = u[1] + id_coord(h, H), gz = u[2] + id_coord(d, D);
+    const bool fin = is_finite_coord(gx, gy, gz);
+    const Taps t = make_taps(fin ? gx : -4.f, fin ? gy : -4.f, fin ? gz : -4.f, D, H, W);
+    float wk[8]; unsigned int lo = 0u, hi = 0u;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int cz = k >> 2, cy = (k >> 1) & 1, cx = k & 1;
+        const int x = t.x0 + cx, y = t.y0 + cy, z = t.z0 + cz;
+        wk[k] = 0.f;
+        unsigned int lb = 255u;
+        if (live && x >= 0 && x < W && y >= 0 && y < H && z >= 0 && z < D) {
+            wk[k] = (cx ? t.fx0 : t.fx1) * (cy ? t.fy0 : t.fy1) * (cz ? t.fz0 : t.fz1);
+            const int l = warp_label_at(lab_m, bm, sb + ((long long)z * H + y) * W + x);
+            if (l >= 0 && l < C) lb = (unsigned int)l;
+        }
+        if (k < 4) lo |= lb << (8 * k); else hi |= lb << (8 * (k - 4));
+    }
+    *reinterpret_cast<float4*>(wrow) = make_float4(wk[0], wk[1], wk[2], wk[3]);
+    *reinterpret_cast<float4*>(wrow + 4) = make_float4(wk[4], wk[5], wk[6], wk[7]);
+    *reinterpret_cast<uint2*>(lrow) = make_uint2(lo, hi);
+}
+
+// W_c of the lane's channel quad (classes c0 ... c0 + 3) from a voxel's row, corners added in the order 0 ... 7
+__device__ __forceinline__ void softwarp_quad(const float* __restrict__ wrow, const unsigned char* __restrict__ lrow, int c0, float (&Wq)[4]) {
+    const float4 wa = *reinterpret_cast<const float4*>(wrow), wb = *reinterpret_cast<const float4*>(wrow + 4);
+    const uint2 lb = *reinterpret_cast<const uint2*>(lrow);
+    const float wk[8] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) Wq[j] = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int rel = (int)(((k < 4 ? lb.x : lb.y) >> (8 * (k & 3))) & 255u) - c0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) Wq[j] += (rel == j) ? wk[k] : 0.f;
+    }
+}
+
+__device__ __forceinline__ void softwarp_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// the voxel range [v0, v1) of a workgroup: whole 256-voxel steps, neighbouring ranges on one XCD when the grid is a multiple of 8
+__device__ __forceinline__ void softwarp_range(long long V, long long& v0, long long& v1) {
+    const long long per = (da_cdiv(V, (long long)gridDim.x) + 255) / 256 * 256;
+    const int b = (gridDim.x % 8 == 0) ? da_xcd_item_of_block((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
+    const long long r0 = (long long)b * per;
+    v0 = r0 < V ? r0 : V;
+    v1 = r0 + per < V ? r0 + per : V;
+}
+
+// grid (blocks, N); partial [N][gridDim.x][3][C] = (I, source sums, target sums) for da_dice_finish
+template <int LPV, int ROLE>
+__global__ void __launch_bounds__(256) softwarp_dice_partial_kernel(const void* __restrict__ lab_m, int bm, const float* __restrict__ disp,
+                                                                    const float* __restrict__ X, int D, int H, int W, double* __restrict__ partial) {
+    constexpr int C = LPV * 4, VPW = 64 / LPV;
+    __shared__ SoftwarpRows rows;
+    __shared__ float red[3][256][4];
+    const int n = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int q = lane % LPV, gl = lane / LPV;
+    const long long V = (long long)D * H * W, sb = (long long)n * V;
+    long long v0, v1; softwarp_range(V, v0, v1);
+    const float* Xn = X + sb * C;
+    float aI[4] = {0, 0, 0, 0}, aW[4] = {0, 0, 0, 0}, aX[4] = {0, 0, 0, 0};
+    for (long long vb = v0 + wave * 64; vb < v1; vb += 256) {
+        float4 xs[LPV];
+#pragma unroll
+        for (int j = 0; j < LPV; ++j)
+            xs[j] = (vb + j * VPW + gl < v1) ? *reinterpret_cast<const float4*>(Xn + vb * C + (long long)(j * 64 + lane) * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const long long v = vb + lane;
+        const bool live = v < v1;
+        softwarp_plan(lab_m, bm, disp, sb, live ? v : V - 1, live, D, H, W, C, rows.w[wave][lane], rows.l[wave][lane]);
+        softwarp_wave_sync();
+#pragma unroll
+        for (int j = 0; j < LPV; ++j) {
+            const int sl = j * VPW + gl;
+            float x[4] = {xs[j].x, xs[j].y, xs[j].z, xs[j].w};
+            if (ROLE == 1) softwarp_softmax4(x, LPV);                      // (whole voxel groups are live or not: every lane of a group takes part)
+            float Wq[4];
+            softwarp_quad(rows.w[wave][sl], rows.l[wave][sl], q * 4, Wq);
+            if (vb + sl < v1) {
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) { aI[jj] += Wq[jj] * x[jj]; aW[jj] += Wq[jj]; aX[jj] += x[jj]; }
+            }
+        }
+        softwarp_wave_sync();
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { red[0][threadIdx.x][j] = aI[j]; red[1][threadIdx.x][j] = ROLE == 0 ? aW[j] : aX[j]; red[2][threadIdx.x][j] = ROLE == 0 ? aX[j] : aW[j]; }
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < 3 * C; idx += 256) {
+        const int k = idx / C, c = idx % C;
+        double t = 0.0;
+        for (int s = 0; s < 256 / LPV; ++s) t += (double)red[k][s * LPV + (c >> 2)][c & 3];
+        partial[(((size_t)n * gridDim.x + blockIdx.x) * 3 + k) * C + c] = t;
+    }
+}
+
+// ROLE 1 backward: dlogits = dloss p (g - sum_k p_k g_k), g_c = coef[0][c] W_c + coef[1][c], p recomputed from the logits: one read of the logits,
+// one write of dlogits, no scatter
+template <int LPV>
+__global__ void __launch_bounds__(256) softwarp_dice_dlogits_kernel(const void* __restrict__ lab_m, int bm, const float* __restrict__ disp,
+                                                                    const float* __restrict__ logits, const float* __restrict__ coef,
+                                                                    const float* __restrict__ dloss, float* __restrict__ dlogits, int N, int D, int H, int W) {
+    constexpr int C = LPV * 4, VPW = 64 / LPV;
+    __shared__ SoftwarpRows rows;
+    const int n = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int q = lane % LPV, gl = lane / LPV;
+    const long long V = (long long)D * H * W, sb = (long long)n * V;
+    long long v0, v1; softwarp_range(V, v0, v1);
+    const float gls = dloss[0];
+    float ca[4], cb[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { ca[j] = coef[n * C + q * 4 + j]; cb[j] = coef[N * C + n * C + q * 4 + j]; }
+    const float* Xn = logits + sb * C;
+    float* On = dlogits + sb * C;
+    for (long long vb = v0 + wave * 64; vb < v1; vb += 256) {
+        float4 xs[LPV];
+#pragma unroll
+        for (int j = 0; j < LPV; ++j)
+            xs[j] = (vb + j * VPW + gl < v1) ? *reinterpret_cast<const float4*>(Xn + vb * C + (long long)(j * 64 + lane) * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const long long v = vb + lane;
+        const bool live = v < v1;
+        softwarp_plan(lab_m, bm, disp, sb, live ? v : V - 1, live, D, H, W, C, rows.w[wave][lane], rows.l[wave][lane]);
+        softwarp_wave_sync();
+#pragma unroll
+        for (int j = 0; j < LPV; ++j) {
+            const int sl = j * VPW + gl;
+            float p[4] = {xs[j].x, xs[j].y, xs[j].z, xs[j].w};
+            softwarp_softmax4(p, LPV);
+            float Wq[4], g[4];
+            softwarp_quad(rows.w[wave][sl], rows.l[wave][sl], q * 4, Wq);
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) g[jj] = ca[jj] * Wq[jj] + cb[jj];
+            float dot = g[0] * p[0] + g[1] * p[1] + g[2] * p[2] + g[3] * p[3];
+            for (int k = 1; k < LPV; k <<= 1) dot += __shfl_xor(dot, k);
+            if (vb + sl < v1)
+                *reinterpret_cast<float4*>(On + vb * C + (long long)(j * 64 + lane) * 4) =
+                    make_float4(gls * p[0] * (g[0] - dot), gls * p[1] * (g[1] - dot), gls * p[2] * (g[2] - dot), gls * p[3] * (g[3] - dot));
+        }
+        softwarp_wave_sync();
+    }
+}
+
+// ROLE 0 backward: label_warp_dice_bwd_kernel with the indicator [lab == target label] replaced by X[v][lab] (reads inside voxel v's own row)
+__global__ void softwarp_dice_bwd_disp_kernel(const void* __restrict__ lab_m, int bm, const float* __restrict__ disp, const float* __restrict__ X,
+                                              const float* __restrict__ coef, const float* __restrict__ dloss,
+                                              float* __restrict__ d_disp, int N, int D, int H, int W, int C) {
+    const long long V = (long long)D * H * W, nvox = V * N;
+    const float gl = dloss[0];
+    const int NC = N * C;
+    for (DaXcdLoop XL = da_xcd_loop(nvox); XL.i < XL.end; XL.i += XL.step) {
+        const long long v = XL.i;
+        int n, d, h, w; da_vox4(v, D, H, W, n, d, h, w);
+        const float gx = disp[v * 3 + 0] + id_coord(w, W);
+        const float gy = disp[v * 3 + 1] + id_coord(h, H);
+        const float gz = disp[v * 3 + 2] + id_coord(d, D);
+        const bool fin = is_finite_coord(gx, gy, gz);
+        const Taps t = make_taps(fin ? gx : -4.f, fin ? gy : -4.f, fin ? gz : -4.f, D, H, W);
+        const long long sbase = (long long)n * V;
+        float gix = 0.f, giy = 0.f, giz = 0.f;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int cz = k >> 2, cy = (k >> 1) & 1, cx = k & 1;
+            const int x = t.x0 + cx, y = t.y0 + cy, z = t.z0 + cz;
+            if (x >= 0 && x < W && y >= 0 && y < H && z >= 0 && z < D) {
+                const float wx = cx ? t.fx0 : t.fx1, wy = cy ? t.fy0 : t.fy1, wz = cz ? t.fz0 : t.fz1;
+                const int lab = warp_label_at(lab_m, bm, sbase + ((long long)z * H + y) * W + x);
+                float dot = 0.f;
+                if (lab >= 0 && lab < C) dot = gl * (coef[n * C + lab] * X[v * C + lab] + coef[NC + n * C + lab]);
+                gix += (cx ? dot : -dot) * wy * wz;
+                giy += (cy ? dot : -dot) * wx * wz;
+                giz += (cz ? dot : -dot) * wx * wy;
+            }
+        }
+        d_disp[v * 3 + 0] = gix * ((float)(W - 1) / 2.f);
+        d_disp[v * 3 + 1] = giy * ((float)(H - 1) / 2.f);
+        d_disp[v * 3 + 2] = giz * ((float)(D - 1) / 2.f);
+    }
+}
+
 static bool vec_ok(int C, int* lpv) {
     if (C % 4 != 0) { *lpv = 1; return false; }
     const int q = C / 4;
@@ -1117,6 +1329,76 @@ extern "C" int da_seg_anat_dlogits(const float* prob, const void* lab_m, int lab
     const size_t shm = (size_t)C * (tv + 1) * sizeof(float);
     hipLaunchKernelGGL(seg_anat_dlogits_kernel, dim3(da_grid(ntiles * 256, 256)), dim3(256), shm, da_stream(stream), prob, lab_m, lab_m_bytes, A, B, dlogits,
                        coef_sup, coef_anat, dloss_sup, dloss_anat, N, V, C, lpv, tv);
+    DA_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- Dice of a warped label map against a dense tensor (pairs whose fixed image is unlabelled) ----------------------------------
+extern "C" size_t da_softwarp_dice_ws_bytes(int N, int C) { return da_label_warp_dice_ws_bytes(N, C); }
+
+static bool softwarp_args_ok(const void* lab_m, int lab_m_bytes, const float* disp, const float* dense, int N, int D, int H, int W, int C) {
+    return lab_m && disp && dense && N > 0 && N <= 64 && D >= 2 && H >= 2 && W >= 2 && C > 0 && (lab_m_bytes == 1 || lab_m_bytes == 8);
+}
+static bool softwarp_classes_ok(int C) { return C == 4 || C == 8 || C == 16 || C == 32 || C == 64; }
+
+template <int LPV>
+static void softwarp_launch_partial(int role, dim3 grid, hipStream_t st, const void* lab_m, int bm, const float* disp, const float* dense,
+                                    int D, int H, int W, double* partial) {
+    if (role == 0) hipLaunchKernelGGL((softwarp_dice_partial_kernel<LPV, 0>), grid, dim3(256), 0, st, lab_m, bm, disp, dense, D, H, W, partial);
+    else hipLaunchKernelGGL((softwarp_dice_partial_kernel<LPV, 1>), grid, dim3(256), 0, st, lab_m, bm, disp, dense, D, H, W, partial);
+}
+
+extern "C" int da_softwarp_dice_fwd(const void* lab_m, int lab_m_bytes, const float* disp, const float* dense, int role,
+                                    int N, int D, int H, int W, int C, int weight_type, int no_bg, float eps,
+                                    float* loss, float* coef, void* ws, size_t ws_bytes, void* stream) {
+    if (!softwarp_args_ok(lab_m, lab_m_bytes, disp, dense, N, D, H, W, C) || !loss || !coef || !ws || (role != 0 && role != 1)) return DA_ERR_BADARG;
+    if (!softwarp_classes_ok(C)) return DA_ERR_UNSUPPORTED;             // callers compose da_warp_labels_fwd + da_dice_fwd
+    if (ws_bytes < da_softwarp_dice_ws_bytes(N, C)) return DA_ERR_WS_SMALL;
+    hipStream_t st = da_stream(stream);
+    double* partial = (double*)ws;
+    float* isc = (float*)((char*)ws + da_align((size_t)N * kLwdBlocks * 3 * C * sizeof(double)));
+    const long long V = (long long)D * H * W;
+    int nblocks = (int)da_cdiv(V, 256 * 2); if (nblocks > kLwdBlocks) nblocks = kLwdBlocks; if (nblocks < 1) nblocks = 1;
+    const dim3 grid(nblocks, N);
+    switch (C) {
+        case 4: softwarp_launch_partial<1>(role, grid, st, lab_m, lab_m_bytes, disp, dense, D, H, W, partial); break;
+        case 8: softwarp_launch_partial<2>(role, grid, st, lab_m, lab_m_bytes, disp, dense, D, H, W, partial); break;
+        case 16: softwarp_launch_partial<4>(role, grid, st, lab_m, lab_m_bytes, disp, dense, D, H, W, partial); break;
+        case 32: softwarp_launch_partial<8>(role, grid, st, lab_m, lab_m_bytes, disp, dense, D, H, W, partial); break;
+        default: softwarp_launch_partial<16>(role, grid, st, lab_m, lab_m_bytes, disp, dense, D, H, W, partial); break;
+    }
+    DA_LAUNCH_CHECK();
+    return da_dice_finish(partial, nblocks, N, C, weight_type, no_bg, eps, loss, coef, isc, st);
+}
+
+extern "C" int da_softwarp_dice_bwd_disp(const void* lab_m, int lab_m_bytes, const float* disp, const float* prob, const float* coef, const float* dloss,
+                                         float* d_disp, int N, int D, int H, int W, int C, void* stream) {
+    if (!softwarp_args_ok(lab_m, lab_m_bytes, disp, prob, N, D, H, W, C) || !coef || !dloss || !d_disp) return DA_ERR_BADARG;
+    if (!softwarp_classes_ok(C)) return DA_ERR_UNSUPPORTED;
+    const long long nvox = (long long)N * D * H * W;
+    hipLaunchKernelGGL(softwarp_dice_bwd_disp_kernel, dim3(da_grid(nvox, 256)), dim3(256), 0, da_stream(stream), lab_m, lab_m_bytes, disp, prob, coef, dloss,
+                       d_disp, N, D, H, W, C);
+    DA_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int da_softwarp_dice_bwd_logits(const void* lab_m, int lab_m_bytes, const float* disp, const float* logits, const float* coef, const float* dloss,
+                                           float* dlogits, int N, int D, int H, int W, int C, void* stream) {
+    if (!softwarp_args_ok(lab_m, lab_m_bytes, disp, logits, N, D, H, W, C) || !coef || !dloss || !dlogits) return DA_ERR_BADARG;
+    if (!softwarp_classes_ok(C)) return DA_ERR_UNSUPPORTED;
+    hipStream_t st = da_stream(stream);
+    const long long V = (long long)D * H * W;
+    int nblocks = (int)da_cdiv(V, 256 * 2); if (nblocks > kLwdBlocks) nblocks = kLwdBlocks; if (nblocks < 1) nblocks = 1;
+    const dim3 grid(nblocks, N);
+#define DA_SOFTWARP_DLOGITS(LPV) hipLaunchKernelGGL((softwarp_dice_dlogits_kernel<LPV>), grid, dim3(256), 0, st, lab_m, lab_m_bytes, disp, logits, coef, dloss, dlogits, N, D, H, W)
+    switch (C) {
+        case 4: DA_SOFTWARP_DLOGITS(1); break;
+        case 8: DA_SOFTWARP_DLOGITS(2); break;
+        case 16: DA_SOFTWARP_DLOGITS(4); break;
+        case 32: DA_SOFTWARP_DLOGITS(8); break;
+        default: DA_SOFTWARP_DLOGITS(16); break;
+    }
+#undef DA_SOFTWARP_DLOGITS
     DA_LAUNCH_CHECK();
     return 0;
 }

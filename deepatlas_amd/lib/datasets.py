@@ -78,16 +78,30 @@ class SyntheticRegDataset(Dataset):
 
     labeled: the volume indices that have a manual segmentation (None: all).  For an unlabelled MOVING volume the segmentation slot
     holds zeros and has_moving_seg is False (a flag, because default collation cannot batch None); the experiment turns it into
-    seg_m=None.  Pairs whose FIXED volume is unlabelled are left out of the enumeration: the joint step and the registration Dice
-    both need the fixed segmentation (an unlabelled fixed image is not supported)."""
+    seg_m=None.
 
-    def __init__(self, n_volumes, shape, n_classes, seed=230, labeled=None):
+    pairs: which of the n (n - 1) ordered pairs are enumerated, always in the reference's order with the excluded ones removed.
+      'fixed_labeled' (default): the pairs whose FIXED volume is labelled; the 6-tuple above.
+      'any_labeled': those, and the pairs with a labelled moving and an unlabelled fixed volume (the joint step's seg_t=None case: the warped
+                     manual label is the fixed image's training target).
+      'all':         every pair, the ones with no label on either side included (registration by image similarity alone).
+    In the two wider modes a sample carries a seventh element has_fixed_seg, and an unlabelled fixed volume's segmentation slot holds zeros."""
+
+    PAIR_MODES = ('fixed_labeled', 'any_labeled', 'all')
+
+    def __init__(self, n_volumes, shape, n_classes, seed=230, labeled=None, pairs='fixed_labeled'):
         if n_volumes < 2:
             raise ValueError('a pairwise dataset needs at least two volumes')
+        if pairs not in self.PAIR_MODES:
+            raise ValueError("pairs must be one of %s, got %r" % (', '.join(self.PAIR_MODES), pairs))
+        self.pair_mode = pairs
         self.seg = SyntheticSegDataset(n_volumes, shape, n_classes, seed)
         self.n = n_volumes
         self.labeled = set(range(n_volumes)) if labeled is None else set(int(i) for i in labeled)
-        self.pairs = [p for p in (self.pair_of(i, n_volumes) for i in range(n_volumes * (n_volumes - 1))) if p[1] in self.labeled]
+        keep = {'fixed_labeled': lambda m, f: f in self.labeled,
+                'any_labeled': lambda m, f: f in self.labeled or m in self.labeled,
+                'all': lambda m, f: True}[pairs]
+        self.pairs = [p for p in (self.pair_of(i, n_volumes) for i in range(n_volumes * (n_volumes - 1))) if keep(*p)]
 
     @staticmethod
     def pair_of(pair_id, n):
@@ -107,7 +121,13 @@ class SyntheticRegDataset(Dataset):
         has = m in self.labeled
         if not has:
             sm = torch.zeros_like(sm)
-        return im, it, sm, st_, has, '%s_to_%s' % (name_m, name_f)
+        name = '%s_to_%s' % (name_m, name_f)
+        if self.pair_mode == 'fixed_labeled':
+            return im, it, sm, st_, has, name
+        has_fixed = f in self.labeled
+        if not has_fixed:
+            st_ = torch.zeros_like(st_)
+        return im, it, sm, st_, has, name, has_fixed
 
 
 def get_reg_dataset(name):

@@ -4,7 +4,10 @@ names as its goal and lists as TODO (README.md:15-19).
 Two models, two FlatAdams, step = models/joint.py DeepAtlasJointStep (unchanged; weights lam_sim / lam_reg / lam_anat / lam_sp from the
 config).  `num_labeled` of the training volumes -- the first k after a shuffle seeded with random_seed -- have a manual segmentation; a
 pair whose moving volume is unlabelled reaches the step as seg_m=None (the registration phase then warps the segmentation net's own
-prediction and the segmentation phase has no supervised term), pairs whose fixed volume is unlabelled are not enumerated.  The DeepAtlas
+prediction and the segmentation phase has no supervised term).  config['pairs'] chooses the enumeration (lib/datasets.py
+SyntheticRegDataset): 'fixed_labeled' (default) leaves out the pairs whose fixed volume is unlabelled; 'any_labeled' adds those with a labelled
+moving volume, which reach the step as seg_t=None (the warped manual label is the fixed image's pseudo-label); 'all' adds the pairs with no
+label on either side (both None: image similarity and smoothness only, the segmentation net is not touched; single process only).  The DeepAtlas
 recipe pre-trains each net alone: config['seg_resume_dir'] / config['reg_resume_dir'] name checkpoint files of SegmentationExperiment /
 RegistrationExperiment to start from.  Validation = segmentation Dice exactly as SegmentationExperiment.eval computes it + the
 registration metrics of models/registration.py.  Two checkpoint files per save, seg_checkpoint.pth.tar / reg_checkpoint.pth.tar (and
@@ -55,6 +58,12 @@ class DeepAtlasExperiment(BaseExperiment):
             raise ValueError('DeepAtlasExperiment trains one pair per step (labelled and unlabelled moving volumes cannot share a batch)')
         if cfg['num_labeled'] < 1:
             raise ValueError('joint training needs at least one labelled volume (the fixed image of every pair)')
+        pairs = cfg.get('pairs', 'fixed_labeled')
+        if pairs not in med_data.SyntheticRegDataset.PAIR_MODES:
+            raise ValueError("config['pairs'] must be one of %s, got %r" % (', '.join(med_data.SyntheticRegDataset.PAIR_MODES), pairs))
+        if pairs == 'all' and parallel.world_size() > 1:
+            raise ValueError("pairs='all' needs a single process: a rank whose pair has no label skips its segmentation phase and would miss the "
+                             "gradient all-reduce the other ranks enter")
         self.exp_name = self.experiment_name(cfg)
         run_dir = "debug_joint" if cfg['debug_mode'] else self.exp_name
         self.ckpoint_dir = os.path.join(cfg['log_dir'], run_dir, str(cfg['random_seed']))
@@ -69,12 +78,14 @@ class DeepAtlasExperiment(BaseExperiment):
 
     @staticmethod
     def experiment_name(cfg):
-        """Joint_<seg model>_<reg model>_<data dir name>_<n>samples_<k>labeled_<e>epochs_sim<..>_reg<..>_anat<..>_sp<..>_lr_<lr>[_scheduler_<mode>]"""
+        """Joint_<seg model>_<reg model>_<data dir name>_<n>samples_<k>labeled_<e>epochs_sim<..>_reg<..>_anat<..>_sp<..>_lr_<lr>[_scheduler_<mode>][_pairs<mode>]"""
         parts = ['Joint_', cfg['model'], '_', cfg['reg_model'], '_', os.path.basename(cfg['data_dir']), '_%ssamples' % cfg['num_samples'],
                  '_%slabeled' % cfg['num_labeled'], '_%sepochs' % cfg['n_epochs'],
                  '_sim%s_reg%s_anat%s_sp%s' % (cfg['lambda_sim'], cfg['lambda_reg'], cfg['lambda_anat'], cfg['lambda_sp']), '_lr_%s' % cfg['learning_rate']]
         if cfg['lr_mode'] != 'const':
             parts.append('_scheduler_%s' % cfg['lr_mode'])
+        if cfg.get('pairs', 'fixed_labeled') != 'fixed_labeled':
+            parts.append('_pairs%s' % cfg['pairs'])
         return ''.join(str(v) for v in parts)
 
     @staticmethod
@@ -100,7 +111,8 @@ class DeepAtlasExperiment(BaseExperiment):
         if self.training_data_loader is None:
             n = max(cfg['num_samples'], 2)
             self.labeled = self.labeled_subset(n, cfg['num_labeled'], cfg['random_seed'])
-            training_data = med_data.get_reg_dataset(cfg['data'])(n, shape, C, seed=cfg['random_seed'], labeled=self.labeled)
+            training_data = med_data.get_reg_dataset(cfg['data'])(n, shape, C, seed=cfg['random_seed'], labeled=self.labeled,
+                                                                      pairs=cfg.get('pairs', 'fixed_labeled'))
             sampler = parallel.distributed_sampler(training_data, shuffle=True, seed=cfg['random_seed'])
             self.training_data_loader = DataLoader(training_data, batch_size=1, shuffle=sampler is None, sampler=sampler, num_workers=0)
         n_valid = max(cfg.get('num_valid_samples', 2), 2)
@@ -161,13 +173,15 @@ class DeepAtlasExperiment(BaseExperiment):
         print('Finished Training: {}'.format(self.exp_name))
 
     def train_step(self, batch):
-        """One joint step on a (moving image, fixed image, moving seg, fixed seg, has_moving_seg, name) batch of one pair.  Returns the
-        step's dict of loss terms; for an unlabelled moving volume (seg_m=None) it has no supervised term 'sup'."""
+        """One joint step on a (moving image, fixed image, moving seg, fixed seg, has_moving_seg, name[, has_fixed_seg]) batch of one pair.
+        Returns the step's dict of loss terms; for an unlabelled moving volume (seg_m=None) it has no supervised term 'sup'.  An unlabelled
+        fixed volume (the seventh element, present in the wider pair modes) reaches the step as seg_t=None."""
         im_m, im_t, seg_m, seg_t, has = batch[:5]
         d = self.device
         labelled = bool(torch.as_tensor(has).all())
+        fixed_labelled = bool(torch.as_tensor(batch[6]).all()) if len(batch) > 6 else True
         out = self.step(im_m.to(d, non_blocking=True), im_t.to(d, non_blocking=True), seg_m.to(d, non_blocking=True) if labelled else None,
-                        seg_t.to(d, non_blocking=True))
+                        seg_t.to(d, non_blocking=True) if fixed_labelled else None)
         if not labelled:
             out.pop('sup', None)
         return out

@@ -10,6 +10,12 @@ compare against:
   seg phase (reg net frozen):  L = l_sp*Dice(S(Im), Sm) + l_anat*Dice(warp(softmax(S(Im)), phi.detach()), onehot(St))
   Sm = None (moving image without a manual segmentation): the reg phase warps softmax(S(Im)).detach() (segmentation net in eval
   mode under no_grad: no state change) instead of onehot(Sm), and the seg phase drops its supervised term.
+  St = None (fixed image without a manual segmentation), with W = warp(onehot(Sm), phi):
+    reg phase:  L = l_sim*NCC + l_reg*Bending + l_anat*Dice(source = W, target = softmax(S(It)).detach())   (segmentation net in eval mode under no_grad)
+    seg phase:  ONE train-mode forward of cat([Im, It]) -> Zm, Zt;  L = l_sp*Dice(softmax(Zm), Sm) + l_anat*Dice(source = softmax(Zt), target = W.detach()):
+                the manual label supervises its own image and, warped, is the pseudo-label of the unlabelled one.  No phase overlap (the eval and the
+                train forward of one net must not interleave).
+  Sm = St = None: the reg phase with l_sim*NCC + l_reg*Bending only; the segmentation net is not run and its optimiser not stepped.
 """
 
 import torch
@@ -88,6 +94,8 @@ class DeepAtlasJointStep:
         return logits
 
     def __call__(self, im_m, im_t, seg_m, seg_t):
+        if seg_t is None:
+            return self._step_fixed_unlabelled(im_m, im_t, seg_m)
         ahead = None
         if (self.overlap_phases and seg_m is not None and im_m.is_cuda and not torch.cuda.is_current_stream_capturing()):
             ahead = self._seg_forward_ahead(im_m)
@@ -101,9 +109,27 @@ class DeepAtlasJointStep:
         r.update(s)
         return r
 
+    def _step_fixed_unlabelled(self, im_m, im_t, seg_m):
+        """The step for a pair whose fixed image has no manual segmentation (module docstring).  Same keys as the labelled step; absent terms are zeros."""
+        r = self.reg_gradients(im_m, im_t, seg_m, None)
+        parallel.allreduce_gradients(self.reg_opt)
+        self.reg_opt.step()
+        disp = r.pop('disp')
+        if seg_m is None:
+            # neither image is labelled: nothing supervises the segmentation net -- it is not run, its optimiser (step count included) not touched
+            zero = torch.zeros((), device=disp.device)
+            r.update(loss_seg=zero, sup=zero.clone(), anat_seg=zero.clone())
+            return r
+        r.update(self.seg_gradients_fixed_unlabelled(im_m, im_t, seg_m, disp))
+        parallel.allreduce_gradients(self.seg_opt)
+        self.seg_opt.step()
+        return r
+
     def segments(self, im_m, im_t, seg_m, seg_t):
         """(segments, between, optimizers) for graphs.GraphedStep: reg gradients | reg update + seg gradients | seg update, with the
         two flat-bucket all-reduces in the gaps."""
+        if seg_t is None:
+            raise NotImplementedError('graph capture of a step whose fixed image has no segmentation (seg_t=None) is not supported')
         st = {}
 
         def first():
@@ -125,10 +151,14 @@ class DeepAtlasJointStep:
         # one-hot is never materialised
         self.reg.train()
         self.reg_opt.zero_grad()
-        if seg_m is None:
+        if seg_m is None and seg_t is not None:
             with torch.no_grad():
                 self.seg.eval()
                 prob_m = ops.SoftmaxFn.apply(ops.materialize_logits(self.seg(im_m)))
+        if seg_t is None and seg_m is not None:
+            with torch.no_grad():
+                self.seg.eval()
+                prob_t = ops.SoftmaxFn.apply(ops.materialize_logits(self.seg(im_t)))
         with trace.range('joint/reg_phase/forward'):
             disp, warped, deform = self.reg(im_m, im_t)
         if disp.is_cuda and not torch.cuda.is_current_stream_capturing():
@@ -138,7 +168,15 @@ class DeepAtlasJointStep:
         trace.mark('joint/reg_phase/losses')
         l_sim = self.ncc(warped, im_t)
         l_reg = self.bend(disp)
-        if seg_m is not None and fused:
+        if seg_t is None:
+            if seg_m is None:
+                l_anat = None
+            elif fused:
+                # Dice(warp(one_hot(seg_m)), prob_t) from the label map and the probabilities: the warped one-hot is never materialised
+                l_anat = ops.LabelWarpSoftDiceFn.apply(seg_m, disp, prob_t, self.n_classes, 'Uniform', False, 1e-6)
+            else:
+                l_anat = self.dice_prob(ops.WarpLabelsFn.apply(seg_m, disp, self.n_classes), prob_t)
+        elif seg_m is not None and fused:
             # Dice(warp(one_hot(seg_m)), one_hot(seg_t)) straight from the two label maps: no 32-channel tensor in either direction
             l_anat = ops.LabelWarpDiceFn.apply(seg_m, seg_t, disp, self.n_classes, 'Uniform', False, 1e-6)
         else:
@@ -147,7 +185,11 @@ class DeepAtlasJointStep:
             else:
                 warped_seg, _ = ops.WarpFn.apply(prob_m, disp)                          # gradient flows to disp only (prob_m is a constant)
             l_anat = self.dice_prob(warped_seg, seg_t)
-        loss_r = lam['sim'] * l_sim + lam['reg'] * l_reg + lam['anat'] * l_anat
+        if l_anat is None:
+            loss_r = lam['sim'] * l_sim + lam['reg'] * l_reg
+            l_anat = torch.zeros((), device=disp.device)
+        else:
+            loss_r = lam['sim'] * l_sim + lam['reg'] * l_reg + lam['anat'] * l_anat
         with trace.range('joint/reg_phase/backward'):
             loss_r.backward()
         return dict(loss_reg=loss_r.detach(), sim=l_sim.detach(), bend=l_reg.detach(), anat_reg=l_anat.detach(), disp=disp.detach())
@@ -173,6 +215,28 @@ class DeepAtlasJointStep:
         with trace.range('joint/seg_phase/forward'):
             logits = ops.materialize_logits(self.seg(im_m))
         return self._seg_losses_backward(logits, seg_m, seg_t, disp, fused)
+
+    def seg_gradients_fixed_unlabelled(self, im_m, im_t, seg_m, disp):
+        """segmentation phase of a pair (labelled moving, unlabelled fixed image) up to its gradients: one train-mode forward of both images."""
+        lam = self.lam
+        fused = self.fused and ops.fused_anatomy_supported(self.n_classes)
+        n = im_m.shape[0]
+        self.seg.train()
+        self.seg_opt.zero_grad()
+        with trace.range('joint/seg_phase/forward'):
+            logits = ops.materialize_logits(self.seg(torch.cat([im_m, im_t])))
+        z_m, z_t = logits[:n], logits[n:]
+        trace.mark('joint/seg_phase/losses')
+        l_sp = self.dice_logits(z_m, seg_m)
+        if fused:
+            # Dice(softmax(z_t), warp(one_hot(seg_m))) from the logits and the label map: no probability tensor, no warped one-hot, no scatter
+            l_anat2 = ops.SoftmaxLabelWarpDiceFn.apply(z_t, seg_m, disp, 'Uniform', False, 1e-6)
+        else:
+            l_anat2 = self.dice_logits(z_t, ops.WarpLabelsFn.apply(seg_m, disp, self.n_classes).detach())
+        loss_s = lam['sp'] * l_sp + lam['anat'] * l_anat2
+        with trace.range('joint/seg_phase/backward'):
+            loss_s.backward()
+        return dict(loss_seg=loss_s.detach(), sup=l_sp.detach(), anat_seg=l_anat2.detach())
 
     def _seg_losses_backward(self, logits, seg_m, seg_t, disp, fused):
         lam = self.lam

@@ -1823,6 +1823,98 @@ class LabelWarpDiceFn(Function):
         return None, None, ncdhw(d_disp), None, None, None, None
 
 
+def _composed(ctx, fn, leaf):
+    """Forward of a fused node whose entry declined the shape: the op-by-op composition `fn(leaf)` recorded on a private graph."""
+    with torch.enable_grad():
+        leaf = leaf.detach().requires_grad_(True)
+        loss = fn(leaf)
+    ctx.composed = (leaf, loss)
+    return loss.detach()
+
+
+def _composed_backward(ctx, gloss):
+    leaf, loss = ctx.composed
+    ctx.composed = None
+    return torch.autograd.grad(loss, leaf, gloss.detach().to(loss.dtype))[0]
+
+
+class LabelWarpSoftDiceFn(Function):
+    """Dice(source = warp(one_hot(labels_m), identity + disp), target = prob_t) -- the registration phase's anatomy loss for a pair whose fixed
+    image has no manual segmentation (models/joint.py; prob_t = the segmentation net's probabilities, a constant).  The warped one-hot tensor
+    and Dice's gradient tensor are never materialised (da_softwarp_dice_fwd role 0 / da_softwarp_dice_bwd_disp); gradient to disp only.  Same
+    value and d loss / d disp as WarpLabelsFn followed by DiceFn(soft target), which it runs when the entry declines the class count."""
+
+    @staticmethod
+    def forward(ctx, labels_m, disp, prob_t, n_classes, weight_type, no_bg, eps):
+        u = ndhwc(disp)
+        p = ndhwc(prob_t.detach())
+        N, D, H, W, _ = u.shape
+        C = int(n_classes)
+        lm, bm = _labels(labels_m.reshape(N, -1))
+        if lm.shape[1] != D * H * W or tuple(p.shape) != (N, D, H, W, C):
+            raise ValueError('label map, probabilities and displacement field must cover the same volume')
+        loss = _empty((1,), u)
+        coef = _empty((2, N, C), u)
+        wp, wn = _ws(nat.lib().da_softwarp_dice_ws_bytes(N, C), u)
+        ctx.composed = None
+        if not call_supported('da_softwarp_dice_fwd', ptr(lm), bm, ptr(u), ptr(p), 0, N, D, H, W, C, _WEIGHT_TYPES[weight_type], 1 if no_bg else 0,
+                              float(eps), ptr(loss), ptr(coef), wp, wn, stream()):
+            return _composed(ctx, lambda d: DiceFn.apply(WarpLabelsFn.apply(labels_m, d, C), None, prob_t.detach(), weight_type, no_bg, False, eps), disp)
+        ctx.cfg = (N, D, H, W, C, bm)
+        ctx.save_for_backward(lm, u, p, coef)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, gloss):
+        if ctx.composed is not None:
+            return None, _composed_backward(ctx, gloss), None, None, None, None, None
+        lm, u, p, coef = ctx.saved_tensors
+        N, D, H, W, C, bm = ctx.cfg
+        gl = gloss.detach().reshape(1).to(torch.float32).contiguous()
+        d_disp = torch.empty_like(u)
+        call('da_softwarp_dice_bwd_disp', ptr(lm), bm, ptr(u), ptr(p), ptr(coef), ptr(gl), ptr(d_disp), N, D, H, W, C, stream())
+        return None, ncdhw(d_disp), None, None, None, None, None
+
+
+class SoftmaxLabelWarpDiceFn(Function):
+    """Dice(source = softmax(logits), target = warp(one_hot(labels_m), identity + disp)) with disp a constant -- the segmentation phase's anatomy
+    loss for a pair whose fixed image has no manual segmentation: the warped manual label of the moving image is the fixed image's pseudo-label.
+    Neither the probabilities nor the warped one-hot tensor are written (da_softwarp_dice_fwd role 1); backward is one dense pass over the logits
+    (da_softwarp_dice_bwd_logits), no scatter, no atomics.  Falls back to WarpLabelsFn + DiceFn(softmax=True, soft target)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels_m, disp, weight_type, no_bg, eps):
+        a = ndhwc(logits)
+        u = ndhwc(disp.detach())
+        N, D, H, W, C = a.shape
+        lm, bm = _labels(labels_m.reshape(N, -1))
+        if lm.shape[1] != D * H * W or tuple(u.shape) != (N, D, H, W, 3):
+            raise ValueError('label map, logits and displacement field must cover the same volume')
+        loss = _empty((1,), a)
+        coef = _empty((2, N, C), a)
+        wp, wn = _ws(nat.lib().da_softwarp_dice_ws_bytes(N, C), a)
+        ctx.composed = None
+        if a.dtype != torch.float32 or not call_supported('da_softwarp_dice_fwd', ptr(lm), bm, ptr(u), ptr(a), 1, N, D, H, W, C, _WEIGHT_TYPES[weight_type],
+                                                          1 if no_bg else 0, float(eps), ptr(loss), ptr(coef), wp, wn, stream()):
+            with torch.no_grad():
+                target = WarpLabelsFn.apply(labels_m, disp.detach(), C)
+            return _composed(ctx, lambda z: DiceFn.apply(z, None, target, weight_type, no_bg, True, eps), logits)
+        ctx.cfg = (N, D, H, W, C, bm)
+        ctx.save_for_backward(lm, u, a, coef)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, gloss):
+        if ctx.composed is not None:
+            return _composed_backward(ctx, gloss), None, None, None, None, None
+        lm, u, a, coef = ctx.saved_tensors
+        N, D, H, W, C, bm = ctx.cfg
+        gl = gloss.detach().reshape(1).to(torch.float32).contiguous()
+        dlogits = torch.empty_like(a)
+        call('da_softwarp_dice_bwd_logits', ptr(lm), bm, ptr(u), ptr(a), ptr(coef), ptr(gl), ptr(dlogits), N, D, H, W, C, stream())
+        return ncdhw(dlogits), None, None, None, None, None
+
+
 class SegPhaseLossFn(Function):
     """The segmentation phase's two Dice terms as ONE node (models/joint.py):
         l_sup  = Dice(softmax(logits), labels_m)                                   (None labels_m: 0)

@@ -319,6 +319,26 @@ int da_warp_adjoint_labels(const void* lab_t, int lab_t_bytes, const float* disp
 int da_seg_anat_dlogits(const float* prob, const void* lab_m, int lab_m_bytes, const float* A, const float* B, float* dlogits,
                         const float* coef_sup, const float* coef_anat, const float* dloss_sup, const float* dloss_anat,
                         int N, long long V, int C, void* stream);
+/* ---- Dice between a WARPED LABEL MAP and a DENSE tensor (joint step on a pair whose fixed image has no manual segmentation; parts:
+ * lib/loss.py:410-476 Dice, voxel_morph.py:85-91 warp).  W = warp(onehot(lab_m), id + disp) (trilinear, zeros padding, align_corners=True; a corner
+ * label outside [0, C) counts for no class, a non-finite or >= 1e9 coordinate gives no taps) is never written.  dense [N][D][H][W][C] fp32:
+ *   role 0 (registration phase): dense = probabilities, loss = Dice(source = W, target = dense)
+ *   role 1 (segmentation phase): dense = logits, loss = Dice(source = softmax(dense), target = W), the softmax formed per voxel in the kernel
+ * weight_type / no_bg / eps, loss[1] and coef[2][N][C] as da_dice_fwd (weights from the TARGET's volume; d loss / d source_c(v) =
+ * coef[0][n][c] target_c(v) + coef[1][n][c]).  Double partials per workgroup in ws, summed in a fixed order: no atomics, run-to-run bit-identical.
+ * C in {4, 8, 16, 32, 64}, else DA_ERR_UNSUPPORTED (callers compose da_warp_labels_fwd + da_dice_fwd); N <= 64. */
+size_t da_softwarp_dice_ws_bytes(int N, int C);
+int da_softwarp_dice_fwd(const void* lab_m, int lab_m_bytes, const float* disp, const float* dense, int role,
+                         int N, int D, int H, int W, int C, int weight_type, int no_bg, float eps,
+                         float* loss, float* coef /*[2][N][C]*/, void* ws, size_t ws_bytes, void* stream);
+/* role 0 backward (lib/loss.py:410-476 through voxel_morph.py:85-91): d_disp [N][D][H][W][3] = dloss * d loss / d disp, da_label_warp_dice_bwd with the
+ * indicator [corner label == target label] replaced by prob[v][corner label]. */
+int da_softwarp_dice_bwd_disp(const void* lab_m, int lab_m_bytes, const float* disp, const float* prob, const float* coef, const float* dloss,
+                              float* d_disp, int N, int D, int H, int W, int C, void* stream);
+/* role 1 backward (lib/loss.py:410-476, 427 softmax; voxel_morph.py:85-91 on the constant side): dlogits [N][D][H][W][C] = dloss p (g - sum_k p_k g_k),
+ * g_c = coef[0][c] W_c + coef[1][c], p = softmax(logits) recomputed: one read of the logits, one write, no scatter. */
+int da_softwarp_dice_bwd_logits(const void* lab_m, int lab_m_bytes, const float* disp, const float* logits, const float* coef, const float* dloss,
+                                float* dlogits, int N, int D, int H, int W, int C, void* stream);
 /* deterministic d_src (parity runs): the same scatter as da_warp_bwd's d_src, accumulated in 64-bit fixed point with integer atomics
  * (order-independent, hence run-to-run bit-identical), scale = power of two from max|dout|.  d_src is OVERWRITTEN (no pre-zeroing). */
 size_t da_warp_bwd_dsrc_det_ws_bytes(int N, int D, int H, int W, int C);

@@ -1,6 +1,7 @@
 """DeepAtlas joint training of the registration and the segmentation net from few labelled volumes (the reference's stated goal,
 listed as TODO in its README.md:15-19).  Flags of train_reg.py plus the four loss weights of models/joint.py DeepAtlasJointStep,
---num-labeled (how many of the training volumes have a manual segmentation) and --seg-ckpt / --reg-ckpt (checkpoint files of
+--num-labeled (how many of the training volumes have a manual segmentation), --pairs (which ordered pairs are trained on: those with a
+labelled fixed volume, those with a label on either side, or all) and --seg-ckpt / --reg-ckpt (checkpoint files of
 train_seg.py / train_reg.py to start from: the DeepAtlas recipe pre-trains each net alone)."""
 import argparse
 import os
@@ -49,6 +50,7 @@ def build_config(args):
     n_volumes = max(args.num_samples, 2)
     num_labeled = getattr(args, 'num_labeled', None)
     config['num_labeled'] = n_volumes if num_labeled is None else max(0, min(num_labeled, n_volumes))      # clamped to the number of volumes
+    config['pairs'] = getattr(args, 'pairs', 'fixed_labeled')
     config['seg_resume_dir'] = config.pop('seg_ckpt', None) or ''
     config['reg_resume_dir'] = config.pop('reg_ckpt', None) or ''
     if not config.get('matrix_precision'):
@@ -62,6 +64,9 @@ def main(argv=None):
     parser.add_argument('--lambda-anat', default=1.0, type=float, help='weight of the anatomy similarity (Dice of the warped segmentation)')
     parser.add_argument('--lambda-sp', default=1.0, type=float, help='weight of the supervised segmentation loss')
     parser.add_argument('--num-labeled', default=None, type=int, help='number of training volumes with a manual segmentation (default: all)')
+    parser.add_argument('--pairs', default='fixed_labeled', choices=['fixed_labeled', 'any_labeled', 'all'],
+                        help="pairs trained on: fixed volume labelled (default) | a label on either side (an unlabelled fixed image is trained against the "
+                             "warped label of the moving one) | every pair (pairs without any label train the registration net alone)")
     parser.add_argument('--seg-ckpt', default=None, type=str, help='checkpoint file of train_seg.py to start the segmentation net from')
     parser.add_argument('--reg-ckpt', default=None, type=str, help='checkpoint file of train_reg.py to start the registration net from')
     args = parser.parse_args(argv)
