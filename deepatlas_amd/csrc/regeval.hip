@@ -3,6 +3,8 @@
 // its per-sample statistics (folding fraction).  The reference has neither metric (README.md:15-19 lists registration as TODO); the deformation
 // is the one its registration net builds: deform = disp + identity, sampled with align_corners=True (voxel_morph.py:85-91, lib/utils.py:89-102).
 // NDHWC: disp[N][D][H][W][3], channel order (x, y, z) = (W, H, D) axis, normalised units, identity generated in-kernel.
+// Multi-atlas label fusion (registration-based segmentation: K atlas label maps warped with K such fields and voted per voxel) and the
+// weights of locally weighted voting share the nearest-coordinate routine and live here too.
 #include "common.h"
 
 namespace {
@@ -198,6 +200,197 @@ __global__ void jacobian_finalize_kernel(const double* __restrict__ partial, int
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Multi-atlas label fusion: K atlas label maps warped to one target grid (the gather of warp_nearest_counts_kernel, coordinate by
+// nearest_source) and voted per voxel.  A thread owns RUN = 4 consecutive target voxels; per atlas 3 x 16 bytes of displacement and four
+// 1-byte gathers issued back to back.  The K labels of a voxel stay packed four to a register (and the K weights of the per-voxel form
+// in registers): the kernel is instantiated per bucket KB in {4, 8, 16, 32} with every loop fully unrolled and a guard on k < K, so no
+// array is indexed at run time and nothing goes to scratch.  Vote by comparing pairs: s_k = sum over m in atlas order of w_m [l_m = l_k]
+// is the score of atlas k's class, added in fp32 exactly as the definition adds it (w = 1: integer counts); the winner is the largest
+// score, ties to the smallest label; an absent atlas (k >= K) carries weight 0.  conf = winning score / sum_k w_k, (0, 0) for a zero total.
+// WMODE 0: majority vote, 1: w_atlas[N][K], 2: w_voxel[N][K][V].  No atomics: two runs are bit-identical.
+// ------------------------------------------------------------------------------------------------
+// the vote of one voxel: pk = its K labels packed four to a register, wa / wv = the per-atlas / this voxel's per-voxel weights
+template <int KB, int WMODE, int KW, int NA, int NV>
+__device__ __forceinline__ void fusion_vote_one(const unsigned (&pk)[KW], const float (&wa)[NA], const float (&wv)[NV], int K,
+                                                unsigned& best_lab, float& best_s, float& total) {
+    unsigned lab[KB];
+    float wt[KB];
+#pragma unroll
+    for (int k = 0; k < KB; ++k) {
+        lab[k] = (pk[k >> 2] >> ((k & 3) * 8)) & 0xFFu;
+        wt[k] = WMODE == 0 ? (k < K ? 1.f : 0.f) : WMODE == 1 ? wa[k < NA ? k : 0] : wv[k < NV ? k : 0];
+    }
+    float tot = 0.f, bs = 0.f;
+    unsigned bl = 0u;
+#pragma unroll
+    for (int k = 0; k < KB; ++k) tot += wt[k];
+#pragma unroll
+    for (int k = 0; k < KB; ++k) {
+        if (k < K) {
+            float s = 0.f;
+#pragma unroll
+            for (int m = 0; m < KB; ++m) s += (lab[m] == lab[k]) ? wt[m] : 0.f;
+            if (s > bs || (s == bs && lab[k] < bl)) { bs = s; bl = lab[k]; }
+        }
+    }
+    best_lab = bl; best_s = bs; total = tot;
+}
+
+template <int KB, int WMODE, bool VEC>
+__global__ void __launch_bounds__(256)
+label_fusion_vote_kernel(const void* __restrict__ labels, int label_bytes, long long label_sample_stride, const float* __restrict__ disp,
+                         const float* __restrict__ w_atlas, const float* __restrict__ w_voxel, int K, int D, int H, int W,
+                         unsigned char* __restrict__ fused, float* __restrict__ conf) {
+    constexpr int RUN = 4;
+    constexpr int KW = (KB + 3) / 4;         // registers of packed labels per voxel
+    const int n = blockIdx.y;
+    const int V = D * H * W;
+    const long long nk0 = (long long)n * K;
+    float wa[WMODE == 1 ? KB : 1];
+    if (WMODE == 1) {
+#pragma unroll
+        for (int k = 0; k < KB; ++k) wa[k] = (k < K) ? w_atlas[nk0 + k] : 0.f;
+    }
+    const int nruns = (V + RUN - 1) / RUN;
+    for (DaXcdLoop L = da_xcd_loop(nruns, 64); L.i < L.end; L.i += L.step) {
+        const int v0 = (int)L.i * RUN;
+        const int cnt = (V - v0) < RUN ? (V - v0) : RUN;
+        int d0, h0, w0; da_vox3(v0, H, W, d0, h0, w0);
+        unsigned pk[RUN][KW];
+        float wv[WMODE == 2 ? RUN : 1][WMODE == 2 ? KB : 1];
+#pragma unroll
+        for (int j = 0; j < RUN; ++j)
+#pragma unroll
+            for (int q = 0; q < KW; ++q) pk[j][q] = 0u;
+#pragma unroll
+        for (int k = 0; k < KB; ++k) {
+            if (k < K) {
+                const long long field = (nk0 + k) * (long long)V;                  // 64-bit: [N][K][V][3] passes 2^31 elements
+                const float* u = disp + (field + v0) * 3;
+                float uu[RUN * 3];
+                if (VEC) {
+                    const float4* q = reinterpret_cast<const float4*>(u);
+                    const float4 a = q[0], b = q[1], c = q[2];
+                    uu[0] = a.x; uu[1] = a.y; uu[2] = a.z; uu[3] = a.w; uu[4] = b.x; uu[5] = b.y; uu[6] = b.z; uu[7] = b.w;
+                    uu[8] = c.x; uu[9] = c.y; uu[10] = c.z; uu[11] = c.w;
+                } else {
+#pragma unroll
+                    for (int e = 0; e < RUN * 3; ++e) uu[e] = (e < cnt * 3) ? u[e] : 0.f;
+                }
+                int d = d0, h = h0, w = w0;
+                int src[RUN];
+#pragma unroll
+                for (int j = 0; j < RUN; ++j) {
+                    src[j] = (j < cnt) ? nearest_source(uu[3 * j], uu[3 * j + 1], uu[3 * j + 2], d, h, w, D, H, W) : -1;
+                    if (++w == W) { w = 0; if (++h == H) { h = 0; ++d; } }
+                }
+                const long long lab0 = (long long)n * label_sample_stride + (long long)k * V;
+                unsigned m[RUN];
+#pragma unroll
+                for (int j = 0; j < RUN; ++j)      // (independent gathers: issued back to back)
+                    m[j] = src[j] >= 0 ? (unsigned)(unsigned char)load_label(labels, label_bytes, lab0 + src[j]) : 0u;
+#pragma unroll
+                for (int j = 0; j < RUN; ++j) pk[j][k >> 2] |= m[j] << ((k & 3) * 8);
+                if (WMODE == 2) {
+                    const float* wp = w_voxel + field + v0;
+                    if (VEC) {
+                        const float4 t = *reinterpret_cast<const float4*>(wp);
+                        wv[0][k] = t.x; wv[1][k] = t.y; wv[2][k] = t.z; wv[3][k] = t.w;
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < RUN; ++j) wv[j][k] = (j < cnt) ? wp[j] : 0.f;
+                    }
+                }
+            } else if (WMODE == 2) {
+#pragma unroll
+                for (int j = 0; j < RUN; ++j) wv[j][k] = 0.f;
+            }
+        }
+        // (one call per voxel, not a loop: a fully unrolled 4 x KB x KB body passes the unroller's size limit at KB = 32 and the arrays
+        // would then be indexed at run time)
+        unsigned best_lab[RUN];
+        float best_s[RUN], total[RUN];
+        fusion_vote_one<KB, WMODE>(pk[0], wa, wv[0], K, best_lab[0], best_s[0], total[0]);
+        fusion_vote_one<KB, WMODE>(pk[1], wa, wv[WMODE == 2 ? 1 : 0], K, best_lab[1], best_s[1], total[1]);
+        fusion_vote_one<KB, WMODE>(pk[2], wa, wv[WMODE == 2 ? 2 : 0], K, best_lab[2], best_s[2], total[2]);
+        fusion_vote_one<KB, WMODE>(pk[3], wa, wv[WMODE == 2 ? 3 : 0], K, best_lab[3], best_s[3], total[3]);
+        const long long o = (long long)n * V + v0;
+        if (VEC) {
+            *reinterpret_cast<uchar4*>(fused + o) = make_uchar4((unsigned char)best_lab[0], (unsigned char)best_lab[1], (unsigned char)best_lab[2], (unsigned char)best_lab[3]);
+            if (conf) {
+                float4 c;
+                c.x = total[0] > 0.f ? best_s[0] / total[0] : 0.f; c.y = total[1] > 0.f ? best_s[1] / total[1] : 0.f;
+                c.z = total[2] > 0.f ? best_s[2] / total[2] : 0.f; c.w = total[3] > 0.f ? best_s[3] / total[3] : 0.f;
+                *reinterpret_cast<float4*>(conf + o) = c;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < RUN; ++j) {
+                if (j < cnt) {
+                    fused[o + j] = (unsigned char)best_lab[j];
+                    if (conf) conf[o + j] = total[j] > 0.f ? best_s[j] / total[j] : 0.f;
+                }
+            }
+        }
+    }
+}
+
+template <int KB, int WMODE>
+void launch_fusion_vote(bool vec, dim3 grid, hipStream_t st, const void* labels, int label_bytes, long long stride, const float* disp,
+                        const float* w_atlas, const float* w_voxel, int K, int D, int H, int W, unsigned char* fused, float* conf) {
+    if (vec) hipLaunchKernelGGL((label_fusion_vote_kernel<KB, WMODE, true>), grid, dim3(256), 0, st, labels, label_bytes, stride, disp, w_atlas, w_voxel, K, D, H, W, fused, conf);
+    else hipLaunchKernelGGL((label_fusion_vote_kernel<KB, WMODE, false>), grid, dim3(256), 0, st, labels, label_bytes, stride, disp, w_atlas, w_voxel, K, D, H, W, fused, conf);
+}
+
+template <int WMODE>
+void launch_fusion_vote_bucket(bool vec, dim3 grid, hipStream_t st, const void* labels, int label_bytes, long long stride, const float* disp,
+                               const float* w_atlas, const float* w_voxel, int K, int D, int H, int W, unsigned char* fused, float* conf) {
+    if (K <= 4) launch_fusion_vote<4, WMODE>(vec, grid, st, labels, label_bytes, stride, disp, w_atlas, w_voxel, K, D, H, W, fused, conf);
+    else if (K <= 8) launch_fusion_vote<8, WMODE>(vec, grid, st, labels, label_bytes, stride, disp, w_atlas, w_voxel, K, D, H, W, fused, conf);
+    else if (K <= 16) launch_fusion_vote<16, WMODE>(vec, grid, st, labels, label_bytes, stride, disp, w_atlas, w_voxel, K, D, H, W, fused, conf);
+    else launch_fusion_vote<32, WMODE>(vec, grid, st, labels, label_bytes, stride, disp, w_atlas, w_voxel, K, D, H, W, fused, conf);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Weights of locally weighted voting: w = exp(-beta m), m = (2r+1)^-3 x the box sum of (warped - target)^2 over the (2r+1)^3 window,
+// voxels outside the volume contributing 0.  Separable like the LNCC box sums (reglosses.hip box_axis_kernel): along W (the squared
+// difference formed on the fly), along H, along D; each axis adds its 2r+1 terms directly in window order -- no sliding sum, so no
+// cancellation.  STAGE 0 reads (warped, target) and sums along W; 1 sums along H; 2 sums along D, divides by the window size and takes
+// expf.  Fields are [N K][D][H][W]; the voxels are dealt out XCD-contiguously so the +-r rows / planes are found in the XCD's own L2.
+// ------------------------------------------------------------------------------------------------
+template <int STAGE>
+__global__ void __launch_bounds__(256)
+msd_axis_kernel(const float* __restrict__ in, const float* __restrict__ target, float* __restrict__ out, long long total, int K,
+                int D, int H, int W, int r, float n3, float beta) {
+    const long long V = (long long)D * H * W;
+    for (DaXcdLoop L = da_xcd_loop(total, 256); L.i < L.end; L.i += L.step) {
+        const long long i = L.i;
+        const long long f = i / V;                      // field (n, k)
+        const int v = (int)(i - f * V);
+        int d, h, w; da_vox3(v, H, W, d, h, w);
+        float s = 0.f;
+        if (STAGE == 0) {
+            const float* a = in + i - w;                // row start
+            const float* b = target + (f / K) * V + (v - w);
+            const int lo = w - r < 0 ? 0 : w - r, hi = w + r > W - 1 ? W - 1 : w + r;
+            for (int x = lo; x <= hi; ++x) { const float e = a[x] - b[x]; s += e * e; }
+            out[i] = s;
+        } else if (STAGE == 1) {
+            const float* a = in + i - (long long)h * W;
+            const int lo = h - r < 0 ? 0 : h - r, hi = h + r > H - 1 ? H - 1 : h + r;
+            for (int y = lo; y <= hi; ++y) s += a[(long long)y * W];
+            out[i] = s;
+        } else {
+            const long long HW = (long long)H * W;
+            const float* a = in + i - (long long)d * HW;
+            const int lo = d - r < 0 ? 0 : d - r, hi = d + r > D - 1 ? D - 1 : d + r;
+            for (int z = lo; z <= hi; ++z) s += a[(long long)z * HW];
+            out[i] = expf(-beta * (s / n3));
+        }
+    }
+}
+
 int jac_blocks(long long V) {
     long long g = da_cdiv(V, 256);
     if (g > kJacBlocks) g = kJacBlocks;
@@ -249,6 +442,56 @@ extern "C" int da_jacobian_det(const float* disp, int N, int D, int H, int W, do
     hipLaunchKernelGGL(jacobian_det_kernel, dim3(nblocks, N), dim3(256), 0, st, disp, D, H, W, det_out, (double*)ws);
     DA_LAUNCH_CHECK();
     hipLaunchKernelGGL(jacobian_finalize_kernel, dim3(N), dim3(64), 0, st, (const double*)ws, nblocks, V, stats);
+    DA_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int da_label_fusion_vote(const void* labels, int label_bytes, long long label_sample_stride, const float* disp,
+                                    const float* w_atlas, const float* w_voxel, int N, int K, int D, int H, int W,
+                                    unsigned char* fused, float* conf, void* stream) {
+    if (!labels || !disp || !fused || N < 1 || K < 1 || D < 1 || H < 1 || W < 1 || (label_bytes != 1 && label_bytes != 8)) return DA_ERR_BADARG;
+    if (w_atlas && w_voxel) return DA_ERR_BADARG;                          // one weight form at most
+    const long long V = (long long)D * H * W;
+    if (label_sample_stride != 0 && label_sample_stride < (long long)K * V) return DA_ERR_BADARG;      // shared maps, or one [K][V] block per target
+    if (K > 32) return DA_ERR_UNSUPPORTED;
+    if (V >= 0x7FFFFFFFLL / 4) return DA_ERR_UNSUPPORTED;                  // 32-bit voxel offsets inside a volume (field offsets are 64-bit)
+    hipStream_t st = da_stream(stream);
+    const long long nruns = (V + 3) / 4;
+    int g = da_grid(da_cdiv(nruns, 2), 256, 2048);
+    if (g >= 8) g = g / 8 * 8;
+    const bool vec = (V % 4 == 0) && (((size_t)disp & 15) == 0) && (((size_t)fused & 3) == 0) && (!conf || ((size_t)conf & 15) == 0) &&
+                     (!w_voxel || ((size_t)w_voxel & 15) == 0);
+    const dim3 grid(g, N);
+    if (w_voxel) launch_fusion_vote_bucket<2>(vec, grid, st, labels, label_bytes, label_sample_stride, disp, w_atlas, w_voxel, K, D, H, W, fused, conf);
+    else if (w_atlas) launch_fusion_vote_bucket<1>(vec, grid, st, labels, label_bytes, label_sample_stride, disp, w_atlas, w_voxel, K, D, H, W, fused, conf);
+    else launch_fusion_vote_bucket<0>(vec, grid, st, labels, label_bytes, label_sample_stride, disp, w_atlas, w_voxel, K, D, H, W, fused, conf);
+    DA_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t da_local_msd_weights_ws_bytes(int N, int K, int D, int H, int W) {
+    const size_t n = (size_t)(N > 0 ? N : 1) * (size_t)(K > 0 ? K : 1) * (size_t)(D > 0 ? D : 1) * (size_t)(H > 0 ? H : 1) * (size_t)(W > 0 ? W : 1);
+    return da_align(n * sizeof(float));
+}
+
+extern "C" int da_local_msd_weights(const float* warped, const float* target, int N, int K, int D, int H, int W, int radius, float beta,
+                                    float* weights, void* ws, size_t ws_bytes, void* stream) {
+    if (!warped || !target || !weights || !ws || N < 1 || K < 1 || D < 1 || H < 1 || W < 1 || radius < 1 || radius > 4 || !(beta >= 0.f))
+        return DA_ERR_BADARG;
+    if (ws_bytes < da_local_msd_weights_ws_bytes(N, K, D, H, W)) return DA_ERR_WS_SMALL;
+    const long long V = (long long)D * H * W;
+    if (V >= 0x7FFFFFFFLL / 4) return DA_ERR_UNSUPPORTED;
+    hipStream_t st = da_stream(stream);
+    const long long total = (long long)N * K * V;
+    int g = da_grid(total, 256, 4096);
+    if (g >= 8) g = g / 8 * 8;
+    const int F = 2 * radius + 1;
+    float* tmp = (float*)ws;
+    hipLaunchKernelGGL(msd_axis_kernel<0>, dim3(g), dim3(256), 0, st, warped, target, weights, total, K, D, H, W, radius, 0.f, 0.f);
+    DA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(msd_axis_kernel<1>, dim3(g), dim3(256), 0, st, (const float*)weights, (const float*)nullptr, tmp, total, K, D, H, W, radius, 0.f, 0.f);
+    DA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(msd_axis_kernel<2>, dim3(g), dim3(256), 0, st, (const float*)tmp, (const float*)nullptr, weights, total, K, D, H, W, radius, (float)(F * F * F), beta);
     DA_LAUNCH_CHECK();
     return 0;
 }

@@ -167,3 +167,54 @@ def jacobian_stats(disp):
     n_vox = float(np.prod(disp.shape[2:]))
     return {'mean': s[:, 5].copy(), 'std': np.sqrt(s[:, 6]), 'min': s[:, 2].copy(), 'max': s[:, 3].copy(),
             'n_nonpos': s[:, 4].copy(), 'nonpos_frac': s[:, 4] / n_vox}
+
+
+def atlas_label_fusion(labels, disp, weights=None, n_targets=None):
+    """Multi-atlas label fusion (ops.label_fusion): the atlas label maps `labels` (K x D x H x W, or (N K) x D x H x W per target) warped
+    with the fields `disp` ((N K) x 3 x D x H x W, atlas index fastest) and voted per voxel -- majority vote, or weighted by `weights`
+    (N x K per atlas, N x K x D x H x W per voxel).  N comes from `weights`, else from shared K x D x H x W maps, else from `n_targets`
+    (default 1: without it an unweighted batch of per-target maps is one target with N K atlases).  Returns the fused map, uint8 N x D x H x W."""
+    return ops.label_fusion(labels, disp, weights, n_targets=n_targets)
+
+
+ATLAS_FUSION_MODES = ('majority', 'local')
+
+
+def atlas_segmentation(reg_model, atlas_images, atlas_labels, target_image, mode='majority', radius=2, sigma=0.1, chunk=4):
+    """Registration-based segmentation of one image from K labelled atlases: the registration net (in eval mode, `chunk` pairs at a time)
+    registers every atlas image (moving) to the target image (fixed), the atlas label maps are warped with those fields (nearest
+    neighbour) and fused per voxel.  mode 'majority': every atlas one vote.  mode 'local': locally weighted voting -- the atlas images
+    are warped with the same fields (ops.WarpFn) and atlas k votes at voxel x with exp(-m_k(x) / (2 sigma^2)), m_k the mean squared
+    difference to the target over the (2 radius + 1)^3 window (ops.local_msd_weights).
+    atlas_images: K x 1 x D x H x W (or K x D x H x W) float32, atlas_labels: K x D x H x W uint8 / int64, target_image: any shape with
+    D H W voxels; all on the registration net's device.  Returns (fused uint8 1 x D x H x W, confidence float32 1 x D x H x W).
+    Its Dice: dice_from_counts(ops.label_overlap_counts(fused, truth, n_class))."""
+    if mode not in ATLAS_FUSION_MODES:
+        raise ValueError("mode must be one of %s, got %r" % (', '.join(ATLAS_FUSION_MODES), mode))
+    if atlas_images.dim() == 4:
+        atlas_images = atlas_images[:, None]
+    K = int(atlas_images.shape[0])
+    D, H, W = (int(s) for s in atlas_images.shape[-3:])
+    if tuple(atlas_labels.shape) != (K, D, H, W):
+        raise ValueError('atlas_labels must be K x D x H x W matching atlas_images')
+    target = target_image.reshape(1, 1, D, H, W)
+    chunk = max(int(chunk), 1)
+    was_training = reg_model.training
+    fields, warped = [], []
+    with torch.no_grad():
+        reg_model.eval()
+        try:
+            for k0 in range(0, K, chunk):
+                im = atlas_images[k0:k0 + chunk]
+                disp = reg_model(im, target.expand(im.shape[0], 1, D, H, W).contiguous())[0]
+                fields.append(disp)
+                if mode == 'local':
+                    warped.append(ops.WarpFn.apply(im, disp)[0])
+        finally:
+            reg_model.train(was_training)
+        disp = fields[0] if len(fields) == 1 else torch.cat(fields, 0)
+        weights = None
+        if mode == 'local':
+            w = warped[0] if len(warped) == 1 else torch.cat(warped, 0)
+            weights = ops.local_msd_weights(w.reshape(1, K, D, H, W), target[:, 0], radius=radius, sigma=sigma)
+        return ops.label_fusion(atlas_labels, disp, weights, return_confidence=True, n_targets=1)

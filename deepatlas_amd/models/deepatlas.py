@@ -13,6 +13,8 @@ RegistrationExperiment to start from.  Validation = segmentation Dice exactly as
 registration metrics of models/registration.py.  Two checkpoint files per save, seg_checkpoint.pth.tar / reg_checkpoint.pth.tar (and
 seg_ / reg_model_best.pth.tar, each with its own best flag), carrying seg_best_score / reg_best_score: the keys models/base.py:96-101
 reads.  config['resume_dir'] is the directory that holds the two checkpoint files: both nets and both optimisers are restored.
+config['atlas_fusion'] ('majority' | 'local', default None: off) adds the registration net's score as a segmenter: every validation volume is
+segmented from the labelled training volumes by multi-atlas label fusion (models/registration.py eval_atlas_fusion), reported as atlas_dice_*.
 """
 import datetime
 import os
@@ -24,7 +26,7 @@ from torch.utils.data import DataLoader
 
 from .base import BaseExperiment
 from .joint import DeepAtlasJointStep
-from .registration import eval_registration
+from .registration import atlas_fusion_text, check_atlas_fusion, dataset_volumes, eval_atlas_fusion, eval_registration
 from .segmentation import SegmentationExperiment
 from ..lib import datasets as med_data
 from ..lib.network_factory import get_network
@@ -64,6 +66,7 @@ class DeepAtlasExperiment(BaseExperiment):
         if pairs == 'all' and parallel.world_size() > 1:
             raise ValueError("pairs='all' needs a single process: a rank whose pair has no label skips its segmentation phase and would miss the "
                              "gradient all-reduce the other ranks enter")
+        self.atlas_fusion, self.atlas_fusion_max = check_atlas_fusion(cfg)
         self.exp_name = self.experiment_name(cfg)
         run_dir = "debug_joint" if cfg['debug_mode'] else self.exp_name
         self.ckpoint_dir = os.path.join(cfg['log_dir'], run_dir, str(cfg['random_seed']))
@@ -218,7 +221,19 @@ class DeepAtlasExperiment(BaseExperiment):
         dice_per_class, dice_avg, _ = SegmentationExperiment.eval(view, seg_loader or self.validation_data_loader)
         res = eval_registration(self.reg_model, pair_loader or self.validation_pair_loader, self.config['n_classes'], self.device)
         res['seg_dice_per_class'], res['seg_dice_avg'] = dice_per_class, float(dice_avg)
+        if self.atlas_fusion:
+            res.update(eval_atlas_fusion(self.reg_model, self.atlas_volumes(), dataset_volumes(seg_loader or self.validation_data_loader),
+                                         self.config['n_classes'], self.device, mode=self.atlas_fusion))
         return res
+
+    def atlas_volumes(self):
+        """The atlases of config['atlas_fusion']: the labelled training volumes in index order, at most atlas_fusion_max of them."""
+        if self.training_data_loader is None:
+            self.setup_train_data()
+        labeled = getattr(self, 'labeled', None)
+        if labeled is None:                                   # a loader handed in through the config: its dataset knows its labelled volumes
+            labeled = sorted(self.training_data_loader.dataset.labeled)
+        return dataset_volumes(self.training_data_loader, labeled, first=self.atlas_fusion_max)
 
     def validate(self):
         if self.current_epoch % self.config['valid_epoch_period'] != 0:
@@ -244,9 +259,9 @@ class DeepAtlasExperiment(BaseExperiment):
             tag = 'validation_{}/'.format(self.config['data'])
             for k in ('seg_dice_avg', 'dice_avg', 'identity_dice_avg', 'nonpos_frac', 'det_mean', 'det_std'):
                 self.writer.add_scalar(tag + k, res[k], global_step=self.global_step)
-        print("Validation: seg Dice Avg: {:.4f}  registration Dice Avg: {:.4f} (identity {:.4f})  det J {:.4f} +- {:.4f}, folding {:.3%} "
-              "({:.3f} sec) {}".format(scores['seg'], scores['reg'], res['identity_dice_avg'], res['det_mean'], res['det_std'], res['nonpos_frac'],
-                                       time.time() - start_time, datetime.datetime.now().strftime("%D %H:%M:%S")))
+        print("Validation: seg Dice Avg: {:.4f}{}  registration Dice Avg: {:.4f} (identity {:.4f})  det J {:.4f} +- {:.4f}, folding {:.3%} "
+              "({:.3f} sec) {}".format(scores['seg'], atlas_fusion_text(res), scores['reg'], res['identity_dice_avg'], res['det_mean'], res['det_std'],
+                                       res['nonpos_frac'], time.time() - start_time, datetime.datetime.now().strftime("%D %H:%M:%S")))
         if self.current_epoch % self.config['save_ckpts_epoch_period'] == 0:
             for net, model, opt in (('seg', self.seg_model, self.seg_optimizer), ('reg', self.reg_model, self.reg_optimizer)):
                 self.save_checkpoint({'epoch': self.current_epoch,
@@ -266,6 +281,6 @@ class DeepAtlasExperiment(BaseExperiment):
         e_r, _ = self.initialize_model(self.reg_model, optimizer=None, ckpoint_path=files['reg'])
         ops.bump_weights_epoch()
         res = self.eval(self.config.get('testing_data_loader'), self.config.get('testing_pair_loader'))
-        print('Testing Models: {} ({} epochs), {} ({} epochs)  seg Dice_avg: {}  registration Dice_avg: {} (identity {})  folding fraction: {}'.format(
-            files['seg'], e_s, files['reg'], e_r, res['seg_dice_avg'], res['dice_avg'], res['identity_dice_avg'], res['nonpos_frac']))
+        print('Testing Models: {} ({} epochs), {} ({} epochs)  seg Dice_avg: {}  registration Dice_avg: {} (identity {})  folding fraction: {}{}'.format(
+            files['seg'], e_s, files['reg'], e_r, res['seg_dice_avg'], res['dice_avg'], res['identity_dice_avg'], res['nonpos_frac'], atlas_fusion_text(res)))
         return res

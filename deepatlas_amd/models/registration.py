@@ -6,6 +6,9 @@ hard-label registration Dice -- the moving segmentation warped with the predicte
 segmentation -- next to the same Dice for the identity deformation on the same pairs, and the regularity of the deformation (det J:
 mean, standard deviation, folding fraction), all from exact device kernels (lib/evalMetrics.py registration_dice / jacobian_stats).
 Checkpoints carry the keys of SegmentationExperiment's ({'epoch', 'model_state_dict', 'optimizer_state_dict', 'best_score'}).
+config['atlas_fusion'] ('majority' | 'local', default None: off) adds registration-based segmentation to validation and test(): every
+validation volume is segmented from the training volumes (at most atlas_fusion_max = 5) by multi-atlas label fusion (lib/evalMetrics.py
+atlas_segmentation) and scored against its own segmentation: atlas_dice_per_class / atlas_dice_avg.
 """
 import datetime
 import os
@@ -72,6 +75,50 @@ def eval_registration(model, dataloader, n_classes, device):
     return out
 
 
+def dataset_volumes(loader, indices=None, first=None):
+    """The (image 1 x D x H x W, segmentation D x H x W) volumes behind a loader: of a pairwise dataset the volumes its pairs are drawn
+    from (its .seg), of a volume dataset its samples; `indices` selects and orders them, `first` keeps that many (only those are built)."""
+    base = getattr(loader.dataset, 'seg', loader.dataset)
+    indices = list(range(len(base)) if indices is None else indices)
+    return [tuple(base[i][:2]) for i in (indices if first is None else indices[:first])]
+
+
+def eval_atlas_fusion(model, atlases, volumes, n_classes, device, mode='majority', radius=2, sigma=0.1, chunk=4):
+    """Registration-based segmentation as a score of the registration net: every volume of `volumes` is segmented from the labelled
+    `atlases` (lists of (image, segmentation)) with lib/evalMetrics.py atlas_segmentation and scored against its own segmentation.
+    Returns {'atlas_dice_per_class' [C-1] (nanmean over the volumes), 'atlas_dice_avg' (mean over the classes that occur)}."""
+    if not atlases:
+        raise ValueError('atlas fusion needs at least one labelled training volume')
+    ims = torch.stack([a[0] for a in atlases]).to(device)
+    labs = torch.stack([a[1] for a in atlases]).to(device)
+    rows = []
+    for im, seg in volumes:
+        fused, _ = metrics.atlas_segmentation(model, ims, labs, im.to(device), mode=mode, radius=radius, sigma=sigma, chunk=chunk)
+        counts = ops.label_overlap_counts(fused, seg.to(device).reshape(fused.shape), n_classes)
+        rows.append(metrics.dice_from_counts(counts)[:, 1:])
+    per = _nanmean(np.concatenate(rows, 0), axis=0) if rows else np.full(n_classes - 1, np.nan)
+    return {'atlas_dice_per_class': per, 'atlas_dice_avg': float(_nanmean(per)) if np.isfinite(per).any() else float('nan')}
+
+
+def check_atlas_fusion(cfg):
+    """config['atlas_fusion']: None (off, the default), 'majority' or 'local'; config['atlas_fusion_max']: the most atlases used (default 5)."""
+    mode = cfg.get('atlas_fusion')
+    if mode is not None and mode not in metrics.ATLAS_FUSION_MODES:
+        raise ValueError("config['atlas_fusion'] must be None or one of %s, got %r" % (', '.join(metrics.ATLAS_FUSION_MODES), mode))
+    cap = int(cfg.get('atlas_fusion_max', 5))
+    if mode is not None and not 1 <= cap <= ops.FUSION_MAX_ATLASES:
+        raise ValueError("config['atlas_fusion_max'] must be 1..%d, got %r" % (ops.FUSION_MAX_ATLASES, cap))
+    return mode, cap
+
+
+def atlas_fusion_text(res):
+    """What a validation line adds when atlas fusion is on ('' otherwise)."""
+    if 'atlas_dice_avg' not in res:
+        return ''
+    return '  atlas-fusion Dice Avg: {:.4f} per class {}'.format(
+        res['atlas_dice_avg'], np.array2string(np.asarray(res['atlas_dice_per_class']), precision=3, max_line_width=100000))
+
+
 class RegistrationExperiment(BaseExperiment):
     def __init__(self, config):
         super(RegistrationExperiment, self).__init__(config)
@@ -80,6 +127,7 @@ class RegistrationExperiment(BaseExperiment):
         if cfg['debug_mode']:
             print("Debug mode")
             cfg['print_batch_period'] = cfg['valid_epoch_period'] = 2
+        self.atlas_fusion, self.atlas_fusion_max = check_atlas_fusion(cfg)
         self.exp_name = self.experiment_name(cfg)
         run_dir = "debug_reg" if cfg['debug_mode'] else self.exp_name
         self.ckpoint_dir = os.path.join(cfg['log_dir'], run_dir, str(cfg['random_seed']))
@@ -179,7 +227,15 @@ class RegistrationExperiment(BaseExperiment):
                 running_loss = 0.0
 
     def eval(self, dataloader):
-        return eval_registration(self.model, dataloader, self.config['n_classes'], self.device)
+        res = eval_registration(self.model, dataloader, self.config['n_classes'], self.device)
+        if self.atlas_fusion:
+            # the volumes behind the loader's pairs, each segmented from the training volumes (all labelled here), at most atlas_fusion_max
+            if self.training_data_loader is None:
+                self.setup_train_data()
+            atlases = dataset_volumes(self.training_data_loader, first=self.atlas_fusion_max)
+            res.update(eval_atlas_fusion(self.model, atlases, dataset_volumes(dataloader), self.config['n_classes'], self.device,
+                                         mode=self.atlas_fusion))
+        return res
 
     def validate(self):
         if self.current_epoch % self.config['valid_epoch_period'] != 0:
@@ -203,8 +259,8 @@ class RegistrationExperiment(BaseExperiment):
             tag = 'validation_{}/'.format(self.config['data'])
             for k in ('dice_avg', 'identity_dice_avg', 'nonpos_frac', 'det_mean', 'det_std'):
                 self.writer.add_scalar(tag + k, res[k], global_step=self.global_step)
-        print("Validation: registration Dice Avg: {:.4f} (identity {:.4f})  det J {:.4f} +- {:.4f}, folding {:.3%} ({:.3f} sec) {}".format(
-            score, res['identity_dice_avg'], res['det_mean'], res['det_std'], res['nonpos_frac'], time.time() - start_time,
+        print("Validation: registration Dice Avg: {:.4f} (identity {:.4f}){}  det J {:.4f} +- {:.4f}, folding {:.3%} ({:.3f} sec) {}".format(
+            score, res['identity_dice_avg'], atlas_fusion_text(res), res['det_mean'], res['det_std'], res['nonpos_frac'], time.time() - start_time,
             datetime.datetime.now().strftime("%D %H:%M:%S")))
         if self.current_epoch % self.config['save_ckpts_epoch_period'] == 0:
             self.save_checkpoint({'epoch': self.current_epoch,
@@ -222,6 +278,6 @@ class RegistrationExperiment(BaseExperiment):
         last_epoch, best_score = self.initialize_model(self.model, optimizer=None, ckpoint_path=ckpoint_file)
         loader = self.config.get('testing_data_loader') or self.validation_data_loader
         res = self.eval(loader)
-        print('Testing Model: {} ({} epochs)  registration Dice_avg: {} (identity {})  folding fraction: {}'.format(
-            ckpoint_file, last_epoch, res['dice_avg'], res['identity_dice_avg'], res['nonpos_frac']))
+        print('Testing Model: {} ({} epochs)  registration Dice_avg: {} (identity {})  folding fraction: {}{}'.format(
+            ckpoint_file, last_epoch, res['dice_avg'], res['identity_dice_avg'], res['nonpos_frac'], atlas_fusion_text(res)))
         return res

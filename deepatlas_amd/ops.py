@@ -2383,3 +2383,92 @@ def jacobian_det(disp, return_map=False):
         wp, wn = _ws(nat.lib().da_jacobian_det_ws_bytes(N, D, H, W), u)
         call('da_jacobian_det', ptr(u), N, D, H, W, ptr(stats), ptr(det), wp, wn, stream())
     return (stats, det) if return_map else stats
+
+
+# ------------------------------------------------------------------------------------------------
+# multi-atlas label fusion (csrc/regeval.hip): K warped atlas label maps voted per voxel, and the weights of locally weighted voting.
+# No autograd.
+# ------------------------------------------------------------------------------------------------
+FUSION_MAX_ATLASES = 32
+
+
+def label_fusion(labels, disp, weights=None, return_confidence=False, n_targets=None):
+    """Registration-based segmentation of N targets from K atlases each, one da_label_fusion_vote launch: every atlas label map is warped
+    to its target grid exactly as warp_labels_nearest warps it, and the warped labels are voted per voxel.
+    disp: (N K) x 3 x D x H x W float32, atlas index fastest -- the batch a registration net returns for the N K (atlas, target) pairs.
+    labels: K x D x H x W (shared by all targets) or (N K) x D x H x W (per target), uint8 or int64.
+    weights: None (majority vote), N x K (per atlas) or N x K x D x H x W (per voxel, e.g. local_msd_weights) float32, >= 0.
+    N comes from `weights`, else from K x D x H x W labels (N = batch / K), else from n_targets (default 1: all fields belong to one target).
+    score(c) = sum_k w_k [label_k = c] in atlas order; the largest score wins, ties go to the smallest label; confidence = winning score
+    / sum_k w_k; a zero total gives label 0 and confidence 0.  Returns the fused map, uint8 N x D x H x W (return_confidence: and the
+    confidence, float32 N x D x H x W)."""
+    u = _eval_disp(disp)
+    NK, D, H, W, _ = u.shape
+    if labels.dim() != 4 or tuple(labels.shape[1:]) != (D, H, W):
+        raise ValueError('atlas label maps must be K x D x H x W or (N K) x D x H x W matching the displacement fields')
+    if labels.dtype not in (torch.uint8, torch.int64):
+        raise ValueError('atlas label maps must be uint8 or int64')
+    if weights is not None:
+        if weights.dtype != torch.float32 or weights.dim() not in (2, 5):
+            raise ValueError('weights must be float32, N x K or N x K x D x H x W')
+        N, K = int(weights.shape[0]), int(weights.shape[1])
+        if weights.dim() == 5 and tuple(weights.shape[2:]) != (D, H, W):
+            raise ValueError('per-voxel weights must be N x K x D x H x W matching the displacement fields')
+    elif n_targets is not None:
+        N = int(n_targets)
+        K = NK // N if N > 0 else 0
+    elif labels.shape[0] != NK:
+        K = int(labels.shape[0])
+        N = NK // K if K > 0 else 0
+    else:
+        N, K = 1, NK
+    if N < 1 or K < 1 or N * K != NK:
+        raise ValueError('the displacement batch (%d fields) is not N x K = %d x %d' % (NK, N, K))
+    if n_targets is not None and int(n_targets) != N:
+        raise ValueError('n_targets = %d contradicts the weights (N = %d)' % (int(n_targets), N))
+    if labels.shape[0] == K:
+        stride = 0
+    elif labels.shape[0] == NK:
+        stride = K * D * H * W
+    else:
+        raise ValueError('atlas label maps must be K x D x H x W or (N K) x D x H x W: got %d maps for N = %d, K = %d' % (labels.shape[0], N, K))
+    if K > FUSION_MAX_ATLASES:
+        raise ValueError('label_fusion takes at most %d atlases per target, got %d' % (FUSION_MAX_ATLASES, K))
+    lab, lb = _labels(labels)
+    w_atlas = w_voxel = None
+    if weights is not None:
+        nat.require_cuda(weights)
+        if weights.dim() == 2:
+            w_atlas = weights.contiguous()
+        else:
+            w_voxel = weights.contiguous()
+    fused = torch.empty((N, D, H, W), dtype=torch.uint8, device=u.device)
+    conf = torch.empty((N, D, H, W), dtype=torch.float32, device=u.device) if return_confidence else None
+    with torch.cuda.device(u.device):
+        call('da_label_fusion_vote', ptr(lab), lb, stride, ptr(u), ptr(w_atlas), ptr(w_voxel), N, K, D, H, W, ptr(fused), ptr(conf), stream())
+    return (fused, conf) if return_confidence else fused
+
+
+def local_msd_weights(warped, target, radius=2, sigma=0.1):
+    """Weights of locally weighted voting: w[n][k][x] = exp(-m / (2 sigma^2)), m = the mean over the (2 radius + 1)^3 window around x of
+    (warped[n][k] - target[n])^2 (voxels outside the volume contribute 0; the divisor is the full window).
+    warped: N x K x D x H x W float32, the atlas images after the trilinear warp (WarpFn) with the fields label_fusion gets;
+    target: N x D x H x W or N x 1 x D x H x W float32.  radius 1..4, sigma > 0.  Returns float32 N x K x D x H x W."""
+    nat.require_cuda(warped, target)
+    if warped.dim() != 5 or warped.dtype != torch.float32:
+        raise ValueError('warped atlas images must be N x K x D x H x W float32')
+    N, K, D, H, W = (int(s) for s in warped.shape)
+    if target.dtype != torch.float32 or tuple(target.shape) not in ((N, D, H, W), (N, 1, D, H, W)):
+        raise ValueError('target must be N x D x H x W (or N x 1 x D x H x W) float32 matching the warped atlas images')
+    radius = int(radius)
+    if not 1 <= radius <= 4:
+        raise ValueError('radius must be 1..4, got %r' % (radius,))
+    if not float(sigma) > 0.0:
+        raise ValueError('sigma must be positive, got %r' % (sigma,))
+    beta = 1.0 / (2.0 * float(sigma) * float(sigma))
+    a, t = warped.detach().contiguous(), target.detach().contiguous()
+    out = torch.empty_like(a)
+    with torch.cuda.device(a.device):
+        wp, wn = _ws(nat.lib().da_local_msd_weights_ws_bytes(N, K, D, H, W), a)
+        call('da_local_msd_weights', ptr(a), ptr(t), N, K, D, H, W, radius, beta, ptr(out), wp, wn, stream())
+    return out

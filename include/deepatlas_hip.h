@@ -544,6 +544,25 @@ int da_warp_labels_nearest_counts(const void* lab_m, int m_bytes, const void* la
 size_t da_jacobian_det_ws_bytes(int N, int D, int H, int W);
 int da_jacobian_det(const float* disp, int N, int D, int H, int W, double* stats /*[N][8]*/, float* det_out,
                     void* ws, size_t ws_bytes, void* stream);
+/* Multi-atlas label fusion: K atlas label maps warped to each of N target grids and voted per voxel, in one pass.  disp [N][K][D][H][W][3]
+ * (units and channel order as above; field (n, k) maps target n's grid into atlas k), addressed with 64-bit offsets.  labels: uint8 (1) or
+ * int64 (8) maps [K][D][H][W] shared by all targets (label_sample_stride 0) or one block per target (label_sample_stride = elements between
+ * the blocks of consecutive targets, >= K D H W).  The label of atlas k at a target voxel is exactly what da_warp_labels_nearest_counts stores
+ * (same fp32 coordinate, half-to-even rounding, 0 outside the volume or for a non-finite coordinate, stored as uint8).  Weights (>= 0; at
+ * most one form, both NULL = majority vote): w_atlas [N][K] or w_voxel [N][K][D][H][W] fp32.  score(c) = sum_k w_k [label_k = c], added in
+ * atlas order in fp32 (integer counts without weights); fused [N][D][H][W] uint8 = the class of the largest score, ties to the smallest
+ * label; conf (may be NULL) [N][D][H][W] fp32 = winning score / sum_k w_k; a zero total gives fused 0, conf 0.  No atomics: two runs are
+ * bit-identical.  1 <= K <= 32; DA_ERR_UNSUPPORTED for K > 32 or volumes of >= 2^29 voxels. */
+int da_label_fusion_vote(const void* labels, int label_bytes, long long label_sample_stride, const float* disp,
+                         const float* w_atlas, const float* w_voxel, int N, int K, int D, int H, int W,
+                         unsigned char* fused, float* conf, void* stream);
+/* Weights of locally weighted voting: weights[n][k][x] = exp(-beta m), m = (2 radius + 1)^-3 x the sum over the (2 radius + 1)^3 window
+ * around x of (warped[n][k] - target[n])^2; voxels outside the volume contribute 0, the divisor is constant.  warped [N][K][D][H][W],
+ * target [N][D][H][W], weights [N][K][D][H][W] fp32; radius 1..4, beta >= 0.  Separable direct window sums (no sliding sum) in fp32, expf.
+ * ws: one field of the size of `weights` (da_local_msd_weights_ws_bytes). */
+size_t da_local_msd_weights_ws_bytes(int N, int K, int D, int H, int W);
+int da_local_msd_weights(const float* warped, const float* target, int N, int K, int D, int H, int W, int radius, float beta,
+                         float* weights, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- optimiser (models/segmentation.py:91 torch.optim.Adam defaults) -------------------------- */
 int da_adam_step(float* p, const float* g, float* m, float* v, long long n,

@@ -55,6 +55,8 @@ def build_config(args):
     config['reg_resume_dir'] = config.pop('reg_ckpt', None) or ''
     if not config.get('matrix_precision'):
         config.pop('matrix_precision', None)
+    if not config.get('atlas_fusion'):
+        config.pop('atlas_fusion', None)
     return config
 
 

@@ -40,6 +40,8 @@ def build_config(args):
     config['device'] = 'cuda:{}'.format(args.device) if args.device.isdigit() else args.device
     if not config.get('matrix_precision'):                # absent = the package default, 'fp32_split'
         config.pop('matrix_precision', None)
+    if not config.get('atlas_fusion'):                    # absent = no registration-based segmentation at validation
+        config.pop('atlas_fusion', None)
     return config
 
 
@@ -56,6 +58,9 @@ def add_common_arguments(parser):
     parser.add_argument('--matrix-precision', default=None, choices=['fp32', 'fp32_split', 'bf16'],
                         help="arithmetic of the 3x3x3 convolutions, as in train_seg.py ('fp32_split' when absent)")
     parser.add_argument('--lambda-reg', default=1.0, type=float, help='weight of the bending-energy regulariser')
+    parser.add_argument('--atlas-fusion', default=None, choices=['majority', 'local'],
+                        help="also validate the registration net as a segmenter: every validation volume is segmented from the labelled "
+                             "training volumes (at most 5) by multi-atlas label fusion, majority vote or locally weighted voting")
     return parser
 
 
