@@ -147,6 +147,9 @@ SIGNATURES = {
     'da_lncc_ws_bytes': (SZ, [I, I, I, I, I, I, I]),
     'da_lncc_fwd': (I, [P, P, I, I, I, I, I, I, I, F, P, P, P, SZ, P]),
     'da_lncc_bwd': (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, F, P, SZ, P]),
+    'da_mi_ws_bytes': (SZ, [I, LL, I]),
+    'da_mi_fwd': (I, [P, P, I, LL, I, F, F, F, P, P, P, SZ, P]),
+    'da_mi_bwd': (I, [P, P, P, P, P, P, I, LL, I, F, F, F, P]),
     'da_gradloss_ws_bytes': (SZ, [I, I, I, I]),
     'da_gradloss_fwd': (I, [P, I, I, I, I, P, I, I, P, P, SZ, P]),
     'da_gradloss_bwd': (I, [P, P, P, I, I, I, I, P, I, I, P]),

@@ -85,13 +85,32 @@ class SyntheticRegDataset(Dataset):
       'any_labeled': those, and the pairs with a labelled moving and an unlabelled fixed volume (the joint step's seg_t=None case: the warped
                      manual label is the fixed image's training target).
       'all':         every pair, the ones with no label on either side included (registration by image similarity alone).
-    In the two wider modes a sample carries a seventh element has_fixed_seg, and an unlabelled fixed volume's segmentation slot holds zeros."""
+    In the two wider modes a sample carries a seventh element has_fixed_seg, and an unlabelled fixed volume's segmentation slot holds zeros.
+
+    moving_remap: None (default) | 'invert' (1 - x) | 'fold' (|2 x - 1|), applied to the MOVING image only: a pair of two "modalities" whose
+    intensities are related by a decreasing / a non-monotonic map -- what a similarity for multi-modal registration has to cope with.  The
+    segmentations are untouched."""
 
     PAIR_MODES = ('fixed_labeled', 'any_labeled', 'all')
+    MOVING_REMAPS = (None, 'invert', 'fold')
 
-    def __init__(self, n_volumes, shape, n_classes, seed=230, labeled=None, pairs='fixed_labeled'):
+    @staticmethod
+    def remap_intensity(img, mode):
+        """The intensity map of `moving_remap` on an image in [0, 1]."""
+        if mode is None:
+            return img
+        if mode == 'invert':
+            return 1.0 - img
+        if mode == 'fold':
+            return (2.0 * img - 1.0).abs()
+        raise ValueError("moving_remap must be None, 'invert' or 'fold', got %r" % (mode,))
+
+    def __init__(self, n_volumes, shape, n_classes, seed=230, labeled=None, pairs='fixed_labeled', moving_remap=None):
         if n_volumes < 2:
             raise ValueError('a pairwise dataset needs at least two volumes')
+        if moving_remap not in self.MOVING_REMAPS:
+            raise ValueError("moving_remap must be None, 'invert' or 'fold', got %r" % (moving_remap,))
+        self.moving_remap = moving_remap
         if pairs not in self.PAIR_MODES:
             raise ValueError("pairs must be one of %s, got %r" % (', '.join(self.PAIR_MODES), pairs))
         self.pair_mode = pairs
@@ -118,6 +137,8 @@ class SyntheticRegDataset(Dataset):
         m, f = self.pairs[i]
         im, sm, name_m = self.seg[m]
         it, st_, name_f = self.seg[f]
+        if self.moving_remap is not None:
+            im = self.remap_intensity(im, self.moving_remap)
         has = m in self.labeled
         if not has:
             sm = torch.zeros_like(sm)

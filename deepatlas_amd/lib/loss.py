@@ -1,7 +1,8 @@
 """Loss registry: host-side mirror of lib/loss.py:739-761 with the hot-path losses as fused HIP kernels.
 
 Hot path: 'dice' -> DiceLossMultiClass, 'ncc' -> NormalizedCrossCorrelationLoss,
-'bendingEnergy' -> BendingEnergyLoss; SURVEY.md §8f f2: 'lncc' -> VoxelMorphLNCC, 'gradient' -> gradientLoss (reglosses.hip).
+'bendingEnergy' -> BendingEnergyLoss; SURVEY.md §8f f2: 'lncc' -> VoxelMorphLNCC, 'gradient' -> gradientLoss (reglosses.hip);
+'mi' -> MutualInformationLoss (mi.hip; not in the reference's registry: the similarity for multi-modal pairs).
 'mse' / 'L2' are one-line compositions; 'focal' / 'cross_entropy' / 'soft_cross_entropy' share one voxelwise HIP kernel pair (xent.hip).
 """
 import os
@@ -127,6 +128,24 @@ class VoxelMorphLNCC(nn.Module):
                 raise NotImplementedError('VoxelMorphLNCC.filter must stay all ones on the accelerated path')
             self._ones_checked = key
         return ops.LNCCFn.apply(I, J, self.filter_size, self.eps)
+
+
+class MutualInformationLoss(nn.Module):
+    """Negative mutual information of two images (registry name 'mi'), VoxelMorph's global `MutualInformation`: soft histograms from
+    Gaussian Parzen windows over `num_bins` centres linspace(minval, maxval), sigma = bin width x sigma_ratio, intensities clamped to
+    [minval, maxval].  The similarity for pairs whose intensities are not linearly related (other modality, other scanner), where NCC and
+    LNCC have no optimum at alignment.  N x 1 x D x H x W or N x V inputs; mean over the batch.  2 <= num_bins <= 32."""
+
+    def __init__(self, num_bins=32, sigma_ratio=1.0, minval=0.0, maxval=1.0):
+        super(MutualInformationLoss, self).__init__()
+        if not 2 <= int(num_bins) <= 32:
+            raise ValueError('MutualInformationLoss: num_bins must be 2..32 (the kernels pad the bins to one 32 x 32 matrix tile), got %r' % (num_bins,))
+        if not float(minval) < float(maxval) or not float(sigma_ratio) > 0:
+            raise ValueError('MutualInformationLoss: needs minval < maxval and sigma_ratio > 0, got %r, %r, %r' % (minval, maxval, sigma_ratio))
+        self.num_bins, self.sigma_ratio, self.minval, self.maxval = int(num_bins), float(sigma_ratio), float(minval), float(maxval)
+
+    def forward(self, input, target):
+        return ops.MIFn.apply(input, target, self.num_bins, self.sigma_ratio, self.minval, self.maxval)
 
 
 class LNCCLoss(nn.Module):
@@ -269,14 +288,24 @@ loss_dict = {
     'cross_entropy': CrossEntropyLoss,
     'soft_cross_entropy': SoftCrossEntropy,
 }
+# Losses the reference's registry (lib/loss.py:739-761) does not have: in loss_dict and reachable through get_loss_function like the others;
+# get_available_losses() stays the reference's list of names, in its order.
+EXTENSION_LOSSES = {
+    'mi': MutualInformationLoss,
+}
+loss_dict.update(EXTENSION_LOSSES)
 
 
 def get_loss_function(loss_name):
-    if loss_name in get_available_losses():
+    if loss_name in loss_dict:
         return loss_dict[loss_name]
     else:
-        raise KeyError("Network {} is not avaiable!\n Choose from: {}".format(loss_name, get_available_losses()))
+        raise KeyError("Network {} is not avaiable!\n Choose from: {}".format(loss_name, list(loss_dict.keys())))
 
 
 def get_available_losses():
-    return loss_dict.keys()
+    return [name for name in loss_dict if name not in EXTENSION_LOSSES]
+
+
+def get_extension_losses():
+    return list(EXTENSION_LOSSES.keys())

@@ -15,6 +15,8 @@ seg_ / reg_model_best.pth.tar, each with its own best flag), carrying seg_best_s
 reads.  config['resume_dir'] is the directory that holds the two checkpoint files: both nets and both optimisers are restored.
 config['atlas_fusion'] ('majority' | 'local', default None: off) adds the registration net's score as a segmenter: every validation volume is
 segmented from the labelled training volumes by multi-atlas label fusion (models/registration.py eval_atlas_fusion), reported as atlas_dice_*.
+config['sim_loss'] / config['sim_settings'] / config['moving_remap']: the image similarity of the registration phase and the synthetic pairs'
+moving-image remap, as in models/registration.py.
 """
 import datetime
 import os
@@ -26,7 +28,7 @@ from torch.utils.data import DataLoader
 
 from .base import BaseExperiment
 from .joint import DeepAtlasJointStep
-from .registration import atlas_fusion_text, check_atlas_fusion, dataset_volumes, eval_atlas_fusion, eval_registration
+from .registration import atlas_fusion_text, check_atlas_fusion, check_sim_loss, dataset_volumes, eval_atlas_fusion, eval_registration
 from .segmentation import SegmentationExperiment
 from ..lib import datasets as med_data
 from ..lib.network_factory import get_network
@@ -67,6 +69,7 @@ class DeepAtlasExperiment(BaseExperiment):
             raise ValueError("pairs='all' needs a single process: a rank whose pair has no label skips its segmentation phase and would miss the "
                              "gradient all-reduce the other ranks enter")
         self.atlas_fusion, self.atlas_fusion_max = check_atlas_fusion(cfg)
+        self.sim_loss, self.sim_settings = check_sim_loss(cfg)
         self.exp_name = self.experiment_name(cfg)
         run_dir = "debug_joint" if cfg['debug_mode'] else self.exp_name
         self.ckpoint_dir = os.path.join(cfg['log_dir'], run_dir, str(cfg['random_seed']))
@@ -81,7 +84,7 @@ class DeepAtlasExperiment(BaseExperiment):
 
     @staticmethod
     def experiment_name(cfg):
-        """Joint_<seg model>_<reg model>_<data dir name>_<n>samples_<k>labeled_<e>epochs_sim<..>_reg<..>_anat<..>_sp<..>_lr_<lr>[_scheduler_<mode>][_pairs<mode>]"""
+        """Joint_<seg model>_<reg model>_<data dir name>_<n>samples_<k>labeled_<e>epochs_sim<..>_reg<..>_anat<..>_sp<..>_lr_<lr>[_scheduler_<mode>][_pairs<mode>][_<sim_loss>][_moving<remap>]"""
         parts = ['Joint_', cfg['model'], '_', cfg['reg_model'], '_', os.path.basename(cfg['data_dir']), '_%ssamples' % cfg['num_samples'],
                  '_%slabeled' % cfg['num_labeled'], '_%sepochs' % cfg['n_epochs'],
                  '_sim%s_reg%s_anat%s_sp%s' % (cfg['lambda_sim'], cfg['lambda_reg'], cfg['lambda_anat'], cfg['lambda_sp']), '_lr_%s' % cfg['learning_rate']]
@@ -89,6 +92,10 @@ class DeepAtlasExperiment(BaseExperiment):
             parts.append('_scheduler_%s' % cfg['lr_mode'])
         if cfg.get('pairs', 'fixed_labeled') != 'fixed_labeled':
             parts.append('_pairs%s' % cfg['pairs'])
+        if (cfg.get('sim_loss') or 'ncc') != 'ncc':
+            parts.append('_%s' % cfg['sim_loss'])
+        if cfg.get('moving_remap'):
+            parts.append('_moving%s' % cfg['moving_remap'])
         return ''.join(str(v) for v in parts)
 
     @staticmethod
@@ -111,11 +118,12 @@ class DeepAtlasExperiment(BaseExperiment):
     def setup_train_data(self):
         cfg = self.config
         shape, C = cfg['synthetic_shape'], cfg['n_classes']
+        remap = {'moving_remap': cfg['moving_remap']} if cfg.get('moving_remap') else {}
         if self.training_data_loader is None:
             n = max(cfg['num_samples'], 2)
             self.labeled = self.labeled_subset(n, cfg['num_labeled'], cfg['random_seed'])
             training_data = med_data.get_reg_dataset(cfg['data'])(n, shape, C, seed=cfg['random_seed'], labeled=self.labeled,
-                                                                      pairs=cfg.get('pairs', 'fixed_labeled'))
+                                                                      pairs=cfg.get('pairs', 'fixed_labeled'), **remap)
             sampler = parallel.distributed_sampler(training_data, shuffle=True, seed=cfg['random_seed'])
             self.training_data_loader = DataLoader(training_data, batch_size=1, shuffle=sampler is None, sampler=sampler, num_workers=0)
         n_valid = max(cfg.get('num_valid_samples', 2), 2)
@@ -123,7 +131,7 @@ class DeepAtlasExperiment(BaseExperiment):
             data = med_data.get_seg_dataset(cfg['data'])(n_valid, shape, C, seed=cfg['random_seed'] + 1000)
             self.validation_data_loader = DataLoader(data, batch_size=1, shuffle=False, num_workers=0)
         if self.validation_pair_loader is None:
-            data = med_data.get_reg_dataset(cfg['data'])(n_valid, shape, C, seed=cfg['random_seed'] + 1000)
+            data = med_data.get_reg_dataset(cfg['data'])(n_valid, shape, C, seed=cfg['random_seed'] + 1000, **remap)
             self.validation_pair_loader = DataLoader(data, batch_size=1, shuffle=False, num_workers=0)
 
     def setup_model(self):
@@ -141,7 +149,8 @@ class DeepAtlasExperiment(BaseExperiment):
         self.seg_scheduler = SegmentationExperiment.make_scheduler(self.seg_optimizer, cfg)
         self.reg_scheduler = SegmentationExperiment.make_scheduler(self.reg_optimizer, dict(cfg, milestones=fractions))
         self.step = DeepAtlasJointStep(self.seg_model, self.seg_optimizer, self.reg_model, self.reg_optimizer, cfg['n_classes'],
-                                       lam_sim=cfg['lambda_sim'], lam_reg=cfg['lambda_reg'], lam_anat=cfg['lambda_anat'], lam_sp=cfg['lambda_sp'])
+                                       lam_sim=cfg['lambda_sim'], lam_reg=cfg['lambda_reg'], lam_anat=cfg['lambda_anat'], lam_sp=cfg['lambda_sp'],
+                                       sim_loss=self.sim_loss, sim_settings=self.sim_settings)
 
     def initialize_models(self):
         """Resume (both nets, both optimisers, from the two files in config['resume_dir']) or start: each net from its pre-training

@@ -16,20 +16,35 @@ compare against:
                 the manual label supervises its own image and, warped, is the pseudo-label of the unlabelled one.  No phase overlap (the eval and the
                 train forward of one net must not interleave).
   Sm = St = None: the reg phase with l_sim*NCC + l_reg*Bending only; the segmentation net is not run and its optimiser not stepped.
+
+The image similarity ("NCC" above) is chosen with sim_loss = 'ncc' (default: global NCC, what the oracle's steps compute) | 'lncc' (local NCC,
+lib/loss.py VoxelMorphLNCC) | 'mi' (mutual information, lib/loss.py MutualInformationLoss: the one for multi-modal pairs); sim_settings are
+the keyword arguments of that loss's constructor.
 """
 
 import torch
 
 from .. import ops, parallel, trace
-from ..lib.loss import DiceLossMultiClass, NormalizedCrossCorrelationLoss, BendingEnergyLoss
+from ..lib.loss import DiceLossMultiClass, NormalizedCrossCorrelationLoss, BendingEnergyLoss, VoxelMorphLNCC, MutualInformationLoss
+
+SIM_LOSSES = {'ncc': NormalizedCrossCorrelationLoss, 'lncc': VoxelMorphLNCC, 'mi': MutualInformationLoss}
+
+
+def make_sim_loss(sim_loss='ncc', sim_settings=None):
+    """The image-similarity module of a step: SIM_LOSSES[sim_loss](**sim_settings).  An unknown name raises."""
+    if sim_loss not in SIM_LOSSES:
+        raise ValueError("sim_loss must be one of %s, got %r" % (', '.join(sorted(SIM_LOSSES)), sim_loss))
+    return SIM_LOSSES[sim_loss](**dict(sim_settings or {}))
 
 
 class RegistrationStep:
     """One registration optimisation step: VoxelMorph forward -> NCC + lambda * bending -> backward -> Adam."""
 
-    def __init__(self, reg_model, optimizer, lam_reg=1.0):
+    def __init__(self, reg_model, optimizer, lam_reg=1.0, sim_loss='ncc', sim_settings=None):
         self.model, self.opt, self.lam_reg = reg_model, optimizer, lam_reg
-        self.ncc, self.bend = NormalizedCrossCorrelationLoss(), BendingEnergyLoss()
+        self.sim, self.bend = make_sim_loss(sim_loss, sim_settings), BendingEnergyLoss()
+        if any(True for _ in self.sim.parameters()):
+            self.sim.to(next(reg_model.parameters()).device)          # (VoxelMorphLNCC keeps the reference's all-ones filter parameter)
 
     def gradients(self, source, target):
         """zero_grad -> forward -> losses -> backward (device work only: capturable in a HIP graph, graphs.GraphedStep)."""
@@ -38,7 +53,7 @@ class RegistrationStep:
         with trace.range('reg/forward'):
             disp, warped, deform = self.model(source, target)
         with trace.range('reg/loss'):
-            l_sim = self.ncc(warped, target)
+            l_sim = self.sim(warped, target)
             l_reg = self.bend(disp)
             loss = l_sim + self.lam_reg * l_reg
         with trace.range('reg/backward'):
@@ -63,12 +78,14 @@ class DeepAtlasJointStep:
     """Alternating joint step (one reg phase + one seg phase per image pair)."""
 
     def __init__(self, seg_model, seg_opt, reg_model, reg_opt, n_classes,
-                 lam_sim=1.0, lam_reg=1.0, lam_anat=1.0, lam_sp=1.0, fused=True):
+                 lam_sim=1.0, lam_reg=1.0, lam_anat=1.0, lam_sp=1.0, fused=True, sim_loss='ncc', sim_settings=None):
         self.fused = fused             # fused anatomy losses (ops.LabelWarpDiceFn / ops.SegPhaseLossFn); False: the op-by-op composition
         self.seg, self.seg_opt, self.reg, self.reg_opt = seg_model, seg_opt, reg_model, reg_opt
         self.n_classes = n_classes
         self.lam = dict(sim=lam_sim, reg=lam_reg, anat=lam_anat, sp=lam_sp)
-        self.ncc, self.bend = NormalizedCrossCorrelationLoss(), BendingEnergyLoss()
+        self.sim, self.bend = make_sim_loss(sim_loss, sim_settings), BendingEnergyLoss()
+        if any(True for _ in self.sim.parameters()):
+            self.sim.to(next(reg_model.parameters()).device)          # (VoxelMorphLNCC keeps the reference's all-ones filter parameter)
         self.dice_logits = DiceLossMultiClass(n_class=n_classes, weight_type='Uniform', no_bg=False, softmax=True, eps=1e-6)
         self.dice_prob = DiceLossMultiClass(n_class=n_classes, weight_type='Uniform', no_bg=False, softmax=False, eps=1e-6)
 
@@ -166,7 +183,7 @@ class DeepAtlasJointStep:
             self._ev_disp.record()                 # the segmentation phase's losses (phase stream) wait for this, not for the rest of the registration phase
         fused = self.fused and ops.fused_anatomy_supported(self.n_classes)
         trace.mark('joint/reg_phase/losses')
-        l_sim = self.ncc(warped, im_t)
+        l_sim = self.sim(warped, im_t)
         l_reg = self.bend(disp)
         if seg_t is None:
             if seg_m is None:

@@ -9,6 +9,8 @@ Checkpoints carry the keys of SegmentationExperiment's ({'epoch', 'model_state_d
 config['atlas_fusion'] ('majority' | 'local', default None: off) adds registration-based segmentation to validation and test(): every
 validation volume is segmented from the training volumes (at most atlas_fusion_max = 5) by multi-atlas label fusion (lib/evalMetrics.py
 atlas_segmentation) and scored against its own segmentation: atlas_dice_per_class / atlas_dice_avg.
+config['sim_loss'] ('ncc' default | 'lncc' | 'mi') and config['sim_settings'] (constructor arguments of that loss) choose the image
+similarity of the step; config['moving_remap'] (None | 'invert' | 'fold') gives the synthetic pairs a moving image of another "modality".
 """
 import datetime
 import os
@@ -20,7 +22,7 @@ import torch
 from torch.utils.data import DataLoader
 
 from .base import BaseExperiment
-from .joint import RegistrationStep
+from .joint import RegistrationStep, SIM_LOSSES
 from .segmentation import SegmentationExperiment
 from ..lib import datasets as med_data
 from ..lib import evalMetrics as metrics
@@ -111,6 +113,14 @@ def check_atlas_fusion(cfg):
     return mode, cap
 
 
+def check_sim_loss(cfg):
+    """config['sim_loss']: 'ncc' (the default, also when absent), 'lncc' or 'mi'; config['sim_settings']: that loss's constructor arguments."""
+    name = cfg.get('sim_loss') or 'ncc'
+    if name not in SIM_LOSSES:
+        raise ValueError("config['sim_loss'] must be one of %s, got %r" % (', '.join(sorted(SIM_LOSSES)), name))
+    return name, dict(cfg.get('sim_settings') or {})
+
+
 def atlas_fusion_text(res):
     """What a validation line adds when atlas fusion is on ('' otherwise)."""
     if 'atlas_dice_avg' not in res:
@@ -128,6 +138,7 @@ class RegistrationExperiment(BaseExperiment):
             print("Debug mode")
             cfg['print_batch_period'] = cfg['valid_epoch_period'] = 2
         self.atlas_fusion, self.atlas_fusion_max = check_atlas_fusion(cfg)
+        self.sim_loss, self.sim_settings = check_sim_loss(cfg)
         self.exp_name = self.experiment_name(cfg)
         run_dir = "debug_reg" if cfg['debug_mode'] else self.exp_name
         self.ckpoint_dir = os.path.join(cfg['log_dir'], run_dir, str(cfg['random_seed']))
@@ -141,11 +152,13 @@ class RegistrationExperiment(BaseExperiment):
 
     @staticmethod
     def experiment_name(cfg):
-        """Reg_<model>_<data dir name>_<n>samples_batch_<b>_<e>epochs_ncc_bending_<lambda_reg>_lr_<lr>[_scheduler_<mode>]"""
+        """Reg_<model>_<data dir name>_<n>samples_batch_<b>_<e>epochs_<sim_loss>_bending_<lambda_reg>_lr_<lr>[_scheduler_<mode>][_moving<remap>]"""
         parts = ['Reg_', cfg['model'], '_', os.path.basename(cfg['data_dir']), '_%ssamples' % cfg['num_samples'], '_batch_%s' % cfg['batch_size'],
-                 '_%sepochs' % cfg['n_epochs'], '_ncc_bending_%s' % cfg['lambda_reg'], '_lr_%s' % cfg['learning_rate']]
+                 '_%sepochs' % cfg['n_epochs'], '_%s_bending_%s' % (cfg.get('sim_loss') or 'ncc', cfg['lambda_reg']), '_lr_%s' % cfg['learning_rate']]
         if cfg['lr_mode'] != 'const':
             parts.append('_scheduler_%s' % cfg['lr_mode'])
+        if cfg.get('moving_remap'):
+            parts.append('_moving%s' % cfg['moving_remap'])
         return ''.join(str(v) for v in parts)
 
     # ---- setup ---------------------------------------------------------------------------------
@@ -163,12 +176,13 @@ class RegistrationExperiment(BaseExperiment):
             return
         dataset = med_data.get_reg_dataset(self.config['data'])
         shape = self.config['synthetic_shape']
-        training_data = dataset(max(self.config['num_samples'], 2), shape, self.config['n_classes'], seed=self.config['random_seed'])
+        remap = {'moving_remap': self.config['moving_remap']} if self.config.get('moving_remap') else {}
+        training_data = dataset(max(self.config['num_samples'], 2), shape, self.config['n_classes'], seed=self.config['random_seed'], **remap)
         sampler = parallel.distributed_sampler(training_data, shuffle=True, seed=self.config['random_seed'])
         self.training_data_loader = DataLoader(training_data, batch_size=self.config['batch_size'], shuffle=sampler is None,
                                                sampler=sampler, num_workers=0)
         validation_data = dataset(max(self.config.get('num_valid_samples', 2), 2), shape, self.config['n_classes'],
-                                  seed=self.config['random_seed'] + 1000)
+                                  seed=self.config['random_seed'] + 1000, **remap)
         self.validation_data_loader = DataLoader(validation_data, batch_size=1, shuffle=False, num_workers=0)
 
     def setup_model(self):
@@ -180,7 +194,7 @@ class RegistrationExperiment(BaseExperiment):
         ops.enable_async_wgrad(bool(self.config.get('async_wgrad', True)))
         ops.set_matrix_precision(self.config.get('matrix_precision') or ops.DEFAULT_MATRIX_PRECISION)
         self.scheduler = SegmentationExperiment.make_scheduler(self.optimizer, self.config)
-        self.step = RegistrationStep(self.model, self.optimizer, lam_reg=self.config['lambda_reg'])
+        self.step = RegistrationStep(self.model, self.optimizer, lam_reg=self.config['lambda_reg'], sim_loss=self.sim_loss, sim_settings=self.sim_settings)
 
     # ---- training ------------------------------------------------------------------------------
     def train(self):

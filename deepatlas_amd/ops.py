@@ -2074,6 +2074,54 @@ class NCCFn(Function):
         return dx, dy
 
 
+MI_STATS_FLOATS = 1096          # DA_MI_STATS_FLOATS (include/deepatlas_hip.h): per sample G [32][32], ga [32], gb [32], MI, padding
+
+
+class MIFn(Function):
+    """Negative mutual information of two images (VoxelMorph's global MutualInformation: Gaussian Parzen windows over `bins` centres in
+    [vmin, vmax]); N x 1 x D x H x W or flat N x V inputs, as NCCFn.  The V x bins weight matrices exist only inside the kernels (mi.hip)."""
+
+    @staticmethod
+    def forward(ctx, x, y, bins=32, sigma_ratio=1.0, vmin=0.0, vmax=1.0):
+        nat.require_cuda(x, y)
+        if x.shape != y.shape or x.dim() not in (2, 5) or (x.dim() == 5 and x.shape[1] != 1):
+            raise ValueError('mutual information expects two N x 1 x D x H x W volumes or two N x V arrays of the same shape, got %s and %s'
+                             % (tuple(x.shape), tuple(y.shape)))
+        if x.dtype != torch.float32 or y.dtype != torch.float32:
+            raise ValueError('mutual information expects float32 inputs')
+        a = ndhwc(x) if x.dim() == 5 else x.contiguous()
+        b = ndhwc(y) if y.dim() == 5 else y.contiguous()
+        N = a.shape[0]
+        V = a.numel() // max(N, 1)
+        bins, sigma_ratio, vmin, vmax = int(bins), float(sigma_ratio), float(vmin), float(vmax)
+        wsb = nat.lib().da_mi_ws_bytes(N, V, bins)
+        if wsb == 0:
+            raise nat.NativeError('da_mi_fwd: unsupported arguments (N %d, V %d, bins %d; 2 <= bins <= 32)' % (N, V, bins))
+        loss = _empty((1,), a)
+        stats = torch.empty((N, MI_STATS_FLOATS), dtype=torch.float32, device=a.device)
+        wp, wn = _ws(wsb, a)
+        call('da_mi_fwd', ptr(a), ptr(b), N, V, bins, vmin, vmax, sigma_ratio, ptr(loss), ptr(stats), wp, wn, stream())
+        ctx.cfg = (bins, vmin, vmax, sigma_ratio, x.dim() == 5, y.dim() == 5)
+        ctx.save_for_backward(a, b, stats)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, gloss):
+        a, b, stats = ctx.saved_tensors
+        bins, vmin, vmax, sigma_ratio, five_x, five_y = ctx.cfg
+        N = a.shape[0]
+        V = a.numel() // N
+        gl = gloss.detach().reshape(1).to(torch.float32).contiguous()
+        dx = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        dy = torch.empty_like(b) if ctx.needs_input_grad[1] else None
+        call('da_mi_bwd', ptr(a), ptr(b), ptr(stats), ptr(gl), ptr(dx), ptr(dy), N, V, bins, vmin, vmax, sigma_ratio, stream())
+        if dx is not None and five_x:
+            dx = ncdhw(dx)
+        if dy is not None and five_y:
+            dy = ncdhw(dy)
+        return dx, dy, None, None, None, None
+
+
 class BendingFn(Function):
     """BendingEnergyLoss.forward, norm='L2' (lib/loss.py:687-730)."""
 

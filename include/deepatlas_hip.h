@@ -504,6 +504,22 @@ int da_lncc_fwd(const float* I, const float* J, int N, int D, int H, int W, int 
 int da_lncc_bwd(const float* I, const float* J, const float* sums, const float* dloss, float* dI, float* dJ,
                 int N, int D, int H, int W, int F, int dil, int stride, float eps, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- mutual information (VoxelMorph's global MutualInformation; Gaussian Parzen windows) -------------------------------
+ * x, y: [N][V] fp32 (float alignment only).  centres c_i = linspace(vmin, vmax, bins), sigma = (vmax - vmin) / (bins - 1) * sigma_ratio,
+ * values clamped to [vmin, vmax]; w_i(x) = exp(-(x - c_i)^2 / (2 sigma^2)) / sum_k (same); P = mean_v w(x_v) w(y_v)^T, a / b its marginals;
+ * MI = sum_ij P_ij log(P_ij / (a_i b_j + 1e-6) + 1e-6); loss[1] = -mean_n MI.  The V x bins weight matrices are never written: both
+ * directions generate them as operands of the fp32 matrix instructions (mi.hip).  stats [N][DA_MI_STATS_FLOATS] is written by fwd and read
+ * by bwd (per sample G = dMI/dP [32][32], ga[32], gb[32], MI, padding).  d loss / dx is zero where x lies outside (vmin, vmax); a NaN voxel
+ * makes its sample's MI, hence the loss, NaN; +-inf is clamped.  dx or dy may be NULL.  Double partials per workgroup in ws, summed in a fixed
+ * order: no atomics, run-to-run bit-identical.  2 <= bins <= 32, finite vmin < vmax, sigma_ratio > 0, N <= 65535; anything else returns
+ * DA_ERR_BADARG before any launch. */
+#define DA_MI_STATS_FLOATS 1096
+size_t da_mi_ws_bytes(int N, long long V, int bins);
+int da_mi_fwd(const float* x, const float* y, int N, long long V, int bins, float vmin, float vmax, float sigma_ratio,
+              float* loss, float* stats, void* ws, size_t ws_bytes, void* stream);
+int da_mi_bwd(const float* x, const float* y, const float* stats, const float* dloss, float* dx, float* dy,
+              int N, long long V, int bins, float vmin, float vmax, float sigma_ratio, void* stream);
+
 /* ---- displacement gradient regulariser (row f2; lib/loss.py:625-671 gradientLoss, registry 'gradient') ------------------
  * disp [N][D][H][W][3]; norm = 2 ('L2') or 1; keeps the reference's +/- quirk along H and W (loss.py:661,663). */
 size_t da_gradloss_ws_bytes(int N, int D, int H, int W);

@@ -7,7 +7,7 @@ import argparse
 import os
 
 from deepatlas_amd.models.deepatlas import DeepAtlasExperiment
-from train_reg import add_common_arguments
+from train_reg import add_common_arguments, apply_similarity_arguments
 
 
 def build_config(args):
@@ -57,12 +57,13 @@ def build_config(args):
         config.pop('matrix_precision', None)
     if not config.get('atlas_fusion'):
         config.pop('atlas_fusion', None)
+    apply_similarity_arguments(config)
     return config
 
 
 def main(argv=None):
     parser = add_common_arguments(argparse.ArgumentParser())
-    parser.add_argument('--lambda-sim', default=1.0, type=float, help='weight of the image similarity (NCC)')
+    parser.add_argument('--lambda-sim', default=1.0, type=float, help='weight of the image similarity (--sim-loss; NCC by default)')
     parser.add_argument('--lambda-anat', default=1.0, type=float, help='weight of the anatomy similarity (Dice of the warped segmentation)')
     parser.add_argument('--lambda-sp', default=1.0, type=float, help='weight of the supervised segmentation loss')
     parser.add_argument('--num-labeled', default=None, type=int, help='number of training volumes with a manual segmentation (default: all)')

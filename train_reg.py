@@ -1,7 +1,8 @@
 """Train the registration net (VoxelMorph) alone: the registration counterpart of train_seg.py, which the reference lists as TODO
-(README.md:15-19).  Same flag style as train_seg.py; the step is NCC + lambda_reg * bending energy (models/joint.py RegistrationStep),
-the data are ordered pairs of synthetic volumes, validation reports the hard-label registration Dice (against the identity
-deformation's) and the Jacobian statistics of the predicted deformation."""
+(README.md:15-19).  Same flag style as train_seg.py; the step is similarity + lambda_reg * bending energy (models/joint.py RegistrationStep;
+--sim-loss ncc | lncc | mi, NCC by default), the data are ordered pairs of synthetic volumes (--moving-remap: the moving image in another
+"modality"), validation reports the hard-label registration Dice (against the identity deformation's) and the Jacobian statistics of the
+predicted deformation."""
 import argparse
 import os
 
@@ -42,6 +43,21 @@ def build_config(args):
         config.pop('matrix_precision', None)
     if not config.get('atlas_fusion'):                    # absent = no registration-based segmentation at validation
         config.pop('atlas_fusion', None)
+    apply_similarity_arguments(config)
+    return config
+
+
+def apply_similarity_arguments(config):
+    """--sim-loss / --mi-bins / --moving-remap -> config['sim_loss'] (always present, 'ncc' when the flag is absent), config['sim_settings'],
+    config['moving_remap'] (absent = both images of a pair in the same modality)."""
+    config['sim_loss'] = config.get('sim_loss') or 'ncc'
+    bins = config.pop('mi_bins', None)
+    settings = dict(config.get('sim_settings') or {})
+    if config['sim_loss'] == 'mi' and bins is not None:
+        settings['num_bins'] = int(bins)
+    config['sim_settings'] = settings
+    if not config.get('moving_remap'):
+        config.pop('moving_remap', None)
     return config
 
 
@@ -61,6 +77,12 @@ def add_common_arguments(parser):
     parser.add_argument('--atlas-fusion', default=None, choices=['majority', 'local'],
                         help="also validate the registration net as a segmenter: every validation volume is segmented from the labelled "
                              "training volumes (at most 5) by multi-atlas label fusion, majority vote or locally weighted voting")
+    parser.add_argument('--sim-loss', default='ncc', choices=['ncc', 'lncc', 'mi'],
+                        help="image similarity of the registration step: global NCC (default), local NCC over 9^3 windows, or mutual information "
+                             "(for pairs whose intensities are not linearly related)")
+    parser.add_argument('--mi-bins', default=None, type=int, help='intensity bins of --sim-loss mi (2..32, default 32)')
+    parser.add_argument('--moving-remap', default=None, choices=['invert', 'fold'],
+                        help="synthetic multi-modal pairs: the moving image is shown as 1 - x ('invert') or |2 x - 1| ('fold'); labels are untouched")
     return parser
 
 
