@@ -129,6 +129,9 @@ SIGNATURES = {
     'da_warp_labels_nearest_counts': (I, [P, I, P, I, P, I, I, I, I, I, P, P, P]),
     'da_jacobian_det_ws_bytes': (SZ, [I, I, I, I]),
     'da_jacobian_det': (I, [P, I, I, I, I, P, P, P, SZ, P]),
+    'da_jacdet_penalty_ws_bytes': (SZ, [I, I, I, I]),
+    'da_jacdet_penalty_fwd': (I, [P, I, I, I, I, F, I, P, P, P, P, SZ, P]),
+    'da_jacdet_penalty_bwd': (I, [P, P, P, P, I, I, I, I, F, I, P]),
     'da_label_fusion_vote': (I, [P, I, LL, P, P, P, I, I, I, I, I, P, P, P]),
     'da_local_msd_weights_ws_bytes': (SZ, [I, I, I, I, I]),
     'da_local_msd_weights': (I, [P, P, I, I, I, I, I, I, F, P, P, SZ, P]),

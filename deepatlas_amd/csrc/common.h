@@ -223,3 +223,29 @@ __device__ __forceinline__ void da_vox3(long long v, int H, int W, int& d, int& 
     }
 }
 
+// Jacobian of x -> x + u(x) at one voxel, u_c = disp_c (size_c - 1) / 2 voxels (the scales sx, sy, sz), disp[..][3] in NDHWC with channels
+// (x, y, z) = (W, H, D) axis: J[c][a] = delta_ca + d u_c / d a with numpy.gradient's differences at unit spacing (central inside, one-sided on
+// the faces, zero along an axis of extent 1).  q points to the voxel (d, h, w).  One definition for da_jacobian_det (regeval.hip) and the folding
+// penalty (jacpen.hip): what is printed and what is trained cannot disagree.
+struct DaF3 { float x, y, z; };
+struct DaJac9 { float j00, j01, j02, j10, j11, j12, j20, j21, j22; };
+__device__ __forceinline__ DaF3 da_ld3(const float* __restrict__ p, float sx, float sy, float sz) { DaF3 r; r.x = p[0] * sx; r.y = p[1] * sy; r.z = p[2] * sz; return r; }
+__device__ __forceinline__ DaJac9 da_jac_at(const float* __restrict__ q, int d, int h, int w, int D, int H, int W, float sx, float sy, float sz) {
+    const long long sW = 3, sH = (long long)W * 3, sD = (long long)H * W * 3;
+    const int wl = w > 0 ? -1 : 0, wh = w < W - 1 ? 1 : 0;
+    const int hl = h > 0 ? -1 : 0, hh = h < H - 1 ? 1 : 0;
+    const int dl = d > 0 ? -1 : 0, dh = d < D - 1 ? 1 : 0;
+    const DaF3 xa = da_ld3(q + wl * sW, sx, sy, sz), xb = da_ld3(q + wh * sW, sx, sy, sz);
+    const DaF3 ya = da_ld3(q + hl * sH, sx, sy, sz), yb = da_ld3(q + hh * sH, sx, sy, sz);
+    const DaF3 za = da_ld3(q + dl * sD, sx, sy, sz), zb = da_ld3(q + dh * sD, sx, sy, sz);
+    const float kx = (wh - wl == 2) ? 0.5f : 1.f, ky = (hh - hl == 2) ? 0.5f : 1.f, kz = (dh - dl == 2) ? 0.5f : 1.f;
+    DaJac9 J;
+    J.j00 = 1.f + (xb.x - xa.x) * kx; J.j01 = (yb.x - ya.x) * ky; J.j02 = (zb.x - za.x) * kz;
+    J.j10 = (xb.y - xa.y) * kx; J.j11 = 1.f + (yb.y - ya.y) * ky; J.j12 = (zb.y - za.y) * kz;
+    J.j20 = (xb.z - xa.z) * kx; J.j21 = (yb.z - ya.z) * ky; J.j22 = 1.f + (zb.z - za.z) * kz;
+    return J;
+}
+// det J by cofactor expansion along the first row, fp32
+__device__ __forceinline__ float da_jac_det(const DaJac9& J) {
+    return J.j00 * (J.j11 * J.j22 - J.j12 * J.j21) - J.j01 * (J.j10 * J.j22 - J.j12 * J.j20) + J.j02 * (J.j10 * J.j21 - J.j11 * J.j20);
+}

@@ -128,9 +128,6 @@ warp_nearest_counts_kernel(const void* __restrict__ lab_m, int m_bytes, const vo
 // No atomics anywhere: two runs are bit-identical.  The sums are taken of det - 1 (exact in double), so that the variance of a
 // nearly-rigid field does not cancel.
 // ------------------------------------------------------------------------------------------------
-struct F3 { float x, y, z; };
-__device__ __forceinline__ F3 ld3(const float* __restrict__ p, float sx, float sy, float sz) { F3 r; r.x = p[0] * sx; r.y = p[1] * sy; r.z = p[2] * sz; return r; }
-
 __global__ void __launch_bounds__(256)
 jacobian_det_kernel(const float* __restrict__ disp, int D, int H, int W, float* __restrict__ det_out, double* __restrict__ partial) {
     __shared__ double red[4][kJacStats];
@@ -138,25 +135,12 @@ jacobian_det_kernel(const float* __restrict__ disp, int D, int H, int W, float* 
     const int V = D * H * W;
     const float* u = disp + (long long)n * V * 3;
     const float sx = (float)(W - 1) / 2.f, sy = (float)(H - 1) / 2.f, sz = (float)(D - 1) / 2.f;
-    const long long sW = 3, sH = (long long)W * 3, sD = (long long)H * W * 3;
     double s1 = 0.0, s2 = 0.0, cnt = 0.0;
     float mn = INFINITY, mx = -INFINITY;
     for (DaXcdLoop L = da_xcd_loop(V, 256); L.i < L.end; L.i += L.step) {
         const int v = (int)L.i;
         int d, h, w; da_vox3(v, H, W, d, h, w);
-        const float* q = u + (long long)v * 3;
-        const int wl = w > 0 ? -1 : 0, wh = w < W - 1 ? 1 : 0;
-        const int hl = h > 0 ? -1 : 0, hh = h < H - 1 ? 1 : 0;
-        const int dl = d > 0 ? -1 : 0, dh = d < D - 1 ? 1 : 0;
-        const F3 xa = ld3(q + wl * sW, sx, sy, sz), xb = ld3(q + wh * sW, sx, sy, sz);
-        const F3 ya = ld3(q + hl * sH, sx, sy, sz), yb = ld3(q + hh * sH, sx, sy, sz);
-        const F3 za = ld3(q + dl * sD, sx, sy, sz), zb = ld3(q + dh * sD, sx, sy, sz);
-        const float kx = (wh - wl == 2) ? 0.5f : 1.f, ky = (hh - hl == 2) ? 0.5f : 1.f, kz = (dh - dl == 2) ? 0.5f : 1.f;
-        // J[c][a] = delta_ca + d u_c / d a, (c, a) in (x, y, z)
-        const float j00 = 1.f + (xb.x - xa.x) * kx, j01 = (yb.x - ya.x) * ky, j02 = (zb.x - za.x) * kz;
-        const float j10 = (xb.y - xa.y) * kx, j11 = 1.f + (yb.y - ya.y) * ky, j12 = (zb.y - za.y) * kz;
-        const float j20 = (xb.z - xa.z) * kx, j21 = (yb.z - ya.z) * ky, j22 = 1.f + (zb.z - za.z) * kz;
-        const float det = j00 * (j11 * j22 - j12 * j21) - j01 * (j10 * j22 - j12 * j20) + j02 * (j10 * j21 - j11 * j20);
+        const float det = da_jac_det(da_jac_at(u + (long long)v * 3, d, h, w, D, H, W, sx, sy, sz));
         if (det_out) det_out[(long long)n * V + v] = det;
         const double e = (double)det - 1.0;
         s1 += e; s2 += e * e;

@@ -2,7 +2,8 @@
 
 Hot path: 'dice' -> DiceLossMultiClass, 'ncc' -> NormalizedCrossCorrelationLoss,
 'bendingEnergy' -> BendingEnergyLoss; SURVEY.md §8f f2: 'lncc' -> VoxelMorphLNCC, 'gradient' -> gradientLoss (reglosses.hip);
-'mi' -> MutualInformationLoss (mi.hip; not in the reference's registry: the similarity for multi-modal pairs).
+'mi' -> MutualInformationLoss (mi.hip; not in the reference's registry: the similarity for multi-modal pairs);
+'jacobian' -> JacobianFoldingLoss (jacpen.hip; not in the reference's registry either: a regulariser on the negative part of det J).
 'mse' / 'L2' are one-line compositions; 'focal' / 'cross_entropy' / 'soft_cross_entropy' share one voxelwise HIP kernel pair (xent.hip).
 """
 import os
@@ -146,6 +147,24 @@ class MutualInformationLoss(nn.Module):
 
     def forward(self, input, target):
         return ops.MIFn.apply(input, target, self.num_bins, self.sigma_ratio, self.minval, self.maxval)
+
+
+class JacobianFoldingLoss(nn.Module):
+    """Folding penalty of a displacement field N x 3 x D x H x W (registry name 'jacobian'): mean over all voxels of max(0, eps - det J)^power,
+    det J exactly the determinant whose non-positive share validation prints as the folding fraction (ops.jacobian_det).  power=1, eps=0 is
+    LapIRN's mean(relu(-det J)); eps > 0 also pushes nearly folded voxels away from 0.  Zero, with a zero gradient, on a field without such voxels:
+    it is independent of the smoothness weight.  power 1 or 2, 0 <= eps <= 1."""
+
+    def __init__(self, eps=0.0, power=1):
+        super(JacobianFoldingLoss, self).__init__()
+        if isinstance(power, bool) or power not in ops.JACOBIAN_PENALTY_POWERS:
+            raise ValueError('JacobianFoldingLoss: power must be 1 or 2, got %r' % (power,))
+        if not 0.0 <= float(eps) <= 1.0:
+            raise ValueError('JacobianFoldingLoss: needs 0 <= eps <= 1, got %r' % (eps,))
+        self.eps, self.power = float(eps), int(power)
+
+    def forward(self, disp):
+        return ops.JacobianPenaltyFn.apply(disp, self.eps, self.power)
 
 
 class LNCCLoss(nn.Module):
@@ -294,6 +313,12 @@ EXTENSION_LOSSES = {
     'mi': MutualInformationLoss,
 }
 loss_dict.update(EXTENSION_LOSSES)
+# ... and the regularisers it does not have (one argument, the displacement field): reachable through get_loss_function, listed by neither
+# get_available_losses() nor get_extension_losses()
+REGULARISER_LOSSES = {
+    'jacobian': JacobianFoldingLoss,
+}
+loss_dict.update(REGULARISER_LOSSES)
 
 
 def get_loss_function(loss_name):
@@ -304,8 +329,12 @@ def get_loss_function(loss_name):
 
 
 def get_available_losses():
-    return [name for name in loss_dict if name not in EXTENSION_LOSSES]
+    return [name for name in loss_dict if name not in EXTENSION_LOSSES and name not in REGULARISER_LOSSES]
 
 
 def get_extension_losses():
     return list(EXTENSION_LOSSES.keys())
+
+
+def get_regulariser_losses():
+    return list(REGULARISER_LOSSES.keys())

@@ -16,7 +16,8 @@ reads.  config['resume_dir'] is the directory that holds the two checkpoint file
 config['atlas_fusion'] ('majority' | 'local', default None: off) adds the registration net's score as a segmenter: every validation volume is
 segmented from the labelled training volumes by multi-atlas label fusion (models/registration.py eval_atlas_fusion), reported as atlas_dice_*.
 config['sim_loss'] / config['sim_settings'] / config['moving_remap']: the image similarity of the registration phase and the synthetic pairs'
-moving-image remap, as in models/registration.py.
+moving-image remap, as in models/registration.py; so are config['lambda_jac'] / config['jac_settings'], the Jacobian folding penalty of the
+registration phase (default 0: off).
 """
 import datetime
 import os
@@ -28,7 +29,8 @@ from torch.utils.data import DataLoader
 
 from .base import BaseExperiment
 from .joint import DeepAtlasJointStep
-from .registration import atlas_fusion_text, check_atlas_fusion, check_sim_loss, dataset_volumes, eval_atlas_fusion, eval_registration
+from .registration import (atlas_fusion_text, check_atlas_fusion, check_jac_penalty, check_sim_loss, dataset_volumes, eval_atlas_fusion,
+                           eval_registration, jac_name_suffix)
 from .segmentation import SegmentationExperiment
 from ..lib import datasets as med_data
 from ..lib.network_factory import get_network
@@ -70,6 +72,7 @@ class DeepAtlasExperiment(BaseExperiment):
                              "gradient all-reduce the other ranks enter")
         self.atlas_fusion, self.atlas_fusion_max = check_atlas_fusion(cfg)
         self.sim_loss, self.sim_settings = check_sim_loss(cfg)
+        self.lambda_jac, self.jac_settings = check_jac_penalty(cfg)
         self.exp_name = self.experiment_name(cfg)
         run_dir = "debug_joint" if cfg['debug_mode'] else self.exp_name
         self.ckpoint_dir = os.path.join(cfg['log_dir'], run_dir, str(cfg['random_seed']))
@@ -84,7 +87,7 @@ class DeepAtlasExperiment(BaseExperiment):
 
     @staticmethod
     def experiment_name(cfg):
-        """Joint_<seg model>_<reg model>_<data dir name>_<n>samples_<k>labeled_<e>epochs_sim<..>_reg<..>_anat<..>_sp<..>_lr_<lr>[_scheduler_<mode>][_pairs<mode>][_<sim_loss>][_moving<remap>]"""
+        """Joint_<seg model>_<reg model>_<data dir name>_<n>samples_<k>labeled_<e>epochs_sim<..>_reg<..>_anat<..>_sp<..>_lr_<lr>[_scheduler_<mode>][_pairs<mode>][_<sim_loss>][_moving<remap>][_jac<lambda_jac>]"""
         parts = ['Joint_', cfg['model'], '_', cfg['reg_model'], '_', os.path.basename(cfg['data_dir']), '_%ssamples' % cfg['num_samples'],
                  '_%slabeled' % cfg['num_labeled'], '_%sepochs' % cfg['n_epochs'],
                  '_sim%s_reg%s_anat%s_sp%s' % (cfg['lambda_sim'], cfg['lambda_reg'], cfg['lambda_anat'], cfg['lambda_sp']), '_lr_%s' % cfg['learning_rate']]
@@ -96,6 +99,7 @@ class DeepAtlasExperiment(BaseExperiment):
             parts.append('_%s' % cfg['sim_loss'])
         if cfg.get('moving_remap'):
             parts.append('_moving%s' % cfg['moving_remap'])
+        parts.append(jac_name_suffix(cfg))
         return ''.join(str(v) for v in parts)
 
     @staticmethod
@@ -150,7 +154,8 @@ class DeepAtlasExperiment(BaseExperiment):
         self.reg_scheduler = SegmentationExperiment.make_scheduler(self.reg_optimizer, dict(cfg, milestones=fractions))
         self.step = DeepAtlasJointStep(self.seg_model, self.seg_optimizer, self.reg_model, self.reg_optimizer, cfg['n_classes'],
                                        lam_sim=cfg['lambda_sim'], lam_reg=cfg['lambda_reg'], lam_anat=cfg['lambda_anat'], lam_sp=cfg['lambda_sp'],
-                                       sim_loss=self.sim_loss, sim_settings=self.sim_settings)
+                                       sim_loss=self.sim_loss, sim_settings=self.sim_settings,
+                                       lam_jac=self.lambda_jac, jac_settings=self.jac_settings)
 
     def initialize_models(self):
         """Resume (both nets, both optimisers, from the two files in config['resume_dir']) or start: each net from its pre-training
@@ -200,6 +205,8 @@ class DeepAtlasExperiment(BaseExperiment):
 
     def train_one_epoch(self):
         running = {'loss_reg': 0.0, 'loss_seg': 0.0}
+        if self.step.jac is not None:
+            running['jac'] = 0.0                   # the folding penalty of the registration phase, logged only when it is on
         iters_per_epoch = max(self.config['samples_per_epoch'] // parallel.world_size(), 1)
         train_data_iter = None
         period = self.config['print_batch_period']
@@ -216,8 +223,9 @@ class DeepAtlasExperiment(BaseExperiment):
             if i % period == period - 1:
                 if parallel.rank() == 0:
                     div = period if i > 0 else 1
-                    print('Epoch[{}/{}] it {} reg loss: {:.3f} seg loss: {:.3f} lr:{} {}'.format(
-                        self.current_epoch, self.config['n_epochs'], i + 1, running['loss_reg'] / div, running['loss_seg'] / div,
+                    jac_text = ' jac: {:.3e}'.format(running['jac'] / div) if 'jac' in running else ''
+                    print('Epoch[{}/{}] it {} reg loss: {:.3f} seg loss: {:.3f}{} lr:{} {}'.format(
+                        self.current_epoch, self.config['n_epochs'], i + 1, running['loss_reg'] / div, running['loss_seg'] / div, jac_text,
                         self.seg_optimizer.param_groups[0]['lr'], datetime.datetime.now().strftime("%D %H:%M:%S")))
                     if self.writer is not None:
                         for k in running:

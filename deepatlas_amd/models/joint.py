@@ -20,12 +20,15 @@ compare against:
 The image similarity ("NCC" above) is chosen with sim_loss = 'ncc' (default: global NCC, what the oracle's steps compute) | 'lncc' (local NCC,
 lib/loss.py VoxelMorphLNCC) | 'mi' (mutual information, lib/loss.py MutualInformationLoss: the one for multi-modal pairs); sim_settings are
 the keyword arguments of that loss's constructor.
+lam_jac > 0 adds lam_jac * JacobianFoldingLoss(**jac_settings)(disp) (lib/loss.py: the mean negative part of det J) to the registration
+loss of either step, in every branch above; with lam_jac = 0 (default) the module is not built and the steps are exactly the ones above.
 """
 
 import torch
 
 from .. import ops, parallel, trace
-from ..lib.loss import DiceLossMultiClass, NormalizedCrossCorrelationLoss, BendingEnergyLoss, VoxelMorphLNCC, MutualInformationLoss
+from ..lib.loss import (DiceLossMultiClass, NormalizedCrossCorrelationLoss, BendingEnergyLoss, VoxelMorphLNCC, MutualInformationLoss,
+                        JacobianFoldingLoss)
 
 SIM_LOSSES = {'ncc': NormalizedCrossCorrelationLoss, 'lncc': VoxelMorphLNCC, 'mi': MutualInformationLoss}
 
@@ -37,11 +40,21 @@ def make_sim_loss(sim_loss='ncc', sim_settings=None):
     return SIM_LOSSES[sim_loss](**dict(sim_settings or {}))
 
 
-class RegistrationStep:
-    """One registration optimisation step: VoxelMorph forward -> NCC + lambda * bending -> backward -> Adam."""
+def make_jac_penalty(lam_jac=0.0, jac_settings=None):
+    """(weight, module) of the folding penalty of a step: (0.0, None) for lam_jac = 0, else JacobianFoldingLoss(**jac_settings).  A negative or
+    non-finite weight raises."""
+    lam = float(lam_jac or 0.0)
+    if not 0.0 <= lam < float('inf'):
+        raise ValueError('lam_jac must be a finite weight >= 0, got %r' % (lam_jac,))
+    return lam, (JacobianFoldingLoss(**dict(jac_settings or {})) if lam > 0.0 else None)
 
-    def __init__(self, reg_model, optimizer, lam_reg=1.0, sim_loss='ncc', sim_settings=None):
+
+class RegistrationStep:
+    """One registration optimisation step: VoxelMorph forward -> NCC + lambda * bending [+ lam_jac * folding penalty] -> backward -> Adam."""
+
+    def __init__(self, reg_model, optimizer, lam_reg=1.0, sim_loss='ncc', sim_settings=None, lam_jac=0.0, jac_settings=None):
         self.model, self.opt, self.lam_reg = reg_model, optimizer, lam_reg
+        self.lam_jac, self.jac = make_jac_penalty(lam_jac, jac_settings)
         self.sim, self.bend = make_sim_loss(sim_loss, sim_settings), BendingEnergyLoss()
         if any(True for _ in self.sim.parameters()):
             self.sim.to(next(reg_model.parameters()).device)          # (VoxelMorphLNCC keeps the reference's all-ones filter parameter)
@@ -56,9 +69,15 @@ class RegistrationStep:
             l_sim = self.sim(warped, target)
             l_reg = self.bend(disp)
             loss = l_sim + self.lam_reg * l_reg
+            if self.jac is not None:
+                l_jac = self.jac(disp)
+                loss = loss + self.lam_jac * l_jac
         with trace.range('reg/backward'):
             loss.backward()
-        return dict(loss=loss.detach(), disp=disp.detach(), warped=warped.detach(), deform=deform.detach(), sim=l_sim.detach(), bend=l_reg.detach())
+        r = dict(loss=loss.detach(), disp=disp.detach(), warped=warped.detach(), deform=deform.detach(), sim=l_sim.detach(), bend=l_reg.detach())
+        if self.jac is not None:
+            r['jac'] = l_jac.detach()
+        return r
 
     def segments(self, source, target):
         """(segments, between, optimizers) for graphs.GraphedStep: the gradient all-reduce sits between the two segments."""
@@ -67,6 +86,8 @@ class RegistrationStep:
 
     def __call__(self, source, target):
         r = self.gradients(source, target)
+        if self.jac is not None:
+            self.last_jac = r['jac']               # (the return tuple keeps its three parts; the experiment logs the penalty from here)
         with trace.range('reg/allreduce'):
             parallel.allreduce_gradients(self.opt)
         with trace.range('reg/adam'):
@@ -78,11 +99,13 @@ class DeepAtlasJointStep:
     """Alternating joint step (one reg phase + one seg phase per image pair)."""
 
     def __init__(self, seg_model, seg_opt, reg_model, reg_opt, n_classes,
-                 lam_sim=1.0, lam_reg=1.0, lam_anat=1.0, lam_sp=1.0, fused=True, sim_loss='ncc', sim_settings=None):
+                 lam_sim=1.0, lam_reg=1.0, lam_anat=1.0, lam_sp=1.0, fused=True, sim_loss='ncc', sim_settings=None,
+                 lam_jac=0.0, jac_settings=None):
         self.fused = fused             # fused anatomy losses (ops.LabelWarpDiceFn / ops.SegPhaseLossFn); False: the op-by-op composition
         self.seg, self.seg_opt, self.reg, self.reg_opt = seg_model, seg_opt, reg_model, reg_opt
         self.n_classes = n_classes
         self.lam = dict(sim=lam_sim, reg=lam_reg, anat=lam_anat, sp=lam_sp)
+        self.lam_jac, self.jac = make_jac_penalty(lam_jac, jac_settings)
         self.sim, self.bend = make_sim_loss(sim_loss, sim_settings), BendingEnergyLoss()
         if any(True for _ in self.sim.parameters()):
             self.sim.to(next(reg_model.parameters()).device)          # (VoxelMorphLNCC keeps the reference's all-ones filter parameter)
@@ -207,9 +230,15 @@ class DeepAtlasJointStep:
             l_anat = torch.zeros((), device=disp.device)
         else:
             loss_r = lam['sim'] * l_sim + lam['reg'] * l_reg + lam['anat'] * l_anat
+        if self.jac is not None:
+            l_jac = self.jac(disp)
+            loss_r = loss_r + self.lam_jac * l_jac
         with trace.range('joint/reg_phase/backward'):
             loss_r.backward()
-        return dict(loss_reg=loss_r.detach(), sim=l_sim.detach(), bend=l_reg.detach(), anat_reg=l_anat.detach(), disp=disp.detach())
+        r = dict(loss_reg=loss_r.detach(), sim=l_sim.detach(), bend=l_reg.detach(), anat_reg=l_anat.detach(), disp=disp.detach())
+        if self.jac is not None:
+            r['jac'] = l_jac.detach()
+        return r
 
     def seg_gradients(self, im_m, seg_m, seg_t, disp, logits_ahead=None):
         """segmentation phase up to its gradients (deformation fixed).  logits_ahead: the forward pass was already issued on the phase stream (_seg_forward_ahead)."""

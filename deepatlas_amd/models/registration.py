@@ -11,6 +11,8 @@ validation volume is segmented from the training volumes (at most atlas_fusion_m
 atlas_segmentation) and scored against its own segmentation: atlas_dice_per_class / atlas_dice_avg.
 config['sim_loss'] ('ncc' default | 'lncc' | 'mi') and config['sim_settings'] (constructor arguments of that loss) choose the image
 similarity of the step; config['moving_remap'] (None | 'invert' | 'fold') gives the synthetic pairs a moving image of another "modality".
+config['lambda_jac'] (default 0: off) weights the Jacobian folding penalty of the step (lib/loss.py JacobianFoldingLoss: the trained form of the
+folding fraction validation prints); config['jac_settings'] are its constructor arguments (eps, power).
 """
 import datetime
 import os
@@ -22,10 +24,11 @@ import torch
 from torch.utils.data import DataLoader
 
 from .base import BaseExperiment
-from .joint import RegistrationStep, SIM_LOSSES
+from .joint import RegistrationStep, SIM_LOSSES, make_jac_penalty
 from .segmentation import SegmentationExperiment
 from ..lib import datasets as med_data
 from ..lib import evalMetrics as metrics
+from ..lib.loss import JacobianFoldingLoss
 from ..lib.network_factory import get_network
 from ..lib.param_dict import save_dict_to_json
 from ..optim import FlatAdam
@@ -121,6 +124,23 @@ def check_sim_loss(cfg):
     return name, dict(cfg.get('sim_settings') or {})
 
 
+def check_jac_penalty(cfg):
+    """config['lambda_jac']: weight of the Jacobian folding penalty, finite and >= 0 (0, also when absent: off); config['jac_settings']: the
+    constructor arguments of JacobianFoldingLoss (eps in [0, 1], power 1 or 2).  Both are checked here, also when the penalty is off."""
+    settings = dict(cfg.get('jac_settings') or {})
+    unknown = sorted(set(settings) - {'eps', 'power'})
+    if unknown:
+        raise ValueError("config['jac_settings'] takes 'eps' and 'power', got %s" % ', '.join(repr(k) for k in unknown))
+    JacobianFoldingLoss(**settings)                           # raises for a bad eps / power
+    return make_jac_penalty(cfg.get('lambda_jac'))[0], settings
+
+
+def jac_name_suffix(cfg):
+    """'_jac<lambda>' for an experiment name when the penalty is on, '' otherwise (names of runs without it stay as they were)."""
+    lam = cfg.get('lambda_jac') or 0.0
+    return '_jac%s' % lam if lam > 0 else ''
+
+
 def atlas_fusion_text(res):
     """What a validation line adds when atlas fusion is on ('' otherwise)."""
     if 'atlas_dice_avg' not in res:
@@ -139,6 +159,7 @@ class RegistrationExperiment(BaseExperiment):
             cfg['print_batch_period'] = cfg['valid_epoch_period'] = 2
         self.atlas_fusion, self.atlas_fusion_max = check_atlas_fusion(cfg)
         self.sim_loss, self.sim_settings = check_sim_loss(cfg)
+        self.lambda_jac, self.jac_settings = check_jac_penalty(cfg)
         self.exp_name = self.experiment_name(cfg)
         run_dir = "debug_reg" if cfg['debug_mode'] else self.exp_name
         self.ckpoint_dir = os.path.join(cfg['log_dir'], run_dir, str(cfg['random_seed']))
@@ -152,13 +173,14 @@ class RegistrationExperiment(BaseExperiment):
 
     @staticmethod
     def experiment_name(cfg):
-        """Reg_<model>_<data dir name>_<n>samples_batch_<b>_<e>epochs_<sim_loss>_bending_<lambda_reg>_lr_<lr>[_scheduler_<mode>][_moving<remap>]"""
+        """Reg_<model>_<data dir name>_<n>samples_batch_<b>_<e>epochs_<sim_loss>_bending_<lambda_reg>_lr_<lr>[_scheduler_<mode>][_moving<remap>][_jac<lambda_jac>]"""
         parts = ['Reg_', cfg['model'], '_', os.path.basename(cfg['data_dir']), '_%ssamples' % cfg['num_samples'], '_batch_%s' % cfg['batch_size'],
                  '_%sepochs' % cfg['n_epochs'], '_%s_bending_%s' % (cfg.get('sim_loss') or 'ncc', cfg['lambda_reg']), '_lr_%s' % cfg['learning_rate']]
         if cfg['lr_mode'] != 'const':
             parts.append('_scheduler_%s' % cfg['lr_mode'])
         if cfg.get('moving_remap'):
             parts.append('_moving%s' % cfg['moving_remap'])
+        parts.append(jac_name_suffix(cfg))
         return ''.join(str(v) for v in parts)
 
     # ---- setup ---------------------------------------------------------------------------------
@@ -194,7 +216,8 @@ class RegistrationExperiment(BaseExperiment):
         ops.enable_async_wgrad(bool(self.config.get('async_wgrad', True)))
         ops.set_matrix_precision(self.config.get('matrix_precision') or ops.DEFAULT_MATRIX_PRECISION)
         self.scheduler = SegmentationExperiment.make_scheduler(self.optimizer, self.config)
-        self.step = RegistrationStep(self.model, self.optimizer, lam_reg=self.config['lambda_reg'], sim_loss=self.sim_loss, sim_settings=self.sim_settings)
+        self.step = RegistrationStep(self.model, self.optimizer, lam_reg=self.config['lambda_reg'], sim_loss=self.sim_loss, sim_settings=self.sim_settings,
+                                     lam_jac=self.lambda_jac, jac_settings=self.jac_settings)
 
     # ---- training ------------------------------------------------------------------------------
     def train(self):
@@ -218,6 +241,7 @@ class RegistrationExperiment(BaseExperiment):
 
     def train_one_epoch(self):
         running_loss = 0.0
+        running_jac = None                         # the folding penalty of the period, summed on the device (penalty on only)
         iters_per_epoch = max(self.config['samples_per_epoch'] // (self.config['batch_size'] * parallel.world_size()), 1)
         train_data_iter = None
         period = self.config['print_batch_period']
@@ -230,15 +254,21 @@ class RegistrationExperiment(BaseExperiment):
             self.global_step = (self.current_epoch - 1) * iters_per_epoch + (i + 1) * self.config['batch_size']
             loss, _, _ = self.train_step(batch[0], batch[1])
             running_loss += loss.item()
+            if self.step.jac is not None:
+                running_jac = self.step.last_jac if running_jac is None else running_jac + self.step.last_jac
             if i % period == period - 1:
                 if parallel.rank() == 0:
-                    print('Epoch[{}/{}] it {} loss: {:.3f} lr:{} {}'.format(
-                        self.current_epoch, self.config['n_epochs'], i + 1, running_loss / period if i > 0 else running_loss,
+                    jac_text = '' if running_jac is None else ' jac: {:.3e}'.format(running_jac.item() / (period if i > 0 else 1))
+                    print('Epoch[{}/{}] it {} loss: {:.3f}{} lr:{} {}'.format(
+                        self.current_epoch, self.config['n_epochs'], i + 1, running_loss / period if i > 0 else running_loss, jac_text,
                         self.optimizer.param_groups[0]['lr'], datetime.datetime.now().strftime("%D %H:%M:%S")))
                     if self.writer is not None:
                         self.writer.add_scalar('loss/training', running_loss / period, global_step=self.global_step)
                         self.writer.add_scalar('learning_rate', self.optimizer.param_groups[0]['lr'], global_step=self.global_step)
+                        if running_jac is not None:
+                            self.writer.add_scalar('loss/training_jac', running_jac.item() / period, global_step=self.global_step)
                 running_loss = 0.0
+                running_jac = None
 
     def eval(self, dataloader):
         res = eval_registration(self.model, dataloader, self.config['n_classes'], self.device)

@@ -2150,6 +2150,65 @@ class BendingFn(Function):
         return ncdhw(du), None, None, None
 
 
+JACOBIAN_PENALTY_POWERS = (1, 2)
+
+
+def _jacobian_penalty_args(disp, eps, power):
+    """Checks of JacobianPenaltyFn that need no device: (eps, power) as (float, int)."""
+    if disp.dim() != 5 or disp.shape[1] != 3:
+        raise ValueError('the Jacobian penalty expects a N x 3 x D x H x W displacement field, got %s' % (tuple(disp.shape),))
+    if disp.dtype != torch.float32:
+        raise ValueError('the Jacobian penalty expects a float32 displacement field, got %s' % disp.dtype)
+    if isinstance(power, bool) or power not in JACOBIAN_PENALTY_POWERS:
+        raise ValueError('the Jacobian penalty takes power 1 or 2, got %r' % (power,))
+    if not 0.0 <= float(eps) <= 1.0:
+        raise ValueError('the Jacobian penalty takes 0 <= eps <= 1, got %r' % (eps,))
+    return float(eps), int(power)
+
+
+def _jacobian_penalty_fwd(disp, eps, power, want_stats):
+    eps, power = _jacobian_penalty_args(disp, eps, power)
+    u = ndhwc(disp)
+    N, D, H, W, _ = u.shape
+    loss = _empty((1,), u)
+    det = _empty((N, D, H, W), u)
+    stats = torch.empty((2,), dtype=torch.float64, device=u.device) if want_stats else None
+    with torch.cuda.device(u.device):
+        wp, wn = _ws(nat.lib().da_jacdet_penalty_ws_bytes(N, D, H, W), u)
+        call('da_jacdet_penalty_fwd', ptr(u), N, D, H, W, eps, power, ptr(loss), ptr(stats), ptr(det), wp, wn, stream())
+    return u, loss, det, stats, eps, power
+
+
+class JacobianPenaltyFn(Function):
+    """Folding penalty mean(max(0, eps - det J)^power) of a displacement field N x 3 x D x H x W (normalised units, as WarpFn takes it), det J
+    exactly as jacobian_det computes it (csrc/jacpen.hip).  power 1 or 2, 0 <= eps <= 1; a float32 scalar."""
+
+    @staticmethod
+    def forward(ctx, disp, eps=0.0, power=1):
+        u, loss, det, _, eps, power = _jacobian_penalty_fwd(disp, eps, power, False)
+        ctx.cfg = (eps, power)
+        ctx.save_for_backward(u, det)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, gloss):
+        u, det = ctx.saved_tensors
+        N, D, H, W, _ = u.shape
+        eps, power = ctx.cfg
+        gl = gloss.detach().reshape(1).to(torch.float32).contiguous()
+        du = torch.empty_like(u)
+        with torch.cuda.device(u.device):
+            call('da_jacdet_penalty_bwd', ptr(u), ptr(det), ptr(gl), ptr(du), N, D, H, W, eps, power, stream())
+        return ncdhw(du), None, None
+
+
+def jacobian_penalty_stats(disp, eps=0.0, power=1):
+    """What the penalty sees of a field, without autograd: (loss float32 scalar, stats float64 [2] = (sum of the penalties over all N V voxels,
+    number of active voxels: det J < eps)), both on the device."""
+    _, loss, _, stats, _, _ = _jacobian_penalty_fwd(disp.detach(), eps, power, True)
+    return loss.reshape(()), stats
+
+
 class XentFn(Function):
     """Cross-entropy family of the loss registry (lib/loss.py:739-761) on N x C x D x H x W logits: mode 0 nn.CrossEntropyLoss,
     1 FocalLoss.forward (lib/loss.py:181-213), 2 SoftCrossEntropy.forward with a probability target (:115-154)."""

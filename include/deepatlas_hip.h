@@ -560,6 +560,21 @@ int da_warp_labels_nearest_counts(const void* lab_m, int m_bytes, const void* la
 size_t da_jacobian_det_ws_bytes(int N, int D, int H, int W);
 int da_jacobian_det(const float* disp, int N, int D, int H, int W, double* stats /*[N][8]*/, float* det_out,
                     void* ws, size_t ws_bytes, void* stream);
+/* Jacobian folding penalty (jacpen.hip), the differentiable companion of da_jacobian_det's folding count:
+ * loss[1] = 1 / (N V) sum_n sum_x max(0, eps - det J_n(x))^power with det J exactly as above (same units, differences and fp32 cofactor
+ * expansion; here an extent of 1 is accepted and gives a zero derivative along its axis).  power 1 or 2, 0 <= eps <= 1, N <= 65535; anything
+ * else returns DA_ERR_BADARG before any launch, DA_ERR_UNSUPPORTED for volumes of >= 2^29 voxels.  A voxel is active iff det < eps; the
+ * identity field has loss 0 and a gradient of exact zeros.  A voxel whose det is not finite makes the loss NaN (and its gradient terms NaN):
+ * a non-finite displacement never passes as fold-free, and nothing is indexed by a data value.  fwd writes det [N][D][H][W] fp32, which bwd
+ * reads, and, when stats is not NULL, stats[2] doubles = (sum of the penalties, number of active voxels).  The sum is accumulated in double
+ * from per-workgroup partials added in index order.  bwd: d_disp [N][D][H][W][3] = dloss[0] x d loss / d disp, a gather through
+ * d det / d J_ca = cofactor_ca and the difference stencil (one-sided face rows and the scale (size_c - 1) / 2 included); the Jacobian of a
+ * neighbour is formed again only where that neighbour is active.  No atomics in either direction: two runs are bit-identical. */
+size_t da_jacdet_penalty_ws_bytes(int N, int D, int H, int W);
+int da_jacdet_penalty_fwd(const float* disp, int N, int D, int H, int W, float eps, int power, float* loss, double* stats /*[2]*/,
+                          float* det, void* ws, size_t ws_bytes, void* stream);
+int da_jacdet_penalty_bwd(const float* disp, const float* det, const float* dloss, float* d_disp, int N, int D, int H, int W,
+                          float eps, int power, void* stream);
 /* Multi-atlas label fusion: K atlas label maps warped to each of N target grids and voted per voxel, in one pass.  disp [N][K][D][H][W][3]
  * (units and channel order as above; field (n, k) maps target n's grid into atlas k), addressed with 64-bit offsets.  labels: uint8 (1) or
  * int64 (8) maps [K][D][H][W] shared by all targets (label_sample_stride 0) or one block per target (label_sample_stride = elements between

@@ -7,7 +7,7 @@ import argparse
 import os
 
 from deepatlas_amd.models.deepatlas import DeepAtlasExperiment
-from train_reg import add_common_arguments, apply_similarity_arguments
+from train_reg import add_common_arguments, apply_jacobian_arguments, apply_similarity_arguments
 
 
 def build_config(args):
@@ -58,6 +58,7 @@ def build_config(args):
     if not config.get('atlas_fusion'):
         config.pop('atlas_fusion', None)
     apply_similarity_arguments(config)
+    apply_jacobian_arguments(config)
     return config
 
 

@@ -2,7 +2,8 @@
 (README.md:15-19).  Same flag style as train_seg.py; the step is similarity + lambda_reg * bending energy (models/joint.py RegistrationStep;
 --sim-loss ncc | lncc | mi, NCC by default), the data are ordered pairs of synthetic volumes (--moving-remap: the moving image in another
 "modality"), validation reports the hard-label registration Dice (against the identity deformation's) and the Jacobian statistics of the
-predicted deformation."""
+predicted deformation.  --lambda-jac > 0 adds the Jacobian folding penalty (--jac-eps, --jac-power) to the step: it trains against the
+folding fraction that validation prints."""
 import argparse
 import os
 
@@ -44,6 +45,19 @@ def build_config(args):
     if not config.get('atlas_fusion'):                    # absent = no registration-based segmentation at validation
         config.pop('atlas_fusion', None)
     apply_similarity_arguments(config)
+    apply_jacobian_arguments(config)
+    return config
+
+
+def apply_jacobian_arguments(config):
+    """--lambda-jac / --jac-eps / --jac-power -> config['lambda_jac'] (0 when the flag is absent: no penalty) and config['jac_settings']."""
+    config['lambda_jac'] = float(config.get('lambda_jac') or 0.0)
+    settings = dict(config.get('jac_settings') or {})
+    for flag, key in (('jac_eps', 'eps'), ('jac_power', 'power')):
+        value = config.pop(flag, None)
+        if value is not None:
+            settings[key] = value
+    config['jac_settings'] = settings
     return config
 
 
@@ -83,6 +97,10 @@ def add_common_arguments(parser):
     parser.add_argument('--mi-bins', default=None, type=int, help='intensity bins of --sim-loss mi (2..32, default 32)')
     parser.add_argument('--moving-remap', default=None, choices=['invert', 'fold'],
                         help="synthetic multi-modal pairs: the moving image is shown as 1 - x ('invert') or |2 x - 1| ('fold'); labels are untouched")
+    parser.add_argument('--lambda-jac', default=0.0, type=float,
+                        help='weight of the Jacobian folding penalty mean(max(0, eps - det J)^power) of the predicted deformation (0: off)')
+    parser.add_argument('--jac-eps', default=None, type=float, help='margin of --lambda-jac: voxels with det J < eps are penalised (0..1, default 0)')
+    parser.add_argument('--jac-power', default=None, type=int, choices=[1, 2], help='exponent of --lambda-jac (default 1)')
     return parser
 
 
