@@ -132,6 +132,9 @@ SIGNATURES = {
     'da_jacdet_penalty_ws_bytes': (SZ, [I, I, I, I]),
     'da_jacdet_penalty_fwd': (I, [P, I, I, I, I, F, I, P, P, P, P, SZ, P]),
     'da_jacdet_penalty_bwd': (I, [P, P, P, P, I, I, I, I, F, I, P]),
+    'da_invcons_ws_bytes': (SZ, [I, I, I, I]),
+    'da_invcons_fwd': (I, [P, P, I, I, I, I, P, P, P, P, SZ, P]),
+    'da_invcons_bwd': (I, [P, P, P, P, P, P, I, I, I, I, I, P, SZ, P]),
     'da_label_fusion_vote': (I, [P, I, LL, P, P, P, I, I, I, I, I, P, P, P]),
     'da_local_msd_weights_ws_bytes': (SZ, [I, I, I, I, I]),
     'da_local_msd_weights': (I, [P, P, I, I, I, I, I, I, F, P, P, SZ, P]),

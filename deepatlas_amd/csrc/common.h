@@ -249,3 +249,35 @@ __device__ __forceinline__ DaJac9 da_jac_at(const float* __restrict__ q, int d, 
 __device__ __forceinline__ float da_jac_det(const DaJac9& J) {
     return J.j00 * (J.j11 * J.j22 - J.j12 * J.j21) - J.j01 * (J.j10 * J.j22 - J.j12 * J.j20) + J.j02 * (J.j10 * J.j21 - J.j11 * J.j20);
 }
+
+// Trilinear sampling of a volume at identity + disp, as the warp defines it (warp.hip): `deform = disp + identity` with the identity of
+// lib/utils.py:97 and grid_sample(bilinear, zeros, align_corners=True)'s unnormalisation, all in fp32.  One definition for the warp family
+// (warp.hip) and the inverse-consistency composition (invcons.hip): what is warped and what is composed sample the same point.
+struct DaTaps {
+    int x0, y0, z0;
+    float fx0, fx1, fy0, fy1, fz0, fz1;   // f?0 = coord - floor, f?1 = floor + 1 - coord
+};
+
+__device__ __forceinline__ float da_id_coord(int k, int size) {
+    // lib/utils.py:97: arange(size).float() / (size - 1) * 2.0 - 1
+    return (float)k / (float)(size - 1) * 2.0f - 1.0f;
+}
+
+__device__ __forceinline__ DaTaps da_make_taps(float gx, float gy, float gz, int D, int H, int W) {
+    // grid_sampler_unnormalize(align_corners=True): ((coord + 1) / 2) * (size - 1)
+    const float ix = ((gx + 1.f) / 2.f) * (float)(W - 1);
+    const float iy = ((gy + 1.f) / 2.f) * (float)(H - 1);
+    const float iz = ((gz + 1.f) / 2.f) * (float)(D - 1);
+    DaTaps t;
+    const float x0 = floorf(ix), y0 = floorf(iy), z0 = floorf(iz);
+    t.x0 = (int)x0; t.y0 = (int)y0; t.z0 = (int)z0;
+    t.fx0 = ix - x0; t.fx1 = (x0 + 1.f) - ix;
+    t.fy0 = iy - y0; t.fy1 = (y0 + 1.f) - iy;
+    t.fz0 = iz - z0; t.fz1 = (z0 + 1.f) - iz;
+    return t;
+}
+
+__device__ __forceinline__ bool da_is_finite_coord(float a, float b, float c) {
+    // NaN / huge coordinates -> every tap out of range (int conversion of NaN is undefined)
+    return fabsf(a) < 1e9f && fabsf(b) < 1e9f && fabsf(c) < 1e9f;
+}

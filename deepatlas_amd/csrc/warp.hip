@@ -8,35 +8,6 @@
 
 namespace {
 
-struct Taps {
-    int x0, y0, z0;
-    float fx0, fx1, fy0, fy1, fz0, fz1;   // f?0 = coord - floor, f?1 = floor + 1 - coord
-};
-
-__device__ __forceinline__ float id_coord(int k, int size) {
-    // lib/utils.py:97: arange(size).float() / (size - 1) * 2.0 - 1
-    return (float)k / (float)(size - 1) * 2.0f - 1.0f;
-}
-
-__device__ __forceinline__ Taps make_taps(float gx, float gy, float gz, int D, int H, int W) {
-    // grid_sampler_unnormalize(align_corners=True): ((coord + 1) / 2) * (size - 1)
-    const float ix = ((gx + 1.f) / 2.f) * (float)(W - 1);
-    const float iy = ((gy + 1.f) / 2.f) * (float)(H - 1);
-    const float iz = ((gz + 1.f) / 2.f) * (float)(D - 1);
-    Taps t;
-    const float x0 = floorf(ix), y0 = floorf(iy), z0 = floorf(iz);
-    t.x0 = (int)x0; t.y0 = (int)y0; t.z0 = (int)z0;
-    t.fx0 = ix - x0; t.fx1 = (x0 + 1.f) - ix;
-    t.fy0 = iy - y0; t.fy1 = (y0 + 1.f) - iy;
-    t.fz0 = iz - z0; t.fz1 = (z0 + 1.f) - iz;
-    return t;
-}
-
-__device__ __forceinline__ bool is_finite_coord(float a, float b, float c) {
-    // NaN / huge coordinates -> every tap out of range (int conversion of NaN is undefined)
-    return fabsf(a) < 1e9f && fabsf(b) < 1e9f && fabsf(c) < 1e9f;
-}
-
 // LPV lanes cooperate on one voxel (each owns VEC contiguous channels); LPV == 1 loops over all channels.
 template <int VEC>
 __global__ void warp_fwd_kernel(const float* __restrict__ src, const float* __restrict__ disp,
@@ -48,12 +19,12 @@ __global__ void warp_fwd_kernel(const float* __restrict__ src, const float* __re
         const long long i = L.i;
         int q; long long v; da_divmod(i, lpv, v, q);
         int n, d, h, w; da_vox4(v, D, H, W, n, d, h, w);
-        const float gx = disp[v * 3 + 0] + id_coord(w, W);
-        const float gy = disp[v * 3 + 1] + id_coord(h, H);
-        const float gz = disp[v * 3 + 2] + id_coord(d, D);
+        const float gx = disp[v * 3 + 0] + da_id_coord(w, W);
+        const float gy = disp[v * 3 + 1] + da_id_coord(h, H);
+        const float gz = disp[v * 3 + 2] + da_id_coord(d, D);
         if (deform && q == 0) { deform[v * 3 + 0] = gx; deform[v * 3 + 1] = gy; deform[v * 3 + 2] = gz; }
-        const bool fin = is_finite_coord(gx, gy, gz);
-        const Taps t = make_taps(fin ? gx : -4.f, fin ? gy : -4.f, fin ? gz : -4.f, D, H, W);
+        const bool fin = da_is_finite_coord(gx, gy, gz);
+        const DaTaps t = da_make_taps(fin ? gx : -4.f, fin ? gy : -4.f, fin ? gz : -4.f, D, H, W);
         const float* sb = src + (long long)n * D * H * W * C;
         if (VEC == 4) {
             float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -98,8 +69,8 @@ __global__ void warp_fwd_kernel(const float* __restrict__ src, const float* __re
 struct GatherPlan { int base, mask; float fx0, fx1, fy0, fy1, fz0, fz1; };
 
 __device__ __forceinline__ GatherPlan gather_plan(float gx, float gy, float gz, bool live, int D, int H, int W, int C) {
-    const bool fin = live && is_finite_coord(gx, gy, gz);
-    const Taps t = make_taps(fin ? gx : -4.f, fin ? gy : -4.f, fin ? gz : -4.f, D, H, W);
+    const bool fin = live && da_is_finite_coord(gx, gy, gz);
+    const DaTaps t = da_make_taps(fin ? gx : -4.f, fin ? gy : -4.f, fin ? gz : -4.f, D, H, W);
     GatherPlan p;
     p.fx0 = t.fx0; p.fx1 = t.fx1; p.fy0 = t.fy0; p.fy1 = t.fy1; p.fz0 = t.fz0; p.fz1 = t.fz1;
     int m = 0;
@@ -198,7 +169,7 @@ __global__ void __launch_bounds__(256) warp_fwd_grouped_kernel(const float* __re
         if (live) {
             int d, h, w; da_vox3(v, H, W, d, h, w);
             const float* u = disp + ((long long)n * V + v) * 3;
-            gx = u[0] + id_coord(w, W); gy = u[1] + id_coord(h, H); gz = u[2] + id_coord(d, D);
+            gx = u[0] + da_id_coord(w, W); gy = u[1] + da_id_coord(h, H); gz = u[2] + da_id_coord(d, D);
             if (deform) { float* o = deform + ((long long)n * V + v) * 3; o[0] = gx; o[1] = gy; o[2] = gz; }
         }
         const GatherPlan p = gather_plan(gx, gy, gz, live, D, H, W, C);
@@ -232,11 +203,11 @@ __global__ void warp_bwd_kernel(const float* __restrict__ dout, const float* __r
         const long long i = L.i;
         int q; long long v; da_divmod(i, lpv, v, q);
         int n, d, h, w; da_vox4(v, D, H, W, n, d, h, w);
-        const float gx = disp[v * 3 + 0] + id_coord(w, W);
-        const float gy = disp[v * 3 + 1] + id_coord(h, H);
-        const float gz = disp[v * 3 + 2] + id_coord(d, D);
-        const bool fin = is_finite_coord(gx, gy, gz);
-        const Taps t = make_taps(fin ? gx : -4.f, fin ? gy : -4.f, fin ? gz : -4.f, D, H, W);
+        const float gx = disp[v * 3 + 0] + da_id_coord(w, W);
+        const float gy = disp[v * 3 + 1] + da_id_coord(h, H);
+        const float gz = disp[v * 3 + 2] + da_id_coord(d, D);
+        const bool fin = da_is_finite_coord(gx, gy, gz);
+        const DaTaps t = da_make_taps(fin ? gx : -4.f, fin ? gy : -4.f, fin ? gz : -4.f, D, H, W);
         const long long sbase = (long long)n * D * H * W * C;
         float gix = 0.f, giy = 0.f, giz = 0.f;
         const int c0 = (VEC == 4) ? q * 4 : 0;
@@ -296,11 +267,11 @@ __global__ void warp_bwd_dsrc_lane_kernel(const float* __restrict__ dout, const 
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         int c; long long v; da_divmod(i, C, v, c);
         int n, d, h, w; da_vox4(v, D, H, W, n, d, h, w);
-        const float gx = disp[v * 3 + 0] + id_coord(w, W);
-        const float gy = disp[v * 3 + 1] + id_coord(h, H);
-        const float gz = disp[v * 3 + 2] + id_coord(d, D);
-        if (!is_finite_coord(gx, gy, gz)) continue;
-        const Taps t = make_taps(gx, gy, gz, D, H, W);
+        const float gx = disp[v * 3 + 0] + da_id_coord(w, W);
+        const float gy = disp[v * 3 + 1] + da_id_coord(h, H);
+        const float gz = disp[v * 3 + 2] + da_id_coord(d, D);
+        if (!da_is_finite_coord(gx, gy, gz)) continue;
+        const DaTaps t = da_make_taps(gx, gy, gz, D, H, W);
         const float g = dout[i];
         float* base = d_src + (long long)n * D * H * W * C + c;
 #pragma unroll
@@ -345,11 +316,11 @@ __global__ void warp_bwd_dsrc_fixed_kernel(const float* __restrict__ dout, const
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         int c; long long v; da_divmod(i, C, v, c);
         int n, d, h, w; da_vox4(v, D, H, W, n, d, h, w);
-        const float gx = disp[v * 3 + 0] + id_coord(w, W);
-        const float gy = disp[v * 3 + 1] + id_coord(h, H);
-        const float gz = disp[v * 3 + 2] + id_coord(d, D);
-        if (!is_finite_coord(gx, gy, gz)) continue;
-        const Taps t = make_taps(gx, gy, gz, D, H, W);
+        const float gx = disp[v * 3 + 0] + da_id_coord(w, W);
+        const float gy = disp[v * 3 + 1] + da_id_coord(h, H);
+        const float gz = disp[v * 3 + 2] + da_id_coord(d, D);
+        if (!da_is_finite_coord(gx, gy, gz)) continue;
+        const DaTaps t = da_make_taps(gx, gy, gz, D, H, W);
         const float g = dout[i];
         unsigned long long* base = acc + (long long)n * D * H * W * C + c;
 #pragma unroll
@@ -387,11 +358,11 @@ __global__ void warp_labels_fwd_kernel(const void* __restrict__ labels, int labe
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         int c0; long long v; da_divmod(i, cq, v, c0); c0 *= VEC;
         int n, d, h, w; da_vox4(v, D, H, W, n, d, h, w);
-        const float gx = disp[v * 3 + 0] + id_coord(w, W);
-        const float gy = disp[v * 3 + 1] + id_coord(h, H);
-        const float gz = disp[v * 3 + 2] + id_coord(d, D);
-        const bool fin = is_finite_coord(gx, gy, gz);
-        const Taps t = make_taps(fin ? gx : -4.f, fin ? gy : -4.f, fin ? gz : -4.f, D, H, W);
+        const float gx = disp[v * 3 + 0] + da_id_coord(w, W);
+        const float gy = disp[v * 3 + 1] + da_id_coord(h, H);
+        const float gz = disp[v * 3 + 2] + da_id_coord(d, D);
+        const bool fin = da_is_finite_coord(gx, gy, gz);
+        const DaTaps t = da_make_taps(fin ? gx : -4.f, fin ? gy : -4.f, fin ? gz : -4.f, D, H, W);
         const long long sbase = (long long)n * D * H * W;
         float acc[VEC];
 #pragma unroll
@@ -420,11 +391,11 @@ __global__ void warp_labels_bwd_kernel(const float* __restrict__ dout, const voi
     for (DaXcdLoop XL = da_xcd_loop(nvox); XL.i < XL.end; XL.i += XL.step) {
         const long long v = XL.i;
         int n, d, h, w; da_vox4(v, D, H, W, n, d, h, w);
-        const float gx = disp[v * 3 + 0] + id_coord(w, W);
-        const float gy = disp[v * 3 + 1] + id_coord(h, H);
-        const float gz = disp[v * 3 + 2] + id_coord(d, D);
-        const bool fin = is_finite_coord(gx, gy, gz);
-        const Taps t = make_taps(fin ? gx : -4.f, fin ? gy : -4.f, fin ? gz : -4.f, D, H, W);
+        const float gx = disp[v * 3 + 0] + da_id_coord(w, W);
+        const float gy = disp[v * 3 + 1] + da_id_coord(h, H);
+        const float gz = disp[v * 3 + 2] + da_id_coord(d, D);
+        const bool fin = da_is_finite_coord(gx, gy, gz);
+        const DaTaps t = da_make_taps(fin ? gx : -4.f, fin ? gy : -4.f, fin ? gz : -4.f, D, H, W);
         const long long sbase = (long long)n * D * H * W;
         float gix = 0.f, giy = 0.f, giz = 0.f;
 #pragma unroll
@@ -450,9 +421,9 @@ __global__ void identity_grid_kernel(float* __restrict__ out, int D, int H, int 
     const long long V = (long long)D * H * W;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < V; i += (long long)gridDim.x * blockDim.x) {
         int d, h, w; da_vox3(i, H, W, d, h, w);
-        out[i] = normalize ? id_coord(w, W) : (float)w;           // channel 0: W axis (x)
-        out[V + i] = normalize ? id_coord(h, H) : (float)h;       // channel 1: H axis (y)
-        out[2 * V + i] = normalize ? id_coord(d, D) : (float)d;   // channel 2: D axis (z)
+        out[i] = normalize ? da_id_coord(w, W) : (float)w;           // channel 0: W axis (x)
+        out[V + i] = normalize ? da_id_coord(h, H) : (float)h;       // channel 1: H axis (y)
+        out[2 * V + i] = normalize ? da_id_coord(d, D) : (float)d;   // channel 2: D axis (z)
     }
 }
 
@@ -486,9 +457,9 @@ __global__ void __launch_bounds__(256) warp_dice_partial_kernel(const float* __r
     for (long long v = v0 + s; v < v1; v += slots) {
         int d, h, w; da_vox3(v, H, W, d, h, w);
         const float* u = disp + ((long long)n * V + v) * 3;
-        const float gx = u[0] + id_coord(w, W), gy = u[1] + id_coord(h, H), gz = u[2] + id_coord(d, D);
-        const bool fin = is_finite_coord(gx, gy, gz);
-        const Taps t = make_taps(fin ? gx : -4.f, fin ? gy : -4.f, fin ? gz : -4.f, D, H, W);
+        const float gx = u[0] + da_id_coord(w, W), gy = u[1] + da_id_coord(h, H), gz = u[2] + da_id_coord(d, D);
+        const bool fin = da_is_finite_coord(gx, gy, gz);
+        const DaTaps t = da_make_taps(fin ? gx : -4.f, fin ? gy : -4.f, fin ? gz : -4.f, D, H, W);
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
@@ -539,7 +510,7 @@ __global__ void __launch_bounds__(256) warp_dice_grouped_kernel(const float* __r
         if (live) {
             int d, h, w; da_vox3(v, H, W, d, h, w);
             const float* u = disp + ((long long)n * V + v) * 3;
-            gx = u[0] + id_coord(w, W); gy = u[1] + id_coord(h, H); gz = u[2] + id_coord(d, D);
+            gx = u[0] + da_id_coord(w, W); gy = u[1] + da_id_coord(h, H); gz = u[2] + da_id_coord(d, D);
             lab = warp_label_at(lab_t, bt, (long long)n * V + v);
         }
         const GatherPlan p = gather_plan(gx, gy, gz, live, D, H, W, C);
@@ -615,9 +586,9 @@ __global__ void __launch_bounds__(256) label_warp_dice_partial_kernel(const void
         const long long vv = live ? v : V - 1;
         int d, h, w; da_vox3(vv, H, W, d, h, w);
         const float* u = disp + (sb + vv) * 3;
-        const float gx = u[0] + id_coord(w, W), gy = u[1] + id_coord(h, H), gz = u[2] + id_coord(d, D);
-        const bool fin = is_finite_coord(gx, gy, gz);
-        const Taps t = make_taps(fin ? gx : -4.f, fin ? gy : -4.f, fin ? gz : -4.f, D, H, W);
+        const float gx = u[0] + da_id_coord(w, W), gy = u[1] + da_id_coord(h, H), gz = u[2] + da_id_coord(d, D);
+        const bool fin = da_is_finite_coord(gx, gy, gz);
+        const DaTaps t = da_make_taps(fin ? gx : -4.f, fin ? gy : -4.f, fin ? gz : -4.f, D, H, W);
         int tl = warp_label_at(lab_t, bt, sb + vv);
         if (!live || tl < 0 || tl >= C) tl = -1;
         int lab[8]; float wk[8];
@@ -676,11 +647,11 @@ __global__ void label_warp_dice_bwd_kernel(const void* __restrict__ lab_m, int b
     for (DaXcdLoop XL = da_xcd_loop(nvox); XL.i < XL.end; XL.i += XL.step) {
         const long long v = XL.i;
         int n, d, h, w; da_vox4(v, D, H, W, n, d, h, w);
-        const float gx = disp[v * 3 + 0] + id_coord(w, W);
-        const float gy = disp[v * 3 + 1] + id_coord(h, H);
-        const float gz = disp[v * 3 + 2] + id_coord(d, D);
-        const bool fin = is_finite_coord(gx, gy, gz);
-        const Taps t = make_taps(fin ? gx : -4.f, fin ? gy : -4.f, fin ? gz : -4.f, D, H, W);
+        const float gx = disp[v * 3 + 0] + da_id_coord(w, W);
+        const float gy = disp[v * 3 + 1] + da_id_coord(h, H);
+        const float gz = disp[v * 3 + 2] + da_id_coord(d, D);
+        const bool fin = da_is_finite_coord(gx, gy, gz);
+        const DaTaps t = da_make_taps(fin ? gx : -4.f, fin ? gy : -4.f, fin ? gz : -4.f, D, H, W);
         const long long sbase = (long long)n * V;
         const int tl = warp_label_at(lab_t, bt, v);
         float gix = 0.f, giy = 0.f, giz = 0.f;
@@ -725,11 +696,11 @@ __global__ void warp_adjoint_labels_kernel(const void* __restrict__ lab_t, int b
         const bool inr = v < nvox;
         int n = 0, d = 0, h = 0, w = 0;
         if (inr) da_vox4(v, D, H, W, n, d, h, w);
-        const float gx = inr ? disp[v * 3 + 0] + id_coord(w, W) : 0.f;
-        const float gy = inr ? disp[v * 3 + 1] + id_coord(h, H) : 0.f;
-        const float gz = inr ? disp[v * 3 + 2] + id_coord(d, D) : 0.f;
-        const bool live = inr && is_finite_coord(gx, gy, gz);
-        const Taps t = make_taps(live ? gx : 0.f, live ? gy : 0.f, live ? gz : 0.f, D, H, W);
+        const float gx = inr ? disp[v * 3 + 0] + da_id_coord(w, W) : 0.f;
+        const float gy = inr ? disp[v * 3 + 1] + da_id_coord(h, H) : 0.f;
+        const float gz = inr ? disp[v * 3 + 2] + da_id_coord(d, D) : 0.f;
+        const bool live = inr && da_is_finite_coord(gx, gy, gz);
+        const DaTaps t = da_make_taps(live ? gx : 0.f, live ? gy : 0.f, live ? gz : 0.f, D, H, W);
         const int lab = inr ? warp_label_at(lab_t, bt, v) : -1;
         const bool lok = lab >= 0 && lab < C;
         // this lane's cell, as one comparable key per (n, label, z0, y0) and the x0 beside it
@@ -785,9 +756,9 @@ __global__ void __launch_bounds__(256) warp_adjoint_labels_box_kernel(const void
         const int x = bx * BX + l % BX, y = by * BY + (l / BX) % BY, z = bz * BZ + l / (BX * BY);
         if (x >= W || y >= H || z >= D) continue;
         const long long v = sbase + ((long long)z * H + y) * W + x;
-        const float gx = disp[v * 3 + 0] + id_coord(x, W), gy = disp[v * 3 + 1] + id_coord(y, H), gz = disp[v * 3 + 2] + id_coord(z, D);
-        if (!is_finite_coord(gx, gy, gz)) continue;
-        const Taps t = make_taps(gx, gy, gz, D, H, W);
+        const float gx = disp[v * 3 + 0] + da_id_coord(x, W), gy = disp[v * 3 + 1] + da_id_coord(y, H), gz = disp[v * 3 + 2] + da_id_coord(z, D);
+        if (!da_is_finite_coord(gx, gy, gz)) continue;
+        const DaTaps t = da_make_taps(gx, gy, gz, D, H, W);
         const int lab = warp_label_at(lab_t, bt, v);
         const bool lok = lab >= 0 && lab < C;
         float* plane = lok ? B + ((long long)n * C + lab) * V : (A_extra ? A_extra + sbase : nullptr);
@@ -954,9 +925,9 @@ __device__ __forceinline__ void softwarp_plan(const void* __restrict__ lab_m, in
                                               int D, int H, int W, int C, float* __restrict__ wrow, unsigned char* __restrict__ lrow) {
     int d, h, w; da_vox3(v, H, W, d, h, w);
     const float* u = disp + (sb + v) * 3;
-    const float gx = u[0] + id_coord(w, W), gy = u[1] + id_coord(h, H), gz = u[2] + id_coord(d, D);
-    const bool fin = is_finite_coord(gx, gy, gz);
-    const Taps t = make_taps(fin ? gx : -4.f, fin ? gy : -4.f, fin ? gz : -4.f, D, H, W);
+    const float gx = u[0] + da_id_coord(w, W), gy = u[1] + da_id_coord(h, H), gz = u[2] + da_id_coord(d, D);
+    const bool fin = da_is_finite_coord(gx, gy, gz);
+    const DaTaps t = da_make_taps(fin ? gx : -4.f, fin ? gy : -4.f, fin ? gz : -4.f, D, H, W);
     float wk[8]; unsigned int lo = 0u, hi = 0u;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
@@ -1109,11 +1080,11 @@ __global__ void softwarp_dice_bwd_disp_kernel(const void* __restrict__ lab_m, in
     for (DaXcdLoop XL = da_xcd_loop(nvox); XL.i < XL.end; XL.i += XL.step) {
         const long long v = XL.i;
         int n, d, h, w; da_vox4(v, D, H, W, n, d, h, w);
-        const float gx = disp[v * 3 + 0] + id_coord(w, W);
-        const float gy = disp[v * 3 + 1] + id_coord(h, H);
-        const float gz = disp[v * 3 + 2] + id_coord(d, D);
-        const bool fin = is_finite_coord(gx, gy, gz);
-        const Taps t = make_taps(fin ? gx : -4.f, fin ? gy : -4.f, fin ? gz : -4.f, D, H, W);
+        const float gx = disp[v * 3 + 0] + da_id_coord(w, W);
+        const float gy = disp[v * 3 + 1] + da_id_coord(h, H);
+        const float gz = disp[v * 3 + 2] + da_id_coord(d, D);
+        const bool fin = da_is_finite_coord(gx, gy, gz);
+        const DaTaps t = da_make_taps(fin ? gx : -4.f, fin ? gy : -4.f, fin ? gz : -4.f, D, H, W);
         const long long sbase = (long long)n * V;
         float gix = 0.f, giy = 0.f, giz = 0.f;
 #pragma unroll

@@ -169,6 +169,14 @@ def jacobian_stats(disp):
             'n_nonpos': s[:, 4].copy(), 'nonpos_frac': s[:, 4] / n_vox}
 
 
+def inverse_consistency(disp_ab, disp_ba):
+    """How far the two directions' fields are from being inverses of each other: per-sample float64 arrays of the composition residual
+    r(x) = u_ab(x) + u_ba(x + u_ab(x)) in voxels: `mean_vox` (mean Euclidean norm), `rms_vox`, `max_vox`, and `outside_frac` = the share of
+    voxels whose sample point x + u_ab(x) leaves the volume (u_ba reads zeros there).  ops.inverse_consistency_stats on the host."""
+    s = ops.inverse_consistency_stats(disp_ab, disp_ba)
+    return {k: v.cpu().numpy() for k, v in s.items()}
+
+
 def atlas_label_fusion(labels, disp, weights=None, n_targets=None):
     """Multi-atlas label fusion (ops.label_fusion): the atlas label maps `labels` (K x D x H x W, or (N K) x D x H x W per target) warped
     with the fields `disp` ((N K) x 3 x D x H x W, atlas index fastest) and voted per voxel -- majority vote, or weighted by `weights`

@@ -3,7 +3,8 @@
 Hot path: 'dice' -> DiceLossMultiClass, 'ncc' -> NormalizedCrossCorrelationLoss,
 'bendingEnergy' -> BendingEnergyLoss; SURVEY.md §8f f2: 'lncc' -> VoxelMorphLNCC, 'gradient' -> gradientLoss (reglosses.hip);
 'mi' -> MutualInformationLoss (mi.hip; not in the reference's registry: the similarity for multi-modal pairs);
-'jacobian' -> JacobianFoldingLoss (jacpen.hip; not in the reference's registry either: a regulariser on the negative part of det J).
+'jacobian' -> JacobianFoldingLoss (jacpen.hip; not in the reference's registry either: a regulariser on the negative part of det J);
+'inverse_consistency' -> InverseConsistencyLoss (invcons.hip; likewise: the composition residual of the two directions' fields).
 'mse' / 'L2' are one-line compositions; 'focal' / 'cross_entropy' / 'soft_cross_entropy' share one voxelwise HIP kernel pair (xent.hip).
 """
 import os
@@ -167,6 +168,23 @@ class JacobianFoldingLoss(nn.Module):
         return ops.JacobianPenaltyFn.apply(disp, self.eps, self.power)
 
 
+class InverseConsistencyLoss(nn.Module):
+    """Inverse-consistency penalty of the two directions' displacement fields, each N x 3 x D x H x W (registry name 'inverse_consistency';
+    ICON / GradICON's composition residual): L(u_ab, u_ba) = mean over all voxels of |s (u_ab(x) + u_ba(x + u_ab(x)))|^2 in voxels^2, u_ba
+    sampled as the warp samples (trilinear, zeros outside).  symmetric=True (default) returns (L(u_ab, u_ba) + L(u_ba, u_ab)) / 2.  Zero exactly
+    when the two maps are inverses of each other on the lattice; needs no labels."""
+
+    def __init__(self, symmetric=True):
+        super(InverseConsistencyLoss, self).__init__()
+        self.symmetric = bool(symmetric)
+
+    def forward(self, u_ab, u_ba):
+        l_ab = ops.InverseConsistencyFn.apply(u_ab, u_ba)
+        if not self.symmetric:
+            return l_ab
+        return 0.5 * (l_ab + ops.InverseConsistencyFn.apply(u_ba, u_ab))
+
+
 class LNCCLoss(nn.Module):
     """lib/loss.py:512-586 (not in the registry): multi-scale LNCC.  Scales, weights, dilations and strides follow `__stepup`
     (:516-540): min(img) > 128 -> windows ms/16, ms/8, ms/4 (weights .1/.3/.6, dilation 2); > 64 -> ms/4, ms/2 (.3/.7,
@@ -319,6 +337,12 @@ REGULARISER_LOSSES = {
     'jacobian': JacobianFoldingLoss,
 }
 loss_dict.update(REGULARISER_LOSSES)
+# ... and the losses of a PAIR of displacement fields (two arguments, the two directions' fields): reachable through get_loss_function, listed by
+# none of get_available_losses() / get_extension_losses() / get_regulariser_losses()
+FIELD_PAIR_LOSSES = {
+    'inverse_consistency': InverseConsistencyLoss,
+}
+loss_dict.update(FIELD_PAIR_LOSSES)
 
 
 def get_loss_function(loss_name):
@@ -329,7 +353,7 @@ def get_loss_function(loss_name):
 
 
 def get_available_losses():
-    return [name for name in loss_dict if name not in EXTENSION_LOSSES and name not in REGULARISER_LOSSES]
+    return [name for name in loss_dict if name not in EXTENSION_LOSSES and name not in REGULARISER_LOSSES and name not in FIELD_PAIR_LOSSES]
 
 
 def get_extension_losses():
@@ -338,3 +362,7 @@ def get_extension_losses():
 
 def get_regulariser_losses():
     return list(REGULARISER_LOSSES.keys())
+
+
+def get_field_pair_losses():
+    return list(FIELD_PAIR_LOSSES.keys())

@@ -22,13 +22,18 @@ lib/loss.py VoxelMorphLNCC) | 'mi' (mutual information, lib/loss.py MutualInform
 the keyword arguments of that loss's constructor.
 lam_jac > 0 adds lam_jac * JacobianFoldingLoss(**jac_settings)(disp) (lib/loss.py: the mean negative part of det J) to the registration
 loss of either step, in every branch above; with lam_jac = 0 (default) the module is not built and the steps are exactly the ones above.
+lam_ic > 0 (RegistrationStep only) makes the registration step inverse-consistent: ONE forward of the net on the doubled batch
+model(cat(S, T), cat(T, S)), rows [:N] = phi_ST and rows [N:] = phi_TS; similarity, bending and the folding penalty over all 2N rows, plus
+lam_ic * InverseConsistencyLoss()(disp[:N], disp[N:]) (lib/loss.py: the mean squared composition residual of the two directions, voxels^2).
+With lam_ic = 0 (default) nothing is built, doubled or concatenated.  The joint step does not take it: its registration phase would need the
+anatomy terms in both directions; a net trained with it enters joint training as a checkpoint.
 """
 
 import torch
 
 from .. import ops, parallel, trace
 from ..lib.loss import (DiceLossMultiClass, NormalizedCrossCorrelationLoss, BendingEnergyLoss, VoxelMorphLNCC, MutualInformationLoss,
-                        JacobianFoldingLoss)
+                        JacobianFoldingLoss, InverseConsistencyLoss)
 
 SIM_LOSSES = {'ncc': NormalizedCrossCorrelationLoss, 'lncc': VoxelMorphLNCC, 'mi': MutualInformationLoss}
 
@@ -49,12 +54,23 @@ def make_jac_penalty(lam_jac=0.0, jac_settings=None):
     return lam, (JacobianFoldingLoss(**dict(jac_settings or {})) if lam > 0.0 else None)
 
 
-class RegistrationStep:
-    """One registration optimisation step: VoxelMorph forward -> NCC + lambda * bending [+ lam_jac * folding penalty] -> backward -> Adam."""
+def make_ic_penalty(lam_ic=0.0):
+    """(weight, module) of the inverse-consistency penalty of a step: (0.0, None) for lam_ic = 0, else the symmetric InverseConsistencyLoss.
+    A negative or non-finite weight raises."""
+    lam = float(lam_ic or 0.0)
+    if not 0.0 <= lam < float('inf'):
+        raise ValueError('lam_ic must be a finite weight >= 0, got %r' % (lam_ic,))
+    return lam, (InverseConsistencyLoss(symmetric=True) if lam > 0.0 else None)
 
-    def __init__(self, reg_model, optimizer, lam_reg=1.0, sim_loss='ncc', sim_settings=None, lam_jac=0.0, jac_settings=None):
+
+class RegistrationStep:
+    """One registration optimisation step: VoxelMorph forward -> NCC + lambda * bending [+ lam_jac * folding penalty] [+ lam_ic * inverse
+    consistency, both directions in one doubled-batch forward] -> backward -> Adam."""
+
+    def __init__(self, reg_model, optimizer, lam_reg=1.0, sim_loss='ncc', sim_settings=None, lam_jac=0.0, jac_settings=None, lam_ic=0.0):
         self.model, self.opt, self.lam_reg = reg_model, optimizer, lam_reg
         self.lam_jac, self.jac = make_jac_penalty(lam_jac, jac_settings)
+        self.lam_ic, self.ic = make_ic_penalty(lam_ic)
         self.sim, self.bend = make_sim_loss(sim_loss, sim_settings), BendingEnergyLoss()
         if any(True for _ in self.sim.parameters()):
             self.sim.to(next(reg_model.parameters()).device)          # (VoxelMorphLNCC keeps the reference's all-ones filter parameter)
@@ -63,6 +79,9 @@ class RegistrationStep:
         """zero_grad -> forward -> losses -> backward (device work only: capturable in a HIP graph, graphs.GraphedStep)."""
         self.model.train()
         self.opt.zero_grad()
+        if self.ic is not None:                    # both directions in one forward: rows [:N] source -> target, rows [N:] target -> source
+            n = source.shape[0]
+            source, target = torch.cat((source, target), 0), torch.cat((target, source), 0)
         with trace.range('reg/forward'):
             disp, warped, deform = self.model(source, target)
         with trace.range('reg/loss'):
@@ -72,11 +91,16 @@ class RegistrationStep:
             if self.jac is not None:
                 l_jac = self.jac(disp)
                 loss = loss + self.lam_jac * l_jac
+            if self.ic is not None:
+                l_ic = self.ic(disp[:n], disp[n:])
+                loss = loss + self.lam_ic * l_ic
         with trace.range('reg/backward'):
             loss.backward()
         r = dict(loss=loss.detach(), disp=disp.detach(), warped=warped.detach(), deform=deform.detach(), sim=l_sim.detach(), bend=l_reg.detach())
         if self.jac is not None:
             r['jac'] = l_jac.detach()
+        if self.ic is not None:
+            r['ic'] = l_ic.detach()
         return r
 
     def segments(self, source, target):
@@ -92,6 +116,10 @@ class RegistrationStep:
             parallel.allreduce_gradients(self.opt)
         with trace.range('reg/adam'):
             self.opt.step()
+        if self.ic is not None:                    # the caller's direction is the first half of the doubled batch
+            n = r['disp'].shape[0] // 2
+            self.last_ic, self.last_disp_reverse = r['ic'], r['disp'][n:]
+            return r['loss'], (r['disp'][:n], r['warped'][:n], r['deform'][:n]), (r['sim'], r['bend'])
         return r['loss'], (r['disp'], r['warped'], r['deform']), (r['sim'], r['bend'])
 
 

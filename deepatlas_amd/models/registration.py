@@ -13,6 +13,9 @@ config['sim_loss'] ('ncc' default | 'lncc' | 'mi') and config['sim_settings'] (c
 similarity of the step; config['moving_remap'] (None | 'invert' | 'fold') gives the synthetic pairs a moving image of another "modality".
 config['lambda_jac'] (default 0: off) weights the Jacobian folding penalty of the step (lib/loss.py JacobianFoldingLoss: the trained form of the
 folding fraction validation prints); config['jac_settings'] are its constructor arguments (eps, power).
+config['lambda_ic'] (default 0: off) weights the inverse-consistency penalty of the step (lib/loss.py InverseConsistencyLoss; the step then predicts
+both directions in one doubled-batch forward); config['report_ic'] (default None: on exactly when lambda_ic > 0) makes validation also run the
+reverse direction and report the composition residual in voxels (ic_mean_vox, ic_max_vox, ic_outside_frac).
 """
 import datetime
 import os
@@ -24,7 +27,7 @@ import torch
 from torch.utils.data import DataLoader
 
 from .base import BaseExperiment
-from .joint import RegistrationStep, SIM_LOSSES, make_jac_penalty
+from .joint import RegistrationStep, SIM_LOSSES, make_jac_penalty, make_ic_penalty
 from .segmentation import SegmentationExperiment
 from ..lib import datasets as med_data
 from ..lib import evalMetrics as metrics
@@ -48,13 +51,17 @@ def _nanmean(a, axis=None):
         return np.nanmean(a, axis=axis)
 
 
-def eval_registration(model, dataloader, n_classes, device):
+def eval_registration(model, dataloader, n_classes, device, report_ic=False):
     """Registration metrics of `model` over a loader of (moving image, fixed image, moving seg, fixed seg, has_moving_seg, name) batches.
     Pairs without a moving segmentation have no registration Dice and are skipped for it; every pair counts for the Jacobian statistics.
     Returns a dict: dice_per_class [C-1] (mean over the pairs that have the class: nanmean), dice_avg (mean over the classes that occur),
     identity_dice_per_class / identity_dice_avg (the same for disp = 0 on the same pairs: what registration bought), nonpos_frac (mean
-    folding fraction), det_mean / det_std (means over the pairs of the per-pair mean / standard deviation of det J), n_pairs, n_dice_pairs."""
+    folding fraction), det_mean / det_std (means over the pairs of the per-pair mean / standard deviation of det J), n_pairs, n_dice_pairs.
+    report_ic: the net is also run in the reverse direction, model(im_t, im_m), and the dict gains ic_mean_vox / ic_max_vox / ic_outside_frac:
+    the means over the pairs of the per-pair mean and maximum of the composition residual |u_mt(x) + u_tm(x + u_mt(x))| in voxels and of the
+    share of voxels whose sample point leaves the volume (metrics.inverse_consistency)."""
     dice, dice_id, jac = [], [], {'nonpos_frac': [], 'mean': [], 'std': []}
+    ic = {'mean_vox': [], 'max_vox': [], 'outside_frac': []}
     with torch.no_grad():
         model.eval()
         for im_m, im_t, seg_m, seg_t, has, _name in dataloader:
@@ -63,6 +70,10 @@ def eval_registration(model, dataloader, n_classes, device):
             js = metrics.jacobian_stats(disp)
             for k in jac:
                 jac[k].append(js[k])
+            if report_ic:
+                ics = metrics.inverse_consistency(disp, model(im_t, im_m)[0])
+                for k in ic:
+                    ic[k].append(ics[k])
             keep = torch.as_tensor(has).reshape(-1).bool()
             if bool(keep.any()):
                 sm, st_, dk = seg_m[keep].to(device), seg_t[keep].to(device), disp[keep.to(device)]
@@ -75,6 +86,9 @@ def eval_registration(model, dataloader, n_classes, device):
         out[key + '_avg'] = float(_nanmean(per)) if np.isfinite(per).any() else float('nan')
     for k, name in (('nonpos_frac', 'nonpos_frac'), ('mean', 'det_mean'), ('std', 'det_std')):
         out[name] = float(np.mean(np.concatenate(jac[k]))) if jac[k] else float('nan')
+    if report_ic:
+        for k in ic:
+            out['ic_' + k] = float(np.mean(np.concatenate(ic[k]))) if ic[k] else float('nan')
     out['n_pairs'] = int(sum(len(a) for a in jac['mean']))
     out['n_dice_pairs'] = int(sum(len(a) for a in dice))
     return out
@@ -141,6 +155,27 @@ def jac_name_suffix(cfg):
     return '_jac%s' % lam if lam > 0 else ''
 
 
+def check_ic_penalty(cfg):
+    """config['lambda_ic']: weight of the inverse-consistency penalty, finite and >= 0 (0, also when absent: off); config['report_ic']: whether
+    validation reports the inverse-consistency error: None (the default, also when absent) = exactly when lambda_ic > 0.  Returns (weight, report)."""
+    lam = make_ic_penalty(cfg.get('lambda_ic'))[0]
+    report = cfg.get('report_ic')
+    return lam, (lam > 0.0 if report is None else bool(report))
+
+
+def ic_name_suffix(cfg):
+    """'_ic<lambda>' for an experiment name when the penalty is on, '' otherwise (names of runs without it stay as they were)."""
+    lam = cfg.get('lambda_ic') or 0.0
+    return '_ic%s' % lam if lam > 0 else ''
+
+
+def ic_text(res):
+    """What a validation or test line adds when the inverse-consistency report is on ('' otherwise)."""
+    if 'ic_mean_vox' not in res:
+        return ''
+    return '  inverse consistency {:.4f} vox mean, {:.3f} max, {:.3%} outside'.format(res['ic_mean_vox'], res['ic_max_vox'], res['ic_outside_frac'])
+
+
 def atlas_fusion_text(res):
     """What a validation line adds when atlas fusion is on ('' otherwise)."""
     if 'atlas_dice_avg' not in res:
@@ -160,6 +195,7 @@ class RegistrationExperiment(BaseExperiment):
         self.atlas_fusion, self.atlas_fusion_max = check_atlas_fusion(cfg)
         self.sim_loss, self.sim_settings = check_sim_loss(cfg)
         self.lambda_jac, self.jac_settings = check_jac_penalty(cfg)
+        self.lambda_ic, self.report_ic = check_ic_penalty(cfg)
         self.exp_name = self.experiment_name(cfg)
         run_dir = "debug_reg" if cfg['debug_mode'] else self.exp_name
         self.ckpoint_dir = os.path.join(cfg['log_dir'], run_dir, str(cfg['random_seed']))
@@ -173,7 +209,7 @@ class RegistrationExperiment(BaseExperiment):
 
     @staticmethod
     def experiment_name(cfg):
-        """Reg_<model>_<data dir name>_<n>samples_batch_<b>_<e>epochs_<sim_loss>_bending_<lambda_reg>_lr_<lr>[_scheduler_<mode>][_moving<remap>][_jac<lambda_jac>]"""
+        """Reg_<model>_<data dir name>_<n>samples_batch_<b>_<e>epochs_<sim_loss>_bending_<lambda_reg>_lr_<lr>[_scheduler_<mode>][_moving<remap>][_jac<lambda_jac>][_ic<lambda_ic>]"""
         parts = ['Reg_', cfg['model'], '_', os.path.basename(cfg['data_dir']), '_%ssamples' % cfg['num_samples'], '_batch_%s' % cfg['batch_size'],
                  '_%sepochs' % cfg['n_epochs'], '_%s_bending_%s' % (cfg.get('sim_loss') or 'ncc', cfg['lambda_reg']), '_lr_%s' % cfg['learning_rate']]
         if cfg['lr_mode'] != 'const':
@@ -181,6 +217,7 @@ class RegistrationExperiment(BaseExperiment):
         if cfg.get('moving_remap'):
             parts.append('_moving%s' % cfg['moving_remap'])
         parts.append(jac_name_suffix(cfg))
+        parts.append(ic_name_suffix(cfg))
         return ''.join(str(v) for v in parts)
 
     # ---- setup ---------------------------------------------------------------------------------
@@ -217,7 +254,7 @@ class RegistrationExperiment(BaseExperiment):
         ops.set_matrix_precision(self.config.get('matrix_precision') or ops.DEFAULT_MATRIX_PRECISION)
         self.scheduler = SegmentationExperiment.make_scheduler(self.optimizer, self.config)
         self.step = RegistrationStep(self.model, self.optimizer, lam_reg=self.config['lambda_reg'], sim_loss=self.sim_loss, sim_settings=self.sim_settings,
-                                     lam_jac=self.lambda_jac, jac_settings=self.jac_settings)
+                                     lam_jac=self.lambda_jac, jac_settings=self.jac_settings, lam_ic=self.lambda_ic)
 
     # ---- training ------------------------------------------------------------------------------
     def train(self):
@@ -242,6 +279,8 @@ class RegistrationExperiment(BaseExperiment):
     def train_one_epoch(self):
         running_loss = 0.0
         running_jac = None                         # the folding penalty of the period, summed on the device (penalty on only)
+        running_ic = None                          # likewise the inverse-consistency penalty (report on and penalty on only)
+        log_ic = self.report_ic and self.step.ic is not None
         iters_per_epoch = max(self.config['samples_per_epoch'] // (self.config['batch_size'] * parallel.world_size()), 1)
         train_data_iter = None
         period = self.config['print_batch_period']
@@ -256,9 +295,13 @@ class RegistrationExperiment(BaseExperiment):
             running_loss += loss.item()
             if self.step.jac is not None:
                 running_jac = self.step.last_jac if running_jac is None else running_jac + self.step.last_jac
+            if log_ic:
+                running_ic = self.step.last_ic if running_ic is None else running_ic + self.step.last_ic
             if i % period == period - 1:
                 if parallel.rank() == 0:
                     jac_text = '' if running_jac is None else ' jac: {:.3e}'.format(running_jac.item() / (period if i > 0 else 1))
+                    if running_ic is not None:
+                        jac_text += ' ic: {:.3e}'.format(running_ic.item() / (period if i > 0 else 1))
                     print('Epoch[{}/{}] it {} loss: {:.3f}{} lr:{} {}'.format(
                         self.current_epoch, self.config['n_epochs'], i + 1, running_loss / period if i > 0 else running_loss, jac_text,
                         self.optimizer.param_groups[0]['lr'], datetime.datetime.now().strftime("%D %H:%M:%S")))
@@ -267,11 +310,14 @@ class RegistrationExperiment(BaseExperiment):
                         self.writer.add_scalar('learning_rate', self.optimizer.param_groups[0]['lr'], global_step=self.global_step)
                         if running_jac is not None:
                             self.writer.add_scalar('loss/training_jac', running_jac.item() / period, global_step=self.global_step)
+                        if running_ic is not None:
+                            self.writer.add_scalar('loss/training_ic', running_ic.item() / period, global_step=self.global_step)
                 running_loss = 0.0
                 running_jac = None
+                running_ic = None
 
     def eval(self, dataloader):
-        res = eval_registration(self.model, dataloader, self.config['n_classes'], self.device)
+        res = eval_registration(self.model, dataloader, self.config['n_classes'], self.device, report_ic=self.report_ic)
         if self.atlas_fusion:
             # the volumes behind the loader's pairs, each segmented from the training volumes (all labelled here), at most atlas_fusion_max
             if self.training_data_loader is None:
@@ -303,8 +349,11 @@ class RegistrationExperiment(BaseExperiment):
             tag = 'validation_{}/'.format(self.config['data'])
             for k in ('dice_avg', 'identity_dice_avg', 'nonpos_frac', 'det_mean', 'det_std'):
                 self.writer.add_scalar(tag + k, res[k], global_step=self.global_step)
-        print("Validation: registration Dice Avg: {:.4f} (identity {:.4f}){}  det J {:.4f} +- {:.4f}, folding {:.3%} ({:.3f} sec) {}".format(
-            score, res['identity_dice_avg'], atlas_fusion_text(res), res['det_mean'], res['det_std'], res['nonpos_frac'], time.time() - start_time,
+            for k in ('ic_mean_vox', 'ic_max_vox', 'ic_outside_frac'):
+                if k in res:
+                    self.writer.add_scalar(tag + k, res[k], global_step=self.global_step)
+        print("Validation: registration Dice Avg: {:.4f} (identity {:.4f}){}  det J {:.4f} +- {:.4f}, folding {:.3%}{} ({:.3f} sec) {}".format(
+            score, res['identity_dice_avg'], atlas_fusion_text(res), res['det_mean'], res['det_std'], res['nonpos_frac'], ic_text(res), time.time() - start_time,
             datetime.datetime.now().strftime("%D %H:%M:%S")))
         if self.current_epoch % self.config['save_ckpts_epoch_period'] == 0:
             self.save_checkpoint({'epoch': self.current_epoch,
@@ -322,6 +371,6 @@ class RegistrationExperiment(BaseExperiment):
         last_epoch, best_score = self.initialize_model(self.model, optimizer=None, ckpoint_path=ckpoint_file)
         loader = self.config.get('testing_data_loader') or self.validation_data_loader
         res = self.eval(loader)
-        print('Testing Model: {} ({} epochs)  registration Dice_avg: {} (identity {})  folding fraction: {}{}'.format(
-            ckpoint_file, last_epoch, res['dice_avg'], res['identity_dice_avg'], res['nonpos_frac'], atlas_fusion_text(res)))
+        print('Testing Model: {} ({} epochs)  registration Dice_avg: {} (identity {})  folding fraction: {}{}{}'.format(
+            ckpoint_file, last_epoch, res['dice_avg'], res['identity_dice_avg'], res['nonpos_frac'], atlas_fusion_text(res), ic_text(res)))
         return res

@@ -2209,6 +2209,68 @@ def jacobian_penalty_stats(disp, eps=0.0, power=1):
     return loss.reshape(()), stats
 
 
+INVCONS_STATS = 4          # doubles per sample of da_invcons_fwd's stats: sum |s r|^2, sum |s r|, max |s r|, voxels sampled outside
+
+
+def _invcons_fwd(u_a, u_b, want_stats, want_resid):
+    for name, t in (('u_a', u_a), ('u_b', u_b)):
+        if t.dim() != 5 or t.shape[1] != 3:
+            raise ValueError('inverse consistency expects N x 3 x D x H x W displacement fields, got %s for %s' % (tuple(t.shape), name))
+    if u_a.shape != u_b.shape:
+        raise ValueError('inverse consistency expects two fields of one shape, got %s and %s' % (tuple(u_a.shape), tuple(u_b.shape)))
+    a, b = ndhwc(u_a), ndhwc(u_b)
+    N, D, H, W, _ = a.shape
+    loss = _empty((1,), a)
+    resid = torch.empty_like(a) if want_resid else None
+    stats = torch.empty((N, INVCONS_STATS), dtype=torch.float64, device=a.device) if want_stats else None
+    with torch.cuda.device(a.device):
+        wp, wn = _ws(nat.lib().da_invcons_ws_bytes(N, D, H, W), a)
+        call('da_invcons_fwd', ptr(a), ptr(b), N, D, H, W, ptr(loss), ptr(stats), ptr(resid), wp, wn, stream())
+    return a, b, loss, stats, resid
+
+
+class InverseConsistencyFn(Function):
+    """Inverse-consistency penalty of two displacement fields N x 3 x D x H x W (normalised units, as WarpFn takes them), one direction:
+    mean over all voxels of |s (u_a(x) + u_b(x + u_a(x)))|^2 in voxels^2, u_b sampled exactly as WarpFn samples (csrc/invcons.hip).
+    Gradients reach both fields; the one of u_b is a scatter (float atomics, or the fixed-point accumulation under DETERMINISTIC)."""
+
+    @staticmethod
+    def forward(ctx, u_a, u_b):
+        a, b, loss, _, resid = _invcons_fwd(u_a, u_b, False, True)
+        ctx.save_for_backward(a, b, resid)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, gloss):
+        a, b, resid = ctx.saved_tensors
+        N, D, H, W, _ = a.shape
+        gl = gloss.detach().reshape(1).to(torch.float32).contiguous()
+        det = bool(DETERMINISTIC)
+        da = torch.empty_like(a) if ctx.needs_input_grad[0] else None
+        db = None
+        if ctx.needs_input_grad[1]:
+            db = torch.empty_like(b) if det else torch.zeros_like(b)
+        with torch.cuda.device(a.device):
+            wp, wn = (_ws(nat.lib().da_warp_bwd_dsrc_det_ws_bytes(N, D, H, W, 3), a) if det and db is not None else (None, 0))
+            call('da_invcons_bwd', ptr(a), ptr(b), ptr(resid), ptr(gl), ptr(da), ptr(db), N, D, H, W, 1 if det else 0, wp, wn, stream())
+        return (ncdhw(da) if da is not None else None), (ncdhw(db) if db is not None else None)
+
+
+def inverse_consistency_forward(u_a, u_b):
+    """Everything da_invcons_fwd writes, without autograd: (loss float32 scalar, stats float64 N x 4 = per sample (sum |s r|^2, sum |s r|,
+    max |s r|, voxels sampled outside the volume), the residual r = u_a + u_b(x + u_a) as N x 3 x D x H x W in normalised units), on the device."""
+    _, _, loss, stats, resid = _invcons_fwd(u_a.detach(), u_b.detach(), True, True)
+    return loss.reshape(()), stats, ncdhw(resid)
+
+
+def inverse_consistency_stats(u_a, u_b):
+    """The composition residual r(x) = u_a(x) + u_b(x + u_a(x)) of two fields in voxels, per sample and without autograd: a dict of float64
+    device tensors [N]: mean_vox (mean |s r|), rms_vox, max_vox, outside_frac (share of voxels whose sample point leaves the volume)."""
+    a, _, _, stats, _ = _invcons_fwd(u_a.detach(), u_b.detach(), True, False)
+    V = float(a.shape[1] * a.shape[2] * a.shape[3])
+    return dict(mean_vox=stats[:, 1] / V, rms_vox=(stats[:, 0] / V).sqrt(), max_vox=stats[:, 2].clone(), outside_frac=stats[:, 3] / V)
+
+
 class XentFn(Function):
     """Cross-entropy family of the loss registry (lib/loss.py:739-761) on N x C x D x H x W logits: mode 0 nn.CrossEntropyLoss,
     1 FocalLoss.forward (lib/loss.py:181-213), 2 SoftCrossEntropy.forward with a probability target (:115-154)."""

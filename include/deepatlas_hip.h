@@ -575,6 +575,26 @@ int da_jacdet_penalty_fwd(const float* disp, int N, int D, int H, int W, float e
                           float* det, void* ws, size_t ws_bytes, void* stream);
 int da_jacdet_penalty_bwd(const float* disp, const float* det, const float* dloss, float* d_disp, int N, int D, int H, int W,
                           float eps, int power, void* stream);
+/* Inverse-consistency penalty of two displacement fields (invcons.hip): the composition residual r(x) = u_a(x) + T[u_b](x + u_a(x)), where T is
+ * da_warp_fwd's trilinear sample (zeros outside, align_corners=True) at da_warp_fwd's own fp32 coordinate, and
+ * loss[1] = 1 / (N V) sum_n sum_x sum_c (s_c r_c(x))^2 in voxels^2, s_c = (size_c - 1) / 2.  disp_a, disp_b [N][D][H][W][3], units and
+ * channel order as above.  A NULL input, N <= 0 or N > 65535, or an extent < 2 returns DA_ERR_BADARG before any launch, a short workspace
+ * DA_ERR_WS_SMALL, a volume of >= 2^29 voxels DA_ERR_UNSUPPORTED.  A voxel whose sample coordinate is NaN, infinite or >= 1e9 samples
+ * nothing, as in the warp; it makes the loss and both sums NaN and the maximum infinite, and bwd writes NaN into its three d_disp_a components
+ * (it adds nothing to d_disp_b), so a bad field never passes as consistent in either direction.
+ * fwd writes, when not NULL, resid [N][D][H][W][3] = r (normalised units; bwd reads it) and stats [N][4] doubles per sample = (sum |s r|^2,
+ * sum |s r|, max |s r|, number of voxels whose sample point leaves [0, size - 1] on some axis or is not finite), |.| the Euclidean norm in
+ * voxels.  The sums are accumulated in double from per-workgroup partials added in index order: two runs are bit-identical.
+ * bwd, with g_c(x) = dloss[0] 2 s_c^2 r_c(x) / (N V): d_disp_a (written; may be NULL) = g_k(x) + s_k sum_c g_c(x) dT[u_b,c] / d(voxel
+ * coordinate k), a gather; d_disp_b (ADDED into: the caller zero-fills it; may be NULL) = the adjoint of the gather, sum_x w(x -> y) g_c(x),
+ * by fp32 atomic adds, one lane per element, in a kernel of its own (arrival order: the last bits vary from run to run).  deterministic != 0: d_disp_b is written (no zero-fill needed)
+ * through da_warp_bwd_dsrc_det's fixed-point accumulation, bit-identical from run to run, and ws must hold
+ * da_warp_bwd_dsrc_det_ws_bytes(N, D, H, W, 3) bytes; otherwise bwd uses no workspace and ws may be NULL. */
+size_t da_invcons_ws_bytes(int N, int D, int H, int W);
+int da_invcons_fwd(const float* disp_a, const float* disp_b, int N, int D, int H, int W, float* loss, double* stats /*[N][4] or NULL*/,
+                   float* resid /*[N][V][3] or NULL*/, void* ws, size_t ws_bytes, void* stream);
+int da_invcons_bwd(const float* disp_a, const float* disp_b, const float* resid, const float* dloss, float* d_disp_a, float* d_disp_b,
+                   int N, int D, int H, int W, int deterministic, void* ws, size_t ws_bytes, void* stream);
 /* Multi-atlas label fusion: K atlas label maps warped to each of N target grids and voted per voxel, in one pass.  disp [N][K][D][H][W][3]
  * (units and channel order as above; field (n, k) maps target n's grid into atlas k), addressed with 64-bit offsets.  labels: uint8 (1) or
  * int64 (8) maps [K][D][H][W] shared by all targets (label_sample_stride 0) or one block per target (label_sample_stride = elements between

@@ -3,7 +3,9 @@
 --sim-loss ncc | lncc | mi, NCC by default), the data are ordered pairs of synthetic volumes (--moving-remap: the moving image in another
 "modality"), validation reports the hard-label registration Dice (against the identity deformation's) and the Jacobian statistics of the
 predicted deformation.  --lambda-jac > 0 adds the Jacobian folding penalty (--jac-eps, --jac-power) to the step: it trains against the
-folding fraction that validation prints."""
+folding fraction that validation prints.  --lambda-ic > 0 adds the inverse-consistency penalty: the step predicts both directions of every pair
+in one doubled-batch forward and penalises the composition of the two fields; validation then (or with --report-ic alone) also prints the
+inverse-consistency error in voxels."""
 import argparse
 import os
 
@@ -46,6 +48,18 @@ def build_config(args):
         config.pop('atlas_fusion', None)
     apply_similarity_arguments(config)
     apply_jacobian_arguments(config)
+    apply_inverse_consistency_arguments(config)
+    return config
+
+
+def apply_inverse_consistency_arguments(config):
+    """--lambda-ic / --report-ic -> config['lambda_ic'] and config['report_ic']; an absent flag leaves no key (no penalty; the report follows the
+    penalty), so a run without them has the config it always had."""
+    lam = float(config.pop('lambda_ic', None) or 0.0)
+    if lam != 0.0:
+        config['lambda_ic'] = lam
+    if config.pop('report_ic', None):
+        config['report_ic'] = True
     return config
 
 
@@ -104,8 +118,17 @@ def add_common_arguments(parser):
     return parser
 
 
+def add_inverse_consistency_arguments(parser):
+    """The flags of the registration experiment alone (the joint step has no inverse-consistency term: train a net here and pass it on as --reg-ckpt)."""
+    parser.add_argument('--lambda-ic', default=0.0, type=float,
+                        help='weight of the inverse-consistency penalty: mean |u_ab(x) + u_ba(x + u_ab(x))|^2 in voxels^2, both directions (0: off)')
+    parser.add_argument('--report-ic', action='store_true',
+                        help='validation also runs the reverse direction and prints the inverse-consistency error in voxels (implied by --lambda-ic > 0)')
+    return parser
+
+
 def main(argv=None):
-    args = add_common_arguments(argparse.ArgumentParser()).parse_args(argv)
+    args = add_inverse_consistency_arguments(add_common_arguments(argparse.ArgumentParser())).parse_args(argv)
     exp = RegistrationExperiment(build_config(args))
     if not args.test_only:
         exp.train()
