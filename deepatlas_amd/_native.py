@@ -135,6 +135,10 @@ SIGNATURES = {
     'da_invcons_ws_bytes': (SZ, [I, I, I, I]),
     'da_invcons_fwd': (I, [P, P, I, I, I, I, P, P, P, P, SZ, P]),
     'da_invcons_bwd': (I, [P, P, P, P, P, P, I, I, I, I, I, P, SZ, P]),
+    'da_affine_warp_fwd': (I, [P, P, P, I, I, I, I, I, P]),
+    'da_affine_warp_ws_bytes': (SZ, [I, I, I, I]),
+    'da_affine_warp_bwd_theta': (I, [P, P, P, P, I, I, I, I, I, P, SZ, P]),
+    'da_affine_compose_disp': (I, [P, P, P, I, I, I, I, P]),
     'da_label_fusion_vote': (I, [P, I, LL, P, P, P, I, I, I, I, I, P, P, P]),
     'da_local_msd_weights_ws_bytes': (SZ, [I, I, I, I, I]),
     'da_local_msd_weights': (I, [P, P, I, I, I, I, I, I, F, P, P, SZ, P]),

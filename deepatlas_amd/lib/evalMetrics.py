@@ -177,6 +177,18 @@ def inverse_consistency(disp_ab, disp_ba):
     return {k: v.cpu().numpy() for k, v in s.items()}
 
 
+def affine_align(moving, fixed, **kw):
+    """Affine pre-alignment of a batch of pairs (lib/affine.py affine_register; `kw` are its arguments: mode, sim, sim_settings, levels,
+    iters, lr, init): returns (theta N x 3 x 4, the moving images resampled with it, N x 1 x D x H x W), both on the device, no autograd.
+    ops.affine_disp(theta, u) turns theta and a field u predicted on the aligned image into the one field that warps the ORIGINAL moving
+    image and its labels."""
+    from . import affine
+    theta = affine.affine_register(moving, fixed, **kw)
+    with torch.no_grad():
+        aligned = ops.AffineWarpFn.apply(moving.detach(), theta)
+    return theta, aligned
+
+
 def atlas_label_fusion(labels, disp, weights=None, n_targets=None):
     """Multi-atlas label fusion (ops.label_fusion): the atlas label maps `labels` (K x D x H x W, or (N K) x D x H x W per target) warped
     with the fields `disp` ((N K) x 3 x D x H x W, atlas index fastest) and voted per voxel -- majority vote, or weighted by `weights`

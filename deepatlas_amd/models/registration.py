@@ -16,11 +16,17 @@ folding fraction validation prints); config['jac_settings'] are its constructor 
 config['lambda_ic'] (default 0: off) weights the inverse-consistency penalty of the step (lib/loss.py InverseConsistencyLoss; the step then predicts
 both directions in one doubled-batch forward); config['report_ic'] (default None: on exactly when lambda_ic > 0) makes validation also run the
 reverse direction and report the composition residual in voxels (ic_mean_vox, ic_max_vox, ic_outside_frac).
+config['affine_init'] (None default: off | 'rigid' | 'affine') runs an affine pre-alignment (lib/affine.py affine_register, settings in
+config['affine_settings']) on every pair: training sees (aligned moving, fixed); validation aligns, runs the net on the aligned pair, composes
+the affine with the predicted field (ops.affine_disp) and scores that ONE field, so labels are interpolated once, and also reports the Dice of
+the affine alone (affine_dice_avg).  config['misalign'] = (rotation in degrees, translation in voxels) (default None) gives every pair's moving
+image and segmentation a rigid misalignment, the same one in every epoch (seeded by the pair's name), in training and validation alike.
 """
 import datetime
 import os
 import time
 import warnings
+import zlib
 
 import numpy as np
 import torch
@@ -31,6 +37,8 @@ from .joint import RegistrationStep, SIM_LOSSES, make_jac_penalty, make_ic_penal
 from .segmentation import SegmentationExperiment
 from ..lib import datasets as med_data
 from ..lib import evalMetrics as metrics
+from ..lib import affine as affine_lib
+from ..lib.transforms import rigid_index_affine
 from ..lib.loss import JacobianFoldingLoss
 from ..lib.network_factory import get_network
 from ..lib.param_dict import save_dict_to_json
@@ -51,7 +59,29 @@ def _nanmean(a, axis=None):
         return np.nanmean(a, axis=axis)
 
 
-def eval_registration(model, dataloader, n_classes, device, report_ic=False):
+def misalign_pairs(im_m, seg_m, names, misalign):
+    """Rigid misalignment of the moving images (N x 1 x D x H x W, on the device) and segmentations (N x D x H x W or None) of a batch:
+    per pair, rotation angles (x, y, z) ~ N(0, rot_deg / 2) degrees and a translation ~ N(0, trans_vox / 2) voxels per axis, as
+    lib/transforms.py draw_rigid draws them, from a generator seeded by zlib.crc32 of the pair's name: a pair is misaligned the same way in
+    every epoch.  About the volume's centre, through rigid_index_affine + ops.spatial_resample: trilinear image with 0.1 outside the
+    volume, nearest labels with 0 outside.  Returns (images, segmentations)."""
+    rot, trans = misalign
+    D, H, W = (int(v) for v in im_m.shape[-3:])
+    centre = ((W - 1) / 2.0, (H - 1) / 2.0, (D - 1) / 2.0)
+    if len(names) != im_m.shape[0]:
+        raise ValueError('misalign needs one name per pair, got %d names for %d pairs' % (len(names), im_m.shape[0]))
+    mats = []
+    for name in names:
+        rs = np.random.RandomState(zlib.crc32(str(name).encode()) & 0xffffffff)
+        angles = rs.normal(0, rot / 2, 3) * np.pi / 180 if rot > 0 else np.zeros(3)
+        shift = rs.normal(0, trans / 2, 3) if trans > 0 else np.zeros(3)
+        mats.append(rigid_index_affine(angles, shift, (1.0, 1.0, 1.0), centre))
+    if seg_m is not None and seg_m.dtype not in (torch.uint8, torch.int32, torch.int64):
+        seg_m = seg_m.long()
+    return ops.spatial_resample(im_m.float(), seg_m, np.stack(mats), interpolator='linear')
+
+
+def eval_registration(model, dataloader, n_classes, device, report_ic=False, affine_init=None, affine_settings=None, misalign=None):
     """Registration metrics of `model` over a loader of (moving image, fixed image, moving seg, fixed seg, has_moving_seg, name) batches.
     Pairs without a moving segmentation have no registration Dice and are skipped for it; every pair counts for the Jacobian statistics.
     Returns a dict: dice_per_class [C-1] (mean over the pairs that have the class: nanmean), dice_avg (mean over the classes that occur),
@@ -59,19 +89,34 @@ def eval_registration(model, dataloader, n_classes, device, report_ic=False):
     folding fraction), det_mean / det_std (means over the pairs of the per-pair mean / standard deviation of det J), n_pairs, n_dice_pairs.
     report_ic: the net is also run in the reverse direction, model(im_t, im_m), and the dict gains ic_mean_vox / ic_max_vox / ic_outside_frac:
     the means over the pairs of the per-pair mean and maximum of the composition residual |u_mt(x) + u_tm(x + u_mt(x))| in voxels and of the
-    share of voxels whose sample point leaves the volume (metrics.inverse_consistency)."""
+    share of voxels whose sample point leaves the volume (metrics.inverse_consistency).
+    misalign: every pair's moving image and segmentation are first misaligned (misalign_pairs).  affine_init ('rigid' | 'affine'): every pair
+    is pre-aligned (metrics.affine_align with affine_settings), the net runs on (aligned moving, fixed) and its field is composed with the
+    affine (ops.affine_disp): Dice and det J are those of that one field on the ORIGINAL moving labels; the dict gains
+    affine_dice_per_class / affine_dice_avg, the Dice under the affine's field alone (the inverse-consistency report is then that of the net on the aligned pair)."""
+    dice_aff = []
     dice, dice_id, jac = [], [], {'nonpos_frac': [], 'mean': [], 'std': []}
     ic = {'mean_vox': [], 'max_vox': [], 'outside_frac': []}
     with torch.no_grad():
         model.eval()
         for im_m, im_t, seg_m, seg_t, has, _name in dataloader:
             im_m, im_t = im_m.to(device), im_t.to(device)
-            disp = model(im_m, im_t)[0]
+            if misalign is not None:
+                im_m, seg_m = misalign_pairs(im_m, seg_m.to(device), _name, misalign)
+            disp_aff = None
+            if affine_init is None:
+                disp = net_disp = model(im_m, im_t)[0]
+            else:
+                theta, im_a = metrics.affine_align(im_m, im_t, mode=affine_init, **dict(affine_settings or {}))
+                net_disp = model(im_a, im_t)[0]
+                disp = ops.affine_disp(theta, net_disp)
+                disp_aff = ops.affine_disp(theta, size=im_m.shape[2:])
+                im_m = im_a
             js = metrics.jacobian_stats(disp)
             for k in jac:
                 jac[k].append(js[k])
             if report_ic:
-                ics = metrics.inverse_consistency(disp, model(im_t, im_m)[0])
+                ics = metrics.inverse_consistency(net_disp, model(im_t, im_m)[0])
                 for k in ic:
                     ic[k].append(ics[k])
             keep = torch.as_tensor(has).reshape(-1).bool()
@@ -79,8 +124,10 @@ def eval_registration(model, dataloader, n_classes, device, report_ic=False):
                 sm, st_, dk = seg_m[keep].to(device), seg_t[keep].to(device), disp[keep.to(device)]
                 dice.append(metrics.registration_dice(sm, st_, dk, n_classes))
                 dice_id.append(metrics.registration_dice(sm, st_, torch.zeros_like(dk), n_classes))
+                if disp_aff is not None:
+                    dice_aff.append(metrics.registration_dice(sm, st_, disp_aff[keep.to(device)], n_classes))
     out = {}
-    for key, rows in (('dice', dice), ('identity_dice', dice_id)):
+    for key, rows in (('dice', dice), ('identity_dice', dice_id)) + ((('affine_dice', dice_aff),) if affine_init is not None else ()):
         per = _nanmean(np.concatenate(rows, 0), axis=0) if rows else np.full(n_classes - 1, np.nan)
         out[key + '_per_class'] = per
         out[key + '_avg'] = float(_nanmean(per)) if np.isfinite(per).any() else float('nan')
@@ -169,6 +216,60 @@ def ic_name_suffix(cfg):
     return '_ic%s' % lam if lam > 0 else ''
 
 
+AFFINE_SETTINGS_KEYS = ('sim', 'sim_settings', 'levels', 'iters', 'lr')
+
+
+def check_affine_init(cfg):
+    """config['affine_init']: None (off, the default, also when absent), 'rigid' or 'affine'; config['affine_settings']: arguments of
+    lib/affine.py affine_register among sim, sim_settings, levels, iters, lr (checked here, also when the stage is off).  The stage does not go
+    with the inverse-consistency penalty (the symmetric step would need both directions pre-aligned): lambda_ic > 0 raises.
+    Returns (mode or None, settings)."""
+    mode = cfg.get('affine_init')
+    if mode is not None and mode not in affine_lib.AFFINE_MODES:
+        raise ValueError("config['affine_init'] must be None or one of %s, got %r" % (', '.join(affine_lib.AFFINE_MODES), mode))
+    settings = dict(cfg.get('affine_settings') or {})
+    unknown = sorted(set(settings) - set(AFFINE_SETTINGS_KEYS))
+    if unknown:
+        raise ValueError("config['affine_settings'] takes %s, got %s" % (', '.join(AFFINE_SETTINGS_KEYS), ', '.join(repr(k) for k in unknown)))
+    if 'levels' in settings or 'iters' in settings:
+        affine_lib.check_schedule(settings.get('levels', affine_lib.DEFAULT_LEVELS), settings.get('iters', affine_lib.DEFAULT_ITERS))
+    if 'sim' in settings and settings['sim'] not in affine_lib.SIM_LOSSES:
+        raise ValueError("config['affine_settings']['sim'] must be one of %s, got %r" % (', '.join(sorted(affine_lib.SIM_LOSSES)), settings['sim']))
+    if 'lr' in settings and not 0.0 < float(settings['lr']) < float('inf'):
+        raise ValueError("config['affine_settings']['lr'] must be a finite learning rate > 0, got %r" % (settings['lr'],))
+    if mode is not None and float(cfg.get('lambda_ic') or 0.0) > 0.0:
+        raise ValueError("config['affine_init'] does not go with config['lambda_ic'] > 0: the symmetric step predicts both directions of a pair, "
+                         "and the pre-alignment aligns only the moving image; train with one of the two")
+    return mode, settings
+
+
+def check_misalign(cfg):
+    """config['misalign']: None (off, the default, also when absent) or (rotation in degrees, translation in voxels), both finite and >= 0."""
+    mis = cfg.get('misalign')
+    if mis is None:
+        return None
+    try:
+        rot, trans = (float(v) for v in mis)
+    except (TypeError, ValueError):
+        raise ValueError("config['misalign'] must be None or (rotation in degrees, translation in voxels), got %r" % (mis,))
+    if not (0.0 <= rot < float('inf') and 0.0 <= trans < float('inf')):
+        raise ValueError("config['misalign'] takes two finite values >= 0, got %r" % (mis,))
+    return rot, trans
+
+
+def affine_name_suffix(cfg):
+    """'_misalign<rot>_<trans>' and '_affine<mode>' for an experiment name when they are on, '' otherwise (names of runs without them stay as
+    they were)."""
+    mis = cfg.get('misalign')
+    text = '_misalign%s_%s' % tuple(mis) if mis is not None else ''
+    return text + ('_affine%s' % cfg['affine_init'] if cfg.get('affine_init') else '')
+
+
+def affine_text(res):
+    """What a validation or test line adds beside the identity Dice when the affine stage is on ('' otherwise)."""
+    return ', affine {:.4f}'.format(res['affine_dice_avg']) if 'affine_dice_avg' in res else ''
+
+
 def ic_text(res):
     """What a validation or test line adds when the inverse-consistency report is on ('' otherwise)."""
     if 'ic_mean_vox' not in res:
@@ -196,6 +297,8 @@ class RegistrationExperiment(BaseExperiment):
         self.sim_loss, self.sim_settings = check_sim_loss(cfg)
         self.lambda_jac, self.jac_settings = check_jac_penalty(cfg)
         self.lambda_ic, self.report_ic = check_ic_penalty(cfg)
+        self.affine_init, self.affine_settings = check_affine_init(cfg)
+        self.misalign = check_misalign(cfg)
         self.exp_name = self.experiment_name(cfg)
         run_dir = "debug_reg" if cfg['debug_mode'] else self.exp_name
         self.ckpoint_dir = os.path.join(cfg['log_dir'], run_dir, str(cfg['random_seed']))
@@ -209,7 +312,7 @@ class RegistrationExperiment(BaseExperiment):
 
     @staticmethod
     def experiment_name(cfg):
-        """Reg_<model>_<data dir name>_<n>samples_batch_<b>_<e>epochs_<sim_loss>_bending_<lambda_reg>_lr_<lr>[_scheduler_<mode>][_moving<remap>][_jac<lambda_jac>][_ic<lambda_ic>]"""
+        """Reg_<model>_<data dir name>_<n>samples_batch_<b>_<e>epochs_<sim_loss>_bending_<lambda_reg>_lr_<lr>[_scheduler_<mode>][_moving<remap>][_jac<lambda_jac>][_ic<lambda_ic>][_misalign<rot>_<trans>][_affine<mode>]"""
         parts = ['Reg_', cfg['model'], '_', os.path.basename(cfg['data_dir']), '_%ssamples' % cfg['num_samples'], '_batch_%s' % cfg['batch_size'],
                  '_%sepochs' % cfg['n_epochs'], '_%s_bending_%s' % (cfg.get('sim_loss') or 'ncc', cfg['lambda_reg']), '_lr_%s' % cfg['learning_rate']]
         if cfg['lr_mode'] != 'const':
@@ -218,6 +321,7 @@ class RegistrationExperiment(BaseExperiment):
             parts.append('_moving%s' % cfg['moving_remap'])
         parts.append(jac_name_suffix(cfg))
         parts.append(ic_name_suffix(cfg))
+        parts.append(affine_name_suffix(cfg))
         return ''.join(str(v) for v in parts)
 
     # ---- setup ---------------------------------------------------------------------------------
@@ -272,9 +376,19 @@ class RegistrationExperiment(BaseExperiment):
             self.writer.close()
         print('Finished Training: {}'.format(self.exp_name))
 
-    def train_step(self, im_m, im_t):
-        """One RegistrationStep on a batch of pairs: (loss, (disp, warped, deform), (similarity, bending))."""
-        return self.step(im_m.to(self.device, non_blocking=True), im_t.to(self.device, non_blocking=True))
+    def train_step(self, im_m, im_t, names=None):
+        """One RegistrationStep on a batch of pairs: (loss, (disp, warped, deform), (similarity, bending)).  With config['misalign'] the moving
+        images are misaligned first (`names`: the pairs' names, which seed it); with config['affine_init'] they are then pre-aligned to the
+        fixed images without autograd, and the step sees (aligned moving, fixed)."""
+        im_m, im_t = im_m.to(self.device, non_blocking=True), im_t.to(self.device, non_blocking=True)
+        if self.misalign is not None:
+            if names is None:
+                raise ValueError("config['misalign'] needs the pairs' names to seed the misalignment")
+            im_m = misalign_pairs(im_m, None, names, self.misalign)[0]
+        if self.affine_init is not None:
+            with torch.no_grad():
+                im_m = metrics.affine_align(im_m, im_t, mode=self.affine_init, **self.affine_settings)[1]
+        return self.step(im_m, im_t)
 
     def train_one_epoch(self):
         running_loss = 0.0
@@ -291,7 +405,7 @@ class RegistrationExperiment(BaseExperiment):
                 train_data_iter = iter(self.training_data_loader)
                 batch = next(train_data_iter)
             self.global_step = (self.current_epoch - 1) * iters_per_epoch + (i + 1) * self.config['batch_size']
-            loss, _, _ = self.train_step(batch[0], batch[1])
+            loss, _, _ = self.train_step(batch[0], batch[1], batch[5])
             running_loss += loss.item()
             if self.step.jac is not None:
                 running_jac = self.step.last_jac if running_jac is None else running_jac + self.step.last_jac
@@ -317,7 +431,8 @@ class RegistrationExperiment(BaseExperiment):
                 running_ic = None
 
     def eval(self, dataloader):
-        res = eval_registration(self.model, dataloader, self.config['n_classes'], self.device, report_ic=self.report_ic)
+        res = eval_registration(self.model, dataloader, self.config['n_classes'], self.device, report_ic=self.report_ic,
+                                affine_init=self.affine_init, affine_settings=self.affine_settings, misalign=self.misalign)
         if self.atlas_fusion:
             # the volumes behind the loader's pairs, each segmented from the training volumes (all labelled here), at most atlas_fusion_max
             if self.training_data_loader is None:
@@ -349,11 +464,11 @@ class RegistrationExperiment(BaseExperiment):
             tag = 'validation_{}/'.format(self.config['data'])
             for k in ('dice_avg', 'identity_dice_avg', 'nonpos_frac', 'det_mean', 'det_std'):
                 self.writer.add_scalar(tag + k, res[k], global_step=self.global_step)
-            for k in ('ic_mean_vox', 'ic_max_vox', 'ic_outside_frac'):
+            for k in ('ic_mean_vox', 'ic_max_vox', 'ic_outside_frac', 'affine_dice_avg'):
                 if k in res:
                     self.writer.add_scalar(tag + k, res[k], global_step=self.global_step)
-        print("Validation: registration Dice Avg: {:.4f} (identity {:.4f}){}  det J {:.4f} +- {:.4f}, folding {:.3%}{} ({:.3f} sec) {}".format(
-            score, res['identity_dice_avg'], atlas_fusion_text(res), res['det_mean'], res['det_std'], res['nonpos_frac'], ic_text(res), time.time() - start_time,
+        print("Validation: registration Dice Avg: {:.4f} (identity {:.4f}{}){}  det J {:.4f} +- {:.4f}, folding {:.3%}{} ({:.3f} sec) {}".format(
+            score, res['identity_dice_avg'], affine_text(res), atlas_fusion_text(res), res['det_mean'], res['det_std'], res['nonpos_frac'], ic_text(res), time.time() - start_time,
             datetime.datetime.now().strftime("%D %H:%M:%S")))
         if self.current_epoch % self.config['save_ckpts_epoch_period'] == 0:
             self.save_checkpoint({'epoch': self.current_epoch,
@@ -371,6 +486,6 @@ class RegistrationExperiment(BaseExperiment):
         last_epoch, best_score = self.initialize_model(self.model, optimizer=None, ckpoint_path=ckpoint_file)
         loader = self.config.get('testing_data_loader') or self.validation_data_loader
         res = self.eval(loader)
-        print('Testing Model: {} ({} epochs)  registration Dice_avg: {} (identity {})  folding fraction: {}{}{}'.format(
-            ckpoint_file, last_epoch, res['dice_avg'], res['identity_dice_avg'], res['nonpos_frac'], atlas_fusion_text(res), ic_text(res)))
+        print('Testing Model: {} ({} epochs)  registration Dice_avg: {} (identity {}{})  folding fraction: {}{}{}'.format(
+            ckpoint_file, last_epoch, res['dice_avg'], res['identity_dice_avg'], affine_text(res), res['nonpos_frac'], atlas_fusion_text(res), ic_text(res)))
         return res

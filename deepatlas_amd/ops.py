@@ -2271,6 +2271,86 @@ def inverse_consistency_stats(u_a, u_b):
     return dict(mean_vox=stats[:, 1] / V, rms_vox=(stats[:, 0] / V).sqrt(), max_vox=stats[:, 2].clone(), outside_frac=stats[:, 3] / V)
 
 
+def _affine_theta(theta, n):
+    """Checks of the affine ops on `theta` that need no device: N x 3 x 4 float32; returns it dense."""
+    if theta.dim() != 3 or tuple(theta.shape) != (n, 3, 4):
+        raise ValueError('theta must be N x 3 x 4 matching the batch of %d, got %s' % (n, tuple(theta.shape)))
+    if theta.dtype != torch.float32:
+        raise ValueError('the affine warp expects a float32 theta, got %s' % theta.dtype)
+    return theta.contiguous()
+
+
+def _affine_extents(size):
+    if len(size) != 3 or min(int(s) for s in size) < 2:
+        raise ValueError('the affine warp needs a volume of >= 2 voxels per axis (align_corners=True), got %s' % (tuple(size),))
+
+
+class AffineWarpFn(Function):
+    """warped = grid_sample(src, affine_grid(theta, src.shape, align_corners=True), bilinear, zeros, align_corners=True) without the grid
+    (csrc/affine.hip).  src N x C x D x H x W float32, theta N x 3 x 4 float32 in affine_grid's normalised (x, y, z) convention, the frame of
+    WarpFn's deform.  The gradient reaches theta only (one fused pass, deterministic); asking for d src raises NotImplementedError."""
+
+    @staticmethod
+    def forward(ctx, src, theta):
+        if src.dim() != 5:
+            raise ValueError('the affine warp expects a N x C x D x H x W source volume, got %s' % (tuple(src.shape),))
+        if src.dtype != torch.float32:
+            raise ValueError('the affine warp expects a float32 source volume, got %s' % src.dtype)
+        _affine_extents(src.shape[2:])
+        th = _affine_theta(theta.detach(), src.shape[0])
+        nat.require_cuda(src, th)
+        s = ndhwc(src.detach())
+        N, D, H, W, C = s.shape
+        out = torch.empty_like(s)
+        with torch.cuda.device(s.device):
+            call('da_affine_warp_fwd', ptr(s), ptr(th), ptr(out), N, D, H, W, C, stream())
+        ctx.save_for_backward(s, th)
+        return ncdhw(out)
+
+    @staticmethod
+    def backward(ctx, g_out):
+        if ctx.needs_input_grad[0]:
+            raise NotImplementedError('AffineWarpFn has no gradient with respect to the source volume (only theta is optimised)')
+        if not ctx.needs_input_grad[1]:
+            return None, None
+        s, th = ctx.saved_tensors
+        N, D, H, W, C = s.shape
+        g = ndhwc(g_out)
+        d_theta = torch.empty_like(th)
+        with torch.cuda.device(s.device):
+            wp, wn = _ws(nat.lib().da_affine_warp_ws_bytes(N, D, H, W), s)
+            call('da_affine_warp_bwd_theta', ptr(g), ptr(s), ptr(th), ptr(d_theta), N, D, H, W, C, wp, wn, stream())
+        return None, d_theta
+
+
+def affine_disp(theta, disp=None, size=None):
+    """The displacement field of an affine map, alone or composed with a field predicted on the pre-aligned image: N x 3 x D x H x W float32
+    in WarpFn's normalised units, out(x) = theta (x_n + disp(x), 1) - x_n (da_affine_compose_disp).  WarpFn(src, affine_disp(theta)) samples
+    where AffineWarpFn(src, theta) does; WarpFn(src, affine_disp(theta, u)) is WarpFn(AffineWarpFn(src, theta), u) with one interpolation.
+    disp None: the affine's own field on a volume of `size` = (D, H, W).  No autograd."""
+    if disp is None:
+        if size is None:
+            raise ValueError('affine_disp needs `size` = (D, H, W) when no displacement field is given')
+        D, H, W = (int(s) for s in size)
+        u = None
+    else:
+        if disp.dim() != 5 or disp.shape[1] != 3 or disp.dtype != torch.float32:
+            raise ValueError('displacement field must be N x 3 x D x H x W float32')
+        if size is not None and tuple(int(s) for s in size) != tuple(disp.shape[2:]):
+            raise ValueError('size %s does not match the displacement field %s' % (tuple(size), tuple(disp.shape)))
+        D, H, W = (int(s) for s in disp.shape[2:])
+    _affine_extents((D, H, W))
+    th = _affine_theta(theta.detach(), theta.shape[0] if disp is None else disp.shape[0])
+    nat.require_cuda(th, disp)
+    if disp is not None:
+        u = ndhwc(disp.detach())
+    N = th.shape[0]
+    out = torch.empty((N, D, H, W, 3), dtype=torch.float32, device=th.device)
+    with torch.cuda.device(th.device):
+        call('da_affine_compose_disp', ptr(th), ptr(u), ptr(out), N, D, H, W, stream())
+    return ncdhw(out)
+
+
 class XentFn(Function):
     """Cross-entropy family of the loss registry (lib/loss.py:739-761) on N x C x D x H x W logits: mode 0 nn.CrossEntropyLoss,
     1 FocalLoss.forward (lib/loss.py:181-213), 2 SoftCrossEntropy.forward with a probability target (:115-154)."""

@@ -595,6 +595,29 @@ int da_invcons_fwd(const float* disp_a, const float* disp_b, int N, int D, int H
                    float* resid /*[N][V][3] or NULL*/, void* ws, size_t ws_bytes, void* stream);
 int da_invcons_bwd(const float* disp_a, const float* disp_b, const float* resid, const float* dloss, float* d_disp_a, float* d_disp_b,
                    int N, int D, int H, int W, int deterministic, void* ws, size_t ws_bytes, void* stream);
+/* Affine pre-alignment (affine.hip).  theta [N][3][4] fp32 on the device, in exactly the convention of
+ *     grid = torch.nn.functional.affine_grid(theta, (N, C, D, H, W), align_corners=True)
+ *     out  = torch.nn.functional.grid_sample(src, grid, mode='bilinear', padding_mode='zeros', align_corners=True)
+ * which these entries restate without the V x 3 grid: normalised coordinates, rows and columns in (x, y, z) = (W, H, D) order, the frame of
+ * da_warp_fwd's deform; resolution-independent, so one theta serves every pyramid level.  src / out / g [N][D][H][W][C], any C >= 1.
+ * The arithmetic runs in centred index space: with s_k = (size_k - 1) / 2 the sample point of output voxel i is
+ * q_k = sum_j theta_kj (s_k / s_j) (i_j - s_j) + theta_k3 s_k + s_k, the twelve coefficients, q, the tap weights and the eight-tap sums in double: an output is rounded once.
+ * The identity theta returns src bit for bit; a translation by a whole number of voxels whose theta entry 2 t / (size - 1) is exact in fp32
+ * returns the shifted volume bit for bit, zeros where it leaves.  A sample coordinate that is NaN, infinite or >= 1e9 in magnitude samples
+ * nothing, as in the warp; nothing is indexed by a data value.  A NULL pointer, N <= 0 or N > 65535, C < 1 or an extent < 2 returns
+ * DA_ERR_BADARG before any launch, a short workspace DA_ERR_WS_SMALL, a volume of >= 2^29 voxels DA_ERR_UNSUPPORTED.
+ * bwd_theta: d_theta [N][3][4] (written) = the gradient of sum_x sum_c g_c(x) out_c(x) with respect to theta,
+ * d theta_kj = sum_x sum_c g_c(x) d out_c / d q_k (x) (i_j - s_j) s_k / s_j and d theta_k3 = sum ... s_k: one pass over g, eight taps of src
+ * per voxel, accumulated in double from per-workgroup partial rows added in index order (no atomics: two runs are bit-identical).  A sample
+ * with a refused coordinate gets a d_theta of NaN, so a broken transform never passes as converged; the other samples are untouched.
+ * compose_disp: out(x) = theta (x_n + disp(x), 1) - x_n in the warp's normalised units, x_n the identity coordinate of voxel x: the single
+ * displacement field of "affine, then the field predicted on the pre-aligned image"; disp NULL gives the affine's own field. */
+int da_affine_warp_fwd(const float* src, const float* theta, float* out, int N, int D, int H, int W, int C, void* stream);
+size_t da_affine_warp_ws_bytes(int N, int D, int H, int W);
+int da_affine_warp_bwd_theta(const float* g, const float* src, const float* theta, float* d_theta /*[N][3][4]*/, int N, int D, int H, int W,
+                             int C, void* ws, size_t ws_bytes, void* stream);
+int da_affine_compose_disp(const float* theta, const float* disp /*[N][D][H][W][3] or NULL*/, float* out /*[N][D][H][W][3]*/,
+                           int N, int D, int H, int W, void* stream);
 /* Multi-atlas label fusion: K atlas label maps warped to each of N target grids and voted per voxel, in one pass.  disp [N][K][D][H][W][3]
  * (units and channel order as above; field (n, k) maps target n's grid into atlas k), addressed with 64-bit offsets.  labels: uint8 (1) or
  * int64 (8) maps [K][D][H][W] shared by all targets (label_sample_stride 0) or one block per target (label_sample_stride = elements between

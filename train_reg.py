@@ -5,7 +5,10 @@
 predicted deformation.  --lambda-jac > 0 adds the Jacobian folding penalty (--jac-eps, --jac-power) to the step: it trains against the
 folding fraction that validation prints.  --lambda-ic > 0 adds the inverse-consistency penalty: the step predicts both directions of every pair
 in one doubled-batch forward and penalises the composition of the two fields; validation then (or with --report-ic alone) also prints the
-inverse-consistency error in voxels."""
+inverse-consistency error in voxels.  --affine-init rigid | affine pre-aligns every pair's moving image to the fixed one (lib/affine.py
+affine_register: a coarse-to-fine Adam on 6 or 12 parameters through the fused affine warp kernels) before the net sees it, in training and in
+validation, where the affine and the predicted field are composed into one field; --misalign ROT_DEG TRANS_VOX gives the synthetic pairs the
+global misalignment that stage is for."""
 import argparse
 import os
 
@@ -49,6 +52,22 @@ def build_config(args):
     apply_similarity_arguments(config)
     apply_jacobian_arguments(config)
     apply_inverse_consistency_arguments(config)
+    apply_affine_arguments(config)
+    return config
+
+
+def apply_affine_arguments(config):
+    """--affine-init / --affine-iters / --misalign -> config['affine_init'], config['affine_settings']['iters'], config['misalign']; an absent
+    flag leaves no key, so a run without them has the config it always had."""
+    mode = config.pop('affine_init', None)
+    iters = config.pop('affine_iters', None)
+    mis = config.pop('misalign', None)
+    if mode:
+        config['affine_init'] = mode
+    if iters is not None:
+        config['affine_settings'] = dict(config.get('affine_settings') or {}, iters=tuple(int(k) for k in iters))
+    if mis is not None:
+        config['misalign'] = tuple(float(v) for v in mis)
     return config
 
 
@@ -127,8 +146,23 @@ def add_inverse_consistency_arguments(parser):
     return parser
 
 
+def add_affine_arguments(parser):
+    """The affine pre-alignment stage and the synthetic misalignment it is for (registration experiment only; not with --lambda-ic)."""
+    parser.add_argument('--affine-init', default=None, choices=['rigid', 'affine'],
+                        help="pre-align every pair's moving image to the fixed image before the net sees it: 6-parameter rigid or 12-parameter "
+                             "affine, coarse to fine (pooling 4, 2, 1) by Adam on the image similarity; validation composes the affine with the "
+                             "predicted field and also prints the Dice of the affine alone")
+    parser.add_argument('--affine-iters', default=None, type=int, nargs=3, metavar=('I4', 'I2', 'I1'),
+                        help='Adam iterations of --affine-init on the three pyramid levels (default 60 40 20)')
+    parser.add_argument('--misalign', default=None, type=float, nargs=2, metavar=('ROT_DEG', 'TRANS_VOX'),
+                        help="give every pair's moving image and segmentation a rigid misalignment, in training and validation alike: per axis a "
+                             "rotation ~ N(0, ROT_DEG / 2) degrees and a translation ~ N(0, TRANS_VOX / 2) voxels, seeded by the pair's name (the "
+                             "same in every epoch).  The resample fills the image with 0.1 outside the volume (labels: 0)")
+    return parser
+
+
 def main(argv=None):
-    args = add_inverse_consistency_arguments(add_common_arguments(argparse.ArgumentParser())).parse_args(argv)
+    args = add_affine_arguments(add_inverse_consistency_arguments(add_common_arguments(argparse.ArgumentParser()))).parse_args(argv)
     exp = RegistrationExperiment(build_config(args))
     if not args.test_only:
         exp.train()
