@@ -135,6 +135,10 @@ SIGNATURES = {
     'da_invcons_ws_bytes': (SZ, [I, I, I, I]),
     'da_invcons_fwd': (I, [P, P, I, I, I, I, P, P, P, P, SZ, P]),
     'da_invcons_bwd': (I, [P, P, P, P, P, P, I, I, I, I, I, P, SZ, P]),
+    'da_field_invert_ws_bytes': (SZ, [I, I, I, I]),
+    'da_field_invert': (I, [P, P, P, I, I, I, I, I, F, P, P, SZ, P]),
+    'da_field_points_ws_bytes': (SZ, [I, I]),
+    'da_field_transport_points': (I, [P, P, P, I, I, I, I, I, I, I, F, P, P, SZ, P]),
     'da_affine_warp_fwd': (I, [P, P, P, I, I, I, I, I, P]),
     'da_affine_warp_ws_bytes': (SZ, [I, I, I, I]),
     'da_affine_warp_bwd_theta': (I, [P, P, P, P, I, I, I, I, I, P, SZ, P]),

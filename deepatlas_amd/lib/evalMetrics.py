@@ -177,6 +177,109 @@ def inverse_consistency(disp_ab, disp_ba):
     return {k: v.cpu().numpy() for k, v in s.items()}
 
 
+def invert_deformation(disp, **kw):
+    """The inverse field of `disp` (ops.invert_field; `kw` are its max_iters and tol_vox) and how well the iteration did: returns
+    (inverse N x 3 x D x H x W on the device, dict of per-sample float64 arrays): `max_update_vox` (the largest final update, infinite for a
+    non-finite field), `unconverged_frac` (share of voxels whose final update exceeds tol_vox), `mean_iters` (updates per voxel) and
+    `outside_frac` (share of voxels whose inverse point lies outside the volume, where the field was extrapolated by its border value)."""
+    inv, stats = ops.invert_field(disp, return_stats=True, **kw)
+    s = stats.cpu().numpy()
+    n_vox = float(np.prod(disp.shape[2:]))
+    return inv, {'max_update_vox': s[:, 0].copy(), 'unconverged_frac': s[:, 1] / n_vox, 'mean_iters': s[:, 2] / n_vox, 'outside_frac': s[:, 3] / n_vox}
+
+
+def _landmark_norms(diff, spacing):
+    """Per-sample (mean, std, max) of |spacing * diff| over the rows of `diff` (N x P x 3 float64 numpy) that are finite; NaN without one."""
+    e = np.sqrt(((diff * np.asarray(spacing, dtype=np.float64).reshape(1, 1, 3)) ** 2).sum(-1))
+    out = np.full((3, e.shape[0]), np.nan)
+    for n in range(e.shape[0]):
+        row = e[n][np.isfinite(e[n])]
+        if row.size:
+            out[:, n] = row.mean(), row.std(), row.max()
+    return out
+
+
+def target_registration_error(disp, fixed_points, moving_points, spacing=(1, 1, 1)):
+    """Landmark error of a predicted field: the fixed-frame landmarks f (N x P x 3, voxel index coordinates (x, y, z)) are carried into the
+    moving frame, f + s u(f) (ops.transport_points), and compared with their moving-frame partners m: per-sample float64 arrays `tre_mean`,
+    `tre_std`, `tre_max` of |spacing * (f + s u(f) - m)| over the P pairs, and `initial_mean`, `initial_max`, the same for disp = 0.
+    `spacing` is the voxel size per (x, y, z) axis; pairs with a NaN in either point are skipped."""
+    f = torch.as_tensor(fixed_points, dtype=torch.float32, device=disp.device)
+    m = torch.as_tensor(moving_points, dtype=torch.float32)
+    if f.dim() != 3 or tuple(f.shape) != tuple(m.shape):
+        raise ValueError('fixed_points and moving_points must both be N x P x 3, got %s and %s' % (tuple(f.shape), tuple(m.shape)))
+    if len(spacing) != 3:
+        raise ValueError('spacing takes one voxel size per axis (x, y, z), got %r' % (spacing,))
+    skip = (~torch.isfinite(f).all(-1)).cpu().numpy() | (~torch.isfinite(m).all(-1)).cpu().numpy()
+    moved = ops.transport_points(disp, torch.nan_to_num(f)).cpu().double().numpy()
+    f64, m64 = f.cpu().double().numpy(), m.cpu().double().numpy()
+    moved[skip] = np.nan
+    f64[skip] = np.nan
+    tre = _landmark_norms(moved - m64, spacing)
+    init = _landmark_norms(f64 - m64, spacing)
+    return {'tre_mean': tre[0], 'tre_std': tre[1], 'tre_max': tre[2], 'initial_mean': init[0], 'initial_max': init[2]}
+
+
+def known_deformation_field(names, size, amp_vox, lip, device):
+    """One smooth random field per name, N x 3 x D x H x W float32 in normalised units on `device`: a 4 x 4 x 4 lattice of normal values per
+    component from a generator seeded by zlib.crc32(name), trilinearly up-sampled (align_corners=True) to `size`, scaled to a largest
+    displacement of amp_vox voxels and then, if needed, down until its Lipschitz bound -- the largest difference of the displacement between
+    axis-adjacent voxels, in voxels, times sqrt(3) -- is at most `lip`."""
+    import zlib
+    D, H, W = (int(s) for s in size)
+    fields = []
+    for name in names:
+        g = torch.Generator().manual_seed(zlib.crc32(str(name).encode()) & 0xffffffff)
+        lattice = torch.randn((1, 3, 4, 4, 4), generator=g, dtype=torch.float64)
+        u = torch.nn.functional.interpolate(lattice, size=(D, H, W), mode='trilinear', align_corners=True)
+        u = u * (float(amp_vox) / float(u.pow(2).sum(1).sqrt().max()))
+        step = max(float((u[:, :, 1:] - u[:, :, :-1]).pow(2).sum(1).sqrt().max()), float((u[:, :, :, 1:] - u[:, :, :, :-1]).pow(2).sum(1).sqrt().max()),
+                   float((u[..., 1:] - u[..., :-1]).pow(2).sum(1).sqrt().max()))
+        bound = step * 3.0 ** 0.5
+        if bound > lip:
+            u = u * (lip / bound)
+        fields.append(u)
+    scale = torch.tensor([2.0 / (W - 1), 2.0 / (H - 1), 2.0 / (D - 1)], dtype=torch.float64).view(1, 3, 1, 1, 1)
+    return (torch.cat(fields, 0) * scale).float().to(device)
+
+
+def known_deformation_tre(model, image, names, amp_vox=3.0, n_points=1000, lip=0.5):
+    """Landmark error of a registration net against a deformation whose inverse is known.  Every image of the batch (N x 1 x D x H x W) is
+    deformed by a smooth random field g (known_deformation_field, seeded by the sample's name): moving = WarpFn(image, g), that is
+    moving(x) = image(x + g(x)).  The net registers moving to image and wants moving(x + u(x)) ~ image(x), so u(x) + g(x + u(x)) = 0: the true
+    answer u* is the inverse of g, ops.invert_field(g, tol_vox=1e-4, max_iters=64).  n_points landmarks f per sample, uniform and at least
+    amp_vox + 1 voxels from every face (seeded by the name as well), are carried through both fields (ops.transport_points).
+    Returns a dict of per-sample float64 arrays: `tre_mean_vox`, `tre_max_vox` of |s (u(f) - u*(f))|, `tre_initial_mean_vox` = the mean of
+    |s u*(f)| (what no registration leaves) and `truth_unconverged_frac`, the share of voxels at which u* did not converge."""
+    import zlib
+    N = int(image.shape[0])
+    D, H, W = (int(s) for s in image.shape[2:])
+    if len(names) != N:
+        raise ValueError('known_deformation_tre needs one name per image, got %d names for %d images' % (len(names), N))
+    margin = float(amp_vox) + 1.0
+    if min(D, H, W) - 1 <= 2 * margin:
+        raise ValueError('a volume of %s has no point %g voxels from every face' % ((D, H, W), margin))
+    with torch.no_grad():
+        g = known_deformation_field(names, (D, H, W), amp_vox, lip, image.device)
+        moving = ops.WarpFn.apply(image.float(), g)[0]
+        truth, stats = ops.invert_field(g, tol_vox=1e-4, max_iters=64, return_stats=True)
+        u = model(moving, image)[0].detach().float()
+        pts = []
+        for name in names:
+            gen = torch.Generator().manual_seed((zlib.crc32(str(name).encode()) + 1) & 0xffffffff)
+            r = torch.rand((int(n_points), 3), generator=gen, dtype=torch.float64)
+            lo = torch.tensor([margin] * 3, dtype=torch.float64)
+            hi = torch.tensor([W - 1 - margin, H - 1 - margin, D - 1 - margin], dtype=torch.float64)
+            pts.append(lo + r * (hi - lo))
+        f = torch.stack(pts).float().to(image.device)
+        at_truth = ops.transport_points(truth, f).cpu().double().numpy()
+        at_pred = ops.transport_points(u, f).cpu().double().numpy()
+    tre = _landmark_norms(at_truth - at_pred, (1, 1, 1))
+    init = _landmark_norms(at_truth - f.cpu().double().numpy(), (1, 1, 1))
+    return {'tre_mean_vox': tre[0], 'tre_max_vox': tre[2], 'tre_initial_mean_vox': init[0],
+            'truth_unconverged_frac': stats[:, 1].cpu().numpy() / float(D * H * W)}
+
+
 def affine_align(moving, fixed, **kw):
     """Affine pre-alignment of a batch of pairs (lib/affine.py affine_register; `kw` are its arguments: mode, sim, sim_settings, levels,
     iters, lr, init): returns (theta N x 3 x 4, the moving images resampled with it, N x 1 x D x H x W), both on the device, no autograd.

@@ -21,6 +21,9 @@ config['affine_settings']) on every pair: training sees (aligned moving, fixed);
 the affine with the predicted field (ops.affine_disp) and scores that ONE field, so labels are interpolated once, and also reports the Dice of
 the affine alone (affine_dice_avg).  config['misalign'] = (rotation in degrees, translation in voxels) (default None) gives every pair's moving
 image and segmentation a rigid misalignment, the same one in every epoch (seeded by the pair's name), in training and validation alike.
+config['report_tre'] (None default: off | a dict with 'amp_vox' and optionally 'points') makes validation also run the known-deformation
+probe (lib/evalMetrics.py known_deformation_tre) on the fixed image of every pair, one more net forward: the landmark error in voxels against
+the exact inverse of a known smooth field (tre_mean_vox, tre_max_vox, tre_initial_mean_vox).  It takes no part in the experiment's name.
 """
 import datetime
 import os
@@ -81,7 +84,7 @@ def misalign_pairs(im_m, seg_m, names, misalign):
     return ops.spatial_resample(im_m.float(), seg_m, np.stack(mats), interpolator='linear')
 
 
-def eval_registration(model, dataloader, n_classes, device, report_ic=False, affine_init=None, affine_settings=None, misalign=None):
+def eval_registration(model, dataloader, n_classes, device, report_ic=False, affine_init=None, affine_settings=None, misalign=None, tre_probe=None):
     """Registration metrics of `model` over a loader of (moving image, fixed image, moving seg, fixed seg, has_moving_seg, name) batches.
     Pairs without a moving segmentation have no registration Dice and are skipped for it; every pair counts for the Jacobian statistics.
     Returns a dict: dice_per_class [C-1] (mean over the pairs that have the class: nanmean), dice_avg (mean over the classes that occur),
@@ -93,8 +96,12 @@ def eval_registration(model, dataloader, n_classes, device, report_ic=False, aff
     misalign: every pair's moving image and segmentation are first misaligned (misalign_pairs).  affine_init ('rigid' | 'affine'): every pair
     is pre-aligned (metrics.affine_align with affine_settings), the net runs on (aligned moving, fixed) and its field is composed with the
     affine (ops.affine_disp): Dice and det J are those of that one field on the ORIGINAL moving labels; the dict gains
-    affine_dice_per_class / affine_dice_avg, the Dice under the affine's field alone (the inverse-consistency report is then that of the net on the aligned pair)."""
+    affine_dice_per_class / affine_dice_avg, the Dice under the affine's field alone (the inverse-consistency report is then that of the net on the aligned pair).
+    tre_probe (a dict amp_vox, points): the known-deformation probe (metrics.known_deformation_tre) runs on the fixed image of every batch, one
+    more net forward, and the dict gains tre_mean_vox / tre_initial_mean_vox (means over the pairs of the per-pair mean landmark error against
+    the exact inverse of the known field, and of what no registration would leave) and tre_max_vox (the largest landmark error of any pair)."""
     dice_aff = []
+    tre = {'tre_mean_vox': [], 'tre_max_vox': [], 'tre_initial_mean_vox': []}
     dice, dice_id, jac = [], [], {'nonpos_frac': [], 'mean': [], 'std': []}
     ic = {'mean_vox': [], 'max_vox': [], 'outside_frac': []}
     with torch.no_grad():
@@ -119,6 +126,10 @@ def eval_registration(model, dataloader, n_classes, device, report_ic=False, aff
                 ics = metrics.inverse_consistency(net_disp, model(im_t, im_m)[0])
                 for k in ic:
                     ic[k].append(ics[k])
+            if tre_probe is not None:
+                probe = metrics.known_deformation_tre(model, im_t, _name, amp_vox=tre_probe['amp_vox'], n_points=tre_probe['points'])
+                for k in tre:
+                    tre[k].append(probe[k])
             keep = torch.as_tensor(has).reshape(-1).bool()
             if bool(keep.any()):
                 sm, st_, dk = seg_m[keep].to(device), seg_t[keep].to(device), disp[keep.to(device)]
@@ -136,6 +147,10 @@ def eval_registration(model, dataloader, n_classes, device, report_ic=False, aff
     if report_ic:
         for k in ic:
             out['ic_' + k] = float(np.mean(np.concatenate(ic[k]))) if ic[k] else float('nan')
+    if tre_probe is not None:
+        for k in tre:
+            rows = np.concatenate(tre[k]) if tre[k] else np.full(1, np.nan)
+            out[k] = float(np.max(rows) if k == 'tre_max_vox' else np.mean(rows))
     out['n_pairs'] = int(sum(len(a) for a in jac['mean']))
     out['n_dice_pairs'] = int(sum(len(a) for a in dice))
     return out
@@ -257,6 +272,35 @@ def check_misalign(cfg):
     return rot, trans
 
 
+TRE_PROBE_POINTS = 1000
+
+
+def check_report_tre(cfg):
+    """config['report_tre']: None (off, the default, also when absent) or a dict with 'amp_vox' (the largest displacement of the known field in
+    voxels, finite and > 0) and optionally 'points' (landmarks per pair, default 1000).  The probe deforms the fixed image itself, so it does
+    not go with config['affine_init'] (the net would see a pair that was never pre-aligned): that raises.  Returns None or the complete dict."""
+    probe = cfg.get('report_tre')
+    if probe is None:
+        return None
+    if not isinstance(probe, dict) or 'amp_vox' not in probe or set(probe) - {'amp_vox', 'points'}:
+        raise ValueError("config['report_tre'] must be None or a dict with 'amp_vox' and optionally 'points', got %r" % (probe,))
+    amp, points = float(probe['amp_vox']), probe.get('points', TRE_PROBE_POINTS)
+    if not 0.0 < amp < float('inf'):
+        raise ValueError("config['report_tre']['amp_vox'] must be a finite number of voxels > 0, got %r" % (probe['amp_vox'],))
+    if int(points) != points or int(points) < 1:
+        raise ValueError("config['report_tre']['points'] must be a whole number >= 1, got %r" % (points,))
+    if cfg.get('affine_init'):
+        raise ValueError("config['report_tre'] does not go with config['affine_init']: the probe's pairs are not pre-aligned")
+    return {'amp_vox': amp, 'points': int(points)}
+
+
+def tre_text(res):
+    """What a validation or test line adds when the known-deformation probe is on ('' otherwise)."""
+    if 'tre_mean_vox' not in res:
+        return ''
+    return ', TRE {:.2f} (initial {:.2f}) vox'.format(res['tre_mean_vox'], res['tre_initial_mean_vox'])
+
+
 def affine_name_suffix(cfg):
     """'_misalign<rot>_<trans>' and '_affine<mode>' for an experiment name when they are on, '' otherwise (names of runs without them stay as
     they were)."""
@@ -299,6 +343,7 @@ class RegistrationExperiment(BaseExperiment):
         self.lambda_ic, self.report_ic = check_ic_penalty(cfg)
         self.affine_init, self.affine_settings = check_affine_init(cfg)
         self.misalign = check_misalign(cfg)
+        self.report_tre = check_report_tre(cfg)
         self.exp_name = self.experiment_name(cfg)
         run_dir = "debug_reg" if cfg['debug_mode'] else self.exp_name
         self.ckpoint_dir = os.path.join(cfg['log_dir'], run_dir, str(cfg['random_seed']))
@@ -432,7 +477,7 @@ class RegistrationExperiment(BaseExperiment):
 
     def eval(self, dataloader):
         res = eval_registration(self.model, dataloader, self.config['n_classes'], self.device, report_ic=self.report_ic,
-                                affine_init=self.affine_init, affine_settings=self.affine_settings, misalign=self.misalign)
+                                affine_init=self.affine_init, affine_settings=self.affine_settings, misalign=self.misalign, tre_probe=self.report_tre)
         if self.atlas_fusion:
             # the volumes behind the loader's pairs, each segmented from the training volumes (all labelled here), at most atlas_fusion_max
             if self.training_data_loader is None:
@@ -464,11 +509,11 @@ class RegistrationExperiment(BaseExperiment):
             tag = 'validation_{}/'.format(self.config['data'])
             for k in ('dice_avg', 'identity_dice_avg', 'nonpos_frac', 'det_mean', 'det_std'):
                 self.writer.add_scalar(tag + k, res[k], global_step=self.global_step)
-            for k in ('ic_mean_vox', 'ic_max_vox', 'ic_outside_frac', 'affine_dice_avg'):
+            for k in ('ic_mean_vox', 'ic_max_vox', 'ic_outside_frac', 'affine_dice_avg', 'tre_mean_vox', 'tre_max_vox', 'tre_initial_mean_vox'):
                 if k in res:
                     self.writer.add_scalar(tag + k, res[k], global_step=self.global_step)
-        print("Validation: registration Dice Avg: {:.4f} (identity {:.4f}{}){}  det J {:.4f} +- {:.4f}, folding {:.3%}{} ({:.3f} sec) {}".format(
-            score, res['identity_dice_avg'], affine_text(res), atlas_fusion_text(res), res['det_mean'], res['det_std'], res['nonpos_frac'], ic_text(res), time.time() - start_time,
+        print("Validation: registration Dice Avg: {:.4f} (identity {:.4f}{}){}  det J {:.4f} +- {:.4f}, folding {:.3%}{}{} ({:.3f} sec) {}".format(
+            score, res['identity_dice_avg'], affine_text(res), atlas_fusion_text(res), res['det_mean'], res['det_std'], res['nonpos_frac'], ic_text(res), tre_text(res), time.time() - start_time,
             datetime.datetime.now().strftime("%D %H:%M:%S")))
         if self.current_epoch % self.config['save_ckpts_epoch_period'] == 0:
             self.save_checkpoint({'epoch': self.current_epoch,
@@ -486,6 +531,6 @@ class RegistrationExperiment(BaseExperiment):
         last_epoch, best_score = self.initialize_model(self.model, optimizer=None, ckpoint_path=ckpoint_file)
         loader = self.config.get('testing_data_loader') or self.validation_data_loader
         res = self.eval(loader)
-        print('Testing Model: {} ({} epochs)  registration Dice_avg: {} (identity {}{})  folding fraction: {}{}{}'.format(
-            ckpoint_file, last_epoch, res['dice_avg'], res['identity_dice_avg'], affine_text(res), res['nonpos_frac'], atlas_fusion_text(res), ic_text(res)))
+        print('Testing Model: {} ({} epochs)  registration Dice_avg: {} (identity {}{})  folding fraction: {}{}{}{}'.format(
+            ckpoint_file, last_epoch, res['dice_avg'], res['identity_dice_avg'], affine_text(res), res['nonpos_frac'], atlas_fusion_text(res), ic_text(res), tre_text(res)))
         return res

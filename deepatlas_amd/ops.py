@@ -2271,6 +2271,74 @@ def inverse_consistency_stats(u_a, u_b):
     return dict(mean_vox=stats[:, 1] / V, rms_vox=(stats[:, 0] / V).sqrt(), max_vox=stats[:, 2].clone(), outside_frac=stats[:, 3] / V)
 
 
+FIELDINV_STATS = 4         # doubles per sample of da_field_invert / da_field_transport_points: largest final update (voxels), elements not
+#                            converged, updates performed, elements whose last sample point leaves the volume
+
+
+def _fieldinv_args(disp, max_iters, tol_vox, what):
+    """Checks of the field-inversion ops that need no device: N x 3 x D x H x W float32, extents >= 2, 1 <= max_iters <= 255, tol_vox >= 0."""
+    if not torch.is_tensor(disp) or disp.dim() != 5 or disp.shape[1] != 3:
+        raise ValueError('%s expects a N x 3 x D x H x W displacement field, got %s' % (what, tuple(disp.shape) if torch.is_tensor(disp) else type(disp)))
+    if disp.dtype != torch.float32:
+        raise ValueError('%s expects a float32 displacement field, got %s' % (what, disp.dtype))
+    if disp.shape[0] < 1 or min(int(s) for s in disp.shape[2:]) < 2:
+        raise ValueError('%s needs at least one sample and >= 2 voxels per axis (align_corners=True), got %s' % (what, tuple(disp.shape)))
+    if int(max_iters) != max_iters or not 1 <= int(max_iters) <= 255:
+        raise ValueError('%s takes 1 <= max_iters <= 255 (the iteration count is stored in a byte), got %r' % (what, max_iters))
+    if not float(tol_vox) >= 0.0:
+        raise ValueError('%s takes a tol_vox >= 0 voxels, got %r' % (what, tol_vox))
+    return int(max_iters), float(tol_vox)
+
+
+def invert_field(disp, max_iters=32, tol_vox=1e-3, return_stats=False, return_iters=False):
+    """The inverse of the deformation x -> x + u(x): v with (id + u)(id + v) = id, N x 3 x D x H x W float32 in WarpFn's normalised units, by
+    the fixed-point iteration v_0 = 0, v_{k+1}(x) = -u(x + v_k(x)) with u sampled trilinearly under border padding (csrc/fieldinv.hip: every
+    update of a voxel in registers, one launch).  A voxel stops after the first update of at most tol_vox voxels or after max_iters updates;
+    the iteration contracts where u changes by less than one voxel per voxel.  A net's field maps the fixed frame into the moving frame;
+    its inverse carries fixed-frame data into the moving frame: warp_labels_nearest(seg_t, invert_field(u)).  No autograd.
+    return_stats: also a float64 N x FIELDINV_STATS device tensor per sample (largest final update in voxels, voxels not converged, updates
+    performed, voxels whose last sample point left the volume, where the inverse is an extrapolation).  return_iters: also the updates
+    performed per voxel, uint8 N x D x H x W.  Returns the field, or a tuple (field[, stats][, iters])."""
+    max_iters, tol_vox = _fieldinv_args(disp, max_iters, tol_vox, 'invert_field')
+    nat.require_cuda(disp)
+    u = ndhwc(disp.detach())
+    N, D, H, W, _ = u.shape
+    out = torch.empty_like(u)
+    stats = torch.empty((N, FIELDINV_STATS), dtype=torch.float64, device=u.device) if return_stats else None
+    iters = torch.empty((N, D, H, W), dtype=torch.uint8, device=u.device) if return_iters else None
+    with torch.cuda.device(u.device):
+        wp, wn = _ws(nat.lib().da_field_invert_ws_bytes(N, D, H, W), u) if return_stats else (None, 0)
+        call('da_field_invert', ptr(u), ptr(out), ptr(iters), N, D, H, W, max_iters, tol_vox, ptr(stats), wp, wn, stream())
+    res = (ncdhw(out),) + ((stats,) if return_stats else ()) + ((iters,) if return_iters else ())
+    return res[0] if len(res) == 1 else res
+
+
+def transport_points(disp, points, inverse=False, max_iters=32, tol_vox=1e-3, return_stats=False):
+    """Points carried through the deformation x -> x + u(x) of `disp` (N x 3 x D x H x W float32, normalised units).  points: N x P x 3 float32
+    in voxel index coordinates (x, y, z) = (W, H, D) axis.  inverse False: fixed frame -> moving frame, q = p + s u(p), u sampled trilinearly
+    under border padding, s = (size - 1) / 2.  inverse True: moving frame -> fixed frame, the solution x of x + s u(x) = q by the iteration of
+    invert_field (same stopping rule, same device function: at the grid nodes it is invert_field's result).  A point outside the volume
+    samples the nearest face; a non-finite point gives a NaN row.  No autograd.  Returns N x P x 3, with return_stats also the float64
+    N x FIELDINV_STATS statistics of invert_field over each sample's points."""
+    max_iters, tol_vox = _fieldinv_args(disp, max_iters, tol_vox, 'transport_points')
+    if not torch.is_tensor(points) or points.dim() != 3 or points.shape[2] != 3 or points.shape[0] != disp.shape[0] or points.shape[1] < 1:
+        raise ValueError('transport_points expects N x P x 3 points (P >= 1) matching the batch of %d, got %s'
+                         % (disp.shape[0], tuple(points.shape) if torch.is_tensor(points) else type(points)))
+    if points.dtype != torch.float32:
+        raise ValueError('transport_points expects float32 points, got %s' % points.dtype)
+    nat.require_cuda(disp, points)
+    u = ndhwc(disp.detach())
+    p = points.detach().contiguous()
+    N, D, H, W, _ = u.shape
+    P = int(p.shape[1])
+    out = torch.empty_like(p)
+    stats = torch.empty((N, FIELDINV_STATS), dtype=torch.float64, device=u.device) if return_stats else None
+    with torch.cuda.device(u.device):
+        wp, wn = _ws(nat.lib().da_field_points_ws_bytes(N, P), u) if return_stats else (None, 0)
+        call('da_field_transport_points', ptr(u), ptr(p), ptr(out), N, D, H, W, P, 1 if inverse else 0, max_iters, tol_vox, ptr(stats), wp, wn, stream())
+    return (out, stats) if return_stats else out
+
+
 def _affine_theta(theta, n):
     """Checks of the affine ops on `theta` that need no device: N x 3 x 4 float32; returns it dense."""
     if theta.dim() != 3 or tuple(theta.shape) != (n, 3, 4):

@@ -618,6 +618,34 @@ int da_affine_warp_bwd_theta(const float* g, const float* src, const float* thet
                              int C, void* ws, size_t ws_bytes, void* stream);
 int da_affine_compose_disp(const float* theta, const float* disp /*[N][D][H][W][3] or NULL*/, float* out /*[N][D][H][W][3]*/,
                            int N, int D, int H, int W, void* stream);
+/* Inverse of a displacement field and transport of points through it (fieldinv.hip).  disp [N][D][H][W][3], units and channel order as above,
+ * is the pull-back map x -> x + u(x).  B[u](p) = F.grid_sample(u, p, 'bilinear', padding_mode='border', align_corners=True): the unnormalised
+ * coordinate is clamped to [0, size - 1] before the taps are formed, a tap of index `size` has weight 0 and is not read.  With g the
+ * normalised coordinate of an element (da_identity_grid's value at a grid node; index / (size - 1) * 2 - 1 for a point), v_0 = 0 and
+ * v_{k+1} = -B[u](g + v_k); the update d_k = |s (v_{k+1} - v_k)| is the Euclidean norm in voxels, s_c = (size_c - 1) / 2.  An element stops
+ * after the first update with d_k <= tol_vox or after max_iters updates, all of them inside one launch (tol_vox = 0 runs max_iters updates
+ * except where an update is exactly 0).
+ * da_field_invert: out [N][D][H][W][3] = v at every voxel, the field with (id + u)(id + v) = id wherever the map stays inside the volume;
+ * iters (may be NULL) [N][D][H][W] uint8 = updates performed.
+ * da_field_transport_points: points / out [N][P][3] fp32 in voxel index coordinates (x, y, z).  inverse == 0: out = p + s B[u](p), the
+ * fixed-frame point p carried into the moving frame (one sample; max_iters and tol_vox are checked but not used).  inverse != 0: out = q + s v,
+ * the solution x of x + s B[u](x) = q.  At the grid nodes this is da_field_invert's v bit for bit: both run one device function, and the
+ * output's product and sum are rounded separately.
+ * An element whose coordinate g + v_k is NaN, infinite or >= 1e9 in magnitude at any update reads no memory, yields NaN in all three
+ * components and counts as not converged; so does one whose last update is not finite.  No other element is affected.
+ * stats (may be NULL; then ws may be NULL too) [N][4] doubles per sample = (largest final update in voxels, infinite if any element is
+ * non-finite; number of elements not converged: final update > tol_vox, or non-finite; number of updates performed; number of elements whose
+ * last sample point leaves [0, size - 1] on some axis, where the result is an extrapolation, or is non-finite).  For inverse == 0 the first is
+ * the largest displacement and only non-finite points count as not converged.  Reduced per thread, wave, workgroup and then over the
+ * per-workgroup rows in index order: no atomics, two runs are bit-identical.
+ * A NULL disp / points / out, N <= 0 or N > 65535, an extent < 2, P < 1, max_iters < 1 or > 255, a tol_vox that is negative or NaN return
+ * DA_ERR_BADARG before any launch, a short workspace DA_ERR_WS_SMALL, a volume of >= 2^29 voxels DA_ERR_UNSUPPORTED. */
+size_t da_field_invert_ws_bytes(int N, int D, int H, int W);
+int da_field_invert(const float* disp, float* out, unsigned char* iters /*[N][V] or NULL*/, int N, int D, int H, int W, int max_iters,
+                    float tol_vox, double* stats /*[N][4] or NULL*/, void* ws, size_t ws_bytes, void* stream);
+size_t da_field_points_ws_bytes(int N, int P);
+int da_field_transport_points(const float* disp, const float* points, float* out, int N, int D, int H, int W, int P, int inverse,
+                              int max_iters, float tol_vox, double* stats /*[N][4] or NULL*/, void* ws, size_t ws_bytes, void* stream);
 /* Multi-atlas label fusion: K atlas label maps warped to each of N target grids and voted per voxel, in one pass.  disp [N][K][D][H][W][3]
  * (units and channel order as above; field (n, k) maps target n's grid into atlas k), addressed with 64-bit offsets.  labels: uint8 (1) or
  * int64 (8) maps [K][D][H][W] shared by all targets (label_sample_stride 0) or one block per target (label_sample_stride = elements between

@@ -53,6 +53,16 @@ def build_config(args):
     apply_jacobian_arguments(config)
     apply_inverse_consistency_arguments(config)
     apply_affine_arguments(config)
+    apply_tre_arguments(config)
+    return config
+
+
+def apply_tre_arguments(config):
+    """--report-tre AMP_VOX -> config['report_tre'] = {'amp_vox': AMP_VOX}; an absent flag leaves no key, so a run without it has the config it
+    always had."""
+    amp = config.pop('report_tre', None)
+    if amp is not None:
+        config['report_tre'] = {'amp_vox': float(amp)}
     return config
 
 
@@ -161,8 +171,16 @@ def add_affine_arguments(parser):
     return parser
 
 
+def add_tre_arguments(parser):
+    """The known-deformation probe of the registration experiment's validation (not with --affine-init)."""
+    parser.add_argument('--report-tre', default=None, type=float, metavar='AMP_VOX',
+                        help="validation also deforms every fixed image by a known smooth field of at most AMP_VOX voxels, registers it back and "
+                             "prints the landmark error in voxels against the exact inverse of that field (one more net forward per pair)")
+    return parser
+
+
 def main(argv=None):
-    args = add_affine_arguments(add_inverse_consistency_arguments(add_common_arguments(argparse.ArgumentParser()))).parse_args(argv)
+    args = add_tre_arguments(add_affine_arguments(add_inverse_consistency_arguments(add_common_arguments(argparse.ArgumentParser())))).parse_args(argv)
     exp = RegistrationExperiment(build_config(args))
     if not args.test_only:
         exp.train()
