@@ -146,6 +146,10 @@ SIGNATURES = {
     'da_label_fusion_vote': (I, [P, I, LL, P, P, P, I, I, I, I, I, P, P, P]),
     'da_local_msd_weights_ws_bytes': (SZ, [I, I, I, I, I]),
     'da_local_msd_weights': (I, [P, P, I, I, I, I, I, I, F, P, P, SZ, P]),
+    'da_cc_ws_bytes': (SZ, [I, I, I, I]),
+    'da_cc_label': (I, [P, I, I, I, I, I, I, I, P, P, P, SZ, P]),
+    'da_cc_select': (I, [P, I, P, I, LL, I, P, P, P]),
+    'da_cc_filter': (I, [P, I, P, P, P, I, LL, I, I, I, P, P]),
     'da_conv_k2s2_fwd': (I, [P, P, P, P, I, I, I, I, I, I, P, SZ, P]),
     'da_conv_k2s2_dgrad': (I, [P, P, P, I, I, I, I, I, I, P, SZ, P]),
     'da_conv_k2s2_wgrad_ws_bytes': (SZ, [I, I, I, I, I, I]),

@@ -341,3 +341,59 @@ def atlas_segmentation(reg_model, atlas_images, atlas_labels, target_image, mode
             w = warped[0] if len(warped) == 1 else torch.cat(warped, 0)
             weights = ops.local_msd_weights(w.reshape(1, K, D, H, W), target[:, 0], radius=radius, sigma=sigma)
         return ops.label_fusion(atlas_labels, disp, weights, return_confidence=True, n_targets=1)
+
+
+def largest_component_filter(pred, n_class, connectivity=6):
+    """The usual clean-up of a predicted label map before it is scored or used: of every class 1..n_class-1 only the largest connected
+    component of each sample stays, every island becomes background (ops.keep_largest_component, on the device).  pred: N x D x H x W
+    uint8 / int32 / int64; returns a map of the same dtype."""
+    return ops.keep_largest_component(pred, n_class, connectivity=connectivity)
+
+
+def component_stats(labels, n_class, connectivity=6):
+    """How fragmented a label map is, per sample and class: a dict of numpy arrays [N][n_class] -- `n_components` (int64), `voxels` (int64,
+    the class's voxel count) and `largest_frac` (float64, the share of the class's voxels that lie in its largest component; NaN for a class
+    without voxels).  Row 0 (background) is 0 / NaN."""
+    _, stats = ops.keep_largest_component(labels, n_class, connectivity=connectivity, return_stats=True)
+    s = stats.cpu().numpy()
+    with np.errstate(invalid='ignore', divide='ignore'):
+        frac = s[:, :, 1].astype(np.float64) / s[:, :, 2].astype(np.float64)
+    return {'n_components': s[:, :, 0].copy(), 'largest_frac': frac, 'voxels': s[:, :, 2].copy()}
+
+
+POSTPROCESS_MODES = ('largest_cc', 'min_size')
+
+
+def parse_postprocess(spec):
+    """config['postprocess'] -> None or the dict {'mode', 'connectivity', 'min_size'}.  Accepted: None, 'largest_cc', or a dict with 'mode' in
+    POSTPROCESS_MODES and optionally 'connectivity' (6 / 18 / 26, default 6) and 'min_size' (>= 1; required for mode 'min_size')."""
+    if spec is None:
+        return None
+    if isinstance(spec, str):
+        spec = {'mode': spec}
+    if not isinstance(spec, dict):
+        raise ValueError("postprocess must be None, 'largest_cc' or a dict, got %r" % (spec,))
+    unknown = set(spec) - {'mode', 'connectivity', 'min_size'}
+    if unknown:
+        raise ValueError('postprocess: unknown keys %s' % sorted(unknown))
+    mode = spec.get('mode')
+    if mode not in POSTPROCESS_MODES:
+        raise ValueError('postprocess mode must be one of %s, got %r' % (', '.join(POSTPROCESS_MODES), mode))
+    connectivity = spec.get('connectivity', 6)
+    if connectivity not in ops.CC_CONNECTIVITIES:
+        raise ValueError('postprocess connectivity must be 6, 18 or 26, got %r' % (connectivity,))
+    min_size = spec.get('min_size')
+    if mode == 'min_size':
+        if min_size is None or int(min_size) < 1:
+            raise ValueError("postprocess mode 'min_size' needs min_size >= 1, got %r" % (min_size,))
+        min_size = int(min_size)
+    elif min_size is not None:
+        raise ValueError("postprocess: min_size belongs to mode 'min_size'")
+    return {'mode': mode, 'connectivity': int(connectivity), 'min_size': min_size}
+
+
+def postprocess_labels(pred, n_class, post, return_stats=False):
+    """Applies a parsed postprocess setting (parse_postprocess) to a label map N x D x H x W on the device."""
+    if post['mode'] == 'largest_cc':
+        return ops.keep_largest_component(pred, n_class, connectivity=post['connectivity'], return_stats=return_stats)
+    return ops.remove_small_components(pred, n_class, post['min_size'], connectivity=post['connectivity'], return_stats=return_stats)

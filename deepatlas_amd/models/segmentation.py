@@ -202,21 +202,55 @@ class SegmentationExperiment(BaseExperiment):
                 running_loss = 0.0
 
     def eval(self, dataloader):
-        """models/segmentation.py:179-201; Dice from exact integer counts computed on the device."""
+        """models/segmentation.py:179-201; Dice from exact integer counts computed on the device.
+        With config['postprocess'] set (lib/evalMetrics.py parse_postprocess: 'largest_cc', or a dict with mode / connectivity / min_size) the
+        argmax label map is additionally cleaned on the device (ops.keep_largest_component / remove_small_components) and scored again; those
+        numbers go to self.eval_extra (post_dice_per_class, post_dice_avg, components_per_class, removed_frac).  The return value, and with it
+        model selection, the scheduler and best_score, stay on the raw Dice."""
+        post = metrics.parse_postprocess(self.config.get('postprocess'))
+        n_class = self.config["n_classes"]
+        self.eval_extra = {}
         with torch.no_grad():
             self.model.eval()
-            dice_per_class = torch.zeros(self.config["n_classes"] - 1, dtype=torch.float64)
+            dice_per_class = torch.zeros(n_class - 1, dtype=torch.float64)
+            post_dice = torch.zeros(n_class - 1, dtype=torch.float64)
+            components = np.zeros(n_class - 1, dtype=np.float64)
+            kept = total = 0
             n_vol = 0
             pred = images = truths = None
             for j, (images, truths, name) in enumerate(dataloader):
                 pred = self.model(images.to(self.device))
-                d = metrics.metricEval('dice', pred, truths.to(self.device))       # [N][C-1]
+                if post is None:
+                    d = metrics.metricEval('dice', pred, truths.to(self.device))   # [N][C-1]
+                else:
+                    truth = truths.to(self.device)
+                    counts, lab = metrics.eval_dice_counts(pred, truth)            # the counts metricEval('dice', ...) is computed from
+                    d = metrics.dice_from_counts(counts)[:, 1:]
+                    clean, stats = metrics.postprocess_labels(lab, n_class, post, return_stats=True)
+                    pc = ops.label_overlap_counts(clean, truth, n_class)
+                    post_dice += torch.from_numpy(metrics.dice_from_counts(pc)[:, 1:].sum(0))
+                    components += stats[:, 1:, 0].sum(0).cpu().numpy()
+                    kept += int(pc[:, 1:, 0].sum())
+                    total += int(counts[:, 1:, 0].sum())
                 dice_per_class += torch.from_numpy(d.sum(0))
                 n_vol += d.shape[0]                                                # average over VOLUMES (loaders may batch > 1)
             dice_per_class = (dice_per_class / max(n_vol, 1)).float()
             dice_avg = dice_per_class.mean()
+            if post is not None:
+                post_dice = (post_dice / max(n_vol, 1)).float()
+                self.eval_extra = {'post_dice_per_class': post_dice, 'post_dice_avg': post_dice.mean(),
+                                   'components_per_class': components / max(n_vol, 1),      # per class, averaged over the volumes
+                                   'removed_frac': (total - kept) / float(total) if total else 0.0}
             sample_for_vis = {'img': images, 'truth': truths, 'pred': pred}
         return dice_per_class, dice_avg, sample_for_vis
+
+    def _post_suffix(self):
+        """', post-processed Dice Avg: x.xxxx (n.n components / class)' after an eval with config['postprocess'], else ''."""
+        extra = getattr(self, 'eval_extra', None)
+        if not extra:
+            return ''
+        return ', post-processed Dice Avg: {:.4f} ({:.1f} components / class)'.format(float(extra['post_dice_avg']),
+                                                                                     float(np.mean(extra['components_per_class'])))
 
     def validate(self):
         if self.current_epoch % self.config['valid_epoch_period'] == 0:
@@ -235,8 +269,8 @@ class SegmentationExperiment(BaseExperiment):
                 return
             if self.writer is not None:
                 self.writer.add_scalar('validation_{}/dice_avg'.format(self.config['data']), dice_avg, global_step=self.global_step)
-            print("Validation: Dice Avg: {:.4f} ({:.3f} sec) {}".format(float(dice_avg), time.time() - start_time,
-                                                                         datetime.datetime.now().strftime("%D %H:%M:%S")))
+            print("Validation: Dice Avg: {:.4f} ({:.3f} sec) {}{}".format(float(dice_avg), time.time() - start_time,
+                                                                           datetime.datetime.now().strftime("%D %H:%M:%S"), self._post_suffix()))
             if self.current_epoch % self.config['save_ckpts_epoch_period'] == 0:
                 self.save_checkpoint({'epoch': self.current_epoch,
                                       'model_state_dict': self.model.state_dict(),
@@ -251,5 +285,5 @@ class SegmentationExperiment(BaseExperiment):
         last_epoch, best_score = self.initialize_model(self.model, optimizer=None, ckpoint_path=ckpoint_file)
         loader = self.config.get('testing_data_loader') or self.validation_data_loader
         dice_per_class, dice_avg, samples = self.eval(loader)
-        print('Testing Model: {} ({} epochs)  Dice_avg: {}'.format(ckpoint_file, last_epoch, float(dice_avg)))
+        print('Testing Model: {} ({} epochs)  Dice_avg: {}{}'.format(ckpoint_file, last_epoch, float(dice_avg), self._post_suffix()))
         return dice_per_class, dice_avg

@@ -2789,3 +2789,98 @@ def local_msd_weights(warped, target, radius=2, sigma=0.1):
         wp, wn = _ws(nat.lib().da_local_msd_weights_ws_bytes(N, K, D, H, W), a)
         call('da_local_msd_weights', ptr(a), ptr(t), N, K, D, H, W, radius, beta, ptr(out), wp, wn, stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# connected components of a label map, largest-component / minimum-size clean-up (csrc/cc.hip).  No autograd.
+# ------------------------------------------------------------------------------------------------
+CC_CONNECTIVITIES = (6, 18, 26)
+CC_TILE = (4, 8, 32)            # (td, th, tw) = DA_CC_TILE_D / _H / _W (include/deepatlas_hip.h): the tile one workgroup labels in LDS
+CC_MAX_CLASSES = 1024           # DA_CC_MAX_CLASSES
+CC_STATS = ('n_components', 'largest', 'voxels')      # columns of the [N][n_class][3] statistics
+
+
+def _cc_args(labels, connectivity, n_class=None, min_size=None):
+    """Argument checks of the component ops, all before anything touches the device; returns (N, D, H, W)."""
+    if not torch.is_tensor(labels) or labels.dtype not in _LABEL_BYTES:
+        raise ValueError('labels must be a uint8, int32 or int64 tensor, got %s' % (getattr(labels, 'dtype', type(labels)),))
+    if labels.dim() != 4:
+        raise ValueError('labels must be N x D x H x W, got %d dimensions' % labels.dim())
+    if connectivity not in CC_CONNECTIVITIES:
+        raise ValueError('connectivity must be 6, 18 or 26, got %r' % (connectivity,))
+    N, D, H, W = (int(s) for s in labels.shape)
+    if N < 1 or D < 1 or H < 1 or W < 1:
+        raise ValueError('labels must not be empty, got %s' % (tuple(labels.shape),))
+    if D * H * W >= 2 ** 31:
+        raise ValueError('a volume of %d x %d x %d has >= 2^31 voxels: raster indices are int32' % (D, H, W))
+    if N > 65535:
+        raise ValueError('at most 65535 samples per call, got %d' % N)
+    if n_class is not None and not 1 <= int(n_class) <= CC_MAX_CLASSES:
+        raise ValueError('n_class must be 1..%d, got %r' % (CC_MAX_CLASSES, n_class))
+    if min_size is not None and int(min_size) < 1:
+        raise ValueError('min_size must be at least 1, got %r' % (min_size,))
+    return N, D, H, W
+
+
+def _cc_label(lab, n_class, connectivity):
+    """da_cc_label on a contiguous device label map: (roots, sizes), both int32 N x D x H x W."""
+    N, D, H, W = (int(s) for s in lab.shape)
+    roots = torch.empty((N, D, H, W), dtype=torch.int32, device=lab.device)
+    sizes = torch.empty((N, D, H, W), dtype=torch.int32, device=lab.device)
+    wp, wn = _ws(nat.lib().da_cc_ws_bytes(N, D, H, W), lab)
+    call('da_cc_label', ptr(lab), _LABEL_BYTES[lab.dtype], N, D, H, W, int(n_class), int(connectivity), ptr(roots), ptr(sizes), wp, wn, stream())
+    return roots, sizes
+
+
+def connected_components(labels, connectivity=6, return_sizes=False, compact=False):
+    """Connected components of a label map N x D x H x W (uint8 / int32 / int64; labels <= 0 are background).  Two voxels are connected when
+    they hold the same label and are neighbours under `connectivity`: 6 (faces), 18 (faces and edges) or 26 (faces, edges and corners =
+    scipy.ndimage.generate_binary_structure(3, 3)).  Samples never interact.
+    Returns the root map, int32 N x D x H x W: 0 on background, elsewhere 1 + the smallest raster index (d H + h) W + w of the voxel's
+    component -- a function of the input alone, bit-identical from run to run.  compact=True renumbers the components of each sample 1..K in
+    the order of their roots, which is the numbering of scipy.ndimage.label when the map holds one label.  return_sizes: (map, sizes), sizes
+    int32 N x D x H x W = the component's voxel count at its root's position, 0 elsewhere."""
+    N, D, H, W = _cc_args(labels, connectivity)
+    nat.require_cuda(labels)
+    lab = labels.contiguous()
+    with torch.cuda.device(lab.device):
+        roots, sizes = _cc_label(lab, 0, connectivity)
+        if compact:
+            rank = torch.cumsum((sizes.reshape(N, -1) > 0).to(torch.int32), dim=1, dtype=torch.int32)
+            flat = roots.reshape(N, -1)
+            numbered = rank.gather(1, (flat - 1).clamp_(min=0).long())
+            roots = torch.where(flat > 0, numbered, torch.zeros_like(numbered)).reshape(N, D, H, W)
+    return (roots, sizes) if return_sizes else roots
+
+
+def _cc_clean(labels, n_class, connectivity, mode, min_size, return_stats):
+    N, D, H, W = _cc_args(labels, connectivity, n_class=n_class, min_size=min_size if mode == 1 else None)
+    nat.require_cuda(labels)
+    lab = labels.contiguous()
+    n_class, V = int(n_class), D * H * W
+    out = torch.empty_like(lab)
+    stats = best = None
+    with torch.cuda.device(lab.device):
+        roots, sizes = _cc_label(lab, n_class, connectivity)
+        if mode == 0 or return_stats:
+            best = torch.zeros((N, n_class), dtype=torch.int64, device=lab.device)
+            stats = torch.zeros((N, n_class, 3), dtype=torch.int64, device=lab.device)
+            call('da_cc_select', ptr(lab), _LABEL_BYTES[lab.dtype], ptr(sizes), N, V, n_class, ptr(best), ptr(stats), stream())
+        call('da_cc_filter', ptr(lab), _LABEL_BYTES[lab.dtype], ptr(roots), ptr(sizes), ptr(best), N, V, n_class, mode,
+             int(min_size) if mode == 1 else 1, ptr(out), stream())
+    return (out, stats) if return_stats else out
+
+
+def keep_largest_component(labels, n_class, connectivity=6, return_stats=False):
+    """The label map with only the largest connected component of every class 1..n_class-1 in every sample; every other voxel, and every
+    label outside [0, n_class), becomes 0.  The largest component is the one with the most voxels, ties go to the component whose first
+    voxel in raster order comes first.  Same dtype as the input, which is not modified.
+    return_stats: (map, stats), stats int64 N x n_class x 3 with the columns CC_STATS = (number of components, size of the largest, voxels
+    of the class) of the INPUT; row 0 (background) is 0."""
+    return _cc_clean(labels, n_class, connectivity, 0, None, return_stats)
+
+
+def remove_small_components(labels, n_class, min_size, connectivity=6, return_stats=False):
+    """The label map without the connected components of fewer than `min_size` voxels (and without labels outside [0, n_class)): their
+    voxels become 0.  min_size = 1 changes nothing but the out-of-range labels.  return_stats as keep_largest_component."""
+    return _cc_clean(labels, n_class, connectivity, 1, min_size, return_stats)

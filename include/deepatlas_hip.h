@@ -666,6 +666,38 @@ size_t da_local_msd_weights_ws_bytes(int N, int K, int D, int H, int W);
 int da_local_msd_weights(const float* warped, const float* target, int N, int K, int D, int H, int W, int radius, float beta,
                          float* weights, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- connected components of a label map and the largest-component / minimum-size clean-up (cc.hip).  No reference call site: the
+ *      reference scores the raw argmax; these replace what its users run before scoring or using a prediction, scipy.ndimage.label on a
+ *      host copy, once per class and volume. ---------- */
+/* labels: uint8 (1), int32 (4) or int64 (8) maps [N][D][H][W].  Labels <= 0 are background, and so are labels >= n_class where n_class > 0
+ * (da_cc_label: n_class 0 = every positive label is a class).  Two voxels are connected when they hold the same class and are neighbours
+ * under `connectivity`: 6 (faces), 18 (faces, edges) or 26 (faces, edges, corners); samples, rows and planes never wrap into each other.
+ * da_cc_label: roots [N][D][H][W] int32 = 0 on background, elsewhere 1 + the smallest raster index (d H + h) W + w of the voxel's component;
+ * sizes [N][D][H][W] int32 = the component's voxel count at its root's position, 0 elsewhere.  Both are functions of the input alone: two runs
+ * are bit-identical.  Union-find over the grid: tiles of DA_CC_TILE_D x _H x _W labelled in LDS, the tile seams joined with lock-free
+ * min-linking on agent-scope atomics (no workgroup waits for another), roots and sizes written by a launch of its own.
+ * ws: one int32 per voxel (da_cc_ws_bytes).
+ * da_cc_select (after da_cc_label with the same labels and n_class): best [N][n_class] uint64, zero-filled by the caller =
+ * max over the components of the class of (size << 32) | (0xFFFFFFFF - root index): the largest component, ties to the smallest root;
+ * 0 for a class without voxels.  stats [N][n_class][3] int64, zero-filled by the caller = (number of components, size of the largest,
+ * voxels of the class); row 0 (background) stays 0.
+ * da_cc_filter: out [N][D][H][W] in the labels' dtype = the label where the voxel is kept, else 0.  mode 0 keeps the voxels of their class's
+ * largest component (needs best), mode 1 those of components with at least min_size >= 1 voxels (needs sizes).
+ * A NULL pointer, N <= 0 or N > 65535, an extent < 1, label_bytes not 1 / 4 / 8, another connectivity or mode, n_class < 0 (label) or < 1
+ * (select, filter), min_size < 1 return DA_ERR_BADARG before any launch, a short workspace DA_ERR_WS_SMALL, a volume of >= 2^31 voxels or
+ * n_class > DA_CC_MAX_CLASSES DA_ERR_UNSUPPORTED. */
+#define DA_CC_TILE_D 4
+#define DA_CC_TILE_H 8
+#define DA_CC_TILE_W 32
+#define DA_CC_MAX_CLASSES 1024
+size_t da_cc_ws_bytes(int N, int D, int H, int W);
+int da_cc_label(const void* labels, int label_bytes, int N, int D, int H, int W, int n_class, int connectivity,
+                int* roots, int* sizes, void* ws, size_t ws_bytes, void* stream);
+int da_cc_select(const void* labels, int label_bytes, const int* sizes, int N, long long V, int n_class,
+                 unsigned long long* best /*[N][n_class]*/, unsigned long long* stats /*[N][n_class][3]*/, void* stream);
+int da_cc_filter(const void* labels, int label_bytes, const int* roots, const int* sizes, const unsigned long long* best,
+                 int N, long long V, int n_class, int mode, int min_size, void* out, void* stream);
+
 /* ---- optimiser (models/segmentation.py:91 torch.optim.Adam defaults) -------------------------- */
 int da_adam_step(float* p, const float* g, float* m, float* v, long long n,
                  float lr, float beta1, float beta2, float eps, int step, float grad_scale, void* stream);

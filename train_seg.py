@@ -51,6 +51,15 @@ def build_config(args):
         augment.append(['bspline', {'deform_scale': aug_bspline}])
     if augment:
         config['augment'] = augment
+    # opt-in clean-up of the validation / test prediction (lib/evalMetrics.py parse_postprocess); absent = the reference's raw argmax alone
+    mode = config.pop('postprocess', None)
+    connectivity = config.pop('cc_connectivity', None)
+    min_size = config.pop('cc_min_size', None)
+    if mode:
+        post = {'mode': {'largest-cc': 'largest_cc', 'min-size': 'min_size'}[mode], 'connectivity': connectivity or 6}
+        if post['mode'] == 'min_size':
+            post['min_size'] = min_size if min_size is not None else 64
+        config['postprocess'] = post
     if not config.get('matrix_precision'):                # (--matrix-precision; not a key of the reference's config: absent = the package default, 'fp32_split')
         config.pop('matrix_precision', None)
     return config
@@ -78,6 +87,11 @@ def main(argv=None):
                         help='augment training batches with RandomRigidTransform: rotation_angles (degrees) and translation (voxels), (x, y, z)')
     parser.add_argument('--aug-bspline', type=float, default=None, metavar='DEFORM_SCALE',
                         help='augment training batches with RandomBSplineTransform(deform_scale=DEFORM_SCALE), after the rigid one')
+    parser.add_argument('--postprocess', default=None, choices=['largest-cc', 'min-size'],
+                        help="additionally score the validation / test prediction after a connected-component clean-up on the device: "
+                             "'largest-cc' keeps the largest component of every class, 'min-size' drops components below --cc-min-size voxels")
+    parser.add_argument('--cc-connectivity', type=int, default=None, choices=[6, 18, 26], help='connectivity of --postprocess (default 6)')
+    parser.add_argument('--cc-min-size', type=int, default=None, metavar='VOXELS', help="smallest component --postprocess min-size keeps (default 64)")
     args = parser.parse_args(argv)
     exp = SegmentationExperiment(build_config(args))
     if not args.test_only:
