@@ -439,8 +439,10 @@ extern "C" int da_conv3d_k3_dgrad(const float* dy, const float* w_tio, float* dx
         DA_LAUNCH_CHECK();
         return da_conv3_direct_fwd(dy, Cout, nullptr, 0, wf, nullptr, dx1, C1, dx2, C2, N, D, H, W, Cin, 1, -1.f, st);
     }
-    if (!g_force_direct && da_conv3_s2_supported(C1, C2, Cout))
-        return da_conv3_s2_dgrad(dy, w_tio, dx1, C1, N, D, H, W, Cout, ws, ws_bytes - da_bn_ws_bytes(0, Cout) - 4096, st);
+    if (!g_force_direct && da_conv3_s2_supported(C1, C2, Cout)) {
+        const int rc = da_conv3_s2_dgrad(dy, w_tio, dx1, C1, N, D, H, W, Cout, ws, ws_bytes - da_bn_ws_bytes(0, Cout) - 4096, st);
+        if (rc != DA_ERR_UNSUPPORTED) return rc;           // Cout % 16 != 0 outside the native kernels: the direct kernel below
+    }
     const int Do = (D - 1) / 2 + 1, Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     const long long nvox = (long long)N * D * H * W;
     hipLaunchKernelGGL((conv3_s2_dgrad_kernel<16>), dim3((unsigned)da_cdiv(nvox, 256), (unsigned)da_cdiv(Cin, 16)), dim3(256), 0, st,

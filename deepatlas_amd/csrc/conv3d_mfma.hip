@@ -1926,6 +1926,7 @@ static int conv3_mfma_fwd_impl(const float* in1, int C1, const float* in2, int C
     const int NT = (Cout + 15) / 16;
     int NREP = pick_nrep(NT);
     if ((bf || split || pro) && NREP > 2) NREP = 2;        // bf16 mode is not matrix-bound, three N-tiles would spill; the prologue variant parks the whole next tile in registers
+    if (s2d_cin > 0 && NREP > 2) NREP = 2;                 // the sparse-tap kernels exist for one and two N-tiles per workgroup (stride 2, Cout = 48: two groups, the fourth tile empty)
     const bool want_bst = g_bst.y != nullptr && split && stats_partial != nullptr;
     if (want_bst) NREP = 1;                                // the BatchNorm-backward epilogue holds TY quads of the producer's output: one N-tile per workgroup
     {   // Coarse levels have few tiles (30 per volume at 20x24x20, 180 at 40x48x40): the persistent grid then runs one or two

@@ -83,6 +83,8 @@ int da_conv3_s2_dgrad(const float* dy, const float* w_tio, float* dx, int Cin, i
                       void* ws, size_t ws_bytes, hipStream_t st, int act_bf16) {
     if (act_bf16 && da_matrix_mode() != 1) return DA_ERR_UNSUPPORTED;
     if (s2_native(Cin, Cout, N, D, H, W)) return da_conv3_s2n_dgrad(dy, w_tio, dx, Cin, N, D, H, W, Cout, ws, ws_bytes, st);
+    // the tap-masked kernels stage their input, here dY, in 16-channel chunks: Cout = 8, 24, ... goes back to the caller (da_conv3d_k3_dgrad: the direct kernel)
+    if (Cout % 16 != 0) return DA_ERR_UNSUPPORTED;
     const S2Plan p = s2_plan(N, D, H, W, Cin, Cout);
     if (ws_bytes < da_conv3_s2_ws_bytes(N, D, H, W, Cin, Cout)) return DA_ERR_WS_SMALL;
     float* We = (float*)ws; char* inner = (char*)ws + 2 * p.we_bytes;

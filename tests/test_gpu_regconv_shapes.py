@@ -1,0 +1,247 @@
+"""Randomised float64 parity for the registration network's own convolution kernels, through ops.Conv3dK3Fn only (`stride`, the `up2` extra, the `fork` extra):
+conv3d_s2n.hip (encoder, stride 2), conv3d_up2.hip (decoder, nearest x2 folded into the conv), conv3d_flowmm.hip (flow conv forward / data gradient),
+conv3d_flow.hip (flow-conv and first-layer weight gradients) and the thin / small-Cin / masked space-to-depth / direct kernels their neighbours take.
+
+Reference: plain torch in float64 on the widened fp32 inputs -- F.conv3d(cat(x1, x2), w, b, stride, padding=1), F.interpolate(scale_factor=2, mode='nearest') in
+front for `up2`, then the activation, gradients by autograd with a drawn output gradient (fork: one per alias, the reference adds the two); forward, dx1, dx2, dw and
+db are compared.  Cases, builders, the reference, the guard-band rule (block_cases.activate / check_band / G), the restated launcher predicates, CEIL and TOL live in
+tests/regconv_cases.py; every family runs `regconv_cases.run_cases`: the pinned examples, then 60 derandomised hypothesis examples, every example in matrix mode
+'fp32_split' and 'fp32', both against ONE float64 reference.  tests/test_regconv_reference.py runs the same examples on the CPU and shows the fp32 oracle within a
+quarter of each tolerance and the guard band under its cap.  Drawn slopes: -1.0 (no activation), 0.0, 0.01.  bf16 activation storage is not covered here
+(tests/test_gpu_bf16_storage.py).
+
+Routes (regconv_cases.reached restates da_conv3d_k3_fwd / _dgrad / _wgrad, da_conv3_s2_*, da_conv3_mfma_wgrad, da_upconv3d_k3_*; every pinned example carries the
+route and the counts below in `want` and regconv_cases.check_pinned asserts them on every run, here and in the CPU file):
+  family   class                                                     forward    data gradient          weight gradient
+  stride2  split mode, Cin 16 / 32, Cout 32 / 64                     s2n        s2n                    s2n (conv3d_s2n.hip)
+  stride2  fp32 mode Cin 16 / 32, Cout >= 8, % 4; split Cout 8 16 24 48   s2d   s2d (Cout % 16 == 0) | direct   s2d (masked space-to-depth, fp32 matrix kernels)
+  stride2  Cin 8, 24, 48 or Cout 3, 5                                direct     direct                 direct
+  up2      the 16 (C1, C2) classes x Cout 8, 16, 24, 32, split mode  up2        up2 (1 | 2 | 4 N-tiles) up2 (conv3d_up2.hip); fp32 mode: declined, the materialised route
+  flow     (8,16) (16,16) (16,0) (8,8) (8,0), Cout <= 3, split mode  flowmm     flowmm                 flow_split <6, C2 > 0, 8 | 16>, tile 2 x 8 x 16
+  flow     the same in fp32 mode; (16,8); Cout <= 3                  thin       thin                   flow_fp32, tile 4 x 8 x 16 (split mode (16,8): flow_split)
+  flow     Cout = 4; (24,0), (32,0)                                  thin       thin                   swapped small-Cin
+  flow     (32,32)                                                   thin       direct                 generic
+  flow     (12,0)                                                    direct     thin                   direct
+  first    (1,0) Cout 8, 16                                          thin       thin                   valu (fewcin_wgrad_valu_kernel)
+  first    Cin <= 2, Cout 4, 8, 12, 16 otherwise                     thin | direct (Cout 4)  thin | direct      exchanged: flow_launch<2 | 4, false, 8>; split tile for C2 = 0 in split mode
+  first    the rest ((3,0), (4,0), (2,2); Cout 24, 32)               thin       thin | direct          smallcin
+
+Pinned examples (input shape N x D x H x W, coarse for up2) -> what `want` asserts:
+  stride2 (output tile 2 x 4 x 16; tiles / slabs of s2n_wgrad_slabs / most tiles one slab walks):
+      1x1x1x1 16->32 and 1x2x2x2 32->64 (one output voxel) 1/1/1; 3x7x31 32->32 and 4x8x32 16->64 (exactly one tile) 1/1/1; 5x9x33 16->32 fork 8/8/1;
+      W = 1: 9x13x1 32->32 6/6/1; D = 1: 1x37x70 16->32 15/15/1;
+      slab walks: 11x23x127 32->64 fork 36/32/2; 3x7x4127 16->32 129/128/2; 3x7x8223 16->32 257/128/3; 3x7x2079 32->32 65/64/2;
+      N = 2: 2x3x7x1055 16->64 and 2x4x7x1053 32->32 66/64/2 (65 is odd, no N = 2 gives it);
+      on 3x7x4127 16->32 (slab 0 walks tiles 0 and 128): zero_first, zero_last, jump_dn, jump_up (the first tile's x and dY x 2^-30 / 2^+30; jump_up takes the
+      `Emin + 40` clamp, jump_dn the accumulator rescale `da_acc_factor(Enext - Eacc)` by 2^-60);
+      masked 16->8, 16->16, 32->24, 32->48 and direct 8->16, 24->32, 48->8, 16->3, 32->5 at 5x9x33 / 2x4x7x10.
+  up2 (coarse tile 2 x 4 x 16; tiles / slabs of up_wgrad_slabs / walk; data-gradient N-tiles):
+      the 16 classes at 3x5x17 (8 tiles), 2x2x3x9 (2), 1x6x20 (4) with Cout cycling 8, 16, 24, 32 (one forward N-tile, a half-empty second, a full second);
+      1x1x1 32+32->32 1/1/1; 2x4x16 16->16 fork 1/1/1; 3x5x17 16+16->24 8/8/1; W = 1: 4x7x1 32+16->16 4/4/1; N = 2: 2x2x4x48 8->8 6/6/1;
+      nslabs 3 and 5: 2x4x48 24->16, 2x4x80 40->32; slab walks: 2x4x141 32+32->32 fork 9/8/2; 2x3x271 64->16 17/8/3; 1x4x144 32+16->24 9/8/2; 2x4x267 16+16->8 17/16/2;
+      1x2x1038 8->8 65/64/2  (nslabs 1, 2, 3, 4, 5, 6, 8, 16, 64: up_wgrad_reduce_kernel's four-at-a-time loop and its tail);
+      on 2x4x141 32+32->16 (slab 0 walks tiles 0 and 8): zero_first, zero_last, jump_dn, jump_up.
+  flow (split tile 2 x 8 x 16 | fp32 tile 4 x 8 x 16; grid = min(tiles, 512) over da_xcd_items; da_reduce_partials nparts = grid):
+      the 6 weight-gradient classes x Cout 1, 2, 3 at 5x9x18 (12 | 8 tiles) = all 18 flow-wgrad and all 15 flowmm classes; 8+16->4, 24->3, 32->2, 32+32->3, 12->3;
+      on 8+16->3: 2x8x16 1 | 1; 2x8x109 7 | 7 (grid no multiple of 8); 4x15x31 8 | 4; 2x17x33 9 | 9; 2x4x16x32 16 | 8; 2x8x267 17 | 17; 13x49x15 49 | 28;
+      8x32x64 64 | 32; 10x100x13 65 | 39; 6x24x905 513 | 342 (a workgroup walks 2 | 1 tiles); 9x2x3273 1025 | 615 (3 | 2).
+  first: valu, 1->8 (XW 32) and 1->16 (XW 16): 2xHx5 with H = 33, 34, 66, 67, 35, 68 (y-strips 1, 2, 2, 3, 2, 3; rows left for the `yb += 3` tail 0, 1, 0, 1, 2, 2);
+      2x35xW with W = XW - 1, XW, XW + 1 (ragged last x-strip with a ragged last y-strip); D = 1: 1x40x37 1->8; N = 2: 2x3x34x20 1->16;
+      137x67x65 1->16: 2055 strips over 512 x 4 waves, a wave walks 2;
+      exchanged: 1+1->16 at 1 tile, 2->16 at 8 | 4, 1->12 at 9, 2->8 at 513 | 342 (walk 2 | 1), 1+1->4 at 9, 1+1->12 at 342 (two window tensors: the fp32 kernel in both modes);
+      smallcin: 3->8, 4->16, 2+2->24, 1->32, 2->24, 1+1->32, 3->12.
+  C ABI: da_upconv3d_k3_fwd / _dgrad / _wgrad return DA_ERR_UNSUPPORTED and leave a sentinel-filled output untouched for (C1, C2, Cout) = (8, 8, 16), (12, 0, 16),
+      (64, 8, 16), (16, 0, 40), (16, 0, 12) and, in matrix mode 'fp32', for all 64 classes of the table; ops.upconv_supported agrees.
+
+Worst case over all examples on an MI355X (distance from float64: max(rel-l2, max-abs / max|ref|)), the fp32 CPU oracle's worst on the same examples
+(tests/test_regconv_reference.py), the ceiling (what the existing tests of these kernels assert, regconv_cases.CEIL) and what is asserted; filled from the report
+files DA_REGCONV_SHAPES_REPORT writes.  'up2' device = the larger of the folded and the materialised route in that mode.
+  family   mode        quantity   device worst  fp32 oracle worst  ceiling   asserted
+  stride2  fp32_split  output     1.0e-06       7.8e-07           1e-05     1.0e-05  (max(4 x device, 8 x oracle) = 6.3e-06: less than 10 x below the ceiling, stays)
+  stride2  fp32_split  dx1, dx2   6.0e-07       7.8e-07           1e-05     1.0e-05  (max(4 x device, 8 x oracle) = 6.3e-06: less than 10 x below the ceiling, stays)
+  stride2  fp32_split  dw         3.7e-07       1.9e-06           1e-05     1.0e-05  (max(4 x device, 8 x oracle) = 1.6e-05: less than 10 x below the ceiling, stays)
+  stride2  fp32_split  db         6.7e-08       1.7e-06           1e-05     1.0e-05  (max(4 x device, 8 x oracle) = 1.4e-05: less than 10 x below the ceiling, stays)
+  stride2  fp32        output     1.3e-06       7.8e-07           1e-04     6.3e-06  
+  stride2  fp32        dx1, dx2   9.7e-07       7.8e-07           1e-04     6.3e-06  
+  stride2  fp32        dw         4.7e-07       1.9e-06           1e-04     1.0e-04  (max(4 x device, 8 x oracle) = 1.6e-05: less than 10 x below the ceiling, stays)
+  stride2  fp32        db         6.7e-08       1.7e-06           1e-04     1.0e-04  (max(4 x device, 8 x oracle) = 1.4e-05: less than 10 x below the ceiling, stays)
+  up2      fp32_split  output     1.4e-06       8.2e-07           1e-05     1.0e-05  (max(4 x device, 8 x oracle) = 6.6e-06: less than 10 x below the ceiling, stays) (folded 7.2e-07, materialised 1.4e-06)
+  up2      fp32_split  dx1, dx2   1.4e-06       4.3e-07           1e-05     1.0e-05  (max(4 x device, 8 x oracle) = 5.6e-06: less than 10 x below the ceiling, stays) (folded 1.4e-06, materialised 3.7e-07)
+  up2      fp32_split  dw         2.0e-07       2.1e-06           1e-05     1.0e-05  (max(4 x device, 8 x oracle) = 1.7e-05: less than 10 x below the ceiling, stays) (folded 1.9e-07, materialised 2.0e-07)
+  up2      fp32_split  db         6.4e-08       1.9e-06           1e-05     1.0e-05  (max(4 x device, 8 x oracle) = 1.6e-05: less than 10 x below the ceiling, stays) (folded 6.4e-08, materialised 6.4e-08)
+  up2      fp32        output     1.9e-06       8.2e-07           1e-04     7.8e-06  
+  up2      fp32        dx1, dx2   7.9e-07       4.3e-07           1e-04     3.5e-06  
+  up2      fp32        dw         6.0e-07       2.1e-06           1e-04     1.0e-04  (max(4 x device, 8 x oracle) = 1.7e-05: less than 10 x below the ceiling, stays)
+  up2      fp32        db         6.4e-08       1.9e-06           1e-04     1.0e-04  (max(4 x device, 8 x oracle) = 1.6e-05: less than 10 x below the ceiling, stays)
+  flow     fp32_split  output     1.4e-06       1.4e-06           1e-05     1.0e-05  (max(4 x device, 8 x oracle) = 1.2e-05: less than 10 x below the ceiling, stays)
+  flow     fp32_split  dx1, dx2   4.7e-07       4.1e-07           1e-05     1.0e-05  (max(4 x device, 8 x oracle) = 3.3e-06: less than 10 x below the ceiling, stays)
+  flow     fp32_split  dw         4.3e-07       1.5e-06           1e-05     1.0e-05  (max(4 x device, 8 x oracle) = 1.2e-05: less than 10 x below the ceiling, stays)
+  flow     fp32_split  db         5.7e-08       6.7e-07           1e-05     1.0e-05  (max(4 x device, 8 x oracle) = 5.4e-06: less than 10 x below the ceiling, stays)
+  flow     fp32        output     1.4e-06       1.4e-06           1e-04     1.0e-04  (max(4 x device, 8 x oracle) = 1.2e-05: less than 10 x below the ceiling, stays)
+  flow     fp32        dx1, dx2   4.8e-07       4.1e-07           1e-04     3.3e-06  
+  flow     fp32        dw         4.3e-07       1.5e-06           1e-04     1.0e-04  (max(4 x device, 8 x oracle) = 1.2e-05: less than 10 x below the ceiling, stays)
+  flow     fp32        db         5.7e-08       6.7e-07           1e-04     5.4e-06  
+  first    fp32_split  output     4.2e-07       4.5e-07           1e-05     1.0e-05  (max(4 x device, 8 x oracle) = 3.7e-06: less than 10 x below the ceiling, stays)
+  first    fp32_split  dx1, dx2   1.1e-06       8.4e-07           1e-05     1.0e-05  (max(4 x device, 8 x oracle) = 6.8e-06: less than 10 x below the ceiling, stays)
+  first    fp32_split  dw         6.9e-07       1.6e-06           1e-05     1.0e-05  (max(4 x device, 8 x oracle) = 1.3e-05: less than 10 x below the ceiling, stays)
+  first    fp32_split  db         7.0e-08       1.3e-06           1e-05     1.0e-05  (max(4 x device, 8 x oracle) = 1.1e-05: less than 10 x below the ceiling, stays)
+  first    fp32        output     4.2e-07       4.5e-07           1e-04     3.7e-06  
+  first    fp32        dx1, dx2   1.1e-06       8.4e-07           1e-04     6.8e-06  
+  first    fp32        dw         6.9e-07       1.6e-06           1e-04     1.0e-04  (max(4 x device, 8 x oracle) = 1.3e-05: less than 10 x below the ceiling, stays)
+  first    fp32        db         7.0e-08       1.3e-06           1e-04     1.0e-04  (max(4 x device, 8 x oracle) = 1.1e-05: less than 10 x below the ceiling, stays)
+Asserted = max(4 x device worst, 8 x fp32 oracle worst) rounded up to two digits wherever that is more than 10 x below the ceiling, else the ceiling.
+Device against oracle: the device is further from float64 than the fp32 oracle by at most 3.2 x (the folded data gradient, 1.4e-6 against 4.3e-7; its summed
+weights carry up to eight terms), 2.4 x (output of the materialised route in fp32 mode) and below 1.7 x elsewhere; dw and db, summed in double over the partials,
+are 2 ... 30 x CLOSER than the oracle.  The split arithmetic's per-product bound is 12 x fp32's (2^-21 + 2^-22 against 2^-24): no finding.
+Guard band: at most 52 elements of a tensor per example (the 1 052 672-element output of the 257-tile stride-2 example; cap: 0.1 % and 64).
+Total time of this file on one MI355X: 13 s of pytest time, the slowest test (up2) 4.3 s.
+
+What these examples found (fixed in the launchers, see conv3d_s2.hip / conv3d_mfma.hip):
+  * stride 2, Cin 16 / 32, Cout 8 or 24 (any Cout % 16 != 0 outside the native kernels), either mode: da_conv3d_k3_dgrad failed with DA_ERR_UNSUPPORTED -- the
+    masked space-to-depth data gradient stages dY in 16-channel chunks.  It now goes to the direct kernel (pinned: 16->8 at 5x9x33, 32->24).
+  * stride 2, Cin 16 / 32, Cout 48 (three N-tiles), either mode: da_conv3d_k3_fwd failed with DA_ERR_UNSUPPORTED -- the masked kernels exist for one and two N-tiles
+    per workgroup and pick_nrep chose three.  Capped at two (pinned: 32->48 at 2x4x7x10).
+What the issue's route table says and the launchers do not: the masked route's data gradient takes Cout % 16 == 0 only (above); the data gradient of (32, 32) -> Cout
+is a thin conv Cout -> 64 and da_conv3_thin_supported stops at 32 outputs, so it runs the direct kernel; 65 tiles with N = 2 do not exist (66 are pinned, and 65 with
+N = 1).  The drawn output gradient is N(0.5, 1), not N(0, 1):
+with Cout 1 ... 4 the bias gradient of a zero-mean gradient is a cancelling sum the fp32 oracle itself misses by 2.7e-6 (regconv_cases.G_MEAN); drawn examples with an
+activation are also narrowed to 500 000 output elements, where the guard band's expected population (4e-5 per element) stays far below the cap of 64.
+"""
+import pytest
+import torch
+
+import regconv_cases as rc
+from test_gpu_ops import cl, dev
+
+pytestmark = pytest.mark.gpu
+
+
+class _mode(object):
+    def __init__(self, mode):
+        self.mode = mode
+
+    def __enter__(self):
+        from deepatlas_amd import ops
+        self.prev = ops.set_matrix_precision(self.mode)
+
+    def __exit__(self, *exc):
+        from deepatlas_amd import ops
+        ops.set_matrix_precision(self.prev)
+
+
+def _cpu(t):
+    return t.detach().cpu() if t is not None else None
+
+
+def _run(inp, folded=True):
+    """ops.Conv3dK3Fn on the example: forward, then backward with the drawn output gradient(s).  folded = False ('up2' only): the materialised route,
+    ops.UpsampleNearestFn on each source + the plain convolution."""
+    from deepatlas_amd import ops
+    x1 = cl(inp['x1']).requires_grad_(True)
+    x2 = cl(inp['x2']).requires_grad_(True) if inp['x2'] is not None else None
+    w, b = inp['w'].to(dev()).requires_grad_(True), inp['b'].to(dev()).requires_grad_(True)
+    if inp['up2'] and not folded:
+        size = tuple(2 * v for v in inp['dims'][1:])
+        res = ops.Conv3dK3Fn.apply(ops.UpsampleNearestFn.apply(x1, size), ops.UpsampleNearestFn.apply(x2, size) if x2 is not None else None, w, b, 1, inp['slope'],
+                                   False, inp['fork'])
+    else:
+        res = ops.Conv3dK3Fn.apply(x1, x2, w, b, inp['stride'], inp['slope'], False, inp['fork'], inp['up2'])
+    if inp['fork']:
+        out, alias = res
+        assert alias.data_ptr() == out.data_ptr()
+        torch.autograd.backward([out, alias], [cl(inp['g1']), cl(inp['g2'])])
+    else:
+        out = res
+        out.backward(cl(inp['g1']))
+    torch.cuda.synchronize()
+    return dict(out=_cpu(out), dx1=_cpu(x1.grad), dx2=_cpu(x2.grad) if x2 is not None else None, dw=_cpu(w.grad), db=_cpu(b.grad))
+
+
+def _family(family):
+    """Every example in both matrix modes against ONE float64 reference (recomputed only where the two runs decide differently inside the guard band)."""
+    from deepatlas_amd import ops
+    strategy, pinned = rc.FAMILY[family]
+
+    def body(case):
+        if case.get('fixed'):
+            rc.check_pinned(case)
+        inp = rc.build(case)
+        jump = (case.get('kind') or '').startswith('jump')
+        ref = ref_from = None
+        runs = [(mode, True) for mode in rc.MODES]
+        if family == 'up2':                                 # the folded route exists in split mode only; the materialised route runs in both
+            runs = [('fp32_split', True), ('fp32_split', False), ('fp32', False)]
+        for mode, folded in runs:
+            with _mode(mode):
+                if family == 'up2':
+                    assert ops.upconv_supported(case['ch'][0], case['ch'][1], case['cout']) == (mode == 'fp32_split')
+                got = _run(inp, folded)
+            if ref is None or not rc.same_decisions(ref, got['out'], ref_from):
+                ref, ref_from = rc.ref(inp, torch.float64, decided=got['out']), got['out']
+                rc.check_band(ref['band'])
+                for k, n in ref['band']:
+                    rc.note(family, 'band elements', k)
+            name = '%s %s' % (family, mode) + ('' if folded else ' materialised')
+            (rc.compare_jump(name, inp, got, ref, rc.TOL[family][mode]) if jump else rc.compare(name, got, ref, rc.TOL[family][mode]))
+    rc.run_cases(strategy, body, pinned=pinned)
+
+
+def test_stride2_random_shapes():
+    """Stride-2 conv + activation: conv3d_s2n.hip (split mode, Cin 16 / 32 -> Cout 32 / 64), the masked space-to-depth route (fp32 mode, and Cout 8 ... 48 in
+    split mode) and the direct kernels."""
+    _family('stride2')
+
+
+def test_up2_random_shapes():
+    """conv(nearest-x2(cat(a, b))) + activation: conv3d_up2.hip against float64, and the materialised route on the same inputs in both modes."""
+    _family('up2')
+
+
+def test_flow_random_shapes():
+    """Cout 1 ... 4: conv3d_flowmm.hip forward / data gradient, the weight gradient's split and exact kernels of conv3d_flow.hip, the thin VALU kernel, the
+    swapped small-Cin and the generic weight gradient."""
+    _family('flow')
+
+
+def test_first_random_shapes():
+    """Cin 1 ... 4: fewcin_wgrad_valu_kernel, the operand-exchanged matrix form, smallcin; forward and (never asked for in training) data gradient on the
+    thin / direct kernels."""
+    _family('first')
+
+
+SENTINEL = -12345.0
+
+
+@pytest.mark.parametrize('mode', rc.MODES)
+def test_folded_upsampling_declines_through_the_c_abi(mode):
+    """da_upconv3d_k3_fwd / _dgrad / _wgrad return DA_ERR_UNSUPPORTED and leave the output untouched (pre-filled with a sentinel) for C1 = 8 with C2 = 8,
+    C1 = 12, Cin = 72, Cout = 40, Cout = 12 -- and for every class of the table while the matrix mode is 'fp32'; ops.upconv_supported agrees."""
+    from deepatlas_amd import _native as nat, ops
+    N, D, H, W = 1, 2, 3, 5
+    classes = list(rc.UP_DECLINED) if mode == 'fp32_split' else list(rc.UP_DECLINED) + [ch + (co,) for ch in rc.UP_CLASSES for co in rc.UP_COUTS]
+    with _mode(mode):
+        if mode == 'fp32_split':
+            assert all(ops.upconv_supported(c1, c2, co) for (c1, c2) in rc.UP_CLASSES for co in rc.UP_COUTS)
+        for c1, c2, cout in classes:
+            assert not ops.upconv_supported(c1, c2, cout) and not rc.upconv_supported(c1, c2, cout, mode), (c1, c2, cout)
+            cin = c1 + c2
+            s1 = torch.ones((N, D, H, W, c1), device=dev())
+            s2 = torch.ones((N, D, H, W, c2), device=dev()) if c2 else None
+            w_tio, bias = torch.ones((27, cin, cout), device=dev()), torch.ones((cout,), device=dev())
+            dy = torch.ones((N, 2 * D, 2 * H, 2 * W, cout), device=dev())
+            out = torch.full((N, 2 * D, 2 * H, 2 * W, cout), SENTINEL, device=dev())
+            dx1 = torch.full((N, D, H, W, c1), SENTINEL, device=dev())
+            dx2 = torch.full((N, D, H, W, c2), SENTINEL, device=dev()) if c2 else None
+            dw = torch.full((27, cin, cout), SENTINEL, device=dev())
+            wp, wn = nat.workspace.get(1 << 20, dev())
+            p, L, st = nat.ptr, nat.lib(), nat.stream()
+            rcs = [L.da_upconv3d_k3_fwd(p(s1), c1, p(s2), c2, p(w_tio), p(bias), p(out), N, D, H, W, cout, 0.0, wp, wn, st),
+                   L.da_upconv3d_k3_dgrad(p(dy), p(w_tio), p(dx1), c1, p(dx2), c2, N, D, H, W, cout, wp, wn, st),
+                   L.da_upconv3d_k3_wgrad(p(s1), c1, p(s2), c2, p(dy), p(dw), N, D, H, W, cout, wp, wn, st)]
+            torch.cuda.synchronize()
+            assert rcs == [-3, -3, -3], (c1, c2, cout, rcs)          # DA_ERR_UNSUPPORTED
+            for t in (out, dx1, dx2, dw):
+                assert t is None or bool((t == SENTINEL).all()), (c1, c2, cout)
+            with pytest.raises(NotImplementedError):
+                ops.Conv3dK3Fn.apply(s1.permute(0, 4, 1, 2, 3), s2.permute(0, 4, 1, 2, 3) if c2 else None, torch.ones((cout, cin, 3, 3, 3), device=dev()), bias, 1, 0.0,
+                                     False, False, True)
