@@ -74,6 +74,13 @@ __device__ __forceinline__ int da_xcd_item_of_block(int b, int n) {
     const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
     return base + loc;
 }
+// item t of a tile list -> sample n and tile indices, z fastest, then y, then x: z / y neighbours share the most halo and, behind
+// da_xcd_item_of_block, run back to back on one XCD.  The caller multiplies by its own tile extents.
+__device__ __forceinline__ void da_tile_zyx(int t, int ntz, int nty, int ntx, int& n, int& tz, int& ty, int& tx) {
+    tz = t % ntz; t /= ntz;
+    ty = t % nty; t /= nty;
+    tx = t % ntx; n = t / ntx;
+}
 
 __device__ __forceinline__ float da_wave_sum(float v) {
 #pragma unroll
@@ -88,6 +95,11 @@ __device__ __forceinline__ double da_wave_sum(double v) {
 __device__ __forceinline__ float da_wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ double da_wave_max(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
     return v;
 }
 
@@ -186,6 +198,42 @@ __device__ __forceinline__ float da_rows_max(float v) {
     float a, b;
     da_swap16(v, a, b); v = fmaxf(a, b);
     da_swap32(v, a, b); return fmaxf(a, b);
+}
+
+// Buffer descriptor over `bytes` bytes at `base` (raw buffer, 32-bit byte offsets).  A lane whose offset is out of range -- the kernels pass
+// 0xFFFFFFFF for everything outside the volume or the tile -- loads zeros and stores nothing: the hardware range check replaces an
+// exec-mask branch per access, so a tile's loads issue back to back.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t da_rsrc(const void* base, unsigned bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, bytes, 0x00020000);
+}
+__device__ __forceinline__ float4 da_buf_load4(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
+    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0));
+}
+__device__ __forceinline__ float da_buf_load1(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, byte_off, 0, 0));
+}
+__device__ __forceinline__ void da_buf_store4(__amdgpu_buffer_rsrc_t r, unsigned byte_off, da_f4v v) {
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned, v), r, byte_off, 0, 0);
+}
+// lane ^ 1 / lane ^ 2 exchanges inside a lane quad as DPP quad_perm moves (VALU, no trip through the LDS crossbar like __shfl_xor)
+__device__ __forceinline__ float da_quad_xor1(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true)); }   // quad_perm [1,0,3,2]
+__device__ __forceinline__ float da_quad_xor2(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true)); }   // quad_perm [2,3,0,1]
+// 4 x 4 transpose across a lane quad (q = lane & 3): in = (4 voxels x 1 channel) per lane (MFMA C layout: row = 4 g + reg), out = (1 voxel x 4 channels)
+__device__ __forceinline__ da_f4v da_quad_transpose(da_f4v a, int q) {
+    float t0 = a[0], t1 = a[1], t2 = a[2], t3 = a[3];
+    {
+        const bool odd = (q & 1) != 0;
+        const float s01 = odd ? t0 : t1, s23 = odd ? t2 : t3;
+        const float r01 = da_quad_xor1(s01), r23 = da_quad_xor1(s23);
+        if (odd) { t0 = r01; t2 = r23; } else { t1 = r01; t3 = r23; }
+    }
+    {
+        const bool hi2 = (q & 2) != 0;
+        const float s02 = hi2 ? t0 : t2, s13 = hi2 ? t1 : t3;
+        const float r02 = da_quad_xor2(s02), r13 = da_quad_xor2(s13);
+        if (hi2) { t0 = r02; t1 = r13; } else { t2 = r02; t3 = r13; }
+    }
+    return (da_f4v){t0, t1, t2, t3};
 }
 
 // Linear voxel index -> coordinates.  In 32-bit arithmetic whenever the index fits: a 64-bit integer division costs the VALU roughly ten

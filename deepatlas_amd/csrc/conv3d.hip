@@ -130,8 +130,8 @@ conv3_tinycin_fwd_kernel(const float* __restrict__ in1, int C1, const float* __r
     const int y = (int)(r % H); r /= H;
     const int z = (int)(r % D); const int n = (int)(r / D);
     const int Cin = C1 + C2;
-    const __amdgpu_buffer_rsrc_t r1 = __builtin_amdgcn_make_buffer_rsrc((void*)in1, 0, (unsigned)((unsigned long long)nvox * C1 * 4ull), 0x00020000);
-    const __amdgpu_buffer_rsrc_t r2 = __builtin_amdgcn_make_buffer_rsrc((void*)(C2 > 0 ? in2 : in1), 0, (unsigned)((unsigned long long)nvox * (C2 > 0 ? C2 : C1) * 4ull), 0x00020000);
+    const __amdgpu_buffer_rsrc_t r1 = da_rsrc(in1, (unsigned)((unsigned long long)nvox * C1 * 4ull));
+    const __amdgpu_buffer_rsrc_t r2 = da_rsrc(C2 > 0 ? in2 : in1, (unsigned)((unsigned long long)nvox * (C2 > 0 ? C2 : C1) * 4ull));
     float xin[27][2];
 #pragma unroll
     for (int tap = 0; tap < 27; ++tap) {

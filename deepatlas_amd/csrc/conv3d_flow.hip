@@ -30,10 +30,6 @@ struct FlowWgP {
     int N, D, H, W, Cout, ntz, nty, ntx, ntiles;
 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t flow_rsrc(const float* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, bytes, 0x00020000);
-}
-
 // MT: M-tiles of 16 (tap, cout) rows; TWO: a second N-tile for in1; S1: LDS row stride (floats) of the in1 tile, 8 or 16
 // XB: the "x" operand (in1 / in2) is stored as bf16 (bf16 activation storage, common.h); the "dy" operand is fp32 in every use (the
 // displacement field's gradient, or -- roles exchanged -- the fp32 network input)
@@ -84,8 +80,8 @@ __global__ void __launch_bounds__(256, 2) flow_wgrad_kernel(FlowWgP p) {
         const int tz = t % p.ntz; const int n = t / p.ntz;
         const int x0 = tx * TX, y0 = ty * TY, z0 = tz * TZ;
         const unsigned long long vol = (unsigned long long)p.D * p.H * p.W;
-        const __amdgpu_buffer_rsrc_t r2 = flow_rsrc(p.C2 > 0 ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(p.in2) + (size_t)n * vol * p.C2 * EX) : p.dy, p.C2 > 0 ? (unsigned)(vol * p.C2 * EX) : 0u);
-        const __amdgpu_buffer_rsrc_t r1 = flow_rsrc(p.C1 > 0 ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(p.in1) + (size_t)n * vol * p.C1 * EX) : p.dy, p.C1 > 0 ? (unsigned)(vol * p.C1 * EX) : 0u);
+        const __amdgpu_buffer_rsrc_t r2 = da_rsrc(p.C2 > 0 ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(p.in2) + (size_t)n * vol * p.C2 * EX) : p.dy, p.C2 > 0 ? (unsigned)(vol * p.C2 * EX) : 0u);
+        const __amdgpu_buffer_rsrc_t r1 = da_rsrc(p.C1 > 0 ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(p.in1) + (size_t)n * vol * p.C1 * EX) : p.dy, p.C1 > 0 ? (unsigned)(vol * p.C1 * EX) : 0u);
         auto ldx = [](__amdgpu_buffer_rsrc_t r, unsigned off) -> float4 {
             if constexpr (XB) {
                 typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
@@ -94,8 +90,8 @@ __global__ void __launch_bounds__(256, 2) flow_wgrad_kernel(FlowWgP p) {
             } else return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
         };
         const int Cd2 = Cout - p.Cd1;
-        const __amdgpu_buffer_rsrc_t ry = flow_rsrc(p.dy + (size_t)n * vol * p.Cd1, (unsigned)(vol * p.Cd1 * 4ull));
-        const __amdgpu_buffer_rsrc_t ry2 = flow_rsrc(Cd2 > 0 ? p.dyb + (size_t)n * vol * Cd2 : p.dy, Cd2 > 0 ? (unsigned)(vol * Cd2 * 4ull) : 0u);
+        const __amdgpu_buffer_rsrc_t ry = da_rsrc(p.dy + (size_t)n * vol * p.Cd1, (unsigned)(vol * p.Cd1 * 4ull));
+        const __amdgpu_buffer_rsrc_t ry2 = da_rsrc(Cd2 > 0 ? p.dyb + (size_t)n * vol * Cd2 : p.dy, Cd2 > 0 ? (unsigned)(vol * Cd2 * 4ull) : 0u);
 #pragma unroll
         for (int it = 0; it < NX2; ++it) {
             int idx = threadIdx.x + it * 256;
@@ -313,16 +309,16 @@ __global__ void __launch_bounds__(256, 2) flow_wgrad_split_kernel(FlowWgP p) {
         const int tz = t % p.ntz; const int n = t / p.ntz;
         const int x0 = tx * TX, y0 = ty * TY, z0 = tz * TZ;
         const unsigned long long vol = (unsigned long long)p.D * p.H * p.W;
-        const __amdgpu_buffer_rsrc_t r2 = flow_rsrc(p.C2 > 0 ? p.in2 + (size_t)n * vol * p.C2 : p.dy, p.C2 > 0 ? (unsigned)(vol * p.C2 * 4ull) : 0u);
-        const __amdgpu_buffer_rsrc_t r1 = flow_rsrc(p.C1 > 0 ? p.in1 + (size_t)n * vol * p.C1 : p.dy, p.C1 > 0 ? (unsigned)(vol * p.C1 * 4ull) : 0u);
+        const __amdgpu_buffer_rsrc_t r2 = da_rsrc(p.C2 > 0 ? p.in2 + (size_t)n * vol * p.C2 : p.dy, p.C2 > 0 ? (unsigned)(vol * p.C2 * 4ull) : 0u);
+        const __amdgpu_buffer_rsrc_t r1 = da_rsrc(p.C1 > 0 ? p.in1 + (size_t)n * vol * p.C1 : p.dy, p.C1 > 0 ? (unsigned)(vol * p.C1 * 4ull) : 0u);
 #if defined(DA_FWS_ABL) && (DA_FWS_ABL & 8)
         auto ld4 = [](__amdgpu_buffer_rsrc_t r, unsigned off) -> float4 { return make_float4((float)off, 1.f, 2.f, 3.f); };      // timing only: no x loads
 #else
         auto ld4 = [](__amdgpu_buffer_rsrc_t r, unsigned off) -> float4 { return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0)); };
 #endif
         const int Cd2 = Cout - p.Cd1;
-        const __amdgpu_buffer_rsrc_t ry = flow_rsrc(p.dy + (size_t)n * vol * p.Cd1, (unsigned)(vol * p.Cd1 * 4ull));
-        const __amdgpu_buffer_rsrc_t ry2 = flow_rsrc(Cd2 > 0 ? p.dyb + (size_t)n * vol * Cd2 : p.dy, Cd2 > 0 ? (unsigned)(vol * Cd2 * 4ull) : 0u);
+        const __amdgpu_buffer_rsrc_t ry = da_rsrc(p.dy + (size_t)n * vol * p.Cd1, (unsigned)(vol * p.Cd1 * 4ull));
+        const __amdgpu_buffer_rsrc_t ry2 = da_rsrc(Cd2 > 0 ? p.dyb + (size_t)n * vol * Cd2 : p.dy, Cd2 > 0 ? (unsigned)(vol * Cd2 * 4ull) : 0u);
         // x loads: the thread's tile-relative byte offsets are fixed for the launch (xo2 / xo1: -1 = no such pair); per tile one scalar base and the ragged-edge test
         const unsigned tb2 = (unsigned)(((z0 * p.H + y0) * p.W + x0) * p.C2 * 4), tb1 = (unsigned)(((z0 * p.H + y0) * p.W + x0) * p.C1 * 4);
         const int lz = p.D - z0, ly = p.H - y0, lx = p.W - x0;      // local coordinates below these are inside the volume
@@ -358,7 +354,7 @@ __global__ void __launch_bounds__(256, 2) flow_wgrad_split_kernel(FlowWgP p) {
             pd[it] = v;
         }
     };
-    int Eacc = 0, Emin = 0;
+    DaSplitScale sc;
     bool first_tile = true;
     // largest magnitudes of the parked tile (two workgroup-wide maxima through one barrier), its exponents, split + transposed stores.  Returns the tile's E.
     auto stage = [&]() -> int {
@@ -378,9 +374,7 @@ __global__ void __launch_bounds__(256, 2) flow_wgrad_split_kernel(FlowWgP p) {
         mx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(fmaxf(fmaxf(fmaxf(m4.x, m4.y), fmaxf(m4.z, m4.w)), fmaxf(fmaxf(m5.x, m5.y), fmaxf(m5.z, m5.w))))));
         my = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(fmaxf(fmaxf(fmaxf(n4.x, n4.y), fmaxf(n4.z, n4.w)), fmaxf(fmaxf(n5.x, n5.y), fmaxf(n5.z, n5.w))))));
         const int ex = da_scale_exp(mx);
-        int E = ex + da_scale_exp(my);
-        if (!first_tile) E = min(E, Emin + 40);
-        Emin = first_tile ? E : min(Emin, E);
+        const int E = sc.admit(ex + da_scale_exp(my), first_tile);
         first_tile = false;
         const float sx = da_pow2(ex), sy = da_pow2(E - ex);
         // x planes: per channel of the quad the two voxels' halves side by side (one 4-byte store per plane)
@@ -444,12 +438,11 @@ __global__ void __launch_bounds__(256, 2) flow_wgrad_split_kernel(FlowWgP p) {
         const bool has_next = tile + 1 < t_end;
         if (has_next) issue(tile + 1);
         {
-            const float f = da_acc_factor(Ecur - Eacc);          // the running sums into this tile's unit (exact)
+            const float f = sc.enter(Ecur);                      // the running sums into this tile's unit (exact)
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
                 for (int nt = 0; nt < NTT; ++nt) acc[mt][nt] = acc[mt][nt] * f;
-            Eacc = Ecur;
         }
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
@@ -485,7 +478,7 @@ __global__ void __launch_bounds__(256, 2) flow_wgrad_split_kernel(FlowWgP p) {
         }
     }
     // the sums back to the true unit (two exact factors), then as in flow_wgrad_kernel: cross-wave reduction through LDS, this workgroup's partial dW[tap][ci][co]
-    const float inv1 = da_pow2(-(Eacc / 2)), inv2 = da_pow2(-(Eacc - Eacc / 2));
+    float inv1, inv2; sc.leave(inv1, inv2);
     __syncthreads();
     float4* red = reinterpret_cast<float4*>(lds8);
     for (int w = 0; w < 4; ++w) {
@@ -622,8 +615,8 @@ __global__ void __launch_bounds__(256) fewcin_wgrad_valu_kernel(const float* __r
     // ci -> (tensor, channel): one tensor with CIN channels (cstride = CIN) or two one-channel tensors (cstride = 1)
     const float* xt = (CIN == 2 && cstride == 1 && ci == 1) ? xb : xa;
     const int coff = (cstride == 1) ? 0 : ci;
-    const __amdgpu_buffer_rsrc_t rx = flow_rsrc(xt, (unsigned)((unsigned long long)N * vol * cstride * 4ull));
-    const __amdgpu_buffer_rsrc_t rg = flow_rsrc(dy, (unsigned)((unsigned long long)N * vol * COUT * 4ull));
+    const __amdgpu_buffer_rsrc_t rx = da_rsrc(xt, (unsigned)((unsigned long long)N * vol * cstride * 4ull));
+    const __amdgpu_buffer_rsrc_t rg = da_rsrc(dy, (unsigned)((unsigned long long)N * vol * COUT * 4ull));
     float acc[27][4];
 #pragma unroll
     for (int t = 0; t < 27; ++t) { acc[t][0] = 0.f; acc[t][1] = 0.f; acc[t][2] = 0.f; acc[t][3] = 0.f; }

@@ -23,35 +23,10 @@ constexpr int TZ = 2, TY = 8, TX = 16;                     // output tile
 constexpr int HZ = TZ + 2, HY = TY + 2, HX = TX + 2;       // halo 4 x 10 x 18
 constexpr int HV = HZ * HY * HX;                           // 720 voxels
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t fm_rsrc(const void* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, bytes, 0x00020000);
-}
-__device__ __forceinline__ float4 fm_load4(__amdgpu_buffer_rsrc_t r, unsigned off) {
-    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
-}
-__device__ __forceinline__ float fm_load1(__amdgpu_buffer_rsrc_t r, unsigned off) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0));
-}
-__device__ __forceinline__ void fm_store4(__amdgpu_buffer_rsrc_t r, unsigned off, f32x4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned, v), r, off, 0, 0);
-}
-__device__ __forceinline__ void fm_tile(int t, int ntz, int nty, int ntx, int& n, int& z0, int& y0, int& x0) {      // z fastest: neighbours in z / y share the most halo
-    const int tz = t % ntz; t /= ntz;
-    const int ty = t % nty; t /= nty;
-    const int tx = t % ntx; n = t / ntx;
-    z0 = tz * TZ; y0 = ty * TY; x0 = tx * TX;
-}
-// largest |w| of a small weight tensor (n floats) by one 256-thread workgroup
-__device__ __forceinline__ float fm_tensor_absmax(const float* __restrict__ w, int n, float* red) {
-    float m = 0.f;
-    for (int k = threadIdx.x; k < n; k += 256) m = fmaxf(m, fabsf(w[k]));
-    return da_block_max4(m, red, (int)threadIdx.x >> 6, (int)threadIdx.x & 63);
-}
-// products of a split multiply, small terms first, weights as the MFMA's A operand: (w plane, x plane) = (h, l) (l, h) (h, h)
+// the three products of a split multiply (kSplitPA / kSplitPB), weights as the MFMA's A operand
 __device__ __forceinline__ f32x4 fm_mma3(f32x4 c, const f16x8 (&w)[2], const f16x8 (&x)[2]) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[0], x[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[1], x[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[0], x[0], c, 0, 0, 0);
+#pragma unroll
+    for (int pr = 0; pr < 3; ++pr) c = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[kSplitPA[pr]], x[kSplitPB[pr]], c, 0, 0, 0);
     return c;
 }
 
@@ -68,7 +43,7 @@ struct FwdP {
 // channels 8 (b % NB8) .. + 7), column n = (dy = n >> 2, co = n & 3).  One scale for the tensor (exponent -> wexp[0]).
 __global__ void __launch_bounds__(256) fm_pack_fwd_kernel(const float* __restrict__ w, unsigned short* __restrict__ wp, int* __restrict__ wexp, int Cin, int Cout, int NSTEP) {
     __shared__ float red[4];
-    const int ew = da_scale_exp(fm_tensor_absmax(w, 27 * Cin * Cout, red));
+    const int ew = da_scale_exp(da_tensor_absmax(w, 27 * Cin * Cout, red));
     if (threadIdx.x == 0) wexp[0] = ew;
     const float sc = da_pow2(ew);
     const int NB8 = Cin / 8, NBLK = 9 * NB8;
@@ -79,11 +54,7 @@ __global__ void __launch_bounds__(256) fm_pack_fwd_kernel(const float* __restric
 #pragma unroll
         for (int e = 0; e < 8; ++e)
             v[e] = (b < NBLK && dy < 3 && co < Cout) ? w[((size_t)((dz * 3 + dy) * 3 + dx) * Cin + cib * 8 + e) * Cout + co] : 0.f;
-        uint2 h0, l0, h1, l1;
-        da_split2(make_float4(v[0], v[1], v[2], v[3]), sc, h0, l0);
-        da_split2(make_float4(v[4], v[5], v[6], v[7]), sc, h1, l1);
-        uint4* o = reinterpret_cast<uint4*>(wp) + (size_t)st * 128 + lane;
-        o[0] = make_uint4(h0.x, h0.y, h1.x, h1.y); o[64] = make_uint4(l0.x, l0.y, l1.x, l1.y);
+        da_split_store8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), sc, reinterpret_cast<uint4*>(wp) + (size_t)st * 128 + lane, 64);
     }
 }
 
@@ -103,7 +74,7 @@ __global__ void __launch_bounds__(256, 2) fm_fwd_kernel(FwdP p) {
     const int zl = wave >> 1, half = wave & 1;
     // weights: 2 KB per K-step, L1 / L2-resident, fetched one step ahead (the whole operand in registers -- 56 of them -- spills beside the
     // 72 registers of the parked next tile)
-    const __amdgpu_buffer_rsrc_t rsw = fm_rsrc(p.wp, (unsigned)(NSTEP * 2048));
+    const __amdgpu_buffer_rsrc_t rsw = da_rsrc(p.wp, (unsigned)(NSTEP * 2048));
     auto wb = [&](int s, int pl) -> f16x8 {
         return __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rsw, (unsigned)lane * 16u, (unsigned)((s * 2 + pl) * 1024), 0));
     };
@@ -119,11 +90,12 @@ __global__ void __launch_bounds__(256, 2) fm_fwd_kernel(FwdP p) {
     // staging: tensor k, iteration it covers halo voxel hv = (tid + 256 it) / Qk, channel quad (tid + 256 it) % Qk
     float4 pre[NITS];
     auto issue = [&](int tile) {
-        int n, z0, y0, x0;
-        fm_tile(tile, p.ntz, p.nty, p.ntx, n, z0, y0, x0);
+        int n, tz, ty, tx;
+        da_tile_zyx(tile, p.ntz, p.nty, p.ntx, n, tz, ty, tx);
+        const int z0 = tz * TZ, y0 = ty * TY, x0 = tx * TX;
         const long long vox = (long long)p.D * p.H * p.W;
-        const __amdgpu_buffer_rsrc_t r1 = fm_rsrc(p.in1 + (long long)n * vox * C1, (unsigned)(vox * C1 * 4));
-        const __amdgpu_buffer_rsrc_t r2 = fm_rsrc(C2 ? p.in2 + (long long)n * vox * C2 : p.in1, (unsigned)(C2 ? vox * C2 * 4 : 0));
+        const __amdgpu_buffer_rsrc_t r1 = da_rsrc(p.in1 + (long long)n * vox * C1, (unsigned)(vox * C1 * 4));
+        const __amdgpu_buffer_rsrc_t r2 = da_rsrc(C2 ? p.in2 + (long long)n * vox * C2 : p.in1, (unsigned)(C2 ? vox * C2 * 4 : 0));
 #pragma unroll
         for (int it = 0; it < NITS; ++it) {
             const bool second = it >= NIT1;
@@ -134,15 +106,12 @@ __global__ void __launch_bounds__(256, 2) fm_fwd_kernel(FwdP p) {
             const int hx = hv % HX, t = hv / HX, hy = t % HY, hz = t / HY;
             const int z = z0 - 1 + hz, y = y0 - 1 + hy, x = x0 - 1 + hx;
             const bool inb = hv < HV && (unsigned)z < (unsigned)p.D && (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W;
-            pre[it] = fm_load4(second ? r2 : r1, inb ? ((unsigned)((z * p.H + y) * p.W + x) * (unsigned)Ck + (unsigned)q * 4u) * 4u : 0xFFFFFFFFu);
+            pre[it] = da_buf_load4(second ? r2 : r1, inb ? ((unsigned)((z * p.H + y) * p.W + x) * (unsigned)Ck + (unsigned)q * 4u) * 4u : 0xFFFFFFFFu);
         }
     };
     int Ecur = 0;
     auto stage = [&]() {                                     // (its barrier retires the tile in LDS)
-        float m = 0.f;
-#pragma unroll
-        for (int it = 0; it < NITS; ++it) m = da_absmax4(m, pre[it]);
-        const int ex = da_scale_exp(da_block_max4(m, smax, wave, lane));
+        const int ex = da_scale_exp(da_block_max4(stage_absmax<NITS>(pre), smax, wave, lane));
         const float sx = da_pow2(ex);
         Ecur = ex + ew;
 #pragma unroll
@@ -151,11 +120,7 @@ __global__ void __launch_bounds__(256, 2) fm_fwd_kernel(FwdP p) {
             const int Qk = second ? Q2 : Q1;
             const int idx = (int)threadIdx.x + (second ? it - NIT1 : it) * 256;
             const int hv = idx / (Qk ? Qk : 1), q = idx & ((Qk ? Qk : 1) - 1);
-            if (hv < HV) {
-                uint2 h, l; da_split2(pre[it], sx, h, l);
-                unsigned char* o = lds + hv * VB + ((second ? C1 : 0) + q * 4) * 2;
-                *reinterpret_cast<uint2*>(o) = h; *reinterpret_cast<uint2*>(o + PLANE) = l;
-            }
+            if (hv < HV) da_split_store4(pre[it], sx, reinterpret_cast<uint2*>(lds + hv * VB + ((second ? C1 : 0) + q * 4) * 2), PLANE / 8);
         }
     };
     float bv[3];
@@ -204,11 +169,12 @@ __global__ void __launch_bounds__(256, 2) fm_fwd_kernel(FwdP p) {
         }
         // epilogue: out[y][co] = P[y][(0, co)] + P[y + 1][(1, co)] + P[y + 2][(2, co)]; lane group g holds the columns (dy = g, co = reg)
         {
-            int n, z0, y0, x0;
-            fm_tile(tile, p.ntz, p.nty, p.ntx, n, z0, y0, x0);
-            const float inv1 = da_pow2(-(Eused / 2)), inv2 = da_pow2(-(Eused - Eused / 2));
+            int n, tz, ty, tx;
+            da_tile_zyx(tile, p.ntz, p.nty, p.ntx, n, tz, ty, tx);
+            const int z0 = tz * TZ, y0 = ty * TY, x0 = tx * TX;
+            float inv1, inv2; da_unscale_factors(Eused, inv1, inv2);
             const long long osample = (long long)p.D * p.H * p.W * p.Cout;
-            const __amdgpu_buffer_rsrc_t ro = fm_rsrc(p.out + (long long)n * osample, (unsigned)(osample * 4));
+            const __amdgpu_buffer_rsrc_t ro = da_rsrc(p.out + (long long)n * osample, (unsigned)(osample * 4));
             const int z = z0 + zl, x = x0 + i;
 #pragma unroll
             for (int yl = 0; yl < 4; ++yl) {
@@ -248,7 +214,7 @@ constexpr int DG_STEPS = 4;                                  // K = 27 taps x 4 
 // packed weights of the data gradient: [step][N-tile][plane][lane][8]; lane (j, g): K = taps 8 step + 2 g + (e >> 2), cout e & 3; N = cin 16 nt + j
 __global__ void __launch_bounds__(256) fm_pack_dgrad_kernel(const float* __restrict__ w, unsigned short* __restrict__ wp, int* __restrict__ wexp, int Cin, int Cout, int NTN) {
     __shared__ float red[4];
-    const int ew = da_scale_exp(fm_tensor_absmax(w, 27 * Cin * Cout, red));
+    const int ew = da_scale_exp(da_tensor_absmax(w, 27 * Cin * Cout, red));
     if (threadIdx.x == 0) wexp[0] = ew;
     const float sc = da_pow2(ew);
     for (int u = threadIdx.x; u < DG_STEPS * NTN * 64; u += 256) {
@@ -260,11 +226,7 @@ __global__ void __launch_bounds__(256) fm_pack_dgrad_kernel(const float* __restr
             const int tap = 8 * st + 2 * g + (e >> 2), co = e & 3;
             v[e] = (tap < 27 && co < Cout && ci < Cin) ? w[((size_t)tap * Cin + ci) * Cout + co] : 0.f;
         }
-        uint2 h0, l0, h1, l1;
-        da_split2(make_float4(v[0], v[1], v[2], v[3]), sc, h0, l0);
-        da_split2(make_float4(v[4], v[5], v[6], v[7]), sc, h1, l1);
-        uint4* o = reinterpret_cast<uint4*>(wp) + (size_t)blk * 128 + lane;
-        o[0] = make_uint4(h0.x, h0.y, h1.x, h1.y); o[64] = make_uint4(l0.x, l0.y, l1.x, l1.y);
+        da_split_store8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), sc, reinterpret_cast<uint4*>(wp) + (size_t)blk * 128 + lane, 64);
     }
 }
 
@@ -300,10 +262,11 @@ __global__ void __launch_bounds__(256, 2) fm_dgrad_kernel(DgP p) {
     const int abase = ((zl * HY + 4 * half) * HX + i) * 8;
     float4 pre[NIT];
     auto issue = [&](int tile) {
-        int n, z0, y0, x0;
-        fm_tile(tile, p.ntz, p.nty, p.ntx, n, z0, y0, x0);
+        int n, tz, ty, tx;
+        da_tile_zyx(tile, p.ntz, p.nty, p.ntx, n, tz, ty, tx);
+        const int z0 = tz * TZ, y0 = ty * TY, x0 = tx * TX;
         const long long ysample = (long long)p.D * p.H * p.W * p.Cout;
-        const __amdgpu_buffer_rsrc_t ry = fm_rsrc(p.dy + (long long)n * ysample, (unsigned)(ysample * 4));
+        const __amdgpu_buffer_rsrc_t ry = da_rsrc(p.dy + (long long)n * ysample, (unsigned)(ysample * 4));
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
             const int hv = (int)threadIdx.x + it * 256;
@@ -313,25 +276,19 @@ __global__ void __launch_bounds__(256, 2) fm_dgrad_kernel(DgP p) {
             const unsigned off = (unsigned)((z * p.H + y) * p.W + x) * (unsigned)p.Cout * 4u;      // (voxel index < 2^31 by da_conv3_flowmm_supported; the byte offset needs all 32 bits: unsigned arithmetic)
             float v[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int c = 0; c < 3; ++c) v[c] = fm_load1(ry, (inb && c < p.Cout) ? off + 4 * c : 0xFFFFFFFFu);
+            for (int c = 0; c < 3; ++c) v[c] = da_buf_load1(ry, (inb && c < p.Cout) ? off + 4 * c : 0xFFFFFFFFu);
             pre[it] = make_float4(v[0], v[1], v[2], v[3]);
         }
     };
     int Ecur = 0;
     auto stage = [&]() {                                     // (its barrier retires the tile in LDS)
-        float m = 0.f;
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) m = da_absmax4(m, pre[it]);
-        const int ey = da_scale_exp(da_block_max4(m, smax, wave, lane));
+        const int ey = da_scale_exp(da_block_max4(stage_absmax<NIT>(pre), smax, wave, lane));
         const float sy = da_pow2(ey);
         Ecur = ey + ew;
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
             const int hv = (int)threadIdx.x + it * 256;
-            if (hv < HV) {
-                uint2 h, l; da_split2(pre[it], sy, h, l);
-                *reinterpret_cast<uint2*>(lds + hv * 8) = h; *reinterpret_cast<uint2*>(lds + PLANE + hv * 8) = l;
-            }
+            if (hv < HV) da_split_store4(pre[it], sy, reinterpret_cast<uint2*>(lds + hv * 8), PLANE / 8);
         }
     };
     typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
@@ -369,12 +326,13 @@ __global__ void __launch_bounds__(256, 2) fm_dgrad_kernel(DgP p) {
                 for (int r = 0; r < 4; ++r) acc[r][nt] = fm_mma3(acc[r][nt], B[s][nt], A[r]);
         }
         {
-            int n, z0, y0, x0;
-            fm_tile(tile, p.ntz, p.nty, p.ntx, n, z0, y0, x0);
-            const float inv1 = da_pow2(-(Eused / 2)), inv2 = da_pow2(-(Eused - Eused / 2));
+            int n, tz, ty, tx;
+            da_tile_zyx(tile, p.ntz, p.nty, p.ntx, n, tz, ty, tx);
+            const int z0 = tz * TZ, y0 = ty * TY, x0 = tx * TX;
+            float inv1, inv2; da_unscale_factors(Eused, inv1, inv2);
             const long long vox = (long long)p.D * p.H * p.W;
-            const __amdgpu_buffer_rsrc_t r1 = fm_rsrc(p.dx1 + (long long)n * vox * C1, (unsigned)(vox * C1 * 4));
-            const __amdgpu_buffer_rsrc_t r2 = fm_rsrc(C2 ? p.dx2 + (long long)n * vox * C2 : p.dx1, (unsigned)(C2 ? vox * C2 * 4 : 0));
+            const __amdgpu_buffer_rsrc_t r1 = da_rsrc(p.dx1 + (long long)n * vox * C1, (unsigned)(vox * C1 * 4));
+            const __amdgpu_buffer_rsrc_t r2 = da_rsrc(C2 ? p.dx2 + (long long)n * vox * C2 : p.dx1, (unsigned)(C2 ? vox * C2 * 4 : 0));
             const int z = z0 + zl, x = x0 + i;
 #pragma unroll
             for (int nt = 0; nt < NTN; ++nt) {
@@ -386,7 +344,7 @@ __global__ void __launch_bounds__(256, 2) fm_dgrad_kernel(DgP p) {
                     const bool ok = c0 < Cin && z < p.D && y < p.H && x < p.W;
                     const int v = (z * p.H + y) * p.W + x;
                     const unsigned off = to1 ? ((unsigned)v * (unsigned)C1 + (unsigned)c0) * 4u : ((unsigned)v * (unsigned)C2 + (unsigned)(c0 - C1)) * 4u;
-                    fm_store4(to1 ? r1 : r2, ok ? off : 0xFFFFFFFFu, acc[r][nt] * inv1 * inv2);
+                    da_buf_store4(to1 ? r1 : r2, ok ? off : 0xFFFFFFFFu, acc[r][nt] * inv1 * inv2);
                 }
             }
         }

@@ -197,12 +197,11 @@ __global__ void __launch_bounds__(256, 2) conv3_mfma_fwd_kernel(FwdP p) {
         const float4 mm = *reinterpret_cast<const float4*>(smax);
         const int mi = __builtin_amdgcn_readfirstlane(__float_as_int(fmaxf(fmaxf(mm.x, mm.y), fmaxf(mm.z, mm.w))));
         const int ew = p.wexp[chn];
-        int E = da_scale_exp(__int_as_float(mi)) + ew;
-        if (chn != 0) E = min(E, Emin + 40);
+        int E = da_split_cap(da_scale_exp(__int_as_float(mi)) + ew, chn == 0, Emin);
         // keep the accumulators' unit (Ecur: the item being accumulated) while the next chunk fits it -- staged up to 8x smaller than its own
         // maximum allows; see conv3_split_wgrad_kernel -- so that the per-item accumulator multiplies run only when the magnitude moves
         if (chn != 0 && E >= Ecur && E <= Ecur + 3 && !(p.ablate & 8)) E = Ecur;
-        Emin = (chn == 0) ? E : min(Emin, E);
+        da_split_track(E, chn == 0, Emin);
         Enext = E;
         return da_pow2(E - ew);
     };
@@ -267,6 +266,7 @@ __global__ void __launch_bounds__(256, 2) conv3_mfma_fwd_kernel(FwdP p) {
     // before this item's epilogue stores); (2) the next item's staging loads are spread over the K-steps, at most one per step;
     // (3) nothing that touches vector memory sits inside a branch: invalid work (no next item, not the last chunk, ragged
     // lanes) is expressed as out-of-range buffer offsets, so hipcc's s_waitcnt vmcnt(N) stay exact instead of collapsing to 0.
+    // (written out rather than da_rsrc(): through the helper hipcc trades v_mov_b32 for v_mov_b64 in the bf16 forward kernels)
     const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)p.wp, 0, (unsigned)(nchunks * NSTEPS * p.NT * (K32 ? 1024 * NP : 256 * EB)), 0x00020000);
     auto wb = [&](int chunk, int step, int nn, int pl = 0) -> Frag {
         if constexpr (SP) return __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rsw, (unsigned)lane * 16u, (unsigned)((((chunk * NSTEPS + step) * p.NT + nt0 + nn) * 2 + pl) * 1024), 0));
@@ -1101,7 +1101,7 @@ __global__ void __launch_bounds__(256, 2) conv3_mfma_wgrad_kernel(WgP p) {
             int c = c4 * 4;
             if (SWZ) c ^= (v & 1) << 4;
             if (idx < TVOX * QY) {
-                if constexpr (BF) reinterpret_cast<uint2*>(ldsY)[idx] = make_uint2(da_bf16x2(preY[it].x, preY[it].y), da_bf16x2(preY[it].z, preY[it].w));   // linear [v][CG] in bf16
+                if constexpr (BF) reinterpret_cast<uint2*>(ldsY)[idx] = make_uint2(da_pack_bf16x2(preY[it].x, preY[it].y), da_pack_bf16x2(preY[it].z, preY[it].w));   // linear [v][CG] in bf16
                 else *reinterpret_cast<float4*>(ldsY + v * CG + c) = preY[it];
             }
         }
@@ -1372,14 +1372,13 @@ __global__ void __launch_bounds__(256, 2) conv3_split_wgrad_kernel(WgP p) {
             const float4 ma = *reinterpret_cast<const float4*>(smax), my = *reinterpret_cast<const float4*>(smax + 4);
             const int ea = da_scale_exp(__int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(fmaxf(fmaxf(ma.x, ma.y), fmaxf(ma.z, ma.w))))));
             const int ey = da_scale_exp(__int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(fmaxf(fmaxf(my.x, my.y), fmaxf(my.z, my.w))))));
-            int E = ea + ey;
-            if (!first_tile) E = min(E, Emin + 40);
+            int E = da_split_cap(ea + ey, first_tile, Emin);
             // keep the accumulators' unit while this tile fits it: a tile up to 8x smaller than the unit allows is staged at the unit's scale
             // (its largest value then lies in [2^11, 2^15) instead of [2^14, 2^15): the per-product bound is unchanged, only the floor below
             // which l underflows rises from 2^-40 to 2^-37 of the tile maximum), so the 60 accumulator multiplies run only when the data's
             // magnitude really moves -- they cost 0.19 of 1.98 ms on the 48 -> 16 layer when done every tile
             if (!first_tile && E >= Eacc && E <= Eacc + 3 && !(p.ablate & 32)) E = Eacc;
-            Emin = first_tile ? E : min(Emin, E);
+            da_split_track(E, first_tile, Emin);
             first_tile = false;
             Enext = E;
             sy = da_pow2(ey); sa = da_pow2(E - ey);
@@ -1395,7 +1394,7 @@ __global__ void __launch_bounds__(256, 2) conv3_split_wgrad_kernel(WgP p) {
                     uint2 h, l; da_split2(preY[it], sy, h, l);
                     reinterpret_cast<uint2*>(ldsY)[idx] = h; reinterpret_cast<uint2*>(ldsY)[idx + TVOX * QY] = l;
                 } else if constexpr (RAWY) reinterpret_cast<uint2*>(ldsY)[idx] = make_uint2(__float_as_uint(preY[it].x), __float_as_uint(preY[it].y));
-                else reinterpret_cast<uint2*>(ldsY)[idx] = make_uint2(da_bf16x2(preY[it].x, preY[it].y), da_bf16x2(preY[it].z, preY[it].w));
+                else reinterpret_cast<uint2*>(ldsY)[idx] = make_uint2(da_pack_bf16x2(preY[it].x, preY[it].y), da_pack_bf16x2(preY[it].z, preY[it].w));
             }
         }
     };

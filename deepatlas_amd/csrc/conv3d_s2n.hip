@@ -40,50 +40,7 @@ constexpr int PLANE_V = HZ * HY * XS;                           // voxel slots p
 constexpr int PLANE_B = PLANE_V * 16;                           // bytes per plane (8 bf16 per voxel)
 constexpr int NSTEPS = 7;                                       // forward K-steps per 8-channel chunk: 4 taps each (28 slots, the last one empty)
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t s2n_rsrc(const void* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, bytes, 0x00020000);
-}
-__device__ __forceinline__ float4 s2n_load4(__amdgpu_buffer_rsrc_t r, unsigned off) {
-    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
-}
-__device__ __forceinline__ void s2n_store4(__amdgpu_buffer_rsrc_t r, unsigned off, f32x4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned, v), r, off, 0, 0);
-}
-__device__ __forceinline__ float s2n_qx1(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true)); }   // lane ^ 1
-__device__ __forceinline__ float s2n_qx2(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true)); }   // lane ^ 2
-// 4 x 4 transpose across a lane quad: in = (4 voxels x 1 channel) per lane (MFMA C layout: row = 4 g + reg), out = (1 voxel x 4 channels)
-__device__ __forceinline__ f32x4 s2n_quad_transpose(f32x4 a, int q) {
-    float t0 = a[0], t1 = a[1], t2 = a[2], t3 = a[3];
-    {
-        const bool odd = (q & 1) != 0;
-        const float s01 = odd ? t0 : t1, s23 = odd ? t2 : t3;
-        const float r01 = s2n_qx1(s01), r23 = s2n_qx1(s23);
-        if (odd) { t0 = r01; t2 = r23; } else { t1 = r01; t3 = r23; }
-    }
-    {
-        const bool hi2 = (q & 2) != 0;
-        const float s02 = hi2 ? t0 : t2, s13 = hi2 ? t1 : t3;
-        const float r02 = s2n_qx2(s02), r13 = s2n_qx2(s13);
-        if (hi2) { t0 = r02; t1 = r13; } else { t2 = r02; t3 = r13; }
-    }
-    return (f32x4){t0, t1, t2, t3};
-}
-__device__ __forceinline__ int s2n_xcd_remap(int bid, int nwg) {        // consecutive tiles on the same XCD (shared halos hit that XCD's L2)
-    const int q = nwg / 8, r = nwg % 8;
-    const int xcd = bid % 8, loc = bid / 8;
-    const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + loc;
-}
-// products of a split multiply, small terms first: (a plane, b plane) = (h,l) (l,h) (h,h)
-#define S2N_PLANE_PAIRS constexpr int kPA[3] = {0, 1, 0}, kPB[3] = {1, 0, 0}
 constexpr int NPLN = 2;                                         // operand planes (h, l)
-// largest |w| of a whole weight tensor (n floats, n % 4 == 0, 16-byte aligned), by one 256-thread workgroup; `red` = 4 floats of LDS
-__device__ __forceinline__ float s2n_tensor_absmax(const float* __restrict__ w, int n, float* red) {
-    float m = 0.f;
-#pragma unroll 4
-    for (int q = threadIdx.x; q < n / 4; q += 256) m = da_absmax4(m, reinterpret_cast<const float4*>(w)[q]);
-    return da_block_max4(m, red, (int)threadIdx.x >> 6, (int)threadIdx.x & 63);
-}
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // halo staging shared by forward and weight gradient: 5 x 9 x 33 voxels x 8 channels (two 16-byte quads per voxel), 12 iterations
@@ -117,18 +74,8 @@ struct HaloMap {
     __device__ __forceinline__ void write(unsigned char* lds, const float4* pre, const float scale) const {
 #pragma unroll
         for (int it = 0; it < HALO_NIT; ++it) {
-            if (ldsq[it] >= 0) {
-                uint2 h, l; da_split2(pre[it], scale, h, l);
-                uint2* p = reinterpret_cast<uint2*>(lds) + ldsq[it];
-                p[0] = h; p[PLANE_B / 8] = l;
-            }
+            if (ldsq[it] >= 0) da_split_store4(pre[it], scale, reinterpret_cast<uint2*>(lds) + ldsq[it], PLANE_B / 8);
         }
-    }
-    __device__ __forceinline__ float absmax(const float4* pre) const {      // (quads past the tile were loaded out of range: zeros)
-        float m = 0.f;
-#pragma unroll
-        for (int it = 0; it < HALO_NIT; ++it) m = da_absmax4(m, pre[it]);
-        return m;
     }
 };
 
@@ -163,11 +110,8 @@ __global__ void __launch_bounds__(256) s2n_pack_fwd_kernel(const float* __restri
         float v[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = (tap < 27 && co < Cout) ? w[((size_t)tap * Cin + ch * 8 + e) * Cout + co] : 0.f;
-        uint2 h0, l0, h1, l1;
-        da_split2(make_float4(v[0], v[1], v[2], v[3]), sc, h0, l0);
-        da_split2(make_float4(v[4], v[5], v[6], v[7]), sc, h1, l1);
-        uint4* o = reinterpret_cast<uint4*>(wp + ((size_t)((ch * NSTEPS + st) * NT + nt) * NPLN) * 512) + lane;
-        o[0] = make_uint4(h0.x, h0.y, h1.x, h1.y); o[64] = make_uint4(l0.x, l0.y, l1.x, l1.y);
+        da_split_store8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), sc,
+                        reinterpret_cast<uint4*>(wp + ((size_t)((ch * NSTEPS + st) * NT + nt) * NPLN) * 512) + lane, 64);
     }
 }
 
@@ -178,20 +122,17 @@ __global__ void __launch_bounds__(256, 2) s2n_fwd_kernel(FwdP p) {
     const int i = lane & 15, g = lane >> 4, q = lane & 3, a4 = (lane & 15) >> 2;
     const int zi = wave >> 1;                                   // output z plane of the tile
     const int nt = blockIdx.y * 2 + (wave & 1);                 // this wave's N-tile
-    // tile of this workgroup: z fastest, then y, then x (z / y neighbours share the most halo and run back to back on one XCD)
-    int t = s2n_xcd_remap(blockIdx.x, gridDim.x);
-    const int tz = t % p.ntz; t /= p.ntz;
-    const int ty = t % p.nty; t /= p.nty;
-    const int tx = t % p.ntx; const int n = t / p.ntx;
+    int n, tz, ty, tx;
+    da_tile_zyx(da_xcd_item_of_block(blockIdx.x, gridDim.x), p.ntz, p.nty, p.ntx, n, tz, ty, tx);
     const int z0 = tz * TZ, y0 = ty * TY, x0 = tx * TX;
     const long long sample = (long long)p.D * p.H * p.W * p.Cin;
-    const __amdgpu_buffer_rsrc_t rs = s2n_rsrc(p.in + (long long)n * sample, (unsigned)(sample * sizeof(float)));
-    const __amdgpu_buffer_rsrc_t rsw = s2n_rsrc(p.wp, (unsigned)((size_t)p.nchunks * NSTEPS * p.NT * NPLN * 1024));
+    const __amdgpu_buffer_rsrc_t rs = da_rsrc(p.in + (long long)n * sample, (unsigned)(sample * sizeof(float)));
+    const __amdgpu_buffer_rsrc_t rsw = da_rsrc(p.wp, (unsigned)((size_t)p.nchunks * NSTEPS * p.NT * NPLN * 1024));
     HaloMap hm; hm.init();
     float4 pre[HALO_NIT];
     auto issue = [&](int ch) {
 #pragma unroll
-        for (int it = 0; it < HALO_NIT; ++it) pre[it] = s2n_load4(rs, hm.offset(it, 2 * z0 - 1, 2 * y0 - 1, 2 * x0 - 1, p.D, p.H, p.W, p.Cin, ch * 8));
+        for (int it = 0; it < HALO_NIT; ++it) pre[it] = da_buf_load4(rs, hm.offset(it, 2 * z0 - 1, 2 * y0 - 1, 2 * x0 - 1, p.D, p.H, p.W, p.Cin, ch * 8));
     };
     // per-lane tap offsets (bytes) of the K-steps: lane group g -> tap 4 s + g
     int aoff[NSTEPS];
@@ -207,21 +148,17 @@ __global__ void __launch_bounds__(256, 2) s2n_fwd_kernel(FwdP p) {
         return __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rsw, (unsigned)lane * 16u, (unsigned)((((ch * NSTEPS + s) * p.NT + nt) * NPLN + pl) * 1024), 0));
     };
     auto ld = [&](int off) -> f16x8 { return *reinterpret_cast<const f16x8*>(lds + off); };
-    // scale bookkeeping (wave-uniform; conv3d_mfma.hip "SP"): the accumulators hold (true sums) x 2^Eacc, chunk ch was staged at 2^(E - wexp[ch]),
-    // E of a later chunk is capped at 40 above the smallest E so far
+    // scale bookkeeping (DaSplitScale): chunk ch was staged at 2^(E - wexp[ch])
     float* smax = reinterpret_cast<float*>(lds + NPLN * PLANE_B);
-    int Eacc = 0, Emin = 0;
+    DaSplitScale sc;
     auto stage = [&](int ch) -> int {                            // publish the tile's largest magnitude, barrier, split + write; returns the chunk's E
-        const float m = da_block_max4(hm.absmax(pre), smax, wave, lane);
+        const float m = da_block_max4(stage_absmax<HALO_NIT>(pre), smax, wave, lane);
         const int ew = p.wexp[ch];
-        int E = da_scale_exp(m) + ew;
-        if (ch != 0) E = min(E, Emin + 40);
-        Emin = (ch == 0) ? E : min(Emin, E);
+        const int E = sc.admit(da_scale_exp(m) + ew, ch == 0);
         hm.write(lds, pre, da_pow2(E - ew));
         return E;
     };
 
-    S2N_PLANE_PAIRS;
     f32x4 acc[TY];
 #pragma unroll
     for (int r = 0; r < TY; ++r) acc[r] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -233,10 +170,9 @@ __global__ void __launch_bounds__(256, 2) s2n_fwd_kernel(FwdP p) {
         const bool more = ch + 1 < p.nchunks;
         if (more) issue(ch + 1);                                 // next chunk's loads fly under this chunk's MFMAs
         {
-            const float f = da_acc_factor(Ecur - Eacc);                // the running sums into this chunk's unit (exact)
+            const float f = sc.enter(Ecur);                      // the running sums into this chunk's unit (exact)
 #pragma unroll
             for (int r = 0; r < TY; ++r) acc[r] = acc[r] * f;
-            Eacc = Ecur;
         }
         f16x8 B[NPLN], Bn[NPLN], A[TY][NPLN], An[TY][NPLN];
 #pragma unroll
@@ -259,7 +195,7 @@ __global__ void __launch_bounds__(256, 2) s2n_fwd_kernel(FwdP p) {
             for (int pr = 0; pr < 3; ++pr)
 #pragma unroll
                 for (int r = 0; r < TY; ++r)
-                    acc[r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[r][kPA[pr]], B[kPB[pr]], acc[r], 0, 0, 0);
+                    acc[r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[r][kSplitPA[pr]], B[kSplitPB[pr]], acc[r], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
             if (s + 1 < NSTEPS) {
 #pragma unroll
@@ -276,7 +212,7 @@ __global__ void __launch_bounds__(256, 2) s2n_fwd_kernel(FwdP p) {
         }
     }
     {
-        const float inv1 = da_pow2(-(Eacc / 2)), inv2 = da_pow2(-(Eacc - Eacc / 2));      // back to the true unit
+        float inv1, inv2; sc.leave(inv1, inv2);                  // back to the true unit
 #pragma unroll
         for (int r = 0; r < TY; ++r) acc[r] = acc[r] * inv1 * inv2;
     }
@@ -286,15 +222,14 @@ __global__ void __launch_bounds__(256, 2) s2n_fwd_kernel(FwdP p) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) bv[j] = (p.bias && co0 + j < p.Cout) ? p.bias[co0 + j] : 0.f;
     const long long osample = (long long)p.Do * p.Ho * p.Wo * p.Cout;
-    const __amdgpu_buffer_rsrc_t ro = s2n_rsrc(p.out + (long long)n * osample, (unsigned)(osample * sizeof(float)));
+    const __amdgpu_buffer_rsrc_t ro = da_rsrc(p.out + (long long)n * osample, (unsigned)(osample * sizeof(float)));
     const int z = z0 + zi, x = x0 + 4 * g + q;
     const bool ok0 = z < p.Do && x < p.Wo && co0 + 3 < p.Cout;
 #pragma unroll
     for (int r = 0; r < TY; ++r) {
-        const f32x4 v = s2n_quad_transpose(acc[r], q);
-        const f32x4 o = {da_act(v[0] + bv[0], p.slope), da_act(v[1] + bv[1], p.slope), da_act(v[2] + bv[2], p.slope), da_act(v[3] + bv[3], p.slope)};
+        const f32x4 o = da_bias_act4(da_quad_transpose(acc[r], q), bv, p.slope);
         const int y = y0 + r;
-        s2n_store4(ro, (ok0 && y < p.Ho) ? (unsigned)((((z * p.Ho + y) * p.Wo + x) * p.Cout + co0) * 4) : 0xFFFFFFFFu, o);
+        da_buf_store4(ro, (ok0 && y < p.Ho) ? (unsigned)((((z * p.Ho + y) * p.Wo + x) * p.Cout + co0) * 4) : 0xFFFFFFFFu, o);
     }
 }
 
@@ -327,7 +262,7 @@ __host__ __device__ inline int s2n_class_base(int c) { int b = 0; for (int k = 0
 // exponent in wexp[0].
 __global__ void __launch_bounds__(256) s2n_pack_dgrad_kernel(const float* __restrict__ w, unsigned short* __restrict__ wp, int* __restrict__ wexp, int Cin, int Cout, int KS, int NTN) {
     __shared__ float red[4];
-    const int ew = da_scale_exp(s2n_tensor_absmax(w, 27 * Cin * Cout, red));
+    const int ew = da_scale_exp(da_tensor_absmax(w, 27 * Cin * Cout, red));
     if (blockIdx.x == 0 && threadIdx.x == 0) wexp[0] = ew;
     const float sc = da_pow2(ew);
     const int units = 27 * KS * NTN * 64;
@@ -344,10 +279,7 @@ __global__ void __launch_bounds__(256) s2n_pack_dgrad_kernel(const float* __rest
             const float* q = w + ((size_t)tap * Cin + ci) * Cout + co0;
             v0 = *reinterpret_cast<const float4*>(q); v1 = *reinterpret_cast<const float4*>(q + 4);
         }
-        uint2 h0, l0, h1, l1;
-        da_split2(v0, sc, h0, l0); da_split2(v1, sc, h1, l1);
-        uint4* o = reinterpret_cast<uint4*>(wp + (size_t)blk * NPLN * 512) + lane;
-        o[0] = make_uint4(h0.x, h0.y, h1.x, h1.y); o[64] = make_uint4(l0.x, l0.y, l1.x, l1.y);
+        da_split_store8(v0, v1, sc, reinterpret_cast<uint4*>(wp + (size_t)blk * NPLN * 512) + lane, 64);
     }
 }
 
@@ -357,10 +289,8 @@ __global__ void __launch_bounds__(256, 2) s2n_dgrad_kernel(DgP p) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int i = lane & 15, g = lane >> 4, q = lane & 3, a4 = (lane & 15) >> 2;
-    int t = s2n_xcd_remap(blockIdx.x, gridDim.x);
-    const int tz = t % p.ntz; t /= p.ntz;
-    const int ty = t % p.nty; t /= p.nty;
-    const int tx = t % p.ntx; const int n = t / p.ntx;
+    int n, tz, ty, tx;
+    da_tile_zyx(da_xcd_item_of_block(blockIdx.x, gridDim.x), p.ntz, p.nty, p.ntx, n, tz, ty, tx);
     const int z0 = tz * TZ, y0 = ty * TY, x0 = tx * TX;
     const int nch = p.Cout / 8;                                  // 8-channel chunks of dY: LDS [plane][chunk][voxel][8]
     const int planeB = nch * GV * 16;
@@ -369,7 +299,7 @@ __global__ void __launch_bounds__(256, 2) s2n_dgrad_kernel(DgP p) {
     int E = 0;
     {
         const long long ysample = (long long)p.Do * p.Ho * p.Wo * p.Cout;
-        const __amdgpu_buffer_rsrc_t ry = s2n_rsrc(p.dy + (long long)n * ysample, (unsigned)(ysample * sizeof(float)));
+        const __amdgpu_buffer_rsrc_t ry = da_rsrc(p.dy + (long long)n * ysample, (unsigned)(ysample * sizeof(float)));
         const int qpv = p.Cout / 4;                              // quads per voxel
         const int total = GV * qpv;
         constexpr int MAXU = 16;                                 // GV * 16 quads / 256 threads
@@ -382,7 +312,7 @@ __global__ void __launch_bounds__(256, 2) s2n_dgrad_kernel(DgP p) {
             const int hx = hv % GX, t2 = hv / GX, hy = t2 % GY, hz = t2 / GY;
             const int z = z0 + hz, y = y0 + hy, x = x0 + hx;
             const bool inb = idx < total && z < p.Do && y < p.Ho && x < p.Wo;
-            v[u] = s2n_load4(ry, inb ? (unsigned)((((z * p.Ho + y) * p.Wo + x) * p.Cout + c4 * 4) * 4) : 0xFFFFFFFFu);
+            v[u] = da_buf_load4(ry, inb ? (unsigned)((((z * p.Ho + y) * p.Wo + x) * p.Cout + c4 * 4) * 4) : 0xFFFFFFFFu);
             li[u] = idx < total ? (((c4 >> 1) * GV + hv) * 2 + (c4 & 1)) : -1;
         }
 #pragma unroll
@@ -393,24 +323,19 @@ __global__ void __launch_bounds__(256, 2) s2n_dgrad_kernel(DgP p) {
         const float sy = da_pow2(ey);
 #pragma unroll
         for (int u = 0; u < MAXU; ++u) {
-            if (li[u] >= 0) {
-                uint2 h, l; da_split2(v[u], sy, h, l);
-                uint2* o = reinterpret_cast<uint2*>(lds) + li[u];
-                o[0] = h; o[planeB / 8] = l;
-            }
+            if (li[u] >= 0) da_split_store4(v[u], sy, reinterpret_cast<uint2*>(lds) + li[u], planeB / 8);
         }
     }
     __syncthreads();
-    const float inv1 = da_pow2(-(E / 2)), inv2 = da_pow2(-(E - E / 2));      // the sums back to the true unit (two exact factors)
-    const __amdgpu_buffer_rsrc_t rsw = s2n_rsrc(p.wp, (unsigned)((size_t)27 * p.KS * NTN * NPLN * 1024));
+    float inv1, inv2; da_unscale_factors(E, inv1, inv2);         // the sums back to the true unit
+    const __amdgpu_buffer_rsrc_t rsw = da_rsrc(p.wp, (unsigned)((size_t)27 * p.KS * NTN * NPLN * 1024));
     const long long xsample = (long long)p.D * p.H * p.W * p.Cin;
-    const __amdgpu_buffer_rsrc_t rx = s2n_rsrc(p.dx + (long long)n * xsample, (unsigned)(xsample * sizeof(float)));
+    const __amdgpu_buffer_rsrc_t rx = da_rsrc(p.dx + (long long)n * xsample, (unsigned)(xsample * sizeof(float)));
     // class groups per wave role (rotated by workgroup so that the 8-tap class does not always sit on the same SIMD)
     const int role = (wave + blockIdx.x) & 3;
     const int ncls = role == 0 ? 1 : (role == 1 ? 3 : 2);
     auto cls_of = [&](int k) -> int { return role == 0 ? 7 : (role == 1 ? (k == 0 ? 6 : (k == 1 ? 4 : 0)) : (role == 2 ? (k == 0 ? 5 : 2) : (k == 0 ? 3 : 1))); };
     auto ld = [&](int off) -> f16x8 { return *reinterpret_cast<const f16x8*>(lds + off); };
-    S2N_PLANE_PAIRS;
 #pragma unroll 1
     for (int kc = 0; kc < ncls; ++kc) {
         const int c = cls_of(kc);
@@ -447,7 +372,7 @@ __global__ void __launch_bounds__(256, 2) s2n_dgrad_kernel(DgP p) {
                         for (int nn = 0; nn < NTN; ++nn)
 #pragma unroll
                             for (int my = 0; my < TY; ++my)
-                                acc[mz * TY + my][nn] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[my][kPA[pr]], B[nn][kPB[pr]], acc[mz * TY + my][nn], 0, 0, 0);
+                                acc[mz * TY + my][nn] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[my][kSplitPA[pr]], B[nn][kSplitPB[pr]], acc[mz * TY + my][nn], 0, 0, 0);
                 }
             }
         }
@@ -462,8 +387,8 @@ __global__ void __launch_bounds__(256, 2) s2n_dgrad_kernel(DgP p) {
                 const bool ok = zin < p.D && yin < p.H && xin < p.W;
 #pragma unroll
                 for (int nn = 0; nn < NTN; ++nn) {
-                    const f32x4 v = s2n_quad_transpose(acc[mz * TY + my][nn] * inv1 * inv2, q);
-                    s2n_store4(rx, ok ? (unsigned)((((zin * p.H + yin) * p.W + xin) * p.Cin + nn * 16 + 4 * a4) * 4) : 0xFFFFFFFFu, v);
+                    const f32x4 v = da_quad_transpose(acc[mz * TY + my][nn] * inv1 * inv2, q);
+                    da_buf_store4(rx, ok ? (unsigned)((((zin * p.H + yin) * p.W + xin) * p.Cin + nn * 16 + 4 * a4) * 4) : 0xFFFFFFFFu, v);
                 }
             }
         }
@@ -529,56 +454,37 @@ __global__ void __launch_bounds__(256, 1) s2n_wgrad_kernel(WgP p) {
     float4 preA[HALO_NIT], preY[4];
     const int yv0 = (int)threadIdx.x >> 3, yq = (int)threadIdx.x & 7;      // dY staging: iteration u covers voxel yv0 + 32 u, cout quad yq (of 8)
     auto issue = [&](int pos) {
-        int t = pos;
-        const int tz = t % p.ntz; t /= p.ntz;
-        const int ty = t % p.nty; t /= p.nty;
-        const int tx = t % p.ntx; const int n = t / p.ntx;
+        int n, tz, ty, tx;
+        da_tile_zyx(pos, p.ntz, p.nty, p.ntx, n, tz, ty, tx);
         const int z0 = tz * TZ, y0 = ty * TY, x0 = tx * TX;
         const long long sample = (long long)p.D * p.H * p.W * p.Cin;
-        const __amdgpu_buffer_rsrc_t rs = s2n_rsrc(p.in + (long long)n * sample, (unsigned)(sample * sizeof(float)));
+        const __amdgpu_buffer_rsrc_t rs = da_rsrc(p.in + (long long)n * sample, (unsigned)(sample * sizeof(float)));
 #pragma unroll
-        for (int it = 0; it < HALO_NIT; ++it) preA[it] = s2n_load4(rs, hm.offset(it, 2 * z0 - 1, 2 * y0 - 1, 2 * x0 - 1, p.D, p.H, p.W, p.Cin, ch * 8));
+        for (int it = 0; it < HALO_NIT; ++it) preA[it] = da_buf_load4(rs, hm.offset(it, 2 * z0 - 1, 2 * y0 - 1, 2 * x0 - 1, p.D, p.H, p.W, p.Cin, ch * 8));
         const long long ysample = (long long)p.Do * p.Ho * p.Wo * p.Cout;
-        const __amdgpu_buffer_rsrc_t ry = s2n_rsrc(p.dy + (long long)n * ysample, (unsigned)(ysample * sizeof(float)));
+        const __amdgpu_buffer_rsrc_t ry = da_rsrc(p.dy + (long long)n * ysample, (unsigned)(ysample * sizeof(float)));
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int v = yv0 + 32 * u;
             const int vx = v & 15, vy = (v >> 4) & 3, vz = v >> 6;
             const int z = z0 + vz, y = y0 + vy, x = x0 + vx, co = cg * 32 + yq * 4;
             const bool inb = z < p.Do && y < p.Ho && x < p.Wo && co < p.Cout;
-            preY[u] = s2n_load4(ry, inb ? (unsigned)((((z * p.Ho + y) * p.Wo + x) * p.Cout + co) * 4) : 0xFFFFFFFFu);
+            preY[u] = da_buf_load4(ry, inb ? (unsigned)((((z * p.Ho + y) * p.Wo + x) * p.Cout + co) * 4) : 0xFFFFFFFFu);
         }
     };
-    // scale bookkeeping (wave-uniform; conv3d_mfma.hip, conv3_split_wgrad_kernel): the accumulators hold (true sums) x 2^Eacc; a tile is staged at
-    // E = x exponent + dY exponent, capped at 40 above the smallest E of this workgroup's walk so far
+    // scale bookkeeping (DaSplitScale, over this workgroup's walk): a tile is staged at E = x exponent + dY exponent
     float* smax = reinterpret_cast<float*>(ldsY + NPLN * YPLANE_B);      // [2][4]
-    int Eacc = 0, Emin = 0, Enext = 0; bool first_tile = true;
+    DaSplitScale sc; int Enext = 0; bool first_tile = true;
     auto write_lds = [&]() {                                     // (starts with the barrier that retires the tile in LDS)
-        float my = 0.f;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) my = da_absmax4(my, preY[u]);
-        const float ma = da_wave_max_nonneg(hm.absmax(preA));
-        my = da_wave_max_nonneg(my);
-        if (lane == 0) { smax[wave] = ma; smax[4 + wave] = my; }
-        __syncthreads();
-        const float4 a4 = *reinterpret_cast<const float4*>(smax), y4 = *reinterpret_cast<const float4*>(smax + 4);
-        const int ea = da_scale_exp(__int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(fmaxf(fmaxf(a4.x, a4.y), fmaxf(a4.z, a4.w))))));
-        const int ey = da_scale_exp(__int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(fmaxf(fmaxf(y4.x, y4.y), fmaxf(y4.z, y4.w))))));
-        int E = ea + ey;
-        if (!first_tile) E = min(E, Emin + 40);
-        Emin = first_tile ? E : min(Emin, E);
+        const DaMax2 m = da_block_max4x2(stage_absmax<HALO_NIT>(preA), stage_absmax<4>(preY), smax, wave, lane);
+        const int ey = da_scale_exp(m.b);
+        Enext = sc.admit(da_scale_exp(m.a) + ey, first_tile);
         first_tile = false;
-        Enext = E;
         const float sy = da_pow2(ey);
-        hm.write(lds, preA, da_pow2(E - ey));
+        hm.write(lds, preA, da_pow2(Enext - ey));
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            uint2 h, l; da_split2(preY[u], sy, h, l);
-            uint2* o = reinterpret_cast<uint2*>(ldsY) + (yv0 + 32 * u) * 8 + yq;
-            o[0] = h; o[YPLANE_B / 8] = l;
-        }
+        for (int u = 0; u < 4; ++u) da_split_store4(preY[u], sy, reinterpret_cast<uint2*>(ldsY) + (yv0 + 32 * u) * 8 + yq, YPLANE_B / 8);
     };
-    S2N_PLANE_PAIRS;
     const int slab = blockIdx.x;
     const int cnt = (p.ntiles > slab) ? (p.ntiles - slab + p.nslabs - 1) / p.nslabs : 0;
     if (cnt > 0) { issue(slab); write_lds(); }
@@ -588,10 +494,9 @@ __global__ void __launch_bounds__(256, 1) s2n_wgrad_kernel(WgP p) {
         const bool more = k + 1 < cnt;
         if (more) issue(slab + (k + 1) * p.nslabs);              // next tile's global loads fly during this tile's MFMAs
         {
-            const float f = da_acc_factor(Enext - Eacc);               // the running sums into this tile's unit (exact)
+            const float f = sc.enter(Enext);                     // the running sums into this tile's unit (exact)
 #pragma unroll
             for (int s = 0; s < WG_SLOTS; ++s) { acc[s][0] = acc[s][0] * f; acc[s][1] = acc[s][1] * f; }
-            Eacc = Enext;
         }
         const F3 Y0 = loadY(0), Y1 = loadY(1);
         F3 F = loadF(0), Fn;
@@ -600,8 +505,8 @@ __global__ void __launch_bounds__(256, 1) s2n_wgrad_kernel(WgP p) {
             if (s + 1 < WG_SLOTS) Fn = loadF(s + 1);
 #pragma unroll
             for (int pr = 0; pr < 3; ++pr) {
-                acc[s][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(F.p[kPA[pr]], Y0.p[kPB[pr]], acc[s][0], 0, 0, 0);
-                acc[s][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(F.p[kPA[pr]], Y1.p[kPB[pr]], acc[s][1], 0, 0, 0);
+                acc[s][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(F.p[kSplitPA[pr]], Y0.p[kSplitPB[pr]], acc[s][0], 0, 0, 0);
+                acc[s][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(F.p[kSplitPA[pr]], Y1.p[kSplitPB[pr]], acc[s][1], 0, 0, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
             if (s + 1 < WG_SLOTS) F = Fn;
@@ -612,7 +517,7 @@ __global__ void __launch_bounds__(256, 1) s2n_wgrad_kernel(WgP p) {
         }
     }
     {
-        const float inv1 = da_pow2(-(Eacc / 2)), inv2 = da_pow2(-(Eacc - Eacc / 2));      // back to the true unit
+        float inv1, inv2; sc.leave(inv1, inv2);                  // back to the true unit
 #pragma unroll
         for (int s = 0; s < WG_SLOTS; ++s) { acc[s][0] = acc[s][0] * inv1 * inv2; acc[s][1] = acc[s][1] * inv1 * inv2; }
     }

@@ -34,14 +34,6 @@ namespace {
 
 constexpr int TY = 8, TX = 16, HY = TY + 2, HX = TX + 2;
 
-// bijective XCD-aware remap: consecutive tiles land on the same XCD (shared halos hit that XCD's L2)
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg / 8, r = nwg % 8;
-    const int xcd = bid % 8, loc = bid / 8;
-    const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + loc;
-}
-
 // Staging of an (HZ x HY x HX) halo tile of CK channels into LDS as [voxel][CK]; out-of-volume voxels are zero
 // (padding 1).  Split T14-style: stage_load issues the global loads into registers (one work item AHEAD, so their
 // latency hides under the current item's MFMAs), stage_write drops them into LDS after the barrier that retires the
@@ -52,22 +44,9 @@ template <int CK, int HZ> struct StageGeom {
     static constexpr int NIT = (TOTAL + 255) / 256;
 };
 
-// Global loads go through a buffer descriptor over ONE sample's tensor: an out-of-volume voxel gets byte offset
-// 0xFFFFFFFF, which the hardware range check turns into zeros -- no exec-mask branch per load, so the NIT loads issue
-// back to back.  The (hz, hy, hx) decomposition of the flat index is done once and then stepped by 256/Q voxels per
+// Global loads go through a buffer descriptor (da_rsrc, common.h) over ONE sample's tensor, out-of-volume voxels at byte offset
+// 0xFFFFFFFF.  The (hz, hy, hx) decomposition of the flat index is done once and then stepped by 256/Q voxels per
 // iteration with carries (two compares) instead of two magic-number divisions per iteration.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t da_rsrc(const float* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, bytes, 0x00020000);
-}
-__device__ __forceinline__ unsigned da_bf16x2(float lo, float hi) {      // round-to-nearest-even, ONE v_cvt_pk_bf16_f32 for the pair
-    typedef float f32x2_t __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-    const f32x2_t v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-}
-__device__ __forceinline__ float4 da_buf_load4(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
-    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0));
-}
 // HB: the tensor is stored as bf16 (bf16 activation storage, common.h): a channel quad is 8 bytes and is widened to fp32 on arrival, so
 // everything behind the load (prologue arithmetic, the conversion into the bf16 LDS image -- exact for these values) is shared with the
 // fp32-storage kernels.  Only instantiated for the bf16 matrix mode (BF && !SP).
@@ -84,7 +63,7 @@ template <bool HB, bool RAW = false> __device__ __forceinline__ float4 da_buf_lo
 }
 // buffer descriptor over sample n of a tensor with `sample` elements per sample
 template <bool HB> __device__ __forceinline__ __amdgpu_buffer_rsrc_t da_rsrc_n(const float* base, long long n, long long sample) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(reinterpret_cast<const char*>(base) + n * sample * (long long)HbEl<HB>::ES), 0, (unsigned)(sample * HbEl<HB>::ES), 0x00020000);
+    return da_rsrc(reinterpret_cast<const char*>(base) + n * sample * (long long)HbEl<HB>::ES, (unsigned)(sample * HbEl<HB>::ES));
 }
 
 template <int CK, int HZ, int IT0 = 0, int IT1 = StageGeom<CK, HZ>::NIT, bool HB = false, bool RAW = false>
@@ -170,7 +149,7 @@ __device__ __forceinline__ void stage_write_pro(float* __restrict__ lds, const f
             float4 v;
             v.x = ok ? da_act01(t.x * sc.x + sf.x, slope) : 0.f; v.y = ok ? da_act01(t.y * sc.y + sf.y, slope) : 0.f;
             v.z = ok ? da_act01(t.z * sc.z + sf.z, slope) : 0.f; v.w = ok ? da_act01(t.w * sc.w + sf.w, slope) : 0.f;
-            if constexpr (BF) reinterpret_cast<uint2*>(lds)[idx] = make_uint2(da_bf16x2(v.x, v.y), da_bf16x2(v.z, v.w));
+            if constexpr (BF) reinterpret_cast<uint2*>(lds)[idx] = make_uint2(da_pack_bf16x2(v.x, v.y), da_pack_bf16x2(v.z, v.w));
             else reinterpret_cast<float4*>(lds)[idx] = v;
         }
     }
@@ -205,18 +184,10 @@ __device__ __forceinline__ void stage_write(float* __restrict__ lds, const float
                 reinterpret_cast<uint2*>(lds)[idx] = make_uint2(__float_as_uint(pre[it - IT0].x), __float_as_uint(pre[it - IT0].y));
             } else if constexpr (BF) {
                 const float4 v = pre[it - IT0];
-                reinterpret_cast<uint2*>(lds)[idx] = make_uint2(da_bf16x2(v.x, v.y), da_bf16x2(v.z, v.w));
+                reinterpret_cast<uint2*>(lds)[idx] = make_uint2(da_pack_bf16x2(v.x, v.y), da_pack_bf16x2(v.z, v.w));
             } else reinterpret_cast<float4*>(lds)[idx] = pre[it - IT0];
         }
     }
-}
-// largest magnitude among the quads a thread parks for one tile (iterations past the tile hold zeros: their offsets were out of range)
-template <int NITS>
-__device__ __forceinline__ float stage_absmax(const float4* pre) {
-    float m = 0.f;
-#pragma unroll
-    for (int it = 0; it < NITS; ++it) m = da_absmax4(m, pre[it]);
-    return m;
 }
 
 // The same staging loads, one at a time: a cursor that carries the incremental (hz, hy, hx) decomposition so the loads of the
@@ -300,9 +271,6 @@ template <int CK, int HZ, bool VO = true> struct StageMap {      // VO = false: 
         return inb ? (unsigned)(((z * t.H + y) * t.W + x) * t.Cs4 + t.cofs4) : 0xFFFFFFFFu;
     }
 };
-__device__ __forceinline__ void da_buf_store4(__amdgpu_buffer_rsrc_t r, unsigned byte_off, f32x4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned, v), r, byte_off, 0, 0);
-}
 template <bool HB> __device__ __forceinline__ void da_buf_storeq(__amdgpu_buffer_rsrc_t r, unsigned byte_off, f32x4 v) {
     if constexpr (HB) {
         typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
@@ -312,10 +280,6 @@ template <bool HB> __device__ __forceinline__ void da_buf_storeq(__amdgpu_buffer
 }
 template <bool B> struct BoolC { static constexpr bool value = B; };
 template <int V> struct IntC { static constexpr int value = V; };
-// lane ^ 1 / lane ^ 2 exchanges inside a lane quad as DPP quad_perm moves (VALU, no trip through the LDS crossbar like __shfl_xor)
-__device__ __forceinline__ float da_quad_xor1(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true)); }   // quad_perm [1,0,3,2]
-__device__ __forceinline__ float da_quad_xor2(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true)); }   // quad_perm [2,3,0,1]
-
 
 // ---------------------------------------------------------------------------------------------------
 // XCD-aware tile walk.  Workgroup b lands on XCD b % 8 (round-robin dispatch) and each XCD has its own 4 MiB L2, so the tiles

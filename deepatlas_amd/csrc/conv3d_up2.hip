@@ -33,40 +33,6 @@ constexpr int SV = SZ * SY * SX;                                // 432 voxels
 constexpr int SPLANE_B = SV * 16;                               // bytes per plane of one 8-channel chunk
 constexpr int S_NIT = (SV * 2 + 255) / 256;                     // 4 staging iterations (two 16-byte quads per voxel)
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t up_rsrc(const void* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, bytes, 0x00020000);
-}
-__device__ __forceinline__ float4 up_load4(__amdgpu_buffer_rsrc_t r, unsigned off) {
-    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
-}
-__device__ __forceinline__ void up_store4(__amdgpu_buffer_rsrc_t r, unsigned off, f32x4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned, v), r, off, 0, 0);
-}
-__device__ __forceinline__ float up_qx1(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true)); }
-__device__ __forceinline__ float up_qx2(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true)); }
-__device__ __forceinline__ f32x4 up_quad_transpose(f32x4 a, int q) {      // (4 voxels x 1 channel) per lane -> (1 voxel x 4 channels)
-    float t0 = a[0], t1 = a[1], t2 = a[2], t3 = a[3];
-    {
-        const bool odd = (q & 1) != 0;
-        const float s01 = odd ? t0 : t1, s23 = odd ? t2 : t3;
-        const float r01 = up_qx1(s01), r23 = up_qx1(s23);
-        if (odd) { t0 = r01; t2 = r23; } else { t1 = r01; t3 = r23; }
-    }
-    {
-        const bool hi2 = (q & 2) != 0;
-        const float s02 = hi2 ? t0 : t2, s13 = hi2 ? t1 : t3;
-        const float r02 = up_qx2(s02), r13 = up_qx2(s13);
-        if (hi2) { t0 = r02; t1 = r13; } else { t2 = r02; t3 = r13; }
-    }
-    return (f32x4){t0, t1, t2, t3};
-}
-__device__ __forceinline__ int up_xcd_remap(int bid, int nwg) {
-    const int q = nwg / 8, r = nwg % 8;
-    const int xcd = bid % 8, loc = bid / 8;
-    const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + loc;
-}
-#define UP_PLANE_PAIRS constexpr int kPA[3] = {0, 1, 0}, kPB[3] = {1, 0, 0}      // split products, small terms first: (h,l) (l,h) (h,h)
 constexpr int NPLN = 2;                                         // operand planes (h, l)
 
 // per axis: original taps that feed coarse tap j of parity p (forward / weight gradient)
@@ -103,18 +69,8 @@ struct SMap {
     __device__ __forceinline__ void write(unsigned char* lds, const float4* pre, const float scale) const {
 #pragma unroll
         for (int it = 0; it < S_NIT; ++it) {
-            if (hv[it] >= 0) {
-                uint2 h, l; da_split2(pre[it], scale, h, l);
-                uint2* o = reinterpret_cast<uint2*>(lds) + hv[it] * 2 + c4;
-                o[0] = h; o[SPLANE_B / 8] = l;
-            }
+            if (hv[it] >= 0) da_split_store4(pre[it], scale, reinterpret_cast<uint2*>(lds) + hv[it] * 2 + c4, SPLANE_B / 8);
         }
-    }
-    __device__ __forceinline__ float absmax(const float4* pre) const {      // (quads past the tile were loaded out of range: zeros)
-        float m = 0.f;
-#pragma unroll
-        for (int it = 0; it < S_NIT; ++it) m = da_absmax4(m, pre[it]);
-        return m;
     }
 };
 
@@ -165,11 +121,7 @@ __global__ void __launch_bounds__(256) up_pack_fwd_kernel(const float* __restric
             for (int j = 0; j < 8; ++j) { const int a = j >> 2, b = (j >> 1) & 1, c = j & 1; if (a < nz && b < ny && c < nx) acc += (double)t[j]; }
             v[e] = (ci < Cin && co < Cout) ? (float)acc : 0.f;
         }
-        uint2 h0, l0, h1, l1;
-        da_split2(make_float4(v[0], v[1], v[2], v[3]), sc, h0, l0);
-        da_split2(make_float4(v[4], v[5], v[6], v[7]), sc, h1, l1);
-        uint4* o = reinterpret_cast<uint4*>(wp + ((size_t)(((ch * 8 + cls) * 2 + s) * NT + nt) * NPLN) * 512) + lane;
-        o[0] = make_uint4(h0.x, h0.y, h1.x, h1.y); o[64] = make_uint4(l0.x, l0.y, l1.x, l1.y);
+        da_split_store8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), sc, reinterpret_cast<uint4*>(wp + ((size_t)(((ch * 8 + cls) * 2 + s) * NT + nt) * NPLN) * 512) + lane, 64);
     }
 }
 
@@ -180,15 +132,13 @@ __global__ void __launch_bounds__(256, 2) up_fwd_kernel(FwdP p) {
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int i = lane & 15, g = lane >> 4, q = lane & 3, a4 = (lane & 15) >> 2;
     const int nt0 = blockIdx.y * NT;
-    int t = up_xcd_remap(blockIdx.x, gridDim.x);
-    const int tz = t % p.ntz; t /= p.ntz;
-    const int ty = t % p.nty; t /= p.nty;
-    const int tx = t % p.ntx; const int n = t / p.ntx;
+    int n, tz, ty, tx;
+    da_tile_zyx(da_xcd_item_of_block(blockIdx.x, gridDim.x), p.ntz, p.nty, p.ntx, n, tz, ty, tx);
     const int z0 = tz * CTZ, y0 = ty * CTY, x0 = tx * CTX;
     const long long vox = (long long)p.Dc * p.Hc * p.Wc;
-    const __amdgpu_buffer_rsrc_t r1 = up_rsrc(p.s1 + (long long)n * vox * p.C1, (unsigned)(vox * p.C1 * sizeof(float)));
-    const __amdgpu_buffer_rsrc_t r2 = up_rsrc(p.C2 ? p.s2 + (long long)n * vox * p.C2 : p.s1, (unsigned)(p.C2 ? vox * p.C2 * sizeof(float) : 0));
-    const __amdgpu_buffer_rsrc_t rsw = up_rsrc(p.wp, (unsigned)((size_t)p.nchunks * 16 * p.NTall * NPLN * 1024));
+    const __amdgpu_buffer_rsrc_t r1 = da_rsrc(p.s1 + (long long)n * vox * p.C1, (unsigned)(vox * p.C1 * sizeof(float)));
+    const __amdgpu_buffer_rsrc_t r2 = da_rsrc(p.C2 ? p.s2 + (long long)n * vox * p.C2 : p.s1, (unsigned)(p.C2 ? vox * p.C2 * sizeof(float) : 0));
+    const __amdgpu_buffer_rsrc_t rsw = da_rsrc(p.wp, (unsigned)((size_t)p.nchunks * 16 * p.NTall * NPLN * 1024));
     SMap sm; sm.init();
     float4 pre[S_NIT];
     auto issue = [&](int ch) {
@@ -196,22 +146,19 @@ __global__ void __launch_bounds__(256, 2) up_fwd_kernel(FwdP p) {
         const bool first = cb < p.C1;
 #pragma unroll
         for (int it = 0; it < S_NIT; ++it)
-            pre[it] = up_load4(first ? r1 : r2, sm.offset(it, z0 - 1, y0 - 1, x0 - 1, p.Dc, p.Hc, p.Wc, first ? p.C1 : p.C2, first ? cb : cb - p.C1));
+            pre[it] = da_buf_load4(first ? r1 : r2, sm.offset(it, z0 - 1, y0 - 1, x0 - 1, p.Dc, p.Hc, p.Wc, first ? p.C1 : p.C2, first ? cb : cb - p.C1));
     };
     auto ld = [&](int off) -> f16x8 { return *reinterpret_cast<const f16x8*>(lds + off); };
-    // scale bookkeeping (wave-uniform; conv3d_mfma.hip "SP")
+    // scale bookkeeping (DaSplitScale)
     float* smax = reinterpret_cast<float*>(lds + NPLN * SPLANE_B);
-    int Eacc = 0, Emin = 0;
+    DaSplitScale sc;
     auto stage = [&](int ch) -> int {                            // publish the tile's largest magnitude, barrier, split + write; returns the chunk's E
-        const float m = da_block_max4(sm.absmax(pre), smax, wave, lane);
+        const float m = da_block_max4(stage_absmax<S_NIT>(pre), smax, wave, lane);
         const int ew = p.wexp[ch];
-        int E = da_scale_exp(m) + ew;
-        if (ch != 0) E = min(E, Emin + 40);
-        Emin = (ch == 0) ? E : min(Emin, E);
+        const int E = sc.admit(da_scale_exp(m) + ew, ch == 0);
         sm.write(lds, pre, da_pow2(E - ew));
         return E;
     };
-    UP_PLANE_PAIRS;
     f32x4 acc[2][CTZ * CTY][NT];
 #pragma unroll
     for (int c = 0; c < 2; ++c)
@@ -227,14 +174,13 @@ __global__ void __launch_bounds__(256, 2) up_fwd_kernel(FwdP p) {
         const bool more = ch + 1 < p.nchunks;
         if (more) issue(ch + 1);
         {
-            const float f = da_acc_factor(Ecur - Eacc);                // the running sums into this chunk's unit (exact)
+            const float f = sc.enter(Ecur);                      // the running sums into this chunk's unit (exact)
 #pragma unroll
             for (int c = 0; c < 2; ++c)
 #pragma unroll
                 for (int m = 0; m < CTZ * CTY; ++m)
 #pragma unroll
                     for (int nn = 0; nn < NT; ++nn) acc[c][m][nn] = acc[c][m][nn] * f;
-            Eacc = Ecur;
         }
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
@@ -264,7 +210,7 @@ __global__ void __launch_bounds__(256, 2) up_fwd_kernel(FwdP p) {
                         for (int nn = 0; nn < NT; ++nn)
 #pragma unroll
                             for (int my = 0; my < CTY; ++my)
-                                acc[c][mz * CTY + my][nn] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[my][kPA[pr]], B[nn][kPB[pr]], acc[c][mz * CTY + my][nn], 0, 0, 0);
+                                acc[c][mz * CTY + my][nn] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[my][kSplitPA[pr]], B[nn][kSplitPB[pr]], acc[c][mz * CTY + my][nn], 0, 0, 0);
                 }
             }
         }
@@ -273,11 +219,11 @@ __global__ void __launch_bounds__(256, 2) up_fwd_kernel(FwdP p) {
             __syncthreads();
         }
     }
-    const float inv1 = da_pow2(-(Eacc / 2)), inv2 = da_pow2(-(Eacc - Eacc / 2));      // the sums back to the true unit (two exact factors)
+    float inv1, inv2; sc.leave(inv1, inv2);                      // the sums back to the true unit
     // epilogue: fine voxel (2 (z0 + mz) + pz, 2 (y0 + my) + py, 2 (x0 + 4 g + q) + px), couts 16 (nt0 + nn) + 4 a4 .. + 3
     const int Df = 2 * p.Dc, Hf = 2 * p.Hc, Wf = 2 * p.Wc;
     const long long osample = (long long)Df * Hf * Wf * p.Cout;
-    const __amdgpu_buffer_rsrc_t ro = up_rsrc(p.out + (long long)n * osample, (unsigned)(osample * sizeof(float)));
+    const __amdgpu_buffer_rsrc_t ro = da_rsrc(p.out + (long long)n * osample, (unsigned)(osample * sizeof(float)));
     const int xc = x0 + 4 * g + q;
 #pragma unroll
     for (int nn = 0; nn < NT; ++nn) {
@@ -294,11 +240,10 @@ __global__ void __launch_bounds__(256, 2) up_fwd_kernel(FwdP p) {
             for (int mz = 0; mz < CTZ; ++mz)
 #pragma unroll
                 for (int my = 0; my < CTY; ++my) {
-                    const f32x4 v = up_quad_transpose(acc[c][mz * CTY + my][nn] * inv1 * inv2, q);
-                    const f32x4 o = {da_act(v[0] + bv[0], p.slope), da_act(v[1] + bv[1], p.slope), da_act(v[2] + bv[2], p.slope), da_act(v[3] + bv[3], p.slope)};
+                    const f32x4 o = da_bias_act4(da_quad_transpose(acc[c][mz * CTY + my][nn] * inv1 * inv2, q), bv, p.slope);
                     const int zc = z0 + mz, yc = y0 + my;
                     const bool ok = cok && zc < p.Dc && yc < p.Hc;
-                    up_store4(ro, ok ? (unsigned)(((((2 * zc + pz) * Hf + 2 * yc + py) * Wf + 2 * xc + px) * p.Cout + co0) * 4) : 0xFFFFFFFFu, o);
+                    da_buf_store4(ro, ok ? (unsigned)(((((2 * zc + pz) * Hf + 2 * yc + py) * Wf + 2 * xc + px) * p.Cout + co0) * 4) : 0xFFFFFFFFu, o);
                 }
         }
     }
@@ -379,11 +324,7 @@ __global__ void __launch_bounds__(256) up_pack_dgrad_kernel(const float* __restr
         float v[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = (float)acc[e];
-        uint2 h0, l0, h1, l1;
-        da_split2(make_float4(v[0], v[1], v[2], v[3]), sc, h0, l0);
-        da_split2(make_float4(v[4], v[5], v[6], v[7]), sc, h1, l1);
-        uint4* o = reinterpret_cast<uint4*>(wp + ((size_t)((ch * 16 + st) * NTN + nt) * NPLN) * 512) + lane;
-        o[0] = make_uint4(h0.x, h0.y, h1.x, h1.y); o[64] = make_uint4(l0.x, l0.y, l1.x, l1.y);
+        da_split_store8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), sc, reinterpret_cast<uint4*>(wp + ((size_t)((ch * 16 + st) * NTN + nt) * NPLN) * 512) + lane, 64);
     }
 }
 
@@ -395,15 +336,13 @@ __global__ void __launch_bounds__(256, 1) up_dgrad_kernel(DgP p) {
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int i = lane & 15, g = lane >> 4, q = lane & 3, a4 = (lane & 15) >> 2;
     const int nt = wave % NTN, mg = wave / NTN;
-    int t = up_xcd_remap(blockIdx.x, gridDim.x);
-    const int tz = t % p.ntz; t /= p.ntz;
-    const int ty = t % p.nty; t /= p.nty;
-    const int tx = t % p.ntx; const int n = t / p.ntx;
+    int n, tz, ty, tx;
+    da_tile_zyx(da_xcd_item_of_block(blockIdx.x, gridDim.x), p.ntz, p.nty, p.ntx, n, tz, ty, tx);
     const int z0 = tz * CTZ, y0 = ty * CTY, x0 = tx * CTX;
     const int Df = 2 * p.Dc, Hf = 2 * p.Hc, Wf = 2 * p.Wc;
     const long long ysample = (long long)Df * Hf * Wf * p.Cout;
-    const __amdgpu_buffer_rsrc_t ry = up_rsrc(p.dy + (long long)n * ysample, (unsigned)(ysample * sizeof(float)));
-    const __amdgpu_buffer_rsrc_t rsw = up_rsrc(p.wp, (unsigned)((size_t)p.nchunks * 16 * NTN * NPLN * 1024));
+    const __amdgpu_buffer_rsrc_t ry = da_rsrc(p.dy + (long long)n * ysample, (unsigned)(ysample * sizeof(float)));
+    const __amdgpu_buffer_rsrc_t rsw = da_rsrc(p.wp, (unsigned)((size_t)p.nchunks * 16 * NTN * NPLN * 1024));
     // staging map: iteration it covers halo voxel v = (tid + 256 it) / 2 = (hz, hy, hx), quad tid & 1; LDS slot de-interleaves x by parity
     const int c4 = (int)threadIdx.x & 1;
     unsigned pk[F_NIT]; int slot[F_NIT];
@@ -425,11 +364,11 @@ __global__ void __launch_bounds__(256, 1) up_dgrad_kernel(DgP p) {
             const int hz = (int)(pk[it] >> 16), hy = (int)((pk[it] >> 8) & 255u), hx = (int)(pk[it] & 255u);
             const int z = 2 * z0 - 1 + hz, y = 2 * y0 - 1 + hy, x = 2 * x0 - 1 + hx;
             const bool inb = hz != 0xFFFF && (unsigned)z < (unsigned)Df && (unsigned)y < (unsigned)Hf && (unsigned)x < (unsigned)Wf;
-            const float4 v = up_load4(ry, inb ? (unsigned)((((z * Hf + y) * Wf + x) * p.Cout + ch * 8 + c4 * 4) * 4) : 0xFFFFFFFFu);
+            const float4 v = da_buf_load4(ry, inb ? (unsigned)((((z * Hf + y) * Wf + x) * p.Cout + ch * 8 + c4 * 4) * 4) : 0xFFFFFFFFu);
             if (it < FH) preA[it < FH ? it : 0] = v; else preB[it >= FH ? it - FH : 0] = v;
         }
     };
-    // scale bookkeeping (wave-uniform; conv3d_mfma.hip "SP"): chunk = 8 output channels of dY
+    // scale bookkeeping: chunk = 8 output channels of dY.  DaSplitScale's rule on two plain ints: with the struct hipcc spills a fifth SGPR here.
     float* smax = reinterpret_cast<float*>(lds + NPLN * FPLANE_B);
     int Eacc = 0, Emin = 0;
     auto stage = [&](int ch) -> int {                            // publish the tile's largest magnitude, barrier, split + write; returns the chunk's E
@@ -438,22 +377,15 @@ __global__ void __launch_bounds__(256, 1) up_dgrad_kernel(DgP p) {
         for (int it = 0; it < FH; ++it) { m = da_absmax4(m, preA[it]); m = da_absmax4(m, preB[it]); }
         m = da_block_max4(m, smax, wave, lane);
         const int ew = p.wexp[ch];
-        int E = da_scale_exp(m) + ew;
-        if (ch != 0) E = min(E, Emin + 40);
-        Emin = (ch == 0) ? E : min(Emin, E);
+        const int E = da_split_admit(da_scale_exp(m) + ew, ch == 0, Emin);
         const float sy = da_pow2(E - ew);
 #pragma unroll
         for (int it = 0; it < F_NIT; ++it) {
-            if (slot[it] >= 0) {
-                uint2 h, l; da_split2(it < FH ? preA[it < FH ? it : 0] : preB[it >= FH ? it - FH : 0], sy, h, l);
-                uint2* o = reinterpret_cast<uint2*>(lds) + slot[it];
-                o[0] = h; o[FPLANE_B / 8] = l;
-            }
+            if (slot[it] >= 0) da_split_store4(it < FH ? preA[it < FH ? it : 0] : preB[it >= FH ? it - FH : 0], sy, reinterpret_cast<uint2*>(lds) + slot[it], FPLANE_B / 8);
         }
         return E;
     };
     auto ld = [&](int off) -> f16x8 { return *reinterpret_cast<const f16x8*>(lds + off); };
-    UP_PLANE_PAIRS;
     f32x4 acc[MPW];
 #pragma unroll
     for (int m = 0; m < MPW; ++m) acc[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -465,7 +397,7 @@ __global__ void __launch_bounds__(256, 1) up_dgrad_kernel(DgP p) {
         const bool more = ch + 1 < p.nchunks;
         if (more) issue(ch + 1);
         {
-            const float f = da_acc_factor(Ecur - Eacc);                // the running sums into this chunk's unit (exact)
+            const float f = da_acc_factor(Ecur - Eacc);          // the running sums into this chunk's unit (exact)
 #pragma unroll
             for (int m = 0; m < MPW; ++m) acc[m] = acc[m] * f;
             Eacc = Ecur;
@@ -491,27 +423,27 @@ __global__ void __launch_bounds__(256, 1) up_dgrad_kernel(DgP p) {
             for (int pr = 0; pr < 3; ++pr)
 #pragma unroll
                 for (int m = 0; m < MPW; ++m)
-                    acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[m][kPA[pr]], B[kPB[pr]], acc[m], 0, 0, 0);
+                    acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[m][kSplitPA[pr]], B[kSplitPB[pr]], acc[m], 0, 0, 0);
         }
         if (more) {
             Ecur = stage(ch + 1);                                // (its barrier: every wave is done reading this chunk's tile)
             __syncthreads();
         }
     }
-    const float inv1 = da_pow2(-(Eacc / 2)), inv2 = da_pow2(-(Eacc - Eacc / 2));      // the sums back to the true unit (two exact factors)
+    float inv1, inv2; da_unscale_factors(Eacc, inv1, inv2);      // the sums back to the true unit
     // stores: coarse voxel (z0 + mz, y0 + my, x0 + 4 g + q), input channels 16 nt + 4 a4 .. + 3 of dx1 | dx2
     const int ci0 = nt * 16 + 4 * a4;
     const bool first = ci0 < p.C1;
     const int Cd = first ? p.C1 : p.C2, cd = first ? ci0 : ci0 - p.C1;
     const long long vox = (long long)p.Dc * p.Hc * p.Wc;
-    const __amdgpu_buffer_rsrc_t rd = up_rsrc((first ? p.dx1 : p.dx2) + (long long)n * vox * Cd, (unsigned)(vox * Cd * sizeof(float)));
+    const __amdgpu_buffer_rsrc_t rd = da_rsrc((first ? p.dx1 : p.dx2) + (long long)n * vox * Cd, (unsigned)(vox * Cd * sizeof(float)));
     const int xc = x0 + 4 * g + q;
     const bool cok = ci0 + 3 < p.C1 + p.C2 && xc < p.Wc;
 #pragma unroll
     for (int m = 0; m < MPW; ++m) {
         const int mt = mg * MPW + m, zc = z0 + mt / CTY, yc = y0 + mt % CTY;
-        const f32x4 v = up_quad_transpose(acc[m] * inv1 * inv2, q);
-        up_store4(rd, (cok && zc < p.Dc && yc < p.Hc) ? (unsigned)((((zc * p.Hc + yc) * p.Wc + xc) * Cd + cd) * 4) : 0xFFFFFFFFu, v);
+        const f32x4 v = da_quad_transpose(acc[m] * inv1 * inv2, q);
+        da_buf_store4(rd, (cok && zc < p.Dc && yc < p.Hc) ? (unsigned)((((zc * p.Hc + yc) * p.Wc + xc) * Cd + cd) * 4) : 0xFFFFFFFFu, v);
     }
 }
 
@@ -570,55 +502,37 @@ __global__ void __launch_bounds__(256, 2) up_wgrad_kernel(WgP p) {
     const int yv0 = (int)threadIdx.x >> 3, yq = (int)threadIdx.x & 7;
     const int Df = 2 * p.Dc, Hf = 2 * p.Hc, Wf = 2 * p.Wc;
     auto issue = [&](int pos) {
-        int t = pos;
-        const int tz = t % p.ntz; t /= p.ntz;
-        const int ty = t % p.nty; t /= p.nty;
-        const int tx = t % p.ntx; const int n = t / p.ntx;
+        int n, tz, ty, tx;
+        da_tile_zyx(pos, p.ntz, p.nty, p.ntx, n, tz, ty, tx);
         const int z0 = tz * CTZ, y0 = ty * CTY, x0 = tx * CTX;
         const long long vox = (long long)p.Dc * p.Hc * p.Wc;
-        const __amdgpu_buffer_rsrc_t rs = up_rsrc(src + (long long)n * vox * Cs, (unsigned)(vox * Cs * sizeof(float)));
+        const __amdgpu_buffer_rsrc_t rs = da_rsrc(src + (long long)n * vox * Cs, (unsigned)(vox * Cs * sizeof(float)));
 #pragma unroll
-        for (int it = 0; it < S_NIT; ++it) preA[it] = up_load4(rs, sm.offset(it, z0 - 1, y0 - 1, x0 - 1, p.Dc, p.Hc, p.Wc, Cs, choff));
+        for (int it = 0; it < S_NIT; ++it) preA[it] = da_buf_load4(rs, sm.offset(it, z0 - 1, y0 - 1, x0 - 1, p.Dc, p.Hc, p.Wc, Cs, choff));
         const long long ysample = (long long)Df * Hf * Wf * p.Cout;
-        const __amdgpu_buffer_rsrc_t ry = up_rsrc(p.dy + (long long)n * ysample, (unsigned)(ysample * sizeof(float)));
+        const __amdgpu_buffer_rsrc_t ry = da_rsrc(p.dy + (long long)n * ysample, (unsigned)(ysample * sizeof(float)));
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int v = yv0 + 32 * u;
             const int vx = v & 15, vy = (v >> 4) & 3, vz = v >> 6;
             const int zc = z0 + vz, yc = y0 + vy, xc = x0 + vx, co = yq * 4;
             const bool inb = zc < p.Dc && yc < p.Hc && xc < p.Wc && co < p.Cout;
-            preY[u] = up_load4(ry, inb ? (unsigned)(((((2 * zc + pz) * Hf + 2 * yc + py) * Wf + 2 * xc + px) * p.Cout + co) * 4) : 0xFFFFFFFFu);
+            preY[u] = da_buf_load4(ry, inb ? (unsigned)(((((2 * zc + pz) * Hf + 2 * yc + py) * Wf + 2 * xc + px) * p.Cout + co) * 4) : 0xFFFFFFFFu);
         }
     };
-    // scale bookkeeping (wave-uniform; conv3d_mfma.hip, conv3_split_wgrad_kernel)
+    // scale bookkeeping (DaSplitScale, over this workgroup's walk): a tile is staged at E = S exponent + dY exponent
     float* smax = reinterpret_cast<float*>(ldsY + NPLN * YPLANE_B);      // [2][4]
-    int Eacc = 0, Emin = 0, Enext = 0; bool first_tile = true;
+    DaSplitScale sc; int Enext = 0; bool first_tile = true;
     auto write_lds = [&]() {                                     // (starts with the barrier that retires the tile in LDS)
-        float my = 0.f;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) my = da_absmax4(my, preY[u]);
-        const float ma = da_wave_max_nonneg(sm.absmax(preA));
-        my = da_wave_max_nonneg(my);
-        if (lane == 0) { smax[wave] = ma; smax[4 + wave] = my; }
-        __syncthreads();
-        const float4 a4 = *reinterpret_cast<const float4*>(smax), y4 = *reinterpret_cast<const float4*>(smax + 4);
-        const int ea = da_scale_exp(__int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(fmaxf(fmaxf(a4.x, a4.y), fmaxf(a4.z, a4.w))))));
-        const int ey = da_scale_exp(__int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(fmaxf(fmaxf(y4.x, y4.y), fmaxf(y4.z, y4.w))))));
-        int E = ea + ey;
-        if (!first_tile) E = min(E, Emin + 40);
-        Emin = first_tile ? E : min(Emin, E);
+        const DaMax2 m = da_block_max4x2(stage_absmax<S_NIT>(preA), stage_absmax<4>(preY), smax, wave, lane);
+        const int ey = da_scale_exp(m.b);
+        Enext = sc.admit(da_scale_exp(m.a) + ey, first_tile);
         first_tile = false;
-        Enext = E;
         const float sy = da_pow2(ey);
-        sm.write(lds, preA, da_pow2(E - ey));
+        sm.write(lds, preA, da_pow2(Enext - ey));
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            uint2 h, l; da_split2(preY[u], sy, h, l);
-            uint2* o = reinterpret_cast<uint2*>(ldsY) + (yv0 + 32 * u) * 8 + yq;
-            o[0] = h; o[YPLANE_B / 8] = l;
-        }
+        for (int u = 0; u < 4; ++u) da_split_store4(preY[u], sy, reinterpret_cast<uint2*>(ldsY) + (yv0 + 32 * u) * 8 + yq, YPLANE_B / 8);
     };
-    UP_PLANE_PAIRS;
     const int slab = blockIdx.x;
     const int cnt = (p.ntiles > slab) ? (p.ntiles - slab + p.nslabs - 1) / p.nslabs : 0;
     if (cnt > 0) { issue(slab); write_lds(); }
@@ -628,10 +542,9 @@ __global__ void __launch_bounds__(256, 2) up_wgrad_kernel(WgP p) {
         const bool more = k + 1 < cnt;
         if (more) issue(slab + (k + 1) * p.nslabs);
         {
-            const float f = da_acc_factor(Enext - Eacc);               // the running sums into this tile's unit (exact)
+            const float f = sc.enter(Enext);                     // the running sums into this tile's unit (exact)
 #pragma unroll
             for (int s = 0; s < 4; ++s) { acc[s][0] = acc[s][0] * f; acc[s][1] = acc[s][1] * f; }
-            Eacc = Enext;
         }
         const F3 Y0 = loadY(0), Y1 = loadY(1);
         F3 F = loadF(0), Fn;
@@ -640,8 +553,8 @@ __global__ void __launch_bounds__(256, 2) up_wgrad_kernel(WgP p) {
             if (s + 1 < 4) Fn = loadF(s + 1);
 #pragma unroll
             for (int pr = 0; pr < 3; ++pr) {
-                acc[s][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(F.p[kPA[pr]], Y0.p[kPB[pr]], acc[s][0], 0, 0, 0);
-                acc[s][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(F.p[kPA[pr]], Y1.p[kPB[pr]], acc[s][1], 0, 0, 0);
+                acc[s][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(F.p[kSplitPA[pr]], Y0.p[kSplitPB[pr]], acc[s][0], 0, 0, 0);
+                acc[s][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(F.p[kSplitPA[pr]], Y1.p[kSplitPB[pr]], acc[s][1], 0, 0, 0);
             }
             if (s + 1 < 4) F = Fn;
         }
@@ -651,7 +564,7 @@ __global__ void __launch_bounds__(256, 2) up_wgrad_kernel(WgP p) {
         }
     }
     {
-        const float inv1 = da_pow2(-(Eacc / 2)), inv2 = da_pow2(-(Eacc - Eacc / 2));      // back to the true unit
+        float inv1, inv2; sc.leave(inv1, inv2);                  // back to the true unit
 #pragma unroll
         for (int s = 0; s < 4; ++s) { acc[s][0] = acc[s][0] * inv1 * inv2; acc[s][1] = acc[s][1] * inv1 * inv2; }
     }

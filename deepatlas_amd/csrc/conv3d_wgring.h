@@ -201,10 +201,9 @@ __global__ void __launch_bounds__(512, 1) conv3_split_wgrad16r_kernel(WgP p) {
     // the unit 2^-E of a tile's products given the ring's x exponent and the tile's ideal dY exponent (hysteresis and cap as in the other forms)
     int Eacc = 0, Emin = 0; bool first_tile = true;
     auto pick_E = [&](int ea, int ey_ideal, int Eref) -> int {
-        int E = ea + ey_ideal;
-        if (!first_tile) E = min(E, Emin + 40);
+        int E = da_split_cap(ea + ey_ideal, first_tile, Emin);
         if (!first_tile && E >= Eref && E <= Eref + 3) E = Eref;
-        Emin = first_tile ? E : min(Emin, E);
+        da_split_track(E, first_tile, Emin);
         first_tile = false;
         return E;
     };
@@ -522,7 +521,7 @@ __global__ void __launch_bounds__(512, 1) conv3_bf16_wgrad16r_kernel(WgP p) {
         }
     };
     auto pack = [&](const float4 v, bool raw) -> uint2 {
-        return raw ? make_uint2(__float_as_uint(v.x), __float_as_uint(v.y)) : make_uint2(da_bf16x2(v.x, v.y), da_bf16x2(v.z, v.w));
+        return raw ? make_uint2(__float_as_uint(v.x), __float_as_uint(v.y)) : make_uint2(da_pack_bf16x2(v.x, v.y), da_pack_bf16x2(v.z, v.w));
     };
     auto write_x = [&](int ps0) {
         if constexpr (PRO) {

@@ -112,15 +112,9 @@ __device__ __forceinline__ void fi_count(FiAcc& a, const FiResult& r, float tol_
     if (r.outside) a.out += 1.0;
 }
 
-__device__ __forceinline__ double fi_wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    return v;
-}
-
 // every lane of the workgroup calls this; row: the workgroup's partial row (may be NULL)
 __device__ __forceinline__ void fi_block_reduce(FiAcc a, double (*red)[kFiStats], double* __restrict__ row) {
-    a.mx = fi_wave_max(a.mx); a.unconv = da_wave_sum(a.unconv); a.iters = da_wave_sum(a.iters); a.out = da_wave_sum(a.out);
+    a.mx = da_wave_max(a.mx); a.unconv = da_wave_sum(a.unconv); a.iters = da_wave_sum(a.iters); a.out = da_wave_sum(a.out);
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     if (lane == 0) { red[wid][0] = a.mx; red[wid][1] = a.unconv; red[wid][2] = a.iters; red[wid][3] = a.out; }
     __syncthreads();
@@ -199,7 +193,7 @@ __global__ void fieldinv_finalize_kernel(const double* __restrict__ partial, int
             mx = fmax(mx, p[(size_t)b * kFiStats]); un += p[(size_t)b * kFiStats + 1];
             it += p[(size_t)b * kFiStats + 2]; out += p[(size_t)b * kFiStats + 3];
         }
-        mx = fi_wave_max(mx); un = da_wave_sum(un); it = da_wave_sum(it); out = da_wave_sum(out);
+        mx = da_wave_max(mx); un = da_wave_sum(un); it = da_wave_sum(it); out = da_wave_sum(out);
         if (lane == 0) { double* o = stats + (size_t)n * kFiStats; o[0] = mx; o[1] = un; o[2] = it; o[3] = out; }
     }
 }

@@ -39,12 +39,6 @@ __device__ __forceinline__ bool ic_outside(const IcPoint& p, int D, int H, int W
     return !(ix >= 0.f && ix <= (float)(W - 1) && iy >= 0.f && iy <= (float)(H - 1) && iz >= 0.f && iz <= (float)(D - 1));
 }
 
-__device__ __forceinline__ double ic_wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    return v;
-}
-
 __global__ void __launch_bounds__(256)
 invcons_fwd_kernel(const float* __restrict__ disp_a, const float* __restrict__ disp_b, int D, int H, int W, float* __restrict__ resid,
                    double* __restrict__ partial) {
@@ -83,7 +77,7 @@ invcons_fwd_kernel(const float* __restrict__ disp_a, const float* __restrict__ d
         mx = fmax(mx, (double)e);                                   // (fmax drops a NaN operand; the sums carry it)
         if (ic_outside(p, D, H, W)) out += 1.0;
     }
-    s2 = da_wave_sum(s2); s1 = da_wave_sum(s1); mx = ic_wave_max(mx); out = da_wave_sum(out);
+    s2 = da_wave_sum(s2); s1 = da_wave_sum(s1); mx = da_wave_max(mx); out = da_wave_sum(out);
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     if (lane == 0) { red[wid][0] = s2; red[wid][1] = s1; red[wid][2] = mx; red[wid][3] = out; }
     __syncthreads();
@@ -109,7 +103,7 @@ __global__ void invcons_finalize_kernel(const double* __restrict__ partial, int 
             s2 += p[(size_t)b * kIcStats]; s1 += p[(size_t)b * kIcStats + 1];
             mx = fmax(mx, p[(size_t)b * kIcStats + 2]); out += p[(size_t)b * kIcStats + 3];
         }
-        s2 = da_wave_sum(s2); s1 = da_wave_sum(s1); mx = ic_wave_max(mx); out = da_wave_sum(out);
+        s2 = da_wave_sum(s2); s1 = da_wave_sum(s1); mx = da_wave_max(mx); out = da_wave_sum(out);
         total += s2;
         if (stats && lane == 0) { double* o = stats + (size_t)n * kIcStats; o[0] = s2; o[1] = s1; o[2] = mx; o[3] = out; }
     }

@@ -316,10 +316,8 @@ __global__ void __launch_bounds__(256) pw_mfma_wgrad_kernel(PwWgP p) {
     const long long slice0 = p.up ? vblk / ((long long)p.H * p.W) : 0;          // n*D + d of the first voxel
     const long long fbase = p.up ? slice0 * 2 * (2ll * p.H) * (2ll * p.W) : vblk;   // first dy voxel the descriptor covers
     auto clip32 = [](unsigned long long b) -> unsigned { return b > 0xFFFFFFF0ull ? 0xFFFFFFF0u : (unsigned)b; };
-    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void*)(reinterpret_cast<const char*>(p.in) + vblk * p.ldi * (long long)EI), 0,
-                                           clip32((unsigned long long)(p.M - vblk) * p.ldi * (unsigned long long)EI), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rdy = __builtin_amdgcn_make_buffer_rsrc((void*)(reinterpret_cast<const char*>(p.dy) + fbase * p.ldy * (long long)EY), 0,
-                                           clip32((unsigned long long)(p.M * fine_mult - fbase) * p.ldy * (unsigned long long)EY), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rin = da_rsrc(reinterpret_cast<const char*>(p.in) + vblk * p.ldi * (long long)EI, clip32((unsigned long long)(p.M - vblk) * p.ldi * (unsigned long long)EI));
+    const __amdgpu_buffer_rsrc_t rdy = da_rsrc(reinterpret_cast<const char*>(p.dy) + fbase * p.ldy * (long long)EY, clip32((unsigned long long)(p.M * fine_mult - fbase) * p.ldy * (unsigned long long)EY));
     // this lane's voxel (v0 + g, then += 4 per K-step) tracked as (w, h, rest = n*D + d - slice0) with carries
     int cw = 0, chh = 0; long long crest = 0;
     if (p.up) {

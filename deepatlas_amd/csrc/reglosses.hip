@@ -204,7 +204,6 @@ __global__ void __launch_bounds__(256, 2) lncc_march_kernel(MarchP p) {
     const int nplanes = zo1 - zo0 + F - 1;
     const long long plane_in = (long long)p.Liy * p.Lix, plane_out = (long long)p.Loy * p.Lox;
     const unsigned in_bytes = (unsigned)(plane_in * 4), out_bytes = (unsigned)(plane_out * 4);
-    auto rsrc = [](const float* ptr, unsigned bytes) { return __builtin_amdgcn_make_buffer_rsrc((void*)ptr, 0, bytes, 0x00020000); };
     auto ld = [](__amdgpu_buffer_rsrc_t r, unsigned o) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, o, 0, 0)); };
     auto st = [](__amdgpu_buffer_rsrc_t r, unsigned o, float x) { __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, x), r, o, 0, 0); };
     unsigned voff[NSL]; int lofs[NSL];
@@ -226,13 +225,13 @@ __global__ void __launch_bounds__(256, 2) lncc_march_kernel(MarchP p) {
     // descriptors span one sample of one field and are built once; a plane is a scalar byte offset (the launcher keeps a sample below 2 GiB); a
     // plane outside the volume / the chunk keeps its offset inside the sample and loads (stores) through the EMPTY descriptor instead
     const unsigned in_sample = in_bytes * (unsigned)p.Liz, out_sample = out_bytes * (unsigned)p.Loz;
-    const __amdgpu_buffer_rsrc_t r_null = rsrc(p.I, 0u);
+    const __amdgpu_buffer_rsrc_t r_null = da_rsrc(p.I, 0u);
     const float* in0 = BWD ? p.sums_in : p.I;
     const float* in1 = BWD ? p.sums_in + p.P : p.J;
-    const __amdgpu_buffer_rsrc_t r_in0 = rsrc(in0 + (long long)n * p.Liz * plane_in, in_sample), r_in1 = rsrc(in1 + (long long)n * p.Liz * plane_in, in_sample);
-    const __amdgpu_buffer_rsrc_t r_in2 = rsrc(BWD ? p.sums_in + 2 * p.P + (long long)n * p.Liz * plane_in : p.I, BWD ? in_sample : 0u);
-    const __amdgpu_buffer_rsrc_t r_in3 = rsrc(BWD ? p.sums_in + 3 * p.P + (long long)n * p.Liz * plane_in : p.I, BWD ? in_sample : 0u);
-    const __amdgpu_buffer_rsrc_t r_in4 = rsrc(BWD ? p.sums_in + 4 * p.P + (long long)n * p.Liz * plane_in : p.I, BWD ? in_sample : 0u);
+    const __amdgpu_buffer_rsrc_t r_in0 = da_rsrc(in0 + (long long)n * p.Liz * plane_in, in_sample), r_in1 = da_rsrc(in1 + (long long)n * p.Liz * plane_in, in_sample);
+    const __amdgpu_buffer_rsrc_t r_in2 = da_rsrc(BWD ? p.sums_in + 2 * p.P + (long long)n * p.Liz * plane_in : p.I, BWD ? in_sample : 0u);
+    const __amdgpu_buffer_rsrc_t r_in3 = da_rsrc(BWD ? p.sums_in + 3 * p.P + (long long)n * p.Liz * plane_in : p.I, BWD ? in_sample : 0u);
+    const __amdgpu_buffer_rsrc_t r_in4 = da_rsrc(BWD ? p.sums_in + 4 * p.P + (long long)n * p.Liz * plane_in : p.I, BWD ? in_sample : 0u);
     auto ldo = [](__amdgpu_buffer_rsrc_t r, unsigned o, unsigned so) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, o, so, 0)); };
     auto sto = [](__amdgpu_buffer_rsrc_t r, unsigned o, unsigned so, float x) { __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, x), r, o, so, 0); };
     float v[NIN][NSL];
@@ -246,7 +245,7 @@ __global__ void __launch_bounds__(256, 2) lncc_march_kernel(MarchP p) {
             if constexpr (BWD) { v[2][j] = ldo(zok ? r_in2 : r_null, voff[j], so); v[3][j] = ldo(zok ? r_in3 : r_null, voff[j], so); v[4][j] = ldo(zok ? r_in4 : r_null, voff[j], so); }
         }
     };
-    const __amdgpu_buffer_rsrc_t r_pi = rsrc(p.I + (long long)n * p.Loz * plane_out, BWD ? out_sample : 0u), r_pj = rsrc(p.J + (long long)n * p.Loz * plane_out, BWD ? out_sample : 0u);
+    const __amdgpu_buffer_rsrc_t r_pi = da_rsrc(p.I + (long long)n * p.Loz * plane_out, BWD ? out_sample : 0u), r_pj = da_rsrc(p.J + (long long)n * p.Loz * plane_out, BWD ? out_sample : 0u);
     float pi[2] = {0.f, 0.f}, pj[2] = {0.f, 0.f};               // backward: I, J at this thread's two voxels of the output plane of walk step i
     auto issue_post = [&](int i) {
         if constexpr (BWD) {
@@ -261,10 +260,10 @@ __global__ void __launch_bounds__(256, 2) lncc_march_kernel(MarchP p) {
     const float* o0 = BWD ? p.dI : p.sums_out;
     const float* o1 = BWD ? p.dJ : p.sums_out + p.P;
     const long long osmp = (long long)n * p.Loz * plane_out;
-    const __amdgpu_buffer_rsrc_t r_o0 = rsrc(o0 ? o0 + osmp : nullptr, o0 ? out_sample : 0u), r_o1 = rsrc(o1 ? o1 + osmp : nullptr, o1 ? out_sample : 0u);
-    const __amdgpu_buffer_rsrc_t r_o2 = rsrc(BWD ? nullptr : p.sums_out + 2 * p.P + osmp, BWD ? 0u : out_sample);
-    const __amdgpu_buffer_rsrc_t r_o3 = rsrc(BWD ? nullptr : p.sums_out + 3 * p.P + osmp, BWD ? 0u : out_sample);
-    const __amdgpu_buffer_rsrc_t r_o4 = rsrc(BWD ? nullptr : p.sums_out + 4 * p.P + osmp, BWD ? 0u : out_sample);
+    const __amdgpu_buffer_rsrc_t r_o0 = da_rsrc(o0 ? o0 + osmp : nullptr, o0 ? out_sample : 0u), r_o1 = da_rsrc(o1 ? o1 + osmp : nullptr, o1 ? out_sample : 0u);
+    const __amdgpu_buffer_rsrc_t r_o2 = da_rsrc(BWD ? nullptr : p.sums_out + 2 * p.P + osmp, BWD ? 0u : out_sample);
+    const __amdgpu_buffer_rsrc_t r_o3 = da_rsrc(BWD ? nullptr : p.sums_out + 3 * p.P + osmp, BWD ? 0u : out_sample);
+    const __amdgpu_buffer_rsrc_t r_o4 = da_rsrc(BWD ? nullptr : p.sums_out + 4 * p.P + osmp, BWD ? 0u : out_sample);
     float gs = 0.f;
     if constexpr (BWD) gs = -p.dloss[0] * p.inv_m;
     const float inv_n = 1.f / p.n;
