@@ -150,6 +150,12 @@ SIGNATURES = {
     'da_cc_label': (I, [P, I, I, I, I, I, I, I, P, P, P, SZ, P]),
     'da_cc_select': (I, [P, I, P, I, LL, I, P, P, P]),
     'da_cc_filter': (I, [P, I, P, P, P, I, LL, I, I, I, P, P]),
+    'da_edt_ws_bytes': (SZ, [I, I, I, I, I]),
+    'da_edt_sq': (I, [P, I, I, I, I, I, F, F, F, I, P, P, SZ, P]),
+    'da_signed_distance_maps': (I, [P, I, P, I, I, I, I, I, F, F, F, P, P, SZ, P]),
+    'da_boundary_loss_ws_bytes': (SZ, [I]),
+    'da_boundary_loss_fwd': (I, [P, P, P, I, LL, I, I, P, P, SZ, P]),
+    'da_boundary_loss_bwd': (I, [P, P, P, P, I, LL, I, I, P, P]),
     'da_conv_k2s2_fwd': (I, [P, P, P, P, I, I, I, I, I, I, P, SZ, P]),
     'da_conv_k2s2_dgrad': (I, [P, P, P, I, I, I, I, I, I, P, SZ, P]),
     'da_conv_k2s2_wgrad_ws_bytes': (SZ, [I, I, I, I, I, I]),

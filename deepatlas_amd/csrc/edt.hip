@@ -1,0 +1,488 @@
+// Exact Euclidean distance transform of 3-D volumes, signed distance maps of a label map and the boundary loss on them (no reference call
+// site: it replaces a device-to-host copy and scipy.ndimage.distance_transform_edt once per class and volume; the loss is Kervadec et al.,
+// "Boundary loss for highly unbalanced segmentation").
+// A site set is the set of voxels a distance is measured to; the transform is  out(x) = min over sites y of sum_a (s_a (x_a - y_a))^2  with the
+// spacing s = (sD, sH, sW) in float32.  It separates over the axes:
+//   1. edt_row_kernel (W, the contiguous axis): one wave per row and site set.  Per chunk of 64 voxels one ballot of the site predicate; the
+//      nearest site at or left of a lane is the highest set bit of the ballot below the lane (else the last site of the chunks before it), the
+//      nearest at or right the lowest set bit above it (else the first site of the chunks behind).  A row without a site gets +inf.
+//   2. edt_line_kernel along H, then along D:  out[i] = min_j g[j] + (s (i - j))^2.  A workgroup owns 64 neighbouring lines (lanes run along W,
+//      so every global access is a coalesced 256-byte row), stages them in LDS in chunks of kEdtLineChunk entries, and its four waves share
+//      the outputs i.  The minimum is the exhaustive one, walked outwards from j = i and pruned: it stops at the first k = |i - j| with
+//      (s k)^2 >= the best value of every lane of the wave, which no later j can beat because g >= 0 and float32 rounding is
+//      monotone; entries that are +inf in all 64 lanes (a ballot map of the chunk) are stepped over, and a lane whose whole line is +inf does
+//      not keep the scan going.  No lower-envelope stacks, no divisions: the result IS the float32 minimum over all j.
+// float32 throughout: inf + k^2 = inf needs no sentinel; with unit spacing every value is an integer below 2^24 (the entries refuse extents
+// with D^2 + H^2 + W^2 >= 2^24), so the arithmetic is exact.  With another spacing a value takes two roundings per pass (s k, then the fused
+// multiply-add) on non-negative terms: a relative error below 6 x 2^-24.
+// Site sets come straight from the label map: set (n, c) = the voxels of sample n with label == c, or their complement.  No one-hot tensor.
+// No atomics, no workgroup waits for another, every loop's trip count is bounded by an extent: outputs are functions of the input alone.
+//
+// Signed maps: phi_c = + distance to class c outside it, - distance to its complement inside it; two transforms per class, the last pass of
+// each writes only the voxels of its side.  A side without a site (class absent from the sample, or filling it) yields +inf and is stored as 0.
+//
+// Boundary loss  L = 1 / (N K' V) sum_n sum_{c in classes} sum_x softmax(z)_c(x) phi_c(x)  on channels-last logits (one voxel = K contiguous
+// floats, as xent.hip): K % 4 == 0 -> K / 4 lanes own a voxel, otherwise a thread owns it (K <= 64).  phi is PLANAR, [N][K'][D][H][W]: that is
+// what the last transform pass stores coalesced, and a lane group reads 32-byte runs of a plane that the neighbouring groups complete to lines.
+// A voxel's term is formed in float32 and summed in double: per thread -> per workgroup -> one finalising workgroup, a fixed order.
+#include "common.h"
+
+namespace {
+
+constexpr int kEdtLineChunk = DA_EDT_LINE_CHUNK;       // entries of a line staged in LDS at a time: 256 x 64 lanes x 4 bytes = 64 KiB
+constexpr int kEdtLineFlags = (kEdtLineChunk + 4 * 64) * 4;      // bytes of the line pass's flag arrays behind the staged lines
+constexpr int kEdtLineLdsMax = kEdtLineChunk * 64 * 4 + kEdtLineFlags;
+static_assert(kEdtLineChunk == 256, "the line pass keeps the chunk's finite-entry map in four 64-bit ballots");
+constexpr int kEdtMaxRowChunks = 64;                   // chunks of 64 voxels of a row: W < 4096 since W^2 < 2^24
+constexpr size_t kEdtWsTarget = (size_t)128 << 20;     // bytes per ping-pong buffer the class groups of the signed maps are sized to
+constexpr int kBlBlocks = 1024;                        // workgroups per sample of the loss kernels, at most
+constexpr int kBlMaxC = 64;
+
+__device__ __forceinline__ long long edt_ld(const void* __restrict__ p, int bytes, long long i) {
+    if (bytes == 1) return (long long)((const unsigned char*)p)[i];
+    if (bytes == 4) return (long long)((const int*)p)[i];
+    return ((const long long*)p)[i];
+}
+
+// 1. grid: ceil(rows * G / 4) workgroups of 4 waves; wave id -> (row, g), g fastest so the G readers of a label row run together.
+// labels [N][D][H][W]; out [N][G][D][H][W]; rows = N * D * H; classes == nullptr: the one site set `label == 0` (a mask's zero voxels).
+__global__ void __launch_bounds__(256)
+edt_row_kernel(const void* __restrict__ labels, int bytes, const int* __restrict__ classes, int g0, int G, int complement,
+               long long rows, int DH, int W, float s, float* __restrict__ out) {
+    __shared__ unsigned long long smask[4][kEdtMaxRowChunks];
+    __shared__ int sleft[4][kEdtMaxRowChunks];
+    const int lane = threadIdx.x & 63, q = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const long long id = (long long)blockIdx.x * 4 + q;
+    const bool live = id < rows * G;                   // (a dead wave walks the loops with an empty predicate: every wave reaches the barrier)
+    const long long row = live ? id / G : 0;
+    const int g = live ? (int)(id % G) : 0;
+    const long long n = row / DH, dh = row % DH;
+    const long long cls = classes ? (long long)classes[g0 + g] : 0;
+    const long long src = row * W;                     // = (n DH + dh) W
+    const long long dst = ((n * G + g) * DH + dh) * W;
+    const int nch = (W + 63) >> 6;                     // <= kEdtMaxRowChunks (checked by the launchers)
+    int carry = -1;                                    // wave-uniform: the last site before the chunk
+    for (int c = 0; c < nch; ++c) {
+        const int w = c * 64 + lane;
+        bool site = false;
+        if (live && w < W) site = (edt_ld(labels, bytes, src + w) == cls) != (complement != 0);
+        const unsigned long long m = __ballot(site);
+        if (lane == 0) { smask[q][c] = m; sleft[q][c] = carry; }
+        if (m) carry = c * 64 + 63 - __clzll((long long)m);
+    }
+    __syncthreads();
+    int rcarry = -1;                                   // wave-uniform: the first site behind the chunk
+    for (int c = nch - 1; c >= 0; --c) {
+        const int w = c * 64 + lane;
+        const unsigned long long m = smask[q][c];
+        const unsigned long long ml = m & (~0ull >> (63 - lane)), mr = m & (~0ull << lane);
+        const int pl = ml ? c * 64 + 63 - __clzll((long long)ml) : sleft[q][c];
+        const int pr = mr ? c * 64 + __ffsll((long long)mr) - 1 : rcarry;
+        float d = INFINITY;
+        if (pl >= 0) { const float dk = s * (float)(w - pl); d = dk * dk; }
+        if (pr >= 0) { const float dk = s * (float)(pr - w); d = fminf(d, dk * dk); }
+        if (live && w < W) out[dst + w] = d;
+        if (m) rcarry = c * 64 + __ffsll((long long)m) - 1;
+    }
+}
+
+// what the last pass does with a finished squared distance
+struct EdtEpi {
+    int mode;                    // 0: store the squared distance, 1: its square root, 2: one side of a signed map
+    const void* labels;          // mode 2: [N][V]
+    int bytes;
+    const int* classes;          // mode 2: [Kp]
+    int complement;              // mode 2: 0 = the sites were the class (store + sqrt outside it), 1 = its complement (store - sqrt inside it)
+    int g0, G, Kp;               // the site sets g0 .. g0 + G - 1 of Kp are in flight: outer index o = n G + g -> plane n Kp + g0 + g
+    long long V;
+};
+
+// 2. element (o, i, x) of `in` sits at (o len + i) inner + x: the H pass has o = (n, g, d), inner = W; the D pass o = (n, g), inner = H W.
+// grid: outer * ceil(inner / 64) workgroups of 4 waves; dynamic LDS min(len, kEdtLineChunk) x 64 floats + kEdtLineFlags bytes.
+// Lines longer than a chunk: the running minimum of output i lives in `tmp` between the chunks (the H pass passes its own output, the D pass
+// the buffer the H pass has consumed); the value is final after the last chunk.
+template <bool LAST>
+__global__ void __launch_bounds__(256)
+edt_line_kernel(const float* __restrict__ in, float* __restrict__ tmp, float* __restrict__ out, int tiles, int len, int inner, float s, EdtEpi e) {
+    extern __shared__ float edt_lds[];                 // [chunk entry][lane]: a wave reads one 256-byte bank row per access; then the two flag arrays
+    const int cap = len < kEdtLineChunk ? len : kEdtLineChunk;
+    int* rowfin = (int*)(edt_lds + cap * 64);          // [kEdtLineChunk]: entry j of the chunk is finite in some lane
+    int* lanefin = rowfin + kEdtLineChunk;             // [4][64]: the lane's line has a finite entry among those the wave staged
+    const int lane = threadIdx.x & 63, q = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const long long o = blockIdx.x / tiles;
+    const int x = (int)(blockIdx.x % tiles) * 64 + lane;
+    const bool valid = x < inner;
+    const long long base = o * len * inner + x;
+    long long obase = base;                            // of the final store
+    bool keep = true, zero_inf = false;
+    float sign = 1.f;
+    long long vox0 = 0;
+    if (LAST && e.mode == 2) {
+        const long long n = o / e.G;
+        const int g = (int)(o % e.G);
+        obase = (n * e.Kp + e.g0 + g) * e.V + x;
+        vox0 = n * e.V + x;
+        sign = e.complement ? -1.f : 1.f;
+        zero_inf = true;
+    }
+    for (int j0 = 0; j0 < len; j0 += kEdtLineChunk) {
+        const int nj = len - j0 < kEdtLineChunk ? len - j0 : kEdtLineChunk;
+        const int hi = j0 + nj - 1;
+        const bool first = j0 == 0, last = hi == len - 1;
+        if (!first) __syncthreads();                   // the previous chunk's readers are done
+        int mine = 0;
+        for (int j = q; j < nj; j += 4) {
+            const float v = valid ? in[base + (long long)(j0 + j) * inner] : INFINITY;
+            edt_lds[j * 64 + lane] = v;
+            const bool fin = v < INFINITY;
+            mine |= fin ? 1 : 0;
+            const bool any_fin = __any(fin);
+            if (lane == 0) rowfin[j] = any_fin ? 1 : 0;
+        }
+        lanefin[q * 64 + lane] = mine;
+        __syncthreads();
+        // a lane whose line is all +inf in this chunk can gain nothing: it does not keep the wave's scan going
+        const bool has = (lanefin[lane] | lanefin[64 + lane] | lanefin[128 + lane] | lanefin[192 + lane]) != 0;
+        // bit j of the 256-bit map m: entry j is finite in some lane.  The scans visit only those entries: all others are +inf in every lane.
+        unsigned long long m[4];
+#pragma unroll
+        for (int w = 0; w < 4; ++w) { const int j = w * 64 + lane; m[w] = __ballot(j < nj && rowfin[j] != 0); }
+        const auto word = [&](int w) { return w == 0 ? m[0] : w == 1 ? m[1] : w == 2 ? m[2] : m[3]; };
+        const auto prev_set = [&](int p) {             // the largest set position <= p, or -1; at most four words
+            while (p >= 0) {
+                const int w = p >> 6;
+                const unsigned long long bits = word(w) & (~0ull >> (63 - (p & 63)));
+                if (bits) return (w << 6) + 63 - __clzll((long long)bits);
+                p = (w << 6) - 1;
+            }
+            return -1;
+        };
+        const auto next_set = [&](int p) {             // the smallest set position >= p, or nj
+            while (p < nj) {
+                const int w = p >> 6;
+                const unsigned long long bits = word(w) & (~0ull << (p & 63));
+                if (bits) return (w << 6) + __ffsll((long long)bits) - 1;
+                p = (w + 1) << 6;
+            }
+            return nj;
+        };
+        const int first_set = next_set(0), last_set = prev_set(nj - 1);      // nj / -1: the chunk is +inf in every lane
+        for (int i = q; i < len; i += 4) {             // i, r, k and the map are wave-uniform: so is every branch
+            float best = INFINITY;
+            if (!first && valid) best = tmp[base + (long long)i * inner];
+            const int r = i - j0;                      // the output's position relative to the chunk, possibly outside it
+            if (last_set >= 0) {
+                // k = |r - j| runs from the nearest entry that is finite in some lane to the farthest, two steps a trip (four loads in flight),
+                // and stops at the first k that is too far for every lane.  A candidate outside the chunk reads entry 0 at distance +inf.
+                const int pl = prev_set(r < nj - 1 ? r : nj - 1), pr = next_set(r + 1 > 0 ? r + 1 : 0);
+                const int kl = pl >= 0 ? r - pl : 0x7FFFFFFF, kr = pr < nj ? pr - r : 0x7FFFFFFF;
+                const int kend = r - first_set > last_set - r ? r - first_set : last_set - r;
+                for (int k = kl < kr ? kl : kr; k <= kend; k += 2) {
+                    const float d0 = s * (float)k, d1 = s * (float)(k + 1);
+                    if (!__any(has && d0 * d0 < best)) break;
+                    const int a0 = r - k, b0 = r + k, a1 = a0 - 1, b1 = b0 + 1;
+                    const bool ia0 = a0 >= 0 && a0 < nj, ib0 = b0 >= 0 && b0 < nj, ia1 = a1 >= 0 && a1 < nj, ib1 = b1 >= 0 && b1 < nj;
+                    const float ga0 = edt_lds[(ia0 ? a0 : 0) * 64 + lane], gb0 = edt_lds[(ib0 ? b0 : 0) * 64 + lane];
+                    const float ga1 = edt_lds[(ia1 ? a1 : 0) * 64 + lane], gb1 = edt_lds[(ib1 ? b1 : 0) * 64 + lane];
+                    const float da0 = ia0 ? d0 : INFINITY, db0 = ib0 ? d0 : INFINITY, da1 = ia1 ? d1 : INFINITY, db1 = ib1 ? d1 : INFINITY;
+                    best = fminf(fminf(best, fmaf(da0, da0, ga0)), fmaf(db0, db0, gb0));
+                    best = fminf(fminf(best, fmaf(da1, da1, ga1)), fmaf(db1, db1, gb1));
+                }
+            }
+            if (!valid) continue;
+            if (!LAST || !last) {
+                (last ? out : tmp)[base + (long long)i * inner] = best;
+            } else {
+                if (e.mode == 2) {
+                    const bool inside = edt_ld(e.labels, e.bytes, vox0 + (long long)i * inner) == (long long)e.classes[e.g0 + (int)(o % e.G)];
+                    keep = inside == (e.complement != 0);
+                }
+                float r = best;
+                if (e.mode != 0) r = sign * (float)sqrt((double)best);      // correctly rounded: the double root rounds to the float32 root (53 >= 2 x 24 + 2)
+                if (zero_inf && best == INFINITY) r = 0.f;
+                if (keep) out[obase + (long long)i * inner] = r;
+            }
+        }
+    }
+}
+
+bool edt_bytes_ok(int b) { return b == 1 || b == 4 || b == 8; }
+bool edt_spacing_ok(float s) { return s > 0.f && s < INFINITY; }
+
+// 0 or the error code of the extents
+int edt_extents(int N, int D, int H, int W) {
+    if (N < 1 || N > 65535 || D < 1 || H < 1 || W < 1) return DA_ERR_BADARG;
+    if ((long long)D * D + (long long)H * H + (long long)W * W >= (1LL << 24)) return DA_ERR_UNSUPPORTED;     // squared distances are exact float32 integers
+    if ((long long)D * H * W >= 0x80000000LL) return DA_ERR_UNSUPPORTED;
+    return 0;
+}
+
+// site sets per group of the signed maps: as many as fit kEdtWsTarget bytes per buffer, at least one
+int edt_group(int N, long long V, int Kp) {
+    const size_t per = (size_t)N * (size_t)V * sizeof(float);
+    size_t G = kEdtWsTarget / per;
+    if (G < 1) G = 1;
+    return G > (size_t)Kp ? Kp : (int)G;
+}
+
+// the three passes of G site sets: labels -> a -> b -> (epilogue) out
+int edt_passes(const void* labels, int bytes, const int* classes, int g0, int G, int complement, int N, int D, int H, int W,
+               float sD, float sH, float sW, float* a, float* b, float* out, EdtEpi e, hipStream_t st) {
+    const long long rows = (long long)N * D * H, HW = (long long)H * W;
+    const long long row_blocks = da_cdiv(rows * G, 4);
+    const int tiles_h = (int)da_cdiv(W, 64), tiles_d = (int)da_cdiv(HW, 64);
+    const long long h_blocks = (long long)N * G * D * tiles_h, d_blocks = (long long)N * G * tiles_d;
+    if (row_blocks > 0x7FFFFFFFLL || h_blocks > 0x7FFFFFFFLL || d_blocks > 0x7FFFFFFFLL) return DA_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(edt_row_kernel, dim3((unsigned)row_blocks), dim3(256), 0, st, labels, bytes, classes, g0, G, complement, rows, D * H, W, sW, a);
+    DA_LAUNCH_CHECK();
+    const size_t lds_h = (size_t)(H < kEdtLineChunk ? H : kEdtLineChunk) * 64 * sizeof(float) + kEdtLineFlags;
+    const size_t lds_d = (size_t)(D < kEdtLineChunk ? D : kEdtLineChunk) * 64 * sizeof(float) + kEdtLineFlags;
+    int rc = da_launch_lds<edt_line_kernel<false>, kEdtLineLdsMax>(dim3((unsigned)h_blocks), dim3(256), lds_h, st, (const float*)a, b, b, tiles_h, H, W, sH, e);
+    if (rc) return rc;
+    return da_launch_lds<edt_line_kernel<true>, kEdtLineLdsMax>(dim3((unsigned)d_blocks), dim3(256), lds_d, st, (const float*)b, a, out, tiles_d, D, (int)HW, sD, e);
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// boundary loss
+// ------------------------------------------------------------------------------------------------------------------------------
+template <int L> __device__ __forceinline__ float bl_group_max(float v) {
+#pragma unroll
+    for (int m = 1; m < L; m <<= 1) v = fmaxf(v, __shfl_xor(v, m));
+    return v;
+}
+template <int L> __device__ __forceinline__ float bl_group_sum(float v) {
+#pragma unroll
+    for (int m = 1; m < L; m <<= 1) v += __shfl_xor(v, m);
+    return v;
+}
+// plane of class k in phi, or -1: the slot table is device data, so it is range-checked here
+__device__ __forceinline__ int bl_slot(const int* __restrict__ slots, int k, int Kp) {
+    const int s = slots[k];
+    return (s >= 0 && s < Kp) ? s : -1;
+}
+
+// grid (blocks, N): L = K / 4 lanes own a voxel, 16 bytes of its logits each
+template <int L>
+__global__ void __launch_bounds__(256)
+bl_fwd_quad_kernel(const float* __restrict__ x, const float* __restrict__ phi, const int* __restrict__ slots, long long V, int Kp, double* __restrict__ partial) {
+    __shared__ double red[4];
+    constexpr int C = 4 * L;
+    const int sub = (int)threadIdx.x & (L - 1), n = blockIdx.y;
+    const float* xn = x + (long long)n * V * C;
+    const float* pj[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { const int s = bl_slot(slots, 4 * sub + j, Kp); pj[j] = s >= 0 ? phi + ((long long)n * Kp + s) * V : nullptr; }
+    const long long vpb = 256 / L, passes = (V + vpb - 1) / vpb;       // every lane of a group runs the same passes (shuffles inside)
+    double dacc = 0.0;
+    for (long long ps = blockIdx.x; ps < passes; ps += gridDim.x) {
+        const long long i = ps * vpb + (long long)(threadIdx.x / L);
+        const bool in = i < V;
+        const long long ii = in ? i : V - 1;
+        const float4 qv = reinterpret_cast<const float4*>(xn + ii * C)[sub];
+        const float v[4] = {qv.x, qv.y, qv.z, qv.w};
+        const float mx = bl_group_max<L>(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
+        float ex[4], t = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { ex[j] = expf(v[j] - mx); t += (pj[j] ? pj[j][ii] : 0.f) * ex[j]; }
+        const float se = bl_group_sum<L>(ex[0] + ex[1] + ex[2] + ex[3]);
+        if (in) dacc += (double)t / (double)se;
+    }
+    const double s = da_block_sum(dacc, red);
+    if (threadIdx.x == 0) partial[(size_t)n * gridDim.x + blockIdx.x] = s;
+}
+
+// ... and a thread owns a voxel (K % 4 != 0 or K / 4 no power of two; K <= kBlMaxC)
+__global__ void __launch_bounds__(256)
+bl_fwd_kernel(const float* __restrict__ x, const float* __restrict__ phi, const int* __restrict__ slots, long long V, int C, int Kp, double* __restrict__ partial) {
+    __shared__ double red[4];
+    const int n = blockIdx.y;
+    const float* xn = x + (long long)n * V * C;
+    const float* pn = phi + (long long)n * Kp * V;
+    double dacc = 0.0;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < V; i += (long long)gridDim.x * 256) {
+        float v[kBlMaxC];
+        float mx = -INFINITY;
+        for (int c = 0; c < C; ++c) { v[c] = xn[i * C + c]; mx = fmaxf(mx, v[c]); }
+        float se = 0.f, t = 0.f;
+        for (int c = 0; c < C; ++c) {
+            const float ex = expf(v[c] - mx);
+            se += ex;
+            const int s = bl_slot(slots, c, Kp);
+            if (s >= 0) t += pn[(long long)s * V + i] * ex;
+        }
+        dacc += (double)t / (double)se;
+    }
+    const double s = da_block_sum(dacc, red);
+    if (threadIdx.x == 0) partial[(size_t)n * gridDim.x + blockIdx.x] = s;
+}
+
+__global__ void bl_finalize_kernel(const double* __restrict__ partial, int nparts, double scale, float* __restrict__ loss) {
+    __shared__ double red[4];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nparts; i += blockDim.x) s += partial[i];
+    s = da_block_sum(s, red);
+    if (threadIdx.x == 0) loss[0] = (float)(s * scale);
+}
+
+// dz_k = g p_k (m_k phi_k - sum_c m_c p_c phi_c) / (N K' V), the softmax recomputed
+template <int L>
+__global__ void __launch_bounds__(256)
+bl_bwd_quad_kernel(const float* __restrict__ x, const float* __restrict__ phi, const int* __restrict__ slots, const float* __restrict__ dloss,
+                   float scale, long long V, int Kp, float* __restrict__ dx) {
+    constexpr int C = 4 * L;
+    const int sub = (int)threadIdx.x & (L - 1), n = blockIdx.y;
+    const float* xn = x + (long long)n * V * C;
+    float* dn = dx + (long long)n * V * C;
+    const float* pj[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { const int s = bl_slot(slots, 4 * sub + j, Kp); pj[j] = s >= 0 ? phi + ((long long)n * Kp + s) * V : nullptr; }
+    const float gs = dloss[0] * scale;
+    const long long vpb = 256 / L, passes = (V + vpb - 1) / vpb;
+    for (long long ps = blockIdx.x; ps < passes; ps += gridDim.x) {
+        const long long i = ps * vpb + (long long)(threadIdx.x / L);
+        const bool in = i < V;
+        const long long ii = in ? i : V - 1;
+        const float4 qv = reinterpret_cast<const float4*>(xn + ii * C)[sub];
+        const float v[4] = {qv.x, qv.y, qv.z, qv.w};
+        const float mx = bl_group_max<L>(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
+        float ex[4], f[4], t = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { ex[j] = expf(v[j] - mx); f[j] = pj[j] ? pj[j][ii] : 0.f; t += f[j] * ex[j]; }
+        const float se = bl_group_sum<L>(ex[0] + ex[1] + ex[2] + ex[3]);
+        const float S = bl_group_sum<L>(t) / se;
+        float d[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) d[j] = gs * (ex[j] / se) * (f[j] - S);
+        if (in) reinterpret_cast<float4*>(dn + i * C)[sub] = make_float4(d[0], d[1], d[2], d[3]);
+    }
+}
+
+__global__ void __launch_bounds__(256)
+bl_bwd_kernel(const float* __restrict__ x, const float* __restrict__ phi, const int* __restrict__ slots, const float* __restrict__ dloss,
+              float scale, long long V, int C, int Kp, float* __restrict__ dx) {
+    const int n = blockIdx.y;
+    const float* xn = x + (long long)n * V * C;
+    const float* pn = phi + (long long)n * Kp * V;
+    float* dn = dx + (long long)n * V * C;
+    const float gs = dloss[0] * scale;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < V; i += (long long)gridDim.x * 256) {
+        float v[kBlMaxC];
+        float mx = -INFINITY;
+        for (int c = 0; c < C; ++c) { v[c] = xn[i * C + c]; mx = fmaxf(mx, v[c]); }
+        float se = 0.f, t = 0.f;
+        for (int c = 0; c < C; ++c) {
+            v[c] = expf(v[c] - mx);
+            se += v[c];
+            const int s = bl_slot(slots, c, Kp);
+            if (s >= 0) t += pn[(long long)s * V + i] * v[c];
+        }
+        const float S = t / se;
+        for (int c = 0; c < C; ++c) {
+            const int s = bl_slot(slots, c, Kp);
+            const float f = s >= 0 ? pn[(long long)s * V + i] : 0.f;
+            dn[i * C + c] = gs * (v[c] / se) * (f - S);
+        }
+    }
+}
+
+int bl_lanes(int C, const float* a, const float* b) {      // lanes per voxel of the quad kernels, 0: thread-per-voxel form
+    if (C % 4 != 0) return 0;
+    const int L = C / 4;
+    if (L != 1 && L != 2 && L != 4 && L != 8 && L != 16) return 0;
+    if (((size_t)a | (size_t)b) & 15) return 0;
+    return L;
+}
+
+int bl_args(const void* logits, const void* phi, const void* slots, int N, long long V, int K, int Kp) {
+    if (!logits || !phi || !slots || N < 1 || N > 65535 || V < 1 || K < 1 || Kp < 1 || Kp > K) return DA_ERR_BADARG;
+    if (K > kBlMaxC || V >= 0x80000000LL) return DA_ERR_UNSUPPORTED;
+    return 0;
+}
+
+int bl_blocks(long long V, int L) {
+    const long long work = L ? da_cdiv(V, 256 / L) : da_cdiv(V, 256);
+    return work < kBlBlocks ? (int)work : kBlBlocks;
+}
+
+}  // namespace
+
+extern "C" size_t da_edt_ws_bytes(int N, int Kp, int D, int H, int W) {
+    if (Kp < 1 || edt_extents(N, D, H, W) != 0) return 0;
+    const long long V = (long long)D * H * W;
+    return 2 * da_align((size_t)N * edt_group(N, V, Kp) * (size_t)V * sizeof(float));
+}
+
+extern "C" int da_edt_sq(const void* mask, int mask_bytes, int N, int D, int H, int W, float sD, float sH, float sW, int take_sqrt,
+                         float* out, void* ws, size_t ws_bytes, void* stream) {
+    if (!mask || !out || !ws || !edt_bytes_ok(mask_bytes) || !edt_spacing_ok(sD) || !edt_spacing_ok(sH) || !edt_spacing_ok(sW)) return DA_ERR_BADARG;
+    if (const int rc = edt_extents(N, D, H, W)) return rc;
+    if (ws_bytes < da_edt_ws_bytes(N, 1, D, H, W)) return DA_ERR_WS_SMALL;
+    const long long V = (long long)D * H * W;
+    float* a = (float*)ws;
+    float* b = (float*)((char*)ws + da_align((size_t)N * (size_t)V * sizeof(float)));
+    EdtEpi e{take_sqrt ? 1 : 0, nullptr, 0, nullptr, 0, 0, 1, 1, V};
+    return edt_passes(mask, mask_bytes, nullptr, 0, 1, 0, N, D, H, W, sD, sH, sW, a, b, out, e, da_stream(stream));
+}
+
+extern "C" int da_signed_distance_maps(const void* labels, int label_bytes, const int* classes, int Kp, int N, int D, int H, int W,
+                                       float sD, float sH, float sW, float* phi, void* ws, size_t ws_bytes, void* stream) {
+    if (!labels || !classes || !phi || !ws || Kp < 1 || !edt_bytes_ok(label_bytes) || !edt_spacing_ok(sD) || !edt_spacing_ok(sH) || !edt_spacing_ok(sW))
+        return DA_ERR_BADARG;
+    if (const int rc = edt_extents(N, D, H, W)) return rc;
+    if (ws_bytes < da_edt_ws_bytes(N, Kp, D, H, W)) return DA_ERR_WS_SMALL;
+    const long long V = (long long)D * H * W;
+    const int G = edt_group(N, V, Kp);
+    float* a = (float*)ws;
+    float* b = (float*)((char*)ws + da_align((size_t)N * G * (size_t)V * sizeof(float)));
+    for (int g0 = 0; g0 < Kp; g0 += G) {
+        const int g = Kp - g0 < G ? Kp - g0 : G;
+        for (int complement = 0; complement < 2; ++complement) {
+            EdtEpi e{2, labels, label_bytes, classes, complement, g0, g, Kp, V};
+            if (const int rc = edt_passes(labels, label_bytes, classes, g0, g, complement, N, D, H, W, sD, sH, sW, a, b, phi, e, da_stream(stream))) return rc;
+        }
+    }
+    return 0;
+}
+
+extern "C" size_t da_boundary_loss_ws_bytes(int N) {
+    if (N < 1) return 0;
+    return da_align((size_t)N * kBlBlocks * sizeof(double));
+}
+
+extern "C" int da_boundary_loss_fwd(const float* logits, const float* phi, const int* slots, int N, long long V, int K, int Kp,
+                                    float* loss, void* ws, size_t ws_bytes, void* stream) {
+    if (!loss || !ws) return DA_ERR_BADARG;
+    if (const int rc = bl_args(logits, phi, slots, N, V, K, Kp)) return rc;
+    if (ws_bytes < da_boundary_loss_ws_bytes(N)) return DA_ERR_WS_SMALL;
+    hipStream_t st = da_stream(stream);
+    const int L = bl_lanes(K, logits, nullptr);
+    const int nblocks = bl_blocks(V, L);
+#define BL_FWD(l) case l: hipLaunchKernelGGL((bl_fwd_quad_kernel<l>), dim3(nblocks, N), dim3(256), 0, st, logits, phi, slots, V, Kp, (double*)ws); break;
+    switch (L) {
+        BL_FWD(1) BL_FWD(2) BL_FWD(4) BL_FWD(8) BL_FWD(16)
+        default: hipLaunchKernelGGL(bl_fwd_kernel, dim3(nblocks, N), dim3(256), 0, st, logits, phi, slots, V, K, Kp, (double*)ws);
+    }
+#undef BL_FWD
+    DA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(bl_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)ws, N * nblocks, 1.0 / ((double)N * Kp * (double)V), loss);
+    DA_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int da_boundary_loss_bwd(const float* logits, const float* phi, const int* slots, const float* dloss, int N, long long V, int K, int Kp,
+                                    float* dlogits, void* stream) {
+    if (!dloss || !dlogits) return DA_ERR_BADARG;
+    if (const int rc = bl_args(logits, phi, slots, N, V, K, Kp)) return rc;
+    hipStream_t st = da_stream(stream);
+    const float scale = (float)(1.0 / ((double)N * Kp * (double)V));
+    const int L = bl_lanes(K, logits, dlogits);
+    const int nblocks = bl_blocks(V, L);
+#define BL_BWD(l) case l: hipLaunchKernelGGL((bl_bwd_quad_kernel<l>), dim3(nblocks, N), dim3(256), 0, st, logits, phi, slots, dloss, scale, V, Kp, dlogits); break;
+    switch (L) {
+        BL_BWD(1) BL_BWD(2) BL_BWD(4) BL_BWD(8) BL_BWD(16)
+        default: hipLaunchKernelGGL(bl_bwd_kernel, dim3(nblocks, N), dim3(256), 0, st, logits, phi, slots, dloss, scale, V, K, Kp, dlogits);
+    }
+#undef BL_BWD
+    DA_LAUNCH_CHECK();
+    return 0;
+}

@@ -5,6 +5,7 @@ Hot path: 'dice' -> DiceLossMultiClass, 'ncc' -> Normali
 'mi' -> MutualInformationLoss (mi.hip; not in the reference's registry: the similarity for multi-modal pairs);
 'jacobian' -> JacobianFoldingLoss (jacpen.hip; not in the reference's registry either: a regulariser on the negative part of det J);
 'inverse_consistency' -> InverseConsistencyLoss (invcons.hip; likewise: the composition residual of the two directions' fields).
+'boundary' -> BoundaryLoss (edt.hip; likewise: Kervadec's boundary loss on signed distance maps built on the device from the index labels).
 'mse' / 'L2' are one-line compositions; 'focal' / 'cross_entropy' / 'soft_cross_entropy' share one voxelwise HIP kernel pair (xent.hip).
 """
 import os
@@ -185,6 +186,38 @@ class InverseConsistencyLoss(nn.Module):
         return 0.5 * (l_ab + ops.InverseConsistencyFn.apply(u_ba, u_ab))
 
 
+class BoundaryLoss(nn.Module):
+    """Boundary loss of Kervadec et al., "Boundary loss for highly unbalanced segmentation" (registry name 'boundary'): the mean over samples,
+    the chosen classes and voxels of softmax(logits)_c(x) * phi_c(x), phi_c the signed Euclidean distance to the ground-truth structure of
+    class c (ops.signed_distance_maps: negative inside, positive outside, the plain signed distance; 0 for a class absent from a sample or
+    filling it).  A wrong voxel costs its distance from the truth, which soft Dice does not see.  `classes` defaults to 1 .. n_class - 1;
+    `spacing` = (sD, sH, sW) voxel size.  The maps are rebuilt from the index labels on every call, on the device and without autograd, so
+    labels that an augmentation has just resampled need no precomputed maps.  Meant as an additional term beside a region loss."""
+
+    def __init__(self, n_class, classes=None, spacing=(1, 1, 1)):
+        super(BoundaryLoss, self).__init__()
+        self.n_class = int(n_class)
+        self.classes = ops._boundary_classes(self.n_class, classes)
+        self.spacing = ops._edt_spacing(spacing)
+
+    def forward(self, logits, target_labels):
+        """logits: N x n_class x D x H x W float32; target_labels: N x D x H x W (or N x 1 x D x H x W) index labels."""
+        if isinstance(logits, ops.LazyLogits):
+            logits = logits.materialize()
+        if logits.dim() != 5 or logits.shape[1] != self.n_class:
+            raise ValueError("logits must be N x {} x D x H x W, got {}".format(self.n_class, tuple(logits.shape)))
+        lab = target_labels
+        if lab.dim() == 5 and lab.shape[1] == 1:
+            lab = lab[:, 0]
+        if lab.dim() != 4 or lab.shape[0] != logits.shape[0] or tuple(lab.shape[1:]) != tuple(logits.shape[2:]):
+            raise ValueError("target labels {} do not match logits {}".format(tuple(target_labels.shape), tuple(logits.shape)))
+        if lab.dtype not in (torch.uint8, torch.int32, torch.int64):
+            lab = lab.long()
+        with torch.no_grad():
+            phi = ops.signed_distance_maps(lab, self.n_class, classes=self.classes, spacing=self.spacing)
+        return ops.BoundaryLossFn.apply(logits, phi, self.classes)
+
+
 class LNCCLoss(nn.Module):
     """lib/loss.py:512-586 (not in the registry): multi-scale LNCC.  Scales, weights, dilations and strides follow `__stepup`
     (:516-540): min(img) > 128 -> windows ms/16, ms/8, ms/4 (weights .1/.3/.6, dilation 2); > 64 -> ms/4, ms/2 (.3/.7,
@@ -343,6 +376,12 @@ FIELD_PAIR_LOSSES = {
     'inverse_consistency': InverseConsistencyLoss,
 }
 loss_dict.update(FIELD_PAIR_LOSSES)
+# ... and the losses of logits against distance maps of the index labels (constructor takes n_class): reachable through get_loss_function,
+# listed by none of the lists above
+LABEL_DISTANCE_LOSSES = {
+    'boundary': BoundaryLoss,
+}
+loss_dict.update(LABEL_DISTANCE_LOSSES)
 
 
 def get_loss_function(loss_name):
@@ -353,7 +392,8 @@ def get_loss_function(loss_name):
 
 
 def get_available_losses():
-    return [name for name in loss_dict if name not in EXTENSION_LOSSES and name not in REGULARISER_LOSSES and name not in FIELD_PAIR_LOSSES]
+    return [name for name in loss_dict if name not in EXTENSION_LOSSES and name not in REGULARISER_LOSSES and name not in FIELD_PAIR_LOSSES
+            and name not in LABEL_DISTANCE_LOSSES]
 
 
 def get_extension_losses():
@@ -366,3 +406,7 @@ def get_regulariser_losses():
 
 def get_field_pair_losses():
     return list(FIELD_PAIR_LOSSES.keys())
+
+
+def get_label_distance_losses():
+    return list(LABEL_DISTANCE_LOSSES.keys())

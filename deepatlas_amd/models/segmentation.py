@@ -7,6 +7,9 @@ scheduler.step + checkpoint (:203-239).  Differences, all host-side: the device 
 (config['device'], default 'cuda'), data comes from config['data'] == 'synthetic' or injected loaders,
 TensorBoard logging is optional, eval Dice is computed on the device (lib/evalMetrics.py), and with
 torch.distributed initialised the gradients are averaged with one flat-bucket all-reduce (parallel.py).
+config['lambda_boundary'] (default 0: off) weights Kervadec's boundary loss as a second term of the step (lib/loss.py BoundaryLoss: signed
+distance maps built on the device from the batch's index labels, after any augmentation); config['boundary_settings'] optionally holds its
+`classes` and `spacing`.  Without the key, or with 0, nothing changes.
 """
 import datetime
 import os
@@ -21,7 +24,7 @@ from .base import BaseExperiment
 from ..lib import datasets as med_data
 from ..lib import evalMetrics as metrics
 from ..lib import transforms as med_transforms
-from ..lib.loss import get_loss_function
+from ..lib.loss import get_loss_function, BoundaryLoss
 from ..lib.network_factory import get_network
 from ..lib.param_dict import save_dict_to_json
 from ..optim import FlatAdam
@@ -35,6 +38,28 @@ except Exception:                                             # tensorboardX is 
     SummaryWriter = None
 
 
+def check_boundary_term(cfg):
+    """config['lambda_boundary']: weight of the boundary loss, finite and >= 0 (0, also when absent: off); config['boundary_settings']: the
+    optional constructor arguments `classes` and `spacing` of BoundaryLoss.  Both are checked here, also when the term is off."""
+    lam = cfg.get('lambda_boundary')
+    lam = 0.0 if lam is None else lam
+    if isinstance(lam, bool) or not isinstance(lam, (int, float)) or not 0.0 <= float(lam) < float('inf'):
+        raise ValueError("config['lambda_boundary'] must be a finite number >= 0, got %r" % (cfg.get('lambda_boundary'),))
+    settings = dict(cfg.get('boundary_settings') or {})
+    unknown = sorted(set(settings) - {'classes', 'spacing'})
+    if unknown:
+        raise ValueError("config['boundary_settings'] takes 'classes' and 'spacing', got %s" % ', '.join(repr(k) for k in unknown))
+    if 'n_classes' in cfg:
+        BoundaryLoss(cfg['n_classes'], **settings)             # raises for a bad class list / spacing
+    return float(lam), settings
+
+
+def boundary_name_suffix(cfg):
+    """'_boundary<lambda>' for an experiment name when the term is on, '' otherwise (names of runs without it stay as they were)."""
+    lam = cfg.get('lambda_boundary') or 0.0
+    return '_boundary%s' % lam if lam > 0 else ''
+
+
 class SegmentationExperiment(BaseExperiment):
     def __init__(self, config):
         super(SegmentationExperiment, self).__init__(config)
@@ -43,6 +68,9 @@ class SegmentationExperiment(BaseExperiment):
         if cfg['debug_mode']:                                    # debug runs print and validate every second batch / epoch
             print("Debug mode")
             cfg['print_batch_period'] = cfg['valid_epoch_period'] = 2
+        self.lambda_boundary, self.boundary_settings = check_boundary_term(cfg)
+        self.boundary_criterion = None
+        self.last_boundary = None                                # the step's boundary term (a device scalar) when the term is on
         self.exp_name = self.experiment_name(cfg)
         # <log_dir>/<experiment name | "debug_seg">/<seed>: the directory layout the reference's checkpoints and resume_dir use
         # (models/segmentation.py:40-42), so runs of either code base can resume each other's checkpoints
@@ -59,7 +87,7 @@ class SegmentationExperiment(BaseExperiment):
     @staticmethod
     def experiment_name(cfg):
         """The run's name, field by field as the reference composes it (models/segmentation.py:27-38) -- it is part of the checkpoint path:
-        Seg_<model>[_bias][_BN]_<data dir name>_<n>samples_batch_<b>_<e>epochs_<loss>_<weighting>_lr_<lr>[_scheduler_<mode>]."""
+        Seg_<model>[_bias][_BN]_<data dir name>_<n>samples_batch_<b>_<e>epochs_<loss>_<weighting>_lr_<lr>[_scheduler_<mode>][_boundary<lambda_boundary>]."""
         ms = cfg['model_settings']
         parts = ['Seg_', cfg['model']]
         if ms['bias']:
@@ -71,6 +99,7 @@ class SegmentationExperiment(BaseExperiment):
                   '_%s_%s' % (cfg['loss'], cfg['loss_settings']['weight_type']), '_lr_%s' % cfg['learning_rate']]
         if cfg['lr_mode'] != 'const':
             parts.append('_scheduler_%s' % cfg['lr_mode'])
+        parts.append(boundary_name_suffix(cfg))
         return ''.join(str(v) for v in parts)
 
     # ---- setup ---------------------------------------------------------------------------------
@@ -102,12 +131,15 @@ class SegmentationExperiment(BaseExperiment):
         self.model.to(self.device)
         # softmax-Dice training (train_seg.py:55): the output convolution is evaluated inside the fused head + softmax + Dice kernels
         # (ops.HeadDiceFn) and the logits tensor is only built on demand (train_step's `output`.materialize(), eval mode)
-        if (self.config.get('fuse_head_dice', True) and self.config.get('loss') == 'dice'
+        # (with the boundary term on, the logits feed two losses: they are materialised once and the head is not fused)
+        if (self.config.get('fuse_head_dice', True) and self.config.get('loss') == 'dice' and not self.lambda_boundary > 0
                 and self.config.get('loss_settings', {}).get('softmax') and hasattr(type(self.model), 'lazy_head')):
             self.model.lazy_head = True
 
     def setup_loss(self):
         self.criterion = get_loss_function(self.config['loss'])(**self.config['loss_settings']).to(self.device)
+        if self.lambda_boundary > 0:
+            self.boundary_criterion = BoundaryLoss(self.config['n_classes'], **self.boundary_settings).to(self.device)
 
     def setup_optimizer(self):
         """models/segmentation.py:90-111: Adam + plateau / multiStep / const."""
@@ -158,7 +190,12 @@ class SegmentationExperiment(BaseExperiment):
         with trace.range('seg/forward'):
             output = self.model(images.to(self.device, non_blocking=True))
         with trace.range('seg/loss'):
-            loss = self.criterion(output, truths.to(self.device, non_blocking=True))
+            truths = truths.to(self.device, non_blocking=True)
+            loss = self.criterion(output, truths)
+            if self.boundary_criterion is not None:
+                boundary = self.boundary_criterion(output, truths)
+                self.last_boundary = boundary.detach()
+                loss = loss + self.lambda_boundary * boundary
         with trace.range('seg/backward'):
             loss.backward()
         with trace.range('seg/allreduce'):
@@ -176,7 +213,7 @@ class SegmentationExperiment(BaseExperiment):
         return sample['image'], sample['segmentation']
 
     def train_one_epoch(self):
-        running_loss = 0.0
+        running_loss = running_boundary = 0.0
         iters_per_epoch = max(self.config['samples_per_epoch'] // (self.config['batch_size'] * parallel.world_size()), 1)
         train_data_iter = None
         for i in range(iters_per_epoch):
@@ -190,16 +227,20 @@ class SegmentationExperiment(BaseExperiment):
                 images, truths = self.augment_batch(images, truths)
             loss, output = self.train_step(images, truths)
             running_loss += loss.item()
+            if self.boundary_criterion is not None:
+                running_boundary += self.last_boundary.item()
             if i % self.config['print_batch_period'] == self.config['print_batch_period'] - 1:
                 if parallel.rank() == 0:
-                    print('Epoch[{}/{}] it {} loss: {:.3f} lr:{} {}'.format(
+                    print('Epoch[{}/{}] it {} loss: {:.3f}{} lr:{} {}'.format(
                         self.current_epoch, self.config['n_epochs'], i + 1,
                         running_loss / self.config['print_batch_period'] if i > 0 else running_loss,
+                        '' if self.boundary_criterion is None else ' boundary: {:.4f}'.format(
+                            running_boundary / self.config['print_batch_period'] if i > 0 else running_boundary),
                         self.optimizer.param_groups[0]['lr'], datetime.datetime.now().strftime("%D %H:%M:%S")))
                     if self.writer is not None:
                         self.writer.add_scalar('loss/training', running_loss / self.config['print_batch_period'], global_step=self.global_step)
                         self.writer.add_scalar('learning_rate', self.optimizer.param_groups[0]['lr'], global_step=self.global_step)
-                running_loss = 0.0
+                running_loss = running_boundary = 0.0
 
     def eval(self, dataloader):
         """models/segmentation.py:179-201; Dice from exact integer counts computed on the device.

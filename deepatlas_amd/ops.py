@@ -2884,3 +2884,135 @@ def remove_small_components(labels, n_class, min_size, connectivity=6, return_st
     """The label map without the connected components of fewer than `min_size` voxels (and without labels outside [0, n_class)): their
     voxels become 0.  min_size = 1 changes nothing but the out-of-range labels.  return_stats as keep_largest_component."""
     return _cc_clean(labels, n_class, connectivity, 1, min_size, return_stats)
+
+
+# ------------------------------------------------------------------------------------------------
+# exact Euclidean distance transform, signed distance maps of a label map, boundary loss (csrc/edt.hip)
+# ------------------------------------------------------------------------------------------------
+EDT_LINE_CHUNK = 256            # DA_EDT_LINE_CHUNK (include/deepatlas_hip.h): entries of a line the H and D passes stage in LDS at a time
+EDT_MAX_SQ_EXTENT = 2 ** 24     # D^2 + H^2 + W^2 must stay below it: squared distances are exact float32 integers at unit spacing
+BOUNDARY_MAX_CLASSES = 64       # channels the boundary-loss kernels keep in registers
+
+
+def _edt_spacing(spacing):
+    try:
+        sp = tuple(float(s) for s in spacing)
+    except TypeError:
+        raise ValueError('spacing must be three positive numbers (sD, sH, sW), got %r' % (spacing,))
+    if len(sp) != 3 or not all(0.0 < s < float('inf') for s in sp):
+        raise ValueError('spacing must be three positive finite numbers (sD, sH, sW), got %r' % (spacing,))
+    return sp
+
+
+def _edt_extents(t, what):
+    """Shape checks of the distance ops, before anything touches the device; returns (N, D, H, W)."""
+    if t.dim() != 4:
+        raise ValueError('%s must be N x D x H x W, got %d dimensions' % (what, t.dim()))
+    N, D, H, W = (int(s) for s in t.shape)
+    if N < 1 or D < 1 or H < 1 or W < 1:
+        raise ValueError('%s must not be empty, got %s' % (what, tuple(t.shape)))
+    if N > 65535:
+        raise ValueError('at most 65535 samples per call, got %d' % N)
+    if D * D + H * H + W * W >= EDT_MAX_SQ_EXTENT:
+        raise ValueError('a volume of %d x %d x %d has D^2 + H^2 + W^2 >= 2^24: squared distances would not be exact in float32' % (D, H, W))
+    if D * H * W >= 2 ** 31:
+        raise ValueError('a volume of %d x %d x %d has >= 2^31 voxels' % (D, H, W))
+    return N, D, H, W
+
+
+def distance_transform_edt(mask, spacing=(1, 1, 1), squared=False):
+    """Exact Euclidean distance transform of N x D x H x W masks (bool, uint8, int32 or int64; nonzero = foreground), scipy's convention:
+    0 on the zero voxels, elsewhere the distance to the nearest zero voxel of the same sample, with the voxel spacing (sD, sH, sW) =
+    scipy.ndimage.distance_transform_edt(mask[n], sampling=spacing).  squared=True returns the squared distance; with unit spacing it is an
+    exact integer.  A sample without a zero voxel returns +inf everywhere (scipy's result is meaningless in that case: it measures to a
+    voxel outside the array).  float32, no autograd."""
+    if not torch.is_tensor(mask) or (mask.dtype != torch.bool and mask.dtype not in _LABEL_BYTES):
+        raise ValueError('mask must be a bool, uint8, int32 or int64 tensor, got %s' % (getattr(mask, 'dtype', type(mask)),))
+    N, D, H, W = _edt_extents(mask, 'mask')
+    sp = _edt_spacing(spacing)
+    nat.require_cuda(mask)
+    m = mask.contiguous()
+    if m.dtype == torch.bool:
+        m = m.view(torch.uint8)
+    out = torch.empty((N, D, H, W), dtype=torch.float32, device=m.device)
+    with torch.cuda.device(m.device):
+        wp, wn = _ws(nat.lib().da_edt_ws_bytes(N, 1, D, H, W), m)
+        call('da_edt_sq', ptr(m), _LABEL_BYTES[m.dtype], N, D, H, W, sp[0], sp[1], sp[2], 0 if squared else 1, ptr(out), wp, wn, stream())
+    return out
+
+
+def _boundary_classes(n_class, classes):
+    """The class list of the signed maps / the boundary loss: default 1 .. n_class - 1 (no background); distinct, inside [0, n_class)."""
+    n_class = int(n_class)
+    if n_class < 1:
+        raise ValueError('n_class must be at least 1, got %r' % (n_class,))
+    cl = list(range(1, n_class)) if classes is None else [int(c) for c in classes]
+    if not cl:
+        raise ValueError('the class list is empty (n_class = %d without the background leaves nothing)' % n_class)
+    if len(set(cl)) != len(cl) or min(cl) < 0 or max(cl) >= n_class:
+        raise ValueError('classes must be distinct and inside [0, %d), got %r' % (n_class, cl))
+    return cl
+
+
+def signed_distance_maps(labels, n_class, classes=None, spacing=(1, 1, 1)):
+    """Signed Euclidean distance maps of an index label map N x D x H x W (uint8 / int32 / int64), one per class of `classes` (default
+    1 .. n_class - 1: the background is left out): N x K' x D x H x W float32, contiguous (planar, the layout BoundaryLossFn reads).
+    Outside class c: + the distance to the nearest voxel of class c; inside: - the distance to the nearest voxel not of class c; a class
+    absent from a sample, or filling it, gives 0 everywhere in that sample, so it contributes nothing to the boundary loss (as in Kervadec's
+    code).  This is the plain signed distance: Kervadec's one_hot2dist shifts the inside by one voxel, -(d - 1); this does not.
+    Labels outside [0, n_class) belong to no class.  The one-hot tensor is never built.  No autograd."""
+    if not torch.is_tensor(labels) or labels.dtype not in _LABEL_BYTES:
+        raise ValueError('labels must be a uint8, int32 or int64 tensor, got %s' % (getattr(labels, 'dtype', type(labels)),))
+    N, D, H, W = _edt_extents(labels, 'labels')
+    cl = _boundary_classes(n_class, classes)
+    sp = _edt_spacing(spacing)
+    nat.require_cuda(labels)
+    lab = labels.contiguous()
+    cls = torch.tensor(cl, dtype=torch.int32, device=lab.device)
+    phi = torch.empty((N, len(cl), D, H, W), dtype=torch.float32, device=lab.device)
+    with torch.cuda.device(lab.device):
+        wp, wn = _ws(nat.lib().da_edt_ws_bytes(N, len(cl), D, H, W), lab)
+        call('da_signed_distance_maps', ptr(lab), _LABEL_BYTES[lab.dtype], ptr(cls), len(cl), N, D, H, W, sp[0], sp[1], sp[2], ptr(phi), wp, wn, stream())
+    return phi
+
+
+class BoundaryLossFn(Function):
+    """Boundary loss (Kervadec et al.): mean over samples, chosen classes and voxels of softmax(logits)_c * phi_c.
+    logits N x K x D x H x W float32; phi N x K' x D x H x W float32 = signed_distance_maps(...) for `classes` (K' entries, distinct,
+    inside [0, K)).  The gradient goes to the logits only."""
+
+    @staticmethod
+    def forward(ctx, logits, phi, classes):
+        if logits.dim() != 5 or phi.dim() != 5 or logits.dtype != torch.float32 or phi.dtype != torch.float32:
+            raise ValueError('logits and phi must be float32 N x K x D x H x W / N x K\' x D x H x W')
+        N, K = int(logits.shape[0]), int(logits.shape[1])
+        cl = _boundary_classes(K, classes)
+        if tuple(phi.shape) != (N, len(cl)) + tuple(logits.shape[2:]):
+            raise ValueError('phi is %s for logits %s and %d classes' % (tuple(phi.shape), tuple(logits.shape), len(cl)))
+        if K > BOUNDARY_MAX_CLASSES:
+            raise ValueError('at most %d channels, got %d' % (BOUNDARY_MAX_CLASSES, K))
+        a = ndhwc(logits.detach())
+        nat.require_cuda(a, phi)
+        p = phi.detach().contiguous()
+        V = a.numel() // (N * K)
+        slots_host = [-1] * K
+        for j, c in enumerate(cl):
+            slots_host[c] = j
+        slots = torch.tensor(slots_host, dtype=torch.int32, device=a.device)
+        loss = _empty((1,), a)
+        with torch.cuda.device(a.device):
+            wp, wn = _ws(nat.lib().da_boundary_loss_ws_bytes(N), a)
+            call('da_boundary_loss_fwd', ptr(a), ptr(p), ptr(slots), N, V, K, len(cl), ptr(loss), wp, wn, stream())
+        ctx.cfg = (N, V, K, len(cl))
+        ctx.save_for_backward(a, p, slots)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, gloss):
+        a, p, slots = ctx.saved_tensors
+        N, V, K, Kp = ctx.cfg
+        gl = gloss.detach().reshape(1).to(torch.float32).contiguous()
+        dx = torch.empty_like(a)
+        with torch.cuda.device(a.device):
+            call('da_boundary_loss_bwd', ptr(a), ptr(p), ptr(slots), ptr(gl), N, V, K, Kp, ptr(dx), stream())
+        return ncdhw(dx), None, None

@@ -698,6 +698,43 @@ int da_cc_select(const void* labels, int label_bytes, const int* sizes, int N, l
 int da_cc_filter(const void* labels, int label_bytes, const int* roots, const int* sizes, const unsigned long long* best,
                  int N, long long V, int n_class, int mode, int min_size, void* out, void* stream);
 
+/* ---- exact Euclidean distance transform, signed distance maps of a label map and the boundary loss on them (edt.hip).  No reference call
+ *      site: these replace a host copy and scipy.ndimage.distance_transform_edt once per class and volume; the loss is Kervadec et al.,
+ *      "Boundary loss for highly unbalanced segmentation". ---------- */
+/* A site set is the set of voxels a distance is measured to; the transform of a volume [D][H][W] with the spacing (sD, sH, sW) is
+ * out(x) = min over sites y of (sD (xd - yd))^2 + (sH (xh - yh))^2 + (sW (xw - yw))^2, +inf where the sample has no site.  Exact and separable:
+ * a pass along W with wave ballots, then the exhaustive pruned minimum along H and along D on lines staged in LDS, DA_EDT_LINE_CHUNK entries at a
+ * time.  float32 throughout; with unit spacing every value is an exact integer, which is why extents with D^2 + H^2 + W^2 >= 2^24 are refused.
+ * No atomics; results are functions of the input alone, bit-identical from run to run.
+ * Maps (masks, labels) are uint8 (1), int32 (4) or int64 (8), [N][D][H][W]; samples never interact.
+ * da_edt_ws_bytes: the workspace of both entries below for Kp site sets per sample (da_edt_sq: Kp = 1).
+ * da_edt_sq: out [N][D][H][W] = the squared distance (take_sqrt != 0: the distance, one correctly rounded square root) of every voxel to the
+ * nearest ZERO voxel of the mask -- scipy's convention: 0 on the zero voxels.
+ * da_signed_distance_maps: classes [Kp] int32 on the device.  phi is PLANAR, [N][Kp][D][H][W] float32 (not channels-last like the logits: the
+ * last pass stores whole rows of a plane, and the loss kernel reads the planes directly): for class c = classes[j],
+ * phi = + the distance to the nearest voxel of class c outside the class, - the distance to the nearest voxel not of class c inside it, and 0
+ * everywhere in a sample where class c is absent or fills the sample.  The plain signed distance: Kervadec's one_hot2dist shifts the inside by
+ * one voxel ((d_in - 1)), this does not.  Labels that are in no class list are simply "not of class c".
+ * da_boundary_loss_fwd: logits [N][D][H][W][K] channels-last (V = D H W), slots [K] int32 on the device = the plane of class k in phi or -1
+ * (entries outside [0, Kp) count as -1);  loss[0] = 1 / (N Kp V) sum_n sum_k with slot sum_x softmax(logits)_k(x) phi_slot(k)(x).  The softmax
+ * runs over all K logits in registers (K % 4 == 0 and K / 4 a power of two <= 16: K / 4 lanes per voxel; otherwise a thread per voxel), nothing of
+ * size K x V is written, the sum has a fixed order (per-workgroup doubles, one finalising workgroup; ws: da_boundary_loss_ws_bytes).
+ * da_boundary_loss_bwd: dlogits [N][V][K] = dloss[0] p_k (m_k phi_k - sum_c m_c p_c phi_c) / (N Kp V), one pass, the softmax recomputed.
+ * A NULL pointer, N < 1 or N > 65535, an extent < 1, bytes not 1 / 4 / 8, a spacing that is not positive and finite, Kp < 1, K < 1 or Kp > K
+ * return DA_ERR_BADARG before any launch, a short workspace DA_ERR_WS_SMALL; D^2 + H^2 + W^2 >= 2^24, a volume of >= 2^31 voxels or K > 64
+ * DA_ERR_UNSUPPORTED. */
+#define DA_EDT_LINE_CHUNK 256
+size_t da_edt_ws_bytes(int N, int Kp, int D, int H, int W);
+int da_edt_sq(const void* mask, int mask_bytes, int N, int D, int H, int W, float sD, float sH, float sW, int take_sqrt,
+              float* out, void* ws, size_t ws_bytes, void* stream);
+int da_signed_distance_maps(const void* labels, int label_bytes, const int* classes /*[Kp]*/, int Kp, int N, int D, int H, int W,
+                            float sD, float sH, float sW, float* phi /*[N][Kp][D][H][W]*/, void* ws, size_t ws_bytes, void* stream);
+size_t da_boundary_loss_ws_bytes(int N);
+int da_boundary_loss_fwd(const float* logits, const float* phi, const int* slots /*[K]*/, int N, long long V, int K, int Kp,
+                         float* loss, void* ws, size_t ws_bytes, void* stream);
+int da_boundary_loss_bwd(const float* logits, const float* phi, const int* slots /*[K]*/, const float* dloss, int N, long long V, int K, int Kp,
+                         float* dlogits, void* stream);
+
 /* ---- optimiser (models/segmentation.py:91 torch.optim.Adam defaults) -------------------------- */
 int da_adam_step(float* p, const float* g, float* m, float* v, long long n,
                  float lr, float beta1, float beta2, float eps, int step, float grad_scale, void* stream);

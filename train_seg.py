@@ -60,6 +60,9 @@ def build_config(args):
         if post['mode'] == 'min_size':
             post['min_size'] = min_size if min_size is not None else 64
         config['postprocess'] = post
+    # opt-in boundary loss beside the region loss (lib/loss.py BoundaryLoss); absent = the step as it was, and no key in the config
+    if config.get('lambda_boundary') is None:
+        config.pop('lambda_boundary', None)
     if not config.get('matrix_precision'):                # (--matrix-precision; not a key of the reference's config: absent = the package default, 'fp32_split')
         config.pop('matrix_precision', None)
     return config
@@ -92,6 +95,9 @@ def main(argv=None):
                              "'largest-cc' keeps the largest component of every class, 'min-size' drops components below --cc-min-size voxels")
     parser.add_argument('--cc-connectivity', type=int, default=None, choices=[6, 18, 26], help='connectivity of --postprocess (default 6)')
     parser.add_argument('--cc-min-size', type=int, default=None, metavar='VOXELS', help="smallest component --postprocess min-size keeps (default 64)")
+    parser.add_argument('--lambda-boundary', type=float, default=None, metavar='W',
+                        help="add W x the boundary loss (Kervadec et al.: softmax probability times the signed distance to the ground truth, the "
+                             "distance maps rebuilt on the device from every batch's labels) to the step's loss; 0 or absent: off")
     args = parser.parse_args(argv)
     exp = SegmentationExperiment(build_config(args))
     if not args.test_only:
