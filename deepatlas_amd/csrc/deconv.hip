@@ -373,6 +373,8 @@ extern "C" int da_conv1x1_wgrad(const float* in, const float* dy, float* dw_io, 
     if (da_pw_supported(Cin, Cout)) rc_pw = da_pw_wgrad(in, dy, dw_io, M, 1, 1, 1, Cin, Cout, 1, 0, ws, cs_off, st);
     if (rc_pw != 0 && rc_pw != DA_ERR_UNSUPPORTED) return rc_pw;
     if (rc_pw == DA_ERR_UNSUPPORTED) {
+        // conv1x1_wgrad_kernel owns 16 x 256 outputs per block: a larger layer the matrix path declined is declined here too, never left partly written
+        if (O > 4096) return DA_ERR_UNSUPPORTED;
         float* partial = (float*)ws;
         hipLaunchKernelGGL(conv1x1_wgrad_kernel, dim3(parts), dim3(256), (size_t)kWgR * (Cin + Cout) * sizeof(float), st, in, dy, partial, M, Cin, Cout, per * kWgR);
         DA_LAUNCH_CHECK();

@@ -729,6 +729,9 @@ int da_pw_gemm(const float* a, const float* w, int transposed, const float* bias
                void* ws, size_t ws_bytes, hipStream_t st, double* stats_partial, const float* pro_scale, const float* pro_shift, float pro_slope, int a_bf, int o_bf) {
     if (!da_pw_supported(K, N)) return DA_ERR_UNSUPPORTED;
     if ((stats_partial || pro_scale) && gather) return DA_ERR_BADARG;
+    // K slices beyond the first accumulate THROUGH the output tensor: a bf16 output would be rounded once per slice (the partial sum, then the sum), not once.
+    // Declined; the caller converts around the fp32 entry, which rounds the finished value.
+    if (o_bf && K > 64) return DA_ERR_UNSUPPORTED;
     if (pro_scale && (!pro_shift || pro_slope >= 1.f)) return DA_ERR_UNSUPPORTED;
     if (ws_bytes < da_pw_packed_bytes(ntaps, K, N)) return DA_ERR_WS_SMALL;
     float* wp = (float*)ws;
@@ -768,11 +771,24 @@ static int wg_blocks(long long M, size_t O, long long* vox_per_wave) {
     return (int)da_cdiv(M, vpw * 4);
 }
 
+// Bytes of block partials the largest slice of a layer needs.  Slices are 64 wide except the last of each side; a NARROWER slice has a higher block cap, so
+// it can run more blocks of fewer voxels and need more partial bytes than the 64 x 64 one (48 x 64 at 10000 coarse voxels: 625 blocks, 61 MB, against 313 and 41 MB).
+static size_t wg_partial_bytes(long long M, int ntaps, int Cin, int Cout) {
+    const int ci[2] = {Cin < 64 ? Cin : 64, Cin % 64 ? Cin % 64 : 64}, co[2] = {Cout < 64 ? Cout : 64, Cout % 64 ? Cout % 64 : 64};
+    size_t worst = 0;
+    for (int a = 0; a < 2; ++a)
+        for (int b = 0; b < 2; ++b) {
+            long long vpw;
+            const size_t O = (size_t)ntaps * ci[a] * co[b];
+            const size_t bytes = da_align((size_t)wg_blocks(M, O, &vpw) * O * sizeof(float));
+            if (bytes > worst) worst = bytes;
+        }
+    return worst;
+}
+
 size_t da_pw_wgrad_ws_bytes(long long M, int ntaps, int Cin, int Cout) {
-    long long vpw;
-    const size_t O = (size_t)ntaps * (Cin < 64 ? Cin : 64) * (Cout < 64 ? Cout : 64);      // one 64 x 64 slice at a time
-    const int nb = wg_blocks(M, O, &vpw);
-    return da_align((size_t)nb * O * sizeof(float)) + da_align(O * sizeof(float));
+    const size_t O = (size_t)ntaps * (Cin < 64 ? Cin : 64) * (Cout < 64 ? Cout : 64);      // one (<= 64 x 64) slice at a time: its reduced result behind the partials
+    return wg_partial_bytes(M, ntaps, Cin, Cout) + da_align(O * sizeof(float));
 }
 
 __global__ void pw_place_kernel(const float* __restrict__ src, float* __restrict__ dw, int ntaps, int cic, int coc, int Cin, int Cout, int ci0, int co0) {
@@ -810,10 +826,7 @@ int da_pw_wgrad(const float* in, const float* dy, float* dw, long long M, int D,
     if (ws_bytes < da_pw_wgrad_ws_bytes(M, ntaps, Cin, Cout)) return DA_ERR_WS_SMALL;
     if (Cin <= 64 && Cout <= 64) return pw_wgrad_slice(in, dy, dw, M, D, H, W, Cin, Cout, Cin, Cout, ntaps, up, ws, st, pro, 0);
     // wide layers: independent 64 x 64 channel slices, each reduced into a dense scratch and placed into dW
-    long long vpw;
-    const size_t Os = (size_t)ntaps * 64 * 64;
-    const int nbmax = wg_blocks(M, Os, &vpw);
-    float* tmp = (float*)((char*)ws + da_align((size_t)nbmax * Os * sizeof(float)));
+    float* tmp = (float*)((char*)ws + wg_partial_bytes(M, ntaps, Cin, Cout));      // behind the partials of EVERY slice shape of this layer
     for (int ci0 = 0; ci0 < Cin; ci0 += 64)
         for (int co0 = 0; co0 < Cout; co0 += 64) {
             const int cic = (Cin - ci0) < 64 ? (Cin - ci0) : 64, coc = (Cout - co0) < 64 ? (Cout - co0) : 64;
@@ -869,6 +882,14 @@ static int pw_wgrad_slice(const float* in, const float* dy, float* dw, long long
         else if (CIT == 4 && COT == 2) rc = launch_pw_wgrad<4, 2, 1>(p, nb, st);
         else if (CIT == 1 && COT == 4) rc = launch_pw_wgrad<1, 4, 1>(p, nb, st);
         else if (CIT == 4 && COT == 1) rc = launch_pw_wgrad<4, 1, 1>(p, nb, st);
+        // 48-channel slices (the ntaps = 8 list has them; without these a 1x1 layer whose 64-wide slicing leaves one was declined half-way)
+        else if (CIT == 1 && COT == 3) rc = launch_pw_wgrad<1, 3, 1>(p, nb, st);
+        else if (CIT == 3 && COT == 1) rc = launch_pw_wgrad<3, 1, 1>(p, nb, st);
+        else if (CIT == 2 && COT == 3) rc = launch_pw_wgrad<2, 3, 1>(p, nb, st);
+        else if (CIT == 3 && COT == 2) rc = launch_pw_wgrad<3, 2, 1>(p, nb, st);
+        else if (CIT == 3 && COT == 3) rc = launch_pw_wgrad<3, 3, 1>(p, nb, st);
+        else if (CIT == 3 && COT == 4) rc = launch_pw_wgrad<3, 4, 1>(p, nb, st);
+        else if (CIT == 4 && COT == 3) rc = launch_pw_wgrad<4, 3, 1>(p, nb, st);
     }
     if (rc) return rc;
     { const int rc2 = da_reduce_partials(p.partial, nb, (int)O, dw, st); if (rc2) return rc2; }

@@ -154,6 +154,8 @@ int da_conv1x1_wgrad_pro(const float* in, const float* pro_scale, const float* p
                          long long M, int Cin, int Cout, void* ws, size_t ws_bytes, void* stream);
 int da_conv1x1_dgrad(const float* dy, const float* w_io, float* dx, long long M, int Cin, int Cout,
                      void* ws, size_t ws_bytes, void* stream);
+/* dW [Cin][Cout] (+ optional dbias).  Channel counts in multiples of 16 run on the matrix cores at any width; every other shape on the direct kernel, which
+ * covers Cin * Cout <= 4096 -- beyond that DA_ERR_UNSUPPORTED (never a partly written dW). */
 size_t da_conv1x1_wgrad_ws_bytes(long long M, int Cin, int Cout);
 int da_conv1x1_wgrad(const float* in, const float* dy, float* dw_io, float* dbias,
                      long long M, int Cin, int Cout, void* ws, size_t ws_bytes, void* stream);
@@ -803,7 +805,8 @@ int da_conv3d_k3_dgrad_bf16(const void* dy, const float* w_tio, void* dx1, int C
 int da_conv3d_k3_wgrad_bf16(const void* in1, int C1, const void* in2, int C2, const void* dy, float* dw_tio, float* dbias,
                             int N, int D, int H, int W, int Cout, int stride, void* ws, size_t ws_bytes, void* stream, unsigned bf16_mask);
 /* deconv.hip / pointwise_mfma.hip: transposed conv k2 s2 (input, output, their gradients bf16); 1x1x1 head (input and its gradient
- * bf16; logits and their gradient fp32) */
+ * bf16; logits and their gradient fp32).  An entry whose OUTPUT is bf16 returns DA_ERR_UNSUPPORTED when its reduction runs over more than 64 channels (forward:
+ * Cin > 64; data gradients: Cout > 64): the 64-channel slices accumulate through the output tensor, which would round a bf16 output once per slice. */
 int da_deconv_k2s2_fwd_bf16(const void* in, const float* w_tio, const float* bias, void* out,
                             int N, int D, int H, int W, int Cin, int Cout, void* ws, size_t ws_bytes, void* stream);
 int da_deconv_k2s2_fwd_bnstats_bf16(const void* in, const float* w_tio, const float* bias, void* out,
