@@ -6,7 +6,7 @@ op fails loudly with the build command.
 """
 import ctypes
 import os
-from ctypes import c_int, c_float, c_longlong, c_size_t, c_void_p, c_char_p, POINTER
+from ctypes import c_int, c_float, c_double, c_longlong, c_size_t, c_void_p, c_char_p, POINTER
 
 import torch
 
@@ -18,6 +18,7 @@ I = c_int
 F = c_float
 LL = c_longlong
 SZ = c_size_t
+DBL = c_double
 
 # name -> (restype, argtypes); mirrors include/deepatlas_hip.h one to one
 SIGNATURES = {
@@ -156,6 +157,9 @@ SIGNATURES = {
     'da_boundary_loss_ws_bytes': (SZ, [I]),
     'da_boundary_loss_fwd': (I, [P, P, P, I, LL, I, I, P, P, SZ, P]),
     'da_boundary_loss_bwd': (I, [P, P, P, P, I, LL, I, I, P, P]),
+    'da_label_surface': (I, [P, I, I, I, I, I, I, P, P]),
+    'da_surface_dist_ws_bytes': (SZ, [I, I, I, I, I]),
+    'da_surface_dist_stats': (I, [P, I, P, I, P, I, I, I, I, I, F, F, F, I, DBL, P, P, SZ, P]),
     'da_conv_k2s2_fwd': (I, [P, P, P, P, I, I, I, I, I, I, P, SZ, P]),
     'da_conv_k2s2_dgrad': (I, [P, P, P, I, I, I, I, I, I, P, SZ, P]),
     'da_conv_k2s2_wgrad_ws_bytes': (SZ, [I, I, I, I, I, I]),

@@ -16,7 +16,8 @@
 // with D^2 + H^2 + W^2 >= 2^24), so the arithmetic is exact.  With another spacing a value takes two roundings per pass (s k, then the fused
 // multiply-add) on non-negative terms: a relative error below 6 x 2^-24.
 // Site sets come straight from the label map: set (n, c) = the voxels of sample n with label == c, or their complement.  No one-hot tensor.
-// No atomics, no workgroup waits for another, every loop's trip count is bounded by an extent: outputs are functions of the input alone.
+// No atomics in the transform, no workgroup waits for another, every loop's trip count is bounded by an extent: outputs are functions of the input
+// alone.
 //
 // Signed maps: phi_c = + distance to class c outside it, - distance to its complement inside it; two transforms per class, the last pass of
 // each writes only the voxels of its side.  A side without a site (class absent from the sample, or filling it) yields +inf and is stored as 0.
@@ -25,6 +26,10 @@
 // floats, as xent.hip): K % 4 == 0 -> K / 4 lanes own a voxel, otherwise a thread owns it (K <= 64).  phi is PLANAR, [N][K'][D][H][W]: that is
 // what the last transform pass stores coalesced, and a lane group reads 32-byte runs of a plane that the neighbouring groups complete to lines.
 // A voxel's term is formed in float32 and summed in double: per thread -> per workgroup -> one finalising workgroup, a fixed order.
+//
+// Surface-distance metrics of two label maps (Hausdorff, its percentile, ASSD): the same transform with the SURFACE of a class as the site set
+// (edt_surface_row_kernel, a sibling of edt_row_kernel on the shared edt_row_body), a gather at the other map's surface voxels and an exact
+// radix select; described at the kernels, below the boundary loss.
 #include "common.h"
 
 namespace {
@@ -44,29 +49,18 @@ __device__ __forceinline__ long long edt_ld(const void* __restrict__ p, int byte
     return ((const long long*)p)[i];
 }
 
-// 1. grid: ceil(rows * G / 4) workgroups of 4 waves; wave id -> (row, g), g fastest so the G readers of a label row run together.
-// labels [N][D][H][W]; out [N][G][D][H][W]; rows = N * D * H; classes == nullptr: the one site set `label == 0` (a mask's zero voxels).
-__global__ void __launch_bounds__(256)
-edt_row_kernel(const void* __restrict__ labels, int bytes, const int* __restrict__ classes, int g0, int G, int complement,
-               long long rows, int DH, int W, float s, float* __restrict__ out) {
-    __shared__ unsigned long long smask[4][kEdtMaxRowChunks];
-    __shared__ int sleft[4][kEdtMaxRowChunks];
-    const int lane = threadIdx.x & 63, q = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const long long id = (long long)blockIdx.x * 4 + q;
-    const bool live = id < rows * G;                   // (a dead wave walks the loops with an empty predicate: every wave reaches the barrier)
-    const long long row = live ? id / G : 0;
-    const int g = live ? (int)(id % G) : 0;
-    const long long n = row / DH, dh = row % DH;
-    const long long cls = classes ? (long long)classes[g0 + g] : 0;
-    const long long src = row * W;                     // = (n DH + dh) W
-    const long long dst = ((n * G + g) * DH + dh) * W;
+// The W pass of one wave on one row: `site(w)` is the site predicate of voxel w of the row (called for w < W on a live wave only).  Shared by
+// the row kernels below, which differ in the predicate alone.
+template <typename Site>
+__device__ __forceinline__ void edt_row_body(Site site, bool live, int q, int lane, int W, float s, float* __restrict__ out, long long dst,
+                                             unsigned long long (*smask)[kEdtMaxRowChunks], int (*sleft)[kEdtMaxRowChunks]) {
     const int nch = (W + 63) >> 6;                     // <= kEdtMaxRowChunks (checked by the launchers)
     int carry = -1;                                    // wave-uniform: the last site before the chunk
     for (int c = 0; c < nch; ++c) {
         const int w = c * 64 + lane;
-        bool site = false;
-        if (live && w < W) site = (edt_ld(labels, bytes, src + w) == cls) != (complement != 0);
-        const unsigned long long m = __ballot(site);
+        bool is_site = false;
+        if (live && w < W) is_site = site(w);
+        const unsigned long long m = __ballot(is_site);
         if (lane == 0) { smask[q][c] = m; sleft[q][c] = carry; }
         if (m) carry = c * 64 + 63 - __clzll((long long)m);
     }
@@ -84,6 +78,64 @@ edt_row_kernel(const void* __restrict__ labels, int bytes, const int* __restrict
         if (live && w < W) out[dst + w] = d;
         if (m) rcarry = c * 64 + __ffsll((long long)m) - 1;
     }
+}
+
+// 1. grid: ceil(rows * G / 4) workgroups of 4 waves; wave id -> (row, g), g fastest so the G readers of a label row run together.
+// labels [N][D][H][W]; out [N][G][D][H][W]; rows = N * D * H; classes == nullptr: the one site set `label == 0` (a mask's zero voxels).
+__global__ void __launch_bounds__(256)
+edt_row_kernel(const void* __restrict__ labels, int bytes, const int* __restrict__ classes, int g0, int G, int complement,
+               long long rows, int DH, int W, float s, float* __restrict__ out) {
+    __shared__ unsigned long long smask[4][kEdtMaxRowChunks];
+    __shared__ int sleft[4][kEdtMaxRowChunks];
+    const int lane = threadIdx.x & 63, q = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const long long id = (long long)blockIdx.x * 4 + q;
+    const bool live = id < rows * G;                   // (a dead wave walks the loops with an empty predicate: every wave reaches the barrier)
+    const long long row = live ? id / G : 0;
+    const int g = live ? (int)(id % G) : 0;
+    const long long n = row / DH, dh = row % DH;
+    const long long cls = classes ? (long long)classes[g0 + g] : 0;
+    const long long src = row * W;                     // = (n DH + dh) W
+    const long long dst = ((n * G + g) * DH + dh) * W;
+    edt_row_body([&](int w) { return (edt_ld(labels, bytes, src + w) == cls) != (complement != 0); }, live, q, lane, W, s, out, dst, smask, sleft);
+}
+
+// Surface voxel of class `cls` (the centre voxel (d, h, w) of sample `base` / V is known to carry it): some neighbour under the connectivity
+// -- order 1 / 2 / 3 = 6 / 18 / 26 neighbours, scipy's generate_binary_structure(3, order) -- carries another label or lies outside the
+// volume; = A & ~binary_erosion(A, structure, border_value=0).  Every index is formed from coordinates checked against the extents, so
+// rows, planes and samples never wrap into each other.
+__device__ __forceinline__ bool edt_on_surface(const void* __restrict__ labels, int bytes, long long base, int d, int h, int w,
+                                               int D, int H, int W, int order, long long cls) {
+    for (int dd = -1; dd <= 1; ++dd)
+        for (int dh = -1; dh <= 1; ++dh)
+            for (int dw = -1; dw <= 1; ++dw) {
+                const int man = (dd != 0) + (dh != 0) + (dw != 0);
+                if (man == 0 || man > order) continue;
+                const int z = d + dd, y = h + dh, x = w + dw;
+                if (z < 0 || z >= D || y < 0 || y >= H || x < 0 || x >= W) return true;
+                if (edt_ld(labels, bytes, base + ((long long)z * H + y) * W + x) != cls) return true;
+            }
+    return false;
+}
+
+// 1s. the sibling of edt_row_kernel whose site set (n, c) is the SURFACE of class c in sample n, straight from the label map.
+__global__ void __launch_bounds__(256)
+edt_surface_row_kernel(const void* __restrict__ labels, int bytes, const int* __restrict__ classes, int g0, int G, int order,
+                       long long rows, int D, int H, int W, float s, float* __restrict__ out) {
+    __shared__ unsigned long long smask[4][kEdtMaxRowChunks];
+    __shared__ int sleft[4][kEdtMaxRowChunks];
+    const int lane = threadIdx.x & 63, q = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const long long id = (long long)blockIdx.x * 4 + q;
+    const bool live = id < rows * G;
+    const long long row = live ? id / G : 0;
+    const int g = live ? (int)(id % G) : 0;
+    const int DH = D * H;
+    const long long n = row / DH;
+    const int dh = (int)(row % DH), d = dh / H, h = dh % H;
+    const long long cls = (long long)classes[g0 + g];
+    const long long base = n * DH * W, src = row * W;
+    const long long dst = ((n * G + g) * DH + dh) * W;
+    edt_row_body([&](int w) { return edt_ld(labels, bytes, src + w) == cls && edt_on_surface(labels, bytes, base, d, h, w, D, H, W, order, cls); },
+                 live, q, lane, W, s, out, dst, smask, sleft);
 }
 
 // what the last pass does with a finished squared distance
@@ -225,21 +277,40 @@ int edt_group(int N, long long V, int Kp) {
     return G > (size_t)Kp ? Kp : (int)G;
 }
 
-// the three passes of G site sets: labels -> a -> b -> (epilogue) out
-int edt_passes(const void* labels, int bytes, const int* classes, int g0, int G, int complement, int N, int D, int H, int W,
-               float sD, float sH, float sW, float* a, float* b, float* out, EdtEpi e, hipStream_t st) {
-    const long long rows = (long long)N * D * H, HW = (long long)H * W;
-    const long long row_blocks = da_cdiv(rows * G, 4);
+// the H and D line passes of G site sets: a (the row pass's output) -> b -> (epilogue) out
+int edt_line_passes(int G, int N, int D, int H, int W, float sD, float sH, float* a, float* b, float* out, EdtEpi e, hipStream_t st) {
+    const long long HW = (long long)H * W;
     const int tiles_h = (int)da_cdiv(W, 64), tiles_d = (int)da_cdiv(HW, 64);
     const long long h_blocks = (long long)N * G * D * tiles_h, d_blocks = (long long)N * G * tiles_d;
-    if (row_blocks > 0x7FFFFFFFLL || h_blocks > 0x7FFFFFFFLL || d_blocks > 0x7FFFFFFFLL) return DA_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(edt_row_kernel, dim3((unsigned)row_blocks), dim3(256), 0, st, labels, bytes, classes, g0, G, complement, rows, D * H, W, sW, a);
-    DA_LAUNCH_CHECK();
+    if (h_blocks > 0x7FFFFFFFLL || d_blocks > 0x7FFFFFFFLL) return DA_ERR_UNSUPPORTED;
     const size_t lds_h = (size_t)(H < kEdtLineChunk ? H : kEdtLineChunk) * 64 * sizeof(float) + kEdtLineFlags;
     const size_t lds_d = (size_t)(D < kEdtLineChunk ? D : kEdtLineChunk) * 64 * sizeof(float) + kEdtLineFlags;
     int rc = da_launch_lds<edt_line_kernel<false>, kEdtLineLdsMax>(dim3((unsigned)h_blocks), dim3(256), lds_h, st, (const float*)a, b, b, tiles_h, H, W, sH, e);
     if (rc) return rc;
     return da_launch_lds<edt_line_kernel<true>, kEdtLineLdsMax>(dim3((unsigned)d_blocks), dim3(256), lds_d, st, (const float*)b, a, out, tiles_d, D, (int)HW, sD, e);
+}
+
+// the three passes of G site sets: labels -> a -> b -> (epilogue) out
+int edt_passes(const void* labels, int bytes, const int* classes, int g0, int G, int complement, int N, int D, int H, int W,
+               float sD, float sH, float sW, float* a, float* b, float* out, EdtEpi e, hipStream_t st) {
+    const long long rows = (long long)N * D * H;
+    const long long row_blocks = da_cdiv(rows * G, 4);
+    if (row_blocks > 0x7FFFFFFFLL) return DA_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(edt_row_kernel, dim3((unsigned)row_blocks), dim3(256), 0, st, labels, bytes, classes, g0, G, complement, rows, D * H, W, sW, a);
+    DA_LAUNCH_CHECK();
+    return edt_line_passes(G, N, D, H, W, sD, sH, a, b, out, e, st);
+}
+
+// ... and with the surfaces of the classes g0 .. g0 + G - 1 as the site sets; the squared distances end in `a` ([N][G][D][H][W])
+int edt_surface_passes(const void* labels, int bytes, const int* classes, int g0, int G, int order, int N, int D, int H, int W,
+                       float sD, float sH, float sW, float* a, float* b, hipStream_t st) {
+    const long long rows = (long long)N * D * H;
+    const long long row_blocks = da_cdiv(rows * G, 4);
+    if (row_blocks > 0x7FFFFFFFLL) return DA_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(edt_surface_row_kernel, dim3((unsigned)row_blocks), dim3(256), 0, st, labels, bytes, classes, g0, G, order, rows, D, H, W, sW, a);
+    DA_LAUNCH_CHECK();
+    EdtEpi e{0, nullptr, 0, nullptr, 0, 0, G, G, (long long)D * H * W};
+    return edt_line_passes(G, N, D, H, W, sD, sH, a, b, a, e, st);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -404,6 +475,266 @@ int bl_blocks(long long V, int L) {
     return work < kBlBlocks ? (int)work : kBlBlocks;
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------
+// surface-distance metrics of two label maps: Hausdorff, its percentile, ASSD
+// ------------------------------------------------------------------------------------------------------------------------------
+// Per sample n and class c = classes[j]:  d_PT = the distances of the surface voxels of P_c to the surface of T_c, d_TP the other way round.
+//   1. sd_count_kernel: the surface voxels of every class in both maps, integer atomics -> cnt[n][j][2].
+//   2. sd_scan_kernel: segment (n, j) of the pooled list holds cnt[n][j][0] + cnt[n][j][1] entries; the classes partition the voxels, so the
+//      list has at most 2 N V entries.
+//   3. per class group and direction: edt_surface_passes of the one map, then sd_gather_kernel reads the squared distances at the other map's
+//      surface voxels: sum of sqrt((double) d2) per thread -> workgroup -> partial[n][j][dir][block], the maximum of d2 by an integer atomic
+//      max on its bits, and the bits appended to the segment behind a slot range from the segment's integer cursor (one add per workgroup).
+//      The order inside a segment varies from run to run; everything downstream is a function of the segment as a multiset.
+//   4. sd_finish_kernel, one workgroup per segment: the partial sums in their fixed order, then a radix select on the bit patterns
+//      (non-negative floats order like their bits; 11 + 10 + 10 bits below the sign) for the two order statistics floor(h) and ceil(h) of the
+//      rank h = p / 100 (n - 1), both in one walk per round; roots and the interpolation in double.
+// Integer atomics only, no workgroup waits for another, every trip count is an extent, a segment length or the three select rounds.
+constexpr int kSdBlocks = 256;                         // workgroups per (sample, class) of the counting and gather passes, at most
+constexpr int kSdVoxPerBlock = 4096;                   // ... each takes a contiguous run of at least this many voxels
+constexpr int kSdBins = 2048;
+constexpr int kSdFinishThreads = 1024;                 // of the one workgroup that walks a segment's list three times
+
+__host__ __device__ inline int sd_blocks(long long V) {
+    const long long b = da_cdiv(V, kSdVoxPerBlock);
+    return b < kSdBlocks ? (int)b : kSdBlocks;
+}
+__host__ __device__ inline long long sd_run(long long V) { return da_cdiv(da_cdiv(V, sd_blocks(V)), 256) * 256; }     // voxels per workgroup
+
+// is voxel v of sample n a surface voxel of class cls in this map?
+__device__ __forceinline__ bool sd_surface_at(const void* __restrict__ labels, int bytes, long long n, long long v, long long V,
+                                              int D, int H, int W, int order, long long cls) {
+    if (edt_ld(labels, bytes, n * V + v) != cls) return false;
+    int d, h, w;
+    da_vox3(v, H, W, d, h, w);
+    return edt_on_surface(labels, bytes, n * V, d, h, w, D, H, W, order, cls);
+}
+
+// mask[n][v] = voxel v is a surface voxel of its own class.  grid-stride over N V.
+__global__ void __launch_bounds__(256)
+sd_label_surface_kernel(const void* __restrict__ labels, int bytes, long long total, int D, int H, int W, int order, unsigned char* __restrict__ mask) {
+    const long long V = (long long)D * H * W;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const long long n = i / V, v = i % V;
+        mask[i] = sd_surface_at(labels, bytes, n, v, V, D, H, W, order, edt_ld(labels, bytes, i)) ? 1 : 0;
+    }
+}
+
+// 1. grid (sd_blocks, Kp, N); cnt [N][Kp][2] (0: pred, 1: truth), zeroed by the launcher
+__global__ void __launch_bounds__(256)
+sd_count_kernel(const void* __restrict__ pred, int pbytes, const void* __restrict__ truth, int tbytes, const int* __restrict__ classes, int Kp,
+                int D, int H, int W, int order, unsigned* __restrict__ cnt) {
+    __shared__ unsigned scnt[2];
+    const long long V = (long long)D * H * W, run = sd_run(V);
+    const int j = blockIdx.y;
+    const long long n = blockIdx.z, cls = (long long)classes[j];
+    if (threadIdx.x < 2) scnt[threadIdx.x] = 0;
+    __syncthreads();
+    const long long lo = (long long)blockIdx.x * run, hi = lo + run < V ? lo + run : V;
+    unsigned cp = 0, ct = 0;
+    for (long long v = lo + threadIdx.x; v < hi; v += 256) {
+        cp += sd_surface_at(pred, pbytes, n, v, V, D, H, W, order, cls) ? 1u : 0u;
+        ct += sd_surface_at(truth, tbytes, n, v, V, D, H, W, order, cls) ? 1u : 0u;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { cp += __shfl_xor(cp, o); ct += __shfl_xor(ct, o); }
+    if ((threadIdx.x & 63) == 0) { if (cp) atomicAdd(&scnt[0], cp); if (ct) atomicAdd(&scnt[1], ct); }
+    __syncthreads();
+    if (threadIdx.x < 2 && scnt[threadIdx.x]) atomicAdd(cnt + ((size_t)n * Kp + j) * 2 + threadIdx.x, scnt[threadIdx.x]);
+}
+
+// 2. one workgroup: off[s] = the exclusive prefix sum of cnt[s][0] + cnt[s][1] over the S = N Kp segments; a thread owns a contiguous run of them
+__global__ void __launch_bounds__(256)
+sd_scan_kernel(const unsigned* __restrict__ cnt, long long S, unsigned long long* __restrict__ off) {
+    __shared__ unsigned long long tot[256];
+    const long long per = da_cdiv(S, 256), lo = (long long)threadIdx.x * per, hi = lo + per < S ? lo + per : S;
+    unsigned long long t = 0;
+    for (long long i = lo; i < hi; ++i) t += (unsigned long long)cnt[2 * i] + cnt[2 * i + 1];
+    tot[threadIdx.x] = t;
+    __syncthreads();
+    unsigned long long base = 0;
+    for (int i = 0; i < (int)threadIdx.x; ++i) base += tot[i];
+    for (long long i = lo; i < hi; ++i) { off[i] = base; base += (unsigned long long)cnt[2 * i] + cnt[2 * i + 1]; }
+}
+
+// 3. grid (sd_blocks, G, N).  d2 [N][G][V]: the squared distance to the surface of class classes[g0 + g] in the OTHER map; labels: the map
+// whose surface voxels are gathered (dir 0: pred, distances to truth; dir 1: truth, distances to pred).  Two walks over the workgroup's run of
+// voxels: the first counts each wave's surface voxels (ballots: a scalar sum), then ONE add on the segment's cursor reserves the workgroup's
+// slots -- a cursor shared by every workgroup of the segment takes about 88 adds a microsecond, and an add per wave and trip ran the pass at
+// that rate -- and the second walk stores wave after wave, trip after trip, lane after lane behind it.
+__global__ void __launch_bounds__(256)
+sd_gather_kernel(const float* __restrict__ d2, const void* __restrict__ labels, int bytes, const int* __restrict__ classes, int g0, int Kp, int dir,
+                 int D, int H, int W, int order, const unsigned* __restrict__ cnt, const unsigned long long* __restrict__ off,
+                 unsigned* __restrict__ cursor, unsigned* __restrict__ list, unsigned* __restrict__ maxbits, double* __restrict__ partial) {
+    __shared__ double red[4];
+    __shared__ unsigned smax, swave[4], sbase;
+    const long long V = (long long)D * H * W, run = sd_run(V);
+    const int g = blockIdx.y, G = gridDim.y, j = g0 + g, lane = threadIdx.x & 63, q = threadIdx.x >> 6;
+    const long long n = blockIdx.z, cls = (long long)classes[j];
+    const size_t seg = (size_t)n * Kp + j;
+    const unsigned seg_len = cnt[2 * seg] + cnt[2 * seg + 1];
+    unsigned* seg_list = list + off[seg];
+    const float* dn = d2 + ((size_t)n * G + g) * V;
+    if (threadIdx.x == 0) smax = 0;
+    const long long lo = (long long)blockIdx.x * run;
+    unsigned mine = 0;                                                     // wave-uniform: the wave's surface voxels
+    for (long long v0 = lo; v0 < lo + run && v0 < V; v0 += 256) {
+        const long long v = v0 + threadIdx.x;
+        mine += (unsigned)__popcll(__ballot(v < V && sd_surface_at(labels, bytes, n, v, V, D, H, W, order, cls)));
+    }
+    if (lane == 0) swave[q] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned total = swave[0] + swave[1] + swave[2] + swave[3];
+        sbase = total ? atomicAdd(cursor + seg, total) : 0;
+    }
+    __syncthreads();
+    unsigned slot0 = sbase;                                                // wave-uniform: the wave's next free slot
+    for (int i = 0; i < q; ++i) slot0 += swave[i];
+    double sum = 0.0;
+    unsigned mx = 0;
+    for (long long v0 = lo; v0 < lo + run && v0 < V; v0 += 256) {
+        const long long v = v0 + threadIdx.x;
+        const bool on = v < V && sd_surface_at(labels, bytes, n, v, V, D, H, W, order, cls);
+        const unsigned long long m = __ballot(on);
+        if (on) {
+            const float x = dn[v];
+            const unsigned bits = __float_as_uint(x);
+            const unsigned slot = slot0 + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
+            if (slot < seg_len) seg_list[slot] = bits;                     // (always true: the counting pass saw the same voxels)
+            sum += sqrt((double)x);
+            mx = bits > mx ? bits : mx;
+        }
+        slot0 += (unsigned)__popcll(m);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const unsigned t = __shfl_xor(mx, o); mx = t > mx ? t : mx; }
+    if (lane == 0 && mx) atomicMax(&smax, mx);
+    const double bs = da_block_sum(sum, red);                              // (its barriers order smax too)
+    if (threadIdx.x == 0) {
+        partial[(seg * 2 + dir) * kSdBlocks + blockIdx.x] = bs;
+        if (smax) atomicMax(maxbits + seg * 2 + dir, smax);
+    }
+}
+
+// the bin of `hist` that holds rank r (0-based, below the histogram's total), by one wave: lane l owns the bins [32 l, 32 l + 32).
+// Returns the bin and leaves the rank inside it in r.
+__device__ __forceinline__ int sd_pick_bin(const unsigned* hist, unsigned& r, int lane) {
+    constexpr int per = kSdBins / 64;
+    unsigned own = 0;
+    for (int i = 0; i < per; ++i) own += hist[lane * per + i];
+    unsigned incl = own;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const unsigned t = __shfl_up(incl, o); if (lane >= o) incl += t; }
+    const unsigned long long m = __ballot(r < incl);
+    const int L = m ? __ffsll((long long)m) - 1 : 63;
+    unsigned below = __shfl(incl - own, L);
+    int bin = L * per;
+    for (int i = 0; i < per - 1; ++i) {                                    // wave-uniform walk of lane L's bins
+        const unsigned c = hist[L * per + i];
+        if (r < below + c) break;
+        below += c;
+        bin = L * per + i + 1;
+    }
+    r -= below;
+    return bin;
+}
+
+// 4. grid N Kp.  out [N][Kp][7] = n_pred, n_truth, hd, hd_pct, assd, asd_pred_truth, asd_truth_pred
+__global__ void __launch_bounds__(kSdFinishThreads)
+sd_finish_kernel(const unsigned* __restrict__ cnt, const unsigned long long* __restrict__ off, const unsigned* __restrict__ list,
+                 const unsigned* __restrict__ maxbits, const double* __restrict__ partial, int nblocks, double pct, double* __restrict__ out) {
+    __shared__ double red[kSdFinishThreads / 64];
+    __shared__ unsigned hist[2][kSdBins];
+    __shared__ unsigned sprefix[2], srank[2];
+    __shared__ double ssum[2];
+    const size_t seg = blockIdx.x;
+    const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
+    const unsigned np = cnt[2 * seg], nt = cnt[2 * seg + 1];
+    double* o = out + seg * 7;
+    if (np == 0 || nt == 0) {                                              // (block-uniform) the class is absent from a map: no distance is defined
+        if (threadIdx.x == 0) { o[0] = (double)np; o[1] = (double)nt; for (int i = 2; i < 7; ++i) o[i] = __longlong_as_double(0x7FF8000000000000LL); }
+        return;
+    }
+    for (int dir = 0; dir < 2; ++dir) {
+        double s = 0.0;
+        for (int i = threadIdx.x; i < nblocks; i += kSdFinishThreads) s += partial[(seg * 2 + dir) * kSdBlocks + i];
+        s = da_block_sum(s, red);
+        if (threadIdx.x == 0) ssum[dir] = s;
+    }
+    const unsigned len = np + nt;
+    const double h = pct / 100.0 * (double)(len - 1);
+    const double hf = floor(h);
+    if (threadIdx.x < 2) {
+        unsigned r = (unsigned)hf + (threadIdx.x == 1 && h > hf ? 1u : 0u);
+        srank[threadIdx.x] = r < len ? r : len - 1;
+        sprefix[threadIdx.x] = 0;
+    }
+    const unsigned* x = list + off[seg];
+    unsigned himask = 0;                                                   // the bits the earlier rounds have fixed
+    for (int round = 0; round < 3; ++round) {
+        const int shift = round == 0 ? 20 : round == 1 ? 10 : 0;
+        const unsigned binmask = round == 0 ? 0x7FFu : 0x3FFu;
+        for (int i = threadIdx.x; i < 2 * kSdBins; i += kSdFinishThreads) (&hist[0][0])[i] = 0;
+        __syncthreads();
+        const unsigned p0 = sprefix[0], p1 = sprefix[1];
+        const bool same = p0 == p1;                                        // both ranks are still in one bucket: one histogram serves both
+        for (unsigned i0 = 0; i0 < len; i0 += kSdFinishThreads) {
+            const unsigned i = i0 + threadIdx.x;
+            const bool in = i < len;
+            const unsigned v = in ? x[i] : 0;
+            const unsigned hi = v & himask, bin = (v >> shift) & binmask;
+            const bool a0 = in && hi == p0, a1 = in && !same && hi == p1;
+            // most entries of a wave fall into one bin (distances 0 and 1): its lanes are counted by a ballot, the others add on their own
+            const unsigned long long m0 = __ballot(a0);
+            if (m0) {
+                const unsigned lead = (unsigned)__shfl((int)bin, __ffsll((long long)m0) - 1);
+                const unsigned long long eq = __ballot(a0 && bin == lead);
+                if (lane == 0) atomicAdd(&hist[0][lead], (unsigned)__popcll(eq));
+                if (a0 && bin != lead) atomicAdd(&hist[0][bin], 1u);
+            }
+            if (a1) atomicAdd(&hist[1][bin], 1u);
+        }
+        __syncthreads();
+        if (q < 2) {                                                       // wave 0 picks the lower rank's bin, wave 1 the upper's
+            unsigned r = srank[q];
+            const int bin = sd_pick_bin(hist[same ? 0 : q], r, lane);
+            if (lane == 0) { srank[q] = r; sprefix[q] = (q == 0 ? p0 : p1) | ((unsigned)bin << shift); }
+        }
+        himask |= binmask << shift;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double xl = sqrt((double)__uint_as_float(sprefix[0])), xh = sqrt((double)__uint_as_float(sprefix[1]));
+        const unsigned mb = maxbits[2 * seg] > maxbits[2 * seg + 1] ? maxbits[2 * seg] : maxbits[2 * seg + 1];
+        const double apt = ssum[0] / (double)np, atp = ssum[1] / (double)nt;
+        o[0] = (double)np;
+        o[1] = (double)nt;
+        o[2] = sqrt((double)__uint_as_float(mb));
+        o[3] = xl + (h - hf) * (xh - xl);
+        o[4] = (apt + atp) / 2.0;
+        o[5] = apt;
+        o[6] = atp;
+    }
+}
+
+int sd_order(int connectivity) { return connectivity == 6 ? 1 : connectivity == 18 ? 2 : connectivity == 26 ? 3 : 0; }
+
+// the workspace behind the two transform buffers: list | cnt | cursor | maxbits | off | partial
+struct SdWs { size_t list, cnt, cursor, maxbits, off, partial, total; };
+SdWs sd_layout(int N, int Kp, long long V, size_t edt_bytes) {
+    const size_t S = (size_t)N * Kp;
+    SdWs w;
+    w.list = edt_bytes;
+    w.cnt = w.list + da_align(2 * (size_t)N * (size_t)V * sizeof(unsigned));
+    w.cursor = w.cnt + S * 2 * sizeof(unsigned);                           // cnt, cursor and maxbits are zeroed together
+    w.maxbits = w.cursor + S * sizeof(unsigned);
+    w.off = da_align(w.maxbits + S * 2 * sizeof(unsigned));
+    w.partial = da_align(w.off + S * sizeof(unsigned long long));
+    w.total = da_align(w.partial + S * 2 * kSdBlocks * sizeof(double));
+    return w;
+}
+
 }  // namespace
 
 extern "C" size_t da_edt_ws_bytes(int N, int Kp, int D, int H, int W) {
@@ -483,6 +814,68 @@ extern "C" int da_boundary_loss_bwd(const float* logits, const float* phi, const
         default: hipLaunchKernelGGL(bl_bwd_kernel, dim3(nblocks, N), dim3(256), 0, st, logits, phi, slots, dloss, scale, V, K, Kp, dlogits);
     }
 #undef BL_BWD
+    DA_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int da_label_surface(const void* labels, int label_bytes, int N, int D, int H, int W, int connectivity, unsigned char* mask, void* stream) {
+    if (!labels || !mask || !edt_bytes_ok(label_bytes) || !sd_order(connectivity)) return DA_ERR_BADARG;
+    if (const int rc = edt_extents(N, D, H, W)) return rc;
+    const long long total = (long long)N * D * H * W;
+    hipLaunchKernelGGL(sd_label_surface_kernel, dim3(da_grid(total, 256)), dim3(256), 0, da_stream(stream), labels, label_bytes, total, D, H, W,
+                       sd_order(connectivity), mask);
+    DA_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t da_surface_dist_ws_bytes(int N, int Kp, int D, int H, int W) {
+    const size_t edt_bytes = da_edt_ws_bytes(N, Kp, D, H, W);
+    if (!edt_bytes || Kp > 65535 || (long long)N * Kp > 0x7FFFFFFFLL) return 0;
+    return sd_layout(N, Kp, (long long)D * H * W, edt_bytes).total;
+}
+
+extern "C" int da_surface_dist_stats(const void* pred, int pred_bytes, const void* truth, int truth_bytes, const int* classes, int Kp,
+                                     int N, int D, int H, int W, float sD, float sH, float sW, int connectivity, double percentile,
+                                     double* stats, void* ws, size_t ws_bytes, void* stream) {
+    if (!pred || !truth || !classes || !stats || !ws || Kp < 1 || !edt_bytes_ok(pred_bytes) || !edt_bytes_ok(truth_bytes) || !sd_order(connectivity) ||
+        !edt_spacing_ok(sD) || !edt_spacing_ok(sH) || !edt_spacing_ok(sW) || !(percentile > 0.0 && percentile <= 100.0))
+        return DA_ERR_BADARG;
+    if (const int rc = edt_extents(N, D, H, W)) return rc;
+    if (Kp > 65535 || (long long)N * Kp > 0x7FFFFFFFLL) return DA_ERR_UNSUPPORTED;      // grid dimensions of the counting and the finishing pass
+    if (ws_bytes < da_surface_dist_ws_bytes(N, Kp, D, H, W)) return DA_ERR_WS_SMALL;
+    hipStream_t st = da_stream(stream);
+    const long long V = (long long)D * H * W;
+    const int G = edt_group(N, V, Kp), order = sd_order(connectivity), nb = sd_blocks(V);
+    const SdWs w = sd_layout(N, Kp, V, da_edt_ws_bytes(N, Kp, D, H, W));
+    char* base = (char*)ws;
+    float* a = (float*)base;
+    float* b = (float*)(base + da_align((size_t)N * G * (size_t)V * sizeof(float)));
+    unsigned* list = (unsigned*)(base + w.list);
+    unsigned* cnt = (unsigned*)(base + w.cnt);
+    unsigned* cursor = (unsigned*)(base + w.cursor);
+    unsigned* maxbits = (unsigned*)(base + w.maxbits);
+    unsigned long long* off = (unsigned long long*)(base + w.off);
+    double* partial = (double*)(base + w.partial);
+    const long long S = (long long)N * Kp;
+    if (const hipError_t e = hipMemsetAsync(cnt, 0, (size_t)S * 5 * sizeof(unsigned), st)) return (int)e;
+    hipLaunchKernelGGL(sd_count_kernel, dim3(nb, Kp, N), dim3(256), 0, st, pred, pred_bytes, truth, truth_bytes, classes, Kp, D, H, W, order, cnt);
+    DA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sd_scan_kernel, dim3(1), dim3(256), 0, st, (const unsigned*)cnt, S, off);
+    DA_LAUNCH_CHECK();
+    for (int g0 = 0; g0 < Kp; g0 += G) {
+        const int g = Kp - g0 < G ? Kp - g0 : G;
+        for (int dir = 0; dir < 2; ++dir) {                                // 0: sites on truth, gathered on pred; 1: the other way
+            const void* site = dir ? pred : truth;
+            const void* at = dir ? truth : pred;
+            const int site_bytes = dir ? pred_bytes : truth_bytes, at_bytes = dir ? truth_bytes : pred_bytes;
+            if (const int rc = edt_surface_passes(site, site_bytes, classes, g0, g, order, N, D, H, W, sD, sH, sW, a, b, st)) return rc;
+            hipLaunchKernelGGL(sd_gather_kernel, dim3(nb, g, N), dim3(256), 0, st, (const float*)a, at, at_bytes, classes, g0, Kp, dir, D, H, W, order,
+                               (const unsigned*)cnt, (const unsigned long long*)off, cursor, list, maxbits, partial);
+            DA_LAUNCH_CHECK();
+        }
+    }
+    hipLaunchKernelGGL(sd_finish_kernel, dim3((unsigned)S), dim3(kSdFinishThreads), 0, st, (const unsigned*)cnt, (const unsigned long long*)off, (const unsigned*)list,
+                       (const unsigned*)maxbits, (const double*)partial, nb, percentile, stats);
     DA_LAUNCH_CHECK();
     return 0;
 }

@@ -397,3 +397,52 @@ def postprocess_labels(pred, n_class, post, return_stats=False):
     if post['mode'] == 'largest_cc':
         return ops.keep_largest_component(pred, n_class, connectivity=post['connectivity'], return_stats=return_stats)
     return ops.remove_small_components(pred, n_class, post['min_size'], connectivity=post['connectivity'], return_stats=return_stats)
+
+
+SURFACE_METRIC_KEYS = ('spacing', 'connectivity', 'percentile', 'classes')
+
+
+def parse_surface_metrics(spec):
+    """config['surface_metrics'] -> None (off) or the keyword dict of surface_distances.  Accepted: None, True, or a dict with any of the
+    keys `spacing` (sD, sH, sW), `connectivity` (6 / 18 / 26), `percentile` (in (0, 100]) and `classes`; the defaults are unit spacing,
+    6, 95 and the classes 1 .. n_class - 1."""
+    if spec is None or spec is False:
+        return None
+    if spec is True:
+        spec = {}
+    if not isinstance(spec, dict):
+        raise ValueError('surface_metrics must be None, True or a dict, got %r' % (spec,))
+    unknown = set(spec) - set(SURFACE_METRIC_KEYS)
+    if unknown:
+        raise ValueError('surface_metrics: unknown keys %s' % sorted(unknown))
+    connectivity = spec.get('connectivity', 6)
+    if connectivity not in ops.SURFACE_CONNECTIVITIES:
+        raise ValueError('surface_metrics connectivity must be 6, 18 or 26, got %r' % (connectivity,))
+    percentile = float(spec.get('percentile', 95.0))
+    if not 0.0 < percentile <= 100.0:
+        raise ValueError('surface_metrics percentile must be in (0, 100], got %r' % (spec.get('percentile'),))
+    spacing = tuple(float(v) for v in spec.get('spacing', (1.0, 1.0, 1.0)))
+    if len(spacing) != 3 or not all(0.0 < v < float('inf') for v in spacing):
+        raise ValueError('surface_metrics spacing must be three positive finite numbers, got %r' % (spec.get('spacing'),))
+    classes = spec.get('classes')
+    return {'spacing': spacing, 'connectivity': int(connectivity), 'percentile': percentile,
+            'classes': None if classes is None else [int(c) for c in classes]}
+
+
+def surface_distances(pred, truth, n_class, **kw):
+    """Surface-distance metrics per sample and class (ops.surface_distance_stats, on the device): a dict of numpy arrays [N][K'], one per
+    column of ops.SURFACE_STATS -- the surface voxel counts `n_pred` and `n_truth` (int64), and `hd`, `hd_pct` (the `percentile`-th
+    percentile, HD95 by default), `assd`, `asd_pred_truth`, `asd_truth_pred` (float64, NaN where the class is absent from either map).
+    pred: logits N x C x D x H x W (argmaxed as eval_dice_counts does) or a label map N x D x H x W; truth: a label map.
+    kw: classes, spacing, connectivity, percentile."""
+    truth = truth.to(pred.device)
+    if truth.dtype not in (torch.uint8, torch.int32, torch.int64):
+        truth = truth.long()
+    if pred.dim() == 5:
+        pred = eval_dice_counts(pred, truth)[1]
+    truth = truth.reshape(pred.shape)
+    s = ops.surface_distance_stats(pred, truth, n_class, **kw).cpu().numpy()
+    out = {name: s[:, :, i].copy() for i, name in enumerate(ops.SURFACE_STATS)}
+    out['n_pred'] = out['n_pred'].astype(np.int64)
+    out['n_truth'] = out['n_truth'].astype(np.int64)
+    return out

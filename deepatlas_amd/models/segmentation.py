@@ -247,8 +247,15 @@ class SegmentationExperiment(BaseExperiment):
         With config['postprocess'] set (lib/evalMetrics.py parse_postprocess: 'largest_cc', or a dict with mode / connectivity / min_size) the
         argmax label map is additionally cleaned on the device (ops.keep_largest_component / remove_small_components) and scored again; those
         numbers go to self.eval_extra (post_dice_per_class, post_dice_avg, components_per_class, removed_frac).  The return value, and with it
-        model selection, the scheduler and best_score, stay on the raw Dice."""
+        model selection, the scheduler and best_score, stay on the raw Dice.
+        With config['surface_metrics'] set (lib/evalMetrics.py parse_surface_metrics: True, or a dict with spacing / connectivity / percentile /
+        classes) the argmax label map is also scored by its surface distances on the device (ops.surface_distance_stats): self.eval_extra
+        gains hd95_per_class, assd_per_class, hd_per_class (NaN-means over the volumes), hd95_avg and assd_avg (NaN-means over the classes)
+        and surface_undefined_frac (the share of (volume, class) pairs without a defined distance); with `postprocess` as well, the same for
+        the cleaned map under post_*.  The return value does not change."""
         post = metrics.parse_postprocess(self.config.get('postprocess'))
+        surf = metrics.parse_surface_metrics(self.config.get('surface_metrics'))
+        surf_raw, surf_post = [], []                                               # per batch: the dicts of metrics.surface_distances
         n_class = self.config["n_classes"]
         self.eval_extra = {}
         with torch.no_grad():
@@ -261,18 +268,23 @@ class SegmentationExperiment(BaseExperiment):
             pred = images = truths = None
             for j, (images, truths, name) in enumerate(dataloader):
                 pred = self.model(images.to(self.device))
-                if post is None:
+                if post is None and surf is None:
                     d = metrics.metricEval('dice', pred, truths.to(self.device))   # [N][C-1]
                 else:
                     truth = truths.to(self.device)
                     counts, lab = metrics.eval_dice_counts(pred, truth)            # the counts metricEval('dice', ...) is computed from
                     d = metrics.dice_from_counts(counts)[:, 1:]
+                    if surf is not None:
+                        surf_raw.append(metrics.surface_distances(lab, truth, n_class, **surf))
+                if post is not None:
                     clean, stats = metrics.postprocess_labels(lab, n_class, post, return_stats=True)
                     pc = ops.label_overlap_counts(clean, truth, n_class)
                     post_dice += torch.from_numpy(metrics.dice_from_counts(pc)[:, 1:].sum(0))
                     components += stats[:, 1:, 0].sum(0).cpu().numpy()
                     kept += int(pc[:, 1:, 0].sum())
                     total += int(counts[:, 1:, 0].sum())
+                    if surf is not None:
+                        surf_post.append(metrics.surface_distances(clean, truth, n_class, **surf))
                 dice_per_class += torch.from_numpy(d.sum(0))
                 n_vol += d.shape[0]                                                # average over VOLUMES (loaders may batch > 1)
             dice_per_class = (dice_per_class / max(n_vol, 1)).float()
@@ -282,16 +294,47 @@ class SegmentationExperiment(BaseExperiment):
                 self.eval_extra = {'post_dice_per_class': post_dice, 'post_dice_avg': post_dice.mean(),
                                    'components_per_class': components / max(n_vol, 1),      # per class, averaged over the volumes
                                    'removed_frac': (total - kept) / float(total) if total else 0.0}
+            if surf_raw:
+                self.eval_extra.update(self._surface_summary(surf_raw, ''))
+            if surf_post:
+                self.eval_extra.update(self._surface_summary(surf_post, 'post_'))
             sample_for_vis = {'img': images, 'truth': truths, 'pred': pred}
         return dice_per_class, dice_avg, sample_for_vis
 
-    def _post_suffix(self):
-        """', post-processed Dice Avg: x.xxxx (n.n components / class)' after an eval with config['postprocess'], else ''."""
-        extra = getattr(self, 'eval_extra', None)
-        if not extra:
+    @staticmethod
+    def _surface_summary(batches, prefix):
+        """The eval_extra entries of one label map's surface distances: `batches` = metrics.surface_distances of every batch."""
+        cols = {k: np.concatenate([b[k] for b in batches], 0) for k in ('hd_pct', 'assd', 'hd')}       # [volumes][K']
+
+        def nanmean(a, axis=None):                                                 # (np.nanmean warns on an all-NaN slice)
+            ok = ~np.isnan(a)
+            with np.errstate(invalid='ignore', divide='ignore'):
+                return np.where(ok, a, 0.0).sum(axis) / ok.sum(axis)
+        out = {prefix + 'hd95_per_class': nanmean(cols['hd_pct'], 0), prefix + 'assd_per_class': nanmean(cols['assd'], 0),
+               prefix + 'hd_per_class': nanmean(cols['hd'], 0)}
+        out[prefix + 'hd95_avg'] = float(nanmean(out[prefix + 'hd95_per_class']))
+        out[prefix + 'assd_avg'] = float(nanmean(out[prefix + 'assd_per_class']))
+        out[prefix + 'surface_undefined_frac'] = float(np.isnan(cols['assd']).mean())
+        return out
+
+    def _surface_suffix(self):
+        """', HD95 Avg: x.xx, ASSD Avg: x.xx' after an eval with config['surface_metrics'], else ''."""
+        extra = getattr(self, 'eval_extra', None) or {}
+        if 'hd95_avg' not in extra:
             return ''
-        return ', post-processed Dice Avg: {:.4f} ({:.1f} components / class)'.format(float(extra['post_dice_avg']),
+        return ', HD95 Avg: {:.2f}, ASSD Avg: {:.2f}'.format(extra['hd95_avg'], extra['assd_avg'])
+
+    def _post_suffix(self):
+        """', post-processed Dice Avg: x.xxxx (n.n components / class)' after an eval with config['postprocess'] (followed by the cleaned
+        map's ', HD95 Avg: x.xx, ASSD Avg: x.xx' with config['surface_metrics'] as well), else ''."""
+        extra = getattr(self, 'eval_extra', None) or {}
+        if 'post_dice_avg' not in extra:
+            return ''
+        text = ', post-processed Dice Avg: {:.4f} ({:.1f} components / class)'.format(float(extra['post_dice_avg']),
                                                                                      float(np.mean(extra['components_per_class'])))
+        if 'post_hd95_avg' in extra:
+            text += ', HD95 Avg: {:.2f}, ASSD Avg: {:.2f}'.format(extra['post_hd95_avg'], extra['post_assd_avg'])
+        return text
 
     def validate(self):
         if self.current_epoch % self.config['valid_epoch_period'] == 0:
@@ -311,7 +354,7 @@ class SegmentationExperiment(BaseExperiment):
             if self.writer is not None:
                 self.writer.add_scalar('validation_{}/dice_avg'.format(self.config['data']), dice_avg, global_step=self.global_step)
             print("Validation: Dice Avg: {:.4f} ({:.3f} sec) {}{}".format(float(dice_avg), time.time() - start_time,
-                                                                           datetime.datetime.now().strftime("%D %H:%M:%S"), self._post_suffix()))
+                                                                           datetime.datetime.now().strftime("%D %H:%M:%S"), self._surface_suffix() + self._post_suffix()))
             if self.current_epoch % self.config['save_ckpts_epoch_period'] == 0:
                 self.save_checkpoint({'epoch': self.current_epoch,
                                       'model_state_dict': self.model.state_dict(),
@@ -326,5 +369,5 @@ class SegmentationExperiment(BaseExperiment):
         last_epoch, best_score = self.initialize_model(self.model, optimizer=None, ckpoint_path=ckpoint_file)
         loader = self.config.get('testing_data_loader') or self.validation_data_loader
         dice_per_class, dice_avg, samples = self.eval(loader)
-        print('Testing Model: {} ({} epochs)  Dice_avg: {}{}'.format(ckpoint_file, last_epoch, float(dice_avg), self._post_suffix()))
+        print('Testing Model: {} ({} epochs)  Dice_avg: {}{}'.format(ckpoint_file, last_epoch, float(dice_avg), self._surface_suffix() + self._post_suffix()))
         return dice_per_class, dice_avg

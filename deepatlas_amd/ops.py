@@ -3016,3 +3016,73 @@ class BoundaryLossFn(Function):
         with torch.cuda.device(a.device):
             call('da_boundary_loss_bwd', ptr(a), ptr(p), ptr(slots), ptr(gl), N, V, K, Kp, ptr(dx), stream())
         return ncdhw(dx), None, None
+
+
+# ------------------------------------------------------------------------------------------------
+# surface-distance metrics of two label maps: Hausdorff, its percentile, ASSD (csrc/edt.hip)
+# ------------------------------------------------------------------------------------------------
+SURFACE_STATS = ('n_pred', 'n_truth', 'hd', 'hd_pct', 'assd', 'asd_pred_truth', 'asd_truth_pred')
+SURFACE_CONNECTIVITIES = (6, 18, 26)      # scipy.ndimage.generate_binary_structure(3, 1 | 2 | 3)
+SURFACE_MAX_CLASSES = 65535               # entries of a class list: a grid dimension of the counting pass
+
+
+def _surface_connectivity(connectivity):
+    if connectivity not in SURFACE_CONNECTIVITIES:
+        raise ValueError('connectivity must be 6, 18 or 26, got %r' % (connectivity,))
+    return int(connectivity)
+
+
+def _surface_labels(t, what):
+    if not torch.is_tensor(t) or t.dtype not in _LABEL_BYTES:
+        raise ValueError('%s must be a uint8, int32 or int64 tensor, got %s' % (what, getattr(t, 'dtype', type(t)),))
+    return _edt_extents(t, what)
+
+
+def label_surface(labels, connectivity=6):
+    """Bool mask N x D x H x W: the voxel is a surface voxel of its own label -- it has a neighbour under the connectivity (6, 18 or 26) with
+    another label or outside the volume; for every label c the mask restricted to c is A & ~scipy.ndimage.binary_erosion(A, structure) with
+    A = (labels == c).  labels: uint8, int32 or int64; the predicate is the one surface_distance_stats measures between."""
+    N, D, H, W = _surface_labels(labels, 'labels')
+    conn = _surface_connectivity(connectivity)
+    nat.require_cuda(labels)
+    lab = labels.contiguous()
+    out = torch.empty((N, D, H, W), dtype=torch.uint8, device=lab.device)
+    with torch.cuda.device(lab.device):
+        call('da_label_surface', ptr(lab), _LABEL_BYTES[lab.dtype], N, D, H, W, conn, ptr(out), stream())
+    return out.view(torch.bool)
+
+
+def surface_distance_stats(pred, truth, n_class, classes=None, spacing=(1, 1, 1), connectivity=6, percentile=95.0):
+    """Surface-distance metrics of two index label maps N x D x H x W (uint8, int32 or int64, each its own; views are accepted), one row per
+    sample and class of `classes` (default 1 .. n_class - 1): float64 N x K' x 7 on the device, columns SURFACE_STATS.
+    With d_PT the Euclidean distances, under `spacing` = (sD, sH, sW), of the surface voxels (label_surface) of class c in `pred` to the
+    nearest surface voxel of class c in `truth`, and d_TP the other way:  hd = max(max d_PT, max d_TP);  hd_pct = numpy's linear percentile
+    of the pooled d_PT and d_TP;  asd_pred_truth = mean d_PT, asd_truth_pred = mean d_TP, assd their mean (medpy's hd, hd95, asd, assd).
+    n_pred and n_truth are the surface voxel counts; where a class is absent from either map of a sample the five metrics are NaN.
+    Labels outside [0, n_class) belong to no class.  Exact at unit spacing, bit-identical from run to run.  No autograd."""
+    N, D, H, W = _surface_labels(pred, 'pred')
+    _surface_labels(truth, 'truth')
+    if tuple(pred.shape) != tuple(truth.shape):
+        raise ValueError('pred is %s and truth is %s: the shapes must agree' % (tuple(pred.shape), tuple(truth.shape)))
+    cl = _boundary_classes(n_class, classes)
+    if len(cl) > SURFACE_MAX_CLASSES:
+        raise ValueError('at most %d classes per call, got %d' % (SURFACE_MAX_CLASSES, len(cl)))
+    sp = _edt_spacing(spacing)
+    conn = _surface_connectivity(connectivity)
+    try:
+        pct = float(percentile)
+    except (TypeError, ValueError):
+        raise ValueError('percentile must be a number in (0, 100], got %r' % (percentile,))
+    if not 0.0 < pct <= 100.0:
+        raise ValueError('percentile must be in (0, 100], got %r' % (percentile,))
+    nat.require_cuda(pred, truth)
+    if truth.device != pred.device:
+        raise ValueError('pred is on %s and truth on %s' % (pred.device, truth.device))
+    p, t = pred.contiguous(), truth.contiguous()
+    cls = torch.tensor(cl, dtype=torch.int32, device=p.device)
+    out = torch.empty((N, len(cl), len(SURFACE_STATS)), dtype=torch.float64, device=p.device)
+    with torch.cuda.device(p.device):
+        wp, wn = _ws(nat.lib().da_surface_dist_ws_bytes(N, len(cl), D, H, W), p)
+        call('da_surface_dist_stats', ptr(p), _LABEL_BYTES[p.dtype], ptr(t), _LABEL_BYTES[t.dtype], ptr(cls), len(cl), N, D, H, W,
+             sp[0], sp[1], sp[2], conn, pct, ptr(out), wp, wn, stream())
+    return out

@@ -737,6 +737,27 @@ int da_boundary_loss_fwd(const float* logits, const float* phi, const int* slots
 int da_boundary_loss_bwd(const float* logits, const float* phi, const int* slots /*[K]*/, const float* dloss, int N, long long V, int K, int Kp,
                          float* dlogits, void* stream);
 
+/* ---- surface-distance metrics of two label maps (edt.hip): Hausdorff distance, its percentile (HD95) and the average symmetric surface
+ *      distance, medpy's conventions.  No reference call site: these replace a host copy, scipy.ndimage.binary_erosion and two
+ *      distance_transform_edt per class and volume. ---------- */
+/* A surface voxel of class c is a voxel with label c that has a neighbour under the connectivity (6, 18 or 26: scipy's
+ * generate_binary_structure(3, 1 | 2 | 3)) with another label or outside the volume.  For c = classes[j] and sample n, d_PT are the Euclidean
+ * distances, under the spacing, of the surface voxels of pred's class c to the nearest surface voxel of truth's class c, d_TP the other way.
+ * stats [N][Kp][7] double = n_pred, n_truth (the surface voxel counts), hd = max(max d_PT, max d_TP), hd_pct = numpy's linear percentile of
+ * the pooled d_PT and d_TP, assd = (mean d_PT + mean d_TP) / 2, mean d_PT, mean d_TP; the last five are NaN where the class is absent from
+ * either map of the sample.  The distances come from the transform above with the surfaces as site sets, in class groups as the signed
+ * maps; the order statistics from a radix select on the float32 bit patterns of the squared distances, the sums from a fixed order in
+ * double: integer atomics only, bit-identical from run to run.  pred and truth are [N][D][H][W], uint8 (1), int32 (4) or int64 (8) each;
+ * a label that is in no entry of `classes` belongs to no class.
+ * da_label_surface: mask [N][D][H][W] uint8 = the voxel is a surface voxel of its own label.
+ * A NULL pointer, bytes not 1 / 4 / 8, a connectivity other than 6 / 18 / 26, a percentile outside (0, 100], a bad spacing, extent or Kp
+ * return DA_ERR_BADARG before any launch, a short workspace DA_ERR_WS_SMALL; extents the transform refuses or Kp > 65535 DA_ERR_UNSUPPORTED. */
+int da_label_surface(const void* labels, int label_bytes, int N, int D, int H, int W, int connectivity, unsigned char* mask, void* stream);
+size_t da_surface_dist_ws_bytes(int N, int Kp, int D, int H, int W);
+int da_surface_dist_stats(const void* pred, int pred_bytes, const void* truth, int truth_bytes, const int* classes /*[Kp]*/, int Kp,
+                          int N, int D, int H, int W, float sD, float sH, float sW, int connectivity, double percentile,
+                          double* stats /*[N][Kp][7]*/, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- optimiser (models/segmentation.py:91 torch.optim.Adam defaults) -------------------------- */
 int da_adam_step(float* p, const float* g, float* m, float* v, long long n,
                  float lr, float beta1, float beta2, float eps, int step, float grad_scale, void* stream);

@@ -60,6 +60,13 @@ def build_config(args):
         if post['mode'] == 'min_size':
             post['min_size'] = min_size if min_size is not None else 64
         config['postprocess'] = post
+    # opt-in surface-distance metrics of the validation / test prediction (lib/evalMetrics.py parse_surface_metrics); absent = Dice alone
+    surface = config.pop('surface_metrics', False)
+    spacing = config.pop('surface_spacing', None)
+    percentile = config.pop('surface_percentile', None)
+    if surface or spacing is not None or percentile is not None:
+        config['surface_metrics'] = {'spacing': list(spacing) if spacing is not None else [1.0, 1.0, 1.0],
+                                     'percentile': percentile if percentile is not None else 95.0}
     # opt-in boundary loss beside the region loss (lib/loss.py BoundaryLoss); absent = the step as it was, and no key in the config
     if config.get('lambda_boundary') is None:
         config.pop('lambda_boundary', None)
@@ -95,6 +102,13 @@ def main(argv=None):
                              "'largest-cc' keeps the largest component of every class, 'min-size' drops components below --cc-min-size voxels")
     parser.add_argument('--cc-connectivity', type=int, default=None, choices=[6, 18, 26], help='connectivity of --postprocess (default 6)')
     parser.add_argument('--cc-min-size', type=int, default=None, metavar='VOXELS', help="smallest component --postprocess min-size keeps (default 64)")
+    parser.add_argument('--surface-metrics', action='store_true',
+                        help='additionally report the Hausdorff percentile (HD95) and the average symmetric surface distance (ASSD) of the '
+                             'validation / test prediction, computed on the device (and of the cleaned map with --postprocess)')
+    parser.add_argument('--surface-spacing', nargs=3, type=float, default=None, metavar=('SD', 'SH', 'SW'),
+                        help='voxel spacing of --surface-metrics (default 1 1 1); implies --surface-metrics')
+    parser.add_argument('--surface-percentile', type=float, default=None, metavar='P',
+                        help='percentile of the pooled surface distances reported as HD95 (default 95); implies --surface-metrics')
     parser.add_argument('--lambda-boundary', type=float, default=None, metavar='W',
                         help="add W x the boundary loss (Kervadec et al.: softmax probability times the signed distance to the ground truth, the "
                              "distance maps rebuilt on the device from every batch's labels) to the step's loss; 0 or absent: off")
