@@ -321,6 +321,28 @@ extern "C" int da_set_conv_direct(int on) { const int prev = g_force_direct ? 1 
 // Coarse stride-2 layers (the registration encoder below 40^3) stay on the space-to-depth route: the direct kernels were measured
 // 2 - 8x SLOWER there (forward 0.33 vs 0.15 ms, data gradient 0.52 vs 0.05, weight gradient 0.58 vs 0.07 at 40^3 -> 20^3).
 
+// The matrix-core call descriptions of the entries below and of their bf16 twins, in the entries' own argument order; what an entry adds (activation,
+// statistics, prologue, bf16 tensors) it sets by name.
+static ConvGemm fwd_gemm(const void* in1, int C1, const void* in2, int C2, const float* w_tio, const float* bias, void* out, int N, int D, int H, int W, int Cout, void* ws, size_t ws_bytes, void* stream) {
+    ConvGemm c = {};
+    c.in1 = (const float*)in1; c.C1 = C1; c.in2 = (const float*)in2; c.C2 = C2; c.w_tio = w_tio; c.bias = bias; c.out1 = (float*)out; c.Cs1 = Cout;
+    c.N = N; c.D = D; c.H = H; c.W = W; c.Cout = Cout; c.slope = -1.f; c.ws = ws; c.ws_bytes = ws_bytes; c.st = da_stream(stream);
+    return c;
+}
+// dX = conv(dY, flip/transpose(W)) : Cin' = Cout, Cout' = Cin, output split over (dx1, dx2)
+static ConvGemm dgrad_gemm(const void* dy, const float* w_tio, void* dx1, int C1, void* dx2, int C2, int N, int D, int H, int W, int Cout, void* ws, size_t ws_bytes, void* stream, int act_bf16) {
+    ConvGemm c = {};
+    c.in1 = (const float*)dy; c.C1 = Cout; c.w_tio = w_tio; c.flipped_tr = 1; c.out1 = (float*)dx1; c.Cs1 = C1; c.out2 = (float*)dx2; c.Cs2 = C2;
+    c.N = N; c.D = D; c.H = H; c.W = W; c.Cout = C1 + C2; c.slope = -1.f; c.ws = ws; c.ws_bytes = ws_bytes; c.st = da_stream(stream); c.act_bf16 = act_bf16;
+    return c;
+}
+static ConvWgrad wgrad_gemm(const void* in1, int C1, const void* in2, int C2, const void* dy, float* dw_tio, int N, int D, int H, int W, int Cout, int stride, void* ws, size_t ws_bytes, void* stream) {
+    ConvWgrad c = {};
+    c.in1 = (const float*)in1; c.C1 = C1; c.in2 = (const float*)in2; c.C2 = C2; c.dy = (const float*)dy; c.dw_tio = dw_tio;
+    c.N = N; c.D = D; c.H = H; c.W = W; c.Cout = Cout; c.stride = stride; c.ws = ws; c.ws_bytes = ws_bytes; c.st = da_stream(stream);
+    return c;
+}
+
 extern "C" int da_conv3d_k3_fwd(const float* in1, int C1, const float* in2, int C2,
                                 const float* w_tio, const float* bias, float* out,
                                 int N, int D, int H, int W, int Cout, int stride, float act_slope,
@@ -334,8 +356,8 @@ extern "C" int da_conv3d_k3_fwd(const float* in1, int C1, const float* in2, int 
     }
     if (!g_force_direct && da_conv3_mfma_fwd_supported(C1, C2, Cout, stride)) {
         if (ws_bytes < da_conv3d_k3_ws_bytes(N, D, H, W, C1 + C2, Cout, stride)) return DA_ERR_WS_SMALL;
-        const int rc = da_conv3_mfma_fwd(in1, C1, in2, C2, w_tio, /*w_is_flipped_tr=*/0, bias, out, Cout, nullptr, 0,
-                                         N, D, H, W, Cout, stride, act_slope, ws, ws_bytes, st);
+        ConvGemm c = fwd_gemm(in1, C1, in2, C2, w_tio, bias, out, N, D, H, W, Cout, ws, ws_bytes, stream); c.slope = act_slope;
+        const int rc = da_conv3_mfma_fwd(c);
         if (rc != DA_ERR_UNSUPPORTED) return rc;           // e.g. a per-sample tensor beyond 32-bit byte offsets: direct kernels below
     }
     if (!g_force_direct && stride == 1 && da_conv3_flowmm_supported(C1, C2, Cout, N, D, H, W)) {      // <= 3 outputs, split mode: (dy, cout) columns on the matrix cores
@@ -369,8 +391,8 @@ extern "C" int da_conv3d_k3_fwd_bnstats(const float* in1, int C1, const float* i
         return DA_ERR_BADARG;
     if (stats_partial && stats_capacity >= 512 && !g_force_direct && stride == 1 && da_conv3_mfma_fwd_supported(C1, C2, Cout, stride)) {
         if (ws_bytes < da_conv3d_k3_ws_bytes(N, D, H, W, C1 + C2, Cout, stride)) return DA_ERR_WS_SMALL;
-        const int rc = da_conv3_mfma_fwd(in1, C1, in2, C2, w_tio, 0, bias, out, Cout, nullptr, 0, N, D, H, W, Cout, stride, -1.f,
-                                         ws, ws_bytes, da_stream(stream), 0, stats_partial, stats_nparts);
+        ConvGemm c = fwd_gemm(in1, C1, in2, C2, w_tio, bias, out, N, D, H, W, Cout, ws, ws_bytes, stream); c.stats_partial = stats_partial; c.stats_nparts = stats_nparts;
+        const int rc = da_conv3_mfma_fwd(c);
         if (rc != DA_ERR_UNSUPPORTED) return rc;
         if (stats_nparts) *stats_nparts = 0;
     }
@@ -393,9 +415,9 @@ extern "C" int da_conv3d_k3_fwd_pro(const float* in1, int C1, const float* pro1_
     if (g_force_direct || !da_conv3_mfma_fwd_supported(C1, C2, Cout, 1)) return DA_ERR_UNSUPPORTED;
     if (ws_bytes < da_conv3d_k3_ws_bytes(N, D, H, W, C1 + C2, Cout, 1)) return DA_ERR_WS_SMALL;
     const DaPro pro = {pro1_scale, pro1_shift, pro1_slope, pro2_scale, pro2_shift, pro2_slope};
-    const bool stats = stats_partial && stats_capacity >= 512;
-    return da_conv3_mfma_fwd(in1, C1, in2, C2, w_tio, 0, bias, out, Cout, nullptr, 0, N, D, H, W, Cout, 1, stats ? -1.f : act_slope,
-                             ws, ws_bytes, da_stream(stream), 0, stats ? stats_partial : nullptr, stats ? stats_nparts : nullptr, &pro);
+    ConvGemm c = fwd_gemm(in1, C1, in2, C2, w_tio, bias, out, N, D, H, W, Cout, ws, ws_bytes, stream); c.pro = &pro; c.slope = act_slope;
+    if (stats_partial && stats_capacity >= 512) { c.stats_partial = stats_partial; c.stats_nparts = stats_nparts; c.slope = -1.f; }
+    return da_conv3_mfma_fwd(c);
 }
 
 extern "C" int da_conv3d_k3_wgrad_pro(const float* in1, int C1, const float* pro1_scale, const float* pro1_shift, float pro1_slope,
@@ -409,7 +431,8 @@ extern "C" int da_conv3d_k3_wgrad_pro(const float* in1, int C1, const float* pro
     if (g_force_direct || !da_conv3_mfma_wgrad_supported(C1, C2, Cout, 1)) return DA_ERR_UNSUPPORTED;
     if (ws_bytes < da_conv3d_k3_ws_bytes(N, D, H, W, C1 + C2, Cout, 1)) return DA_ERR_WS_SMALL;
     const DaPro pro = {pro1_scale, pro1_shift, pro1_slope, pro2_scale, pro2_shift, pro2_slope};
-    return da_conv3_mfma_wgrad(in1, C1, in2, C2, dy, dw_tio, N, D, H, W, Cout, 1, ws, ws_bytes, da_stream(stream), 0, &pro);
+    ConvWgrad c = wgrad_gemm(in1, C1, in2, C2, dy, dw_tio, N, D, H, W, Cout, 1, ws, ws_bytes, stream); c.pro = &pro;
+    return da_conv3_mfma_wgrad(c);
 }
 
 extern "C" int da_conv3d_k3_dgrad(const float* dy, const float* w_tio, float* dx1, int C1, float* dx2, int C2,
@@ -420,10 +443,8 @@ extern "C" int da_conv3d_k3_dgrad(const float* dy, const float* w_tio, float* dx
     const int Cin = C1 + C2;
     if (ws_bytes < da_conv3d_k3_ws_bytes(N, D, H, W, Cin, Cout, stride)) return DA_ERR_WS_SMALL;
     if (stride == 1) {
-        // dX = conv(dY, flip/transpose(W)) : Cin' = Cout, Cout' = Cin, output split over (dx1, dx2)
         if (!g_force_direct && da_conv3_mfma_fwd_supported(Cout, 0, Cin, 1, C1, C2)) {
-            const int rc = da_conv3_mfma_fwd(dy, Cout, nullptr, 0, w_tio, /*w_is_flipped_tr=*/1, nullptr, dx1, C1, dx2, C2,
-                                             N, D, H, W, Cin, 1, -1.f, ws, ws_bytes, st);
+            const int rc = da_conv3_mfma_fwd(dgrad_gemm(dy, w_tio, dx1, C1, dx2, C2, N, D, H, W, Cout, ws, ws_bytes, stream, 0));
             if (rc != DA_ERR_UNSUPPORTED) return rc;
         }
         if (!g_force_direct && da_conv3_flowmm_supported(C1, C2, Cout, N, D, H, W)) {
@@ -465,7 +486,7 @@ extern "C" int da_conv3d_k3_wgrad(const float* in1, int C1, const float* in2, in
     if (!g_force_direct && stride == 2 && da_conv3_s2_supported(C1, C2, Cout)) {
         rc = da_conv3_s2_wgrad(in1, C1, dy, dw_tio, N, D, H, W, Cout, ws, ws_bytes - da_bn_ws_bytes(0, Cout) - 4096, st);
     } else if (!g_force_direct && stride == 1 && da_conv3_mfma_wgrad_supported(C1, C2, Cout, stride)) {
-        rc = da_conv3_mfma_wgrad(in1, C1, in2, C2, dy, dw_tio, N, D, H, W, Cout, stride, ws, ws_bytes, st);
+        rc = da_conv3_mfma_wgrad(wgrad_gemm(in1, C1, in2, C2, dy, dw_tio, N, D, H, W, Cout, stride, ws, ws_bytes, stream));
     } else {
         rc = DA_ERR_UNSUPPORTED;
     }
@@ -518,8 +539,8 @@ extern "C" int da_conv3d_k3_fwd_bf16(const void* in1, int C1, const void* in2, i
         return da_conv3_s2_fwd((const float*)in1, C1, w_tio, bias, (float*)out, N, D, H, W, Cout, act_slope, ws, ws_bytes - da_bn_ws_bytes(0, Cout) - 4096, da_stream(stream), 1);
     }
     if (!da_conv3_mfma_fwd_supported(C1, C2, Cout, stride)) return DA_ERR_UNSUPPORTED;
-    return da_conv3_mfma_fwd((const float*)in1, C1, (const float*)in2, C2, w_tio, 0, bias, (float*)out, Cout, nullptr, 0,
-                             N, D, H, W, Cout, stride, act_slope, ws, ws_bytes, da_stream(stream), 0, nullptr, nullptr, nullptr, nullptr, 1);
+    ConvGemm c = fwd_gemm(in1, C1, in2, C2, w_tio, bias, out, N, D, H, W, Cout, ws, ws_bytes, stream); c.slope = act_slope; c.act_bf16 = 1;
+    return da_conv3_mfma_fwd(c);
 }
 
 extern "C" int da_conv3d_k3_fwd_bnstats_bf16(const void* in1, int C1, const void* in2, int C2,
@@ -535,9 +556,9 @@ extern "C" int da_conv3d_k3_fwd_bnstats_bf16(const void* in1, int C1, const void
     if ((bf16_mask & want) != want || stride != 1 || !da_conv3_mfma_fwd_supported(C1, C2, Cout, stride))      // no fused statistics (*stats_nparts = 0): thin / stride-2 routes
         return da_conv3d_k3_fwd_bf16(in1, C1, in2, C2, w_tio, bias, out, N, D, H, W, Cout, stride, -1.f, ws, ws_bytes, stream, bf16_mask);
     if (ws_bytes < da_conv3d_k3_ws_bytes(N, D, H, W, C1 + C2, Cout, stride)) return DA_ERR_WS_SMALL;
-    const bool stats = stats_partial && stats_capacity >= 512;
-    return da_conv3_mfma_fwd((const float*)in1, C1, (const float*)in2, C2, w_tio, 0, bias, (float*)out, Cout, nullptr, 0, N, D, H, W, Cout, stride, -1.f,
-                             ws, ws_bytes, da_stream(stream), 0, stats ? stats_partial : nullptr, stats ? stats_nparts : nullptr, nullptr, nullptr, 1);
+    ConvGemm c = fwd_gemm(in1, C1, in2, C2, w_tio, bias, out, N, D, H, W, Cout, ws, ws_bytes, stream); c.act_bf16 = 1;
+    if (stats_partial && stats_capacity >= 512) { c.stats_partial = stats_partial; c.stats_nparts = stats_nparts; }
+    return da_conv3_mfma_fwd(c);
 }
 
 extern "C" int da_conv3d_k3_fwd_pro_bf16(const void* in1, int C1, const float* pro1_scale, const float* pro1_shift, float pro1_slope,
@@ -554,9 +575,9 @@ extern "C" int da_conv3d_k3_fwd_pro_bf16(const void* in1, int C1, const float* p
     if ((bf16_mask & want) != want || g_force_direct || !da_conv3_mfma_fwd_supported(C1, C2, Cout, 1)) return DA_ERR_UNSUPPORTED;
     if (ws_bytes < da_conv3d_k3_ws_bytes(N, D, H, W, C1 + C2, Cout, 1)) return DA_ERR_WS_SMALL;
     const DaPro pro = {pro1_scale, pro1_shift, pro1_slope, pro2_scale, pro2_shift, pro2_slope};
-    const bool stats = stats_partial && stats_capacity >= 512;
-    return da_conv3_mfma_fwd((const float*)in1, C1, (const float*)in2, C2, w_tio, 0, bias, (float*)out, Cout, nullptr, 0, N, D, H, W, Cout, 1, stats ? -1.f : act_slope,
-                             ws, ws_bytes, da_stream(stream), 0, stats ? stats_partial : nullptr, stats ? stats_nparts : nullptr, &pro, nullptr, 1);
+    ConvGemm c = fwd_gemm(in1, C1, in2, C2, w_tio, bias, out, N, D, H, W, Cout, ws, ws_bytes, stream); c.pro = &pro; c.act_bf16 = 1; c.slope = act_slope;
+    if (stats_partial && stats_capacity >= 512) { c.stats_partial = stats_partial; c.stats_nparts = stats_nparts; c.slope = -1.f; }
+    return da_conv3_mfma_fwd(c);
 }
 
 extern "C" int da_conv3d_k3_wgrad_pro_bf16(const void* in1, int C1, const float* pro1_scale, const float* pro1_shift, float pro1_slope,
@@ -571,7 +592,8 @@ extern "C" int da_conv3d_k3_wgrad_pro_bf16(const void* in1, int C1, const float*
     if ((bf16_mask & want) != want || g_force_direct || !da_conv3_mfma_wgrad_supported(C1, C2, Cout, 1)) return DA_ERR_UNSUPPORTED;
     if (ws_bytes < da_conv3d_k3_ws_bytes(N, D, H, W, C1 + C2, Cout, 1)) return DA_ERR_WS_SMALL;
     const DaPro pro = {pro1_scale, pro1_shift, pro1_slope, pro2_scale, pro2_shift, pro2_slope};
-    return da_conv3_mfma_wgrad((const float*)in1, C1, (const float*)in2, C2, (const float*)dy, dw_tio, N, D, H, W, Cout, 1, ws, ws_bytes, da_stream(stream), 0, &pro, nullptr, 1);
+    ConvWgrad c = wgrad_gemm(in1, C1, in2, C2, dy, dw_tio, N, D, H, W, Cout, 1, ws, ws_bytes, stream); c.pro = &pro; c.act_bf16 = 1;
+    return da_conv3_mfma_wgrad(c);
 }
 
 extern "C" int da_conv3d_k3_dgrad_bf16(const void* dy, const float* w_tio, void* dx1, int C1, void* dx2, int C2,
@@ -596,8 +618,7 @@ extern "C" int da_conv3d_k3_dgrad_bf16(const void* dy, const float* w_tio, void*
         return da_conv3_s2_dgrad((const float*)dy, w_tio, (float*)dx1, C1, N, D, H, W, Cout, ws, ws_bytes - da_bn_ws_bytes(0, Cout) - 4096, da_stream(stream), 1);
     }
     if (!da_conv3_mfma_fwd_supported(Cout, 0, Cin, 1, C1, C2)) return DA_ERR_UNSUPPORTED;
-    return da_conv3_mfma_fwd((const float*)dy, Cout, nullptr, 0, w_tio, /*w_is_flipped_tr=*/1, nullptr, (float*)dx1, C1, (float*)dx2, C2,
-                             N, D, H, W, Cin, 1, -1.f, ws, ws_bytes, da_stream(stream), 0, nullptr, nullptr, nullptr, nullptr, 1);
+    return da_conv3_mfma_fwd(dgrad_gemm(dy, w_tio, dx1, C1, dx2, C2, N, D, H, W, Cout, ws, ws_bytes, stream, 1));
 }
 
 extern "C" int da_conv3d_k3_wgrad_bf16(const void* in1, int C1, const void* in2, int C2, const void* dy,
@@ -622,5 +643,6 @@ extern "C" int da_conv3d_k3_wgrad_bf16(const void* in1, int C1, const void* in2,
         return da_conv3_s2_wgrad((const float*)in1, C1, (const float*)dy, dw_tio, N, D, H, W, Cout, ws, ws_bytes - da_bn_ws_bytes(0, Cout) - 4096, da_stream(stream), 1);
     }
     if (!da_conv3_mfma_wgrad_supported(C1, C2, Cout, stride)) return DA_ERR_UNSUPPORTED;
-    return da_conv3_mfma_wgrad((const float*)in1, C1, (const float*)in2, C2, (const float*)dy, dw_tio, N, D, H, W, Cout, stride, ws, ws_bytes, da_stream(stream), 0, nullptr, nullptr, 1);
+    ConvWgrad c = wgrad_gemm(in1, C1, in2, C2, dy, dw_tio, N, D, H, W, Cout, stride, ws, ws_bytes, stream); c.act_bf16 = 1;
+    return da_conv3_mfma_wgrad(c);
 }

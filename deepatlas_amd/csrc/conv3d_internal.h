@@ -6,10 +6,6 @@
 
 size_t da_conv3_mfma_ws_bytes(int N, int D, int H, int W, int Cin, int Cout, int stride);
 
-// forward-shaped implicit GEMM.  in = concat(in1[C1], in2[C2]); output channels [0,Cs1) -> out1, rest -> out2.
-// w_is_flipped_tr != 0: `w_tio` is the ORIGINAL layer's [27][Cout][C1] tensor and the kernel runs the data-gradient
-// convolution (taps flipped, channels transposed) -- i.e. logical Cin = C1, logical Cout = `Cout`.
-bool da_matrix_bf16();                 // bf16 matrix mode switch (da_set_matrix_bf16)
 int da_matrix_mode();                  // 0 fp32 MFMA | 1 bf16-rounded operands | 2 two-term fp16 split (da_set_matrix_mode, split_f16.h)
 // Input prologue: in1 / in2 are RAW outputs of a producer whose per-channel affine (BatchNorm scale / shift) and activation
 // (slope as in da_conv3d_k3_fwd: < 0 identity, 0 ReLU, > 0 LeakyReLU) are applied while the tile is staged.  A null scale
@@ -17,19 +13,34 @@ int da_matrix_mode();                  // 0 fp32 MFMA | 1 bf16-rounded operands 
 struct DaPro { const float* s1; const float* t1; float slope1; const float* s2; const float* t2; float slope2; };
 // Stride-2 layers (conv3d_s2.hip) run as tap-masked stride-1 convolutions over the space-to-depth view of their input (s2d_cin > 0, which
 // requires the view).  Forward and weight gradient: `in1` is the ORIGINAL tensor (s2d_cin channels, D0 x H0 x W0) and the staging loads apply
-// the view; data gradient (w_is_flipped_tr): `out1` is the original-resolution gradient and the epilogue stores apply the inverse view.
+// the view; data gradient (flipped_tr): `out1` is the original-resolution gradient and the epilogue stores apply the inverse view.
 struct DaS2dFuse { int D0, H0, W0; };
 bool da_conv3_mfma_fwd_supported(int C1, int C2, int Cout, int stride, int Cs1 = -1, int Cs2 = 0);   // Cs1/Cs2: output split (dgrad of a concat conv)
-int da_conv3_mfma_fwd(const float* in1, int C1, const float* in2, int C2, const float* w_tio, int w_is_flipped_tr,
-                      const float* bias, float* out1, int Cs1, float* out2, int Cs2,
-                      int N, int D, int H, int W, int Cout, int stride, float slope,
-                      void* ws, size_t ws_bytes, hipStream_t st, int s2d_cin = 0, double* stats_partial = nullptr, int* stats_nparts = nullptr,
-                      const DaPro* pro = nullptr, const DaS2dFuse* s2f = nullptr, int act_bf16 = 0);   // act_bf16: in1 / in2 / out1 / out2 are bf16 tensors (bf16 matrix mode only, else DA_ERR_UNSUPPORTED)
+// One forward-shaped implicit-GEMM call; the members with an initialiser are optional.  in = concat(in1[C1], in2[C2]); output channels [0,Cs1) -> out1, rest -> out2.
+// flipped_tr != 0: `w_tio` is the ORIGINAL layer's [27][Cout][C1] tensor and the kernel runs the data-gradient
+// convolution (taps flipped, channels transposed) -- i.e. logical Cin = C1, logical Cout = `Cout`.
+struct ConvBst { const float* y = nullptr; const float* par = nullptr; float slope = -1.f; };       // da_conv3d_k3_dgrad_bst: the producer's raw output, statistics rows, activation
+struct ConvPack { const void* buf[2] = {nullptr, nullptr}; size_t bytes[2] = {0, 0}; };            // a caller's kept packed operand: one region per launch of the call
+struct ConvGemm {
+    const float* in1; int C1; const float* in2; int C2; const float* w_tio; int flipped_tr; const float* bias;
+    float* out1; int Cs1; float* out2; int Cs2;
+    int N, D, H, W, Cout; float slope; void* ws; size_t ws_bytes; hipStream_t st;
+    int s2d_cin = 0; const DaS2dFuse* s2f = nullptr; const DaPro* pro = nullptr;
+    double* stats_partial = nullptr; int* stats_nparts = nullptr;       // BatchNorm partial sums of the output (with bst: the epilogue's sums instead)
+    int act_bf16 = 0;                   // in1 / in2 / out1 / out2 are bf16 tensors (bf16 matrix mode only, else DA_ERR_UNSUPPORTED)
+    int cout0 = 0, CoutW = 0;           // this launch covers output channels [cout0, cout0 + Cout) of a weight tensor with CoutW of them (0: all, CoutW = Cout)
+    ConvBst bst;
+    ConvPack pack;                      // da_conv3_mfma_fwd takes it from the hand-over (da_conv3d_k3_use_prepacked); its callers leave it empty
+};
+int da_conv3_mfma_fwd(const ConvGemm& c);
 
 bool da_conv3_mfma_wgrad_supported(int C1, int C2, int Cout, int stride);
-int da_conv3_mfma_wgrad(const float* in1, int C1, const float* in2, int C2, const float* dy, float* dw_tio,
-                        int N, int D, int H, int W, int Cout, int stride, void* ws, size_t ws_bytes, hipStream_t st, int s2d_cin = 0,
-                        const DaPro* pro = nullptr, const DaS2dFuse* s2f = nullptr, int act_bf16 = 0);   // act_bf16: in1 / in2 / dy are bf16 tensors
+struct ConvWgrad {
+    const float* in1; int C1; const float* in2; int C2; const float* dy; float* dw_tio;
+    int N, D, H, W, Cout, stride; void* ws; size_t ws_bytes; hipStream_t st;
+    int s2d_cin = 0; const DaS2dFuse* s2f = nullptr; const DaPro* pro = nullptr; int act_bf16 = 0;      // act_bf16: in1 / in2 / dy are bf16 tensors
+};
+int da_conv3_mfma_wgrad(const ConvWgrad& c);
 
 int da_conv3_direct_fwd(const float* in1, int C1, const float* in2, int C2, const float* w, const float* bias,
                         float* out1, int Cs1, float* out2, int Cs2,

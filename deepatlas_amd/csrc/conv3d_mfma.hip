@@ -1744,7 +1744,7 @@ static size_t tile_table_bytes(int N, int D, int H, int W) {
 static size_t wg_tile_table_bytes(int N, int D, int H, int W) {
     return da_align((size_t)N * ((D + 1) / 2) * ((H + TY - 1) / TY) * ((W + TX - 1) / TX) * sizeof(int4));
 }
-static const int kScBlocksFwd = 1024;
+static const int kScBlocks = 1024;          // workgroups (= partial dW copies) of the small-Cin weight gradient
 // layout of a forward / data-gradient call: [packed weights | tile counters][tile table]; of a weight-gradient call: [partials]
 size_t da_conv3_mfma_ws_bytes(int N, int D, int H, int W, int Cin, int Cout, int stride) {
     if (stride != 1) return 0;
@@ -1753,8 +1753,8 @@ size_t da_conv3_mfma_ws_bytes(int N, int D, int H, int W, int Cin, int Cout, int
     if (Cout % 8 == 0) { const size_t a = packed_bytes(Cout, Cin, Cout % 16 == 0 ? 16 : 8); if (a > pk) pk = a; }
     size_t part = 0;
     if (Cin % 8 == 0) { part = wgrad_plan(N, D, H, W, Cin, 0, Cout).partial_bytes; const size_t pr = wgrad_plan(N, D, H, W, Cin, 0, Cout, true, true).partial_bytes; if (pr > part) part = pr; }
-    if (Cin <= 4 && Cout <= 32) part = da_align((size_t)kScBlocksFwd * 27 * Cin * Cout * sizeof(float));
-    if (Cout <= 4 && Cin <= 32) { const size_t sw = da_align((size_t)(kScBlocksFwd + 1) * 27 * Cin * Cout * sizeof(float)); if (sw > part) part = sw; }   // swapped-operand weight gradient
+    if (Cin <= 4 && Cout <= 32) part = da_align((size_t)kScBlocks * 27 * Cin * Cout * sizeof(float));
+    if (Cout <= 4 && Cin <= 32) { const size_t sw = da_align((size_t)(kScBlocks + 1) * 27 * Cin * Cout * sizeof(float)); if (sw > part) part = sw; }   // swapped-operand weight gradient
     return pk + tile_table_bytes(N, D, H, W) + part + wg_tile_table_bytes(N, D, H, W);
 }
 
@@ -1852,177 +1852,167 @@ static int pro_identity(const float** ones, const float** zeros) {
     return 0;
 }
 
-// kernel-side activation parameter (da_act01): slope in [0, 1) as is, "no activation" (slope < 0 or no prologue) -> 1
-static int pro_slopes(const DaPro* pro, int C2, float* s1, float* s2) {
+// the prologue's kernel parameters (FwdP / WgP).  Kernel-side activation parameter (da_act01): slope in [0, 1) as is, "no activation" (slope < 0 or no prologue) -> 1
+template <typename P>
+static int set_prologue(P& p, const DaPro* pro, int C2) {
+    p.ps1 = p.pt1 = p.ps2 = p.pt2 = nullptr; p.pslope1 = p.pslope2 = -1.f;
+    if (!pro) return 0;
+    const float *ones, *zeros;
+    if (const int rc = pro_identity(&ones, &zeros)) return rc;
     const float a = pro->s1 ? pro->slope1 : -1.f, b = (C2 > 0 && pro->s2) ? pro->slope2 : -1.f;
-    if (a >= 1.f || b >= 1.f) return 1;
-    *s1 = a < 0.f ? 1.f : a; *s2 = b < 0.f ? 1.f : b;
+    if (a >= 1.f || b >= 1.f) return DA_ERR_UNSUPPORTED;
+    p.pslope1 = a < 0.f ? 1.f : a; p.pslope2 = b < 0.f ? 1.f : b;
+    p.ps1 = pro->s1 ? pro->s1 : ones; p.pt1 = pro->s1 ? pro->t1 : zeros;
+    p.ps2 = (C2 > 0 && pro->s2) ? pro->s2 : ones; p.pt2 = (C2 > 0 && pro->s2) ? pro->t2 : zeros;
     return 0;
 }
 
-static int conv3_mfma_fwd_impl(const float* in1, int C1, const float* in2, int C2, const float* w_tio, int w_is_flipped_tr,
-                               const float* bias, float* out1, int Cs1, float* out2, int Cs2,
-                               int N, int D, int H, int W, int Cout, int stride, float slope,
-                               void* ws, size_t ws_bytes, hipStream_t st, int s2d_cin, double* stats_partial, int* stats_nparts, const DaPro* pro, const DaS2dFuse* s2f,
-                               int cout0, int CoutW, bool hb);
+// ---- the launch plan of a forward-shaped call: pure (no state, no launches); the launcher and da_conv3d_k3_prepack(_many) read it, the sizing functions its byte helpers ----
+// Pack-layout invariant.  What a packed operand depends on is PackJob -- Cin, the cout window (cout0, Cout of CoutW), NTpad, flipped or not, the tile grid (N, D, H, W) --
+// and pk, the offset of the exponents and the tile table, a function of (Cin, Cout).  The plan must yield the same values for a fill and for every call that may consume
+// that fill.  da_conv3d_k3_prepack plans the plain forward / data gradient; its consumers add stats_partial, pro or bst.  In split mode NREP, hence NTpad, depends on
+// (Cout, tile count) alone: stats_partial and pro do not enter (pro's cap at two N-tiles is the split mode's own), and bst, which forces NREP = 1, is confined to NT <= 2
+// (dx1 of <= 32 channels), where NTpad = NT for either NREP.  fwd_launches splits a call by its shape alone (bst rides on the first launch).  Keep it so: a stale pack is silent.
+enum FwdFamily { kFamDense, kFamMasked, kFamSplit, kFamPaired, kFamBst };
+struct FwdPlan {
+    bool split, bf; int CK, NREP, gy, NTpad;      // channels per chunk, N-tiles per workgroup, cout groups (grid.y), N-tiles in the pack
+    int pkmode, NSTEPS;                 // 0 fp32 | 1 bf16, one tap per K-step (sparse taps) | 2 bf16, K = 32 per step | 3 split: three bf16 planes, K = 32
+    size_t pk, tt;                      // bytes of [packed weights | exponents / tile counters] and of the tile table behind them
+    int ntz, nty, ntx, ntiles, nblocks; FwdFamily family;
+};
+static int fwd_plan(const ConvGemm& c, int mode, FwdPlan* plan) {
+    FwdPlan& q = *plan;
+    const int Cin = c.C1 + c.C2;
+    q.CK = pick_ck(c.C1, c.C2);
+    if (!q.CK) return DA_ERR_UNSUPPORTED;
+    if (c.pro && (c.s2d_cin > 0 || c.flipped_tr || Cin > kProMaxC)) return DA_ERR_UNSUPPORTED;
+    if (c.s2d_cin > 0 && !c.s2f) return DA_ERR_UNSUPPORTED;          // (the sparse-tap route reads / writes through the space-to-depth view only)
+    q.split = mode == 2 && c.s2d_cin == 0;      // (the sparse-tap stride-2 route keeps the native fp32 kernels)
+    q.bf = mode == 1;
+    if (q.split) q.CK = 8;
+    {   // every tensor is addressed per sample through a buffer descriptor with 32-bit byte offsets
+        const int cin = c.C1 > c.C2 ? c.C1 : c.C2, cs = c.Cs1 > c.Cs2 ? c.Cs1 : c.Cs2;
+        if ((unsigned long long)c.D * c.H * c.W * 4ull * (unsigned long long)(cin > cs ? cin : cs) >= 0xFFFFFFF0ull) return DA_ERR_UNSUPPORTED;
+    }
+    const int NT = (c.Cout + 15) / 16;
+    q.NREP = pick_nrep(NT);
+    if ((q.bf || q.split || c.pro) && q.NREP > 2) q.NREP = 2;        // bf16 mode is not matrix-bound, three N-tiles would spill; the prologue variant parks the whole next tile in registers
+    if (c.s2d_cin > 0 && q.NREP > 2) q.NREP = 2;           // the sparse-tap kernels exist for one and two N-tiles per workgroup (stride 2, Cout = 48: two groups, the fourth tile empty)
+    const bool want_bst = c.bst.y != nullptr && q.split && c.stats_partial != nullptr;
+    if (want_bst) q.NREP = 1;                              // the BatchNorm-backward epilogue holds TY quads of the producer's output: one N-tile per workgroup
+    q.ntz = (c.D + 3) / 4; q.nty = (c.H + TY - 1) / TY; q.ntx = (c.W + TX - 1) / TX;
+    q.ntiles = c.N * q.ntz * q.nty * q.ntx;
+    if (c.s2d_cin == 0 && q.NREP > 1 && !want_bst) {
+        // Coarse levels have few tiles (30 per volume at 20x24x20, 180 at 40x48x40): the persistent grid then runs one or two
+        // uneven rounds.  Makespan model: a workgroup walks ceil(tiles / nblk) tiles, each costing ~NREP (one N-tile per
+        // workgroup is ~8 % less efficient per FLOP but quadruples / doubles the number of work items); take the cheaper.
+        const long long tiles = (long long)c.N * q.ntz * q.nty * q.ntx;
+        auto cost = [&](int nrep) {
+            const int g = (NT + nrep - 1) / nrep;
+            long long nb = 512 / g; if (nb < 1) nb = 1; if (nb > tiles) nb = tiles;
+            return (double)((tiles + nb - 1) / nb) * nrep * (nrep == 1 ? 1.08 : 1.0);
+        };
+        if (cost(1) < cost(q.NREP)) q.NREP = 1;
+    }
+    q.gy = (NT + q.NREP - 1) / q.NREP; q.NTpad = q.gy * q.NREP;
+    q.pkmode = q.split ? 3 : q.bf ? (c.s2d_cin > 0 ? 1 : 2) : 0;
+    q.NSTEPS = q.pkmode >= 2 ? (q.CK == 16 ? 14 : 7) : (27 * q.CK + 15) / 16;
+    q.pk = packed_bytes(Cin, c.Cout, q.CK); q.tt = tile_table_bytes(c.N, c.D, c.H, c.W);
+    // one resident round: 2 workgroups per CU x 256 CUs, split over the cout groups
+    // (a third workgroup per CU for the split kernels -- 168 VGPRs, 3 x 52 KB of LDS -- was measured and dropped: in split mode the
+    // matrix pipe is already busy ~100 % of the shader cycles and the clock is set by the power limit)
+    q.nblocks = 512 / q.gy; if (q.nblocks < 1) q.nblocks = 1; if (q.nblocks > q.ntiles) q.nblocks = q.ntiles;
+    if (q.nblocks >= 8) q.nblocks &= ~7;                   // multiple of 8: blockIdx.x % 8 is then the XCD (tile_walk)
+    if (!q.split) q.family = c.s2d_cin > 0 ? kFamMasked : kFamDense;
+    else if (want_bst) q.family = kFamBst;                 // (da_conv3d_k3_dgrad_bst checked the shape: one output tensor of <= 32 channels, no prologue)
+    // paired staging (one sector fetch per two chunks): one N-tile, an even number of 8-channel chunks that pair up inside in1 / in2
+    else q.family = (q.NREP == 1 && !c.pro && c.C1 % 16 == 0 && c.C2 % 16 == 0) ? kFamPaired : kFamSplit;
+    if (q.family == kFamMasked && q.CK != 16) return DA_ERR_UNSUPPORTED;
+    if (q.family == kFamBst && (c.pro || c.Cs2 != 0 || q.gy > 2)) return DA_ERR_UNSUPPORTED;
+    return 0;
+}
+
+// Split mode, data gradient of a concat layer whose outputs are 32 + 16 channels (the 48 -> 16 decoder convolution: three N-tiles).  One
+// launch with one N-tile per workgroup stages dY three times; two launches -- two N-tiles sharing every dY fragment for the first output
+// tensor (with da_conv3d_k3_dgrad_bst's epilogue sums, if any), one N-tile (paired staging) for the second -- stage it twice and write each
+// output tensor from its own launch, each with its own region of a kept pack.  Returns the number of launches and fills that many of l[].
+static int fwd_launches(const ConvGemm& c, int mode, ConvGemm l[2]) {
+    l[0] = c;
+    if (!(mode == 2 && c.flipped_tr && c.s2d_cin == 0 && (!c.stats_partial || c.bst.y) && !c.pro && c.Cs1 == 32 && c.Cs2 == 16 && c.Cout == 48 &&
+          pick_ck(c.C1, c.C2) != 0)) return 1;
+    l[0].out2 = nullptr; l[0].Cs2 = 0; l[0].Cout = 32; l[0].CoutW = 48; l[0].pack = ConvPack{{c.pack.buf[0], nullptr}, {c.pack.bytes[0], 0}};
+    l[1] = l[0];
+    l[1].bias = c.bias ? c.bias + 32 : nullptr; l[1].out1 = c.out2; l[1].Cs1 = 16; l[1].Cout = 16; l[1].cout0 = 32;
+    l[1].stats_partial = nullptr; l[1].stats_nparts = nullptr; l[1].bst = ConvBst{}; l[1].pack = ConvPack{{c.pack.buf[1], nullptr}, {c.pack.bytes[1], 0}};
+    return 2;
+}
+
+// the pack of one launch at `base`: [packed weights | exponents / tile counters][tile table]
+static PackJob pack_job(const ConvGemm& c, const FwdPlan& q, char* base) {
+    return PackJob{c.w_tio, reinterpret_cast<unsigned short*>(base), reinterpret_cast<int*>(base + q.pk - da_align(kWexpInts * sizeof(int))), reinterpret_cast<int4*>(base + q.pk),
+                   c.C1 + c.C2, c.Cout, q.NTpad, c.flipped_tr, q.ntiles, q.ntx, q.nty, q.ntz, c.cout0, c.CoutW ? c.CoutW : c.Cout};
+}
+static void launch_split_pack(const PackJob& j, hipStream_t st) {
+    hipLaunchKernelGGL(pack_split_weights_kernel, dim3(j.Cin / 8, 8), dim3(256), 0, st, j.w, j.wp, j.wexp, j.Cin, j.Cout, j.NTpad, j.flipped, j.tiles, j.ntiles, j.ntx, j.nty, j.ntz, j.cout0, j.CoutW);
+}
 
 // ---- packed operands kept across calls (split mode) -----------------------------------------------------------------------------------------
 // A convolution call packs its weights (fragment order, two fp16 planes, per-chunk exponents) and writes its tile table before the matrix kernel can
-// start: a 10-us launch in the dependent chain of every layer, forward and data gradient, every step, for data that only changes when the optimiser
-// steps.  The caller may keep the packed operand itself: da_conv3d_k3_prepack fills a caller-owned buffer (the host side does so for every layer right
-// after the optimiser step, on the side stream), da_conv3d_k3_use_prepacked hands it to the NEXT convolution call of this thread on the same weights.
-// mode 1: use, 2: fill (the matrix kernel is not launched).  Up to two regions: the 48 <- 16 data gradient runs two launches with their own packs.
-// BatchNorm-backward sums in the data gradient's epilogue (STATS == 2): set by da_conv3d_k3_dgrad_bst for the one call it makes
-struct BstState { const float* y; const float* par; float slope; };
-static thread_local BstState g_bst = {nullptr, nullptr, -1.f};
-
-struct PrepackState { int mode; const float* w; char* buf[2]; size_t bytes[2]; int next, used; };
-static thread_local PrepackState g_pp = {0, nullptr, {nullptr, nullptr}, {0, 0}, 0, 0};
-static thread_local PackJobs* g_pp_collect = nullptr;       // fill mode: record the pack launches here instead of issuing them (da_conv3d_k3_prepack_many)
-static thread_local int g_pp_ncollect = 0;
-
-int da_conv3_mfma_fwd(const float* in1, int C1, const float* in2, int C2, const float* w_tio, int w_is_flipped_tr,
-                      const float* bias, float* out1, int Cs1, float* out2, int Cs2,
-                      int N, int D, int H, int W, int Cout, int stride, float slope,
-                      void* ws, size_t ws_bytes, hipStream_t st, int s2d_cin, double* stats_partial, int* stats_nparts, const DaPro* pro, const DaS2dFuse* s2f, int act_bf16) {
-    if (act_bf16 && da_matrix_mode() != 1) return DA_ERR_UNSUPPORTED;          // bf16 activation storage goes with the bf16 matrix mode
-    // Split mode, data gradient of a concat layer whose outputs are 32 + 16 channels (the 48 -> 16 decoder convolution: three N-tiles).  One
-    // launch with one N-tile per workgroup stages dY three times; two launches -- two N-tiles sharing every dY fragment for the first output
-    // tensor, one N-tile (paired staging) for the second -- stage it twice and write each output tensor from its own launch.
-    struct PpReset { ~PpReset() { if (g_pp.mode == 1) g_pp.mode = 0; } } pp_reset;      // a handed-over pack serves exactly one call
-    if (g_pp.mode && g_pp.w != w_tio) g_pp.mode = 0;                                      // (it belongs to other weights: a call in between went elsewhere)
-    if (da_matrix_mode() == 2 && w_is_flipped_tr && s2d_cin == 0 && !stats_partial && !pro && Cs2 > 0 && Cs1 == 32 && Cs2 == 16 && Cout == 48 &&
-        pick_ck(C1, C2) != 0) {
-        int rc = conv3_mfma_fwd_impl(in1, C1, in2, C2, w_tio, 1, bias, out1, 32, nullptr, 0, N, D, H, W, 32, stride, slope, ws, ws_bytes, st, 0, nullptr, nullptr,
-                                     nullptr, nullptr, 0, Cout, false);
-        if (rc) return rc;
-        return conv3_mfma_fwd_impl(in1, C1, in2, C2, w_tio, 1, bias ? bias + 32 : nullptr, out2, 16, nullptr, 0, N, D, H, W, 16, stride, slope, ws, ws_bytes, st, 0,
-                                   nullptr, nullptr, nullptr, nullptr, 32, Cout, false);
-    }
-    return conv3_mfma_fwd_impl(in1, C1, in2, C2, w_tio, w_is_flipped_tr, bias, out1, Cs1, out2, Cs2, N, D, H, W, Cout, stride, slope, ws, ws_bytes, st, s2d_cin,
-                               stats_partial, stats_nparts, pro, s2f, 0, Cout, act_bf16 != 0);
+// start: a 10-us launch in the dependent chain of every layer, every step, for data that only changes when the optimiser steps.  The caller may keep the
+// packed operand itself (da_conv3d_k3_prepack, after the optimiser step on the side stream) and hand it to the NEXT convolution call of this thread on the same
+// weights.  That hand-over is the only state between calls.  use_prepacked parks (weights, up to two regions: one per launch of fwd_launches) in the slot below; the
+// next call that reaches da_conv3_mfma_fwd takes it, which empties the slot, and carries it in its ConvGemm from there.  So it serves one call only; a call
+// on other weights drops it; only the split kernels read it; a region that is missing or too small makes that launch pack for itself into the workspace.
+// A call that never reaches da_conv3_mfma_fwd (thin, flow, direct routes) leaves the slot pending.
+struct Handover { const float* w; ConvPack pack; };
+static thread_local Handover g_handover = {nullptr, {}};
+static ConvPack take_handover(const float* w_tio) {
+    const Handover h = g_handover;
+    g_handover = Handover{nullptr, {}};
+    return h.w == w_tio ? h.pack : ConvPack{};
 }
 
-static int conv3_mfma_fwd_impl(const float* in1, int C1, const float* in2, int C2, const float* w_tio, int w_is_flipped_tr,
-                               const float* bias, float* out1, int Cs1, float* out2, int Cs2,
-                               int N, int D, int H, int W, int Cout, int stride, float slope,
-                               void* ws, size_t ws_bytes, hipStream_t st, int s2d_cin, double* stats_partial, int* stats_nparts, const DaPro* pro, const DaS2dFuse* s2f,
-                               int cout0, int CoutW, bool hb) {
-    (void)stride;
-    const int Cin = C1 + C2;
-    int CK = pick_ck(C1, C2);
-    if (!CK) return DA_ERR_UNSUPPORTED;
-    if (pro && (s2d_cin > 0 || w_is_flipped_tr || Cin > kProMaxC)) return DA_ERR_UNSUPPORTED;
-    if (s2d_cin > 0 && !s2f) return DA_ERR_UNSUPPORTED;          // (the sparse-tap route reads / writes through the space-to-depth view only)
-    const bool split = da_matrix_mode() == 2 && s2d_cin == 0;      // (the sparse-tap stride-2 route keeps the native fp32 kernels)
-    const bool bf = da_matrix_mode() == 1;
-    if (split) CK = 8;
-    {   // every tensor is addressed per sample through a buffer descriptor with 32-bit byte offsets
-        const unsigned long long vox4 = (unsigned long long)D * H * W * 4ull;
-        const int cmax = (C1 > C2 ? C1 : C2) > (Cs1 > Cs2 ? Cs1 : Cs2) ? (C1 > C2 ? C1 : C2) : (Cs1 > Cs2 ? Cs1 : Cs2);
-        if (vox4 * (unsigned long long)cmax >= 0xFFFFFFF0ull) return DA_ERR_UNSUPPORTED;
-    }
-    const int NT = (Cout + 15) / 16;
-    int NREP = pick_nrep(NT);
-    if ((bf || split || pro) && NREP > 2) NREP = 2;        // bf16 mode is not matrix-bound, three N-tiles would spill; the prologue variant parks the whole next tile in registers
-    if (s2d_cin > 0 && NREP > 2) NREP = 2;                 // the sparse-tap kernels exist for one and two N-tiles per workgroup (stride 2, Cout = 48: two groups, the fourth tile empty)
-    const bool want_bst = g_bst.y != nullptr && split && stats_partial != nullptr;
-    if (want_bst) NREP = 1;                                // the BatchNorm-backward epilogue holds TY quads of the producer's output: one N-tile per workgroup
-    {   // Coarse levels have few tiles (30 per volume at 20x24x20, 180 at 40x48x40): the persistent grid then runs one or two
-        // uneven rounds.  Makespan model: a workgroup walks ceil(tiles / nblk) tiles, each costing ~NREP (one N-tile per
-        // workgroup is ~8 % less efficient per FLOP but quadruples / doubles the number of work items); take the cheaper.
-        const long long tiles = (long long)N * ((D + 3) / 4) * ((H + TY - 1) / TY) * ((W + TX - 1) / TX);
-        if (s2d_cin == 0 && NREP > 1 && !want_bst) {
-            auto cost = [&](int nrep) {
-                const int g = (NT + nrep - 1) / nrep;
-                long long nb = 512 / g; if (nb < 1) nb = 1; if (nb > tiles) nb = tiles;
-                return (double)((tiles + nb - 1) / nb) * nrep * (nrep == 1 ? 1.08 : 1.0);
-            };
-            if (cost(1) < cost(NREP)) NREP = 1;
-        }
-    }
-    const int gy = (NT + NREP - 1) / NREP, NTpad = gy * NREP;
-    const int pkmode = split ? 3 : bf ? (s2d_cin > 0 ? 1 : 2) : 0;       // 0 fp32 | 1 bf16, one tap per K-step (sparse taps) | 2 bf16, K = 32 per step | 3 split: three bf16 planes, K = 32
-    const int NSTEPS = pkmode >= 2 ? (CK == 16 ? 14 : 7) : (27 * CK + 15) / 16;
-    const size_t pk = packed_bytes(Cin, Cout, CK);
-    char* opbase = reinterpret_cast<char*>(ws);                 // [packed weights | exponents / tile counters][tile table]: the workspace, or the caller's kept copy
-    int pp_mode = 0;
-    if (g_pp.mode && split) {
-        const int idx = g_pp.next++;
-        if (idx < 2 && g_pp.buf[idx] && g_pp.bytes[idx] >= pk + tile_table_bytes(N, D, H, W)) { opbase = g_pp.buf[idx]; pp_mode = g_pp.mode; }
-        else if (g_pp.mode == 2) return DA_ERR_WS_SMALL;
-    } else if (g_pp.mode == 2) return DA_ERR_UNSUPPORTED;       // (nothing to keep outside the split mode)
-    if (!pp_mode && ws_bytes < pk + tile_table_bytes(N, D, H, W)) return DA_ERR_WS_SMALL;
-    float* wp = reinterpret_cast<float*>(opbase);
-    int4* tiles = reinterpret_cast<int4*>(opbase + pk);
-    const long long total = (long long)(Cin / CK) * NSTEPS * NTpad * 256;
-    int* wexp = reinterpret_cast<int*>(opbase + pk - da_align(kWexpInts * sizeof(int)));
-    FwdP p;
-    p.bst_y = nullptr; p.bst_par = nullptr; p.bst_slope = -1.f;
-    p.ntz = (D + 3) / 4; p.nty = (H + TY - 1) / TY; p.ntx = (W + TX - 1) / TX;
-    p.ntiles = N * p.ntz * p.nty * p.ntx;
-    if (split) {
-        if (Cin / 8 > kWexpInts) return DA_ERR_UNSUPPORTED;
-        if (pp_mode == 2 && g_pp_collect) {
-            if (g_pp_ncollect >= kPackJobsMax) return DA_ERR_WS_SMALL;
-            g_pp_collect->j[g_pp_ncollect++] = PackJob{w_tio, reinterpret_cast<unsigned short*>(wp), wexp, tiles, Cin, Cout, NTpad, w_is_flipped_tr, p.ntiles, p.ntx, p.nty, p.ntz, cout0, CoutW};
-        } else if (pp_mode != 1)
-        hipLaunchKernelGGL(pack_split_weights_kernel, dim3(Cin / 8, 8), dim3(256), 0, st, w_tio, reinterpret_cast<unsigned short*>(wp), wexp, Cin, Cout, NTpad, w_is_flipped_tr,
-                           tiles, p.ntiles, p.ntx, p.nty, p.ntz, cout0, CoutW);
-        if (pp_mode == 2) { DA_LAUNCH_CHECK(); g_pp.used++; return 0; }
-    } else
-    hipLaunchKernelGGL(pack_fwd_weights_kernel, dim3(da_grid(total > p.ntiles ? total : p.ntiles, 256, 1024)), dim3(256), 0, st, w_tio, wp, Cin, Cout, CK, NSTEPS, NTpad, w_is_flipped_tr, total, pkmode,
-                       tiles, p.ntiles, p.ntx, p.nty, p.ntz, cout0, CoutW);
+static int conv3_mfma_launch(const ConvGemm& c) {
+    FwdPlan q;
+    if (const int rc = fwd_plan(c, da_matrix_mode(), &q)) return rc;
+    const int Cin = c.C1 + c.C2, CK = q.CK, NREP = q.NREP, gy = q.gy;
+    const bool bf = q.bf, hb = c.act_bf16 != 0, stats = c.stats_partial != nullptr, pro = c.pro != nullptr;
+    hipStream_t st = c.st;
+    const bool kept = q.split && c.pack.buf[0] && c.pack.bytes[0] >= q.pk + q.tt;
+    if (!kept && c.ws_bytes < q.pk + q.tt) return DA_ERR_WS_SMALL;
+    if (q.split && Cin / 8 > kWexpInts) return DA_ERR_UNSUPPORTED;
+    const PackJob j = pack_job(c, q, kept ? reinterpret_cast<char*>(const_cast<void*>(c.pack.buf[0])) : reinterpret_cast<char*>(c.ws));      // the caller's kept copy, or the workspace
+    const long long total = (long long)(Cin / CK) * q.NSTEPS * q.NTpad * 256;
+    if (!q.split)
+        hipLaunchKernelGGL(pack_fwd_weights_kernel, dim3(da_grid(total > q.ntiles ? total : q.ntiles, 256, 1024)), dim3(256), 0, st, c.w_tio, reinterpret_cast<float*>(j.wp), Cin, c.Cout, CK, q.NSTEPS, q.NTpad,
+                           c.flipped_tr, total, q.pkmode, j.tiles, q.ntiles, q.ntx, q.nty, q.ntz, j.cout0, j.CoutW);
+    else if (!kept) launch_split_pack(j, st);
     DA_LAUNCH_CHECK();
-    p.tiles = tiles;
-    p.in1 = in1; p.in2 = in2; p.C1 = C1; p.C2 = C2; p.wp = wp; p.bias = bias;
-    p.out1 = out1; p.out2 = out2; p.Cs1 = Cs1; p.Cs2 = Cs2;
-    p.N = N; p.D = D; p.H = H; p.W = W; p.Cout = Cout; p.NT = NTpad;
-    p.ntz = (D + 3) / 4; p.nty = (H + TY - 1) / TY; p.ntx = (W + TX - 1) / TX;
-    p.ntiles = N * p.ntz * p.nty * p.ntx; p.slope = slope;
-    p.maskmode = 0;
-    if (s2d_cin > 0) {
-        if (CK != 16) return DA_ERR_UNSUPPORTED;
-        if (!w_is_flipped_tr) { p.maskmode = 1; da_s2d_masks(p.masks, Cin / 16, 16, s2d_cin, 0); }
-        else { p.maskmode = 2; da_s2d_masks(p.masks, gy, NREP * 16, s2d_cin, 1); }
-    }
+    FwdP p;
+    const bool bst = q.family == kFamBst;
+    p.bst_y = bst ? c.bst.y : nullptr; p.bst_par = bst ? c.bst.par : nullptr; p.bst_slope = bst ? c.bst.slope : -1.f;
+    p.tiles = j.tiles; p.wp = reinterpret_cast<float*>(j.wp); p.wexp = j.wexp;
+    p.in1 = c.in1; p.in2 = c.in2; p.C1 = c.C1; p.C2 = c.C2; p.bias = c.bias;
+    p.out1 = c.out1; p.out2 = c.out2; p.Cs1 = c.Cs1; p.Cs2 = c.Cs2;
+    p.N = c.N; p.D = c.D; p.H = c.H; p.W = c.W; p.Cout = c.Cout; p.NT = q.NTpad;
+    p.ntz = q.ntz; p.nty = q.nty; p.ntx = q.ntx; p.ntiles = q.ntiles; p.nblocks = q.nblocks; p.slope = c.slope;
+    p.maskmode = q.family != kFamMasked ? 0 : c.flipped_tr ? 2 : 1;
+    if (p.maskmode == 1) da_s2d_masks(p.masks, Cin / 16, 16, c.s2d_cin, 0);
+    if (p.maskmode == 2) da_s2d_masks(p.masks, gy, NREP * 16, c.s2d_cin, 1);
     { static int abl = -1; if (abl < 0) { const char* e = getenv("DA_ABLATE"); abl = e ? atoi(e) : 0; } p.ablate = abl; }
-    {   // one resident round: 2 workgroups per CU x 256 CUs, split over the cout groups
-        // (a third workgroup per CU for the split kernels -- 168 VGPRs, 3 x 52 KB of LDS -- was measured and dropped: in split mode the
-        // matrix pipe is already busy ~100 % of the shader cycles and the clock is set by the power limit)
-        int nblk = 512 / gy; if (nblk < 1) nblk = 1; if (nblk > p.ntiles) nblk = p.ntiles;
-        if (nblk >= 8) nblk &= ~7;                           // multiple of 8: blockIdx.x % 8 is then the XCD (tile_walk)
-        p.nblocks = nblk;
-    }
     p.s2in = S2dSrc{0, 0, 0, 0}; p.s2out = S2dSrc{0, 0, 0, 0};
-    if (s2d_cin > 0) (w_is_flipped_tr ? p.s2out : p.s2in) = S2dSrc{s2d_cin, s2f->D0, s2f->H0, s2f->W0};
-    p.stats_partial = stats_partial;
-    if (stats_nparts) *stats_nparts = 0;
-    p.ps1 = p.pt1 = p.ps2 = p.pt2 = nullptr; p.pslope1 = p.pslope2 = -1.f;
-    p.wexp = wexp;
-    if (pro) {
-        const float *ones, *zeros;
-        if (const int rc = pro_identity(&ones, &zeros)) return rc;
-        if (pro_slopes(pro, C2, &p.pslope1, &p.pslope2)) return DA_ERR_UNSUPPORTED;
-        p.ps1 = pro->s1 ? pro->s1 : ones; p.pt1 = pro->s1 ? pro->t1 : zeros;
-        p.ps2 = (C2 > 0 && pro->s2) ? pro->s2 : ones; p.pt2 = (C2 > 0 && pro->s2) ? pro->t2 : zeros;
+    if (c.s2d_cin > 0) (c.flipped_tr ? p.s2out : p.s2in) = S2dSrc{c.s2d_cin, c.s2f->D0, c.s2f->H0, c.s2f->W0};
+    p.stats_partial = c.stats_partial;
+    if (c.stats_nparts) *c.stats_nparts = 0;
+    if (const int rc = set_prologue(p, c.pro, c.C2)) return rc;
+    if (q.split) {
+        if (stats && c.stats_nparts) *c.stats_nparts = p.nblocks;
+        if (bst) return launch_fwd_mfma<8, 1, kSplit | kBst>(p, gy, st);      // (unpaired staging: with the pair's second parked chunk the eight y quads of the epilogue spill)
+        if (q.family == kFamPaired) return stats ? launch_fwd_mfma<8, 1, kSplit | kStats | kPair>(p, gy, st) : launch_fwd_mfma<8, 1, kSplit | kPair>(p, gy, st);
+        return NREP == 1 ? launch_fwd_split<1>(stats, pro, p, gy, st) : launch_fwd_split<2>(stats, pro, p, gy, st);
     }
-    if (split) {
-        if (stats_partial && stats_nparts) *stats_nparts = p.nblocks;
-        // paired staging (one sector fetch per two chunks): one N-tile, an even number of 8-channel chunks that pair up inside in1 / in2
-        if (want_bst) {                                      // (da_conv3d_k3_dgrad_bst checked the shape: one output tensor of <= 32 channels, no prologue)
-            if (!(NREP == 1 && !pro && Cs2 == 0 && gy <= 2)) return DA_ERR_UNSUPPORTED;
-            p.bst_y = g_bst.y; p.bst_par = g_bst.par; p.bst_slope = g_bst.slope;
-            return launch_fwd_mfma<8, 1, kSplit | kBst>(p, gy, st);      // (unpaired staging: with the pair's second parked chunk the eight y quads of the epilogue spill)
-        }
-        if (NREP == 1 && !pro && C1 % 16 == 0 && C2 % 16 == 0)
-            return stats_partial ? launch_fwd_mfma<8, 1, kSplit | kStats | kPair>(p, gy, st) : launch_fwd_mfma<8, 1, kSplit | kPair>(p, gy, st);
-        if (NREP == 1) return launch_fwd_split<1>(stats_partial != nullptr, pro != nullptr, p, gy, st);
-        if (NREP == 2) return launch_fwd_split<2>(stats_partial != nullptr, pro != nullptr, p, gy, st);
-        return DA_ERR_UNSUPPORTED;
-    }
-    if (stats_partial && p.maskmode == 0 && (CK == 16 || CK == 8) && NREP <= 2) {
-        if (stats_nparts) *stats_nparts = p.nblocks;
+    if (stats && p.maskmode == 0 && NREP <= 2) {
+        if (c.stats_nparts) *c.stats_nparts = p.nblocks;
         return pro ? launch_fwd_dense<kStats | kPro>(CK, NREP, bf, hb, p, gy, st) : launch_fwd_dense<kStats>(CK, NREP, bf, hb, p, gy, st);
     }
     if (pro) return launch_fwd_dense<kPro>(CK, NREP, bf, hb, p, gy, st);
@@ -2038,6 +2028,16 @@ static int conv3_mfma_fwd_impl(const float* in1, int C1, const float* in2, int C
     return launch_fwd_dense<0>(CK, NREP, bf, hb, p, gy, st);
 }
 
+int da_conv3_mfma_fwd(const ConvGemm& call) {
+    if (call.act_bf16 && da_matrix_mode() != 1) return DA_ERR_UNSUPPORTED;          // bf16 activation storage goes with the bf16 matrix mode
+    ConvGemm c = call, l[2];
+    c.pack = take_handover(c.w_tio);
+    const int n = fwd_launches(c, da_matrix_mode(), l);
+    for (int i = 0; i < n; ++i)
+        if (const int rc = conv3_mfma_launch(l[i])) return rc;
+    return 0;
+}
+
 // matrix mode of the 3x3x3 convolutions: process-wide switch (like da_set_conv_direct); the setters return the previous setting.
 //   0  fp32 operands on v_mfma_f32_16x16x4_f32 (an fmaf chain)
 //   1  operands ROUNDED to bf16 (BASELINE configs[4]'s precision; not fp32-accurate)
@@ -2051,12 +2051,10 @@ int da_matrix_mode() {
     }
     return g_matrix_mode;
 }
-bool da_matrix_bf16() { return da_matrix_mode() == 1; }
 extern "C" int da_set_matrix_bf16(int on) { const int prev = da_matrix_mode() == 1 ? 1 : 0; g_matrix_mode = on ? 1 : 0; return prev; }
 extern "C" int da_set_matrix_mode(int mode) { const int prev = da_matrix_mode(); if (mode < 0 || mode > 2) return -1; g_matrix_mode = mode; return prev; }
 
 static bool smallcin_ok(int C1, int C2, int Cout, int stride) { return stride == 1 && C1 + C2 <= 4 && Cout <= 32; }   // + 32-bit offsets, checked at launch
-static const int kScBlocks = 1024;
 
 bool da_conv3_thin_supported(int C1, int C2, int Cout, int stride) {
     const int Cin = C1 + C2;
@@ -2212,9 +2210,11 @@ static int launch_smallcin_wgrad(int MT, int NT, int nb, const ScP& sp, hipStrea
     return 0;
 }
 
-int da_conv3_mfma_wgrad(const float* in1, int C1, const float* in2, int C2, const float* dy, float* dw_tio,
-                        int N, int D, int H, int W, int Cout, int stride, void* ws, size_t ws_bytes, hipStream_t st, int s2d_cin, const DaPro* pro, const DaS2dFuse* s2f, int act_bf16) {
-    const bool hb = act_bf16 != 0;
+int da_conv3_mfma_wgrad(const ConvWgrad& c) {
+    const float *in1 = c.in1, *in2 = c.in2, *dy = c.dy; float* dw_tio = c.dw_tio; void* ws = c.ws; const size_t ws_bytes = c.ws_bytes; hipStream_t st = c.st;
+    const int C1 = c.C1, C2 = c.C2, N = c.N, D = c.D, H = c.H, W = c.W, Cout = c.Cout, stride = c.stride, s2d_cin = c.s2d_cin;
+    const DaPro* pro = c.pro; const DaS2dFuse* s2f = c.s2f;
+    const bool hb = c.act_bf16 != 0;
     // bf16 activation storage: the matrix-core kernels of the bf16 matrix mode only (few-channel layers: the caller converts)
     if (hb && (da_matrix_mode() != 1 || pick_ck(C1, C2) == 0 || Cout % 4 != 0 || Cout <= 4 || smallcin_ok(C1, C2, Cout, stride) ||
                da_conv3_fewcin_wgrad_supported(C1, C2, Cout, stride))) return DA_ERR_UNSUPPORTED;
@@ -2268,7 +2268,7 @@ int da_conv3_mfma_wgrad(const float* in1, int C1, const float* in2, int C2, cons
     const bool rows1 = hb && da_matrix_mode() == 1 && s2d_cin == 0 && Cout % 4 == 0 && Cout <= 16 && pick_ck(C1, C2) != 0;
     const WgPlan q = wgrad_plan(N, D, H, W, C1, C2, Cout, split || rows1, split || rows1);
     if (!q.CK) return DA_ERR_UNSUPPORTED;
-    const bool bf = da_matrix_bf16();      // (Cout % 4 != 0 keeps the exact kernel: its dY staging is scalar)
+    const bool bf = da_matrix_mode() == 1;      // (Cout % 4 != 0 keeps the exact kernel: its dY staging is scalar)
     if ((unsigned long long)D * H * W * 4ull * (unsigned long long)((C1 > C2 ? C1 : C2) > Cout ? (C1 > C2 ? C1 : C2) : Cout) >= 0xFFFFFFF0ull) return DA_ERR_UNSUPPORTED;
     if (ws_bytes < q.partial_bytes + ((split || rows1) ? wg_tile_table_bytes(N, D, H, W) : 0)) return DA_ERR_WS_SMALL;
     WgP p;
@@ -2291,14 +2291,7 @@ int da_conv3_mfma_wgrad(const float* in1, int C1, const float* in2, int C2, cons
         if (q.CK != 16) return DA_ERR_UNSUPPORTED;
         p.maskmode = 1; da_s2d_masks(p.masks, q.nchunks, 16, s2d_cin, 0);
     }
-    p.ps1 = p.pt1 = p.ps2 = p.pt2 = nullptr; p.pslope1 = p.pslope2 = -1.f;
-    if (pro) {
-        const float *ones, *zeros;
-        if (const int rc0 = pro_identity(&ones, &zeros)) return rc0;
-        if (pro_slopes(pro, C2, &p.pslope1, &p.pslope2)) return DA_ERR_UNSUPPORTED;
-        p.ps1 = pro->s1 ? pro->s1 : ones; p.pt1 = pro->s1 ? pro->t1 : zeros;
-        p.ps2 = (C2 > 0 && pro->s2) ? pro->s2 : ones; p.pt2 = (C2 > 0 && pro->s2) ? pro->t2 : zeros;
-    }
+    if (const int rc0 = set_prologue(p, pro, C2)) return rc0;
     int rc = DA_ERR_UNSUPPORTED;
     if (split || rows1) rc = pro ? launch_rows_wgrad<kPro>(rows1, p, q, st) : launch_rows_wgrad<0>(rows1, p, q, st);
     else if (pro) rc = launch_wgrad_dense<kPro>(bf, hb, p, q, st);
@@ -2313,77 +2306,78 @@ int da_conv3_mfma_wgrad(const float* in1, int C1, const float* in2, int C2, cons
     return da_reduce_partials(p.partial, q.nslabs, p.O, dw_tio, st);
 }
 
-// ---- C ABI of the kept packs (see PrepackState) --------------------------------------------------------------------------------------------
+// ---- C ABI of the kept packs (documented in include/deepatlas_hip.h; the hand-over: take_handover) ------------------------------------------
 extern "C" size_t da_conv3d_k3_pack_bytes(int N, int D, int H, int W, int Cin, int Cout) {
     if (Cin % 8 != 0 && Cout % 8 != 0) return 0;
     size_t a = Cin % 8 == 0 ? packed_bytes(Cin, Cout, 8) : 0;
     if (Cout % 8 == 0) { const size_t b = packed_bytes(Cout, Cin, 8); if (b > a) a = b; }      // (the data gradient: channels exchanged)
     return a + tile_table_bytes(N, D, H, W);
 }
-// Fill caller-owned buffer(s) with the packed operand of the stride-1 3x3x3 convolution C1 + C2 -> Cout on an N x D x H x W grid: the forward's
-// (dgrad = 0) or the data gradient's (dgrad = 1; two regions when that call runs as two launches).  *used = regions filled; 0 = this shape / matrix
-// mode does not run the split matrix-core kernels, keep nothing.  Only enqueues (one small kernel per region) on `stream`.
-extern "C" int da_conv3d_k3_prepack(const float* w_tio, int C1, int C2, int Cout, int dgrad, int N, int D, int H, int W,
-                                    void* b0, size_t n0, void* b1, size_t n1, int* used, void* stream) {
-    if (used) *used = 0;
+// What da_conv3d_k3_prepack has to enqueue: the packs, one per launch (fwd_launches), of the call that will read them -- the plain forward (dgrad = 0)
+// or data gradient of the layer C1 + C2 -> Cout, planned as that call will be.  *njobs = 0: this shape / matrix mode does not run the split kernels.
+static int prepack_jobs(const float* w_tio, int C1, int C2, int Cout, int dgrad, int N, int D, int H, int W, void* b0, size_t n0, void* b1, size_t n1, PackJob jobs[2], int* njobs) {
+    *njobs = 0;
     if (!w_tio || !b0 || C1 <= 0 || C2 < 0 || Cout <= 0 || N <= 0) return DA_ERR_BADARG;
     if (da_matrix_mode() != 2) return 0;
     const int Cin = C1 + C2;
     if (!dgrad ? !da_conv3_mfma_fwd_supported(C1, C2, Cout, 1) : !da_conv3_mfma_fwd_supported(Cout, 0, Cin, 1, C1, C2)) return 0;
-    g_pp = PrepackState{2, w_tio, {(char*)b0, (char*)b1}, {n0, b1 ? n1 : 0}, 0, 0};
-    float* dummy = const_cast<float*>(w_tio);                   // (never dereferenced: in fill mode the call returns before its matrix kernel)
-    const int rc = !dgrad ? da_conv3_mfma_fwd(dummy, C1, C2 > 0 ? dummy : nullptr, C2, w_tio, 0, nullptr, dummy, Cout, nullptr, 0, N, D, H, W, Cout, 1, -1.f,
-                                              b0, 0, (hipStream_t)stream, 0, nullptr, nullptr, nullptr, nullptr, 0)
-                          : da_conv3_mfma_fwd(dummy, Cout, nullptr, 0, w_tio, 1, nullptr, dummy, C1, C2 > 0 ? dummy : nullptr, C2, N, D, H, W, Cin, 1, -1.f,
-                                              b0, 0, (hipStream_t)stream, 0, nullptr, nullptr, nullptr, nullptr, 0);
-    const int n = g_pp.used;
-    g_pp.mode = 0;
-    if (rc == DA_ERR_UNSUPPORTED) return 0;
-    if (rc) return rc;
+    ConvGemm c = {}, l[2];              // (no tensors: the plan and the pack do not read them)
+    c.w_tio = w_tio; c.flipped_tr = dgrad; c.N = N; c.D = D; c.H = H; c.W = W; c.slope = -1.f;
+    if (!dgrad) { c.C1 = C1; c.C2 = C2; c.Cs1 = Cout; c.Cout = Cout; }
+    else { c.C1 = Cout; c.Cs1 = C1; c.Cs2 = C2; c.Cout = Cin; }
+    const int n = fwd_launches(c, 2, l);
+    void* const buf[2] = {b0, b1}; const size_t bytes[2] = {n0, b1 ? n1 : 0};
+    for (int i = 0; i < n; ++i) {
+        FwdPlan q;
+        int rc = fwd_plan(l[i], 2, &q);
+        if (!rc && (!buf[i] || bytes[i] < q.pk + q.tt)) rc = DA_ERR_WS_SMALL;
+        if (!rc && (l[i].C1 + l[i].C2) / 8 > kWexpInts) rc = DA_ERR_UNSUPPORTED;
+        if (rc) return rc == DA_ERR_UNSUPPORTED ? 0 : rc;
+        jobs[i] = pack_job(l[i], q, reinterpret_cast<char*>(buf[i]));
+    }
+    *njobs = n;
+    return 0;
+}
+extern "C" int da_conv3d_k3_prepack(const float* w_tio, int C1, int C2, int Cout, int dgrad, int N, int D, int H, int W,
+                                    void* b0, size_t n0, void* b1, size_t n1, int* used, void* stream) {
+    if (used) *used = 0;
+    PackJob jobs[2]; int n = 0;
+    if (const int rc = prepack_jobs(w_tio, C1, C2, Cout, dgrad, N, D, H, W, b0, n0, b1, n1, jobs, &n)) return rc;
+    for (int i = 0; i < n; ++i) { launch_split_pack(jobs[i], (hipStream_t)stream); DA_LAUNCH_CHECK(); }
     if (used) *used = n;
     return 0;
 }
-// The next stride-1 3x3x3 forward / data-gradient call of this thread on `w_tio` reads its packed operand(s) from here instead of packing (one call only;
-// a call on other weights, or one that takes another kernel family, drops the hand-over).
 extern "C" void da_conv3d_k3_use_prepacked(const float* w_tio, const void* b0, size_t n0, const void* b1, size_t n1) {
-    g_pp = PrepackState{(w_tio && b0) ? 1 : 0, w_tio, {(char*)const_cast<void*>(b0), (char*)const_cast<void*>(b1)}, {n0, b1 ? n1 : 0}, 0, 0};
+    g_handover = (w_tio && b0) ? Handover{w_tio, ConvPack{{b0, b1}, {n0, b1 ? n1 : 0}}} : Handover{nullptr, {}};
 }
 
-// da_conv3d_k3_prepack for `n` layers with as few launches as the kernel-argument size allows (48 regions per launch): what the host side runs after an
-// optimiser step.  Arrays of length n; used[i] as in da_conv3d_k3_prepack.
+// ... for `n` layers with as few launches as the kernel-argument size allows (48 regions per launch): what the host side runs after an optimiser step
 extern "C" int da_conv3d_k3_prepack_many(int n, const float* const* w_tio, const int* C1, const int* C2, const int* Cout, const int* dgrad,
                                          const int* N, const int* D, const int* H, const int* W,
                                          void* const* b0, const size_t* n0, void* const* b1, const size_t* n1, int* used, void* stream) {
     if (n <= 0) return 0;
     if (!w_tio || !C1 || !C2 || !Cout || !dgrad || !N || !D || !H || !W || !b0 || !n0 || !b1 || !n1 || !used) return DA_ERR_BADARG;
-    static thread_local PackJobs jobs;
+    PackJobs jobs; int njobs = 0;
     auto flush = [&]() -> int {
-        if (g_pp_ncollect == 0) return 0;
+        if (njobs == 0) return 0;
         int gx = 1;
-        for (int k = 0; k < g_pp_ncollect; ++k) if (jobs.j[k].Cin / 8 > gx) gx = jobs.j[k].Cin / 8;
-        hipLaunchKernelGGL(pack_split_weights_many_kernel, dim3(gx, 8, g_pp_ncollect), dim3(256), 0, (hipStream_t)stream, jobs);
-        g_pp_ncollect = 0;
+        for (int k = 0; k < njobs; ++k) if (jobs.j[k].Cin / 8 > gx) gx = jobs.j[k].Cin / 8;
+        hipLaunchKernelGGL(pack_split_weights_many_kernel, dim3(gx, 8, njobs), dim3(256), 0, (hipStream_t)stream, jobs);
+        njobs = 0;
         DA_LAUNCH_CHECK();
         return 0;
     };
-    g_pp_collect = &jobs; g_pp_ncollect = 0;
     int rc = 0;
     for (int i = 0; i < n && !rc; ++i) {
-        if (g_pp_ncollect + 2 > kPackJobsMax) rc = flush();
-        if (!rc) rc = da_conv3d_k3_prepack(w_tio[i], C1[i], C2[i], Cout[i], dgrad[i], N[i], D[i], H[i], W[i], b0[i], n0[i], b1[i], n1[i], &used[i], stream);
+        if (njobs + 2 > kPackJobsMax && (rc = flush())) break;
+        rc = prepack_jobs(w_tio[i], C1[i], C2[i], Cout[i], dgrad[i], N[i], D[i], H[i], W[i], b0[i], n0[i], b1[i], n1[i], &jobs.j[njobs], &used[i]);
+        njobs += used[i];
     }
-    if (!rc) rc = flush();
-    g_pp_collect = nullptr; g_pp_ncollect = 0;
-    return rc;
+    return rc ? rc : flush();
 }
 
-// da_conv3d_k3_dgrad of a layer whose FIRST input was act(BN(y)) applied on the fly (y = the producer's raw conv output, `stats4` = its statistics
-// rows [mean | rstd | scale | shift][C1], `slope` its activation): besides dx1 -- the gradient with respect to the ACTIVATED tensor, as always -- the
-// epilogue accumulates the producer's BatchNorm-backward sums, bst[*bst_n][2][C1] doubles = (sum dz, sum dz (y - mean)), dz = dx act'(y scale + shift),
-// for da_bn_act_bwd_dbias_pre: the stand-alone reduction pass over (dx1, y) is not needed.  Split matrix mode; one-input layers of <= 16 channels, and
-// concat layers (dx2 / C2: the decoder's 48 <- 16 data gradient, C1 = 32 up-sampled channels first, unets.py:275) as two launches -- dx1 with one
-// N-tile per workgroup and the epilogue, dx2 as da_conv3d_k3_dgrad does it.  Anything else returns DA_ERR_UNSUPPORTED and the caller runs
-// da_conv3d_k3_dgrad + the usual BatchNorm backward.  autograd of unets.py:30-32.
+// da_conv3d_k3_dgrad with the producer's BatchNorm-backward sums in the epilogue (deepatlas_hip.h): the data-gradient call with ConvGemm::bst set.  One-input
+// layers of one or two N-tiles, and the 32 + 16 concat layer, whose two launches (fwd_launches) carry the epilogue on the first, dx1.
 extern "C" int da_conv3d_k3_dgrad_bst(const float* dy, const float* w_tio, float* dx1, int C1, float* dx2, int C2, int N, int D, int H, int W, int Cout,
                                       const float* y, const float* stats4, float slope, double* bst, int bst_cap, int* bst_n,
                                       void* ws, size_t ws_bytes, void* stream) {
@@ -2392,23 +2386,13 @@ extern "C" int da_conv3d_k3_dgrad_bst(const float* dy, const float* w_tio, float
     if (da_matrix_mode() != 2 || bst_cap < 512) return DA_ERR_UNSUPPORTED;
     if (C2 == 0) {
         if (C1 > 32 || C1 % 4 != 0 || (C1 > 16 && C1 % 16 != 0) || !da_conv3_mfma_fwd_supported(Cout, 0, C1, 1, C1, 0)) return DA_ERR_UNSUPPORTED;      // (one or two N-tiles)
-        if (ws_bytes < da_conv3_mfma_ws_bytes(N, D, H, W, C1, Cout, 1)) return DA_ERR_WS_SMALL;
-        g_bst = BstState{y, stats4, slope};
-        const int rc = da_conv3_mfma_fwd(dy, Cout, nullptr, 0, w_tio, 1, nullptr, dx1, C1, nullptr, 0, N, D, H, W, C1, 1, -1.f, ws, ws_bytes, (hipStream_t)stream, 0, bst, bst_n);
-        g_bst = BstState{nullptr, nullptr, -1.f};
-        return rc;
-    }
-    if (C1 != 32 || C2 % 16 != 0 || C2 > 16 || !da_conv3_mfma_fwd_supported(Cout, 0, C1 + C2, 1, C1, C2) || pick_ck(Cout, 0) == 0) return DA_ERR_UNSUPPORTED;
+    } else if (C1 != 32 || C2 % 16 != 0 || C2 > 16 || !da_conv3_mfma_fwd_supported(Cout, 0, C1 + C2, 1, C1, C2) || pick_ck(Cout, 0) == 0) return DA_ERR_UNSUPPORTED;
     if (ws_bytes < da_conv3_mfma_ws_bytes(N, D, H, W, C1 + C2, Cout, 1)) return DA_ERR_WS_SMALL;
-    struct PpReset { ~PpReset() { if (g_pp.mode == 1) g_pp.mode = 0; } } pp_reset;
-    if (g_pp.mode && g_pp.w != w_tio) g_pp.mode = 0;
-    g_bst = BstState{y, stats4, slope};
-    int rc = conv3_mfma_fwd_impl(dy, Cout, nullptr, 0, w_tio, 1, nullptr, dx1, C1, nullptr, 0, N, D, H, W, C1, 1, -1.f, ws, ws_bytes, (hipStream_t)stream, 0, bst, bst_n,
-                                 nullptr, nullptr, 0, C1 + C2, false);
-    g_bst = BstState{nullptr, nullptr, -1.f};
-    if (rc) { *bst_n = 0; return rc; }
-    rc = conv3_mfma_fwd_impl(dy, Cout, nullptr, 0, w_tio, 1, nullptr, dx2, C2, nullptr, 0, N, D, H, W, C2, 1, -1.f, ws, ws_bytes, (hipStream_t)stream, 0, nullptr, nullptr,
-                             nullptr, nullptr, C1, C1 + C2, false);
+    ConvGemm c = {};
+    c.in1 = dy; c.C1 = Cout; c.w_tio = w_tio; c.flipped_tr = 1; c.out1 = dx1; c.Cs1 = C1; c.out2 = C2 > 0 ? dx2 : nullptr; c.Cs2 = C2;
+    c.N = N; c.D = D; c.H = H; c.W = W; c.Cout = C1 + C2; c.slope = -1.f; c.ws = ws; c.ws_bytes = ws_bytes; c.st = (hipStream_t)stream;
+    c.stats_partial = bst; c.stats_nparts = bst_n; c.bst = ConvBst{y, stats4, slope};
+    const int rc = da_conv3_mfma_fwd(c);
     if (rc) *bst_n = 0;
     return rc;
 }

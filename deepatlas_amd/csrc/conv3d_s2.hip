@@ -75,8 +75,9 @@ int da_conv3_s2_fwd(const float* in, int Cin, const float* w_tio, const float* b
     hipLaunchKernelGGL(expand_weights_s2d_kernel, dim3(da_grid(27 * 8 * Cin * Cout, 256, 512)), dim3(256), 0, st, w_tio, We, Cin, Cout);
     DA_LAUNCH_CHECK();
     const DaS2dFuse f = {D, H, W};
-    return da_conv3_mfma_fwd(in, 8 * Cin, nullptr, 0, We, 0, bias, out, Cout, nullptr, 0, N, p.Dq, p.Hq, p.Wq, Cout, 1, slope,
-                             inner, p.inner_bytes, st, Cin, nullptr, nullptr, nullptr, &f, act_bf16);
+    ConvGemm c = {}; c.in1 = in; c.C1 = 8 * Cin; c.w_tio = We; c.bias = bias; c.out1 = out; c.Cs1 = Cout; c.N = N; c.D = p.Dq; c.H = p.Hq; c.W = p.Wq; c.Cout = Cout; c.slope = slope;
+    c.ws = inner; c.ws_bytes = p.inner_bytes; c.st = st; c.s2d_cin = Cin; c.s2f = &f; c.act_bf16 = act_bf16;
+    return da_conv3_mfma_fwd(c);
 }
 
 int da_conv3_s2_dgrad(const float* dy, const float* w_tio, float* dx, int Cin, int N, int D, int H, int W, int Cout,
@@ -92,8 +93,9 @@ int da_conv3_s2_dgrad(const float* dy, const float* w_tio, float* dx, int Cin, i
     DA_LAUNCH_CHECK();
     // dS = conv(dY, flip/transpose(W')) : logical Cin = Cout, logical Cout = 8*Cin, stored to dX through the inverse view
     const DaS2dFuse f = {D, H, W};
-    return da_conv3_mfma_fwd(dy, Cout, nullptr, 0, We, 1, nullptr, dx, 8 * Cin, nullptr, 0, N, p.Dq, p.Hq, p.Wq, 8 * Cin, 1, -1.f,
-                             inner, p.inner_bytes, st, Cin, nullptr, nullptr, nullptr, &f, act_bf16);
+    ConvGemm c = {}; c.in1 = dy; c.C1 = Cout; c.w_tio = We; c.flipped_tr = 1; c.out1 = dx; c.Cs1 = 8 * Cin; c.N = N; c.D = p.Dq; c.H = p.Hq; c.W = p.Wq; c.Cout = 8 * Cin; c.slope = -1.f;
+    c.ws = inner; c.ws_bytes = p.inner_bytes; c.st = st; c.s2d_cin = Cin; c.s2f = &f; c.act_bf16 = act_bf16;
+    return da_conv3_mfma_fwd(c);
 }
 
 int da_conv3_s2_wgrad(const float* in, int Cin, const float* dy, float* dw_tio, int N, int D, int H, int W, int Cout,
@@ -104,7 +106,9 @@ int da_conv3_s2_wgrad(const float* in, int Cin, const float* dy, float* dw_tio, 
     if (ws_bytes < da_conv3_s2_ws_bytes(N, D, H, W, Cin, Cout)) return DA_ERR_WS_SMALL;
     float* dWe = (float*)((char*)ws + p.we_bytes); char* inner = (char*)ws + 2 * p.we_bytes;
     const DaS2dFuse f = {D, H, W};
-    int rc = da_conv3_mfma_wgrad(in, 8 * Cin, nullptr, 0, dy, dWe, N, p.Dq, p.Hq, p.Wq, Cout, 1, inner, p.inner_bytes, st, Cin, nullptr, &f, act_bf16);
+    ConvWgrad c = {}; c.in1 = in; c.C1 = 8 * Cin; c.dy = dy; c.dw_tio = dWe; c.N = N; c.D = p.Dq; c.H = p.Hq; c.W = p.Wq; c.Cout = Cout; c.stride = 1;
+    c.ws = inner; c.ws_bytes = p.inner_bytes; c.st = st; c.s2d_cin = Cin; c.s2f = &f; c.act_bf16 = act_bf16;
+    int rc = da_conv3_mfma_wgrad(c);
     if (rc) return rc;
     hipLaunchKernelGGL(extract_wgrad_s2d_kernel, dim3(da_grid(27 * Cin * Cout, 256, 512)), dim3(256), 0, st, dWe, dw_tio, Cin, Cout);
     DA_LAUNCH_CHECK();
