@@ -7,8 +7,8 @@ front for `up2`, then the activation, gradients by autograd with a drawn output 
 db are compared.  Cases, builders, the reference, the guard-band rule (block_cases.activate / check_band / G), the restated launcher predicates, CEIL and TOL live in
 tests/regconv_cases.py; every family runs `regconv_cases.run_cases`: the pinned examples, then 60 derandomised hypothesis examples, every example in matrix mode
 'fp32_split' and 'fp32', both against ONE float64 reference.  tests/test_regconv_reference.py runs the same examples on the CPU and shows the fp32 oracle within a
-quarter of each tolerance and the guard band under its cap.  Drawn slopes: -1.0 (no activation), 0.0, 0.01.  bf16 activation storage is not covered here
-(tests/test_gpu_bf16_storage.py).
+quarter of each tolerance and the guard band under its cap.  Drawn slopes: -1.0 (no activation), 0.0, 0.01.  bf16 activation storage is not covered here:
+the `_bf16` twins of these kernels are held to float64 entry by entry in tests/test_gpu_bf16_shapes.py (family `conv3`), whole networks in tests/test_gpu_bf16_storage.py.
 
 Routes (regconv_cases.reached restates da_conv3d_k3_fwd / _dgrad / _wgrad, da_conv3_s2_*, da_conv3_mfma_wgrad, da_upconv3d_k3_*; every pinned example carries the
 route and the counts below in `want` and regconv_cases.check_pinned asserts them on every run, here and in the CPU file):
