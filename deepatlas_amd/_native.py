@@ -172,6 +172,9 @@ SIGNATURES = {
     'da_assemble_tiles': (I, [P, P, I, I, I, I, P, P, I, P]),
     'da_synth_volume': (I, [P, P, I, I, I, I, I, I, F, ctypes.c_uint, I, P]),
     'da_spatial_resample': (I, [P, P, I, I, P, P, I, P, P, I, I, I, I, I, I, I, I, P]),
+    'da_gauss_blur3d': (I, [P, P, P, P, I, P, I, I, I, I, I, P]),
+    'da_bilateral3d': (I, [P, P, P, P, I, I, I, I, F, F, P, I, I, I, I, I, P]),
+    'da_intensity_augment': (I, [P, P, P, P, I, I, I, I, I, I, I, I, I, I, P]),
     'da_lncc_ws_bytes': (SZ, [I, I, I, I, I, I, I]),
     'da_lncc_fwd': (I, [P, P, I, I, I, I, I, I, I, F, P, P, P, SZ, P]),
     'da_lncc_bwd': (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, F, P, SZ, P]),

@@ -2,6 +2,7 @@
 // (:124-158), Partition's overlap tiling with reflect padding and its two assemble modes (:508-649).  Plain HBM-bound copy kernels:
 // one thread per output element, 64-bit indexing, no intermediate padded volume (the reflect index is computed per element).
 #include "common.h"
+#include "counter_hash.h"
 
 namespace {
 
@@ -113,14 +114,7 @@ __global__ void assemble_vote_kernel(const unsigned char* __restrict__ tiles, un
 // ---- synthetic volumes (SURVEY.md row f4 "synthetic-volume generator on device"; BASELINE configs are all synthetic) ----------
 // Counter-based: every element is a pure function of (seed, sample, voxel index), so the numpy restatement (oracle/datapath.py
 // synth_volume) reproduces it bit for bit and ranks / batch sizes do not change what a given sample looks like.
-__device__ __forceinline__ unsigned int mix32(unsigned int x) {
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
-}
-__device__ __forceinline__ unsigned int synth_bits(unsigned int seed, unsigned long long i, unsigned int stream_id) {
-    const unsigned int hi = (unsigned int)(i >> 32), lo = (unsigned int)i;
-    return mix32(mix32(lo ^ mix32(seed + 0x9e3779b9u * hi)) + stream_id);
-}
+// (the hash itself: counter_hash.h, shared with intensity.hip)
 
 // mode 0 (throughput inputs): img ~ U[0,1), lab ~ U{0..C-1}, iid.
 // mode 1 (Dice-parity inputs): blocky label map lab = ((z / bz) * 5 + (y / by) * 3 + x / bx + sample) % C with b = max(dim / 8, 1),
@@ -133,10 +127,10 @@ __global__ void synth_volume_kernel(float* __restrict__ img, unsigned char* __re
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const long long n = i / V, v = i - n * V;
         const unsigned long long ctr = (unsigned long long)(sample0 + n) * (unsigned long long)V + (unsigned long long)v;
-        const float u = (float)(synth_bits(seed, ctr, 0u) >> 8) * inv24;
+        const float u = (float)(da_synth_bits(seed, ctr, 0u) >> 8) * inv24;
         if (mode == 0) {
             if (img) img[i] = u;
-            if (lab) lab[i] = (unsigned char)(synth_bits(seed, ctr, 1u) % (unsigned int)C);
+            if (lab) lab[i] = (unsigned char)(da_synth_bits(seed, ctr, 1u) % (unsigned int)C);
         } else {
             const int x = (int)(v % W); const long long r = v / W;
             const int y = (int)(r % H), z = (int)(r / H);

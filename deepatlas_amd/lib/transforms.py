@@ -1,10 +1,12 @@
 """Tensor-level transforms (lib/transforms.py) on the device: mask_to_one_hot / SegMaskToOneHot (:652-689), and the data path of
 SURVEY.md row f4 -- SitkToTensor's clamp + cast (:71-92), CropTensor (:124-158), Partition's overlap tiling with reflect padding
-and both assemble modes (:508-649), and the two random spatial augmentations RandomRigidTransform (:202-259) and
-RandomBSplineTransform (:161-199) as device resamples.  The SimpleITK read / crop / filter transforms (GaussianBlur, BilateralFilter,
-Resample to a voxel size, Normalization, LeftToRight, RandomCrop, BalancedRandomCrop, SegmentationLabelFilter) are host I/O and stay
-out of scope; these classes take numpy arrays (what sitk.GetArrayFromImage returns) or tensors and hand back DEVICE tensors, so a
-loader thread only uploads the raw volume once.
+and both assemble modes (:508-649), the two random spatial augmentations RandomRigidTransform (:202-259) and
+RandomBSplineTransform (:161-199) as device resamples, and the intensity half: the reference's two image filters GaussianBlur
+(:293-306) and BilateralFilter (:308-320) and the project's own RandomIntensityTransform (bias field, gamma, gain / offset, noise) as
+device kernels.  Only the SimpleITK read / resample-to-voxel-size / crop transforms (Resample to a voxel size, Normalization,
+LeftToRight, RandomCrop, BalancedRandomCrop, SegmentationLabelFilter) are host I/O and stay out of scope; these classes take numpy
+arrays (what sitk.GetArrayFromImage returns) or tensors and hand back DEVICE tensors, so a loader thread only uploads the raw volume
+once.
 """
 import ctypes
 
@@ -383,11 +385,181 @@ class RandomRigidTransform(object):
         return _store(sample, img, seg, single)
 
 
-AUGMENTATIONS = {'rigid': RandomRigidTransform, 'bspline': RandomBSplineTransform}
+# ---- intensity augmentation (lib/transforms.py:293-320, and the project's own pointwise transform) -------------------------------
+def _bessel_i_scaled(n, t):
+    """e^-t I_n(t), fp64, from the ascending series sum_k (t / 2)^(2 k + n) / (k! (k + n)!) (all terms positive: no cancellation)."""
+    h = 0.5 * float(t)
+    term = 1.0
+    for j in range(1, n + 1):
+        term *= h / j
+    total, k = 0.0, 0
+    while True:
+        total += term
+        k += 1
+        term *= h * h / (k * (k + n))
+        if term <= total * 1e-18:
+            return np.exp(-float(t)) * total
+
+
+def discrete_gaussian_taps(variance, maximum_kernel_width, maximum_error):
+    """ITK's GaussianOperator (what sitk.DiscreteGaussian convolves with per axis, useImageSpacing off): c_i = e^-t I_i(t), t = variance.
+    c_0 and c_1 always; terms i >= 2 are appended while the running sum c_0 + 2 sum c_i is below 1 - maximum_error, stopping when a term
+    falls below sum * eps or the number of coefficients exceeds maximum_kernel_width; normalised by the sum and mirrored.  fp64 vector of
+    odd length.  The reference's defaults (0.5, 1, 0.9) give the 3 taps [0.163, 0.673, 0.163]; variance 0 gives [0, 1, 0]."""
+    t = float(variance)
+    if t < 0:
+        raise ValueError('variance must be >= 0')
+    cap = 1.0 - float(maximum_error)
+    coeff = [_bessel_i_scaled(0, t), _bessel_i_scaled(1, t)]
+    total = coeff[0] + 2.0 * coeff[1]
+    i = 2
+    while total < cap:
+        coeff.append(_bessel_i_scaled(i, t))
+        total += 2.0 * coeff[i]
+        if coeff[i] < total * np.finfo(np.float64).eps:
+            break
+        if len(coeff) > maximum_kernel_width:
+            break
+        i += 1
+    c = np.asarray(coeff, dtype=np.float64) / total
+    return np.concatenate([c[:0:-1], c])
+
+
+def _draw_coins(ratio, n):
+    """One coin np.random.rand(1)[0] < ratio per sample, sample after sample."""
+    return [bool(np.random.rand(1)[0] < ratio) for _ in range(n)]
+
+
+class GaussianBlur(object):
+    """lib/transforms.py:293-306 on the device: sitk.DiscreteGaussian(img, variance, maximumKernelWidth, maximumError, useImageSpacing=False)
+    of the image; the segmentation is never touched.  Tensors as RandomRigidTransform (single sample or batch); per sample one coin against
+    `ratio`; samples whose coin fails are copied unchanged in the same launch, and when every coin fails the sample is returned untouched
+    with no device call.  variance: one number, or (x, y, z)."""
+
+    def __init__(self, variance=0.5, maximumKernelWidth=1, maximumError=0.9, ratio=1.0):
+        self.variance = variance
+        self.maximumKernelWidth = maximumKernelWidth
+        self.maximumError = maximumError
+        self.ratio = ratio
+
+    def taps(self):
+        var = self.variance if np.ndim(self.variance) else [self.variance] * 3
+        return [discrete_gaussian_taps(v, self.maximumKernelWidth, self.maximumError) for v in var]
+
+    def draw(self, n):
+        return _draw_coins(self.ratio, n)
+
+    def __call__(self, sample):
+        imgs, _, single = _as_batch(sample)
+        coins = self.draw(imgs.shape[0])
+        if not any(coins):
+            return sample
+        return _store(sample, ops.gaussian_blur(imgs, self.taps(), apply=coins), None, single)
+
+
+class BilateralFilter(object):
+    """lib/transforms.py:308-320 on the device: sitk.Bilateral(img, domainSigma, rangeSigma, numberOfRangeGaussianSamples) of the image
+    (ops.bilateral_filter states the definition), with the spacing sample.get('spacing', (1, 1, 1)) as (x, y, z).  Coins, batching and the
+    untouched segmentation as GaussianBlur."""
+
+    def __init__(self, domainSigma=0.5, rangeSigma=0.06, numberOfRangeGaussianSamples=50, ratio=1.0):
+        self.domainSigma = domainSigma
+        self.rangeSigma = rangeSigma
+        self.numberOfRangeGaussianSamples = numberOfRangeGaussianSamples
+        self.ratio = ratio
+
+    def draw(self, n):
+        return _draw_coins(self.ratio, n)
+
+    def __call__(self, sample):
+        imgs, _, single = _as_batch(sample)
+        coins = self.draw(imgs.shape[0])
+        if not any(coins):
+            return sample
+        spacing = tuple(float(s) for s in sample.get('spacing', (1.0, 1.0, 1.0)))
+        out = ops.bilateral_filter(imgs, self.domainSigma, self.rangeSigma, self.numberOfRangeGaussianSamples, spacing, apply=coins)
+        return _store(sample, out, None, single)
+
+
+def _uniform(rng):
+    return float(np.random.uniform(rng[0], rng[1]))
+
+
+class RandomIntensityTransform(object):
+    """The project's own intensity augmentation (the reference has none) for scanner-to-scanner variation, one fused device pass
+    (ops.intensity_augment): smooth multiplicative bias field exp(b), b a B-spline of `bias_order` over bias_mesh + bias_order control
+    points per axis; gamma clamp01(x)^g (inverted, 1 - (1 - x)^g, with probability gamma_invert_prob); gain x + offset; additive Gaussian
+    noise; clamp to [0, 1].  A range of None turns its stage off.  Per sample, in this order: the coin against `ratio`; gamma uniform in
+    its range; the invert coin (drawn only when gamma_invert_prob > 0); gain; offset; the noise sigma, each uniform in its range; the
+    bias coefficients as ONE vector normal(0, bias_scale / 2, gx gy gz); one 32-bit noise seed.  Only enabled stages draw, and a failed
+    coin draws nothing more.  The segmentation is never touched; when every coin fails the sample is returned untouched with no device
+    call."""
+
+    def __init__(self, ratio=1.0, gamma=(0.7, 1.5), gamma_invert_prob=0.0, gain=(0.75, 1.25), offset=None, noise_std=(0.0, 0.05),
+                 bias_scale=None, bias_mesh=(2, 2, 2), bias_order=2, clamp=True):
+        if bias_order not in (1, 2, 3):
+            raise ValueError('bias_order %r: orders 1, 2 and 3 are supported' % (bias_order,))
+        self.ratio = ratio
+        self.gamma = gamma
+        self.gamma_invert_prob = gamma_invert_prob
+        self.gain = gain
+        self.offset = offset
+        self.noise_std = noise_std
+        self.bias_scale = bias_scale
+        self.bias_mesh = bias_mesh
+        self.bias_order = bias_order
+        self.clamp = clamp
+
+    def _draw_one(self, grid):
+        if not np.random.rand(1)[0] < self.ratio:
+            return None
+        p = {'clamp': bool(self.clamp)}
+        if self.gamma is not None:
+            p['gamma'] = _uniform(self.gamma)
+            if self.gamma_invert_prob > 0:
+                p['invert'] = bool(np.random.rand(1)[0] < self.gamma_invert_prob)
+        if self.gain is not None:
+            p['gain'] = _uniform(self.gain)
+        if self.offset is not None:
+            p['offset'] = _uniform(self.offset)
+        if self.noise_std is not None:
+            p['noise_std'] = _uniform(self.noise_std)
+        if self.bias_scale is not None:
+            gx, gy, gz = grid
+            p['bias_coef'] = np.random.normal(0, self.bias_scale / 2, gx * gy * gz).reshape(gz, gy, gx)
+        if self.noise_std is not None:
+            p['seed'] = int(np.random.randint(0, 2 ** 32, dtype=np.int64))
+        return p
+
+    def draw(self, n, size):
+        """The draws of n samples of `size` (x, y, z) voxels, sample after sample: a list of parameter dicts (ops.intensity_params, plus
+        'bias_coef' gz x gy x gx when the bias field is on) or None."""
+        grid = bspline_grid(size, self.bias_mesh, self.bias_order) if self.bias_scale is not None else None
+        return [self._draw_one(grid) for _ in range(n)]
+
+    def __call__(self, sample):
+        imgs, _, single = _as_batch(sample)
+        D, H, W = (int(s) for s in imgs.shape[-3:])
+        params = self.draw(imgs.shape[0], (W, H, D))
+        if all(p is None for p in params):
+            return sample
+        coef = None
+        if self.bias_scale is not None:
+            gx, gy, gz = bspline_grid((W, H, D), self.bias_mesh, self.bias_order)
+            coef = np.zeros((len(params), gz, gy, gx))
+            for k, p in enumerate(params):
+                if p is not None:
+                    coef[k] = p['bias_coef']
+        return _store(sample, ops.intensity_augment(imgs, params, coef, self.bias_order), None, single)
+
+
+AUGMENTATIONS = {'rigid': RandomRigidTransform, 'bspline': RandomBSplineTransform, 'blur': GaussianBlur, 'bilateral': BilateralFilter,
+                 'intensity': RandomIntensityTransform}
 
 
 def make_augmentation(spec):
-    """SegmentationExperiment's config['augment']: [[name, kwargs], ...] with name 'rigid' or 'bspline' -> the transforms, in order."""
+    """SegmentationExperiment's config['augment']: [[name, kwargs], ...] with name 'rigid', 'bspline', 'blur', 'bilateral' or 'intensity'
+    -> the transforms, in order."""
     out = []
     for name, kwargs in (spec or []):
         if name not in AUGMENTATIONS:

@@ -2641,6 +2641,176 @@ def spatial_resample(image, labels, affine, coef=None, order=0, interpolator='li
 
 
 # ------------------------------------------------------------------------------------------------
+# intensity augmentation (csrc/intensity.hip): Gaussian blur, bilateral filter, fused pointwise pass.  No autograd: these run on inputs.
+# ------------------------------------------------------------------------------------------------
+BLUR_MAX_RADIUS = 16                # DA_BLUR_MAX_RADIUS (include/deepatlas_hip.h)
+BLUR_BLOCK = 256                    # voxels one workgroup of a blur line pass takes per loop trip (consecutive along W)
+BILATERAL_TILE = (8, 8, 32)         # (td, th, tw) = DA_BILATERAL_TILE_D / _H / _W: the output tile one workgroup filters from LDS
+BILATERAL_MAX_RADIUS = 4            # DA_BILATERAL_MAX_RADIUS
+BILATERAL_MAX_SAMPLES = 1024        # DA_BILATERAL_MAX_SAMPLES
+INTENSITY_FLAGS = {'bias': 1, 'gamma': 2, 'invert': 4, 'linear': 8, 'noise': 16, 'clamp': 32}      # DA_INTENSITY_*
+INTENSITY_STREAMS = (2, 3)          # DA_INTENSITY_STREAM_U1 / _U2: the hash streams of the two uniforms
+_INTENSITY_PARAM_STRIDE = 8
+
+
+def _image5(img):
+    nat.require_cuda(img)
+    if img.dim() not in (4, 5) or img.dtype != torch.float32:
+        raise ValueError('image must be C x D x H x W or N x C x D x H x W float32')
+    single = img.dim() == 4
+    return (img.unsqueeze(0) if single else img).contiguous(), single
+
+
+_CONST_CACHE = {}
+
+
+def _const_tensor(arr, device):
+    """Device copy of a small read-only host array (taps, tables, flags), kept by content: a transform that repeats its arguments uploads them
+    once instead of once per call (a pageable upload makes the host wait for the stream).  The first 64 distinct arrays are kept for the life
+    of the process and never released (a kernel on another stream may still be reading one); beyond that an array is uploaded per call."""
+    key = (arr.dtype.str, arr.shape, arr.tobytes(), device.type, device.index)
+    t = _CONST_CACHE.get(key)
+    if t is None:
+        t = torch.from_numpy(arr.copy()).to(device)
+        if len(_CONST_CACHE) < 64:
+            _CONST_CACHE[key] = t
+    return t
+
+
+def _apply_flags(apply, N, device):
+    import numpy as np
+    flags = np.ones(N, dtype=np.int32) if apply is None else np.asarray(apply).astype(bool).astype(np.int32).reshape(-1)
+    if flags.shape[0] != N:
+        raise ValueError('apply must hold one flag per sample (%d), got %d' % (N, flags.shape[0]))
+    return _const_tensor(flags, device)
+
+
+def gaussian_blur(img, taps, apply=None):
+    """sitk.DiscreteGaussian(img, variance, maximumKernelWidth, maximumError, useImageSpacing=False) (lib/transforms.py:293-306) given its
+    taps (lib.transforms.discrete_gaussian_taps): one odd-length vector for all three axes, or three vectors (x, y, z) = (W, H, D) (shorter
+    ones are zero-padded to the longest).  Boundary ZeroFluxNeumann (indices clamped).  img C x D x H x W or N x C x D x H x W float32 on
+    the GPU; apply: per-sample flags, a sample whose flag is false is copied bit for bit.  Returns a fresh tensor."""
+    import numpy as np
+    x, single = _image5(img)
+    N, C, D, H, W = (int(s) for s in x.shape)
+    vecs = [np.asarray(t, dtype=np.float64).reshape(-1) for t in (taps if np.ndim(taps[0]) else [taps] * 3)]
+    if len(vecs) != 3 or any(len(v) % 2 == 0 for v in vecs):
+        raise ValueError('taps: one odd-length vector, or three (x, y, z)')
+    R = max(len(v) for v in vecs) // 2
+    tp = np.zeros((3, 2 * R + 1), dtype=np.float32)
+    for k, v in enumerate(vecs):
+        r = len(v) // 2
+        tp[k, R - r:R + r + 1] = v
+    out, tmp = torch.empty_like(x), torch.empty_like(x)
+    tpt, flags = _const_tensor(tp, x.device), _apply_flags(apply, N, x.device)
+    with torch.cuda.device(x.device):
+        call('da_gauss_blur3d', ptr(x), ptr(out), ptr(tmp), ptr(tpt), R, ptr(flags), N, C, D, H, W, stream())
+    return out[0] if single else out
+
+
+def bilateral_tables(domain_sigma, range_sigma, n_samples=50, spacing=(1.0, 1.0, 1.0)):
+    """Host side of ITK's BilateralImageFilter, fp64: radii (x, y, z) = ceil(2.5 sigma_d / spacing), the domain weights
+    [2 rz + 1][2 ry + 1][2 rx + 1] exp(-sum (o_k spacing_k)^2 / (2 sigma_d^2)), the cutoff 4 sigma_r, the table of n_samples entries
+    exp(-0.5 (i cutoff / n_samples)^2 / sigma_r^2) and the index scale n_samples / cutoff."""
+    import numpy as np
+    sp = np.asarray(spacing, dtype=np.float64)
+    if not (domain_sigma > 0 and range_sigma > 0 and n_samples >= 1 and (sp > 0).all()):
+        raise ValueError('bilateral filter: sigmas, spacing and the number of range samples must be positive')
+    r = np.ceil(2.5 * float(domain_sigma) / sp).astype(int)
+    ox, oy, oz = (np.arange(-r[k], r[k] + 1) * sp[k] for k in range(3))
+    wd = np.exp(-(oz[:, None, None] ** 2 + oy[None, :, None] ** 2 + ox[None, None, :] ** 2) / (2.0 * float(domain_sigma) ** 2))
+    cutoff = 4.0 * float(range_sigma)
+    table = np.exp(-0.5 * (np.arange(int(n_samples)) * cutoff / int(n_samples)) ** 2 / float(range_sigma) ** 2)
+    return tuple(int(v) for v in r), wd, cutoff, table, int(n_samples) / cutoff
+
+
+def bilateral_filter(img, domain_sigma, range_sigma, n_samples=50, spacing=(1, 1, 1), apply=None):
+    """sitk.Bilateral(img, domainSigma, rangeSigma, numberOfRangeGaussianSamples) (lib/transforms.py:308-320) as include/deepatlas_hip.h
+    states it; spacing (x, y, z).  Radii beyond BILATERAL_MAX_RADIUS or more than BILATERAL_MAX_SAMPLES range samples raise NativeError
+    (DA_ERR_UNSUPPORTED).  Tensors and `apply` as gaussian_blur.  Returns a fresh tensor."""
+    import numpy as np
+    x, single = _image5(img)
+    N, C, D, H, W = (int(s) for s in x.shape)
+    (rx, ry, rz), wd, cutoff, table, scale = bilateral_tables(domain_sigma, range_sigma, n_samples, spacing)
+    dev = x.device
+    wdt = _const_tensor(np.ascontiguousarray(wd, dtype=np.float32), dev)
+    tbt = _const_tensor(np.ascontiguousarray(table, dtype=np.float32), dev)
+    flags = _apply_flags(apply, N, dev)
+    out = torch.empty_like(x)
+    with torch.cuda.device(dev):
+        call('da_bilateral3d', ptr(x), ptr(out), ptr(wdt), ptr(tbt), rx, ry, rz, int(n_samples), float(np.float32(cutoff)), float(np.float32(scale)),
+             ptr(flags), N, C, D, H, W, stream())
+    return out[0] if single else out
+
+
+def intensity_params(params, N, seed=0, bias=False):
+    """Per-sample parameter dicts -> the N x 8 uint32 table of da_intensity_augment.  A dict may hold 'gamma' (with 'invert'), 'gain' and /
+    or 'offset', 'noise_std', 'clamp', 'bias' (default: on when a field is given) and 'seed' (default: `seed`); a stage whose key is
+    absent or None is off, and a None entry leaves the whole sample untouched."""
+    import numpy as np
+    if isinstance(params, dict) or params is None:
+        params = [params] * N
+    if len(params) != N:
+        raise ValueError('params must hold one entry per sample (%d), got %d' % (N, len(params)))
+    tab = np.zeros((N, _INTENSITY_PARAM_STRIDE), dtype=np.uint32)
+    f32 = tab.view(np.float32)
+    for n, p in enumerate(params):
+        if p is None:
+            continue
+        flags = 0
+        f32[n, 1], f32[n, 2] = 1.0, 1.0
+        if bias and p.get('bias', True):
+            flags |= INTENSITY_FLAGS['bias']
+        if p.get('gamma') is not None:
+            if not p['gamma'] > 0:
+                raise ValueError('gamma must be positive')
+            flags |= INTENSITY_FLAGS['gamma'] | (INTENSITY_FLAGS['invert'] if p.get('invert') else 0)
+            f32[n, 1] = p['gamma']
+        if p.get('gain') is not None or p.get('offset') is not None:
+            flags |= INTENSITY_FLAGS['linear']
+            f32[n, 2] = 1.0 if p.get('gain') is None else p['gain']
+            f32[n, 3] = 0.0 if p.get('offset') is None else p['offset']
+        if p.get('noise_std') is not None:
+            flags |= INTENSITY_FLAGS['noise']
+            f32[n, 4] = p['noise_std']
+        if p.get('clamp'):
+            flags |= INTENSITY_FLAGS['clamp']
+        tab[n, 0] = flags
+        tab[n, 5] = int(p.get('seed', seed)) & 0xFFFFFFFF
+    return tab
+
+
+def intensity_augment(img, params, bias_coef=None, bias_order=2, seed=0, sample0=0):
+    """The fused pointwise intensity pass (one launch, one read and one write of the image): per sample, in this order and each only when
+    asked for, bias field x exp(b) (b a scalar B-spline of bias_order 1..3 over bias_coef, a host array N x gz x gy x gx on the control grid
+    of lib.transforms.bspline_grid), gamma (optionally inverted), gain / offset, additive Gaussian noise from the counter hash keyed by
+    (seed, sample0 + n, element index, stream), clamp to [0, 1].  params: one dict per sample (intensity_params), or one dict for all.
+    img C x D x H x W or N x C x D x H x W float32 on the GPU.  Returns a fresh tensor; with every stage off, a bit-exact copy."""
+    import numpy as np
+    x, single = _image5(img)
+    N, C, D, H, W = (int(s) for s in x.shape)
+    dev = x.device
+    if bias_coef is not None:
+        if bias_order not in (1, 2, 3):
+            raise ValueError('bias_order %r: orders 1, 2 and 3 are supported' % (bias_order,))
+        cf = np.ascontiguousarray(bias_coef, dtype=np.float32)
+        if cf.ndim == 3 and single:
+            cf = cf[None]
+        if cf.ndim != 4 or cf.shape[0] != N:
+            raise ValueError('bias_coef must be N x gz x gy x gx')
+        gz, gy, gx = (int(s) for s in cf.shape[1:])
+        cft, order = torch.from_numpy(cf).to(dev), int(bias_order)
+    else:
+        gz = gy = gx = order = 0
+        cft = None
+    tab = torch.from_numpy(intensity_params(params, N, seed, bias=cft is not None).view(np.int32)).to(dev)
+    out = torch.empty_like(x)
+    with torch.cuda.device(dev):
+        call('da_intensity_augment', ptr(x), ptr(out), ptr(tab), ptr(cft), order, gx, gy, gz, int(sample0), N, C, D, H, W, stream())
+    return out[0] if single else out
+
+
+# ------------------------------------------------------------------------------------------------
 # registration evaluation (csrc/regeval.hip): hard-label warp + overlap counts, Jacobian determinant.  No autograd.
 # ------------------------------------------------------------------------------------------------
 def _eval_disp(disp):

@@ -494,6 +494,53 @@ int da_spatial_resample(const float* img, float* img_out, int C, int interp,
                         const float* affine, const float* coef, int order, int gx, int gy, int gz,
                         int N, int D, int H, int W, void* stream);
 
+/* ---- intensity augmentation (lib/transforms.py:293-320: GaussianBlur, BilateralFilter; the fused pointwise pass is the project's own) ----
+ * img / out [N][C][D][H][W] fp32, planar, distinct buffers.  `apply` [N] int32 on the device: a sample whose flag is 0 is copied through
+ * bit for bit in the same launch.  No atomics; bit-identical from run to run.  DA_ERR_UNSUPPORTED for volumes of >= 2^31 voxels per
+ * sample and for N C > 65535.
+ *
+ * da_gauss_blur3d (lib/transforms.py:293-306, sitk.DiscreteGaussian with useImageSpacing off): separable, taps [3][2 radius + 1] fp32 on the
+ * device, axis order (x, y, z) = (W, H, D), computed on the host in fp64 (ITK's GaussianOperator) and rounded once.  Boundary
+ * ZeroFluxNeumann: out[i] = sum_k taps[k] in[clamp(i + k - radius)], k ascending, per axis W then H then D.  `tmp`: scratch of the size
+ * of img.  radius <= DA_BLUR_MAX_RADIUS; extents below the radius (down to 1) are fine.
+ *
+ * da_bilateral3d (lib/transforms.py:308-320, sitk.Bilateral = ITK's BilateralImageFilter): domain_w [2 rz + 1][2 ry + 1][2 rx + 1] fp32 =
+ * exp(-sum_k (o_k spacing_k)^2 / (2 sigma_d^2)), table [n_samples] fp32 = exp(-0.5 (i cutoff / n_samples)^2 / sigma_r^2), both computed on
+ * the host in fp64; cutoff = 4 sigma_r, scale = n_samples / cutoff (fp64 on the host, one fp32).  For centre a and neighbour b (indices
+ * clamped to the volume), delta = |b - a|: the tap takes part only if delta < cutoff, with range weight table[floorf(delta * scale)];
+ * out = sum w_d w_r b / sum w_d w_r (evaluated as a + sum w (b - a) / sum w).  A NaN neighbour fails the comparison and is skipped; a NaN
+ * centre skips every tap and yields NaN for that voxel only.  Radii <= DA_BILATERAL_MAX_RADIUS and n_samples <= DA_BILATERAL_MAX_SAMPLES,
+ * else DA_ERR_UNSUPPORTED.  One workgroup per DA_BILATERAL_TILE_D x _H x _W output tile, tile + halo staged in LDS.
+ *
+ * da_intensity_augment: one pointwise pass.  params [N][DA_INTENSITY_PARAM_STRIDE] 32-bit words on the device: [0] flag word (uint32),
+ * [1] gamma, [2] gain, [3] offset, [4] sigma (fp32), [5] seed (uint32).  Stages in this order, each only if its bit is set (all off: an
+ * exact copy): BIAS x *= exp(b(i)), b a scalar B-spline of `order` 1..3 over bias_coef [N][gz][gy][gx] (the support rule of
+ * da_spatial_resample; staged in LDS, gx gy gz <= DA_AUG_MAX_GRID_POINTS; order 0: no field, the bit is ignored); GAMMA x =
+ * clamp01(x)^gamma, with INVERT 1 - (1 - clamp01(x))^gamma; LINEAR x = gain x + offset; NOISE x += sigma n, n = sqrt(-2 ln u1) cos(2 pi u2),
+ * u = ((bits >> 8) + 0.5) 2^-24 from the counter hash keyed by (seed, (sample0 + n) C D H W + element index within the sample, stream
+ * DA_INTENSITY_STREAM_U1 / _U2), accurate logf / cosf; CLAMP to [0, 1]. */
+#define DA_BLUR_MAX_RADIUS 16
+#define DA_BILATERAL_MAX_RADIUS 4
+#define DA_BILATERAL_MAX_SAMPLES 1024
+#define DA_BILATERAL_TILE_D 8
+#define DA_BILATERAL_TILE_H 8
+#define DA_BILATERAL_TILE_W 32
+#define DA_INTENSITY_PARAM_STRIDE 8
+#define DA_INTENSITY_BIAS 1
+#define DA_INTENSITY_GAMMA 2
+#define DA_INTENSITY_INVERT 4
+#define DA_INTENSITY_LINEAR 8
+#define DA_INTENSITY_NOISE 16
+#define DA_INTENSITY_CLAMP 32
+#define DA_INTENSITY_STREAM_U1 2u
+#define DA_INTENSITY_STREAM_U2 3u
+int da_gauss_blur3d(const float* img, float* out, float* tmp, const float* taps, int radius, const int* apply,
+                    int N, int C, int D, int H, int W, void* stream);
+int da_bilateral3d(const float* img, float* out, const float* domain_w, const float* table, int rx, int ry, int rz, int n_samples,
+                   float cutoff, float scale, const int* apply, int N, int C, int D, int H, int W, void* stream);
+int da_intensity_augment(const float* img, float* out, const float* params, const float* bias_coef, int order, int gx, int gy, int gz,
+                         int sample0, int N, int C, int D, int H, int W, void* stream);
+
 /* ---- LNCC similarity (lib/loss.py:589-617 VoxelMorphLNCC = registry 'lncc', and :512-586 LNCCLoss) -----
  * I, J: [N][D][H][W] fp32 (single channel); all-ones F^3 window with dilation `dil` and stride `stride` (1, 1 for VoxelMorphLNCC),
  * valid padding; loss = 1 - mean(cross^2 / (Ivar Jvar + eps)).  Output extent per axis: (L - dil (F-1) - 1) / stride + 1.

@@ -49,6 +49,23 @@ def build_config(args):
         augment.append(['rigid', {'rotation_angles': list(aug_rigid[:3]), 'translation': list(aug_rigid[3:])}])
     if aug_bspline is not None:
         augment.append(['bspline', {'deform_scale': aug_bspline}])
+    # ... and the intensity half (lib/transforms.py:293-320 and RandomIntensityTransform), after the spatial transforms
+    aug_blur = config.pop('aug_blur', None)
+    aug_bilateral = config.pop('aug_bilateral', None)
+    aug_intensity = config.pop('aug_intensity', False)
+    aug_bias = config.pop('aug_bias', None)
+    aug_noise = config.pop('aug_noise', None)
+    if aug_blur is not None:
+        augment.append(['blur', {'variance': aug_blur, 'maximumKernelWidth': 32, 'maximumError': 0.01}])
+    if aug_bilateral:
+        augment.append(['bilateral', {'domainSigma': aug_bilateral[0], 'rangeSigma': aug_bilateral[1]}])
+    if aug_intensity or aug_bias is not None or aug_noise is not None:
+        kwargs = {}
+        if aug_bias is not None:
+            kwargs['bias_scale'] = aug_bias
+        if aug_noise is not None:
+            kwargs['noise_std'] = [0.0, aug_noise]
+        augment.append(['intensity', kwargs])
     if augment:
         config['augment'] = augment
     # opt-in clean-up of the validation / test prediction (lib/evalMetrics.py parse_postprocess); absent = the reference's raw argmax alone
@@ -97,6 +114,16 @@ def main(argv=None):
                         help='augment training batches with RandomRigidTransform: rotation_angles (degrees) and translation (voxels), (x, y, z)')
     parser.add_argument('--aug-bspline', type=float, default=None, metavar='DEFORM_SCALE',
                         help='augment training batches with RandomBSplineTransform(deform_scale=DEFORM_SCALE), after the rigid one')
+    parser.add_argument('--aug-blur', type=float, default=None, metavar='VARIANCE',
+                        help='augment training batches with GaussianBlur(variance=VARIANCE, maximumKernelWidth=32, maximumError=0.01), after the spatial transforms')
+    parser.add_argument('--aug-bilateral', nargs=2, type=float, default=None, metavar=('DOMAIN_SIGMA', 'RANGE_SIGMA'),
+                        help='augment training batches with BilateralFilter(domainSigma=DOMAIN_SIGMA, rangeSigma=RANGE_SIGMA), after the blur')
+    parser.add_argument('--aug-intensity', action='store_true',
+                        help='augment training batches with RandomIntensityTransform at its defaults (gamma, gain, noise, clamp), last')
+    parser.add_argument('--aug-bias', type=float, default=None, metavar='SCALE',
+                        help='bias_scale of --aug-intensity: a smooth multiplicative bias field exp(b), b ~ normal(0, SCALE / 2) on the control grid; implies --aug-intensity')
+    parser.add_argument('--aug-noise', type=float, default=None, metavar='STD_MAX',
+                        help='upper end of the noise_std range of --aug-intensity (default 0.05); implies --aug-intensity')
     parser.add_argument('--postprocess', default=None, choices=['largest-cc', 'min-size'],
                         help="additionally score the validation / test prediction after a connected-component clean-up on the device: "
                              "'largest-cc' keeps the largest component of every class, 'min-size' drops components below --cc-min-size voxels")
