@@ -171,7 +171,14 @@ SIGNATURES = {
     'da_partition_tiles': (I, [P, P, I, I, I, I, P, P, P]),
     'da_assemble_tiles': (I, [P, P, I, I, I, I, P, P, I, P]),
     'da_synth_volume': (I, [P, P, I, I, I, I, I, I, F, ctypes.c_uint, I, P]),
-    'da_spatial_resample': (I, [P, P, I, I, P, P, I, P, P, I, I, I, I, I, I, I, I, P]),
+    'da_resample_axes': (I, [P, I, P, I, I, I, I, I, I, I, I, P, DBL, P]),
+    'da_volume_moments_ws_bytes': (SZ, [LL]),
+    'da_volume_moments': (I, [P, I, LL, P, P, SZ, P]),
+    'da_volume_percentiles_ws_bytes': (SZ, [LL]),
+    'da_volume_percentiles': (I, [P, I, LL, POINTER(c_double), I, P, P, SZ, P]),
+    'da_affine_intensity_to_f32': (I, [P, I, P, LL, F, F, I, P]),
+    'da_label_lut': (I, [P, I, P, LL, P, I, P]),
+    'da_spatial_resample':(I, [P, P, I, I, P, P, I, P, P, I, I, I, I, I, I, I, I, P]),
     'da_gauss_blur3d': (I, [P, P, P, P, I, P, I, I, I, I, I, P]),
     'da_bilateral3d': (I, [P, P, P, P, I, I, I, I, F, F, P, I, I, I, I, I, P]),
     'da_intensity_augment': (I, [P, P, P, P, I, I, I, I, I, I, I, I, I, I, P]),

@@ -3,12 +3,15 @@ SURVEY.md row f4 -- SitkToTensor's clamp + cast (:71-92), CropTensor (:124-158),
 and both assemble modes (:508-649), the two random spatial augmentations RandomRigidTransform (:202-259) and
 RandomBSplineTransform (:161-199) as device resamples, and the intensity half: the reference's two image filters GaussianBlur
 (:293-306) and BilateralFilter (:308-320) and the project's own RandomIntensityTransform (bias field, gamma, gain / offset, noise) as
-device kernels.  Only the SimpleITK read / resample-to-voxel-size / crop transforms (Resample to a voxel size, Normalization,
-LeftToRight, RandomCrop, BalancedRandomCrop, SegmentationLabelFilter) are host I/O and stay out of scope; these classes take numpy
-arrays (what sitk.GetArrayFromImage returns) or tensors and hand back DEVICE tensors, so a loader thread only uploads the raw volume
-once.
+device kernels.  The preprocessing transforms the reference runs through SimpleITK are device kernels too (csrc/preprocess.hip): Resample to
+a voxel size (:9-57), Normalization (:59-68), LeftToRight (:269-284), SegmentationLabelFilter (:692-706), IdentityTransform, and the
+project's own PercentileRescale; they act on the raw arrays lib/nifti.py reads.  Every class takes numpy arrays (what
+sitk.GetArrayFromImage returns) or tensors and hands back DEVICE tensors, so a loader thread only uploads the raw volume once.
+Out of scope: RandomCrop / BalancedRandomCrop (patch sampling, the natural next step beside Partition), reorientation by the affine, oblique
+resampling, anti-aliasing on down-sampling and B-spline interpolation.
 """
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -565,4 +568,159 @@ def make_augmentation(spec):
         if name not in AUGMENTATIONS:
             raise ValueError("augmentation %r: one of %s" % (name, sorted(AUGMENTATIONS)))
         out.append(AUGMENTATIONS[name](**dict(kwargs or {})))
+    return out
+
+
+# ---- preprocessing of raw volumes (lib/transforms.py:9-68, :262-284, :692-706) on csrc/preprocess.hip ------------------------------
+# These act on the sample dict before or after SitkToTensor: image D x H x W or C x D x H x W, numpy or tensor, in the file's own dtype;
+# sample['spacing'] is (x, y, z) = (W, H, D) axis, (1, 1, 1) when absent.
+
+class Compose(object):
+    """torchvision.transforms.Compose's contract (the reference composes its sample transforms with it): the transforms, in order."""
+
+    def __init__(self, transforms):
+        self.transforms = [t for t in transforms if t is not None]
+
+    def __call__(self, sample):
+        for t in self.transforms:
+            sample = t(sample)
+        return sample
+
+
+def _to_kernel_volume(a):
+    """numpy / tensor -> contiguous device tensor in a dtype the preprocessing kernels read (float32, float64, int16, uint8, int32); other
+    dtypes are converted on upload, as SitkToTensor does."""
+    t = _to_device_array(a)
+    if t.dtype in ops.PREPROCESS_DTYPE_CODE:
+        return t
+    if t.dtype.is_floating_point:
+        return t.to(torch.float32)
+    if t.dtype in (torch.int8, torch.bool):
+        return t.to(torch.int16 if t.dtype == torch.int8 else torch.uint8)
+    return t.to(torch.int32)
+
+
+class IdentityTransform(object):
+    """lib/transforms.py:262-266."""
+
+    def __call__(self, sample):
+        return sample
+
+
+class Resample(object):
+    """lib/transforms.py:9-57 on the device: resample image and segmentation to `voxel_size` (one number, or (x, y, z)).  Per axis
+    new_size = int(math.ceil(old_spacing * old_size / voxel_size)), output index o reads input index o * voxel_size / old_spacing (same origin and
+    direction), by the table rule of ops.resample_axis_table; outside voxels get 0; sample['spacing'] is updated.  interpolator 'nearest' is
+    the default for image and segmentation because that is what the reference executes (it passes interpolator 1, SimpleITK's nearest
+    neighbour, although its docstring says linear); 'linear' applies to the image only (float32 out), the segmentation is always nearest.
+    No anti-aliasing when down-sampling."""
+
+    def __init__(self, voxel_size, interpolator='nearest'):
+        if isinstance(voxel_size, (int, float)):
+            voxel_size = (voxel_size,) * 3
+        if len(voxel_size) != 3 or not all(float(v) > 0 and math.isfinite(float(v)) for v in voxel_size):
+            raise ValueError('voxel_size: one positive number, or three (x, y, z); got %r' % (voxel_size,))
+        if interpolator not in ops.RESAMPLE_INTERPOLATORS:
+            raise ValueError("interpolator %r: 'nearest' or 'linear'" % (interpolator,))
+        self.voxel_size = tuple(float(v) for v in voxel_size)
+        self.interpolator = interpolator
+
+    @staticmethod
+    def new_size(old_size, old_spacing, voxel_size):
+        """(x, y, z) sizes: the reference's :35-38."""
+        return tuple(int(math.ceil(old_spacing[i] * old_size[i] / voxel_size[i])) for i in range(3))
+
+    def __call__(self, sample):
+        img = _to_kernel_volume(sample['image'])
+        D, H, W = (int(s) for s in img.shape[-3:])
+        spacing = tuple(float(s) for s in (sample.get('spacing') or (1.0, 1.0, 1.0)))
+        nx, ny, nz = self.new_size((W, H, D), spacing, self.voxel_size)
+        scale = tuple(self.voxel_size[k] / spacing[k] for k in (2, 1, 0))                     # (D, H, W) order
+        sample['image'] = ops.resample_volume(img, (nz, ny, nx), scale, (0.0, 0.0, 0.0), self.interpolator, 0)
+        if sample.get('segmentation') is not None:
+            seg = _to_kernel_volume(sample['segmentation'])
+            sample['segmentation'] = ops.resample_volume(seg, (nz, ny, nx), scale, (0.0, 0.0, 0.0), 'nearest', 0)
+        sample['spacing'] = self.voxel_size
+        return sample
+
+
+class Normalization(object):
+    """lib/transforms.py:59-68 on the device: ITK's NormalizeImageFilter, (x - mean) / sigma with the unbiased sigma over the finite voxels, as
+    float32 (mean and sigma from two passes in double, rounded to float32 for the pointwise pass).  A constant volume gives zeros."""
+
+    def __call__(self, sample):
+        img = _to_kernel_volume(sample['image'])
+        _, mean, var = ops.volume_moments(img)
+        sample['image'] = ops.affine_intensity(img, mean, math.sqrt(var), clamp=False)
+        return sample
+
+
+class PercentileRescale(object):
+    """The project's own transform (the reference's datasets were rescaled offline): (x - P_lo) / (P_hi - P_lo) as float32 with the exact `lo`
+    / `hi` percentiles of the volume (numpy's linear rule), clamped to [0, 1] unless clamp=False -- the step raw MR intensities need before
+    SitkToTensor's clamp to [0, 1] means anything.  P_hi == P_lo gives zeros."""
+
+    def __init__(self, lo=0.5, hi=99.5, clamp=True):
+        if not 0.0 <= float(lo) < float(hi) <= 100.0:
+            raise ValueError('percentiles need 0 <= lo < hi <= 100, got %r and %r' % (lo, hi))
+        self.lo, self.hi, self.clamp = float(lo), float(hi), bool(clamp)
+
+    def __call__(self, sample):
+        img = _to_kernel_volume(sample['image'])
+        p_lo, p_hi = ops.volume_percentiles(img, (self.lo, self.hi))
+        sample['image'] = ops.affine_intensity(img, p_lo, p_hi - p_lo, clamp=self.clamp)
+        return sample
+
+
+class LeftToRight(object):
+    """lib/transforms.py:269-284 on the device: flips numpy axis 0 (z) of image and segmentation when 'LEFT' is in sample['name'] (a left knee
+    shown as a right one).  Bit-exact; anything else passes through untouched."""
+
+    @staticmethod
+    def _flip0(vol):
+        t = _to_kernel_volume(vol)
+        D, H, W = (int(s) for s in t.shape[-3:])
+        return ops.resample_volume(t, (D, H, W), (-1.0, 1.0, 1.0), (float(D - 1), 0.0, 0.0), 'nearest', 0)
+
+    def __call__(self, sample):
+        if 'LEFT' in sample['name']:
+            sample['image'] = self._flip0(sample['image'])
+            if sample.get('segmentation') is not None:
+                sample['segmentation'] = self._flip0(sample['segmentation'])
+        return sample
+
+
+class SegmentationLabelFilter(object):
+    """lib/transforms.py:692-706 on the device: every label in `ignore_labels` becomes 0, through one look-up table.  uint8 labels use a
+    256-entry table; other integer labels are taken as int32 with a 65536-entry table, and labels outside it map to 0."""
+
+    def __init__(self, ignore_labels):
+        self.ignore_labels = [int(l) for l in ignore_labels]
+
+    def __call__(self, sample):
+        if sample.get('segmentation') is not None:
+            seg = _to_kernel_volume(sample['segmentation'])
+            if seg.dtype not in (torch.uint8, torch.int32):
+                seg = seg.to(torch.int32)
+            n = 256 if seg.dtype == torch.uint8 else ops.LABEL_LUT_MAX
+            lut = np.arange(n, dtype=np.int32)
+            for l in self.ignore_labels:
+                if 0 <= l < n:
+                    lut[l] = 0
+            sample['segmentation'] = ops.label_lut(seg, lut)
+        return sample
+
+
+PREPROCESSING = {'resample': Resample, 'percentile_rescale': PercentileRescale, 'normalize': Normalization, 'left_to_right': LeftToRight,
+                 'label_filter': SegmentationLabelFilter, 'identity': IdentityTransform}
+
+
+def make_preprocess(spec):
+    """config['preprocess']: [[name, kwargs], ...] with name 'resample', 'percentile_rescale', 'normalize', 'left_to_right', 'label_filter' or
+    'identity' -> the transforms, in order (they run ahead of SitkToTensor)."""
+    out = []
+    for name, kwargs in (spec or []):
+        if name not in PREPROCESSING:
+            raise ValueError("preprocess step %r: one of %s" % (name, sorted(PREPROCESSING)))
+        out.append(PREPROCESSING[name](**dict(kwargs or {})))
     return out

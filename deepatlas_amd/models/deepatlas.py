@@ -18,6 +18,8 @@ segmented from the labelled training volumes by multi-atlas label fusion (models
 config['sim_loss'] / config['sim_settings'] / config['moving_remap']: the image similarity of the registration phase and the synthetic pairs'
 moving-image remap, as in models/registration.py; so are config['lambda_jac'] / config['jac_settings'], the Jacobian folding penalty of the
 registration phase (default 0: off).
+config['data'] other than 'synthetic' (models/nifti_data.py) trains on the NIfTI volumes of a list file; the labelled volumes are then the first
+num_labeled names of the training list.
 """
 import datetime
 import os
@@ -28,6 +30,7 @@ import torch
 from torch.utils.data import DataLoader
 
 from .base import BaseExperiment
+from . import nifti_data
 from .joint import DeepAtlasJointStep
 from .registration import (atlas_fusion_text, check_atlas_fusion, check_jac_penalty, check_sim_loss, dataset_volumes, eval_atlas_fusion,
                            eval_registration, jac_name_suffix)
@@ -70,6 +73,7 @@ class DeepAtlasExperiment(BaseExperiment):
         if pairs == 'all' and parallel.world_size() > 1:
             raise ValueError("pairs='all' needs a single process: a rank whose pair has no label skips its segmentation phase and would miss the "
                              "gradient all-reduce the other ranks enter")
+        nifti_data.refuse_synthetic_only(cfg, ('misalign', 'report_tre'))
         self.atlas_fusion, self.atlas_fusion_max = check_atlas_fusion(cfg)
         self.sim_loss, self.sim_settings = check_sim_loss(cfg)
         self.lambda_jac, self.jac_settings = check_jac_penalty(cfg)
@@ -119,8 +123,35 @@ class DeepAtlasExperiment(BaseExperiment):
         if SummaryWriter is not None:
             self.writer = SummaryWriter(self.ckpoint_dir)
 
+    def setup_nifti_data(self):
+        """Pairs and validation volumes over the reference's list-file datasets (models/nifti_data.py).  The labelled volumes are the first
+        num_labeled names of the training list; the validation list feeds both the segmentation and the pair validation."""
+        cfg = self.config
+        remap = {'moving_remap': cfg['moving_remap']} if cfg.get('moving_remap') else {}
+        training_vols = validation_vols = None
+        if self.training_data_loader is None:
+            training_vols = nifti_data.seg_dataset(cfg, 'training_list_file', 'data_dir', n_samples=max(cfg['num_samples'], 2))
+            if training_vols is None:
+                raise ValueError("config['data'] = %r needs config['training_list_file']" % (cfg['data'],))
+        if self.validation_data_loader is None or self.validation_pair_loader is None:
+            validation_vols = nifti_data.seg_dataset(cfg, 'validation_list_file', 'valid_data_dir')
+            if validation_vols is None:
+                raise ValueError("config['data'] = %r needs config['validation_list_file']" % (cfg['data'],))
+        nifti_data.check_shapes([training_vols, validation_vols], [cfg['model'], cfg['reg_model']])
+        if training_vols is not None:
+            self.labeled = list(range(max(0, min(int(cfg['num_labeled']), len(training_vols)))))
+            training_data = med_data.NiftiRegDataset(training_vols, labeled=self.labeled, pairs=cfg.get('pairs', 'fixed_labeled'), **remap)
+            sampler = parallel.distributed_sampler(training_data, shuffle=True, seed=cfg['random_seed'])
+            self.training_data_loader = DataLoader(training_data, batch_size=1, shuffle=sampler is None, sampler=sampler, num_workers=0)
+        if self.validation_data_loader is None:
+            self.validation_data_loader = DataLoader(validation_vols, batch_size=1, shuffle=False, num_workers=0)
+        if self.validation_pair_loader is None:
+            self.validation_pair_loader = DataLoader(med_data.NiftiRegDataset(validation_vols, **remap), batch_size=1, shuffle=False, num_workers=0)
+
     def setup_train_data(self):
         cfg = self.config
+        if nifti_data.is_nifti(cfg):
+            return self.setup_nifti_data()
         shape, C = cfg['synthetic_shape'], cfg['n_classes']
         remap = {'moving_remap': cfg['moving_remap']} if cfg.get('moving_remap') else {}
         if self.training_data_loader is None:

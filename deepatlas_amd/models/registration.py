@@ -24,6 +24,8 @@ image and segmentation a rigid misalignment, the same one in every epoch (seeded
 config['report_tre'] (None default: off | a dict with 'amp_vox' and optionally 'points') makes validation also run the known-deformation
 probe (lib/evalMetrics.py known_deformation_tre) on the fixed image of every pair, one more net forward: the landmark error in voxels against
 the exact inverse of a known smooth field (tre_mean_vox, tre_max_vox, tre_initial_mean_vox).  It takes no part in the experiment's name.
+config['data'] other than 'synthetic' (models/nifti_data.py) trains on the ordered pairs of the NIfTI volumes of a list file; misalign and report_tre
+are synthetic-only and raise with such data.
 """
 import datetime
 import os
@@ -36,6 +38,7 @@ import torch
 from torch.utils.data import DataLoader
 
 from .base import BaseExperiment
+from . import nifti_data
 from .joint import RegistrationStep, SIM_LOSSES, make_jac_penalty, make_ic_penalty
 from .segmentation import SegmentationExperiment
 from ..lib import datasets as med_data
@@ -344,6 +347,7 @@ class RegistrationExperiment(BaseExperiment):
         self.affine_init, self.affine_settings = check_affine_init(cfg)
         self.misalign = check_misalign(cfg)
         self.report_tre = check_report_tre(cfg)
+        nifti_data.refuse_synthetic_only(cfg, ('misalign', 'report_tre'))
         self.exp_name = self.experiment_name(cfg)
         run_dir = "debug_reg" if cfg['debug_mode'] else self.exp_name
         self.ckpoint_dir = os.path.join(cfg['log_dir'], run_dir, str(cfg['random_seed']))
@@ -382,6 +386,8 @@ class RegistrationExperiment(BaseExperiment):
     def setup_train_data(self):
         if self.training_data_loader is not None:
             return
+        if nifti_data.is_nifti(self.config):
+            return self.setup_nifti_data()
         dataset = med_data.get_reg_dataset(self.config['data'])
         shape = self.config['synthetic_shape']
         remap = {'moving_remap': self.config['moving_remap']} if self.config.get('moving_remap') else {}
@@ -392,6 +398,21 @@ class RegistrationExperiment(BaseExperiment):
         validation_data = dataset(max(self.config.get('num_valid_samples', 2), 2), shape, self.config['n_classes'],
                                   seed=self.config['random_seed'] + 1000, **remap)
         self.validation_data_loader = DataLoader(validation_data, batch_size=1, shuffle=False, num_workers=0)
+
+    def setup_nifti_data(self):
+        """Pairs over the reference's list-file volume datasets (models/nifti_data.py): the training list's first num_samples scans, the
+        validation list whole; all volumes must share one shape."""
+        cfg = self.config
+        remap = {'moving_remap': cfg['moving_remap']} if cfg.get('moving_remap') else {}
+        training_vols = nifti_data.seg_dataset(cfg, 'training_list_file', 'data_dir', n_samples=max(cfg['num_samples'], 2))
+        validation_vols = nifti_data.seg_dataset(cfg, 'validation_list_file', 'valid_data_dir')
+        if training_vols is None or validation_vols is None:
+            raise ValueError("config['data'] = %r needs config['training_list_file'] and config['validation_list_file']" % (cfg['data'],))
+        nifti_data.check_shapes([training_vols, validation_vols], [cfg['model']])
+        training_data = med_data.NiftiRegDataset(training_vols, **remap)
+        sampler = parallel.distributed_sampler(training_data, shuffle=True, seed=cfg['random_seed'])
+        self.training_data_loader = DataLoader(training_data, batch_size=cfg['batch_size'], shuffle=sampler is None, sampler=sampler, num_workers=0)
+        self.validation_data_loader = DataLoader(med_data.NiftiRegDataset(validation_vols, **remap), batch_size=1, shuffle=False, num_workers=0)
 
     def setup_model(self):
         self.model = get_network(self.config['model'])(**self.config.get('model_settings', {}))

@@ -4,7 +4,10 @@ Same config keys (train_seg.py:33-61), same setup order, same step semantics (mo
 train(); zero_grad(); out = model(x); loss = crit(out, y.long()); backward(); Adam.step(); loss.item()), eval =
 argmax -> per-class Dice for classes 1..C-1 averaged over volumes then classes (:179-201), validate ->
 scheduler.step + checkpoint (:203-239).  Differences, all host-side: the device is explicit
-(config['device'], default 'cuda'), data comes from config['data'] == 'synthetic' or injected loaders,
+(config['device'], default 'cuda'), data comes from config['data'] == 'synthetic', from the reference's NIfTI list-file datasets
+(config['data'] 'OAI', 'OASIS', 'LPBA40', 'CUMC12', 'IBSR18', 'MGH10' or 'MindBoggle' with the reference's keys data_dir, valid_data_dir,
+training_list_file, validation_list_file, testing_list_file, preload, crop_size, num_samples, plus the optional config['preprocess'];
+models/nifti_data.py) or from injected loaders,
 TensorBoard logging is optional, eval Dice is computed on the device (lib/evalMetrics.py), and with
 torch.distributed initialised the gradients are averaged with one flat-bucket all-reduce (parallel.py).
 config['lambda_boundary'] (default 0: off) weights Kervadec's boundary loss as a second term of the step (lib/loss.py BoundaryLoss: signed
@@ -21,6 +24,7 @@ import torch.optim.lr_scheduler as lr_scheduler
 from torch.utils.data import DataLoader
 
 from .base import BaseExperiment
+from . import nifti_data
 from ..lib import datasets as med_data
 from ..lib import evalMetrics as metrics
 from ..lib import transforms as med_transforms
@@ -115,6 +119,8 @@ class SegmentationExperiment(BaseExperiment):
     def setup_train_data(self):
         if self.training_data_loader is not None:
             return
+        if nifti_data.is_nifti(self.config):
+            return self.setup_nifti_data()
         dataset = med_data.get_seg_dataset(self.config['data'])
         shape = self.config['synthetic_shape']
         training_data = dataset(self.config["num_samples"] * 2, shape, self.config['n_classes'], seed=self.config['random_seed'])
@@ -124,6 +130,22 @@ class SegmentationExperiment(BaseExperiment):
         validation_data = dataset(self.config.get('num_valid_samples', 2), shape, self.config['n_classes'],
                                   seed=self.config['random_seed'] + 1000)
         self.validation_data_loader = DataLoader(validation_data, batch_size=1, shuffle=False, num_workers=0)
+
+    def setup_nifti_data(self):
+        """models/segmentation.py:54-79, 241-251: the training list's first num_samples * 2 scans, the validation and test lists whole; every
+        prepared volume must have the one shape the net accepts (nifti_data.check_shapes raises otherwise)."""
+        cfg = self.config
+        training_data = nifti_data.seg_dataset(cfg, 'training_list_file', 'data_dir', n_samples=cfg['num_samples'] * 2)
+        validation_data = nifti_data.seg_dataset(cfg, 'validation_list_file', 'valid_data_dir')
+        testing_data = nifti_data.seg_dataset(cfg, 'testing_list_file', 'valid_data_dir')
+        if training_data is None or validation_data is None:
+            raise ValueError("config['data'] = %r needs config['training_list_file'] and config['validation_list_file']" % (cfg['data'],))
+        nifti_data.check_shapes([training_data, validation_data, testing_data], [cfg['model']])
+        sampler = parallel.distributed_sampler(training_data, shuffle=True, seed=cfg['random_seed'])
+        self.training_data_loader = DataLoader(training_data, batch_size=cfg['batch_size'], shuffle=sampler is None, sampler=sampler, num_workers=0)
+        self.validation_data_loader = DataLoader(validation_data, batch_size=1, shuffle=False, num_workers=0)
+        if testing_data is not None:
+            self.testing_data_loader = DataLoader(testing_data, batch_size=1, shuffle=False, num_workers=0)
 
     def setup_model(self):
         model_type = get_network(self.config['model'])
@@ -367,7 +389,9 @@ class SegmentationExperiment(BaseExperiment):
         self.setup_model()
         ckpoint_file = os.path.join(self.ckpoint_dir, 'model_best.pth.tar' if best else 'checkpoint.pth.tar')
         last_epoch, best_score = self.initialize_model(self.model, optimizer=None, ckpoint_path=ckpoint_file)
-        loader = self.config.get('testing_data_loader') or self.validation_data_loader
+        if self.validation_data_loader is None and nifti_data.is_nifti(self.config):        # test only: the loaders were never built
+            self.setup_train_data()
+        loader = self.config.get('testing_data_loader') or getattr(self, 'testing_data_loader', None) or self.validation_data_loader
         dice_per_class, dice_avg, samples = self.eval(loader)
         print('Testing Model: {} ({} epochs)  Dice_avg: {}{}'.format(ckpoint_file, last_epoch, float(dice_avg), self._surface_suffix() + self._post_suffix()))
         return dice_per_class, dice_avg

@@ -3256,3 +3256,163 @@ def surface_distance_stats(pred, truth, n_class, classes=None, spacing=(1, 1, 1)
         call('da_surface_dist_stats', ptr(p), _LABEL_BYTES[p.dtype], ptr(t), _LABEL_BYTES[t.dtype], ptr(cls), len(cl), N, D, H, W,
              sp[0], sp[1], sp[2], conn, pct, ptr(out), wp, wn, stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# volume preprocessing (preprocess.hip; lib/transforms.py:9-68, :269-284, :692-706): resample to a voxel size, moments, percentiles,
+# intensity rescale, label look-up.  No autograd.
+# ------------------------------------------------------------------------------------------------
+PREPROCESS_DTYPE_CODE = {torch.float32: 0, torch.float64: 1, torch.int16: 2, torch.uint8: 3, torch.int32: 4}
+RESAMPLE_INTERPOLATORS = {'linear': 0, 'nearest': 1}
+PREPROCESS_MAX_VOXELS = 2 ** 31
+LABEL_LUT_MAX = 65536
+
+
+def resample_axis_table(n_in, n_out, scale, offset, interpolator='nearest'):
+    """One axis of da_resample_axes, on the host in float64 (pure numpy, no GPU): output index o reads the continuous input index
+    q = scale * o + offset (one multiply, one add).  Returns (lower int32[n_out], upper int32[n_out], fraction float32[n_out], inside bool[n_out]).
+    Inside iff -0.5 <= q < n_in - 0.5.  'nearest': lower = upper = clamp(floor(q + 0.5), 0, n_in - 1) (ties round up), fraction 0.  'linear':
+    f = floor(q), lower = clamp(f, 0, n_in - 1), upper = min(lower + 1, n_in - 1), fraction float32(q - f); for q < 0 lower 0 and fraction 0.
+    This is ITK ResampleImageFilter's documented behaviour (the buffer test on the continuous index, edge-clamped taps); agreement with ITK
+    itself is not tested.  Entries outside keep their clamped taps here; resample_volume marks them for the kernel."""
+    import numpy as np
+    if interpolator not in RESAMPLE_INTERPOLATORS:
+        raise ValueError("interpolator %r: 'nearest' or 'linear'" % (interpolator,))
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in < 1 or n_out < 1:
+        raise ValueError('resample_axis_table needs n_in >= 1 and n_out >= 1, got %d and %d' % (n_in, n_out))
+    scale, offset = float(scale), float(offset)
+    if not (np.isfinite(scale) and np.isfinite(offset)):
+        raise ValueError('scale and offset must be finite')
+    q = np.float64(scale) * np.arange(n_out, dtype=np.float64) + np.float64(offset)
+    inside = (q >= -0.5) & (q < n_in - 0.5)
+    if interpolator == 'nearest':
+        lo = np.clip(np.floor(q + 0.5), 0, n_in - 1).astype(np.int32)
+        return lo, lo.copy(), np.zeros(n_out, dtype=np.float32), inside
+    f = np.floor(q)
+    lo = np.clip(f, 0, n_in - 1).astype(np.int32)
+    hi = np.minimum(lo + 1, n_in - 1).astype(np.int32)
+    frac = np.where(q < 0, 0.0, q - f).astype(np.float32)
+    return lo, hi, frac, inside
+
+
+def _pack_axis_tables(tables):
+    """Three resample_axis_table results (D, H, W) -> the int32 [Do + Ho + Wo][3] array of da_resample_axes (lower tap -1 = outside)."""
+    import numpy as np
+    rows = []
+    for lo, hi, frac, inside in tables:
+        t = np.empty((len(lo), 3), dtype=np.int32)
+        t[:, 0] = np.where(inside, lo, -1)
+        t[:, 1] = hi
+        t[:, 2] = np.ascontiguousarray(frac, dtype=np.float32).view(np.int32)
+        rows.append(t)
+    return np.ascontiguousarray(np.concatenate(rows, axis=0))
+
+
+def _volume4(vol, what='volume'):
+    if not torch.is_tensor(vol) or vol.dim() not in (3, 4):
+        raise ValueError('%s must be a D x H x W or C x D x H x W tensor' % what)
+    if vol.dtype not in PREPROCESS_DTYPE_CODE:
+        raise ValueError('%s dtype %s: float32, float64, int16, uint8 or int32' % (what, vol.dtype))
+    if vol.numel() == 0:
+        raise ValueError('%s is empty' % what)
+    if vol.numel() >= PREPROCESS_MAX_VOXELS:
+        raise ValueError('%s has %d elements: the preprocessing kernels take fewer than 2^31' % (what, vol.numel()))
+    return vol.dim() == 3
+
+
+def resample_volume(vol, out_size, scale, offset, interpolator='nearest', default=0):
+    """Axis-aligned resample of a D x H x W or C x D x H x W device volume onto a grid out_size = (Do, Ho, Wo): output index o of each axis reads
+    input index scale * o + offset (scale, offset: three numbers each, (D, H, W) order), by the rule of resample_axis_table.  'nearest' returns
+    the source dtype bit for bit, 'linear' float32; voxels outside on any axis get `default`.  A negative scale with offset n - 1 is a flip."""
+    single = _volume4(vol)
+    if interpolator not in RESAMPLE_INTERPOLATORS:
+        raise ValueError("interpolator %r: 'nearest' or 'linear'" % (interpolator,))
+    if len(out_size) != 3 or len(scale) != 3 or len(offset) != 3:
+        raise ValueError('out_size, scale and offset take three values each (D, H, W)')
+    v = vol.unsqueeze(0) if single else vol
+    C, D, H, W = (int(s) for s in v.shape)
+    Do, Ho, Wo = (int(s) for s in out_size)
+    if min(Do, Ho, Wo) < 1:
+        raise ValueError('out_size must be positive, got %s' % (tuple(out_size),))
+    if C * Do * Ho * Wo >= PREPROCESS_MAX_VOXELS:
+        raise ValueError('the output has %d elements: the preprocessing kernels take fewer than 2^31' % (C * Do * Ho * Wo))
+    packed = _pack_axis_tables([resample_axis_table(n, m, s, o, interpolator) for n, m, s, o in zip((D, H, W), (Do, Ho, Wo), scale, offset)])
+    nat.require_cuda(v)
+    v = v.contiguous()
+    tab = _const_tensor(packed, v.device)
+    out = torch.empty((C, Do, Ho, Wo), dtype=torch.float32 if interpolator == 'linear' else v.dtype, device=v.device)
+    with torch.cuda.device(v.device):
+        call('da_resample_axes', ptr(v), PREPROCESS_DTYPE_CODE[v.dtype], ptr(out), RESAMPLE_INTERPOLATORS[interpolator], C, D, H, W, Do, Ho, Wo,
+             ptr(tab), float(default), stream())
+    return out[0] if single else out
+
+
+def volume_moments(vol):
+    """(count of finite voxels, their mean, their unbiased variance) of a device volume as Python floats; two passes in double, fixed order."""
+    _volume4(vol)
+    nat.require_cuda(vol)
+    v = vol.contiguous()
+    out = torch.empty(3, dtype=torch.float64, device=v.device)
+    with torch.cuda.device(v.device):
+        wp, wn = _ws(nat.lib().da_volume_moments_ws_bytes(v.numel()), v)
+        call('da_volume_moments', ptr(v), PREPROCESS_DTYPE_CODE[v.dtype], v.numel(), ptr(out), wp, wn, stream())
+    c, m, s2 = out.tolist()
+    return c, m, s2
+
+
+def volume_order_statistics(vol, percentiles):
+    """The raw result of da_volume_percentiles for one or two percentiles: dict with 'percentiles' (list of doubles), 'order_statistics'
+    (per percentile the (lower, upper) float32 order statistics it interpolates), 'count' (non-NaN values) and 'nan_count'."""
+    import ctypes
+    _volume4(vol)
+    ps = [float(p) for p in (percentiles if hasattr(percentiles, '__len__') else [percentiles])]
+    if not 1 <= len(ps) <= 2:
+        raise ValueError('one or two percentiles per call, got %d' % len(ps))
+    if any(not 0.0 <= p <= 100.0 for p in ps):
+        raise ValueError('percentiles must be in [0, 100], got %r' % (ps,))
+    nat.require_cuda(vol)
+    v = vol.contiguous()
+    out = torch.empty(8, dtype=torch.float64, device=v.device)
+    arr = (ctypes.c_double * len(ps))(*ps)
+    with torch.cuda.device(v.device):
+        wp, wn = _ws(nat.lib().da_volume_percentiles_ws_bytes(v.numel()), v)
+        call('da_volume_percentiles', ptr(v), PREPROCESS_DTYPE_CODE[v.dtype], v.numel(), arr, len(ps), ptr(out), wp, wn, stream())
+    o = out.tolist()
+    return {'percentiles': o[:len(ps)], 'order_statistics': [(o[2 + 2 * j], o[3 + 2 * j]) for j in range(len(ps))],
+            'count': int(o[6]), 'nan_count': int(o[7])}
+
+
+def volume_percentiles(vol, percentiles):
+    """numpy.percentile(x, p) (the 'linear' rule) of the float32 values of a device volume, NaNs left out, for one or two p: a tuple of doubles.
+    Exact order statistics by a three-digit radix select on the device."""
+    return tuple(volume_order_statistics(vol, percentiles)['percentiles'])
+
+
+def affine_intensity(vol, a, b, clamp=False):
+    """(x - a) / b as float32 (a, b rounded to float32), optionally clamped to [0, 1]; b == 0 gives zeros.  Same shape as vol."""
+    _volume4(vol)
+    nat.require_cuda(vol)
+    v = vol.contiguous()
+    out = torch.empty(v.shape, dtype=torch.float32, device=v.device)
+    with torch.cuda.device(v.device):
+        call('da_affine_intensity_to_f32', ptr(v), PREPROCESS_DTYPE_CODE[v.dtype], ptr(out), v.numel(), float(a), float(b), 1 if clamp else 0, stream())
+    return out
+
+
+def label_lut(labels, lut):
+    """lut[label] for a uint8 / int32 device label volume (same dtype out); lut: at most 65536 integers; labels outside the table map to 0."""
+    import numpy as np
+    _volume4(labels, 'labels')
+    if labels.dtype not in (torch.uint8, torch.int32):
+        raise ValueError('labels must be uint8 or int32, got %s' % labels.dtype)
+    table = np.ascontiguousarray(np.asarray(lut).reshape(-1), dtype=np.int32)
+    if not 1 <= table.shape[0] <= LABEL_LUT_MAX:
+        raise ValueError('the look-up table takes 1..%d entries, got %d' % (LABEL_LUT_MAX, table.shape[0]))
+    nat.require_cuda(labels)
+    v = labels.contiguous()
+    out = torch.empty_like(v)
+    t = _const_tensor(table, v.device)
+    with torch.cuda.device(v.device):
+        call('da_label_lut', ptr(v), PREPROCESS_DTYPE_CODE[v.dtype], ptr(out), v.numel(), ptr(t), int(table.shape[0]), stream())
+    return out

@@ -478,6 +478,43 @@ int da_assemble_tiles(const void* tiles, void* vol, int elem_bytes, int D, int H
 int da_synth_volume(float* img, unsigned char* labels, int N, int D, int H, int W, int n_classes, int mode, float noise,
                     unsigned int seed, int sample0, void* stream);
 
+/* ---- volume preprocessing (preprocess.hip; lib/transforms.py:9-57 Resample, :59-68 Normalization, :269-284 LeftToRight, :692-706
+ * SegmentationLabelFilter; the percentile rescale is the project's own) on the raw array of a NIfTI file (lib/nifti.py).
+ * Volumes are [C][D][H][W]; src_dtype as above (0 f32, 1 f64, 2 i16, 3 u8, 4 i32).  Every entry checks its arguments before any launch
+ * (DA_ERR_BADARG), refuses volumes of 2^31 or more elements (DA_ERR_UNSUPPORTED) and has no autograd.  Launch shape of every kernel:
+ * 256-thread workgroups, lanes consecutive along W, no workgroup waits for another, what one launch reads from another goes through
+ * stream order; reductions accumulate in double in a fixed order (thread -> workgroup -> one finishing launch), the only atomics are
+ * integer adds: results are bit-identical from run to run.
+ *
+ * da_resample_axes: axis-aligned resample onto a grid [C][Do][Ho][Wo], a gather through one table per output axis.  `tables` (device):
+ * int32 [Do + Ho + Wo][3], the D entries, then H, then W: {lower tap, upper tap, bits of the float32 fraction}; lower tap -1 marks an entry
+ * outside the input.  The table rule (ops.resample_axis_table builds it on the host in float64): output index o reads the continuous input
+ * index q = scale * o + offset (one multiply, one add); inside iff -0.5 <= q < n_in - 0.5 (ITK ResampleImageFilter's buffer test on the
+ * continuous index).  Nearest: tap clamp(floor(q + 0.5), 0, n_in - 1) (ties round up).  Linear: f = floor(q), lower tap clamp(f, 0, n_in - 1),
+ * upper tap min(lower + 1, n_in - 1), fraction float32(q - f); for q < 0 the lower tap is 0 and the fraction 0 (edge-clamped taps).  A negative
+ * scale with offset n - 1 is a flip; scale 1 with offset 0 a bit-exact copy.  interpolator 1 (nearest) writes the source dtype bit for bit;
+ * interpolator 0 (linear) writes float32, computed in float32 as fmaf(t, b - a, a) along W, then H, then D.  A voxel outside on any axis gets
+ * default_value (converted to the output dtype).  Agreement with ITK itself is not tested. */
+int da_resample_axes(const void* src, int src_dtype, void* dst, int interpolator, int C, int D, int H, int W, int Do, int Ho, int Wo,
+                     const int* tables, double default_value, void* stream);
+/* da_volume_moments: out3 (device doubles) = {number of finite voxels, their mean, their unbiased variance}; two passes over the volume, the
+ * second accumulating (x - mean)^2 (a sigma of 0.01 on a mean of 1000 survives).  No finite voxel: mean 0; fewer than two: variance 0. */
+size_t da_volume_moments_ws_bytes(long long n);
+int da_volume_moments(const void* src, int src_dtype, long long n, double* out3, void* ws, size_t ws_bytes, void* stream);
+/* da_volume_percentiles: exact order statistics of the float32 values of a volume for one or two percentiles in [0, 100] (host array).
+ * Every value maps to a monotone uint32 key (sign bit flipped for non-negatives, all bits for negatives); NaNs are left out and counted.
+ * Three-digit radix select (11 + 11 + 10 bits): per digit one launch builds LDS histograms of the keys matching each wanted rank's prefix
+ * and adds them into a global histogram, one single-workgroup launch picks the digit of each rank.  numpy's 'linear' rule:
+ * rank = p / 100 (n - 1), the two neighbouring order statistics interpolated in double.  out8 (device doubles): {percentile 0, percentile 1,
+ * the order statistics (lower, upper) of percentile 0 and of percentile 1, number of non-NaN values, number of NaNs}; NaN where undefined. */
+size_t da_volume_percentiles_ws_bytes(long long n);
+int da_volume_percentiles(const void* src, int src_dtype, long long n, const double* percentiles, int n_percentiles, double* out8,
+                          void* ws, size_t ws_bytes, void* stream);
+/* y = (x - a) / b in float32 (x converted to float32 first), optionally clamped to [0, 1]; b == 0 writes zeros. */
+int da_affine_intensity_to_f32(const void* src, int src_dtype, float* dst, long long n, float a, float b, int clamp01, void* stream);
+/* dst = lut[label] for u8 (3) / i32 (4) labels, dst of the source dtype; lut: device int32 [n_lut], n_lut <= 65536; labels outside it -> 0. */
+int da_label_lut(const void* src, int src_dtype, void* dst, long long n, const int* lut, int n_lut, void* stream);
+
 /* ---- random spatial augmentation (lib/transforms.py:161-290: RandomBSplineTransform, RandomRigidTransform, resample) --------
  * sitk.Resample with the image as its own reference grid, for a batch of N samples in one launch.  img / img_out [N][C][D][H][W] fp32,
  * labels / labels_out [N][D][H][W] of label_bytes (1, 4 or 8) bytes; either pair may be NULL (not both).  Output voxel i = (x, y, z) =

@@ -7,6 +7,7 @@ import argparse
 import os
 
 from deepatlas_amd.models.deepatlas import DeepAtlasExperiment
+from deepatlas_amd.models.nifti_data import apply_data_arguments
 from train_reg import add_common_arguments, apply_jacobian_arguments, apply_similarity_arguments
 
 
@@ -59,7 +60,7 @@ def build_config(args):
         config.pop('atlas_fusion', None)
     apply_similarity_arguments(config)
     apply_jacobian_arguments(config)
-    return config
+    return apply_data_arguments(config)
 
 
 def main(argv=None):

@@ -1,7 +1,8 @@
 """Train the registration net (VoxelMorph) alone: the registration counterpart of train_seg.py, which the reference lists as TODO
 (README.md:15-19).  Same flag style as train_seg.py; the step is similarity + lambda_reg * bending energy (models/joint.py RegistrationStep;
 --sim-loss ncc | lncc | mi, NCC by default), the data are ordered pairs of synthetic volumes (--moving-remap: the moving image in another
-"modality"), validation reports the hard-label registration Dice (against the identity deformation's) and the Jacobian statistics of the
+"modality") or, with --data NAME, of the NIfTI volumes of a list file (the flags of train_seg.py; --misalign and --report-tre stay
+synthetic-only), validation reports the hard-label registration Dice (against the identity deformation's) and the Jacobian statistics of the
 predicted deformation.  --lambda-jac > 0 adds the Jacobian folding penalty (--jac-eps, --jac-power) to the step: it trains against the
 folding fraction that validation prints.  --lambda-ic > 0 adds the inverse-consistency penalty: the step predicts both directions of every pair
 in one doubled-batch forward and penalises the composition of the two fields; validation then (or with --report-ic alone) also prints the
@@ -12,6 +13,7 @@ global misalignment that stage is for."""
 import argparse
 import os
 
+from deepatlas_amd.models.nifti_data import add_data_arguments, apply_data_arguments
 from deepatlas_amd.models.registration import RegistrationExperiment
 
 
@@ -54,7 +56,7 @@ def build_config(args):
     apply_inverse_consistency_arguments(config)
     apply_affine_arguments(config)
     apply_tre_arguments(config)
-    return config
+    return apply_data_arguments(config)
 
 
 def apply_tre_arguments(config):
@@ -144,7 +146,7 @@ def add_common_arguments(parser):
                         help='weight of the Jacobian folding penalty mean(max(0, eps - det J)^power) of the predicted deformation (0: off)')
     parser.add_argument('--jac-eps', default=None, type=float, help='margin of --lambda-jac: voxels with det J < eps are penalised (0..1, default 0)')
     parser.add_argument('--jac-power', default=None, type=int, choices=[1, 2], help='exponent of --lambda-jac (default 1)')
-    return parser
+    return add_data_arguments(parser)
 
 
 def add_inverse_consistency_arguments(parser):

@@ -1,10 +1,13 @@
 """Train a 3D U-Net: the build's counterpart of the reference's train_seg.py (same flags, same config dict,
 train_seg.py:10-93) with its three shipped bugs fixed: the em-dash in '--num-epochs', the
-positional './data' / './logs' defaults, and the undefined args.leaf.  Device selection is explicit and the
-data source is the synthetic volume generator (the MindBoggle NIfTI pipeline needs SimpleITK)."""
+positional './data' / './logs' defaults, and the undefined args.leaf.  Device selection is explicit.  The data
+source is the synthetic volume generator, or with --data NAME the reference's NIfTI list-file datasets read without SimpleITK (--data-dir,
+--train-list, --valid-list, --test-list) and prepared on the device (--voxel-size, --rescale-percentiles, --normalize, --ignore-labels,
+--crop-size)."""
 import argparse
 import os
 
+from deepatlas_amd.models.nifti_data import add_data_arguments, apply_data_arguments
 from deepatlas_amd.models.segmentation import SegmentationExperiment
 
 
@@ -89,7 +92,7 @@ def build_config(args):
         config.pop('lambda_boundary', None)
     if not config.get('matrix_precision'):                # (--matrix-precision; not a key of the reference's config: absent = the package default, 'fp32_split')
         config.pop('matrix_precision', None)
-    return config
+    return apply_data_arguments(config)
 
 
 def main(argv=None):
@@ -139,6 +142,7 @@ def main(argv=None):
     parser.add_argument('--lambda-boundary', type=float, default=None, metavar='W',
                         help="add W x the boundary loss (Kervadec et al.: softmax probability times the signed distance to the ground truth, the "
                              "distance maps rebuilt on the device from every batch's labels) to the step's loss; 0 or absent: off")
+    add_data_arguments(parser, with_preload=False)              # (--preload is the reference's own flag, above)
     args = parser.parse_args(argv)
     exp = SegmentationExperiment(build_config(args))
     if not args.test_only:
