@@ -178,6 +178,11 @@ SIGNATURES = {
     'da_volume_percentiles': (I, [P, I, LL, POINTER(c_double), I, P, P, SZ, P]),
     'da_affine_intensity_to_f32': (I, [P, I, P, LL, F, F, I, P]),
     'da_label_lut': (I, [P, I, P, LL, P, I, P]),
+    'da_window_label_counts_ws_bytes': (SZ, [I, I, I, I, P]),
+    'da_window_label_counts': (I, [P, I, I, I, I, I, P, LL, P, P, SZ, P]),
+    'da_crop_sample_starts_ws_bytes': (SZ, [I, I, I, I, P, I]),
+    'da_crop_sample_starts': (I, [P, I, I, I, I, I, P, I, I, P, I, P, ctypes.c_uint, I, P, P, P, SZ, P]),
+    'da_crop_gather': (I, [P, P, I, P, P, I, P, I, I, I, I, I, P, P]),
     'da_spatial_resample':(I, [P, P, I, I, P, P, I, P, P, I, I, I, I, I, I, I, I, P]),
     'da_gauss_blur3d': (I, [P, P, P, P, I, P, I, I, I, I, I, P]),
     'da_bilateral3d': (I, [P, P, P, P, I, I, I, I, F, F, P, I, I, I, I, I, P]),

@@ -7,8 +7,9 @@ device kernels.  The preprocessing transforms the reference runs through SimpleI
 a voxel size (:9-57), Normalization (:59-68), LeftToRight (:269-284), SegmentationLabelFilter (:692-706), IdentityTransform, and the
 project's own PercentileRescale; they act on the raw arrays lib/nifti.py reads.  Every class takes numpy arrays (what
 sitk.GetArrayFromImage returns) or tensors and hands back DEVICE tensors, so a loader thread only uploads the raw volume once.
-Out of scope: RandomCrop / BalancedRandomCrop (patch sampling, the natural next step beside Partition), reorientation by the affine, oblique
-resampling, anti-aliasing on down-sampling and B-spline interpolation.
+Patch sampling, RandomCrop (:322-388) and BalancedRandomCrop (:391-505), runs on the device as well (csrc/crop.hip): the class count of every
+crop window as a separable sliding sum, a uniform pick among the starts that pass, one batched gather.
+Out of scope: reorientation by the affine, oblique resampling, anti-aliasing on down-sampling and B-spline interpolation.
 """
 import ctypes
 import math
@@ -556,18 +557,171 @@ class RandomIntensityTransform(object):
         return _store(sample, ops.intensity_augment(imgs, params, coef, self.bias_order), None, single)
 
 
+# ---- random crops (lib/transforms.py:322-505) on csrc/crop.hip -----------------------------------------------------------------------------
+def crop_min_count(threshold, size):
+    """The smallest integer n >= 0 with n / size > threshold in float64 -- the reference's comparison np.sum(seg_crop == c) / seg_crop.size >
+    threshold (:455, :473) as a bound on the integer count.  Found by adjusting around floor(threshold * size); a threshold >= 1 gives
+    size + 1 (no window passes), a negative one 0."""
+    size = int(size)
+    if size < 1:
+        raise ValueError('size must be positive')
+    t = np.float64(threshold)
+    if not np.isfinite(t):
+        raise ValueError('threshold must be finite')
+    if t < 0:
+        return 0
+    n = int(min(max(np.floor(t * size), 0), size + 1))
+    while n > 0 and np.float64(n - 1) / np.float64(size) > t:
+        n -= 1
+    while n <= size and not np.float64(n) / np.float64(size) > t:
+        n += 1
+    return n
+
+
+def _crop_seed(random_state):
+    """The one 32-bit seed of a call: from random_state when given, else from np.random as the other transforms draw."""
+    rs = random_state if random_state is not None else np.random
+    return int(rs.randint(0, 2 ** 32, dtype=np.int64))
+
+
+def _crop_output_size(output_size):
+    assert isinstance(output_size, (int, tuple))
+    if isinstance(output_size, int):
+        return (output_size, output_size, output_size)
+    assert len(output_size) == 3
+    return output_size
+
+
+def _crop_labels(segs):
+    """Labels in a dtype the crop kernels read: uint8, int32 and int64 as they are, other integers as int32."""
+    if segs.dtype in ops.CROP_LABEL_DTYPE_CODE:
+        return segs
+    return segs.to(torch.int32)
+
+
+def _crop_batch(sample):
+    imgs, segs, single = _as_batch(sample)
+    if segs is None:
+        raise ValueError("the crops need sample['segmentation'] (the reference crops both)")
+    imgs = imgs.to(_device())
+    if imgs.dtype != torch.float32:
+        imgs = imgs.float()
+    return imgs, _crop_labels(segs.to(_device())), single
+
+
+class RandomCrop(object):
+    """lib/transforms.py:322-388 on the device: one random crop of output_size (an int, or (x, y, z) in SimpleITK order, flipped to numpy
+    order as Partition flips) from the image and, at the same start, the segmentation.  Tensors as RandomRigidTransform: one sample
+    (C x D x H x W, D x H x W) or a batch.  The start is uniform over random_3d_coordinates' domain, max(S - w, 1) starts per axis
+    (ops.sample_crop_starts, unconditioned).  The reference's own lines 357-359 compare the wrong way round (`size_old < size_new`) and so
+    always crop at start 0, and its threshold test (:381) sets a flag nothing reads: `threshold` is kept for the signature and has no effect
+    here either; the evident intent, a uniform start, is what is implemented.  Unlike the reference, random_state is honoured: it yields the
+    one 32-bit seed per call (np.random does otherwise)."""
+
+    def __init__(self, output_size, threshold=-0, random_state=None):
+        self.output_size = _crop_output_size(output_size)
+        self.threshold = threshold
+        self.random_state = random_state
+
+    def __call__(self, sample):
+        imgs, segs, single = _crop_batch(sample)
+        window = tuple(int(v) for v in np.flipud(np.asarray(self.output_size)))
+        starts, _ = ops.sample_crop_starts(segs, window, [None], [0], _crop_seed(self.random_state))
+        img, seg = ops.crop_gather(imgs, segs, starts, window)
+        return _store(sample, img, seg, single)
+
+
+class BalancedRandomCrop(object):
+    """lib/transforms.py:391-494 on the device: crops that alternate between the classes.  The reference's state machine is kept:
+    current_class starts at 2 and advances per patch through 2, 3, 0, 1, 2, ...; tag 0 is an unconditioned crop, tag 1 asks for a share of
+    class 1 above threshold[0], tags 2 and 3 for a share of class 2 above threshold[1] (threshold: a float, or a 2-tuple).  Where the
+    reference redraws until np.sum(seg_crop == c) / size > threshold, the device picks uniformly among the starts that pass
+    (ops.sample_crop_starts with crop_min_count), which is the distribution that loop converges to; where none passes -- the reference
+    would loop forever -- the start with the largest count is taken.  sample['class'] holds the tags: an int for a single sample with
+    patches = 1, else a list, sample-major.
+    The project's own generalisations: classes, a list of labels (None: unconditioned) to cycle through from its first entry instead, with
+    threshold a float or a sequence of the same length and the position in the list as tag; patches, the number of crops per sample (a
+    single sample with patches = 1 returns a single sample, as the reference does, anything else a batch of N * patches); include_last, the
+    domain S - w + 1 instead of random_3d_coordinates' max(S - w, 1); and random_state, honoured as in RandomCrop."""
+
+    def __init__(self, output_size, threshold=0.01, random_state=None, classes=None, patches=1, include_last=False):
+        self.output_size = _crop_output_size(output_size)
+        if classes is None:
+            assert isinstance(threshold, (float, tuple))
+            if isinstance(threshold, float):
+                self.threshold = (threshold, threshold, threshold)
+            else:
+                assert len(threshold) == 2
+                self.threshold = threshold
+            self.cycle = [(None, 0.0), (1, self.threshold[0]), (2, self.threshold[1]), (2, self.threshold[1])]
+            self.current_class = 2  # tag that which class should be focused on currently
+        else:
+            classes = list(classes)
+            if not classes:
+                raise ValueError('classes must name at least one label (or None)')
+            thr = [float(threshold)] * len(classes) if np.ndim(threshold) == 0 else [float(t) for t in threshold]
+            if len(thr) != len(classes):
+                raise ValueError('threshold must be a float or hold one value per entry of classes')
+            self.threshold = tuple(thr)
+            self.cycle = [(None if c is None else int(c), t) for c, t in zip(classes, thr)]
+            self.current_class = 0
+        if int(patches) < 1:
+            raise ValueError('patches must be >= 1')
+        self.patches = int(patches)
+        self.include_last = bool(include_last)
+        self.random_state = random_state
+
+    def _next_tags(self, n):
+        tags = []
+        for _ in range(n):
+            tags.append(self.current_class)
+            self.current_class = self.current_class + 1
+            if self.current_class > len(self.cycle) - 1:
+                self.current_class = 0
+        return tags
+
+    def __call__(self, sample):
+        imgs, segs, single = _crop_batch(sample)
+        window = tuple(int(v) for v in np.flipud(np.asarray(self.output_size)))
+        size = window[0] * window[1] * window[2]
+        N, P = int(imgs.shape[0]), self.patches
+        tags = self._next_tags(N * P)
+        seed = _crop_seed(self.random_state)
+
+        def draw(lab, t, sample0):
+            return ops.sample_crop_starts(lab, window, [self.cycle[k][0] for k in t], [crop_min_count(self.cycle[k][1], size) for k in t],
+                                          seed, sample0=sample0, include_last=self.include_last)[0]
+        if all(tags[n * P:(n + 1) * P] == tags[:P] for n in range(N)):
+            starts = draw(segs, tags[:P], 0)
+        else:                                            # the samples' tag sequences differ: one call per sample, the same draws
+            starts = torch.cat([draw(segs[n:n + 1], tags[n * P:(n + 1) * P], n) for n in range(N)], 0)
+        img, seg = ops.crop_gather(imgs, segs, starts, window)
+        if single and P == 1:
+            sample['class'] = tags[0]
+            return _store(sample, img, seg, True)
+        sample['class'] = tags
+        return _store(sample, img, seg, False)
+
+
 AUGMENTATIONS = {'rigid': RandomRigidTransform, 'bspline': RandomBSplineTransform, 'blur': GaussianBlur, 'bilateral': BilateralFilter,
                  'intensity': RandomIntensityTransform}
+CROPS = {'crop': RandomCrop, 'balanced_crop': BalancedRandomCrop}       # patch sampling: they change the sample's shape
 
 
 def make_augmentation(spec):
-    """SegmentationExperiment's config['augment']: [[name, kwargs], ...] with name 'rigid', 'bspline', 'blur', 'bilateral' or 'intensity'
-    -> the transforms, in order."""
+    """SegmentationExperiment's config['augment']: [[name, kwargs], ...] with name 'rigid', 'bspline', 'blur', 'bilateral', 'intensity',
+    'crop' or 'balanced_crop' -> the transforms, in order.  (A config file has lists where the crops' asserts want tuples: output_size and
+    threshold are converted.)"""
     out = []
     for name, kwargs in (spec or []):
-        if name not in AUGMENTATIONS:
-            raise ValueError("augmentation %r: one of %s" % (name, sorted(AUGMENTATIONS)))
-        out.append(AUGMENTATIONS[name](**dict(kwargs or {})))
+        if name not in AUGMENTATIONS and name not in CROPS:
+            raise ValueError("augmentation %r: one of %s" % (name, sorted(AUGMENTATIONS) + sorted(CROPS)))
+        kwargs = dict(kwargs or {})
+        if name in CROPS:
+            for k in ('output_size', 'threshold'):
+                if isinstance(kwargs.get(k), list):
+                    kwargs[k] = tuple(kwargs[k])
+        out.append((CROPS if name in CROPS else AUGMENTATIONS)[name](**kwargs))
     return out
 
 

@@ -34,7 +34,7 @@ from . import nifti_data
 from .joint import DeepAtlasJointStep
 from .registration import (atlas_fusion_text, check_atlas_fusion, check_jac_penalty, check_sim_loss, dataset_volumes, eval_atlas_fusion,
                            eval_registration, jac_name_suffix)
-from .segmentation import SegmentationExperiment
+from .segmentation import SegmentationExperiment, refuse_patch
 from ..lib import datasets as med_data
 from ..lib.network_factory import get_network
 from ..lib.param_dict import save_dict_to_json
@@ -60,6 +60,7 @@ class DeepAtlasExperiment(BaseExperiment):
         super(DeepAtlasExperiment, self).__init__(config)
         self.device = torch.device(self.config.get('device', 'cuda'))
         cfg = self.config
+        refuse_patch(cfg, 'joint')
         if cfg['debug_mode']:
             print("Debug mode")
             cfg['print_batch_period'] = cfg['valid_epoch_period'] = 2

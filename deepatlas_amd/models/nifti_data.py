@@ -42,10 +42,26 @@ def shape_multiple(model_name):
     return 8 if str(model_name).startswith('UNet') else 1
 
 
-def check_shapes(datasets, models):
+def check_patch(patch, models):
+    """The patch geometry every net of `models` accepts: extents that are multiples of shape_multiple(model), 2 * overlap < size per axis."""
+    size, overlap = [int(v) for v in patch['size']], [int(v) for v in patch.get('overlap') or (0, 0, 0)]
+    text = 'x'.join(str(v) for v in size)
+    for m in models:
+        k = shape_multiple(m)
+        if any(v % k for v in size) or min(size) < 1:
+            raise ValueError('%s takes patches whose extents are multiples of %d: patch %s' % (m, k, text))
+    if any(o < 0 or 2 * o >= v for o, v in zip(overlap, size)):
+        raise ValueError('the tile overlap %s must satisfy 0 <= 2 * overlap < size on every axis of patch %s' % ('x'.join(str(o) for o in overlap), text))
+    return tuple(size)
+
+
+def check_shapes(datasets, models, patch=None):
     """Raise ValueError, listing names and shapes, unless every prepared volume of `datasets` has one common shape that every net of `models`
     accepts.  Runs at setup (a dataset that is not preloaded reads every volume once here) so that a bad volume does not surface later
-    inside collation or a kernel."""
+    inside collation or a kernel.
+    With `patch` (the experiment's config['patch']: 'size' and 'overlap', (z, y, x)) the volumes may differ in shape: the nets see patches.
+    Then every extent of every volume must be >= the patch's, the patch's extents multiples of shape_multiple(model) and 2 * overlap < size;
+    returns the patch size."""
     found = []
     for ds in datasets:
         if ds is None:
@@ -57,6 +73,13 @@ def check_shapes(datasets, models):
         raise ValueError('the list files name no volume')
     shapes = sorted(set(s for _, s in found))
     listing = ', '.join('%s %s' % (n, 'x'.join(str(v) for v in s)) for n, s in found)
+    if patch is not None:
+        size = check_patch(patch, models)
+        small = [(n, s) for n, s in found if any(v < w for v, w in zip(s, size))]
+        if small:
+            raise ValueError('volumes smaller than the patch %s on some axis: %s' % ('x'.join(str(v) for v in size),
+                                                                                      ', '.join('%s %s' % (n, 'x'.join(str(v) for v in s)) for n, s in small)))
+        return size
     if len(shapes) > 1:
         raise ValueError('the prepared volumes do not share one shape (resample / crop them to a common grid): ' + listing)
     for m in models:

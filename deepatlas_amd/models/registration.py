@@ -40,7 +40,7 @@ from torch.utils.data import DataLoader
 from .base import BaseExperiment
 from . import nifti_data
 from .joint import RegistrationStep, SIM_LOSSES, make_jac_penalty, make_ic_penalty
-from .segmentation import SegmentationExperiment
+from .segmentation import SegmentationExperiment, refuse_patch
 from ..lib import datasets as med_data
 from ..lib import evalMetrics as metrics
 from ..lib import affine as affine_lib
@@ -337,6 +337,7 @@ class RegistrationExperiment(BaseExperiment):
         super(RegistrationExperiment, self).__init__(config)
         self.device = torch.device(self.config.get('device', 'cuda'))
         cfg = self.config
+        refuse_patch(cfg, 'registration')
         if cfg['debug_mode']:
             print("Debug mode")
             cfg['print_batch_period'] = cfg['valid_epoch_period'] = 2

@@ -13,6 +13,10 @@ torch.distributed initialised the gradients are averaged with one flat-bucket al
 config['lambda_boundary'] (default 0: off) weights Kervadec's boundary loss as a second term of the step (lib/loss.py BoundaryLoss: signed
 distance maps built on the device from the batch's index labels, after any augmentation); config['boundary_settings'] optionally holds its
 `classes` and `spacing`.  Without the key, or with 0, nothing changes.
+config['patch'] (default None: off; parse_patch states its form) turns on patch training and tiled evaluation: a training batch is
+batch_size patches cropped on the device (lib/transforms.py BalancedRandomCrop / RandomCrop's uniform draw) from batch_size / per_volume
+volumes, cropped before config['augment'] acts; validation and test tile every volume with Partition, run the net over the tiles and assemble
+the argmax.  Volumes of different shapes then train together.  Without the key nothing changes.
 """
 import datetime
 import os
@@ -64,6 +68,55 @@ def boundary_name_suffix(cfg):
     return '_boundary%s' % lam if lam > 0 else ''
 
 
+PATCH_DEFAULTS = {'size': None, 'mode': 'balanced', 'threshold': 0.01, 'classes': None, 'per_volume': 1, 'overlap': [8, 8, 8], 'tile_batch': 4,
+                  'include_last': False}
+
+
+def parse_patch(spec):
+    """config['patch'] -> None (off) or the full dict {'size': [d, h, w], 'mode': 'balanced' | 'random', 'threshold': a float or a list (the
+    crops' thresholds), 'classes': None or a list of labels, 'per_volume': patches cropped from one volume, 'overlap': [d, h, w] of the
+    evaluation tiles, 'tile_batch': tiles per forward pass, 'include_last': the crop domain}.  Sizes are (z, y, x), like synthetic_shape; only
+    'size' is required.  The geometry against the nets and the volumes is checked at setup (nifti_data.check_shapes)."""
+    if spec is None:
+        return None
+    if not isinstance(spec, dict):
+        raise ValueError("config['patch'] must be None or a dict, got %r" % (spec,))
+    unknown = sorted(set(spec) - set(PATCH_DEFAULTS))
+    if unknown:
+        raise ValueError("config['patch'] takes %s, got %s" % (sorted(PATCH_DEFAULTS), ', '.join(repr(k) for k in unknown)))
+    out = dict(PATCH_DEFAULTS)
+    out.update({k: v for k, v in spec.items() if v is not None or k == 'classes'})
+    for key in ('size', 'overlap'):
+        v = out[key]
+        if v is None or len(v) != 3 or any(int(a) != a for a in v):
+            raise ValueError("config['patch'][%r] takes three integers (z, y, x), got %r" % (key, v))
+        out[key] = [int(a) for a in v]
+    if min(out['size']) < 1 or min(out['overlap']) < 0:
+        raise ValueError("config['patch']: size must be positive and overlap >= 0, got %r and %r" % (out['size'], out['overlap']))
+    if out['mode'] not in ('balanced', 'random'):
+        raise ValueError("config['patch']['mode'] %r: 'balanced' or 'random'" % (out['mode'],))
+    for key in ('per_volume', 'tile_batch'):
+        if isinstance(out[key], bool) or int(out[key]) != out[key] or int(out[key]) < 1:
+            raise ValueError("config['patch'][%r] must be an integer >= 1, got %r" % (key, out[key]))
+        out[key] = int(out[key])
+    out['threshold'] = [float(t) for t in out['threshold']] if np.ndim(out['threshold']) else float(out['threshold'])
+    out['classes'] = None if out['classes'] is None else list(out['classes'])
+    out['include_last'] = bool(out['include_last'])
+    return out
+
+
+def refuse_patch(cfg, what):
+    """Patch training is the segmentation experiment's alone: the `what` experiment raises when given config['patch']."""
+    if cfg.get('patch') is not None:
+        raise ValueError("config['patch'] (patch training and tiled evaluation) is not implemented for the %s experiment" % what)
+
+
+def patch_name_suffix(cfg):
+    """'_patch<d>x<h>x<w>' for an experiment name in patch mode, '' otherwise (names of runs without it stay as they were)."""
+    patch = cfg.get('patch')
+    return '_patch%s' % 'x'.join(str(int(v)) for v in patch['size']) if patch is not None else ''
+
+
 class SegmentationExperiment(BaseExperiment):
     def __init__(self, config):
         super(SegmentationExperiment, self).__init__(config)
@@ -75,6 +128,10 @@ class SegmentationExperiment(BaseExperiment):
         self.lambda_boundary, self.boundary_settings = check_boundary_term(cfg)
         self.boundary_criterion = None
         self.last_boundary = None                                # the step's boundary term (a device scalar) when the term is on
+        self.patch = parse_patch(cfg.get('patch'))
+        self.crop = self.partition = None
+        if self.patch is not None:
+            self.setup_patch()
         self.exp_name = self.experiment_name(cfg)
         # <log_dir>/<experiment name | "debug_seg">/<seed>: the directory layout the reference's checkpoints and resume_dir use
         # (models/segmentation.py:40-42), so runs of either code base can resume each other's checkpoints
@@ -91,7 +148,8 @@ class SegmentationExperiment(BaseExperiment):
     @staticmethod
     def experiment_name(cfg):
         """The run's name, field by field as the reference composes it (models/segmentation.py:27-38) -- it is part of the checkpoint path:
-        Seg_<model>[_bias][_BN]_<data dir name>_<n>samples_batch_<b>_<e>epochs_<loss>_<weighting>_lr_<lr>[_scheduler_<mode>][_boundary<lambda_boundary>]."""
+        Seg_<model>[_bias][_BN]_<data dir name>_<n>samples_batch_<b>_<e>epochs_<loss>_<weighting>_lr_<lr>[_scheduler_<mode>][_boundary<lambda_boundary>]
+        [_patch<d>x<h>x<w>]."""
         ms = cfg['model_settings']
         parts = ['Seg_', cfg['model']]
         if ms['bias']:
@@ -104,9 +162,32 @@ class SegmentationExperiment(BaseExperiment):
         if cfg['lr_mode'] != 'const':
             parts.append('_scheduler_%s' % cfg['lr_mode'])
         parts.append(boundary_name_suffix(cfg))
+        parts.append(patch_name_suffix(cfg))
         return ''.join(str(v) for v in parts)
 
     # ---- setup ---------------------------------------------------------------------------------
+    def setup_patch(self):
+        """The crop transform of the training batches and the tiling of the evaluation volumes, from config['patch'] ((z, y, x) sizes are
+        flipped to the (x, y, z) the two classes take)."""
+        cfg, patch = self.config, self.patch
+        if cfg['batch_size'] % patch['per_volume'] != 0:
+            raise ValueError("config['batch_size'] = %d patches is no multiple of config['patch']['per_volume'] = %d"
+                             % (cfg['batch_size'], patch['per_volume']))
+        if cfg['model_settings'].get('in_channel', 1) != 1:
+            raise ValueError("config['patch']: the tiled evaluation takes single-channel images")
+        nifti_data.check_patch(patch, [cfg['model']])
+        size_xyz = tuple(int(v) for v in reversed(patch['size']))
+        if patch['mode'] == 'random':
+            self.crop = med_transforms.BalancedRandomCrop(size_xyz, threshold=0.0, classes=[None], patches=patch['per_volume'],
+                                                          include_last=patch['include_last'])
+        else:
+            thr = patch['threshold']
+            if patch['classes'] is None:
+                thr = tuple(thr) if isinstance(thr, list) else float(thr)
+            self.crop = med_transforms.BalancedRandomCrop(size_xyz, threshold=thr, classes=patch['classes'], patches=patch['per_volume'],
+                                                          include_last=patch['include_last'])
+        self.partition = med_transforms.Partition(size_xyz, tuple(int(v) for v in reversed(patch['overlap'])))
+
     def setup_log(self):
         if parallel.rank() != 0:
             return
@@ -123,26 +204,31 @@ class SegmentationExperiment(BaseExperiment):
             return self.setup_nifti_data()
         dataset = med_data.get_seg_dataset(self.config['data'])
         shape = self.config['synthetic_shape']
+        if self.patch is not None and any(int(v) < w for v, w in zip(shape, self.patch['size'])):
+            raise ValueError('the synthetic volumes %s are smaller than the patch %s on some axis'
+                             % ('x'.join(str(int(v)) for v in shape), 'x'.join(str(w) for w in self.patch['size'])))
         training_data = dataset(self.config["num_samples"] * 2, shape, self.config['n_classes'], seed=self.config['random_seed'])
         sampler = parallel.distributed_sampler(training_data, shuffle=True, seed=self.config['random_seed'])
-        self.training_data_loader = DataLoader(training_data, batch_size=self.config['batch_size'], shuffle=sampler is None,
-                                               sampler=sampler, num_workers=0)
+        self.training_data_loader = DataLoader(training_data, batch_size=self.config['batch_size'] if self.patch is None else 1,
+                                               shuffle=sampler is None, sampler=sampler, num_workers=0)
         validation_data = dataset(self.config.get('num_valid_samples', 2), shape, self.config['n_classes'],
                                   seed=self.config['random_seed'] + 1000)
         self.validation_data_loader = DataLoader(validation_data, batch_size=1, shuffle=False, num_workers=0)
 
     def setup_nifti_data(self):
         """models/segmentation.py:54-79, 241-251: the training list's first num_samples * 2 scans, the validation and test lists whole; every
-        prepared volume must have the one shape the net accepts (nifti_data.check_shapes raises otherwise)."""
+        prepared volume must have the one shape the net accepts (nifti_data.check_shapes raises otherwise).  With config['patch'] the volumes may
+        differ in shape (each must hold a patch) and the training loader yields one volume at a time."""
         cfg = self.config
         training_data = nifti_data.seg_dataset(cfg, 'training_list_file', 'data_dir', n_samples=cfg['num_samples'] * 2)
         validation_data = nifti_data.seg_dataset(cfg, 'validation_list_file', 'valid_data_dir')
         testing_data = nifti_data.seg_dataset(cfg, 'testing_list_file', 'valid_data_dir')
         if training_data is None or validation_data is None:
             raise ValueError("config['data'] = %r needs config['training_list_file'] and config['validation_list_file']" % (cfg['data'],))
-        nifti_data.check_shapes([training_data, validation_data, testing_data], [cfg['model']])
+        nifti_data.check_shapes([training_data, validation_data, testing_data], [cfg['model']], patch=self.patch)
         sampler = parallel.distributed_sampler(training_data, shuffle=True, seed=cfg['random_seed'])
-        self.training_data_loader = DataLoader(training_data, batch_size=cfg['batch_size'], shuffle=sampler is None, sampler=sampler, num_workers=0)
+        self.training_data_loader = DataLoader(training_data, batch_size=cfg['batch_size'] if self.patch is None else 1, shuffle=sampler is None,
+                                               sampler=sampler, num_workers=0)
         self.validation_data_loader = DataLoader(validation_data, batch_size=1, shuffle=False, num_workers=0)
         if testing_data is not None:
             self.testing_data_loader = DataLoader(testing_data, batch_size=1, shuffle=False, num_workers=0)
@@ -234,16 +320,37 @@ class SegmentationExperiment(BaseExperiment):
             sample = t(sample)
         return sample['image'], sample['segmentation']
 
-    def train_one_epoch(self):
-        running_loss = running_boundary = 0.0
-        iters_per_epoch = max(self.config['samples_per_epoch'] // (self.config['batch_size'] * parallel.world_size()), 1)
-        train_data_iter = None
-        for i in range(iters_per_epoch):
+    def patch_batch(self, train_data_iter):
+        """config['batch_size'] patches: per_volume crops from each of batch_size / per_volume volumes, drawn from the loader one after another
+        (a loader may hand over several volumes of one shape at once).  Returns (images, truths, the loader's iterator)."""
+        need = self.config['batch_size'] // self.patch['per_volume']
+        imgs, segs, have = [], [], 0
+        while have < need:
             try:
                 images, truths, name = next(train_data_iter)
             except (StopIteration, TypeError):
                 train_data_iter = iter(self.training_data_loader)
                 images, truths, name = next(train_data_iter)
+            images, truths = images[:need - have], truths[:need - have]
+            out = self.crop({'image': images.to(self.device, non_blocking=True), 'segmentation': truths.to(self.device, non_blocking=True)})
+            imgs.append(out['image'])
+            segs.append(out['segmentation'])
+            have += int(images.shape[0])
+        return (imgs[0], segs[0], train_data_iter) if len(imgs) == 1 else (torch.cat(imgs, 0), torch.cat(segs, 0), train_data_iter)
+
+    def train_one_epoch(self):
+        running_loss = running_boundary = 0.0
+        iters_per_epoch = max(self.config['samples_per_epoch'] // (self.config['batch_size'] * parallel.world_size()), 1)
+        train_data_iter = None
+        for i in range(iters_per_epoch):
+            if self.patch is not None:
+                images, truths, train_data_iter = self.patch_batch(train_data_iter)
+            else:
+                try:
+                    images, truths, name = next(train_data_iter)
+                except (StopIteration, TypeError):
+                    train_data_iter = iter(self.training_data_loader)
+                    images, truths, name = next(train_data_iter)
             self.global_step = (self.current_epoch - 1) * iters_per_epoch + (i + 1) * self.config['batch_size']
             if self.augment:
                 images, truths = self.augment_batch(images, truths)
@@ -264,8 +371,26 @@ class SegmentationExperiment(BaseExperiment):
                         self.writer.add_scalar('learning_rate', self.optimizer.param_groups[0]['lr'], global_step=self.global_step)
                 running_loss = running_boundary = 0.0
 
+    def predict_tiled(self, images):
+        """Label maps N x D x H x W (uint8) of a batch N x 1 x D x H x W in patch mode: per volume Partition's reflect-padded overlap tiles of
+        the patch size, the net over chunks of tile_batch tiles, the first-max argmax of every tile, and assemble's core copy."""
+        out = []
+        tb = self.patch['tile_batch']
+        for n in range(images.shape[0]):
+            vol = images[n, 0]
+            tiles = self.partition({'image': vol, 'segmentation': vol})['image']                     # T x 1 x tz x ty x tx
+            blank = torch.zeros((min(tb, tiles.shape[0]),) + tuple(tiles.shape[2:]), dtype=torch.uint8, device=tiles.device)
+            labs = []
+            for k in range(0, tiles.shape[0], tb):
+                logits = self.model(tiles[k:k + tb])
+                labs.append(metrics.eval_dice_counts(logits, blank[:logits.shape[0]])[1])
+            out.append(self.partition.assemble(torch.cat(labs, 0)))
+        return torch.stack(out, 0)
+
     def eval(self, dataloader):
         """models/segmentation.py:179-201; Dice from exact integer counts computed on the device.
+        With config['patch'] the label map of a volume is predict_tiled's (tiles, net, argmax, assemble) and the counts are
+        ops.label_overlap_counts of it; everything below acts on that map as it acts on the whole-volume argmax.
         With config['postprocess'] set (lib/evalMetrics.py parse_postprocess: 'largest_cc', or a dict with mode / connectivity / min_size) the
         argmax label map is additionally cleaned on the device (ops.keep_largest_component / remove_small_components) and scored again; those
         numbers go to self.eval_extra (post_dice_per_class, post_dice_avg, components_per_class, removed_frac).  The return value, and with it
@@ -279,6 +404,7 @@ class SegmentationExperiment(BaseExperiment):
         surf = metrics.parse_surface_metrics(self.config.get('surface_metrics'))
         surf_raw, surf_post = [], []                                               # per batch: the dicts of metrics.surface_distances
         n_class = self.config["n_classes"]
+        tiled = getattr(self, 'patch', None) is not None                           # (the joint experiment borrows this method for a view without it)
         self.eval_extra = {}
         with torch.no_grad():
             self.model.eval()
@@ -289,10 +415,19 @@ class SegmentationExperiment(BaseExperiment):
             n_vol = 0
             pred = images = truths = None
             for j, (images, truths, name) in enumerate(dataloader):
-                pred = self.model(images.to(self.device))
-                if post is None and surf is None:
+                if tiled:
+                    truth = truths.to(self.device)
+                    lab = self.predict_tiled(images.to(self.device))
+                    counts = ops.label_overlap_counts(lab, truth, n_class)
+                    d = metrics.dice_from_counts(counts)[:, 1:]
+                    if surf is not None:
+                        surf_raw.append(metrics.surface_distances(lab, truth, n_class, **surf))
+                    pred = lab
+                elif post is None and surf is None:
+                    pred = self.model(images.to(self.device))
                     d = metrics.metricEval('dice', pred, truths.to(self.device))   # [N][C-1]
                 else:
+                    pred = self.model(images.to(self.device))
                     truth = truths.to(self.device)
                     counts, lab = metrics.eval_dice_counts(pred, truth)            # the counts metricEval('dice', ...) is computed from
                     d = metrics.dice_from_counts(counts)[:, 1:]

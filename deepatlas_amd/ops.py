@@ -3416,3 +3416,145 @@ def label_lut(labels, lut):
     with torch.cuda.device(v.device):
         call('da_label_lut', ptr(v), PREPROCESS_DTYPE_CODE[v.dtype], ptr(out), v.numel(), ptr(t), int(table.shape[0]), stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# random crops (csrc/crop.hip; lib/transforms.py:322-505)
+# ------------------------------------------------------------------------------------------------
+CROP_LABEL_DTYPE_CODE = {torch.uint8: 3, torch.int32: 4, torch.int64: 5}
+CROP_STREAM = 4                     # DA_CROP_STREAM (csrc/counter_hash.h): the hash stream of the sampler's draws
+CROP_MAX_DRAWS = 65536
+CROP_MAX_ROW = 32768                # longest row (W) the row pass stages in LDS
+
+
+def _crop_labels(labels):
+    if not torch.is_tensor(labels) or labels.dim() != 4:
+        raise ValueError('labels must be an N x D x H x W tensor')
+    if labels.dtype not in CROP_LABEL_DTYPE_CODE:
+        raise ValueError('labels dtype %s: uint8, int32 or int64' % labels.dtype)
+    if labels.numel() == 0:
+        raise ValueError('labels is empty')
+    nat.require_cuda(labels)
+    return labels.contiguous()
+
+
+def _crop_window(window, extents):
+    if len(window) != 3:
+        raise ValueError('window takes three values (wd, wh, ww)')
+    w = tuple(int(v) for v in window)
+    if any(a < 1 or a > s for a, s in zip(w, extents)):
+        raise ValueError('window %s must lie in 1..extent of a %s volume' % (w, tuple(extents)))
+    return w
+
+
+def _int3_array(v):
+    import ctypes
+    arr = (ctypes.c_int * 3)(int(v[0]), int(v[1]), int(v[2]))
+    return arr, ctypes.cast(arr, ctypes.c_void_p)
+
+
+def crop_domain(extents, window, include_last=False):
+    """Starts per axis of the crop sampler: max(S - w, 1) (what random_3d_coordinates draws: randint's upper end is exclusive, so the last
+    start is never used), or S - w + 1 with include_last."""
+    return tuple((s - w + 1) if include_last else max(s - w, 1) for s, w in zip(extents, window))
+
+
+def crop_conditions(classes, min_counts):
+    """Host half of sample_crop_starts: the draws' (class, min_count) pairs -> (conds int32 [Q][2] sorted by class then min_count, draw_cond
+    int32 [P]: the row of conds of each draw, -1 for class None).  Draws that share a class sit next to each other and share its passes."""
+    import numpy as np
+    classes, min_counts = list(classes), list(min_counts)
+    if len(classes) != len(min_counts) or not 1 <= len(classes) <= CROP_MAX_DRAWS:
+        raise ValueError('classes and min_counts take one entry per draw, 1..%d draws' % CROP_MAX_DRAWS)
+    pairs = []
+    for c, m in zip(classes, min_counts):
+        if c is None:
+            pairs.append(None)
+            continue
+        c, m = int(c), int(0 if m is None else m)
+        if not -2 ** 31 <= c < 2 ** 31 or not 0 <= m < 2 ** 31:
+            raise ValueError('a class must fit int32 and a min_count lie in 0..2^31 - 1, got (%d, %d)' % (c, m))
+        pairs.append((c, m))
+    uniq = sorted(set(p for p in pairs if p is not None))
+    index = {p: q for q, p in enumerate(uniq)}
+    conds = np.asarray(uniq, dtype=np.int32).reshape(-1, 2)
+    draw_cond = np.asarray([-1 if p is None else index[p] for p in pairs], dtype=np.int32)
+    return conds, draw_cond
+
+
+def window_label_counts(labels, window, cls):
+    """Number of voxels equal to `cls` in every window of a label batch: labels N x D x H x W (uint8 / int32 / int64, views accepted),
+    window (wd, wh, ww) -> int32 N x (D - wd + 1) x (H - wh + 1) x (W - ww + 1), exact.  Three separable passes on the device."""
+    lab = _crop_labels(labels)
+    N, D, H, W = (int(s) for s in lab.shape)
+    win = _crop_window(window, (D, H, W))
+    if D * H * W >= 2 ** 31:
+        raise ValueError('a sample has %d voxels: the crop kernels take fewer than 2^31' % (D * H * W))
+    out = torch.empty((N, D - win[0] + 1, H - win[1] + 1, W - win[2] + 1), dtype=torch.int32, device=lab.device)
+    keep, wp3 = _int3_array(win)
+    with torch.cuda.device(lab.device):
+        wp, wn = _ws(nat.lib().da_window_label_counts_ws_bytes(N, D, H, W, wp3), lab)
+        call('da_window_label_counts', ptr(lab), CROP_LABEL_DTYPE_CODE[lab.dtype], N, D, H, W, wp3, int(cls), ptr(out), wp, wn, stream())
+    return out
+
+
+def sample_crop_starts(labels, window, classes, min_counts, seed, sample0=0, include_last=False):
+    """P crop starts per sample, drawn on the device with no host synchronisation.  labels N x D x H x W; classes / min_counts: one entry
+    per draw (class None: no condition).  Per axis the domain is max(S - w, 1) starts (S - w + 1 with include_last); the admissible set A of
+    a draw holds the starts of the domain, in raster order, whose window has >= min_count voxels of the class; with bits =
+    hash(seed, (sample0 + n) * 65536 + p, CROP_STREAM) the result is element (bits * |A|) >> 32 of A.  An empty A yields the start with the
+    largest count (first in raster order) and info[..., 0] = 0.  Returns (starts int32 N x P x 3 (z, y, x), info int32 N x P x 2 =
+    (|A|, count at the chosen start; -1 for an unconditioned draw)), both on the device.  Sample n of a batch with sample0 = 0 equals sample
+    0 of a call with sample0 = n."""
+    lab = _crop_labels(labels)
+    N, D, H, W = (int(s) for s in lab.shape)
+    win = _crop_window(window, (D, H, W))
+    if D * H * W >= 2 ** 31:
+        raise ValueError('a sample has %d voxels: the crop kernels take fewer than 2^31' % (D * H * W))
+    conds, draw_cond = crop_conditions(classes, min_counts)
+    P = int(draw_cond.shape[0])
+    sample0 = int(sample0)
+    if sample0 < 0 or sample0 + N >= 2 ** 31:
+        raise ValueError('sample0 must be >= 0 and sample0 + N below 2^31')
+    dc = _const_tensor(draw_cond, lab.device)
+    starts = torch.empty((N, P, 3), dtype=torch.int32, device=lab.device)
+    info = torch.empty((N, P, 2), dtype=torch.int32, device=lab.device)
+    keep, wp3 = _int3_array(win)
+    Q = int(conds.shape[0])
+    carr = nat.ctypes.cast((nat.ctypes.c_int * max(2 * Q, 1))(*[int(v) for v in conds.reshape(-1)]), nat.ctypes.c_void_p)
+    with torch.cuda.device(lab.device):
+        wp, wn = (None, 0) if Q == 0 else _ws(nat.lib().da_crop_sample_starts_ws_bytes(N, D, H, W, wp3, 1 if include_last else 0), lab)
+        call('da_crop_sample_starts', ptr(lab), CROP_LABEL_DTYPE_CODE[lab.dtype], N, D, H, W, wp3, 1 if include_last else 0, P, carr, Q,
+             ptr(dc), int(seed) & 0xFFFFFFFF, sample0, ptr(starts), ptr(info), wp, wn, stream())
+    return starts, info
+
+
+def crop_gather(image, labels, starts, window):
+    """The crops of a batch at device-resident starts, one launch: image N x C x D x H x W float32, labels N x D x H x W (1-, 4- or 8-byte
+    integers) or None, starts int32 N x P x 3 (z, y, x) -> ((N P) x C x wd x wh x ww, (N P) x wd x wh x ww in the labels' dtype), sample-major.
+    A start outside [0, S - w] is clamped into it inside the kernel."""
+    nat.require_cuda(image, labels, starts)
+    if image.dim() != 5 or image.dtype != torch.float32:
+        raise ValueError('image must be N x C x D x H x W float32')
+    img = image.contiguous()
+    N, C, D, H, W = (int(s) for s in img.shape)
+    win = _crop_window(window, (D, H, W))
+    if D * H * W >= 2 ** 31:
+        raise ValueError('a sample has %d voxels: the crop kernels take fewer than 2^31' % (D * H * W))
+    if starts.dim() != 3 or starts.shape[0] != N or starts.shape[2] != 3 or starts.dtype != torch.int32 or not 1 <= starts.shape[1] <= CROP_MAX_DRAWS:
+        raise ValueError('starts must be int32 N x P x 3 with N = %d and 1 <= P <= %d' % (N, CROP_MAX_DRAWS))
+    st = starts.contiguous()
+    P = int(st.shape[1])
+    lab = lab_out = None
+    lb = 0
+    if labels is not None:
+        if tuple(labels.shape) != (N, D, H, W) or labels.dtype.is_floating_point or labels.element_size() not in (1, 4, 8):
+            raise ValueError('labels must be integers of 1, 4 or 8 bytes, N x D x H x W = %s' % ((N, D, H, W),))
+        lab = labels.contiguous()
+        lb = lab.element_size()
+        lab_out = torch.empty((N * P,) + win, dtype=lab.dtype, device=lab.device)
+    out = torch.empty((N * P, C) + win, dtype=torch.float32, device=img.device)
+    keep, wp3 = _int3_array(win)
+    with torch.cuda.device(img.device):
+        call('da_crop_gather', ptr(img), ptr(out), C, ptr(lab), ptr(lab_out), lb, ptr(st), N, P, D, H, W, wp3, stream())
+    return out, lab_out

@@ -578,6 +578,38 @@ int da_bilateral3d(const float* img, float* out, const float* domain_w, const fl
 int da_intensity_augment(const float* img, float* out, const float* params, const float* bias_coef, int order, int gx, int gy, int gz,
                          int sample0, int N, int C, int D, int H, int W, void* stream);
 
+/* ---- random crops (crop.hip; lib/transforms.py:322-505 RandomCrop, BalancedRandomCrop, random_3d_coordinates) ----------------------
+ * labels [N][D][H][W], label_dtype 3 u8, 4 i32, 5 i64; window3 (host) = {wd, wh, ww}, 1 <= w <= extent.  Every entry checks its arguments
+ * before any launch: DA_ERR_BADARG also for D H W >= 2^31, DA_ERR_UNSUPPORTED for W > 32768 (a row's bits are staged in LDS).  No autograd.
+ * Separate launches in stream order, no workgroup waits for another; the only atomic is an integer maximum: bit-identical results.
+ *
+ * da_window_label_counts (replaces the count of :381, :455 and :473, np.sum(seg_crop == c), for every window at once):
+ * counts int32 [N][D - wd + 1][H - wh + 1][W - ww + 1], entry [n][z][y][x] = #{labels[n][z .. z + wd)[y .. y + wh)[x .. x + ww) == cls}.
+ * Three separable passes: along W per row (wave ballots, a prefix sum over the words' popcounts, uint16), then running sums along H and D
+ * with lanes along x (int32).  Workspace: the two intermediate tensors.
+ *
+ * da_crop_sample_starts (replaces the rejection loops :437-475 and random_3d_coordinates :497-505): P draws per sample.  Domain per axis:
+ * max(S - w, 1) starts (randint's exclusive upper end: the last start is never used), or S - w + 1 with include_last.  conds (host)
+ * int32 [n_conds][2] = {class, min_count >= 0}, equal classes adjacent (they share the row and H passes); draw_cond (device) int32 [P]: the
+ * condition of each draw, or -1 for an unconditioned draw.  A = the starts of the domain, in raster order, whose count of the class is
+ * >= min_count (the whole domain for an unconditioned draw); bits = the counter hash (csrc/counter_hash.h) of seed, counter (sample0 + n) * 65536 + p and stream DA_CROP_STREAM;
+ * k = (bits * |A|) >> 32; the result is the k-th element of A.  If A is empty: the start with the largest count, the first in raster order.
+ * starts int32 [N][P][3] (z, y, x); info int32 [N][P][2] = {|A|, count at the chosen start (-1 for an unconditioned draw)}.  Workspace: the
+ * uint16 row sums and int32 H sums over the domain, one bit per start, one count per z plane; the count tensor itself is never built.
+ *
+ * da_crop_gather (replaces RegionOfInterestImageFilter, :350-351, :366-368, :384, :429-430, :480-483): img [N][C][D][H][W] fp32 ->
+ * img_out [N P][C][wd][wh][ww], labels -> labels_out [N P][wd][wh][ww] of label_bytes (1, 4, 8), sample-major, one launch; img or labels
+ * may be NULL.  starts (device) as above; a start outside [0, S - w] is clamped into it in the kernel. */
+size_t da_window_label_counts_ws_bytes(int N, int D, int H, int W, const int* window3);
+int da_window_label_counts(const void* labels, int label_dtype, int N, int D, int H, int W, const int* window3, long long cls,
+                           int* counts, void* ws, size_t ws_bytes, void* stream);
+size_t da_crop_sample_starts_ws_bytes(int N, int D, int H, int W, const int* window3, int include_last);
+int da_crop_sample_starts(const void* labels, int label_dtype, int N, int D, int H, int W, const int* window3, int include_last,
+                          int P, const int* conds, int n_conds, const int* draw_cond, unsigned int seed, int sample0,
+                          int* starts, int* info, void* ws, size_t ws_bytes, void* stream);
+int da_crop_gather(const float* img, float* img_out, int C, const void* labels, void* labels_out, int label_bytes, const int* starts,
+                   int N, int P, int D, int H, int W, const int* window3, void* stream);
+
 /* ---- LNCC similarity (lib/loss.py:589-617 VoxelMorphLNCC = registry 'lncc', and :512-586 LNCCLoss) -----
  * I, J: [N][D][H][W] fp32 (single channel); all-ones F^3 window with dilation `dil` and stride `stride` (1, 1 for VoxelMorphLNCC),
  * valid padding; loss = 1 - mean(cross^2 / (Ivar Jvar + eps)).  Output extent per axis: (L - dil (F-1) - 1) / stride + 1.

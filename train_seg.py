@@ -3,7 +3,8 @@ train_seg.py:10-93) with its three shipped bugs fixed: the em-da
 positional './data' / './logs' defaults, and the undefined args.leaf.  Device selection is explicit.  The data
 source is the synthetic volume generator, or with --data NAME the reference's NIfTI list-file datasets read without SimpleITK (--data-dir,
 --train-list, --valid-list, --test-list) and prepared on the device (--voxel-size, --rescale-percentiles, --normalize, --ignore-labels,
---crop-size)."""
+--crop-size).  --patch-size D H W trains on patches cropped on the device and evaluates tile by tile (--patch-mode, --patch-threshold,
+--patches-per-volume, --tile-overlap, --tile-batch)."""
 import argparse
 import os
 
@@ -90,6 +91,19 @@ def build_config(args):
     # opt-in boundary loss beside the region loss (lib/loss.py BoundaryLoss); absent = the step as it was, and no key in the config
     if config.get('lambda_boundary') is None:
         config.pop('lambda_boundary', None)
+    # opt-in patch training and tiled evaluation (models/segmentation.py parse_patch); absent = whole volumes, and no key in the config
+    patch_size = config.pop('patch_size', None)
+    patch_mode = config.pop('patch_mode', None)
+    patch_threshold = config.pop('patch_threshold', None)
+    per_volume = config.pop('patches_per_volume', None)
+    tile_overlap = config.pop('tile_overlap', None)
+    tile_batch = config.pop('tile_batch', None)
+    if patch_size is not None:
+        config['patch'] = {'size': list(patch_size), 'mode': patch_mode or 'balanced', 'threshold': 0.01 if patch_threshold is None else patch_threshold,
+                           'classes': None, 'per_volume': per_volume or 1, 'overlap': list(tile_overlap) if tile_overlap is not None else [8, 8, 8],
+                           'tile_batch': tile_batch or 4, 'include_last': False}
+    elif any(v is not None for v in (patch_mode, patch_threshold, per_volume, tile_overlap, tile_batch)):
+        raise ValueError('--patch-mode, --patch-threshold, --patches-per-volume, --tile-overlap and --tile-batch need --patch-size')
     if not config.get('matrix_precision'):                # (--matrix-precision; not a key of the reference's config: absent = the package default, 'fp32_split')
         config.pop('matrix_precision', None)
     return apply_data_arguments(config)
@@ -142,6 +156,17 @@ def main(argv=None):
     parser.add_argument('--lambda-boundary', type=float, default=None, metavar='W',
                         help="add W x the boundary loss (Kervadec et al.: softmax probability times the signed distance to the ground truth, the "
                              "distance maps rebuilt on the device from every batch's labels) to the step's loss; 0 or absent: off")
+    parser.add_argument('--patch-size', nargs=3, type=int, default=None, metavar=('D', 'H', 'W'),
+                        help='train on patches of this size cropped on the device (volumes of different shapes then train together) and evaluate '
+                             'every volume tile by tile; multiples of 8 for the U-Nets')
+    parser.add_argument('--patch-mode', default=None, choices=['balanced', 'random'],
+                        help="'balanced' (default): BalancedRandomCrop's cycle over the classes; 'random': uniform starts")
+    parser.add_argument('--patch-threshold', type=float, default=None, metavar='SHARE',
+                        help='share of the class a balanced patch must exceed (default 0.01)')
+    parser.add_argument('--patches-per-volume', type=int, default=None, metavar='P', help='patches cropped from one loaded volume (default 1); divides the batch size')
+    parser.add_argument('--tile-overlap', nargs=3, type=int, default=None, metavar=('D', 'H', 'W'),
+                        help='overlap of the evaluation tiles on every side (default 8 8 8); 2 x overlap < patch size')
+    parser.add_argument('--tile-batch', type=int, default=None, metavar='T', help='evaluation tiles per forward pass (default 4)')
     add_data_arguments(parser, with_preload=False)              # (--preload is the reference's own flag, above)
     args = parser.parse_args(argv)
     exp = SegmentationExperiment(build_config(args))
