@@ -41,6 +41,77 @@ def _to_device_array(a):
     return a.to(_device()).contiguous()
 
 
+_SIGNED_OF = {1: torch.int8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
+
+
+def _is_integer(dtype):
+    return not (dtype.is_floating_point or dtype.is_complex)
+
+
+def _is_unsigned(dtype):
+    return dtype in (torch.uint8, torch.uint16, torch.uint32, torch.uint64)
+
+
+def _clamp_source(a):
+    """numpy array / tensor / SimpleITK image -> contiguous device tensor in one of da_clamp01_to_f32's five dtypes whose clamp-then-cast equals the
+    clamp of `a` IN ITS OWN DTYPE followed by the cast to float32 (the numpy original).  Every conversion is exact: float16 / bfloat16 widen; bool,
+    int8 and uint16 widen; the integer types no kernel dtype holds (uint32, int64, uint64) are clamped to {0, 1} BEFORE they are narrowed -- in numpy
+    ahead of the upload for an array, on the tensor's device otherwise, where an unsigned type is read through its signed view (its clamp to [0, 1] is
+    `x != 0`; torch implements neither clamp nor comparisons for the wide unsigned types)."""
+    if not torch.is_tensor(a) and not isinstance(a, np.ndarray):
+        try:                                         # a SimpleITK image, when the module is present
+            import SimpleITK as sitk
+            a = sitk.GetArrayFromImage(a)
+        except ImportError:
+            a = np.asarray(a)
+    if isinstance(a, np.ndarray):
+        if a.dtype.kind in 'iu' and a.dtype.itemsize >= 4 and a.dtype != np.int32:
+            a = np.clip(a, 0, 1).astype(np.uint8)
+        elif a.dtype.kind not in 'biuf':
+            raise ValueError('SitkToTensor: an image of dtype %s has no clamp to [0, 1]' % a.dtype)
+        a = torch.from_numpy(np.ascontiguousarray(a))
+    if a.dtype in _DTYPE_CODE:
+        return a.to(_device()).contiguous()
+    if a.dtype.is_complex:
+        raise ValueError('SitkToTensor: an image of dtype %s has no clamp to [0, 1]' % a.dtype)
+    if a.dtype.is_floating_point:                    # float16, bfloat16
+        return a.to(_device()).contiguous().to(torch.float64)
+    a = a.contiguous()
+    if a.dtype == torch.bool:
+        return a.to(_device()).to(torch.uint8)
+    if a.dtype == torch.int8:
+        return a.to(_device()).to(torch.int16)
+    if a.dtype == torch.uint16:
+        return a.view(torch.int16).to(_device()).to(torch.int32) & 0xFFFF
+    if _is_unsigned(a.dtype):                        # uint32, uint64
+        return (a.view(_SIGNED_OF[a.element_size()]).to(_device()) != 0).to(torch.uint8)
+    return a.to(_device()).clamp(0, 1).to(torch.uint8)          # int64
+
+
+def _exact_for_copy(t, what, as_float=False):
+    """A device tensor `t` in a dtype the copy kernels move (4 bytes per element, or 1) that holds exactly t's integer values, or ValueError naming the
+    dtype: there is no silent wrap.  4-byte tensors pass as they are, 1-byte ones too unless as_float (an image: float32, exact).  2-byte integers
+    widen to int32.  8-byte integers become int32 when every value fits int32 (as_float: float32 when every magnitude is at most 2^24), which costs one
+    min / max read-back.  Floating types of other widths go to float32, the rounding SitkToTensor's cast applies as well."""
+    if t.element_size() == 4 or (t.element_size() == 1 and not as_float):
+        return t
+    if t.dtype.is_complex:
+        raise ValueError('%s: dtype %s is not supported' % (what, t.dtype))
+    if t.dtype.is_floating_point:
+        return t.float()
+    if t.element_size() == 2:
+        t = t.to(torch.int32) if t.dtype == torch.int16 else t.contiguous().view(torch.int16).to(torch.int32) & 0xFFFF
+    elif t.element_size() == 8:
+        s = t if t.dtype == torch.int64 else t.contiguous().view(torch.int64)
+        lo, hi = (int(s.min()), int(s.max())) if s.numel() else (0, 0)
+        lo_ok, hi_ok = (-2 ** 24, 2 ** 24) if as_float else (-2 ** 31, 2 ** 31 - 1)
+        if (t.dtype == torch.uint64 and lo < 0) or lo < lo_ok or hi > hi_ok:
+            raise ValueError('%s: the %s values do not all fit %s exactly (the tensor spans [%d, %d] read as int64); convert it yourself'
+                             % (what, t.dtype, 'float32' if as_float else 'int32', lo, hi))
+        t = s.to(torch.int32)
+    return t.float() if as_float else t
+
+
 def _int3(v):
     arr = (ctypes.c_int * 3)(int(v[0]), int(v[1]), int(v[2]))
     return arr, ctypes.cast(arr, ctypes.c_void_p)
@@ -72,9 +143,7 @@ class SitkToTensor(object):
     uint8 (D x H x W).  The clamp compares in the source dtype and then casts, like the numpy original; one kernel, on the device."""
 
     def __call__(self, sample):
-        img = _to_device_array(sample['image'])
-        if img.dtype not in _DTYPE_CODE:
-            img = img.to(torch.float64 if img.dtype.is_floating_point else torch.int32)
+        img = _clamp_source(sample['image'])
         out = torch.empty(img.shape, dtype=torch.float32, device=img.device)
         call('da_clamp01_to_f32', ptr(img), _DTYPE_CODE[img.dtype], ptr(out), img.numel(), stream())
         sample['image'] = out.unsqueeze(0)
@@ -85,7 +154,8 @@ class SitkToTensor(object):
 
 class CropTensor(object):
     """lib/transforms.py:124-158: crop_size [z, y, x] (both sides) or [z_lo, y_lo, x_lo, z_hi, y_hi, x_hi] voxels off a C x D x H x W
-    image and its D x H x W segmentation, as fresh contiguous device tensors from one copy kernel."""
+    image and its D x H x W segmentation, as fresh contiguous device tensors from one copy kernel.  Every integer dtype keeps its values (and
+    8-byte integers their dtype); float64 / float16 come back as float32."""
 
     def __init__(self, crop_size):
         crop_size = list(crop_size)
@@ -101,12 +171,16 @@ class CropTensor(object):
         D, H, W = size
         Do, Ho, Wo = D - c[0] - c[3], H - c[1] - c[4], W - c[2] - c[5]
         t = t.to(_device())                       # host tensors are uploaded: there is no host implementation of this path
-        if t.element_size() not in (1, 4):
-            t = t.float() if t.dtype.is_floating_point else t.to(torch.int32)
-        t = t.contiguous()
-        out = torch.empty(tuple(t.shape[:-3]) + (Do, Ho, Wo), dtype=t.dtype, device=t.device)
-        call('da_crop3d', ptr(t), ptr(out), t.element_size(), lead, D, H, W, c[0], c[1], c[2], Do, Ho, Wo, stream())
-        return out
+        wide = None
+        if t.element_size() == 8 and _is_integer(t.dtype):
+            # a crop only moves elements: an 8-byte integer is moved as the two 4-byte halves it consists of (a row of 2 W), exact for every value
+            wide, t = t.dtype, t.contiguous().view(torch.int32)
+        else:
+            t = _exact_for_copy(t, 'CropTensor').contiguous()
+        k = 2 if wide is not None else 1
+        out = torch.empty(tuple(t.shape[:-3]) + (Do, Ho, k * Wo), dtype=t.dtype, device=t.device)
+        call('da_crop3d', ptr(t), ptr(out), t.element_size(), lead, D, H, k * W, c[0], c[1], k * c[2], Do, Ho, k * Wo, stream())
+        return out if wide is None else out.view(wide)
 
     def __call__(self, sample):
         img = sample['image']
@@ -120,7 +194,9 @@ class CropTensor(object):
 class Partition(object):
     """lib/transforms.py:508-649: overlap-tile strategy.  tile_size / overlap_size are given in SimpleITK order (x, y, z) and
     flipped to numpy order, as in the reference.  __call__ produces the N x 1 x tz x ty x tx tiles from the reflect-padded volume
-    without materialising the padding; assemble() puts predicted tiles back (core copy, or per-voxel majority vote)."""
+    without materialising the padding; assemble() puts predicted tiles back (core copy, or per-voxel majority vote).
+    The kernels move 1- and 4-byte elements: other integer widths are converted only where that is exact (_exact_for_copy) and raise a
+    ValueError naming the dtype otherwise; the vote takes labels 0 ... 255 and refuses anything else the same way."""
 
     def __init__(self, tile_size, overlap_size, padding_mode='reflect', mode="pred"):
         self.tile_size = np.flipud(np.asarray(tile_size))
@@ -145,9 +221,7 @@ class Partition(object):
         return tiles
 
     def __call__(self, sample):
-        image = _to_device_array(sample['image'])
-        if image.element_size() != 4:
-            image = image.float()
+        image = _exact_for_copy(_to_device_array(sample['image']), "Partition: sample['image']", as_float=True)
         self.image = sample['image']
         self.name = sample.get('name')
         self._geom(tuple(image.shape))
@@ -156,9 +230,7 @@ class Partition(object):
         if self.mode == 'pred':
             sample['segmentation'] = seg.unsqueeze(0)
         else:
-            if seg.element_size() not in (1, 4):
-                seg = seg.to(torch.uint8)
-            sample['segmentation'] = self._tiles(seg).unsqueeze(1)
+            sample['segmentation'] = self._tiles(_exact_for_copy(seg, "Partition: sample['segmentation']")).unsqueeze(1)
         return sample
 
     def assemble(self, tiles, is_vote=False, if_itk=False, crop_size=None, data_type=None):
@@ -168,9 +240,15 @@ class Partition(object):
             raise NotImplementedError('if_itk=True needs SimpleITK on the host; call with if_itk=False and wrap the result there')
         t = tiles.to(_device())
         if is_vote:
-            t = t.to(torch.uint8)
-        elif t.element_size() not in (1, 4):
-            t = t.float()
+            if t.dtype != torch.uint8:              # the vote kernel reads uint8 labels: anything else must fit, and is refused by name if it does not
+                # (a wide unsigned type is read through its signed view: what turns negative there is above 255 as well)
+                s = t.contiguous().view(_SIGNED_OF[t.element_size()]) if _is_unsigned(t.dtype) else t
+                if t.dtype.is_complex or (s.numel() and not bool(((s >= 0) & (s <= 255) & (s == s.to(torch.uint8))).all())):
+                    raise ValueError('Partition.assemble(is_vote=True): the %s tiles hold labels above 255 (or negative / fractional ones); '
+                                     'the vote takes labels 0 ... 255' % (t.dtype,))
+                t = s.to(torch.uint8)
+        else:
+            t = _exact_for_copy(t, 'Partition.assemble: tiles')
         t = t.contiguous()
         D, H, W = (int(v) for v in self.image_size)
         out = torch.empty((D, H, W), dtype=t.dtype, device=t.device)

@@ -163,6 +163,7 @@ class FlatAdam(torch.optim.Optimizer):
     def load_state_dict(self, state_dict):
         sd = state_dict
         ids = [i for grp in sd['param_groups'] for i in grp['params']]
+        steps = []
         for (p, off, k), i in zip(self._slices, ids):
             st = sd['state'].get(i)
             if st is None:
@@ -170,7 +171,11 @@ class FlatAdam(torch.optim.Optimizer):
             ops.param_view(self.flat_m, off, p).copy_(st['exp_avg'])
             ops.param_view(self.flat_v, off, p).copy_(st['exp_avg_sq'])
             self.state[p]['step'] = torch.tensor(float(st['step']))
-            self._steps = int(float(st['step']))
+            steps.append(int(float(st['step'])))
+        if steps:
+            # the bucket has ONE step count (one bias correction per launch): that of the parameters that were updated.  A frozen parameter's own
+            # count stays behind (0 when it never took a step), wherever it stands in the list
+            self._steps = max(steps)
         for grp, sg in zip(self.param_groups, sd['param_groups']):
             for key in ('lr', 'betas', 'eps'):
                 if key in sg:

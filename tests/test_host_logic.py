@@ -140,6 +140,23 @@ def test_c_abi_rejects_bad_arguments_before_touching_the_device():
     assert L.da_conv1x1_fwd_pro(fake, None, None, 0.01, fake, None, fake, 100, 16, 32, fake, 1 << 20, None) == BAD                # prologue entry without a prologue
     assert L.da_bn_act_fwd(None, fake, fake, 0.01, fake, 10, 16, None) == BAD
     assert L.da_maxpool2_fwd(fake, fake, 0, 8, 8, 8, 16, None) == BAD
+    # optim.hip / datapath.hip: each of these returns before any launch
+    from ctypes import c_float
+    UNSUPPORTED = -3
+    assert L.da_adam_step(fake, fake, fake, fake, 10, 1e-3, 0.9, 0.999, 1e-8, 0, 1.0, None) == BAD                                # step = 0
+    assert L.da_adam_step(fake, fake, fake, fake, 0, 1e-3, 0.9, 0.999, 1e-8, 1, 1.0, None) == BAD                                 # n = 0
+    assert L.da_adam_step_dev(fake, fake, fake, fake, 10, None, None) == BAD                                                      # null state
+    assert L.da_w_oik_to_tio(fake, fake, 0, 4, 27, None) == BAD and L.da_w_tio_to_iok_acc(fake, fake, 4, 4, 0, None) == BAD       # a zero dimension
+    assert L.da_clamp01_to_f32(fake, 5, fake, 10, None) == BAD                                                                    # dtype code 5
+    assert L.da_crop3d(fake, fake, 4, 1, 8, 8, 8, 4, 0, 0, 5, 8, 8, None) == BAD                                                  # window past the volume
+    assert L.da_crop3d(fake, fake, 2, 1, 8, 8, 8, 0, 0, 0, 8, 8, 8, None) == BAD                                                  # elem_bytes = 2
+    i3 = lambda a, b, c: (c_int * 3)(a, b, c)
+    assert L.da_partition_tiles(fake, fake, 4, 8, 8, 8, i3(4, 4, 4), i3(2, 0, 0), None) == BAD                                    # tile <= 2 * overlap
+    assert L.da_assemble_tiles(fake, fake, 4, 8, 8, 8, i3(4, 4, 4), i3(1, 1, 1), 1, None) == BAD                                  # a vote over 4-byte elements
+    assert L.da_assemble_tiles(fake, fake, 1, 9, 10, 11, i3(10, 10, 10), i3(4, 4, 4), 1, None) == UNSUPPORTED                     # 125 covering tiles
+    assert L.da_synth_volume(fake, fake, 1, 4, 4, 4, 257, 0, c_float(0.1), 1, 0, None) == BAD                                     # 257 classes
+    assert L.da_synth_volume(fake, fake, 1, 4, 4, 4, 32, 2, c_float(0.1), 1, 0, None) == BAD                                      # mode 2
+    assert L.da_cast_f32_to_bf16(fake, fake, 0, None) == BAD and L.da_cast_bf16_to_f32(fake, fake, 0, None) == BAD                # numel = 0
 
 
 def test_two_term_fp16_split_bounds_and_sums_are_fp32_accurate():
