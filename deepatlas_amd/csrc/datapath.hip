@@ -3,6 +3,7 @@
 // one thread per output element, 64-bit indexing, no intermediate padded volume (the reflect index is computed per element).
 #include "common.h"
 #include "counter_hash.h"
+#include "tile_geom.h"          // TileGeom, tile_geom()
 
 namespace {
 
@@ -45,8 +46,6 @@ __device__ __forceinline__ int reflect_idx(int i, int n) {
     int m = i % period; if (m < 0) m += period;
     return m < n ? m : period - m;
 }
-
-struct TileGeom { int D, H, W; int tz, ty, tx; int oz, oy, ox; int gz, gy, gx; };   // volume, tile, overlap, tile grid (numpy order z, y, x)
 
 // tiles[(i*gy + j)*gx + k][z][y][x] = padded[i*ez + z][j*ey + y][k*ex + x], padded = reflect-pad by `overlap` in front
 template <typename T>
@@ -167,14 +166,6 @@ extern "C" int da_crop3d(const void* src, void* dst, int elem_bytes, long long C
     else if (elem_bytes == 1) hipLaunchKernelGGL((crop3d_kernel<unsigned char>), dim3(da_grid(total, 256)), dim3(256), 0, da_stream(stream), (const unsigned char*)src, (unsigned char*)dst, C, D, H, W, d0, h0, w0, Do, Ho, Wo);
     else return DA_ERR_BADARG;
     DA_LAUNCH_CHECK();
-    return 0;
-}
-
-static int tile_geom(TileGeom& g, int D, int H, int W, const int* tile3, const int* overlap3) {
-    g.D = D; g.H = H; g.W = W; g.tz = tile3[0]; g.ty = tile3[1]; g.tx = tile3[2]; g.oz = overlap3[0]; g.oy = overlap3[1]; g.ox = overlap3[2];
-    const int ez = g.tz - 2 * g.oz, ey = g.ty - 2 * g.oy, ex = g.tx - 2 * g.ox;
-    if (D <= 0 || H <= 0 || W <= 0 || ez <= 0 || ey <= 0 || ex <= 0 || g.oz < 0 || g.oy < 0 || g.ox < 0) return DA_ERR_BADARG;
-    g.gz = (D + ez - 1) / ez; g.gy = (H + ey - 1) / ey; g.gx = (W + ex - 1) / ex;
     return 0;
 }
 

@@ -8,7 +8,8 @@ a voxel size (:9-57), Normalization (:59-68), LeftToRight (:269-284), Segmentati
 project's own PercentileRescale; they act on the raw arrays lib/nifti.py reads.  Every class takes numpy arrays (what
 sitk.GetArrayFromImage returns) or tensors and hands back DEVICE tensors, so a loader thread only uploads the raw volume once.
 Patch sampling, RandomCrop (:322-388) and BalancedRandomCrop (:391-505), runs on the device as well (csrc/crop.hip): the class count of every
-crop window as a separable sliding sum, a uniform pick among the starts that pass, one batched gather.
+crop window as a separable sliding sum, a uniform pick among the starts that pass, one batched gather.  importance_window gives the per-axis
+tables that weight a tile in blended sliding-window inference (lib/inference.py).
 Out of scope: reorientation by the affine, oblique resampling, anti-aliasing on down-sampling and B-spline interpolation.
 """
 import ctypes
@@ -956,3 +957,28 @@ def make_preprocess(spec):
             raise ValueError("preprocess step %r: one of %s" % (name, sorted(PREPROCESSING)))
         out.append(PREPROCESSING[name](**dict(kwargs or {})))
     return out
+
+
+IMPORTANCE_WINDOWS = ('gaussian', 'constant')
+
+
+def importance_window(tile, kind='gaussian', sigma_scale=0.125):
+    """The per-axis tables (z, y, x) of the window that weights a tile's probabilities in blended sliding-window inference
+    (ops.blend_accumulate; lib/inference.py): three float32 numpy vectors of tile[k] entries, the window is their product.
+    'gaussian': exp(-(l - (t - 1) / 2)^2 / (2 (sigma_scale t)^2)), evaluated in float64 and rounded to float32 -- MONAI's / nnU-Net's
+    window; being separable it needs no minimum clamp.  'constant': ones (plain averaging of the overlapping tiles)."""
+    if kind not in IMPORTANCE_WINDOWS:
+        raise ValueError("window %r: 'gaussian' or 'constant'" % (kind,))
+    if len(tile) != 3 or any(int(t) != t or int(t) < 1 for t in tile):
+        raise ValueError('tile takes three positive integers (z, y, x), got %r' % (tile,))
+    sigma_scale = float(sigma_scale)
+    if kind == 'gaussian' and not (sigma_scale > 0 and math.isfinite(sigma_scale)):
+        raise ValueError('sigma_scale must be positive and finite, got %r' % (sigma_scale,))
+    out = []
+    for t in (int(v) for v in tile):
+        if kind == 'constant':
+            out.append(np.ones(t, dtype=np.float32))
+        else:
+            l = np.arange(t, dtype=np.float64)
+            out.append(np.exp(-(l - (t - 1) / 2.0) ** 2 / (2.0 * (sigma_scale * t) ** 2)).astype(np.float32))
+    return tuple(out)

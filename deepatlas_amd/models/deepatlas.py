@@ -35,6 +35,7 @@ from .joint import DeepAtlasJointStep
 from .registration import (atlas_fusion_text, check_atlas_fusion, check_jac_penalty, check_sim_loss, dataset_volumes, eval_atlas_fusion,
                            eval_registration, jac_name_suffix)
 from .segmentation import SegmentationExperiment, refuse_patch
+from ..lib.inference import refuse_tile_blend
 from ..lib import datasets as med_data
 from ..lib.network_factory import get_network
 from ..lib.param_dict import save_dict_to_json
@@ -61,6 +62,7 @@ class DeepAtlasExperiment(BaseExperiment):
         self.device = torch.device(self.config.get('device', 'cuda'))
         cfg = self.config
         refuse_patch(cfg, 'joint')
+        refuse_tile_blend(cfg, 'joint')
         if cfg['debug_mode']:
             print("Debug mode")
             cfg['print_batch_period'] = cfg['valid_epoch_period'] = 2

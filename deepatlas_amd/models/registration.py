@@ -41,6 +41,7 @@ from .base import BaseExperiment
 from . import nifti_data
 from .joint import RegistrationStep, SIM_LOSSES, make_jac_penalty, make_ic_penalty
 from .segmentation import SegmentationExperiment, refuse_patch
+from ..lib.inference import refuse_tile_blend
 from ..lib import datasets as med_data
 from ..lib import evalMetrics as metrics
 from ..lib import affine as affine_lib
@@ -338,6 +339,7 @@ class RegistrationExperiment(BaseExperiment):
         self.device = torch.device(self.config.get('device', 'cuda'))
         cfg = self.config
         refuse_patch(cfg, 'registration')
+        refuse_tile_blend(cfg, 'registration')
         if cfg['debug_mode']:
             print("Debug mode")
             cfg['print_batch_period'] = cfg['valid_epoch_period'] = 2

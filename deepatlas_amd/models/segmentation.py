@@ -17,6 +17,9 @@ config['patch'] (default None: off; parse_patch states its form) turns on patch 
 batch_size patches cropped on the device (lib/transforms.py BalancedRandomCrop / RandomCrop's uniform draw) from batch_size / per_volume
 volumes, cropped before config['augment'] acts; validation and test tile every volume with Partition, run the net over the tiles and assemble
 the argmax.  Volumes of different shapes then train together.  Without the key nothing changes.
+config['tile_blend'] (default None: off; lib/inference.py parse_tile_blend states its form; it needs config['patch']) replaces the tiled
+evaluation's core copy by blended sliding-window inference (lib/inference.py SlidingWindowPredictor): the overlapping tiles' probabilities
+are averaged under a window, optionally over mirrored copies.  It takes no part in the experiment's name; without the key nothing changes.
 """
 import datetime
 import os
@@ -31,6 +34,7 @@ from .base import BaseExperiment
 from . import nifti_data
 from ..lib import datasets as med_data
 from ..lib import evalMetrics as metrics
+from ..lib import inference
 from ..lib import transforms as med_transforms
 from ..lib.loss import get_loss_function, BoundaryLoss
 from ..lib.network_factory import get_network
@@ -132,6 +136,8 @@ class SegmentationExperiment(BaseExperiment):
         self.crop = self.partition = None
         if self.patch is not None:
             self.setup_patch()
+        self.tile_blend = inference.parse_tile_blend(cfg.get('tile_blend'), self.patch)
+        self.predictor = None                                    # the SlidingWindowPredictor of config['tile_blend'], built on first use
         self.exp_name = self.experiment_name(cfg)
         # <log_dir>/<experiment name | "debug_seg">/<seed>: the directory layout the reference's checkpoints and resume_dir use
         # (models/segmentation.py:40-42), so runs of either code base can resume each other's checkpoints
@@ -373,7 +379,13 @@ class SegmentationExperiment(BaseExperiment):
 
     def predict_tiled(self, images):
         """Label maps N x D x H x W (uint8) of a batch N x 1 x D x H x W in patch mode: per volume Partition's reflect-padded overlap tiles of
-        the patch size, the net over chunks of tile_batch tiles, the first-max argmax of every tile, and assemble's core copy."""
+        the patch size, the net over chunks of tile_batch tiles, the first-max argmax of every tile, and assemble's core copy.
+        With config['tile_blend'] the tiles' probabilities are blended instead (lib/inference.py SlidingWindowPredictor)."""
+        if getattr(self, 'tile_blend', None) is not None:
+            if self.predictor is None or self.predictor.model is not self.model:
+                self.predictor = inference.SlidingWindowPredictor(self.model, self.config['n_classes'], self.patch['size'], self.patch['overlap'],
+                                                                  tile_batch=self.patch['tile_batch'], **self.tile_blend)
+            return self.predictor.predict_batch(images)
         out = []
         tb = self.patch['tile_batch']
         for n in range(images.shape[0]):

@@ -3558,3 +3558,60 @@ def crop_gather(image, labels, starts, window):
     with torch.cuda.device(img.device):
         call('da_crop_gather', ptr(img), ptr(out), C, ptr(lab), ptr(lab_out), lb, ptr(st), N, P, D, H, W, wp3, stream())
     return out, lab_out
+
+
+# ------------------------------------------------------------------------------------------------
+# blended sliding-window inference (csrc/blend.hip; lib/inference.py SlidingWindowPredictor)
+# ------------------------------------------------------------------------------------------------
+BLEND_MAX_CLASSES = 256             # DA_BLEND_MAX_CLASSES (include/deepatlas_hip.h): labels are uint8
+BLEND_FLIP_BITS = {'z': 1, 'y': 2, 'x': 4}      # bits of da_blend_accumulate's flip mask
+
+
+def _blend_acc(acc):
+    nat.require_cuda(acc)
+    if acc.dim() != 4 or acc.dtype != torch.float32 or not acc.is_contiguous():
+        raise ValueError('acc must be a contiguous float32 D x H x W x K tensor')
+    if not 2 <= acc.shape[3] <= BLEND_MAX_CLASSES:
+        raise ValueError('acc holds %d classes: 2 ... %d' % (acc.shape[3], BLEND_MAX_CLASSES))
+    return tuple(int(s) for s in acc.shape)
+
+
+def blend_accumulate(acc, tile_logits, tile0, tile, overlap, window, flip=0):
+    """Adds the window-weighted softmax of a run of Partition's tiles into the accumulator of their volume, in place (da_blend_accumulate).
+    acc D x H x W x K float32; tile_logits n x K x tz x ty x tx float32, the net's output for tiles tile0 ... tile0 + n - 1 of the raster tile
+    order (channels-last memory, as the nets return it, is read without a copy); tile / overlap (z, y, x); window = three per-axis tables
+    (lib.transforms.importance_window), uploaded once and kept by content; flip: BLEND_FLIP_BITS of the axes along which the tiles were
+    mirrored before the net saw them.  Per voxel the covering tiles are added in ascending tile order, each add from the stored value: the
+    result is bit-identical from run to run and for every split of the tiles into calls.  No autograd.  Returns acc."""
+    import numpy as np
+    D, H, W, K = _blend_acc(acc)
+    if tile_logits.dim() != 5 or tile_logits.dtype != torch.float32 or tile_logits.shape[1] != K or tile_logits.device != acc.device:
+        raise ValueError('tile_logits must be float32 n x %d x tz x ty x tx on the device of acc' % K)
+    if len(tile) != 3 or len(overlap) != 3 or len(window) != 3:
+        raise ValueError('tile, overlap and window take three entries each (z, y, x)')
+    t3 = tuple(int(v) for v in tile)
+    if tuple(int(s) for s in tile_logits.shape[2:]) != t3:
+        raise ValueError('tile_logits holds tiles of %s, tile is %s' % (tuple(tile_logits.shape[2:]), t3))
+    tabs = []
+    for w, t in zip(window, t3):
+        arr = np.ascontiguousarray(np.asarray(w, dtype=np.float32).reshape(-1))
+        if arr.shape[0] != t:
+            raise ValueError('a window table has %d entries, its tile axis %d' % (arr.shape[0], t))
+        tabs.append(_const_tensor(arr, acc.device))
+    a = ndhwc(tile_logits.detach())
+    (k1, tp), (k2, op) = _int3_array(t3), _int3_array(overlap)
+    with torch.cuda.device(acc.device):
+        call('da_blend_accumulate', ptr(a), ptr(acc), D, H, W, K, tp, op, int(tile0), int(a.shape[0]), ptr(tabs[0]), ptr(tabs[1]), ptr(tabs[2]),
+             int(flip), stream())
+    return acc
+
+
+def blend_finalize(acc, return_conf=False):
+    """Label map of an accumulator (da_blend_finalize): acc D x H x W x K float32 -> uint8 D x H x W, the first-maximum argmax over the classes;
+    with return_conf also float32 D x H x W, acc[label] / sum over the classes (NaN where a NaN logit reached the voxel)."""
+    D, H, W, K = _blend_acc(acc)
+    labels = torch.empty((D, H, W), dtype=torch.uint8, device=acc.device)
+    conf = torch.empty((D, H, W), dtype=torch.float32, device=acc.device) if return_conf else None
+    with torch.cuda.device(acc.device):
+        call('da_blend_finalize', ptr(acc), D * H * W, K, ptr(labels), ptr(conf), stream())
+    return (labels, conf) if return_conf else labels

@@ -471,6 +471,25 @@ int da_partition_tiles(const void* vol, void* tiles, int elem_bytes, int D, int 
 /* vote == 0: copy the effective core of each tile; vote != 0 (uint8 labels): per-voxel majority over the covering tiles */
 int da_assemble_tiles(const void* tiles, void* vol, int elem_bytes, int D, int H, int W, const int* tile3, const int* overlap3, int vote, void* stream);
 
+/* ---- blended sliding-window inference (csrc/blend.hip; the project's own, after nnU-Net / MONAI sliding_window_inference) --------------
+ * The tiling is da_partition_tiles': per axis e = t - 2 o, g = ceil(S / e), tile i holds the volume coordinates i e - o + l, l in [0, t);
+ * coordinates outside [0, S) are the reflect padding and take no part.
+ * da_blend_accumulate: logits [n_tiles][tz][ty][tx][K] fp32 channels-last = tiles tile0 ... tile0 + n_tiles - 1 of the raster tile order;
+ * acc [D][H][W][K] fp32 channels-last, read and written; wz / wy / wx [tz] / [ty] / [tx] fp32 on the device, the window of local position
+ * (lz, ly, lx) is (wz[lz] * wy[ly]) * wx[lx] in fp32.  flip: bit 0 / 1 / 2 = the tile was mirrored along z / y / x before the net saw it, its
+ * logits are read at t - 1 - l on that axis (the window always at l).  For every voxel and every tile j of the call that covers it, in ascending
+ * j: acc[x][c] = acc[x][c] + w * p_c (product and sum rounded separately), p = exp(v_c - max v) / sum_c exp(v_c - max v) in fp32.  Every add
+ * starts from the stored value, so acc is a function of the logits and the order of the calls' flip passes alone: bit-identical from run to
+ * run and for every split of the tiles into calls.  No atomics: the lanes of the call's lowest covering tile own a voxel.
+ * K = 2 ... DA_BLEND_MAX_CLASSES.  DA_ERR_BADARG: null pointers, a geometry da_partition_tiles refuses, tile0 < 0, n_tiles < 1,
+ * tile0 + n_tiles beyond the grid, flip outside 0 ... 7, K out of range.
+ * da_blend_finalize: labels [V] uint8 = the first-maximum argmax over c of acc[x][.] (da_argmax_dice_counts' tie rule); conf [V] fp32 (may be
+ * NULL) = acc[x][label] / sum_c acc[x][c], summed in class order in double, rounded once: NaN where a NaN logit reached the voxel. */
+#define DA_BLEND_MAX_CLASSES 256
+int da_blend_accumulate(const float* logits, float* acc, int D, int H, int W, int K, const int* tile3, const int* overlap3, int tile0, int n_tiles,
+                        const float* wz, const float* wy, const float* wx, int flip, void* stream);
+int da_blend_finalize(const float* acc, long long V, int K, unsigned char* labels, float* conf, void* stream);
+
 /* synthetic volumes generated on the device (row f4; the structure of the BASELINE configs' synthetic data, the reference's sample
  * convention lib/datasets.py:150-166: image [N][D][H][W] fp32 in [0,1], segmentation uint8).  Counter-based hash: element = f(seed,
  * sample0 + n, voxel), restated bit-exactly in oracle/datapath.py.  mode 0: iid image ~ U[0,1), labels ~ U{0..C-1};

@@ -1,0 +1,238 @@
+"""Segment NIfTI scans with a trained segmentation net and write the label maps on each scan's own grid.
+
+    python predict_seg.py --ckpt CKPT --output-dir DIR (--input FILE... | --data-dir DIR --list FILE)
+        [--config JSON] [--patch-size D H W] [--tile-overlap D H W] [--tile-batch N] [--tile-blend gaussian|constant] [--tile-mirror AXES]
+        [--postprocess largest-cc|min-size] [--cc-connectivity N] [--cc-min-size N] [--save-confidence]
+        [--labels FILE... | --label-dir DIR] [--surface-metrics]
+
+The config is the train_config.json the experiment wrote beside its checkpoints (--config names another).  Per scan: lib/nifti.py reads the
+file; config['preprocess'] runs as training applied it, then SitkToTensor; the net predicts -- the whole volume at once when the config has
+no `patch` and no patch flag is given, otherwise blended sliding-window inference (lib/inference.py; with `tile_blend` off a constant window,
+plain averaging of the overlapping tiles); optionally the connected-component clean-up; the label map is mapped back to the file's grid
+(lib/inference.py restore_native: the left_to_right flip and the resample are undone, nearest neighbour) and written as <name>_seg.nii.gz
+(uint8) with the input's geometry; --save-confidence adds <name>_conf.nii.gz (float32, restored linearly).  With labels given, Dice per scan
+and its mean are printed on the native grid, with --surface-metrics also HD95 and ASSD at the file's spacing.
+Out of scope: registration and joint inference, writing displacement fields, per-class probability maps, checkpoint ensembling, overlapping
+the host's gzip with the device."""
+import argparse
+import json
+import os
+
+import numpy as np
+import torch
+
+
+def build_parser():
+    parser = argparse.ArgumentParser(description='Segment NIfTI scans with a trained net.')
+    parser.add_argument('--ckpt', required=True, type=str, help='checkpoint file (model_best.pth.tar / checkpoint.pth.tar)')
+    parser.add_argument('--output-dir', required=True, type=str, help='directory the label maps are written to')
+    parser.add_argument('--input', nargs='+', default=None, metavar='FILE', help='scans to segment (.nii / .nii.gz)')
+    parser.add_argument('--data-dir', default=None, type=str, help='with --list: directory of the scans, named as the training dataset names them')
+    parser.add_argument('--list', dest='list_file', default=None, type=str, help='list file of scan names, one per line')
+    parser.add_argument('--config', default=None, type=str, help='config JSON (default: train_config.json beside the checkpoint)')
+    parser.add_argument('--device', '-g', default='0', type=str, help='index of used GPU')
+    parser.add_argument('--patch-size', nargs=3, type=int, default=None, metavar=('D', 'H', 'W'), help='tile size (default: the config\'s patch size)')
+    parser.add_argument('--tile-overlap', nargs=3, type=int, default=None, metavar=('D', 'H', 'W'), help='tile overlap on every side')
+    parser.add_argument('--tile-batch', type=int, default=None, metavar='N', help='tiles per forward pass')
+    parser.add_argument('--tile-blend', default=None, choices=['gaussian', 'constant'], help='window of the blending (default: the config\'s, else constant)')
+    parser.add_argument('--tile-mirror', default=None, metavar='AXES', help="also run the tiles mirrored along these axes, e.g. 'zyx', and average")
+    parser.add_argument('--postprocess', default=None, choices=['largest-cc', 'min-size'], help='connected-component clean-up of the label map')
+    parser.add_argument('--cc-connectivity', type=int, default=None, choices=[6, 18, 26], help='connectivity of --postprocess (default 6)')
+    parser.add_argument('--cc-min-size', type=int, default=None, metavar='VOXELS', help='smallest component --postprocess min-size keeps (default 64)')
+    parser.add_argument('--save-confidence', action='store_true', help='also write <name>_conf.nii.gz: the winning class\'s share of the blended weight')
+    parser.add_argument('--labels', nargs='+', default=None, metavar='FILE', help='label files, one per --input, to score against')
+    parser.add_argument('--label-dir', default=None, type=str, help='directory of label files named as the training dataset names them')
+    parser.add_argument('--surface-metrics', action='store_true', help='with labels: also print HD95 and ASSD at the file\'s spacing')
+    return parser
+
+
+def find_config(ckpt, config=None):
+    """The config file of a checkpoint: `config` when given, else train_config.json in the checkpoint's directory."""
+    path = config or os.path.join(os.path.dirname(os.path.abspath(ckpt)), 'train_config.json')
+    if not os.path.isfile(path):
+        raise ValueError('no config at %s: pass --config' % path)
+    return path
+
+
+def scan_name(path):
+    """File name without .nii / .nii.gz and without the datasets' _image suffix."""
+    base = os.path.basename(str(path))
+    for ext in ('.nii.gz', '.nii'):
+        if base.endswith(ext):
+            base = base[:-len(ext)]
+            break
+    return base[:-len('_image')] if base.endswith('_image') else base
+
+
+def resolve_inputs(args, cfg):
+    """[(name, image path, label path or None)] of the command line."""
+    from deepatlas_amd.lib import datasets as med_data
+    family = med_data.NIFTI_SEG_DATASETS.get(cfg.get('data'), med_data.SegDataSetOAIZIB)
+    if (args.input is None) == (args.list_file is None):
+        raise ValueError('give --input FILE..., or --data-dir DIR --list FILE')
+    if args.input is not None:
+        if args.labels is not None and len(args.labels) != len(args.input):
+            raise ValueError('--labels takes one file per --input')
+        images = list(args.input)
+        names = [scan_name(p) for p in images]
+        labels = list(args.labels) if args.labels is not None else [None] * len(images)
+    else:
+        if not args.data_dir:
+            raise ValueError('--list needs --data-dir')
+        if args.labels is not None:
+            raise ValueError('--labels goes with --input; with --list use --label-dir')
+        images, labels, names = family.read_image_segmentation_list(args.list_file, args.data_dir)
+        labels = [None] * len(images)
+    if args.label_dir is not None:
+        if args.labels is not None:
+            raise ValueError('--labels and --label-dir exclude each other')
+        labels = [os.path.join(args.label_dir, family.SEGMENTATION_PATTERN[0], family.SEGMENTATION_PATTERN[1] % n) for n in names]
+    return list(zip(names, images, labels))
+
+
+def inference_settings(args, cfg):
+    """(patch dict or None, tile_blend dict or None) from the config, overridden by the flags."""
+    from deepatlas_amd.lib.inference import parse_tile_blend
+    from deepatlas_amd.models.segmentation import parse_patch
+    patch = parse_patch(cfg.get('patch'))
+    if args.patch_size is not None:
+        patch = parse_patch(dict(patch or {}, size=list(args.patch_size)))
+    if patch is None:
+        if any(v is not None for v in (args.tile_overlap, args.tile_batch, args.tile_blend, args.tile_mirror)):
+            raise ValueError('--tile-overlap, --tile-batch, --tile-blend and --tile-mirror need a patch size (--patch-size, or the config\'s)')
+        return None, None
+    if args.tile_overlap is not None:
+        patch['overlap'] = [int(v) for v in args.tile_overlap]
+    if args.tile_batch is not None:
+        patch['tile_batch'] = int(args.tile_batch)
+    patch = parse_patch(patch)
+    blend = dict(parse_tile_blend(cfg.get('tile_blend'), patch) or {'window': 'constant'})      # off = plain averaging: no second core-copy route
+    if args.tile_blend is not None:
+        blend['window'] = args.tile_blend
+    if args.tile_mirror is not None:
+        blend['mirror'] = list(args.tile_mirror)
+    return patch, parse_tile_blend(blend, patch)
+
+
+def postprocess_setting(args):
+    from deepatlas_amd.lib import evalMetrics as metrics
+    if not args.postprocess:
+        return None
+    post = {'mode': {'largest-cc': 'largest_cc', 'min-size': 'min_size'}[args.postprocess], 'connectivity': args.cc_connectivity or 6}
+    if post['mode'] == 'min_size':
+        post['min_size'] = args.cc_min_size if args.cc_min_size is not None else 64
+    return metrics.parse_postprocess(post)
+
+
+def prepare(path, name, cfg):
+    """(the file's Volume, image 1 x D x H x W on the device, record for restore_native)."""
+    from deepatlas_amd.lib import transforms as T
+    from deepatlas_amd.lib.inference import RecordedPreprocess
+    from deepatlas_amd.lib.nifti import read_nifti
+    from deepatlas_amd.models import nifti_data
+    vol = read_nifti(path)
+    sample, record = RecordedPreprocess(cfg.get('preprocess'))({'image': vol.array, 'name': name, 'spacing': vol.spacing})
+    sample = T.SitkToTensor()(sample)
+    if nifti_data.is_nifti(cfg) and cfg.get('crop_size'):
+        before = tuple(int(s) for s in sample['image'].shape[-3:])
+        sample = T.CropTensor(cfg['crop_size'])(sample)
+        record['steps'].append(('crop', before, tuple(int(v) for v in T.CropTensor(cfg['crop_size']).crop_size)))
+    return vol, sample['image'], record
+
+
+def predict_volume(model, image, cfg, patch, blend, want_conf):
+    """image 1 x D x H x W -> (labels uint8 D x H x W, confidence float32 D x H x W or None) on the prepared grid."""
+    from deepatlas_amd.lib import evalMetrics as metrics
+    from deepatlas_amd.lib.inference import SlidingWindowPredictor
+    from deepatlas_amd.models import nifti_data
+    shape = tuple(int(s) for s in image.shape[-3:])
+    n_class = int(cfg['n_classes'])
+    if patch is None:
+        nifti_data.check_shapes([[(image, None, 'the prepared volume')]], [cfg['model']])      # the ValueError of a shape the net cannot take
+        if not want_conf:
+            with torch.no_grad():
+                model.eval()
+                logits = model(image.unsqueeze(0))
+                return metrics.eval_dice_counts(logits, torch.zeros((1,) + shape, dtype=torch.uint8, device=image.device))[1][0], None
+        predictor = SlidingWindowPredictor(model, n_class, shape, (0, 0, 0), tile_batch=1, window='constant')      # one tile: acc = the softmax
+    else:
+        predictor = SlidingWindowPredictor(model, n_class, patch['size'], patch['overlap'], tile_batch=patch['tile_batch'], **blend)
+    out = predictor.predict(image[0], return_conf=want_conf)
+    return out if want_conf else (out, None)
+
+
+def load_model(cfg, ckpt, device):
+    from deepatlas_amd import ops
+    from deepatlas_amd.lib.network_factory import get_network
+    from deepatlas_amd.lib.utils import initialize_model
+    model = get_network(cfg['model'])(**cfg['model_settings']).to(device)
+    ops.set_matrix_precision(cfg.get('matrix_precision') or ops.DEFAULT_MATRIX_PRECISION)
+    initialize_model(model, None, ckpt)
+    return model.eval()
+
+
+def format_dice(name, dice):
+    return '%s: Dice Avg: %.6f' % (name, dice)
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    from deepatlas_amd import ops
+    from deepatlas_amd.lib import evalMetrics as metrics
+    from deepatlas_amd.lib import transforms as T
+    from deepatlas_amd.lib.inference import restore_native
+    from deepatlas_amd.lib.nifti import read_nifti, write_nifti
+    with open(find_config(args.ckpt, args.config)) as f:
+        cfg = json.load(f)
+    scans = resolve_inputs(args, cfg)
+    patch, blend = inference_settings(args, cfg)
+    post = postprocess_setting(args)
+    device = torch.device('cuda:{}'.format(args.device) if args.device.isdigit() else args.device)
+    torch.cuda.set_device(device)
+    model = load_model(cfg, args.ckpt, device)
+    n_class = int(cfg['n_classes'])
+    label_filters = [t for t in T.make_preprocess(cfg.get('preprocess')) if isinstance(t, T.SegmentationLabelFilter)]
+    os.makedirs(args.output_dir, exist_ok=True)
+    dices, hd95s, assds = [], [], []
+    for name, path, label_path in scans:
+        vol, image, record = prepare(path, name, cfg)
+        labels, conf = predict_volume(model, image, cfg, patch, blend, args.save_confidence)
+        if post is not None:
+            labels = metrics.postprocess_labels(labels.unsqueeze(0), n_class, post)[0]
+        native = restore_native(labels, record)
+        write_nifti(os.path.join(args.output_dir, name + '_seg.nii.gz'), native.cpu().numpy().astype(np.uint8), like=vol)
+        if conf is not None:
+            write_nifti(os.path.join(args.output_dir, name + '_conf.nii.gz'), restore_native(conf, record, 'linear').cpu().numpy().astype(np.float32),
+                        like=vol)
+        line = '%s: wrote %s' % (name, os.path.join(args.output_dir, name + '_seg.nii.gz'))
+        if label_path is not None:
+            sample = {'segmentation': read_nifti(label_path).array, 'image': None, 'name': name}
+            for t in label_filters:
+                sample = t(sample)
+            truth = T._to_device_array(sample['segmentation']).to(native.device)
+            if tuple(truth.shape) != tuple(native.shape):
+                raise ValueError('%s holds %s voxels, the scan %s' % (label_path, tuple(truth.shape), tuple(native.shape)))
+            truth = truth if truth.dtype in (torch.uint8, torch.int32, torch.int64) else truth.long()
+            counts = ops.label_overlap_counts(native.unsqueeze(0), truth.unsqueeze(0), n_class)
+            d = metrics.dice_from_counts(counts)[0, 1:]
+            dice = float(np.nanmean(d)) if np.any(~np.isnan(d)) else float('nan')
+            dices.append(dice)
+            line = format_dice(name, dice)
+            if args.surface_metrics:
+                spacing = tuple(float(s) for s in reversed(vol.spacing))                       # (z, y, x)
+                s = metrics.surface_distances(native.unsqueeze(0), truth.unsqueeze(0), n_class, spacing=spacing)
+                with np.errstate(invalid='ignore'):
+                    hd, assd = np.nanmean(s['hd_pct']) if np.any(~np.isnan(s['hd_pct'])) else np.nan, np.nanmean(s['assd']) if np.any(~np.isnan(s['assd'])) else np.nan
+                hd95s.append(float(hd))
+                assds.append(float(assd))
+                line += ', HD95 Avg: %.2f, ASSD Avg: %.2f' % (hd, assd)
+        print(line)
+    if dices:
+        line = format_dice('mean over %d scans' % len(dices), float(np.nanmean(dices)))
+        if hd95s:
+            line += ', HD95 Avg: %.2f, ASSD Avg: %.2f' % (float(np.nanmean(hd95s)), float(np.nanmean(assds)))
+        print(line)
+
+
+if __name__ == '__main__':
+    main()

@@ -4,7 +4,8 @@ positional './data' / './logs' defaults, and the undefined args.leaf.  Device se
 source is the synthetic volume generator, or with --data NAME the reference's NIfTI list-file datasets read without SimpleITK (--data-dir,
 --train-list, --valid-list, --test-list) and prepared on the device (--voxel-size, --rescale-percentiles, --normalize, --ignore-labels,
 --crop-size).  --patch-size D H W trains on patches cropped on the device and evaluates tile by tile (--patch-mode, --patch-threshold,
---patches-per-volume, --tile-overlap, --tile-batch)."""
+--patches-per-volume, --tile-overlap, --tile-batch); --tile-blend / --tile-mirror blend the evaluation tiles' probabilities
+(lib/inference.py)."""
 import argparse
 import os
 
@@ -104,6 +105,13 @@ def build_config(args):
                            'tile_batch': tile_batch or 4, 'include_last': False}
     elif any(v is not None for v in (patch_mode, patch_threshold, per_volume, tile_overlap, tile_batch)):
         raise ValueError('--patch-mode, --patch-threshold, --patches-per-volume, --tile-overlap and --tile-batch need --patch-size')
+    # opt-in blending of the evaluation tiles (lib/inference.py parse_tile_blend); absent = the core copy, and no key in the config
+    tile_blend = config.pop('tile_blend', None)
+    tile_mirror = config.pop('tile_mirror', None)
+    if tile_blend is not None or tile_mirror is not None:
+        if patch_size is None:
+            raise ValueError('--tile-blend and --tile-mirror need --patch-size')
+        config['tile_blend'] = {'window': tile_blend or 'gaussian', 'sigma_scale': 0.125, 'mirror': list(tile_mirror or '')}
     if not config.get('matrix_precision'):                # (--matrix-precision; not a key of the reference's config: absent = the package default, 'fp32_split')
         config.pop('matrix_precision', None)
     return apply_data_arguments(config)
@@ -167,6 +175,10 @@ def main(argv=None):
     parser.add_argument('--tile-overlap', nargs=3, type=int, default=None, metavar=('D', 'H', 'W'),
                         help='overlap of the evaluation tiles on every side (default 8 8 8); 2 x overlap < patch size')
     parser.add_argument('--tile-batch', type=int, default=None, metavar='T', help='evaluation tiles per forward pass (default 4)')
+    parser.add_argument('--tile-blend', default=None, choices=['gaussian', 'constant'],
+                        help="blend the evaluation tiles' probabilities under this window instead of copying tile cores (needs --patch-size)")
+    parser.add_argument('--tile-mirror', default=None, metavar='AXES',
+                        help="also run the evaluation tiles mirrored along these axes, e.g. 'zyx', and average (implies --tile-blend gaussian)")
     add_data_arguments(parser, with_preload=False)              # (--preload is the reference's own flag, above)
     args = parser.parse_args(argv)
     exp = SegmentationExperiment(build_config(args))
