@@ -142,7 +142,7 @@ affine_warp_bwd_theta_kernel(const float* __restrict__ g, const float* __restric
     __syncthreads();
     if (threadIdx.x < kAfTerms) {
         const int i = threadIdx.x;
-        partial[((size_t)n * kAfTerms + i) * gridDim.x + blockIdx.x] = ((red[0][i] + red[1][i]) + red[2][i]) + red[3][i];
+        partial[((size_t)n * kAfTerms + i) * gridDim.x + blockIdx.x] = da_sum4(red, i);
     }
 }
 

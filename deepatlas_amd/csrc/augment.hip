@@ -60,17 +60,6 @@ __device__ __forceinline__ float trilinear(const float* __restrict__ p, const Ta
     return fmaf(t.fz, c1 - c0, c0);
 }
 
-__device__ __forceinline__ long long load_label(const void* __restrict__ lab, int bytes, long long i) {
-    if (bytes == 1) return ((const unsigned char*)lab)[i];
-    if (bytes == 4) return ((const int*)lab)[i];
-    return ((const long long*)lab)[i];
-}
-__device__ __forceinline__ void store_label(void* __restrict__ lab, int bytes, long long i, long long v) {
-    if (bytes == 1) ((unsigned char*)lab)[i] = (unsigned char)v;
-    else if (bytes == 4) ((int*)lab)[i] = (int)v;
-    else ((long long*)lab)[i] = v;
-}
-
 // grid: x = workgroups per sample (XCD-contiguous split of the sample's rows), y = sample.  Dynamic LDS: the sample's 3 x gz x gy x gx
 // coefficients when O > 0.
 template <int O>
@@ -134,14 +123,14 @@ __global__ __launch_bounds__(kBlock) void resample_kernel(const float* __restric
             const long long ln = (long long)n * vol;
             long long v[kVec];
 #pragma unroll
-            for (int j = 0; j < kVec; ++j) v[j] = t[j].in ? load_label(lab, g.label_bytes, ln + t[j].nn) : 0;
+            for (int j = 0; j < kVec; ++j) v[j] = t[j].in ? da_load_vol_label(lab, g.label_bytes, ln + t[j].nn) : 0;
             if (vec && g.label_bytes == 1) {
                 const unsigned pk = (unsigned)(v[0] & 0xFF) | ((unsigned)(v[1] & 0xFF) << 8) | ((unsigned)(v[2] & 0xFF) << 16) | ((unsigned)(v[3] & 0xFF) << 24);
                 *reinterpret_cast<unsigned*>((unsigned char*)lab_out + ln + row) = pk;
             } else {
 #pragma unroll
                 for (int j = 0; j < kVec; ++j)
-                    if (w0 + j < W) store_label(lab_out, g.label_bytes, ln + row + j, v[j]);
+                    if (w0 + j < W) da_store_vol_label(lab_out, g.label_bytes, ln + row + j, v[j]);
             }
         }
         if (im) {

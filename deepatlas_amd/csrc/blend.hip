@@ -13,17 +13,6 @@ namespace {
 
 constexpr int kBlendMaxK = DA_BLEND_MAX_CLASSES;
 
-template <int L> __device__ __forceinline__ float bd_group_max(float v) {
-#pragma unroll
-    for (int m = 1; m < L; m <<= 1) v = fmaxf(v, __shfl_xor(v, m));
-    return v;
-}
-template <int L> __device__ __forceinline__ float bd_group_sum(float v) {
-#pragma unroll
-    for (int m = 1; m < L; m <<= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
 // channel of register r of lane `sub`
 template <int L, bool QUAD> __device__ __forceinline__ int bd_channel(int sub, int r) { return QUAD ? 4 * sub + r : sub + r * L; }
 
@@ -102,11 +91,11 @@ blend_accumulate_kernel(const float* __restrict__ logits, float* __restrict__ ac
                     const float* lv = logits + ((((long long)(r - a.tile0) * g.tz + fz) * g.ty + fy) * g.tx + fx) * K;
                     float v[4];
                     bd_load<L, QUAD>(lv, sub, K, -INFINITY, v);
-                    const float mxv = bd_group_max<L>(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
+                    const float mxv = da_group_max<L>(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
                     float e[4];
 #pragma unroll
                     for (int q = 0; q < 4; ++q) e[q] = expf(v[q] - mxv);
-                    const float se = bd_group_sum<L>((e[0] + e[1]) + (e[2] + e[3]));
+                    const float se = da_group_sum<L>((e[0] + e[1]) + (e[2] + e[3]));
                     {
 #pragma clang fp contract(off)                                   // w, w p and the sum are rounded one by one: the formula the header states
                         const float w = (wz[mz] * wy[my]) * wx[mx];

@@ -35,16 +35,6 @@ constexpr int kCcFlatChunks = 8;                        // chunks of 64 voxels p
 constexpr int kCcSelectBlocks = 1024;                   // workgroups per sample of the selection pass (each flushes <= 3 atomics per class)
 static_assert(kCcThreads == 256, "one lane per (h, w) position of a tile plane");
 
-__device__ __forceinline__ long long cc_ld(const void* __restrict__ p, int bytes, long long i) {
-    if (bytes == 1) return (long long)((const unsigned char*)p)[i];
-    if (bytes == 4) return (long long)((const int*)p)[i];
-    return ((const long long*)p)[i];
-}
-__device__ __forceinline__ void cc_st(void* __restrict__ p, int bytes, long long i, long long v) {
-    if (bytes == 1) ((unsigned char*)p)[i] = (unsigned char)v;
-    else if (bytes == 4) ((int*)p)[i] = (int)v;
-    else ((long long*)p)[i] = v;
-}
 // the class of a stored label: 0 = background
 __device__ __forceinline__ long long cc_class(long long l, int n_class) { return (l <= 0 || (n_class > 0 && l >= (long long)n_class)) ? 0 : l; }
 
@@ -104,7 +94,7 @@ cc_local_kernel(const void* __restrict__ labels, int bytes, int D, int H, int W,
     for (int k = 0; k < kCcTD; ++k) {
         const int i = k * kCcThreads + t, d = d0 + k;
         long long l = 0;
-        if (d < D && h < H && w < W) l = cc_class(cc_ld(labels, bytes, base + ((long long)d * H + h) * W + w), n_class);
+        if (d < D && h < H && w < W) l = cc_class(da_load_vol_label(labels, bytes, base + ((long long)d * H + h) * W + w), n_class);
         lab[i] = l;                                    // a voxel of the tile outside the volume is background: nothing joins across the faces
         par[i] = l ? i : -1;
     }
@@ -153,7 +143,7 @@ cc_seam_kernel(const void* __restrict__ labels, int bytes, int D, int H, int W, 
     int d, h, w; da_vox3(v, H, W, d, h, w);
     const int ld = d % kCcTD, lh = h % kCcTH, lw = w % kCcTW;
     if (ld > 0 && ld < kCcTD - 1 && lh > 0 && lh < kCcTH - 1 && lw > 0 && lw < kCcTW - 1) return;      // every neighbour is in the same tile
-    const long long l = cc_class(cc_ld(labels, bytes, base + v), n_class);
+    const long long l = cc_class(da_load_vol_label(labels, bytes, base + v), n_class);
     if (l == 0) return;
     int* parent = parent_all + base;
 #pragma unroll
@@ -164,7 +154,7 @@ cc_seam_kernel(const void* __restrict__ labels, int bytes, int D, int H, int W, 
         if (nd >= D || nh < 0 || nh >= H || nw < 0 || nw >= W) continue;
         if (nd / kCcTD == d / kCcTD && nh / kCcTH == h / kCcTH && nw / kCcTW == w / kCcTW) continue;   // joined by the local pass
         const int u = (nd * H + nh) * W + nw;
-        if (cc_class(cc_ld(labels, bytes, base + u), n_class) != l) continue;
+        if (cc_class(da_load_vol_label(labels, bytes, base + u), n_class) != l) continue;
         cc_unite<__HIP_MEMORY_SCOPE_AGENT>(parent, v, u);
     }
     const int r = cc_find<__HIP_MEMORY_SCOPE_AGENT>(parent, v);
@@ -231,7 +221,7 @@ cc_select_kernel(const void* __restrict__ labels, int bytes, const int* __restri
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < V; i += (long long)gridDim.x * 256) {
         const int s = sizes[base + i];
         if (s <= 0) continue;                          // not a root
-        const long long l = cc_class(cc_ld(labels, bytes, base + i), n_class);
+        const long long l = cc_class(da_load_vol_label(labels, bytes, base + i), n_class);
         if (l == 0 || l >= n_class) continue;
         atomicMax(sbest + l, ((unsigned long long)(unsigned)s << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)i));
         atomicAdd(svox + l, (unsigned long long)s);
@@ -260,7 +250,7 @@ cc_filter_kernel(const void* __restrict__ labels, int bytes, const int* __restri
     const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
     if (v >= V) return;
     const long long base = (long long)blockIdx.y * V;
-    const long long raw = cc_ld(labels, bytes, base + v);
+    const long long raw = da_load_vol_label(labels, bytes, base + v);
     const long long l = cc_class(raw, n_class);
     const int r = roots[base + v];
     bool keep = false;
@@ -272,7 +262,7 @@ cc_filter_kernel(const void* __restrict__ labels, int bytes, const int* __restri
             keep = sizes[base + r - 1] >= min_size;
         }
     }
-    cc_st(out, bytes, base + v, keep ? raw : 0);
+    da_store_vol_label(out, bytes, base + v, keep ? raw : 0);
 }
 
 int cc_max_nz(int connectivity) { return connectivity == 6 ? 1 : connectivity == 18 ? 2 : connectivity == 26 ? 3 : 0; }

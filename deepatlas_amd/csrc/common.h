@@ -103,6 +103,37 @@ __device__ __forceinline__ double da_wave_max(double v) {
     return v;
 }
 
+// the same butterflies over the L lanes (a power of two, <= 64) that own one voxel's channels; every lane of the group gets the result
+template <int L> __device__ __forceinline__ float da_group_max(float v) {
+#pragma unroll
+    for (int m = 1; m < L; m <<= 1) v = fmaxf(v, __shfl_xor(v, m));
+    return v;
+}
+template <int L> __device__ __forceinline__ float da_group_sum(float v) {
+#pragma unroll
+    for (int m = 1; m < L; m <<= 1) v += __shfl_xor(v, m);
+    return v;
+}
+// softmax of one voxel in place: lpv lanes (a run-time power of two, <= 64) own the voxel, 4 channels each.  One definition for the Dice
+// kernels (losses.hip) and the fused label-warp Dice (warp.hip): both phases of the joint step form the same probabilities.
+__device__ __forceinline__ void da_group_softmax4(float (&x)[4], int lpv) {
+    float m = fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3]));
+    for (int o = 1; o < lpv; o <<= 1) m = fmaxf(m, __shfl_xor(m, o));
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { x[j] = expf(x[j] - m); s += x[j]; }
+    for (int o = 1; o < lpv; o <<= 1) s += __shfl_xor(s, o);
+    const float inv = 1.f / s;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) x[j] *= inv;
+}
+
+// Entry k of the four waves' results staged in `double red[4][K]`, combined in wave order.  The order is fixed on purpose: it is part of the
+// determinism contract of the statistics kernels (two runs are bit-identical), so it is written once.  Staging into `red`, and which
+// thread combines, stay with each kernel.
+template <int K> __device__ __forceinline__ double da_sum4(double (*red)[K], int k) { return ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k]; }
+template <int K> __device__ __forceinline__ double da_max4(double (*red)[K], int k) { return fmax(fmax(red[0][k], red[1][k]), fmax(red[2][k], red[3][k])); }
+
 // block-wide sum of a double; result valid in thread 0.  `red` must hold blockDim.x/64 doubles.
 __device__ __forceinline__ double da_block_sum(double v, double* red) {
     v = da_wave_sum(v);
@@ -236,6 +267,38 @@ __device__ __forceinline__ da_f4v da_quad_transpose(da_f4v a, int q) {
     return (da_f4v){t0, t1, t2, t3};
 }
 
+// Label maps come in two width sets, and a loader reads whatever width it is not told about as int64: each launcher's own DA_ERR_BADARG
+// test on label_bytes is what keeps a width out of a kernel that cannot read it.
+//   1 | 8 bytes (uint8, int64): the training and evaluation kernels -- losses.hip, xent.hip, headdice.hip, warp.hip, regeval.hip.  R is the
+//     type the label is used as (int in warp.hip); the cast sits in each branch, so that a narrow R never widens the byte load first.
+template <typename R = long long>
+__device__ __forceinline__ R da_load_label(const void* labels, int label_bytes, long long i) {
+    return label_bytes == 1 ? (R)((const unsigned char*)labels)[i] : (R)((const long long*)labels)[i];
+}
+//   1 | 4 | 8 bytes (uint8, int32, int64): the volume utilities -- augment.hip (da_spatial_resample), cc.hip (da_cc_*), edt.hip (distance
+//     maps, surfaces, surface distances).  The store writes the map back in the width it came in.
+__device__ __forceinline__ long long da_load_vol_label(const void* __restrict__ p, int bytes, long long i) {
+    if (bytes == 1) return (long long)((const unsigned char*)p)[i];
+    if (bytes == 4) return (long long)((const int*)p)[i];
+    return ((const long long*)p)[i];
+}
+__device__ __forceinline__ void da_store_vol_label(void* __restrict__ p, int bytes, long long i, long long v) {
+    if (bytes == 1) ((unsigned char*)p)[i] = (unsigned char)v;
+    else if (bytes == 4) ((int*)p)[i] = (int)v;
+    else ((long long*)p)[i] = v;
+}
+// element i of a host-typed array as fp32, by the source-dtype code of the data path (ops.PREPROCESS_DTYPE_CODE): 0 float32, 1 float64,
+// 2 int16, 3 uint8, 4 int32
+__device__ __forceinline__ float da_load_as_f32(const void* src, int dtype, long long i) {
+    switch (dtype) {
+        case 0: return ((const float*)src)[i];
+        case 1: return (float)((const double*)src)[i];
+        case 2: return (float)((const short*)src)[i];
+        case 3: return (float)((const unsigned char*)src)[i];
+        default: return (float)((const int*)src)[i];
+    }
+}
+
 // Linear voxel index -> coordinates.  In 32-bit arithmetic whenever the index fits: a 64-bit integer division costs the VALU roughly ten
 // times the instructions of a 32-bit one, and the gather kernels (warps, label warps) did three per lane.
 __device__ __forceinline__ void da_vox4(long long v, int D, int H, int W, int& n, int& d, int& h, int& w) {
@@ -271,7 +334,7 @@ __device__ __forceinline__ void da_vox3(long long v, int H, int W, int& d, int& 
     }
 }
 
-// Jacobian of x -> x + u(x) at one voxel, u_c = disp_c (size_c - 1) / 2 voxels (the scales sx, sy, sz), disp[..][3] in NDHWC with channels
+// Jacobian of x -> x + u(x) at one voxel, u_c = disp_c (size_c - 1) / 2 voxels (the scales sx, sy, sz: da_vox_scale), disp[..][3] in NDHWC with channels
 // (x, y, z) = (W, H, D) axis: J[c][a] = delta_ca + d u_c / d a with numpy.gradient's differences at unit spacing (central inside, one-sided on
 // the faces, zero along an axis of extent 1).  q points to the voxel (d, h, w).  One definition for da_jacobian_det (regeval.hip) and the folding
 // penalty (jacpen.hip): what is printed and what is trained cannot disagree.
@@ -300,22 +363,27 @@ __device__ __forceinline__ float da_jac_det(const DaJac9& J) {
 
 // Trilinear sampling of a volume at identity + disp, as the warp defines it (warp.hip): `deform = disp + identity` with the identity of
 // lib/utils.py:97 and grid_sample(bilinear, zeros, align_corners=True)'s unnormalisation, all in fp32.  One definition for the warp family
-// (warp.hip) and the inverse-consistency composition (invcons.hip): what is warped and what is composed sample the same point.
+// (warp.hip), the inverse-consistency composition (invcons.hip), the nearest-neighbour evaluation warp and label fusion (regeval.hip) and the
+// field inversion's grid nodes and points (fieldinv.hip): what is warped, composed, evaluated and inverted sample the same point.
 struct DaTaps {
     int x0, y0, z0;
     float fx0, fx1, fy0, fy1, fz0, fz1;   // f?0 = coord - floor, f?1 = floor + 1 - coord
 };
 
-__device__ __forceinline__ float da_id_coord(int k, int size) {
-    // lib/utils.py:97: arange(size).float() / (size - 1) * 2.0 - 1
-    return (float)k / (float)(size - 1) * 2.0f - 1.0f;
+__device__ __forceinline__ float da_id_coord(float k, int size) {
+    // lib/utils.py:97: arange(size).float() / (size - 1) * 2.0 - 1; a point between the nodes has a real index k
+    return k / (float)(size - 1) * 2.0f - 1.0f;
 }
+__device__ __forceinline__ float da_id_coord(int k, int size) { return da_id_coord((float)k, size); }
+__device__ __forceinline__ float da_unnormalize(float g, int size) {
+    // grid_sampler_unnormalize(align_corners=True): ((coord + 1) / 2) * (size - 1)
+    return ((g + 1.f) / 2.f) * (float)(size - 1);
+}
+// voxels per normalised unit along an axis of `size` nodes: a displacement (or a gradient with respect to one) changes units by this factor
+__device__ __forceinline__ float da_vox_scale(int size) { return (float)(size - 1) / 2.f; }
 
 __device__ __forceinline__ DaTaps da_make_taps(float gx, float gy, float gz, int D, int H, int W) {
-    // grid_sampler_unnormalize(align_corners=True): ((coord + 1) / 2) * (size - 1)
-    const float ix = ((gx + 1.f) / 2.f) * (float)(W - 1);
-    const float iy = ((gy + 1.f) / 2.f) * (float)(H - 1);
-    const float iz = ((gz + 1.f) / 2.f) * (float)(D - 1);
+    const float ix = da_unnormalize(gx, W), iy = da_unnormalize(gy, H), iz = da_unnormalize(gz, D);
     DaTaps t;
     const float x0 = floorf(ix), y0 = floorf(iy), z0 = floorf(iz);
     t.x0 = (int)x0; t.y0 = (int)y0; t.z0 = (int)z0;

@@ -7,22 +7,12 @@
 
 namespace {
 
-__device__ __forceinline__ float load_as_f32(const void* src, int dtype, long long i) {
-    switch (dtype) {
-        case 0: return ((const float*)src)[i];
-        case 1: return (float)((const double*)src)[i];
-        case 2: return (float)((const short*)src)[i];
-        case 3: return (float)((const unsigned char*)src)[i];
-        default: return (float)((const int*)src)[i];
-    }
-}
-
 // img_np[img_np > 1] = 1; img_np[img_np < 0] = 0; np.float32(img_np)   (comparison in the source dtype, then the cast)
 __global__ void clamp01_to_f32_kernel(const void* __restrict__ src, int dtype, float* __restrict__ dst, long long n) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         float v;
         if (dtype == 1) { double d = ((const double*)src)[i]; d = d > 1.0 ? 1.0 : d; d = d < 0.0 ? 0.0 : d; v = (float)d; }
-        else { v = load_as_f32(src, dtype, i); v = v > 1.f ? 1.f : v; v = v < 0.f ? 0.f : v; }
+        else { v = da_load_as_f32(src, dtype, i); v = v > 1.f ? 1.f : v; v = v < 0.f ? 0.f : v; }
         dst[i] = v;
     }
 }

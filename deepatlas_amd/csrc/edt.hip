@@ -43,12 +43,6 @@ constexpr size_t kEdtWsTarget = (size_t)128 << 20;     // bytes per ping-pong bu
 constexpr int kBlBlocks = 1024;                        // workgroups per sample of the loss kernels, at most
 constexpr int kBlMaxC = 64;
 
-__device__ __forceinline__ long long edt_ld(const void* __restrict__ p, int bytes, long long i) {
-    if (bytes == 1) return (long long)((const unsigned char*)p)[i];
-    if (bytes == 4) return (long long)((const int*)p)[i];
-    return ((const long long*)p)[i];
-}
-
 // The W pass of one wave on one row: `site(w)` is the site predicate of voxel w of the row (called for w < W on a live wave only).  Shared by
 // the row kernels below, which differ in the predicate alone.
 template <typename Site>
@@ -96,7 +90,7 @@ edt_row_kernel(const void* __restrict__ labels, int bytes, const int* __restrict
     const long long cls = classes ? (long long)classes[g0 + g] : 0;
     const long long src = row * W;                     // = (n DH + dh) W
     const long long dst = ((n * G + g) * DH + dh) * W;
-    edt_row_body([&](int w) { return (edt_ld(labels, bytes, src + w) == cls) != (complement != 0); }, live, q, lane, W, s, out, dst, smask, sleft);
+    edt_row_body([&](int w) { return (da_load_vol_label(labels, bytes, src + w) == cls) != (complement != 0); }, live, q, lane, W, s, out, dst, smask, sleft);
 }
 
 // Surface voxel of class `cls` (the centre voxel (d, h, w) of sample `base` / V is known to carry it): some neighbour under the connectivity
@@ -112,7 +106,7 @@ __device__ __forceinline__ bool edt_on_surface(const void* __restrict__ labels, 
                 if (man == 0 || man > order) continue;
                 const int z = d + dd, y = h + dh, x = w + dw;
                 if (z < 0 || z >= D || y < 0 || y >= H || x < 0 || x >= W) return true;
-                if (edt_ld(labels, bytes, base + ((long long)z * H + y) * W + x) != cls) return true;
+                if (da_load_vol_label(labels, bytes, base + ((long long)z * H + y) * W + x) != cls) return true;
             }
     return false;
 }
@@ -134,7 +128,7 @@ edt_surface_row_kernel(const void* __restrict__ labels, int bytes, const int* __
     const long long cls = (long long)classes[g0 + g];
     const long long base = n * DH * W, src = row * W;
     const long long dst = ((n * G + g) * DH + dh) * W;
-    edt_row_body([&](int w) { return edt_ld(labels, bytes, src + w) == cls && edt_on_surface(labels, bytes, base, d, h, w, D, H, W, order, cls); },
+    edt_row_body([&](int w) { return da_load_vol_label(labels, bytes, src + w) == cls && edt_on_surface(labels, bytes, base, d, h, w, D, H, W, order, cls); },
                  live, q, lane, W, s, out, dst, smask, sleft);
 }
 
@@ -246,7 +240,7 @@ edt_line_kernel(const float* __restrict__ in, float* __restrict__ tmp, float* __
                 (last ? out : tmp)[base + (long long)i * inner] = best;
             } else {
                 if (e.mode == 2) {
-                    const bool inside = edt_ld(e.labels, e.bytes, vox0 + (long long)i * inner) == (long long)e.classes[e.g0 + (int)(o % e.G)];
+                    const bool inside = da_load_vol_label(e.labels, e.bytes, vox0 + (long long)i * inner) == (long long)e.classes[e.g0 + (int)(o % e.G)];
                     keep = inside == (e.complement != 0);
                 }
                 float r = best;
@@ -316,16 +310,6 @@ int edt_surface_passes(const void* labels, int bytes, const int* classes, int g0
 // ------------------------------------------------------------------------------------------------------------------------------
 // boundary loss
 // ------------------------------------------------------------------------------------------------------------------------------
-template <int L> __device__ __forceinline__ float bl_group_max(float v) {
-#pragma unroll
-    for (int m = 1; m < L; m <<= 1) v = fmaxf(v, __shfl_xor(v, m));
-    return v;
-}
-template <int L> __device__ __forceinline__ float bl_group_sum(float v) {
-#pragma unroll
-    for (int m = 1; m < L; m <<= 1) v += __shfl_xor(v, m);
-    return v;
-}
 // plane of class k in phi, or -1: the slot table is device data, so it is range-checked here
 __device__ __forceinline__ int bl_slot(const int* __restrict__ slots, int k, int Kp) {
     const int s = slots[k];
@@ -351,11 +335,11 @@ bl_fwd_quad_kernel(const float* __restrict__ x, const float* __restrict__ phi, c
         const long long ii = in ? i : V - 1;
         const float4 qv = reinterpret_cast<const float4*>(xn + ii * C)[sub];
         const float v[4] = {qv.x, qv.y, qv.z, qv.w};
-        const float mx = bl_group_max<L>(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
+        const float mx = da_group_max<L>(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
         float ex[4], t = 0.f;
 #pragma unroll
         for (int j = 0; j < 4; ++j) { ex[j] = expf(v[j] - mx); t += (pj[j] ? pj[j][ii] : 0.f) * ex[j]; }
-        const float se = bl_group_sum<L>(ex[0] + ex[1] + ex[2] + ex[3]);
+        const float se = da_group_sum<L>(ex[0] + ex[1] + ex[2] + ex[3]);
         if (in) dacc += (double)t / (double)se;
     }
     const double s = da_block_sum(dacc, red);
@@ -415,12 +399,12 @@ bl_bwd_quad_kernel(const float* __restrict__ x, const float* __restrict__ phi, c
         const long long ii = in ? i : V - 1;
         const float4 qv = reinterpret_cast<const float4*>(xn + ii * C)[sub];
         const float v[4] = {qv.x, qv.y, qv.z, qv.w};
-        const float mx = bl_group_max<L>(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
+        const float mx = da_group_max<L>(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
         float ex[4], f[4], t = 0.f;
 #pragma unroll
         for (int j = 0; j < 4; ++j) { ex[j] = expf(v[j] - mx); f[j] = pj[j] ? pj[j][ii] : 0.f; t += f[j] * ex[j]; }
-        const float se = bl_group_sum<L>(ex[0] + ex[1] + ex[2] + ex[3]);
-        const float S = bl_group_sum<L>(t) / se;
+        const float se = da_group_sum<L>(ex[0] + ex[1] + ex[2] + ex[3]);
+        const float S = da_group_sum<L>(t) / se;
         float d[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) d[j] = gs * (ex[j] / se) * (f[j] - S);
@@ -504,7 +488,7 @@ __host__ __device__ inline long long sd_run(long long V) { return da_cdiv(da_cdi
 // is voxel v of sample n a surface voxel of class cls in this map?
 __device__ __forceinline__ bool sd_surface_at(const void* __restrict__ labels, int bytes, long long n, long long v, long long V,
                                               int D, int H, int W, int order, long long cls) {
-    if (edt_ld(labels, bytes, n * V + v) != cls) return false;
+    if (da_load_vol_label(labels, bytes, n * V + v) != cls) return false;
     int d, h, w;
     da_vox3(v, H, W, d, h, w);
     return edt_on_surface(labels, bytes, n * V, d, h, w, D, H, W, order, cls);
@@ -516,7 +500,7 @@ sd_label_surface_kernel(const void* __restrict__ labels, int bytes, long long to
     const long long V = (long long)D * H * W;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
         const long long n = i / V, v = i % V;
-        mask[i] = sd_surface_at(labels, bytes, n, v, V, D, H, W, order, edt_ld(labels, bytes, i)) ? 1 : 0;
+        mask[i] = sd_surface_at(labels, bytes, n, v, V, D, H, W, order, da_load_vol_label(labels, bytes, i)) ? 1 : 0;
     }
 }
 

@@ -37,7 +37,7 @@ struct FiResult {
 
 __device__ __forceinline__ FiDims fi_dims(int D, int H, int W) {
     FiDims m; m.D = D; m.H = H; m.W = W;
-    m.sx = (float)(W - 1) / 2.f; m.sy = (float)(H - 1) / 2.f; m.sz = (float)(D - 1) / 2.f;
+    m.sx = da_vox_scale(W); m.sy = da_vox_scale(H); m.sz = da_vox_scale(D);
     return m;
 }
 
@@ -119,10 +119,10 @@ __device__ __forceinline__ void fi_block_reduce(FiAcc a, double (*red)[kFiStats]
     if (lane == 0) { red[wid][0] = a.mx; red[wid][1] = a.unconv; red[wid][2] = a.iters; red[wid][3] = a.out; }
     __syncthreads();
     if (threadIdx.x == 0 && row) {
-        row[0] = fmax(fmax(red[0][0], red[1][0]), fmax(red[2][0], red[3][0]));
-        row[1] = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
-        row[2] = ((red[0][2] + red[1][2]) + red[2][2]) + red[3][2];
-        row[3] = ((red[0][3] + red[1][3]) + red[2][3]) + red[3][3];
+        row[0] = da_max4(red, 0);
+        row[1] = da_sum4(red, 1);
+        row[2] = da_sum4(red, 2);
+        row[3] = da_sum4(red, 3);
     }
 }
 
@@ -154,7 +154,7 @@ fieldinv_dense_kernel(const float* __restrict__ disp, float* __restrict__ out, u
 }
 
 // one lane per point: sample n = blockIdx.y, a grid-stride over its P points (N P lanes' worth of work over the grid), so that the
-// statistics stay per sample in a fixed order.  The normalised coordinate of a point is da_id_coord's formula at a real index.
+// statistics stay per sample in a fixed order.  The normalised coordinate of a point is da_id_coord at a real index.
 // inverse: x = q + s v.  forward: one update from v = 0 gives v = -B[u](p), and p + s B[u](p) = p - s v.  The products and sums of the output
 // are not contracted, so that the host can restate them from the dense inverse.
 __global__ void __launch_bounds__(256)
@@ -172,7 +172,7 @@ fieldinv_points_kernel(const float* __restrict__ disp, const float* __restrict__
         const bool live = i < P;
         const float* q = points + ((long long)n * P + (live ? i : 0)) * 3;
         const float qx = q[0], qy = q[1], qz = q[2];
-        const float gx = qx / (float)(W - 1) * 2.0f - 1.0f, gy = qy / (float)(H - 1) * 2.0f - 1.0f, gz = qz / (float)(D - 1) * 2.0f - 1.0f;
+        const float gx = da_id_coord(qx, W), gy = da_id_coord(qy, H), gz = da_id_coord(qz, D);
         const FiResult r = fi_solve(u, m, gx, gy, gz, live, max_iters, tol_vox);
         if (live) {
             float* o = out + ((long long)n * P + i) * 3;

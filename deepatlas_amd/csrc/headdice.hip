@@ -33,9 +33,6 @@ struct HdP {
 };
 
 __device__ __forceinline__ float hd_act01(float z, float s) { return fmaxf(z, z * s); }
-__device__ __forceinline__ long long hd_label(const void* labels, int label_bytes, long long i) {
-    return label_bytes == 1 ? (long long)((const unsigned char*)labels)[i] : ((const long long*)labels)[i];
-}
 
 // packed B: wp[n][c][lane][m] = B[k = 16c + 4(lane>>4) + m][j = 16n + (lane&15)];  transposed == 0: B[k][j] = w[k*Nt + j], else w[j*Kt + k]
 __global__ void hd_pack_kernel(const float* __restrict__ w, float* __restrict__ wp, int K, int N, int transposed) {

@@ -32,7 +32,8 @@ __device__ __forceinline__ IcPoint ic_point(const float* __restrict__ ua, int d,
     return p;
 }
 
-// does the sample point leave [0, size - 1] on some axis?  (the unnormalised coordinate of da_make_taps, formed the same way)
+// does the sample point leave [0, size - 1] on some axis?  (da_unnormalize's expression, written out: the call gave the forward kernel
+// another register allocation)
 __device__ __forceinline__ bool ic_outside(const IcPoint& p, int D, int H, int W) {
     if (!p.fin) return true;
     const float ix = ((p.gx + 1.f) / 2.f) * (float)(W - 1), iy = ((p.gy + 1.f) / 2.f) * (float)(H - 1), iz = ((p.gz + 1.f) / 2.f) * (float)(D - 1);
@@ -47,7 +48,7 @@ invcons_fwd_kernel(const float* __restrict__ disp_a, const float* __restrict__ d
     const int V = D * H * W;
     const float* ua = disp_a + (long long)n * V * 3;
     const float* ub = disp_b + (long long)n * V * 3;
-    const float sx = (float)(W - 1) / 2.f, sy = (float)(H - 1) / 2.f, sz = (float)(D - 1) / 2.f;
+    const float sx = da_vox_scale(W), sy = da_vox_scale(H), sz = da_vox_scale(D);
     double s2 = 0.0, s1 = 0.0, mx = 0.0, out = 0.0;
     for (DaXcdLoop L = da_xcd_loop(V, 256); L.i < L.end; L.i += L.step) {
         const int v = (int)L.i;
@@ -83,10 +84,10 @@ invcons_fwd_kernel(const float* __restrict__ disp_a, const float* __restrict__ d
     __syncthreads();
     if (threadIdx.x == 0) {
         double* o = partial + ((size_t)n * gridDim.x + blockIdx.x) * kIcStats;
-        o[0] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
-        o[1] = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
-        o[2] = fmax(fmax(red[0][2], red[1][2]), fmax(red[2][2], red[3][2]));
-        o[3] = ((red[0][3] + red[1][3]) + red[2][3]) + red[3][3];
+        o[0] = da_sum4(red, 0);
+        o[1] = da_sum4(red, 1);
+        o[2] = da_max4(red, 2);
+        o[3] = da_sum4(red, 3);
     }
 }
 
@@ -120,7 +121,7 @@ invcons_bwd_kernel(const float* __restrict__ disp_a, const float* __restrict__ d
     const long long sb = (long long)n * V * 3;
     const float* ua = disp_a + sb;
     const float* ub = disp_b + sb;
-    const float sx = (float)(W - 1) / 2.f, sy = (float)(H - 1) / 2.f, sz = (float)(D - 1) / 2.f;
+    const float sx = da_vox_scale(W), sy = da_vox_scale(H), sz = da_vox_scale(D);
     const float gl = dloss[0] * inv_count * 2.f;
     for (DaXcdLoop L = da_xcd_loop(V, 256); L.i < L.end; L.i += L.step) {
         const int v = (int)L.i;
@@ -160,14 +161,13 @@ invcons_scatter_kernel(const float* __restrict__ disp_a, const float* __restrict
     const int V = D * H * W;
     const long long sb = (long long)n * V * 3;
     const float* ua = disp_a + sb;
-    const float sx = (float)(W - 1) / 2.f, sy = (float)(H - 1) / 2.f, sz = (float)(D - 1) / 2.f;
     const float gl = dloss[0] * inv_count * 2.f;
     for (DaXcdLoop L = da_xcd_loop((long long)V * 3, 256); L.i < L.end; L.i += L.step) {
         const int i = (int)L.i;
         const int v = (int)((unsigned)i / 3u), c = i - v * 3;
         int d, h, w; da_vox3(v, H, W, d, h, w);
         const IcPoint p = ic_point(ua + (long long)v * 3, d, h, w, D, H, W);
-        const float sc = c == 0 ? sx : (c == 1 ? sy : sz);
+        const float sc = da_vox_scale(c == 0 ? W : (c == 1 ? H : D));
         const float g = gl * (sc * sc) * resid[sb + i];
         float* base = d_disp_b + sb + c;
 #pragma unroll

@@ -30,7 +30,7 @@ jacdet_penalty_fwd_kernel(const float* __restrict__ disp, int D, int H, int W, f
     const int n = blockIdx.y;
     const int V = D * H * W;
     const float* u = disp + (long long)n * V * 3;
-    const float sx = (float)(W - 1) / 2.f, sy = (float)(H - 1) / 2.f, sz = (float)(D - 1) / 2.f;
+    const float sx = da_vox_scale(W), sy = da_vox_scale(H), sz = da_vox_scale(D);
     double s = 0.0, cnt = 0.0;
     for (DaXcdLoop L = da_xcd_loop(V, 256); L.i < L.end; L.i += L.step) {
         const int v = (int)L.i;
@@ -51,8 +51,8 @@ jacdet_penalty_fwd_kernel(const float* __restrict__ disp, int D, int H, int W, f
     __syncthreads();
     if (threadIdx.x == 0) {
         double* p = partial + ((size_t)n * gridDim.x + blockIdx.x) * kPenStats;
-        p[0] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
-        p[1] = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
+        p[0] = da_sum4(red, 0);
+        p[1] = da_sum4(red, 1);
     }
 }
 
@@ -78,7 +78,7 @@ jacdet_penalty_bwd_kernel(const float* __restrict__ disp, const float* __restric
     const float* u = disp + (long long)n * V * 3;
     const float* dt = det + (long long)n * V;
     float* du = d_disp + (long long)n * V * 3;
-    const float sx = (float)(W - 1) / 2.f, sy = (float)(H - 1) / 2.f, sz = (float)(D - 1) / 2.f;
+    const float sx = da_vox_scale(W), sy = da_vox_scale(H), sz = da_vox_scale(D);
     const float gl = dloss[0] * inv_count;
     const int HW = H * W;
     for (DaXcdLoop L = da_xcd_loop(V, 256); L.i < L.end; L.i += L.step) {

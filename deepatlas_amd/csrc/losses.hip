@@ -12,27 +12,9 @@ constexpr int kBlocks = 512;     // partial blocks per sample
 constexpr int kBendBlocks = 4096; // bending forward: 25-point stencil per element, latency-bound without occupancy
 constexpr int kDiceBlocks = 2048; // Dice forward: 8 workgroups per CU per sample (softmax latency needs the occupancy)
 
-__device__ __forceinline__ long long load_label(const void* labels, int label_bytes, long long i) {
-    return label_bytes == 1 ? (long long)((const unsigned char*)labels)[i] : ((const long long*)labels)[i];
-}
-
 // ------------------------------------------------------------------------------------------------
-// softmax helpers: LPV lanes (power of two, <= 64) own one voxel, 4 channels each.
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void group_softmax4(float (&x)[4], int lpv) {
-    float m = fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3]));
-    for (int o = 1; o < lpv; o <<= 1) m = fmaxf(m, __shfl_xor(m, o));
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { x[j] = expf(x[j] - m); s += x[j]; }
-    for (int o = 1; o < lpv; o <<= 1) s += __shfl_xor(s, o);
-    const float inv = 1.f / s;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) x[j] *= inv;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Dice forward partial sums.  partial[n][block][3][C] doubles = (I, S, T)
+// Dice forward partial sums.  partial[n][block][3][C] doubles = (I, S, T).  The vector kernels give LPV lanes (power of two, <= 64) one
+// voxel, 4 channels each; their softmax is da_group_softmax4 (common.h), shared with the fused label-warp Dice of warp.hip.
 // ------------------------------------------------------------------------------------------------
 __global__ void dice_partial_vec_kernel(const float* __restrict__ src, const void* __restrict__ labels, int label_bytes,
                                         const float* __restrict__ soft, long long V, int C, int lpv, int softmax,
@@ -51,7 +33,7 @@ __global__ void dice_partial_vec_kernel(const float* __restrict__ src, const voi
     // (and label bytes) are in flight before the first softmax's shuffles, which doubles the bytes in flight per wave.
     auto accumulate = [&](float4 a, const float* tt, long long row) {
         float p[4] = {a.x, a.y, a.z, a.w};
-        if (softmax) group_softmax4(p, lpv);
+        if (softmax) da_group_softmax4(p, lpv);
         if (prob_out) *reinterpret_cast<float4*>(prob_out + row * C + q * 4) = make_float4(p[0], p[1], p[2], p[3]);
 #pragma unroll
         for (int j = 0; j < 4; ++j) { aI[j] += p[j] * tt[j]; aS[j] += p[j]; aT[j] += tt[j]; }
@@ -61,7 +43,7 @@ __global__ void dice_partial_vec_kernel(const float* __restrict__ src, const voi
             const float4 b = *reinterpret_cast<const float4*>(soft + row * C + q * 4);
             tt[0] = b.x; tt[1] = b.y; tt[2] = b.z; tt[3] = b.w;
         } else {
-            const int lab = (int)load_label(labels, label_bytes, row) - q * 4;
+            const int lab = (int)da_load_label(labels, label_bytes, row) - q * 4;
 #pragma unroll
             for (int j = 0; j < 4; ++j) tt[j] = (lab == j) ? 1.f : 0.f;
         }
@@ -117,7 +99,7 @@ __global__ void dice_partial_gen_kernel(const float* __restrict__ src, const voi
             ssum = 0.f;
             for (int c = 0; c < C; ++c) ssum += expf(src[row * C + c] - m);
         }
-        const int lab = soft ? -1 : (int)load_label(labels, label_bytes, row);
+        const int lab = soft ? -1 : (int)da_load_label(labels, label_bytes, row);
         for (int c = 0; c < C; ++c) {
             float p = src[row * C + c];
             if (softmax) p = expf(p - m) / ssum;
@@ -216,13 +198,13 @@ __global__ void dice_bwd_vec_kernel(const float* __restrict__ src, const void* _
         const int n = (int)(row / V);
         const float4 a = *reinterpret_cast<const float4*>(src + row * C + q * 4);
         float p[4] = {a.x, a.y, a.z, a.w};
-        if (softmax) group_softmax4(p, lpv);
+        if (softmax) da_group_softmax4(p, lpv);
         float t[4];
         if (soft) {
             const float4 b = *reinterpret_cast<const float4*>(soft + row * C + q * 4);
             t[0] = b.x; t[1] = b.y; t[2] = b.z; t[3] = b.w;
         } else {
-            const int lab = (int)load_label(labels, label_bytes, row) - q * 4;
+            const int lab = (int)da_load_label(labels, label_bytes, row) - q * 4;
 #pragma unroll
             for (int j = 0; j < 4; ++j) t[j] = (lab == j) ? 1.f : 0.f;
         }
@@ -250,7 +232,7 @@ __global__ void dice_bwd_gen_kernel(const float* __restrict__ src, const void* _
     const int NC = N * C;
     for (long long row = (long long)blockIdx.x * blockDim.x + threadIdx.x; row < total; row += (long long)gridDim.x * blockDim.x) {
         const int n = (int)(row / V);
-        const int lab = soft ? -1 : (int)load_label(labels, label_bytes, row);
+        const int lab = soft ? -1 : (int)da_load_label(labels, label_bytes, row);
         float m = -INFINITY, ssum = 1.f, dot = 0.f;
         if (softmax) {
             for (int c = 0; c < C; ++c) m = fmaxf(m, src[row * C + c]);
@@ -279,7 +261,7 @@ __global__ void softmax_fwd_kernel(const float* __restrict__ x, float* __restric
             const int q = (int)(i % lpv); const long long row = i / lpv;
             const float4 a = *reinterpret_cast<const float4*>(x + row * C + q * 4);
             float p[4] = {a.x, a.y, a.z, a.w};
-            group_softmax4(p, lpv);
+            da_group_softmax4(p, lpv);
             *reinterpret_cast<float4*>(y + row * C + q * 4) = make_float4(p[0], p[1], p[2], p[3]);
         }
     } else {
@@ -317,7 +299,7 @@ __global__ void one_hot_kernel(const void* __restrict__ labels, int label_bytes,
     const long long total = M * C;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const long long row = i / C; const int c = (int)(i % C);
-        out[i] = ((int)load_label(labels, label_bytes, row) == c) ? 1.f : 0.f;
+        out[i] = ((int)da_load_label(labels, label_bytes, row) == c) ? 1.f : 0.f;
     }
 }
 
@@ -649,7 +631,7 @@ __global__ void argmax_counts_kernel(const float* __restrict__ logits, const voi
             for (int c = 1; c < C; ++c) { const float a = logits[row * C + c]; if (a > best) { best = a; bi = c; } }
         }
         if (q == 0) {
-            const int t = (int)load_label(truth, label_bytes, row);
+            const int t = (int)da_load_label(truth, label_bytes, row);
             atomicAdd(&shc[bi], 1u);
             if (t >= 0 && t < C) atomicAdd(&shc[C + t], 1u);
             if (t == bi) atomicAdd(&shc[2 * C + bi], 1u);
@@ -689,7 +671,7 @@ __global__ void label_overlap_counts_kernel(const void* __restrict__ pred, int p
         int pl = -1, tl = -1; unsigned int len = 0u;
         for (int k = 0; k < cnt; ++k) {
             const long long row = (long long)n * V + v0 + k;
-            const int a = (int)load_label(pred, pred_bytes, row), b = (int)load_label(truth, truth_bytes, row);
+            const int a = (int)da_load_label(pred, pred_bytes, row), b = (int)da_load_label(truth, truth_bytes, row);
             if (a != pl || b != tl) { flush(pl, tl, len); pl = a; tl = b; len = 0u; }
             ++len;
         }

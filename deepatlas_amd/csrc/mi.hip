@@ -123,7 +123,7 @@ __global__ void __launch_bounds__(256) mi_reduce_kernel(const double* __restrict
     for (int bk = q; bk < nblocks; bk += 4) s += src[(size_t)bk * 1024];
     red[q][threadIdx.x & 63] = s;
     __syncthreads();
-    if (q == 0) psum[(size_t)n * 1024 + e] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+    if (q == 0) psum[(size_t)n * 1024 + e] = da_sum4(red, threadIdx.x);
 }
 
 // one workgroup of 1024 threads, thread (i, j); samples one after the other.  stats[n] = G[32][32] | ga[32] | gb[32] | MI, 0...

@@ -19,17 +19,8 @@ constexpr int PP_HIST_GROUPS = 512;         // workgroups of the histogram passe
 constexpr int PP_BINS = 2048;               // 11-bit digits (the last digit has 10 bits)
 constexpr int PP_MAX_RANKS = 4;             // two percentiles, two neighbouring order statistics each
 
-__device__ __forceinline__ float pp_load_f32(const void* src, int dtype, long long i) {
-    switch (dtype) {
-        case 0: return ((const float*)src)[i];
-        case 1: return (float)((const double*)src)[i];
-        case 2: return (float)((const short*)src)[i];
-        case 3: return (float)((const unsigned char*)src)[i];
-        default: return (float)((const int*)src)[i];
-    }
-}
 __device__ __forceinline__ double pp_load_f64(const void* src, int dtype, long long i) {
-    return dtype == 1 ? ((const double*)src)[i] : (double)pp_load_f32(src, dtype, i);
+    return dtype == 1 ? ((const double*)src)[i] : (double)da_load_as_f32(src, dtype, i);
 }
 
 // ---- 3a. axis-aligned resample ---------------------------------------------------------------------------------------------------
@@ -64,10 +55,10 @@ __global__ void resample_linear_kernel(const void* __restrict__ src, int dtype, 
             const long long r00 = ((base + d0) * H + h0) * W, r01 = ((base + d0) * H + h1) * W;
             const long long r10 = ((base + d1) * H + h0) * W, r11 = ((base + d1) * H + h1) * W;
             float a, b;
-            a = pp_load_f32(src, dtype, r00 + w0); b = pp_load_f32(src, dtype, r00 + w1); const float x00 = fmaf(fw, b - a, a);
-            a = pp_load_f32(src, dtype, r01 + w0); b = pp_load_f32(src, dtype, r01 + w1); const float x01 = fmaf(fw, b - a, a);
-            a = pp_load_f32(src, dtype, r10 + w0); b = pp_load_f32(src, dtype, r10 + w1); const float x10 = fmaf(fw, b - a, a);
-            a = pp_load_f32(src, dtype, r11 + w0); b = pp_load_f32(src, dtype, r11 + w1); const float x11 = fmaf(fw, b - a, a);
+            a = da_load_as_f32(src, dtype, r00 + w0); b = da_load_as_f32(src, dtype, r00 + w1); const float x00 = fmaf(fw, b - a, a);
+            a = da_load_as_f32(src, dtype, r01 + w0); b = da_load_as_f32(src, dtype, r01 + w1); const float x01 = fmaf(fw, b - a, a);
+            a = da_load_as_f32(src, dtype, r10 + w0); b = da_load_as_f32(src, dtype, r10 + w1); const float x10 = fmaf(fw, b - a, a);
+            a = da_load_as_f32(src, dtype, r11 + w0); b = da_load_as_f32(src, dtype, r11 + w1); const float x11 = fmaf(fw, b - a, a);
             const float y0 = fmaf(fh, x01 - x00, x00), y1 = fmaf(fh, x11 - x10, x10);
             v = fmaf(fd, y1 - y0, y0);
         }
@@ -165,7 +156,7 @@ __global__ void select_hist_kernel(const void* __restrict__ src, int dtype, long
     unsigned pre[PP_MAX_RANKS];
     for (int r = 0; r < PP_MAX_RANKS; ++r) pre[r] = (pass > 0 && r < nranks) ? st->prefix[r] : 0u;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const float x = pp_load_f32(src, dtype, i);
+        const float x = da_load_as_f32(src, dtype, i);
         if (x != x) { if (pass == 0) atomicAdd(&lnan, 1u); continue; }
         const unsigned key = pp_key(x);
         const unsigned digit = (key >> shift) & mask;
@@ -245,7 +236,7 @@ __global__ void affine_intensity_kernel(const void* __restrict__ src, int dtype,
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         float y = 0.f;
         if (b != 0.f) {
-            const float x = pp_load_f32(src, dtype, i);
+            const float x = da_load_as_f32(src, dtype, i);
             y = (x - a) / b;
             if (clamp01) { y = y > 1.f ? 1.f : y; y = y < 0.f ? 0.f : y; }
         }

@@ -12,20 +12,14 @@ namespace {
 constexpr int kJacBlocks = 2048;   // Jacobian partial blocks per sample (multiple of 8: XCD-contiguous split)
 constexpr int kJacStats = 5;       // per-block partials: sum(det - 1), sum((det - 1)^2), min, max, #(det <= 0)
 
-__device__ __forceinline__ long long load_label(const void* labels, int label_bytes, long long i) {
-    return label_bytes == 1 ? (long long)((const unsigned char*)labels)[i] : ((const long long*)labels)[i];
-}
-
-// the fp32 expressions of warp.hip (id_coord / make_taps), so that the training warp and this evaluation sample the same coordinate
-__device__ __forceinline__ float id_coord(int k, int size) { return (float)k / (float)(size - 1) * 2.0f - 1.0f; }
-__device__ __forceinline__ float unnormalize(float g, int size) { return ((g + 1.f) / 2.f) * (float)(size - 1); }
-
-// index of the moving voxel the target voxel (d, h, w) reads, or -1 (outside the volume, or a non-finite coordinate): every axis rounded
-// half-to-even (rintf in the default rounding mode = ATen's nearbyint), then the bounds test of padding_mode='zeros'
+// index of the moving voxel the target voxel (d, h, w) reads, or -1 (outside the volume, or a non-finite coordinate): the training warp's
+// own coordinate (da_id_coord / da_unnormalize, common.h), every axis rounded half-to-even (rintf in the default rounding mode = ATen's
+// nearbyint), then the bounds test of padding_mode='zeros'.  (The finiteness test is da_is_finite_coord's, written out: the call gave the
+// fusion kernels another register allocation.)
 __device__ __forceinline__ int nearest_source(float ux, float uy, float uz, int d, int h, int w, int D, int H, int W) {
-    const float gx = ux + id_coord(w, W), gy = uy + id_coord(h, H), gz = uz + id_coord(d, D);
+    const float gx = ux + da_id_coord(w, W), gy = uy + da_id_coord(h, H), gz = uz + da_id_coord(d, D);
     if (!(fabsf(gx) < 1e9f && fabsf(gy) < 1e9f && fabsf(gz) < 1e9f)) return -1;      // NaN / inf: reads 0
-    const float x = rintf(unnormalize(gx, W)), y = rintf(unnormalize(gy, H)), z = rintf(unnormalize(gz, D));
+    const float x = rintf(da_unnormalize(gx, W)), y = rintf(da_unnormalize(gy, H)), z = rintf(da_unnormalize(gz, D));
     if (!(x >= 0.f && x <= (float)(W - 1) && y >= 0.f && y <= (float)(H - 1) && z >= 0.f && z <= (float)(D - 1))) return -1;
     return ((int)z * H + (int)y) * W + (int)x;
 }
@@ -80,7 +74,7 @@ warp_nearest_counts_kernel(const void* __restrict__ lab_m, int m_bytes, const vo
         unsigned char m[RUN];
 #pragma unroll
         for (int k = 0; k < RUN; ++k)      // (the RUN gathers are independent: issued back to back)
-            m[k] = src[k] >= 0 ? (unsigned char)load_label(lab_m, m_bytes, sample + src[k]) : (unsigned char)0;
+            m[k] = src[k] >= 0 ? (unsigned char)da_load_label(lab_m, m_bytes, sample + src[k]) : (unsigned char)0;
         if (warped) {
             if (VEC) {
                 *reinterpret_cast<uchar4*>(warped + sample + v0) = make_uchar4(m[0], m[1], m[2], m[3]);
@@ -96,7 +90,7 @@ warp_nearest_counts_kernel(const void* __restrict__ lab_m, int m_bytes, const vo
                 t[0] = tt.x; t[1] = tt.y; t[2] = tt.z; t[3] = tt.w;
             } else {
 #pragma unroll
-                for (int k = 0; k < RUN; ++k) t[k] = (k < cnt) ? (int)load_label(lab_t, t_bytes, sample + v0 + k) : -1;
+                for (int k = 0; k < RUN; ++k) t[k] = (k < cnt) ? (int)da_load_label(lab_t, t_bytes, sample + v0 + k) : -1;
             }
             int pl = -1, tl = -1; unsigned int len = 0u;
 #pragma unroll
@@ -134,7 +128,7 @@ jacobian_det_kernel(const float* __restrict__ disp, int D, int H, int W, float* 
     const int n = blockIdx.y;
     const int V = D * H * W;
     const float* u = disp + (long long)n * V * 3;
-    const float sx = (float)(W - 1) / 2.f, sy = (float)(H - 1) / 2.f, sz = (float)(D - 1) / 2.f;
+    const float sx = da_vox_scale(W), sy = da_vox_scale(H), sz = da_vox_scale(D);
     double s1 = 0.0, s2 = 0.0, cnt = 0.0;
     float mn = INFINITY, mx = -INFINITY;
     for (DaXcdLoop L = da_xcd_loop(V, 256); L.i < L.end; L.i += L.step) {
@@ -155,11 +149,11 @@ jacobian_det_kernel(const float* __restrict__ disp, int D, int H, int W, float* 
     __syncthreads();
     if (threadIdx.x == 0) {
         double* p = partial + ((size_t)n * gridDim.x + blockIdx.x) * kJacStats;
-        p[0] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
-        p[1] = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
+        p[0] = da_sum4(red, 0);
+        p[1] = da_sum4(red, 1);
         p[2] = fmin(fmin(red[0][2], red[1][2]), fmin(red[2][2], red[3][2]));
-        p[3] = fmax(fmax(red[0][3], red[1][3]), fmax(red[2][3], red[3][3]));
-        p[4] = ((red[0][4] + red[1][4]) + red[2][4]) + red[3][4];
+        p[3] = da_max4(red, 3);
+        p[4] = da_sum4(red, 4);
     }
 }
 
@@ -273,7 +267,7 @@ label_fusion_vote_kernel(const void* __restrict__ labels, int label_bytes, long 
                 unsigned m[RUN];
 #pragma unroll
                 for (int j = 0; j < RUN; ++j)      // (independent gathers: issued back to back)
-                    m[j] = src[j] >= 0 ? (unsigned)(unsigned char)load_label(labels, label_bytes, lab0 + src[j]) : 0u;
+                    m[j] = src[j] >= 0 ? (unsigned)(unsigned char)da_load_label(labels, label_bytes, lab0 + src[j]) : 0u;
 #pragma unroll
                 for (int j = 0; j < RUN; ++j) pk[j][k >> 2] |= m[j] << ((k & 3) * 8);
                 if (WMODE == 2) {

@@ -250,9 +250,9 @@ __global__ void warp_bwd_kernel(const float* __restrict__ dout, const float* __r
             }
             if (q == 0) {
                 // grad wrt normalised coords: * (size - 1) / 2 ; d deform / d disp = 1
-                d_disp[v * 3 + 0] = gix * ((float)(W - 1) / 2.f);
-                d_disp[v * 3 + 1] = giy * ((float)(H - 1) / 2.f);
-                d_disp[v * 3 + 2] = giz * ((float)(D - 1) / 2.f);
+                d_disp[v * 3 + 0] = gix * da_vox_scale(W);
+                d_disp[v * 3 + 1] = giy * da_vox_scale(H);
+                d_disp[v * 3 + 2] = giz * da_vox_scale(D);
             }
         }
     }
@@ -346,9 +346,6 @@ __global__ void fixed_to_float_kernel(const unsigned long long* __restrict__ acc
 // Warp of a LABEL map as if it were its one-hot encoding (the joint step's registration phase warps one-hot(seg_m) with the
 // predicted field): out[v][c] = sum_k w_k [label[corner_k] == c].  The 32-channel one-hot tensor (629 MB per
 // volume) is never materialised: 8 label bytes are read per voxel instead of 8 x 128 bytes.  One lane per channel.
-__device__ __forceinline__ int warp_label_at(const void* lab, int label_bytes, long long i) {
-    return label_bytes == 1 ? (int)((const unsigned char*)lab)[i] : (int)((const long long*)lab)[i];
-}
 
 template <int VEC>
 __global__ void warp_labels_fwd_kernel(const void* __restrict__ labels, int label_bytes, const float* __restrict__ disp,
@@ -373,7 +370,7 @@ __global__ void warp_labels_fwd_kernel(const void* __restrict__ labels, int labe
             const int x = t.x0 + cx, y = t.y0 + cy, z = t.z0 + cz;
             if (x >= 0 && x < W && y >= 0 && y < H && z >= 0 && z < D) {
                 const float wgt = (cx ? t.fx0 : t.fx1) * (cy ? t.fy0 : t.fy1) * (cz ? t.fz0 : t.fz1);
-                const int rel = warp_label_at(labels, label_bytes, sbase + ((long long)z * H + y) * W + x) - c0;
+                const int rel = da_load_label<int>(labels, label_bytes, sbase + ((long long)z * H + y) * W + x) - c0;
 #pragma unroll
                 for (int j = 0; j < VEC; ++j) acc[j] += (rel == j) ? wgt : 0.f;
             }
@@ -404,16 +401,16 @@ __global__ void warp_labels_bwd_kernel(const float* __restrict__ dout, const voi
             const int x = t.x0 + cx, y = t.y0 + cy, z = t.z0 + cz;
             if (x >= 0 && x < W && y >= 0 && y < H && z >= 0 && z < D) {
                 const float wx = cx ? t.fx0 : t.fx1, wy = cy ? t.fy0 : t.fy1, wz = cz ? t.fz0 : t.fz1;
-                const int lab = warp_label_at(labels, label_bytes, sbase + ((long long)z * H + y) * W + x);
+                const int lab = da_load_label<int>(labels, label_bytes, sbase + ((long long)z * H + y) * W + x);
                 const float dot = (lab >= 0 && lab < C) ? dout[v * C + lab] : 0.f;
                 gix += (cx ? dot : -dot) * wy * wz;
                 giy += (cy ? dot : -dot) * wx * wz;
                 giz += (cz ? dot : -dot) * wx * wy;
             }
         }
-        d_disp[v * 3 + 0] = gix * ((float)(W - 1) / 2.f);
-        d_disp[v * 3 + 1] = giy * ((float)(H - 1) / 2.f);
-        d_disp[v * 3 + 2] = giz * ((float)(D - 1) / 2.f);
+        d_disp[v * 3 + 0] = gix * da_vox_scale(W);
+        d_disp[v * 3 + 1] = giy * da_vox_scale(H);
+        d_disp[v * 3 + 2] = giz * da_vox_scale(D);
     }
 }
 
@@ -471,7 +468,7 @@ __global__ void __launch_bounds__(256) warp_dice_partial_kernel(const float* __r
                 acc.x += a.x * wgt; acc.y += a.y * wgt; acc.z += a.z * wgt; acc.w += a.w * wgt;
             }
         }
-        const int rel = warp_label_at(lab_t, bt, (long long)n * V + v) - q * 4;
+        const int rel = da_load_label<int>(lab_t, bt, (long long)n * V + v) - q * 4;
         const float pv[4] = {acc.x, acc.y, acc.z, acc.w};
 #pragma unroll
         for (int j = 0; j < 4; ++j) { const float tt = (rel == j) ? 1.f : 0.f; aI[j] += pv[j] * tt; aS[j] += pv[j]; aT[j] += tt; }
@@ -511,7 +508,7 @@ __global__ void __launch_bounds__(256) warp_dice_grouped_kernel(const float* __r
             int d, h, w; da_vox3(v, H, W, d, h, w);
             const float* u = disp + ((long long)n * V + v) * 3;
             gx = u[0] + da_id_coord(w, W); gy = u[1] + da_id_coord(h, H); gz = u[2] + da_id_coord(d, D);
-            lab = warp_label_at(lab_t, bt, (long long)n * V + v);
+            lab = da_load_label<int>(lab_t, bt, (long long)n * V + v);
         }
         const GatherPlan p = gather_plan(gx, gy, gz, live, D, H, W, C);
         gather_walk(sb, p, lpv, vpw, gl, q, H, W, C, [&](int sl, const float4 acc) {
@@ -589,7 +586,7 @@ __global__ void __launch_bounds__(256) label_warp_dice_partial_kernel(const void
         const float gx = u[0] + da_id_coord(w, W), gy = u[1] + da_id_coord(h, H), gz = u[2] + da_id_coord(d, D);
         const bool fin = da_is_finite_coord(gx, gy, gz);
         const DaTaps t = da_make_taps(fin ? gx : -4.f, fin ? gy : -4.f, fin ? gz : -4.f, D, H, W);
-        int tl = warp_label_at(lab_t, bt, sb + vv);
+        int tl = da_load_label<int>(lab_t, bt, sb + vv);
         if (!live || tl < 0 || tl >= C) tl = -1;
         int lab[8]; float wk[8];
 #pragma unroll
@@ -599,7 +596,7 @@ __global__ void __launch_bounds__(256) label_warp_dice_partial_kernel(const void
             lab[k] = -1; wk[k] = 0.f;
             if (live && x >= 0 && x < W && y >= 0 && y < H && z >= 0 && z < D) {
                 wk[k] = (cx ? t.fx0 : t.fx1) * (cy ? t.fy0 : t.fy1) * (cz ? t.fz0 : t.fz1);
-                const int l = warp_label_at(lab_m, bm, sb + ((long long)z * H + y) * W + x);
+                const int l = da_load_label<int>(lab_m, bm, sb + ((long long)z * H + y) * W + x);
                 lab[k] = (l >= 0 && l < C) ? l : -1;
             }
         }
@@ -653,7 +650,7 @@ __global__ void label_warp_dice_bwd_kernel(const void* __restrict__ lab_m, int b
         const bool fin = da_is_finite_coord(gx, gy, gz);
         const DaTaps t = da_make_taps(fin ? gx : -4.f, fin ? gy : -4.f, fin ? gz : -4.f, D, H, W);
         const long long sbase = (long long)n * V;
-        const int tl = warp_label_at(lab_t, bt, v);
+        const int tl = da_load_label<int>(lab_t, bt, v);
         float gix = 0.f, giy = 0.f, giz = 0.f;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
@@ -661,7 +658,7 @@ __global__ void label_warp_dice_bwd_kernel(const void* __restrict__ lab_m, int b
             const int x = t.x0 + cx, y = t.y0 + cy, z = t.z0 + cz;
             if (x >= 0 && x < W && y >= 0 && y < H && z >= 0 && z < D) {
                 const float wx = cx ? t.fx0 : t.fx1, wy = cy ? t.fy0 : t.fy1, wz = cz ? t.fz0 : t.fz1;
-                const int lab = warp_label_at(lab_m, bm, sbase + ((long long)z * H + y) * W + x);
+                const int lab = da_load_label<int>(lab_m, bm, sbase + ((long long)z * H + y) * W + x);
                 float dot = 0.f;
                 if (lab >= 0 && lab < C) dot = gl * (coef[n * C + lab] * (lab == tl ? 1.f : 0.f) + coef[NC + n * C + lab]);
                 gix += (cx ? dot : -dot) * wy * wz;
@@ -669,9 +666,9 @@ __global__ void label_warp_dice_bwd_kernel(const void* __restrict__ lab_m, int b
                 giz += (cz ? dot : -dot) * wx * wy;
             }
         }
-        d_disp[v * 3 + 0] = gix * ((float)(W - 1) / 2.f);
-        d_disp[v * 3 + 1] = giy * ((float)(H - 1) / 2.f);
-        d_disp[v * 3 + 2] = giz * ((float)(D - 1) / 2.f);
+        d_disp[v * 3 + 0] = gix * da_vox_scale(W);
+        d_disp[v * 3 + 1] = giy * da_vox_scale(H);
+        d_disp[v * 3 + 2] = giz * da_vox_scale(D);
     }
 }
 
@@ -701,7 +698,7 @@ __global__ void warp_adjoint_labels_kernel(const void* __restrict__ lab_t, int b
         const float gz = inr ? disp[v * 3 + 2] + da_id_coord(d, D) : 0.f;
         const bool live = inr && da_is_finite_coord(gx, gy, gz);
         const DaTaps t = da_make_taps(live ? gx : 0.f, live ? gy : 0.f, live ? gz : 0.f, D, H, W);
-        const int lab = inr ? warp_label_at(lab_t, bt, v) : -1;
+        const int lab = inr ? da_load_label<int>(lab_t, bt, v) : -1;
         const bool lok = lab >= 0 && lab < C;
         // this lane's cell, as one comparable key per (n, label, z0, y0) and the x0 beside it
         const bool inbox = live && t.z0 >= -1 && t.z0 < D && t.y0 >= -1 && t.y0 < H;      // (cells with no corner row inside the volume never merge)
@@ -759,7 +756,7 @@ __global__ void __launch_bounds__(256) warp_adjoint_labels_box_kernel(const void
         const float gx = disp[v * 3 + 0] + da_id_coord(x, W), gy = disp[v * 3 + 1] + da_id_coord(y, H), gz = disp[v * 3 + 2] + da_id_coord(z, D);
         if (!da_is_finite_coord(gx, gy, gz)) continue;
         const DaTaps t = da_make_taps(gx, gy, gz, D, H, W);
-        const int lab = warp_label_at(lab_t, bt, v);
+        const int lab = da_load_label<int>(lab_t, bt, v);
         const bool lok = lab >= 0 && lab < C;
         float* plane = lok ? B + ((long long)n * C + lab) * V : (A_extra ? A_extra + sbase : nullptr);
         if (!plane) continue;
@@ -836,7 +833,7 @@ __global__ void __launch_bounds__(256) seg_anat_dlogits_kernel(const float* __re
             for (int k = 1; k < lpv; k <<= 1) a += __shfl_xor(a, k);
             if (A) a += A[row];
             const float p[4] = {pv.x, pv.y, pv.z, pv.w};
-            const int lab = (coef_s && lab_m) ? warp_label_at(lab_m, bm, row) - q * 4 : -1;
+            const int lab = (coef_s && lab_m) ? da_load_label<int>(lab_m, bm, row) - q * 4 : -1;
             float g[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -879,7 +876,7 @@ __global__ void __launch_bounds__(256) seg_anat_dlogits_lane_kernel(const float*
             const float4 v = *reinterpret_cast<const float4*>(prob + row * CC + q * 4);
             p[4 * q] = v.x; p[4 * q + 1] = v.y; p[4 * q + 2] = v.z; p[4 * q + 3] = v.w;
         }
-        const int lab = (coef_s && lab_m) ? warp_label_at(lab_m, bm, row) : -1;
+        const int lab = (coef_s && lab_m) ? da_load_label<int>(lab_m, bm, row) : -1;
         float dot = 0.f;
 #pragma unroll
         for (int c = 0; c < CC; ++c) {
@@ -904,20 +901,9 @@ __global__ void __launch_bounds__(256) seg_anat_dlogits_lane_kernel(const float*
 // label_warp_dice_partial_kernel.  A wave takes 64 consecutive voxels: every lane derives ONE voxel's eight (weight, label) pairs into the wave's
 // LDS rows -- the C / 4 lanes of a voxel do not each repeat the divisions, the floor and the eight label reads -- and the wave then walks the
 // 64 x C dense block in LPV coalesced 1 KB pieces (16 bytes per lane, issued before the taps are derived), lane (voxel, channel quad) forming
-// its four W_c from the voxel's row.  No atomics: per-lane fp32 sums, combined in double in a fixed order per workgroup.
+// its four W_c from the voxel's row.  No atomics: per-lane fp32 sums, combined in double in a fixed order per workgroup.  The softmax of
+// ROLE 1 is da_group_softmax4 (common.h), the one the Dice kernels of losses.hip apply to the same logits.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void softwarp_softmax4(float (&x)[4], int lpv) {      // group_softmax4 of losses.hip: the same expressions
-    float m = fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3]));
-    for (int o = 1; o < lpv; o <<= 1) m = fmaxf(m, __shfl_xor(m, o));
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { x[j] = expf(x[j] - m); s += x[j]; }
-    for (int o = 1; o < lpv; o <<= 1) s += __shfl_xor(s, o);
-    const float inv = 1.f / s;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) x[j] *= inv;
-}
-
 struct alignas(16) SoftwarpRows { float w[4][64][8]; unsigned char l[4][64][8]; };      // per wave: 64 voxels x 8 corners (label 255: counts for no class)
 
 // voxel v of sample n (first voxel sb = n V) -> its row: corner weights (0 where the corner is outside the volume) and corner labels
@@ -937,7 +923,7 @@ __device__ __forceinline__ void softwarp_plan(const void* __restrict__ lab_m, in
         unsigned int lb = 255u;
         if (live && x >= 0 && x < W && y >= 0 && y < H && z >= 0 && z < D) {
             wk[k] = (cx ? t.fx0 : t.fx1) * (cy ? t.fy0 : t.fy1) * (cz ? t.fz0 : t.fz1);
-            const int l = warp_label_at(lab_m, bm, sb + ((long long)z * H + y) * W + x);
+            const int l = da_load_label<int>(lab_m, bm, sb + ((long long)z * H + y) * W + x);
             if (l >= 0 && l < C) lb = (unsigned int)l;
         }
         if (k < 4) lo |= lb << (8 * k); else hi |= lb << (8 * (k - 4));
@@ -1003,7 +989,7 @@ __global__ void __launch_bounds__(256) softwarp_dice_partial_kernel(const void* 
         for (int j = 0; j < LPV; ++j) {
             const int sl = j * VPW + gl;
             float x[4] = {xs[j].x, xs[j].y, xs[j].z, xs[j].w};
-            if (ROLE == 1) softwarp_softmax4(x, LPV);                      // (whole voxel groups are live or not: every lane of a group takes part)
+            if (ROLE == 1) da_group_softmax4(x, LPV);                      // (whole voxel groups are live or not: every lane of a group takes part)
             float Wq[4];
             softwarp_quad(rows.w[wave][sl], rows.l[wave][sl], q * 4, Wq);
             if (vb + sl < v1) {
@@ -1055,7 +1041,7 @@ __global__ void __launch_bounds__(256) softwarp_dice_dlogits_kernel(const void* 
         for (int j = 0; j < LPV; ++j) {
             const int sl = j * VPW + gl;
             float p[4] = {xs[j].x, xs[j].y, xs[j].z, xs[j].w};
-            softwarp_softmax4(p, LPV);
+            da_group_softmax4(p, LPV);
             float Wq[4], g[4];
             softwarp_quad(rows.w[wave][sl], rows.l[wave][sl], q * 4, Wq);
 #pragma unroll
@@ -1093,7 +1079,7 @@ __global__ void softwarp_dice_bwd_disp_kernel(const void* __restrict__ lab_m, in
             const int x = t.x0 + cx, y = t.y0 + cy, z = t.z0 + cz;
             if (x >= 0 && x < W && y >= 0 && y < H && z >= 0 && z < D) {
                 const float wx = cx ? t.fx0 : t.fx1, wy = cy ? t.fy0 : t.fy1, wz = cz ? t.fz0 : t.fz1;
-                const int lab = warp_label_at(lab_m, bm, sbase + ((long long)z * H + y) * W + x);
+                const int lab = da_load_label<int>(lab_m, bm, sbase + ((long long)z * H + y) * W + x);
                 float dot = 0.f;
                 if (lab >= 0 && lab < C) dot = gl * (coef[n * C + lab] * X[v * C + lab] + coef[NC + n * C + lab]);
                 gix += (cx ? dot : -dot) * wy * wz;
@@ -1101,9 +1087,9 @@ __global__ void softwarp_dice_bwd_disp_kernel(const void* __restrict__ lab_m, in
                 giz += (cz ? dot : -dot) * wx * wy;
             }
         }
-        d_disp[v * 3 + 0] = gix * ((float)(W - 1) / 2.f);
-        d_disp[v * 3 + 1] = giy * ((float)(H - 1) / 2.f);
-        d_disp[v * 3 + 2] = giz * ((float)(D - 1) / 2.f);
+        d_disp[v * 3 + 0] = gix * da_vox_scale(W);
+        d_disp[v * 3 + 1] = giy * da_vox_scale(H);
+        d_disp[v * 3 + 2] = giz * da_vox_scale(D);
     }
 }
 

@@ -10,10 +10,6 @@ namespace {
 constexpr int kXentBlocks = 2048;
 constexpr int kMaxC = 64;
 
-__device__ __forceinline__ long long xe_label(const void* labels, int label_bytes, long long i) {
-    return label_bytes == 1 ? (long long)((const unsigned char*)labels)[i] : ((const long long*)labels)[i];
-}
-
 struct XentCfg {
     int mode;            // 0 cross_entropy, 1 focal, 2 soft cross entropy
     int softmax;         // focal: P = softmax(x) (1) or x (0); soft CE: log_softmax(x) (1) or log(max(x, 1e-8)) (0)
@@ -80,7 +76,7 @@ __global__ void xent_fwd_kernel(const float* __restrict__ x, const void* __restr
     __shared__ double red[4];
     float acc = 0.f; float cnt = 0.f; double dacc = 0.0, dcnt = 0.0; int k = 0;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < M; i += (long long)gridDim.x * blockDim.x) {
-        const long long lab = labels ? xe_label(labels, label_bytes, i) : 0;
+        const long long lab = labels ? da_load_label(labels, label_bytes, i) : 0;
         acc += xent_voxel<false>(x + i * C, C, lab, soft ? soft + i * C : nullptr, alpha, cfg, 0.f, nullptr);
         if (cfg.mode == 0 && lab != cfg.ignore && lab >= 0 && lab < C) cnt += 1.f;
         if (++k == 16) { dacc += (double)acc; dcnt += (double)cnt; acc = 0.f; cnt = 0.f; k = 0; }
@@ -111,7 +107,7 @@ __global__ void xent_bwd_kernel(const float* __restrict__ x, const void* __restr
                                 float* __restrict__ dx, long long M, int C, XentCfg cfg) {
     const float gscale = dloss[0] / denom[0];
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < M; i += (long long)gridDim.x * blockDim.x) {
-        const long long lab = labels ? xe_label(labels, label_bytes, i) : 0;
+        const long long lab = labels ? da_load_label(labels, label_bytes, i) : 0;
         xent_voxel<true>(x + i * C, C, lab, soft ? soft + i * C : nullptr, alpha, cfg, gscale, dx + i * C);
     }
 }
@@ -121,25 +117,14 @@ __global__ void xent_bwd_kernel(const float* __restrict__ x, const void* __restr
 // (1 KiB contiguous), the logits never leave registers, and max / sum-exp / the target's logit travel across the L lanes by xor shuffles.
 // (The thread-per-voxel form above reads at a C * 4-byte lane stride and indexes a private array with the label: 0.07 of HBM.)
 // ------------------------------------------------------------------------------------------------------------------------------
-template <int L> __device__ __forceinline__ float xe_group_max(float v) {
-#pragma unroll
-    for (int m = 1; m < L; m <<= 1) v = fmaxf(v, __shfl_xor(v, m));
-    return v;
-}
-template <int L> __device__ __forceinline__ float xe_group_sum(float v) {
-#pragma unroll
-    for (int m = 1; m < L; m <<= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
 // returns the voxel's loss value (the same on all L lanes); BWD: this lane's quad of d loss / d logits
 template <int L, bool BWD>
 __device__ __forceinline__ float xent_quad(const float4 q, int sub, long long lab, const float4 sq, const float* __restrict__ alpha,
                                            const XentCfg cfg, float gscale, float4& dq) {
     const int C = 4 * L;
     const float v[4] = {q.x, q.y, q.z, q.w};
-    const float mx = xe_group_max<L>(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
-    const float se = xe_group_sum<L>(expf(v[0] - mx) + expf(v[1] - mx) + expf(v[2] - mx) + expf(v[3] - mx));
+    const float mx = da_group_max<L>(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
+    const float se = da_group_sum<L>(expf(v[0] - mx) + expf(v[1] - mx) + expf(v[2] - mx) + expf(v[3] - mx));
     const float lse = mx + logf(se);
     const bool own = lab >= 0 && (int)(lab >> 2) == sub;             // this lane holds the target's logit
     const int lj = (int)(lab & 3);
@@ -147,7 +132,7 @@ __device__ __forceinline__ float xent_quad(const float4 q, int sub, long long la
     float loss = 0.f;
     if (cfg.mode == 0 || cfg.mode == 1) {
         const bool valid = lab >= 0 && lab < C && !(cfg.mode == 0 && lab == cfg.ignore);
-        const float vt = xe_group_sum<L>(own ? (lj == 0 ? v[0] : lj == 1 ? v[1] : lj == 2 ? v[2] : v[3]) : 0.f);
+        const float vt = da_group_sum<L>(own ? (lj == 0 ? v[0] : lj == 1 ? v[1] : lj == 2 ? v[2] : v[3]) : 0.f);
         const float l = vt - lse;
         if (cfg.mode == 0) {
             loss = valid ? -l : 0.f;
@@ -178,8 +163,8 @@ __device__ __forceinline__ float xent_quad(const float4 q, int sub, long long la
             float acc = 0.f, ts = 0.f;
 #pragma unroll
             for (int j = 0; j < 4; ++j) { acc -= s[j] * (v[j] - lse); ts += s[j]; }
-            loss = xe_group_sum<L>(acc);
-            ts = xe_group_sum<L>(ts);
+            loss = da_group_sum<L>(acc);
+            ts = da_group_sum<L>(ts);
             if (BWD) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) d[j] = gscale * (expf(v[j] - lse) * ts - s[j]);
@@ -192,7 +177,7 @@ __device__ __forceinline__ float xent_quad(const float4 q, int sub, long long la
                 acc -= s[j] * logf(pass ? v[j] : 1e-8f);
                 if (BWD) d[j] = pass ? gscale * (-s[j] / v[j]) : 0.f;
             }
-            loss = xe_group_sum<L>(acc);
+            loss = da_group_sum<L>(acc);
         }
     }
     if (BWD) dq = make_float4(d[0], d[1], d[2], d[3]);
@@ -213,7 +198,7 @@ __global__ void __launch_bounds__(256) xent_fwd_quad_kernel(const float* __restr
         const long long ii = in ? i : M - 1;
         const float4 q = reinterpret_cast<const float4*>(x + ii * C)[sub];
         const float4 sq = soft ? reinterpret_cast<const float4*>(soft + ii * C)[sub] : make_float4(0.f, 0.f, 0.f, 0.f);
-        const long long lab = labels ? xe_label(labels, label_bytes, ii) : 0;
+        const long long lab = labels ? da_load_label(labels, label_bytes, ii) : 0;
         float4 dq;
         const float l = xent_quad<L, false>(q, sub, lab, sq, alpha, cfg, 0.f, dq);
         if (in && sub == 0) {
@@ -241,7 +226,7 @@ __global__ void __launch_bounds__(256) xent_bwd_quad_kernel(const float* __restr
         const long long ii = in ? i : M - 1;
         const float4 q = reinterpret_cast<const float4*>(x + ii * C)[sub];
         const float4 sq = soft ? reinterpret_cast<const float4*>(soft + ii * C)[sub] : make_float4(0.f, 0.f, 0.f, 0.f);
-        const long long lab = labels ? xe_label(labels, label_bytes, ii) : 0;
+        const long long lab = labels ? da_load_label(labels, label_bytes, ii) : 0;
         float4 dq;
         xent_quad<L, true>(q, sub, lab, sq, alpha, cfg, gscale, dq);
         if (in) reinterpret_cast<float4*>(dx + i * C)[sub] = dq;

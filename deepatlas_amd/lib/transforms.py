@@ -12,7 +12,6 @@ crop window as a separable sliding sum, a uniform pick among the starts that pas
 tables that weight a tile in blended sliding-window inference (lib/inference.py).
 Out of scope: reorientation by the affine, oblique resampling, anti-aliasing on down-sampling and B-spline interpolation.
 """
-import ctypes
 import math
 
 import numpy as np
@@ -21,8 +20,6 @@ import torch
 from .. import ops
 from .. import _native as nat
 from .._native import call, ptr, stream
-
-_DTYPE_CODE = {torch.float32: 0, torch.float64: 1, torch.int16: 2, torch.uint8: 3, torch.int32: 4}
 
 
 def _device():
@@ -71,7 +68,7 @@ def _clamp_source(a):
         elif a.dtype.kind not in 'biuf':
             raise ValueError('SitkToTensor: an image of dtype %s has no clamp to [0, 1]' % a.dtype)
         a = torch.from_numpy(np.ascontiguousarray(a))
-    if a.dtype in _DTYPE_CODE:
+    if a.dtype in ops.PREPROCESS_DTYPE_CODE:
         return a.to(_device()).contiguous()
     if a.dtype.is_complex:
         raise ValueError('SitkToTensor: an image of dtype %s has no clamp to [0, 1]' % a.dtype)
@@ -113,11 +110,6 @@ def _exact_for_copy(t, what, as_float=False):
     return t.float() if as_float else t
 
 
-def _int3(v):
-    arr = (ctypes.c_int * 3)(int(v[0]), int(v[1]), int(v[2]))
-    return arr, ctypes.cast(arr, ctypes.c_void_p)
-
-
 def mask_to_one_hot(mask, n_classes):
     """lib/transforms.py:675-689: B x 1 x D x M x N index mask -> B x C x D x M x N float one-hot."""
     return ops.one_hot(mask, n_classes)
@@ -146,7 +138,7 @@ class SitkToTensor(object):
     def __call__(self, sample):
         img = _clamp_source(sample['image'])
         out = torch.empty(img.shape, dtype=torch.float32, device=img.device)
-        call('da_clamp01_to_f32', ptr(img), _DTYPE_CODE[img.dtype], ptr(out), img.numel(), stream())
+        call('da_clamp01_to_f32', ptr(img), ops.PREPROCESS_DTYPE_CODE[img.dtype], ptr(out), img.numel(), stream())
         sample['image'] = out.unsqueeze(0)
         if 'segmentation' in sample.keys():
             sample['segmentation'] = _to_device_array(sample['segmentation']).to(torch.uint8)
@@ -217,7 +209,7 @@ class Partition(object):
         D, H, W = vol.shape
         n = int(np.prod(self.tiles_grid_size))
         tiles = torch.empty((n,) + tuple(int(v) for v in self.tile_size), dtype=vol.dtype, device=vol.device)
-        (ka, ta), (kb, ov) = _int3(self.tile_size), _int3(self.overlap_size)
+        (ka, ta), (kb, ov) = ops._int3_array(self.tile_size), ops._int3_array(self.overlap_size)
         call('da_partition_tiles', ptr(vol), ptr(tiles), vol.element_size(), D, H, W, ta, ov, stream())
         return tiles
 
@@ -253,7 +245,7 @@ class Partition(object):
         t = t.contiguous()
         D, H, W = (int(v) for v in self.image_size)
         out = torch.empty((D, H, W), dtype=t.dtype, device=t.device)
-        (ka, ta), (kb, ov) = _int3(self.tile_size), _int3(self.overlap_size)
+        (ka, ta), (kb, ov) = ops._int3_array(self.tile_size), ops._int3_array(self.overlap_size)
         call('da_assemble_tiles', ptr(t), ptr(out), t.element_size(), D, H, W, ta, ov, 1 if is_vote else 0, stream())
         if data_type:
             out = out.to(data_type if isinstance(data_type, torch.dtype) else torch.from_numpy(np.zeros(1, dtype=data_type)).dtype)

@@ -7,6 +7,7 @@ their outputs as N x D x H x W x C and return the permuted N x C x D x H x W vie
 
 Every op is a HIP kernel launch on the current torch stream; there is no eager fallback.
 """
+import ctypes
 import os
 
 import torch
@@ -414,7 +415,6 @@ def _pack_stamp(e):
 
 
 def _pack_fill(e, w_tio, st):
-    import ctypes
     C1, C2, Cout, dgrad, N, D, H, W = e.args
     used = ctypes.c_int(0)
     b1 = e.bufs[1]
@@ -492,7 +492,6 @@ def repack_after_step(flat_p):
         _pack_entries.pop(k, None)
     if not mine:
         return
-    import ctypes
     n = len(mine)
     views = [torch.as_strided(e.base(), e.view[0], e.view[1], e.view[2]) for e in mine]
     PA, IA, SA = ctypes.c_void_p * n, ctypes.c_int * n, ctypes.c_size_t * n
@@ -836,7 +835,6 @@ class Conv3dK3Fn(Function):
                 # the per-channel finish of the column sums (a Cout-workgroup kernel) goes to the side stream and accumulates straight
                 # into the flat gradient bucket: behind persistent matrix kernels such a kernel waits 20 - 100 us for a CU slot, and
                 # nothing on the main stream needs its result
-                import ctypes
                 pbytes = nat.lib().da_bn_ws_bytes(M, Cout)
                 pbuf = torch.empty((pbytes,), dtype=torch.uint8, device=g.device)
                 npar = ctypes.c_int(0)
@@ -1260,7 +1258,6 @@ class ConvBNActFn(Function):
         wp, wn = _ws(wsb, a1)
         b = bias.detach().contiguous() if bias is not None else None
         partials = None
-        import ctypes
         train_stats = bool(training or running_mean is None)
         pbuf = torch.empty((512, 2, Cout), dtype=torch.float64, device=a1.device) if train_stats else None
         npar = ctypes.c_int(0)
@@ -1324,7 +1321,6 @@ class ConvBNActFn(Function):
                 # the same summation order -- as an eager one: tests/test_gpu_dp.py compares them bit for bit)
                 # the input was the raw output of a conv + BatchNorm block (a1) with its statistics rows (mean, rstd, scale, shift): that block's
                 # BatchNorm-backward sums are accumulated in this data gradient's epilogue instead of a pass over (dx1, a1)
-                import ctypes
                 bst = torch.empty((512, 2, C1), dtype=torch.float64, device=a1.device)
                 nb = ctypes.c_int(0)
                 done = nat.call_supported('da_conv3d_k3_dgrad_bst', ptr(dy), ptr(w_tio), ptr(dx1), C1, ptr(dx2), C2, N, D, H, W, Cout, ptr(a1), ctypes.c_void_p(p1s.data_ptr() - 8 * C1),
@@ -1373,7 +1369,6 @@ def _deconv_bn_bwd_fused(ctx, go, a, w_tio, y, stats, N, D, H, W, Cin, Cout, st)
     if not (FUSE_DECONV_BN_BWD and train and Cin == 32 and Cout == 32 and go.dtype == torch.float32 and y.dtype == torch.float32 and a.dtype == torch.float32
             and go.is_contiguous() and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and ctx.has_bias):
         return None
-    import ctypes
     pre = _bwd_stats.pop(go.data_ptr(), None) if _bwd_stats else None
     if pre is not None and not (pre[3] == M and pre[4] == C):
         pre = None
@@ -1424,7 +1419,6 @@ class DeconvBNActFn(Function):
         partials = None
         if training or running_mean is None:
             # the matrix-core epilogue accumulates the BatchNorm partial sums (one set per 256 coarse voxels): no statistics pass over y
-            import ctypes
             nblk = (N * D * H * W + 255) // 256
             pbuf = torch.empty((nblk, 2, Cout), dtype=torch.float64, device=a.device)
             npar = ctypes.c_int(0)
@@ -1573,7 +1567,6 @@ class MaxPool2SkipFn(Function):
         dx = torch.empty_like(a)
         if len(ctx.saved_tensors) == 3 and FUSE_BN_BWD_STATS and g.dtype == torch.float32:
             # the pooled tensor was the raw output of a conv + BatchNorm block: dx and that block's BatchNorm-backward sums from one kernel
-            import ctypes
             raw, ps = ctx.saved_tensors[1], ctx.saved_tensors[2]
             bst = torch.empty((1024, 2, C), dtype=torch.float64, device=a.device)
             nb = ctypes.c_int(0)
@@ -1770,7 +1763,6 @@ class HeadDiceFn(Function):
                 and ps.untyped_storage().data_ptr() <= ps.data_ptr() - 8 * Cin):
             # x is the raw output of a conv + BatchNorm block whose statistics are the rows (mean, rstd, scale, shift) of one [4][C] buffer
             # (_bn_forward): that block's BatchNorm-backward sums are accumulated here, where x and its gradient are in registers anyway
-            import ctypes
             bst = torch.empty((1024, 2, Cin), dtype=torch.float64, device=a.device)
             nb = ctypes.c_int(0)
             call('da_head_dice_bwd_bst', ptr(a), ptr(ps), ptr(pt), float(sl), ctypes.c_void_p(ps.data_ptr() - 8 * Cin), ptr(w_io), ptr(b), ptr(lab), lb,
@@ -2529,7 +2521,6 @@ class GradLossFn(Function):
 
 
 def ctypes_float3(v):
-    import ctypes
     arr = (ctypes.c_float * 3)(float(v[0]), float(v[1]), float(v[2]))
     return ctypes.cast(arr, ctypes.c_void_p)
 
@@ -2588,6 +2579,12 @@ def label_overlap_counts(pred, truth, n_class):
 
 AUG_INTERPOLATORS = {'linear': 0, 'nearest': 1}
 _LABEL_BYTES = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}
+
+
+def _require_label_tensor(t, what):
+    """The dtype check of the volume utilities' label maps (the 1 / 4 / 8-byte loader of csrc/common.h), before anything touches the device."""
+    if not torch.is_tensor(t) or t.dtype not in _LABEL_BYTES:
+        raise ValueError('%s must be a uint8, int32 or int64 tensor, got %s' % (what, getattr(t, 'dtype', type(t)),))
 
 
 def spatial_resample(image, labels, affine, coef=None, order=0, interpolator='linear'):
@@ -2972,8 +2969,7 @@ CC_STATS = ('n_components', 'largest', 'voxels')      # columns of the [N][n_cla
 
 def _cc_args(labels, connectivity, n_class=None, min_size=None):
     """Argument checks of the component ops, all before anything touches the device; returns (N, D, H, W)."""
-    if not torch.is_tensor(labels) or labels.dtype not in _LABEL_BYTES:
-        raise ValueError('labels must be a uint8, int32 or int64 tensor, got %s' % (getattr(labels, 'dtype', type(labels)),))
+    _require_label_tensor(labels, 'labels')
     if labels.dim() != 4:
         raise ValueError('labels must be N x D x H x W, got %d dimensions' % labels.dim())
     if connectivity not in CC_CONNECTIVITIES:
@@ -3131,8 +3127,7 @@ def signed_distance_maps(labels, n_class, classes=None, spacing=(1, 1, 1)):
     absent from a sample, or filling it, gives 0 everywhere in that sample, so it contributes nothing to the boundary loss (as in Kervadec's
     code).  This is the plain signed distance: Kervadec's one_hot2dist shifts the inside by one voxel, -(d - 1); this does not.
     Labels outside [0, n_class) belong to no class.  The one-hot tensor is never built.  No autograd."""
-    if not torch.is_tensor(labels) or labels.dtype not in _LABEL_BYTES:
-        raise ValueError('labels must be a uint8, int32 or int64 tensor, got %s' % (getattr(labels, 'dtype', type(labels)),))
+    _require_label_tensor(labels, 'labels')
     N, D, H, W = _edt_extents(labels, 'labels')
     cl = _boundary_classes(n_class, classes)
     sp = _edt_spacing(spacing)
@@ -3203,8 +3198,7 @@ def _surface_connectivity(connectivity):
 
 
 def _surface_labels(t, what):
-    if not torch.is_tensor(t) or t.dtype not in _LABEL_BYTES:
-        raise ValueError('%s must be a uint8, int32 or int64 tensor, got %s' % (what, getattr(t, 'dtype', type(t)),))
+    _require_label_tensor(t, what)
     return _edt_extents(t, what)
 
 
@@ -3364,7 +3358,6 @@ def volume_moments(vol):
 def volume_order_statistics(vol, percentiles):
     """The raw result of da_volume_percentiles for one or two percentiles: dict with 'percentiles' (list of doubles), 'order_statistics'
     (per percentile the (lower, upper) float32 order statistics it interpolates), 'count' (non-NaN values) and 'nan_count'."""
-    import ctypes
     _volume4(vol)
     ps = [float(p) for p in (percentiles if hasattr(percentiles, '__len__') else [percentiles])]
     if not 1 <= len(ps) <= 2:
@@ -3448,7 +3441,6 @@ def _crop_window(window, extents):
 
 
 def _int3_array(v):
-    import ctypes
     arr = (ctypes.c_int * 3)(int(v[0]), int(v[1]), int(v[2]))
     return arr, ctypes.cast(arr, ctypes.c_void_p)
 

@@ -255,7 +255,7 @@ def layout_ref(name, src, dst_before=None):
 
 
 # ---- clamp ------------------------------------------------------------------------------------------------------------------------
-CLAMP_DTYPES = [np.float32, np.float64, np.int16, np.uint8, np.int32]       # the kernel's dtype codes 0 ... 4 (lib/transforms.py _DTYPE_CODE)
+CLAMP_DTYPES = [np.float32, np.float64, np.int16, np.uint8, np.int32]       # the kernel's dtype codes 0 ... 4 (ops.PREPROCESS_DTYPE_CODE)
 CLAMP_SIZES = [1, 257, TRIP + 3]
 _FLOAT_EDGES = [0.0, 1.0, -0.0, 0.5, float('nan'), float('inf'), -float('inf'), 1.0000001, 0.99999994, -1e-30, 1e-45, 3.0e38, -3.0e38, 2.0 ** 24 + 2]
 _F64_EDGES = _FLOAT_EDGES + [1 + 1e-12, 1 - 1e-12, -1e-300, 5e-324, 1e300, -1e300]
