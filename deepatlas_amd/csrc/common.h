@@ -30,6 +30,26 @@ static inline hipStream_t da_stream(void* s) { return (hipStream_t)s; }
 __host__ __device__ static inline long long da_cdiv(long long a, long long b) { return (a + b - 1) / b; }
 static inline size_t da_align(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
+// Workspace carving.  A workspace is described ONCE, by a layout function that walks a DaCarve over a base pointer: da_X_ws_bytes calls it with a null base and
+// returns the total, the launcher calls it with `ws` and reads the pointers (`return L{c.take<A>(n), c.take<B>(m), c.off};` -- braces evaluate left to right).
+// take<T>(n) is the next region (null when sizing) and moves `off` to the next multiple of `align` behind it; align = 1 packs the next region directly behind.
+struct DaCarve {
+    char* base; size_t off = 0;
+    explicit DaCarve(void* ws) : base((char*)ws) {}
+    template <typename T> T* take(size_t n, size_t align = 256) { T* p = base ? (T*)(base + off) : nullptr; off = da_align(off + n * sizeof(T), align); return p; }
+};
+// Nothing is located from the caller's ws_bytes.  The column-sum scratch of the weight gradients that also produce dbias (da_colsum's workspace, da_bn_ws_bytes(0, Cout)
+// bytes) is the tail of the REQUIRED size `need` = da_X_ws_bytes(...); the `front` bytes before it are the budget of the weight gradient itself.
+struct DaColsumTail { size_t front; void* ws; size_t bytes; };
+static inline DaColsumTail da_colsum_tail(void* ws, size_t need, int Cout) {
+    const size_t bytes = da_bn_ws_bytes(0, Cout);
+    return DaColsumTail{need - bytes, ws ? (char*)ws + (need - bytes) : nullptr, bytes};
+}
+// the packed weights of the split-mode stride-2, up-sampling and flow convolutions: the weight scale exponents in a 256-byte slot, then the operand, which starts where
+// `c` stands afterwards (the size function takes its bytes from there; a launcher needs the two pointers only)
+struct DaExpPack { int* wexp; unsigned char* wp; };
+static inline DaExpPack da_exp_pack(DaCarve& c) { int* e = c.take<int>(1); return DaExpPack{e, c.base ? (unsigned char*)c.base + c.off : nullptr}; }
+
 // grid size for grid-stride elementwise kernels: enough workgroups to fill 256 CUs x 8, capped
 static inline int da_grid(long long work_items, int block, int cap = 256 * 16) {
     long long g = da_cdiv(work_items, block);
@@ -164,7 +184,10 @@ int da_reduce_partials(const float* partial, int nparts, int O, float* out, hipS
 // losses.hip: Dice loss / coefficients from per-block partial sums (shared with the fused label-warp Dice in warp.hip)
 int da_dice_finish(double* partial, int nblocks, int N, int C, int weight_type, int no_bg, float eps,
                    float* loss, float* coef, float* isc, hipStream_t st);
-
+// its workspace, behind whatever `c` already holds: per-block partial sums [N][blocks][3][C] and da_dice_finish's 3*N*C floats of scratch
+struct DaDiceWs { double* partial; float* isc; size_t bytes; };
+static inline DaDiceWs da_dice_carve(DaCarve& c, int N, int blocks, int C) { return DaDiceWs{c.take<double>((size_t)N * blocks * 3 * C), c.take<float>((size_t)3 * N * C), c.off}; }
+static inline DaDiceWs da_dice_layout(void* ws, int N, int blocks, int C) { DaCarve c(ws); return da_dice_carve(c, N, blocks, C); }
 // ---------------------------------------------------------------------------------------------------
 // bf16 ACTIVATION STORAGE (BASELINE configs[4]: "bf16 activations / MFMA, fp32 master weights, fp32 reductions").  The `_bf16` twins of
 // the C-ABI entry points take the network-internal activation / gradient tensors as bf16 in HBM (same NDHWC layout, 2 bytes per

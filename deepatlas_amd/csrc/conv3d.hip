@@ -301,17 +301,25 @@ static size_t wgrad_direct_parts(long long nrows, int O, int* rows_per_block) {
     return (size_t)da_cdiv(nrows, *rows_per_block);
 }
 
+// Workspace of the 3x3x3 entries.  Every route starts at `ws`: the direct weight gradient's partials, the direct data gradient's flipped weights, the thin routes' 64 KiB
+// pack, the matrix routes' own layouts (conv3d_mfma.hip, conv3d_s2.hip).  The column-sum scratch of dbias is the tail of the size (da_colsum_tail).  k3_reserve (a floor
+// for the routes that size nothing themselves) and kK3Pad (it absorbed the rounding when the scratch was located from the end of the caller's buffer; the stride-2
+// routes' budget still ends that far in front of the scratch) are added on top of the largest route: kept so that sizes do not change.
+constexpr size_t kK3Pad = 4096;
+static size_t k3_reserve(int O) { return da_align((size_t)2 * O * sizeof(float) + 65536); }
 extern "C" size_t da_conv3d_k3_ws_bytes(int N, int D, int H, int W, int Cin, int Cout, int stride) {
     const int Do = (D - 1) / stride + 1, Ho = (H - 1) / stride + 1;
     const int O = 27 * Cin * Cout;
     int rpb;
-    const size_t parts = wgrad_direct_parts((long long)N * Do * Ho, O, &rpb);
-    size_t direct = da_align(parts * (size_t)O * sizeof(float));
+    const size_t direct = da_align(wgrad_direct_parts((long long)N * Do * Ho, O, &rpb) * (size_t)O * sizeof(float));
     size_t mfma = da_conv3_mfma_ws_bytes(N, D, H, W, Cin, Cout, stride);
     if (stride == 2 && da_conv3_s2_supported(Cin, 0, Cout)) mfma = da_conv3_s2_ws_bytes(N, D, H, W, Cin, Cout);
-    size_t packed = da_align((size_t)2 * O * sizeof(float) + 65536);
     const int Cm = Cin > Cout ? Cin : Cout;
-    return packed + (direct > mfma ? direct : mfma) + da_bn_ws_bytes(0, Cm) + 4096;
+    return k3_reserve(O) + (direct > mfma ? direct : mfma) + da_bn_ws_bytes(0, Cm) + kK3Pad;
+}
+// what the stride-2 routes may use: up to kK3Pad in front of the column-sum scratch
+static size_t k3_s2_budget(int N, int D, int H, int W, int Cin, int Cout) {
+    return da_colsum_tail(nullptr, da_conv3d_k3_ws_bytes(N, D, H, W, Cin, Cout, 2), Cout).front - kK3Pad;
 }
 
 // da_set_conv_direct(1): every 3x3x3 call on the direct kernels (the tests' cross-check of the other routes)
@@ -352,7 +360,7 @@ extern "C" int da_conv3d_k3_fwd(const float* in1, int C1, const float* in2, int 
     hipStream_t st = da_stream(stream);
     if (!g_force_direct && stride == 2 && da_conv3_s2_supported(C1, C2, Cout)) {
         if (ws_bytes < da_conv3d_k3_ws_bytes(N, D, H, W, C1 + C2, Cout, stride)) return DA_ERR_WS_SMALL;
-        return da_conv3_s2_fwd(in1, C1, w_tio, bias, out, N, D, H, W, Cout, act_slope, ws, ws_bytes - da_bn_ws_bytes(0, Cout) - 4096, st);
+        return da_conv3_s2_fwd(in1, C1, w_tio, bias, out, N, D, H, W, Cout, act_slope, ws, k3_s2_budget(N, D, H, W, C1, Cout), st);
     }
     if (!g_force_direct && da_conv3_mfma_fwd_supported(C1, C2, Cout, stride)) {
         if (ws_bytes < da_conv3d_k3_ws_bytes(N, D, H, W, C1 + C2, Cout, stride)) return DA_ERR_WS_SMALL;
@@ -461,7 +469,7 @@ extern "C" int da_conv3d_k3_dgrad(const float* dy, const float* w_tio, float* dx
         return da_conv3_direct_fwd(dy, Cout, nullptr, 0, wf, nullptr, dx1, C1, dx2, C2, N, D, H, W, Cin, 1, -1.f, st);
     }
     if (!g_force_direct && da_conv3_s2_supported(C1, C2, Cout)) {
-        const int rc = da_conv3_s2_dgrad(dy, w_tio, dx1, C1, N, D, H, W, Cout, ws, ws_bytes - da_bn_ws_bytes(0, Cout) - 4096, st);
+        const int rc = da_conv3_s2_dgrad(dy, w_tio, dx1, C1, N, D, H, W, Cout, ws, k3_s2_budget(N, D, H, W, C1, Cout), st);
         if (rc != DA_ERR_UNSUPPORTED) return rc;           // Cout % 16 != 0 outside the native kernels: the direct kernel below
     }
     const int Do = (D - 1) / 2 + 1, Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
@@ -484,7 +492,7 @@ extern "C" int da_conv3d_k3_wgrad(const float* in1, int C1, const float* in2, in
     const int O = 27 * Cin * Cout;
     int rc = 0;
     if (!g_force_direct && stride == 2 && da_conv3_s2_supported(C1, C2, Cout)) {
-        rc = da_conv3_s2_wgrad(in1, C1, dy, dw_tio, N, D, H, W, Cout, ws, ws_bytes - da_bn_ws_bytes(0, Cout) - 4096, st);
+        rc = da_conv3_s2_wgrad(in1, C1, dy, dw_tio, N, D, H, W, Cout, ws, k3_s2_budget(N, D, H, W, C1, Cout), st);
     } else if (!g_force_direct && stride == 1 && da_conv3_mfma_wgrad_supported(C1, C2, Cout, stride)) {
         rc = da_conv3_mfma_wgrad(wgrad_gemm(in1, C1, in2, C2, dy, dw_tio, N, D, H, W, Cout, stride, ws, ws_bytes, stream));
     } else {
@@ -503,9 +511,8 @@ extern "C" int da_conv3d_k3_wgrad(const float* in1, int C1, const float* in2, in
     }
     if (rc) return rc;
     if (dbias) {
-        // the column-sum scratch sits after the largest partial region
-        const size_t off = ws_bytes - da_bn_ws_bytes(0, Cout);
-        rc = da_colsum(dy, (long long)N * Do * Ho * Wo, Cout, dbias, (char*)ws + (off / 256) * 256, da_bn_ws_bytes(0, Cout), stream);
+        const DaColsumTail cs = da_colsum_tail(ws, da_conv3d_k3_ws_bytes(N, D, H, W, Cin, Cout, stride), Cout);
+        rc = da_colsum(dy, (long long)N * Do * Ho * Wo, Cout, dbias, cs.ws, cs.bytes, stream);
     }
     return rc;
 }
@@ -536,7 +543,7 @@ extern "C" int da_conv3d_k3_fwd_bf16(const void* in1, int C1, const void* in2, i
     if ((bf16_mask & want) != want) return DA_ERR_UNSUPPORTED;
     if (stride == 2) {
         if (!da_conv3_s2_supported(C1, C2, Cout)) return DA_ERR_UNSUPPORTED;
-        return da_conv3_s2_fwd((const float*)in1, C1, w_tio, bias, (float*)out, N, D, H, W, Cout, act_slope, ws, ws_bytes - da_bn_ws_bytes(0, Cout) - 4096, da_stream(stream), 1);
+        return da_conv3_s2_fwd((const float*)in1, C1, w_tio, bias, (float*)out, N, D, H, W, Cout, act_slope, ws, k3_s2_budget(N, D, H, W, C1, Cout), da_stream(stream), 1);
     }
     if (!da_conv3_mfma_fwd_supported(C1, C2, Cout, stride)) return DA_ERR_UNSUPPORTED;
     ConvGemm c = fwd_gemm(in1, C1, in2, C2, w_tio, bias, out, N, D, H, W, Cout, ws, ws_bytes, stream); c.slope = act_slope; c.act_bf16 = 1;
@@ -615,7 +622,7 @@ extern "C" int da_conv3d_k3_dgrad_bf16(const void* dy, const float* w_tio, void*
     if ((bf16_mask & want) != want) return DA_ERR_UNSUPPORTED;
     if (stride == 2) {
         if (!da_conv3_s2_supported(C1, C2, Cout)) return DA_ERR_UNSUPPORTED;
-        return da_conv3_s2_dgrad((const float*)dy, w_tio, (float*)dx1, C1, N, D, H, W, Cout, ws, ws_bytes - da_bn_ws_bytes(0, Cout) - 4096, da_stream(stream), 1);
+        return da_conv3_s2_dgrad((const float*)dy, w_tio, (float*)dx1, C1, N, D, H, W, Cout, ws, k3_s2_budget(N, D, H, W, C1, Cout), da_stream(stream), 1);
     }
     if (!da_conv3_mfma_fwd_supported(Cout, 0, Cin, 1, C1, C2)) return DA_ERR_UNSUPPORTED;
     return da_conv3_mfma_fwd(dgrad_gemm(dy, w_tio, dx1, C1, dx2, C2, N, D, H, W, Cout, ws, ws_bytes, stream, 1));
@@ -640,7 +647,7 @@ extern "C" int da_conv3d_k3_wgrad_bf16(const void* in1, int C1, const void* in2,
     if ((bf16_mask & want) != want) return DA_ERR_UNSUPPORTED;
     if (stride == 2) {
         if (!da_conv3_s2_supported(C1, C2, Cout)) return DA_ERR_UNSUPPORTED;
-        return da_conv3_s2_wgrad((const float*)in1, C1, (const float*)dy, dw_tio, N, D, H, W, Cout, ws, ws_bytes - da_bn_ws_bytes(0, Cout) - 4096, da_stream(stream), 1);
+        return da_conv3_s2_wgrad((const float*)in1, C1, (const float*)dy, dw_tio, N, D, H, W, Cout, ws, k3_s2_budget(N, D, H, W, C1, Cout), da_stream(stream), 1);
     }
     if (!da_conv3_mfma_wgrad_supported(C1, C2, Cout, stride)) return DA_ERR_UNSUPPORTED;
     ConvWgrad c = wgrad_gemm(in1, C1, in2, C2, dy, dw_tio, N, D, H, W, Cout, stride, ws, ws_bytes, stream); c.act_bf16 = 1;

@@ -519,7 +519,13 @@ bool da_conv3_flow_wgrad_supported(int C1, int C2, int Cout, int stride) {
     return stride == 1 && Cout >= 1 && Cout <= 3 && C1 % 4 == 0 && C2 % 4 == 0 && C1 <= 16 && C2 <= 16 && C1 + C2 >= 4;
 }
 
-size_t da_conv3_flow_wgrad_ws_bytes(int Cin, int Cout) { return da_align((size_t)kFlowBlocks * 27 * Cin * Cout * sizeof(float)); }
+// per-workgroup dW partials (all the flow conv needs: partial_bytes), then, for the few-input-channel form, their sum before it is placed into dW
+struct FlowWgWs { float* partial; size_t partial_bytes; float* tmp; size_t bytes; };
+static FlowWgWs flow_wgrad_layout(int Cin, int Cout, void* ws) {
+    const size_t O = (size_t)27 * Cin * Cout;
+    DaCarve c(ws); return FlowWgWs{c.take<float>(kFlowBlocks * O), c.off, c.take<float>(O), c.off};
+}
+size_t da_conv3_flow_wgrad_ws_bytes(int Cin, int Cout) { return flow_wgrad_layout(Cin, Cout, nullptr).partial_bytes; }
 
 template <int MTT, bool TWO, int S1, bool XB>
 static int flow_launch_t(const FlowWgP& p, int nb, hipStream_t st) {
@@ -715,7 +721,8 @@ int da_conv3_fewcin_wgrad(const float* in1, int C1, const float* in2, int C2, co
                           int N, int D, int H, int W, int Cout, void* ws, size_t ws_bytes, hipStream_t st, int dy_bf16) {
     if (!da_conv3_fewcin_wgrad_supported(C1, C2, Cout, 1)) return DA_ERR_UNSUPPORTED;
     const int Cin = C1 + C2, O = 27 * Cin * Cout;
-    if (ws_bytes < da_align((size_t)kFlowBlocks * O * sizeof(float)) + da_align((size_t)O * sizeof(float))) return DA_ERR_WS_SMALL;
+    const FlowWgWs l = flow_wgrad_layout(Cin, Cout, ws);
+    if (ws_bytes < l.bytes) return DA_ERR_WS_SMALL;
     if ((unsigned long long)D * H * W * 16ull * 4ull >= 0xFFFFFFF0ull) return DA_ERR_UNSUPPORTED;
     if (!dy_bf16 && (unsigned long long)N * D * H * W * (unsigned long long)Cout * 4ull < 0xFFFFFFF0ull && (Cout == 8 || Cout == 16) && (C2 == 0 || (C1 == 1 && C2 == 1))) {
         if (Cin == 1 && Cout == 8) return fewcin_valu_launch<1, 2>(in1, C1, in2, dy, dw_tio, N, D, H, W, ws, st);
@@ -730,7 +737,7 @@ int da_conv3_fewcin_wgrad(const float* in1, int C1, const float* in2, int C2, co
     flow_geom(p, N, D, H, W, &nb);
     const int rc = Cin == 1 ? flow_launch<2, false, 8>(p, nb, st, dy_bf16) : flow_launch<4, false, 8>(p, nb, st, dy_bf16);
     if (rc) return rc;
-    float* tmp = (float*)((char*)ws + da_align((size_t)kFlowBlocks * O * sizeof(float)));
+    float* tmp = l.tmp;
     const int rc2 = da_reduce_partials(p.partial, nb, O, tmp, st);
     if (rc2) return rc2;
     hipLaunchKernelGGL(fewcin_place_kernel, dim3(da_grid(O, 256, 64)), dim3(256), 0, st, tmp, dw_tio, Cin, Cout);

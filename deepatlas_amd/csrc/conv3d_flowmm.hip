@@ -373,7 +373,7 @@ bool da_conv3_flowmm_supported(int C1, int C2, int Cout, int N, int D, int H, in
     const long long vox = (long long)D * H * W;
     return vox * 16 * 4 < (1ll << 32) && (long long)N * vox < (1ll << 31);
 }
-size_t da_conv3_flowmm_ws_bytes() { return 65536; }          // exponent (256 B) + the packed weights (<= 36 KB)
+size_t da_conv3_flowmm_ws_bytes() { DaCarve c(nullptr); da_exp_pack(c); c.take<char>(65536 - 256); return c.off; }          // 64 KiB: the exponent slot + the packed weights (<= 36 KB)
 
 #define FM_CASES(X) X(8, 16) X(16, 16) X(16, 0) X(8, 8) X(8, 0)
 
@@ -384,9 +384,9 @@ int da_conv3_flowmm_fwd(const float* in1, int C1, const float* in2, int C2, cons
     const Plan q = fm_plan(N, D, H, W);
     const int Cin = C1 + C2, NSTEP = (9 * (Cin / 8) + 3) / 4;
     FwdP p;
-    p.in1 = in1; p.in2 = in2; p.wexp = (const int*)ws; p.wp = (const unsigned char*)ws + 256; p.bias = bias; p.out = out;
+    DaCarve c(ws); const DaExpPack pk = da_exp_pack(c); p.in1 = in1; p.in2 = in2; p.wexp = pk.wexp; p.wp = pk.wp; p.bias = bias; p.out = out;
     p.N = N; p.D = D; p.H = H; p.W = W; p.Cout = Cout; p.ntz = q.ntz; p.nty = q.nty; p.ntx = q.ntx; p.ntiles = q.ntiles; p.slope = slope;
-    hipLaunchKernelGGL(fm_pack_fwd_kernel, dim3(1), dim3(256), 0, st, w_tio, (unsigned short*)((unsigned char*)ws + 256), (int*)ws, Cin, Cout, NSTEP);
+    hipLaunchKernelGGL(fm_pack_fwd_kernel, dim3(1), dim3(256), 0, st, w_tio, (unsigned short*)pk.wp, pk.wexp, Cin, Cout, NSTEP);
     DA_LAUNCH_CHECK();
     const int grid = q.ntiles < 512 ? q.ntiles : 512;
     const size_t shm = (size_t)2 * HV * Cin * 2 + 16;
@@ -403,9 +403,9 @@ int da_conv3_flowmm_dgrad(const float* dy, const float* w_tio, float* dx1, int C
     const Plan q = fm_plan(N, D, H, W);
     const int Cin = C1 + C2, NTN = (Cin + 15) / 16;
     DgP p;
-    p.dy = dy; p.wexp = (const int*)ws; p.wp = (const unsigned char*)ws + 256; p.dx1 = dx1; p.dx2 = dx2;
+    DaCarve c(ws); const DaExpPack pk = da_exp_pack(c); p.dy = dy; p.wexp = pk.wexp; p.wp = pk.wp; p.dx1 = dx1; p.dx2 = dx2;
     p.N = N; p.D = D; p.H = H; p.W = W; p.Cout = Cout; p.Cin = Cin; p.ntz = q.ntz; p.nty = q.nty; p.ntx = q.ntx; p.ntiles = q.ntiles;
-    hipLaunchKernelGGL(fm_pack_dgrad_kernel, dim3(1), dim3(256), 0, st, w_tio, (unsigned short*)((unsigned char*)ws + 256), (int*)ws, Cin, Cout, NTN);
+    hipLaunchKernelGGL(fm_pack_dgrad_kernel, dim3(1), dim3(256), 0, st, w_tio, (unsigned short*)pk.wp, pk.wexp, Cin, Cout, NTN);
     DA_LAUNCH_CHECK();
     const int grid = q.ntiles < 512 ? q.ntiles : 512;
     const size_t shm = (size_t)2 * HV * 8 + 16;

@@ -1689,17 +1689,17 @@ static int pick_ck(int C1, int C2) {
 static int pick_nrep(int NT) { return NT <= 3 ? NT : (NT % 2 == 0 ? 2 : (NT % 3 == 0 ? 3 : 2)); }
 
 static const int kWexpInts = 256;            // behind the packed weights; split mode: the chunks' weight exponents (<= 256 chunks)
-static size_t packed_bytes(int Cin, int Cout, int CK) {
+static size_t operand_bytes(int Cin, int Cout, int CK) {
     const int NT = (Cout + 15) / 16, NREP = pick_nrep(NT);
     const int NTpad = ((NT + NREP - 1) / NREP * NREP + 1) & ~1;      // (even: the bf16 / split modes use <= 2 N-tiles per workgroup)
     const int NSTEPS = (27 * CK + 15) / 16;
     size_t b = (size_t)(Cin / CK) * NSTEPS * NTpad * 256 * sizeof(float);
     const size_t sp = (size_t)(Cin / 8) * 7 * NTpad * 2048;           // split mode: 8-channel chunks, 7 K-steps of 32, two 1 KiB planes
     if (Cin % 8 == 0 && sp > b) b = sp;
-    return da_align(b) + da_align(kWexpInts * sizeof(int));
+    return b;
 }
 
-struct WgPlan { int CK, NREP, ngroups, nchunks, ntz, nty, ntx, ntiles, nslabs, tps; size_t partial_bytes; bool ring; };      // ring: the eight-wave ring form of conv3d_wgring.h (16-channel chunks, one workgroup per CU) instead of the four-wave row-owner kernel
+struct WgPlan { int CK, NREP, ngroups, nchunks, ntz, nty, ntx, ntiles, nslabs, tps; bool ring; };      // ring: the eight-wave ring form of conv3d_wgring.h (16-channel chunks, one workgroup per CU) instead of the four-wave row-owner kernel
 static WgPlan wgrad_plan(int N, int D, int H, int W, int C1, int C2, int Cout, bool split = false, bool allow_ring = false) {
     WgPlan q;
     q.CK = pick_ck(C1, C2);
@@ -1724,7 +1724,6 @@ static WgPlan wgrad_plan(int N, int D, int H, int W, int C1, int C2, int Cout, b
             q.ring = true; q.nchunks = (C1 + C2) / 16; slabs = s16;
             q.tps = (int)da_cdiv(q.ntiles, slabs);
             q.nslabs = (int)da_cdiv(q.ntiles, q.tps);           // (every slab non-empty)
-            q.partial_bytes = da_align((size_t)q.nslabs * O * sizeof(float));
             return q;
         }
     }
@@ -1732,30 +1731,44 @@ static WgPlan wgrad_plan(int N, int D, int H, int W, int C1, int C2, int Cout, b
     if (slabs >= 8) slabs &= ~7ll;                           // multiple of 8: blockIdx.x % 8 is then the XCD (tile_walk)
     q.tps = (int)da_cdiv(q.ntiles, slabs);
     q.nslabs = (int)slabs;
-    q.partial_bytes = da_align((size_t)q.nslabs * O * sizeof(float));
     return q;
 }
 
 }  // namespace
 
-static size_t tile_table_bytes(int N, int D, int H, int W) {
-    return da_align((size_t)N * ((D + 3) / 4) * ((H + TY - 1) / TY) * ((W + TX - 1) / TX) * sizeof(int4));
+// The pack image of one forward-shaped launch: [packed operand][kWexpInts exponents / tile counters][tile table].  A kept pack (da_conv3d_k3_prepack) is written by
+// one call and read by later ones, and the workspace copy is the same image: this is its only description.
+struct PackImage { unsigned short* wp; int* wexp; int4* tiles; size_t bytes; };
+static size_t tile_count(int N, int D, int H, int W, int dz) { return (size_t)N * ((D + dz - 1) / dz) * ((H + TY - 1) / TY) * ((W + TX - 1) / TX); }      // tiles of dz planes
+static PackImage pack_image(int Cin, int Cout, int CK, int N, int D, int H, int W, void* base) {
+    DaCarve c(base); return PackImage{(unsigned short*)c.take<char>(operand_bytes(Cin, Cout, CK)), c.take<int>(kWexpInts), c.take<int4>(tile_count(N, D, H, W, 4)), c.off};
 }
-static size_t wg_tile_table_bytes(int N, int D, int H, int W) {
-    return da_align((size_t)N * ((D + 1) / 2) * ((H + TY - 1) / TY) * ((W + TX - 1) / TX) * sizeof(int4));
+// a weight-gradient call: [per-slab partials (partial_bytes)][tile table of the row-owner kernels]
+struct WgWs { float* partial; size_t partial_bytes; int4* tiles; size_t bytes; };
+static WgWs wg_layout(size_t partial_floats, int N, int D, int H, int W, void* ws) {
+    DaCarve c(ws); return WgWs{c.take<float>(partial_floats), c.off, c.take<int4>(tile_count(N, D, H, W, 2)), c.off};
 }
 static const int kScBlocks = 1024;          // workgroups (= partial dW copies) of the small-Cin weight gradient
-// layout of a forward / data-gradient call: [packed weights | tile counters][tile table]; of a weight-gradient call: [partials]
+// ... of the small-Cin kernel: [partials]; with the operands swapped: [partials][their sum, before it is permuted into dW]; packed, `bytes` not rounded
+struct ScWs { float *partial, *tmp; size_t bytes; };
+static ScWs sc_layout(size_t O, bool swapped, void* ws) {
+    DaCarve c(ws); return ScWs{c.take<float>(kScBlocks * O, 1), swapped ? c.take<float>(O, 1) : nullptr, c.off};
+}
+// The size is the SUM of the largest pack image and the largest weight-gradient layout, though a call uses one of them, from the start of ws; a shape no plan packs
+// still counts a tile table, and the small-Cin layouts a weight-gradient tile table behind them.  Kept so: sizes do not change.
 size_t da_conv3_mfma_ws_bytes(int N, int D, int H, int W, int Cin, int Cout, int stride) {
     if (stride != 1) return 0;
-    size_t pk = 0;
-    if (Cin % 8 == 0) { const size_t a = packed_bytes(Cin, Cout, Cin % 16 == 0 ? 16 : 8); if (a > pk) pk = a; const size_t b = packed_bytes(Cin, Cout, 8); if (b > pk) pk = b; }
-    if (Cout % 8 == 0) { const size_t a = packed_bytes(Cout, Cin, Cout % 16 == 0 ? 16 : 8); if (a > pk) pk = a; }
-    size_t part = 0;
-    if (Cin % 8 == 0) { part = wgrad_plan(N, D, H, W, Cin, 0, Cout).partial_bytes; const size_t pr = wgrad_plan(N, D, H, W, Cin, 0, Cout, true, true).partial_bytes; if (pr > part) part = pr; }
-    if (Cin <= 4 && Cout <= 32) part = da_align((size_t)kScBlocks * 27 * Cin * Cout * sizeof(float));
-    if (Cout <= 4 && Cin <= 32) { const size_t sw = da_align((size_t)(kScBlocks + 1) * 27 * Cin * Cout * sizeof(float)); if (sw > part) part = sw; }   // swapped-operand weight gradient
-    return pk + tile_table_bytes(N, D, H, W) + part + wg_tile_table_bytes(N, D, H, W);
+    size_t img = da_align(tile_count(N, D, H, W, 4) * sizeof(int4));
+    const int plans[3][3] = {{Cin, Cout, Cin % 16 == 0 ? 16 : 8}, {Cin, Cout, 8}, {Cout, Cin, Cout % 16 == 0 ? 16 : 8}};      // forward (either chunking), data gradient
+    for (const auto& f : plans)
+        if (f[0] % 8 == 0) { const size_t b = pack_image(f[0], f[1], f[2], N, D, H, W, nullptr).bytes; if (b > img) img = b; }
+    const size_t O = (size_t)27 * Cin * Cout, table = wg_layout(0, N, D, H, W, nullptr).bytes;
+    int slabs = 0;
+    if (Cin % 8 == 0) { slabs = wgrad_plan(N, D, H, W, Cin, 0, Cout).nslabs; const int ring = wgrad_plan(N, D, H, W, Cin, 0, Cout, true, true).nslabs; if (ring > slabs) slabs = ring; }
+    size_t part = wg_layout(slabs * O, N, D, H, W, nullptr).bytes;
+    if (Cin <= 4 && Cout <= 32) part = table + da_align(sc_layout(O, false, nullptr).bytes);
+    if (Cout <= 4 && Cin <= 32) { const size_t sw = table + da_align(sc_layout(O, true, nullptr).bytes); if (sw > part) part = sw; }   // swapped-operand weight gradient
+    return img + part;
 }
 
 bool da_conv3_mfma_fwd_supported(int C1, int C2, int Cout, int stride, int Cs1, int Cs2) {
@@ -1869,7 +1882,7 @@ static int set_prologue(P& p, const DaPro* pro, int C2) {
 
 // ---- the launch plan of a forward-shaped call: pure (no state, no launches); the launcher and da_conv3d_k3_prepack(_many) read it, the sizing functions its byte helpers ----
 // Pack-layout invariant.  What a packed operand depends on is PackJob -- Cin, the cout window (cout0, Cout of CoutW), NTpad, flipped or not, the tile grid (N, D, H, W) --
-// and pk, the offset of the exponents and the tile table, a function of (Cin, Cout).  The plan must yield the same values for a fill and for every call that may consume
+// and the image's offsets of the exponents and the tile table (pack_image), a function of (Cin, Cout, CK).  The plan must yield the same values for a fill and for every call that may consume
 // that fill.  da_conv3d_k3_prepack plans the plain forward / data gradient; its consumers add stats_partial, pro or bst.  In split mode NREP, hence NTpad, depends on
 // (Cout, tile count) alone: stats_partial and pro do not enter (pro's cap at two N-tiles is the split mode's own), and bst, which forces NREP = 1, is confined to NT <= 2
 // (dx1 of <= 32 channels), where NTpad = NT for either NREP.  fwd_launches splits a call by its shape alone (bst rides on the first launch).  Keep it so: a stale pack is silent.
@@ -1877,7 +1890,7 @@ enum FwdFamily { kFamDense, kFamMasked, kFamSplit, kFamPaired, kFamBst };
 struct FwdPlan {
     bool split, bf; int CK, NREP, gy, NTpad;      // channels per chunk, N-tiles per workgroup, cout groups (grid.y), N-tiles in the pack
     int pkmode, NSTEPS;                 // 0 fp32 | 1 bf16, one tap per K-step (sparse taps) | 2 bf16, K = 32 per step | 3 split: three bf16 planes, K = 32
-    size_t pk, tt;                      // bytes of [packed weights | exponents / tile counters] and of the tile table behind them
+    size_t pack_bytes;                  // bytes of the pack image (pack_image)
     int ntz, nty, ntx, ntiles, nblocks; FwdFamily family;
 };
 static int fwd_plan(const ConvGemm& c, int mode, FwdPlan* plan) {
@@ -1917,7 +1930,7 @@ static int fwd_plan(const ConvGemm& c, int mode, FwdPlan* plan) {
     q.gy = (NT + q.NREP - 1) / q.NREP; q.NTpad = q.gy * q.NREP;
     q.pkmode = q.split ? 3 : q.bf ? (c.s2d_cin > 0 ? 1 : 2) : 0;
     q.NSTEPS = q.pkmode >= 2 ? (q.CK == 16 ? 14 : 7) : (27 * q.CK + 15) / 16;
-    q.pk = packed_bytes(Cin, c.Cout, q.CK); q.tt = tile_table_bytes(c.N, c.D, c.H, c.W);
+    q.pack_bytes = pack_image(Cin, c.Cout, q.CK, c.N, c.D, c.H, c.W, nullptr).bytes;
     // one resident round: 2 workgroups per CU x 256 CUs, split over the cout groups
     // (a third workgroup per CU for the split kernels -- 168 VGPRs, 3 x 52 KB of LDS -- was measured and dropped: in split mode the
     // matrix pipe is already busy ~100 % of the shader cycles and the clock is set by the power limit)
@@ -1947,9 +1960,10 @@ static int fwd_launches(const ConvGemm& c, int mode, ConvGemm l[2]) {
     return 2;
 }
 
-// the pack of one launch at `base`: [packed weights | exponents / tile counters][tile table]
+// the pack of one launch at `base`
 static PackJob pack_job(const ConvGemm& c, const FwdPlan& q, char* base) {
-    return PackJob{c.w_tio, reinterpret_cast<unsigned short*>(base), reinterpret_cast<int*>(base + q.pk - da_align(kWexpInts * sizeof(int))), reinterpret_cast<int4*>(base + q.pk),
+    const PackImage m = pack_image(c.C1 + c.C2, c.Cout, q.CK, c.N, c.D, c.H, c.W, base);
+    return PackJob{c.w_tio, m.wp, m.wexp, m.tiles,
                    c.C1 + c.C2, c.Cout, q.NTpad, c.flipped_tr, q.ntiles, q.ntx, q.nty, q.ntz, c.cout0, c.CoutW ? c.CoutW : c.Cout};
 }
 static void launch_split_pack(const PackJob& j, hipStream_t st) {
@@ -1978,8 +1992,8 @@ static int conv3_mfma_launch(const ConvGemm& c) {
     const int Cin = c.C1 + c.C2, CK = q.CK, NREP = q.NREP, gy = q.gy;
     const bool bf = q.bf, hb = c.act_bf16 != 0, stats = c.stats_partial != nullptr, pro = c.pro != nullptr;
     hipStream_t st = c.st;
-    const bool kept = q.split && c.pack.buf[0] && c.pack.bytes[0] >= q.pk + q.tt;
-    if (!kept && c.ws_bytes < q.pk + q.tt) return DA_ERR_WS_SMALL;
+    const bool kept = q.split && c.pack.buf[0] && c.pack.bytes[0] >= q.pack_bytes;
+    if (!kept && c.ws_bytes < q.pack_bytes) return DA_ERR_WS_SMALL;
     if (q.split && Cin / 8 > kWexpInts) return DA_ERR_UNSUPPORTED;
     const PackJob j = pack_job(c, q, kept ? reinterpret_cast<char*>(const_cast<void*>(c.pack.buf[0])) : reinterpret_cast<char*>(c.ws));      // the caller's kept copy, or the workspace
     const long long total = (long long)(Cin / CK) * q.NSTEPS * q.NTpad * 256;
@@ -2226,10 +2240,11 @@ int da_conv3_mfma_wgrad(const ConvWgrad& c) {
     }
     if (smallcin_ok(C1, C2, Cout, stride)) {
         const int Cin = C1 + C2, O = 27 * Cin * Cout;
-        if (ws_bytes < (size_t)kScBlocks * O * sizeof(float)) return DA_ERR_WS_SMALL;
+        const ScWs l = sc_layout(O, false, ws);
+        if (ws_bytes < l.bytes) return DA_ERR_WS_SMALL;
         if ((unsigned long long)D * H * W * (Cout > Cin ? Cout : Cin) * 4ull >= 0xFFFFFFF0ull) return DA_ERR_UNSUPPORTED;
         ScP sp;
-        sp.in1 = in1; sp.in2 = in2; sp.C1 = C1; sp.C2 = C2; sp.dy = dy; sp.partial = (float*)ws;
+        sp.in1 = in1; sp.in2 = in2; sp.C1 = C1; sp.C2 = C2; sp.dy = dy; sp.partial = l.partial;
         sp.N = N; sp.D = D; sp.H = H; sp.W = W; sp.Cout = Cout; sp.nrows = (long long)N * D * H; sp.dyb = nullptr; sp.Cd1 = Cout;
         int nb = (int)da_cdiv(sp.nrows, 4); if (nb > kScBlocks) nb = kScBlocks;
         const int MT = (27 * Cin + 15) / 16, NT = (Cout + 15) / 16;
@@ -2247,14 +2262,15 @@ int da_conv3_mfma_wgrad(const ConvWgrad& c) {
         // gradient" x (Cin channels, possibly two tensors) and the taps mirrored; 27*Cout <= 108 rows instead of an MFMA N-tile
         // that is 13/16 padding.  The result [27][Cout][Cin] (mirrored) is permuted into dw_tio by a tiny kernel.
         const int Cin = C1 + C2, O = 27 * Cin * Cout;
-        if (ws_bytes < (size_t)(kScBlocks + 1) * O * sizeof(float)) return DA_ERR_WS_SMALL;
+        const ScWs l = sc_layout(O, true, ws);
+        if (ws_bytes < l.bytes) return DA_ERR_WS_SMALL;
         ScP sp;
         sp.in1 = dy; sp.in2 = nullptr; sp.C1 = Cout; sp.C2 = 0; sp.dy = in1; sp.dyb = in2; sp.Cd1 = C1; sp.Cout = Cin;
-        sp.partial = (float*)ws; sp.N = N; sp.D = D; sp.H = H; sp.W = W; sp.nrows = (long long)N * D * H;
+        sp.partial = l.partial; sp.N = N; sp.D = D; sp.H = H; sp.W = W; sp.nrows = (long long)N * D * H;
         int nb = (int)da_cdiv(sp.nrows, 4); if (nb > kScBlocks) nb = kScBlocks;
         const int MT = (27 * Cout + 15) / 16, NT = (Cin + 15) / 16;
         if (const int rcs = launch_smallcin_wgrad(MT, NT, nb, sp, st)) return rcs;
-        float* tmp = (float*)ws + (size_t)kScBlocks * O;
+        float* tmp = l.tmp;
         { const int rc2 = da_reduce_partials(sp.partial, nb, O, tmp, st); if (rc2) return rc2; }
         hipLaunchKernelGGL(swapped_wgrad_place_kernel, dim3(da_grid(O, 256, 64)), dim3(256), 0, st, tmp, dw_tio, Cin, Cout);
         DA_LAUNCH_CHECK();
@@ -2270,19 +2286,20 @@ int da_conv3_mfma_wgrad(const ConvWgrad& c) {
     if (!q.CK) return DA_ERR_UNSUPPORTED;
     const bool bf = da_matrix_mode() == 1;      // (Cout % 4 != 0 keeps the exact kernel: its dY staging is scalar)
     if ((unsigned long long)D * H * W * 4ull * (unsigned long long)((C1 > C2 ? C1 : C2) > Cout ? (C1 > C2 ? C1 : C2) : Cout) >= 0xFFFFFFF0ull) return DA_ERR_UNSUPPORTED;
-    if (ws_bytes < q.partial_bytes + ((split || rows1) ? wg_tile_table_bytes(N, D, H, W) : 0)) return DA_ERR_WS_SMALL;
+    const WgWs l = wg_layout((size_t)q.nslabs * 27 * (C1 + C2) * Cout, N, D, H, W, ws);
+    if (ws_bytes < ((split || rows1) ? l.bytes : l.partial_bytes)) return DA_ERR_WS_SMALL;
     WgP p;
     p.tiles = nullptr;
     p.s2in = s2d_cin > 0 ? S2dSrc{s2d_cin, s2f->D0, s2f->H0, s2f->W0} : S2dSrc{0, 0, 0, 0};
     { static int abl = -1; if (abl < 0) { const char* e = getenv("DA_WG_ABLATE"); abl = e ? atoi(e) : 0; } p.ablate = abl; }
     if (split || rows1) {
-        int4* tiles = reinterpret_cast<int4*>(reinterpret_cast<char*>(ws) + q.partial_bytes);
+        int4* tiles = l.tiles;
         if (q.ring) tiles = nullptr;               // (the ring form derives its tiles from the position: no table, no launch)
         else hipLaunchKernelGGL(wgrad_tiles_kernel, dim3(da_grid(q.ntiles, 256, 256)), dim3(256), 0, st, tiles, q.ntiles, q.ntx, q.nty, q.ntz, 2);
         DA_LAUNCH_CHECK();
         p.tiles = tiles;
     }
-    p.in1 = in1; p.in2 = in2; p.C1 = C1; p.C2 = C2; p.dy = dy; p.partial = (float*)ws;
+    p.in1 = in1; p.in2 = in2; p.C1 = C1; p.C2 = C2; p.dy = dy; p.partial = l.partial;
     p.N = N; p.D = D; p.H = H; p.W = W; p.Cout = Cout;
     p.ntz = q.ntz; p.nty = q.nty; p.ntx = q.ntx; p.ntiles = q.ntiles; p.tiles_per_slab = q.tps;
     p.O = 27 * (C1 + C2) * Cout;
@@ -2309,9 +2326,9 @@ int da_conv3_mfma_wgrad(const ConvWgrad& c) {
 // ---- C ABI of the kept packs (documented in include/deepatlas_hip.h; the hand-over: take_handover) ------------------------------------------
 extern "C" size_t da_conv3d_k3_pack_bytes(int N, int D, int H, int W, int Cin, int Cout) {
     if (Cin % 8 != 0 && Cout % 8 != 0) return 0;
-    size_t a = Cin % 8 == 0 ? packed_bytes(Cin, Cout, 8) : 0;
-    if (Cout % 8 == 0) { const size_t b = packed_bytes(Cout, Cin, 8); if (b > a) a = b; }      // (the data gradient: channels exchanged)
-    return a + tile_table_bytes(N, D, H, W);
+    size_t a = Cin % 8 == 0 ? pack_image(Cin, Cout, 8, N, D, H, W, nullptr).bytes : 0;
+    if (Cout % 8 == 0) { const size_t b = pack_image(Cout, Cin, 8, N, D, H, W, nullptr).bytes; if (b > a) a = b; }      // (the data gradient: channels exchanged)
+    return a;
 }
 // What da_conv3d_k3_prepack has to enqueue: the packs, one per launch (fwd_launches), of the call that will read them -- the plain forward (dgrad = 0)
 // or data gradient of the layer C1 + C2 -> Cout, planned as that call will be.  *njobs = 0: this shape / matrix mode does not run the split kernels.
@@ -2330,7 +2347,7 @@ static int prepack_jobs(const float* w_tio, int C1, int C2, int Cout, int dgrad,
     for (int i = 0; i < n; ++i) {
         FwdPlan q;
         int rc = fwd_plan(l[i], 2, &q);
-        if (!rc && (!buf[i] || bytes[i] < q.pk + q.tt)) rc = DA_ERR_WS_SMALL;
+        if (!rc && (!buf[i] || bytes[i] < q.pack_bytes)) rc = DA_ERR_WS_SMALL;
         if (!rc && (l[i].C1 + l[i].C2) / 8 > kWexpInts) rc = DA_ERR_UNSUPPORTED;
         if (rc) return rc == DA_ERR_UNSUPPORTED ? 0 : rc;
         jobs[i] = pack_job(l[i], q, reinterpret_cast<char*>(buf[i]));

@@ -39,13 +39,13 @@ __global__ void extract_wgrad_s2d_kernel(const float* __restrict__ dwe, float* _
     }
 }
 
-struct S2Plan { int Dq, Hq, Wq; size_t we_bytes, inner_bytes; };
-static S2Plan s2_plan(int N, int D, int H, int W, int Cin, int Cout) {
-    S2Plan p;
-    p.Dq = (D + 1) / 2; p.Hq = (H + 1) / 2; p.Wq = (W + 1) / 2;
-    p.we_bytes = da_align((size_t)27 * 8 * Cin * Cout * sizeof(float));
-    p.inner_bytes = da_conv3_mfma_ws_bytes(N, p.Dq, p.Hq, p.Wq, 8 * Cin, Cout, 1) + 65536;
-    return p;
+// the space-to-depth route's workspace: [W' expanded][dW' expanded][inner conv scratch]; kInnerPad: slack behind the inner call's own size, nothing is placed there (kept: sizes do not change)
+constexpr size_t kInnerPad = 65536;
+struct S2Plan { int Dq, Hq, Wq; size_t inner_bytes; float *We, *dWe; char* inner; size_t bytes; };
+static S2Plan s2_plan(int N, int D, int H, int W, int Cin, int Cout, void* ws = nullptr) {
+    const int Dq = (D + 1) / 2, Hq = (H + 1) / 2, Wq = (W + 1) / 2;
+    const size_t inner = da_conv3_mfma_ws_bytes(N, Dq, Hq, Wq, 8 * Cin, Cout, 1) + kInnerPad, we = (size_t)27 * 8 * Cin * Cout;
+    DaCarve c(ws); return S2Plan{Dq, Hq, Wq, inner, c.take<float>(we), c.take<float>(we), c.take<char>(inner, 1), c.off};
 }
 
 // split matrix mode: the native stride-2 kernels (conv3d_s2n.hip) take the shapes they support; the other modes take the masked route
@@ -58,20 +58,19 @@ bool s2_native(int Cin, int Cout, int N, int D, int H, int W) {
 bool da_conv3_s2_supported(int C1, int C2, int Cout) { return C2 == 0 && C1 % 16 == 0 && C1 <= 32 && Cout >= 8 && Cout % 4 == 0; }
 
 size_t da_conv3_s2_ws_bytes(int N, int D, int H, int W, int Cin, int Cout) {
-    const S2Plan p = s2_plan(N, D, H, W, Cin, Cout);
-    size_t b = 2 * p.we_bytes + p.inner_bytes;
+    size_t b = s2_plan(N, D, H, W, Cin, Cout).bytes;
     if (da_conv3_s2n_supported(Cin, Cout, N, D, H, W)) { const size_t nb = da_conv3_s2n_ws_bytes(N, D, H, W, Cin, Cout); if (nb > b) b = nb; }
     return b;
 }
 
-// ws layout: [W' expanded] [dW' expanded] [inner conv scratch].  The MFMA kernels read X / write dX through the space-to-depth view (DaS2dFuse).
+// The MFMA kernels read X / write dX through the space-to-depth view (DaS2dFuse).
 int da_conv3_s2_fwd(const float* in, int Cin, const float* w_tio, const float* bias, float* out,
                     int N, int D, int H, int W, int Cout, float slope, void* ws, size_t ws_bytes, hipStream_t st, int act_bf16) {
     if (act_bf16 && da_matrix_mode() != 1) return DA_ERR_UNSUPPORTED;      // bf16 activation storage: bf16 matrix mode
     if (s2_native(Cin, Cout, N, D, H, W)) return da_conv3_s2n_fwd(in, Cin, w_tio, bias, out, N, D, H, W, Cout, slope, ws, ws_bytes, st);
-    const S2Plan p = s2_plan(N, D, H, W, Cin, Cout);
+    const S2Plan p = s2_plan(N, D, H, W, Cin, Cout, ws);
     if (ws_bytes < da_conv3_s2_ws_bytes(N, D, H, W, Cin, Cout)) return DA_ERR_WS_SMALL;
-    float* We = (float*)ws; char* inner = (char*)ws + 2 * p.we_bytes;
+    float* We = p.We; char* inner = p.inner;
     hipLaunchKernelGGL(expand_weights_s2d_kernel, dim3(da_grid(27 * 8 * Cin * Cout, 256, 512)), dim3(256), 0, st, w_tio, We, Cin, Cout);
     DA_LAUNCH_CHECK();
     const DaS2dFuse f = {D, H, W};
@@ -86,9 +85,9 @@ int da_conv3_s2_dgrad(const float* dy, const float* w_tio, float* dx, int Cin, i
     if (s2_native(Cin, Cout, N, D, H, W)) return da_conv3_s2n_dgrad(dy, w_tio, dx, Cin, N, D, H, W, Cout, ws, ws_bytes, st);
     // the tap-masked kernels stage their input, here dY, in 16-channel chunks: Cout = 8, 24, ... goes back to the caller (da_conv3d_k3_dgrad: the direct kernel)
     if (Cout % 16 != 0) return DA_ERR_UNSUPPORTED;
-    const S2Plan p = s2_plan(N, D, H, W, Cin, Cout);
+    const S2Plan p = s2_plan(N, D, H, W, Cin, Cout, ws);
     if (ws_bytes < da_conv3_s2_ws_bytes(N, D, H, W, Cin, Cout)) return DA_ERR_WS_SMALL;
-    float* We = (float*)ws; char* inner = (char*)ws + 2 * p.we_bytes;
+    float* We = p.We; char* inner = p.inner;
     hipLaunchKernelGGL(expand_weights_s2d_kernel, dim3(da_grid(27 * 8 * Cin * Cout, 256, 512)), dim3(256), 0, st, w_tio, We, Cin, Cout);
     DA_LAUNCH_CHECK();
     // dS = conv(dY, flip/transpose(W')) : logical Cin = Cout, logical Cout = 8*Cin, stored to dX through the inverse view
@@ -102,9 +101,9 @@ int da_conv3_s2_wgrad(const float* in, int Cin, const float* dy, float* dw_tio, 
                       void* ws, size_t ws_bytes, hipStream_t st, int act_bf16) {
     if (act_bf16 && da_matrix_mode() != 1) return DA_ERR_UNSUPPORTED;
     if (s2_native(Cin, Cout, N, D, H, W)) return da_conv3_s2n_wgrad(in, Cin, dy, dw_tio, N, D, H, W, Cout, ws, ws_bytes, st);
-    const S2Plan p = s2_plan(N, D, H, W, Cin, Cout);
+    const S2Plan p = s2_plan(N, D, H, W, Cin, Cout, ws);
     if (ws_bytes < da_conv3_s2_ws_bytes(N, D, H, W, Cin, Cout)) return DA_ERR_WS_SMALL;
-    float* dWe = (float*)((char*)ws + p.we_bytes); char* inner = (char*)ws + 2 * p.we_bytes;
+    float* dWe = p.dWe; char* inner = p.inner;
     const DaS2dFuse f = {D, H, W};
     ConvWgrad c = {}; c.in1 = in; c.C1 = 8 * Cin; c.dy = dy; c.dw_tio = dWe; c.N = N; c.D = p.Dq; c.H = p.Hq; c.W = p.Wq; c.Cout = Cout; c.stride = 1;
     c.ws = inner; c.ws_bytes = p.inner_bytes; c.st = st; c.s2d_cin = Cin; c.s2f = &f; c.act_bf16 = act_bf16;

@@ -593,7 +593,8 @@ size_t da_conv3_s2n_ws_bytes(int N, int D, int H, int W, int Cin, int Cout) {
     const size_t part = (size_t)s2n_wgrad_slabs(q.ntiles, Cin / 8, Cout / 32) * 27 * Cin * Cout * sizeof(float);
     size_t m = pack_f > pack_d ? pack_f : pack_d;
     if (part > m) m = part;
-    return da_align(m) + 256;        // (+ 256: the weight scale exponents in front of the packed operand)
+    DaCarve c(nullptr); da_exp_pack(c); c.take<char>(m);      // (the weight gradient's partials reuse the same bytes from the start)
+    return c.off;
 }
 
 int da_conv3_s2n_fwd(const float* in, int Cin, const float* w_tio, const float* bias, float* out,
@@ -601,10 +602,10 @@ int da_conv3_s2n_fwd(const float* in, int Cin, const float* w_tio, const float* 
     if (ws_bytes < da_conv3_s2n_ws_bytes(N, D, H, W, Cin, Cout)) return DA_ERR_WS_SMALL;
     const Plan q = s2n_plan(N, D, H, W);
     FwdP p;
-    p.in = in; p.wexp = (const int*)ws; p.wp = (const unsigned char*)ws + 256; p.bias = bias; p.out = out;
+    DaCarve c(ws); const DaExpPack pk = da_exp_pack(c); p.in = in; p.wexp = pk.wexp; p.wp = pk.wp; p.bias = bias; p.out = out;
     p.N = N; p.D = D; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.Do = q.Do; p.Ho = q.Ho; p.Wo = q.Wo;
     p.ntz = q.ntz; p.nty = q.nty; p.ntx = q.ntx; p.nchunks = Cin / 8; p.NT = Cout / 16; p.slope = slope;
-    hipLaunchKernelGGL(s2n_pack_fwd_kernel, dim3(p.nchunks, 4), dim3(256), 0, st, w_tio, (unsigned short*)((unsigned char*)ws + 256), (int*)ws, Cin, Cout, p.NT);
+    hipLaunchKernelGGL(s2n_pack_fwd_kernel, dim3(p.nchunks, 4), dim3(256), 0, st, w_tio, (unsigned short*)pk.wp, pk.wexp, Cin, Cout, p.NT);
     DA_LAUNCH_CHECK();
     return da_launch_lds<s2n_fwd_kernel>(dim3(q.ntiles, Cout / 32), dim3(256), NPLN * PLANE_B + 16, st, p);
 }
@@ -614,10 +615,10 @@ int da_conv3_s2n_dgrad(const float* dy, const float* w_tio, float* dx, int Cin, 
     if (ws_bytes < da_conv3_s2n_ws_bytes(N, D, H, W, Cin, Cout)) return DA_ERR_WS_SMALL;
     const Plan q = s2n_plan(N, D, H, W);
     DgP p;
-    p.dy = dy; p.wexp = (const int*)ws; p.wp = (const unsigned char*)ws + 256; p.dx = dx;
+    DaCarve c(ws); const DaExpPack pk = da_exp_pack(c); p.dy = dy; p.wexp = pk.wexp; p.wp = pk.wp; p.dx = dx;
     p.N = N; p.D = D; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.Do = q.Do; p.Ho = q.Ho; p.Wo = q.Wo;
     p.ntz = q.ntz; p.nty = q.nty; p.ntx = q.ntx; p.KS = Cout / 32; p.NTN = Cin / 16;
-    hipLaunchKernelGGL(s2n_pack_dgrad_kernel, dim3(da_grid((long long)27 * p.KS * p.NTN * 64, 256, 32)), dim3(256), 0, st, w_tio, (unsigned short*)((unsigned char*)ws + 256), (int*)ws, Cin, Cout, p.KS, p.NTN);
+    hipLaunchKernelGGL(s2n_pack_dgrad_kernel, dim3(da_grid((long long)27 * p.KS * p.NTN * 64, 256, 32)), dim3(256), 0, st, w_tio, (unsigned short*)pk.wp, pk.wexp, Cin, Cout, p.KS, p.NTN);
     DA_LAUNCH_CHECK();
     const size_t shm = (size_t)NPLN * (Cout / 8) * GV * 16 + 16;
     switch (p.NTN) {      // (shm grows with Cout: the attribute is the bound of Cout = 64)

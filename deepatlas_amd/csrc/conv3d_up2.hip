@@ -666,7 +666,8 @@ extern "C" size_t da_upconv3d_k3_ws_bytes(int N, int Dc, int Hc, int Wc, int Cin
     const size_t part = (size_t)up_wgrad_slabs(q.ntiles, Cin / 8) * 64 * Cin * Cout * sizeof(float);
     size_t m = pack_f > pack_d ? pack_f : pack_d;
     if (part > m) m = part;
-    return da_align(m) + 256;        // (+ 256: the weight scale exponents in front of the packed operand)
+    DaCarve c(nullptr); da_exp_pack(c); c.take<char>(m);      // (the weight gradient's partials reuse the same bytes from the start)
+    return c.off;
 }
 
 static bool up_sizes_ok(int N, int Dc, int Hc, int Wc, int Cin, int Cout) {
@@ -684,9 +685,9 @@ extern "C" int da_upconv3d_k3_fwd(const float* s1, int C1, const float* s2, int 
     const Plan q = up_plan(N, Dc, Hc, Wc);
     FwdP p;
     p.nchunks = Cin / 8; p.NTall = (Cout + 15) / 16; p.slope = act_slope;
-    p.s1 = s1; p.s2 = s2; p.C1 = C1; p.C2 = C2; p.wexp = (const int*)ws; p.wp = (const unsigned char*)ws + 256; p.bias = bias; p.out = out;
+    DaCarve c(ws); const DaExpPack pk = da_exp_pack(c); p.s1 = s1; p.s2 = s2; p.C1 = C1; p.C2 = C2; p.wexp = pk.wexp; p.wp = pk.wp; p.bias = bias; p.out = out;
     p.N = N; p.Dc = Dc; p.Hc = Hc; p.Wc = Wc; p.Cout = Cout; p.ntz = q.ntz; p.nty = q.nty; p.ntx = q.ntx;
-    hipLaunchKernelGGL(up_pack_fwd_kernel, dim3(p.nchunks, 4 * p.NTall), dim3(256), 0, st, w_tio, (unsigned short*)((unsigned char*)ws + 256), (int*)ws, Cin, Cout, p.NTall);
+    hipLaunchKernelGGL(up_pack_fwd_kernel, dim3(p.nchunks, 4 * p.NTall), dim3(256), 0, st, w_tio, (unsigned short*)pk.wp, pk.wexp, Cin, Cout, p.NTall);
     DA_LAUNCH_CHECK();
     const size_t shm = NPLN * SPLANE_B + 16;
     if (p.NTall == 1) return da_launch_lds<up_fwd_kernel<1>>(dim3(q.ntiles, 1), dim3(256), shm, st, p);
@@ -705,9 +706,9 @@ extern "C" int da_upconv3d_k3_dgrad(const float* dy, const float* w_tio, float* 
     p.nchunks = Cout / 8;
     int NTN = (Cin + 15) / 16; if (NTN == 3) NTN = 4;            // (48 input channels: a fourth, empty tile)
     p.NTN = NTN;
-    p.dy = dy; p.wexp = (const int*)ws; p.wp = (const unsigned char*)ws + 256; p.dx1 = dx1; p.dx2 = dx2; p.C1 = C1; p.C2 = C2;
+    DaCarve c(ws); const DaExpPack pk = da_exp_pack(c); p.dy = dy; p.wexp = pk.wexp; p.wp = pk.wp; p.dx1 = dx1; p.dx2 = dx2; p.C1 = C1; p.C2 = C2;
     p.N = N; p.Dc = Dc; p.Hc = Hc; p.Wc = Wc; p.Cout = Cout; p.ntz = q.ntz; p.nty = q.nty; p.ntx = q.ntx;
-    hipLaunchKernelGGL(up_pack_dgrad_kernel, dim3(p.nchunks, 4 * NTN), dim3(256), 0, st, w_tio, (unsigned short*)((unsigned char*)ws + 256), (int*)ws, Cin, Cout, NTN);
+    hipLaunchKernelGGL(up_pack_dgrad_kernel, dim3(p.nchunks, 4 * NTN), dim3(256), 0, st, w_tio, (unsigned short*)pk.wp, pk.wexp, Cin, Cout, NTN);
     DA_LAUNCH_CHECK();
     const size_t shm = NPLN * FPLANE_B + 16;
     switch (NTN) {

@@ -313,9 +313,13 @@ inline bool cr_geom(int D, int H, int W, const int* win, int mode, CrGeom& g) {
     return true;
 }
 
-inline size_t cr_rows_bytes(int N, int D, int H, const CrGeom& g) { return da_align(sizeof(unsigned short) * (size_t)N * D * H * g.Wd); }
-inline size_t cr_hs_bytes(int N, int D, const CrGeom& g) { return da_align(sizeof(int) * (size_t)N * D * g.Hd * g.Wd); }
 inline int cr_words(const CrGeom& g) { return (int)da_cdiv((long long)g.Hd * g.Wd, 64); }
+// one class's row and H passes (all da_window_label_counts needs: counts_bytes), then the selection's candidate mask, per-plane counts and best keys
+struct CrWs { unsigned short* rows; int* hs; size_t counts_bytes; u64* mask; unsigned* zcount; u64* best; size_t bytes; };
+inline CrWs cr_layout(int N, int D, int H, const CrGeom& g, void* ws) {
+    DaCarve c(ws); return CrWs{c.take<unsigned short>((size_t)N * D * H * g.Wd), c.take<int>((size_t)N * D * g.Hd * g.Wd), c.off,
+                c.take<u64>((size_t)N * g.Dd * cr_words(g)), c.take<unsigned>((size_t)N * g.Dd), c.take<u64>((size_t)N), c.off};
+}
 inline int cr_seg(int w) { return w > 16 ? w : 16; }
 
 // row pass + H pass of one class into rows / hs
@@ -342,7 +346,7 @@ inline bool cr_dims_ok(int N, int D, int H, int W) { return N > 0 && N <= 65535 
 extern "C" size_t da_window_label_counts_ws_bytes(int N, int D, int H, int W, const int* window3) {
     CrGeom g;
     if (!cr_dims_ok(N, D, H, W) || (long long)D * H * W >= CR_MAX_V || W > CR_MAX_W || !cr_geom(D, H, W, window3, 1, g)) return 0;
-    return cr_rows_bytes(N, D, H, g) + cr_hs_bytes(N, D, g);
+    return cr_layout(N, D, H, g, nullptr).counts_bytes;
 }
 
 extern "C" int da_window_label_counts(const void* labels, int label_dtype, int N, int D, int H, int W, const int* window3, long long cls,
@@ -353,8 +357,8 @@ extern "C" int da_window_label_counts(const void* labels, int label_dtype, int N
     if (W > CR_MAX_W) return DA_ERR_UNSUPPORTED;
     if (ws_bytes < da_window_label_counts_ws_bytes(N, D, H, W, window3)) return DA_ERR_WS_SMALL;
     hipStream_t st = da_stream(stream);
-    unsigned short* rows = (unsigned short*)ws;
-    int* hs = (int*)((char*)ws + cr_rows_bytes(N, D, H, g));
+    const CrWs l = cr_layout(N, D, H, g, ws);
+    unsigned short* rows = l.rows; int* hs = l.hs;
     const int rc = cr_class_passes(labels, label_dtype, N, D, H, W, g, cls, rows, hs, st);
     if (rc) return rc;
     const long long inner = (long long)g.Hd * g.Wd;
@@ -368,8 +372,7 @@ extern "C" int da_window_label_counts(const void* labels, int label_dtype, int N
 extern "C" size_t da_crop_sample_starts_ws_bytes(int N, int D, int H, int W, const int* window3, int include_last) {
     CrGeom g;
     if (!cr_dims_ok(N, D, H, W) || (long long)D * H * W >= CR_MAX_V || W > CR_MAX_W || !cr_geom(D, H, W, window3, include_last ? 1 : 0, g)) return 0;
-    return cr_rows_bytes(N, D, H, g) + cr_hs_bytes(N, D, g) + da_align(sizeof(u64) * (size_t)N * g.Dd * cr_words(g))
-           + da_align(sizeof(unsigned) * (size_t)N * g.Dd) + da_align(sizeof(u64) * (size_t)N);
+    return cr_layout(N, D, H, g, nullptr).bytes;
 }
 
 extern "C" int da_crop_sample_starts(const void* labels, int label_dtype, int N, int D, int H, int W, const int* window3, int include_last,
@@ -392,12 +395,8 @@ extern "C" int da_crop_sample_starts(const void* labels, int label_dtype, int N,
     DA_LAUNCH_CHECK();
     if (n_conds == 0) return 0;
     const int nW = cr_words(g);
-    char* base = (char*)ws;
-    unsigned short* rows = (unsigned short*)base; base += cr_rows_bytes(N, D, H, g);
-    int* hs = (int*)base; base += cr_hs_bytes(N, D, g);
-    u64* mask = (u64*)base; base += da_align(sizeof(u64) * (size_t)N * g.Dd * nW);
-    unsigned* zcount = (unsigned*)base; base += da_align(sizeof(unsigned) * (size_t)N * g.Dd);
-    u64* best = (u64*)base;
+    const CrWs l = cr_layout(N, D, H, g, ws);
+    unsigned short* rows = l.rows; int* hs = l.hs; u64* mask = l.mask; unsigned* zcount = l.zcount; u64* best = l.best;
     const long long inner = (long long)g.Hd * g.Wd;
     const int seg = cr_seg(g.wd);
     const dim3 sgrid((unsigned)da_cdiv(inner, CR_BLOCK), (unsigned)da_cdiv(g.Dd, seg), (unsigned)N);

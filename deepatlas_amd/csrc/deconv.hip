@@ -247,9 +247,13 @@ extern "C" int da_deconv_k2s2_dgrad(const float* dy, const float* w_tio, float* 
 // conv's bias gradient, dgamma, dbeta.  The BatchNorm-backward sums come from one reduction pass over (gout, y) or from `pre` (sums the producer of gout
 // accumulated: da_bn_act_bwd_dbias_pre's argument); the apply pass, the tensor dy and the data / weight gradients' second and third read of it do not exist.
 // DA_ERR_UNSUPPORTED for channel counts without the fused kernel (callers then run da_bn_act_bwd_dbias + da_deconv_k2s2_dgrad + da_deconv_k2s2_wgrad).
+struct BnBwdWs { size_t bn_bytes, fused_bytes; void *bn, *fused; size_t bytes; };      // [BatchNorm-backward sums (da_bn_bwd_sums)][the fused kernel's workspace]
+static BnBwdWs bn_bwd_layout(long long M, int Cin, int Cout, void* ws) {
+    const size_t bn = da_bn_ws_bytes(M * 8, Cout), fused = da_deconv_bn_bwd_ws_bytes(M, Cin, Cout);
+    DaCarve c(ws); return BnBwdWs{bn, fused, c.take<char>(bn), c.take<char>(fused), c.off};
+}
 extern "C" size_t da_deconv_k2s2_bn_bwd_ws_bytes(int N, int D, int H, int W, int Cin, int Cout) {
-    const long long M = (long long)N * D * H * W;
-    return da_align(da_bn_ws_bytes(M * 8, Cout)) + da_deconv_bn_bwd_ws_bytes(M, Cin, Cout);
+    return bn_bwd_layout((long long)N * D * H * W, Cin, Cout, nullptr).bytes;
 }
 extern "C" int da_deconv_k2s2_bn_bwd(const float* gout, const float* y, const float* mean, const float* rstd, const float* scale, const float* shift, float act_slope,
                                      const float* in, const float* w_tio, float* dx, float* dw_tio, float* dbias, float* dgamma, float* dbeta,
@@ -260,23 +264,28 @@ extern "C" int da_deconv_k2s2_bn_bwd(const float* gout, const float* y, const fl
     if (ws_bytes < da_deconv_k2s2_bn_bwd_ws_bytes(N, D, H, W, Cin, Cout)) return DA_ERR_WS_SMALL;
     const long long M = (long long)N * D * H * W;
     hipStream_t st = da_stream(stream);
-    const size_t bnb = da_align(da_bn_ws_bytes(M * 8, Cout));
+    const BnBwdWs l = bn_bwd_layout(M, Cin, Cout, ws);
     const float* cm = nullptr;
-    int rc = da_bn_bwd_sums(gout, y, mean, rstd, scale, shift, act_slope, M * 8, Cout, dgamma, dbeta, &cm, ws, bnb, st, pre, pre_n);
+    int rc = da_bn_bwd_sums(gout, y, mean, rstd, scale, shift, act_slope, M * 8, Cout, dgamma, dbeta, &cm, l.bn, l.bn_bytes, st, pre, pre_n);
     if (rc) return rc;
-    return da_deconv_bn_bwd(gout, y, mean, rstd, scale, shift, cm, act_slope, in, w_tio, dx, dw_tio, dbias, M, D, H, W, Cin, Cout, (char*)ws + bnb, ws_bytes - bnb, st);
+    return da_deconv_bn_bwd(gout, y, mean, rstd, scale, shift, cm, act_slope, in, w_tio, dx, dw_tio, dbias, M, D, H, W, Cin, Cout, l.fused, l.fused_bytes, st);
 }
 
-extern "C" size_t da_deconv_k2s2_wgrad_ws_bytes(int N, int D, int H, int W, int Cin, int Cout) {
+// Workspace of the pointwise weight gradients: [partials of the direct kernel or of the matrix path, whichever needs more][kWgPad][column-sum scratch of dbias]; the scratch is
+// found from this size (da_colsum_tail).  kWgPad: slack from when it was found by rounding down from the end of the caller's buffer; unused, kept so that sizes do not change.
+constexpr size_t kWgPad = 512;
+static size_t wgrad_bytes(size_t direct_floats, size_t matrix_bytes, int Cout) {
+    const size_t direct = da_align(direct_floats * sizeof(float));
+    return (direct > matrix_bytes ? direct : matrix_bytes) + kWgPad + da_bn_ws_bytes(0, Cout);
+}
+static size_t k2s2_wgrad_bytes(int N, int D, int H, int W, int Cin, int Cout, int Cbias) {
     long long per;
     const int O = 8 * Cin * Cout;
     const int parts = parts_for((long long)N * D * H * W, O, &per);
-    const int Cm = Cout;
-    size_t direct = da_align((size_t)parts * O * sizeof(float));
     const size_t mf = da_pw_supported(Cin, Cout) ? da_pw_wgrad_ws_bytes((long long)N * D * H * W, 8, Cin, Cout) : 0;
-    if (mf > direct) direct = mf;
-    return direct + da_bn_ws_bytes(0, Cm) + 512;
+    return wgrad_bytes((size_t)parts * O, mf, Cbias);
 }
+extern "C" size_t da_deconv_k2s2_wgrad_ws_bytes(int N, int D, int H, int W, int Cin, int Cout) { return k2s2_wgrad_bytes(N, D, H, W, Cin, Cout, Cout); }
 
 extern "C" int da_deconv_k2s2_wgrad(const float* in, const float* dy, float* dw_tio, float* dbias,
                                     int N, int D, int H, int W, int Cin, int Cout,
@@ -287,9 +296,9 @@ extern "C" int da_deconv_k2s2_wgrad(const float* in, const float* dy, float* dw_
     long long per;
     const int O = 8 * Cin * Cout;
     const int parts = parts_for((long long)N * D * H * W, O, &per);
-    const size_t cs_off = ((ws_bytes - da_bn_ws_bytes(0, Cout)) / 256) * 256;
+    const DaColsumTail cs = da_colsum_tail(ws, da_deconv_k2s2_wgrad_ws_bytes(N, D, H, W, Cin, Cout), Cout);
     int rc_pw = DA_ERR_UNSUPPORTED;
-    if (da_pw_supported(Cin, Cout)) rc_pw = da_pw_wgrad(in, dy, dw_tio, (long long)N * D * H * W, D, H, W, Cin, Cout, 8, 1, ws, cs_off, st);
+    if (da_pw_supported(Cin, Cout)) rc_pw = da_pw_wgrad(in, dy, dw_tio, (long long)N * D * H * W, D, H, W, Cin, Cout, 8, 1, ws, cs.front, st);
     if (rc_pw != 0 && rc_pw != DA_ERR_UNSUPPORTED) return rc_pw;
     if (rc_pw == DA_ERR_UNSUPPORTED) {          // odd channel counts, or tensors beyond 32-bit byte offsets
         float* partial = (float*)ws;
@@ -299,7 +308,7 @@ extern "C" int da_deconv_k2s2_wgrad(const float* in, const float* dy, float* dw_
         DA_LAUNCH_CHECK();
     }
     if (dbias)
-        return da_colsum(dy, (long long)N * D * H * W * 8, Cout, dbias, (char*)ws + cs_off, da_bn_ws_bytes(0, Cout), stream);
+        return da_colsum(dy, (long long)N * D * H * W * 8, Cout, dbias, cs.ws, cs.bytes, stream);
     return 0;
 }
 
@@ -330,10 +339,10 @@ extern "C" int da_conv1x1_wgrad_pro(const float* in, const float* pro_scale, con
     if (!in || !pro_scale || !pro_shift || !dy || !dw_io || M <= 0 || Cin <= 0 || Cout <= 0) return DA_ERR_BADARG;
     if (!da_pw_supported(Cin, Cout)) return DA_ERR_UNSUPPORTED;
     if (ws_bytes < da_conv1x1_wgrad_ws_bytes(M, Cin, Cout)) return DA_ERR_WS_SMALL;
-    const size_t cs_off = ((ws_bytes - da_bn_ws_bytes(0, Cout)) / 256) * 256;
-    const int rc = da_pw_wgrad(in, dy, dw_io, M, 1, 1, 1, Cin, Cout, 1, 0, ws, cs_off, da_stream(stream), pro_scale, pro_shift, pro_slope);
+    const DaColsumTail cs = da_colsum_tail(ws, da_conv1x1_wgrad_ws_bytes(M, Cin, Cout), Cout);
+    const int rc = da_pw_wgrad(in, dy, dw_io, M, 1, 1, 1, Cin, Cout, 1, 0, ws, cs.front, da_stream(stream), pro_scale, pro_shift, pro_slope);
     if (rc) return rc;
-    if (dbias) return da_colsum(dy, M, Cout, dbias, (char*)ws + cs_off, da_bn_ws_bytes(0, Cout), stream);
+    if (dbias) return da_colsum(dy, M, Cout, dbias, cs.ws, cs.bytes, stream);
     return 0;
 }
 
@@ -353,10 +362,8 @@ extern "C" size_t da_conv1x1_wgrad_ws_bytes(long long M, int Cin, int Cout) {
     long long per;
     const int O = Cin * Cout;
     const int parts = parts_for(da_cdiv(M, kWgR), O, &per);
-    size_t direct = da_align((size_t)parts * O * sizeof(float));
     const size_t mf = da_pw_supported(Cin, Cout) ? da_pw_wgrad_ws_bytes(M, 1, Cin, Cout) : 0;
-    if (mf > direct) direct = mf;
-    return direct + da_bn_ws_bytes(0, Cout) + 512;
+    return wgrad_bytes((size_t)parts * O, mf, Cout);
 }
 
 extern "C" int da_conv1x1_wgrad(const float* in, const float* dy, float* dw_io, float* dbias,
@@ -368,9 +375,9 @@ extern "C" int da_conv1x1_wgrad(const float* in, const float* dy, float* dw_io, 
     hipStream_t st = da_stream(stream);
     long long per;
     const int parts = parts_for(da_cdiv(M, kWgR), O, &per);
-    const size_t cs_off = ((ws_bytes - da_bn_ws_bytes(0, Cout)) / 256) * 256;
+    const DaColsumTail cs = da_colsum_tail(ws, da_conv1x1_wgrad_ws_bytes(M, Cin, Cout), Cout);
     int rc_pw = DA_ERR_UNSUPPORTED;
-    if (da_pw_supported(Cin, Cout)) rc_pw = da_pw_wgrad(in, dy, dw_io, M, 1, 1, 1, Cin, Cout, 1, 0, ws, cs_off, st);
+    if (da_pw_supported(Cin, Cout)) rc_pw = da_pw_wgrad(in, dy, dw_io, M, 1, 1, 1, Cin, Cout, 1, 0, ws, cs.front, st);
     if (rc_pw != 0 && rc_pw != DA_ERR_UNSUPPORTED) return rc_pw;
     if (rc_pw == DA_ERR_UNSUPPORTED) {
         // conv1x1_wgrad_kernel owns 16 x 256 outputs per block: a larger layer the matrix path declined is declined here too, never left partly written
@@ -382,7 +389,7 @@ extern "C" int da_conv1x1_wgrad(const float* in, const float* dy, float* dw_io, 
         DA_LAUNCH_CHECK();
     }
     if (dbias)
-        return da_colsum(dy, M, Cout, dbias, (char*)ws + cs_off, da_bn_ws_bytes(0, Cout), stream);
+        return da_colsum(dy, M, Cout, dbias, cs.ws, cs.bytes, stream);
     return 0;
 }
 
@@ -408,8 +415,9 @@ extern "C" int da_conv_k2s2_dgrad(const float* dy, const float* w_tio, float* dx
     return da_pw_gemm(dy, w_tio, 1, nullptr, dx, (long long)N * D * H * W, D, H, W, Cout, Cin, 8, 1, 0, ws, ws_bytes, da_stream(stream));
 }
 
+// The transposed conv's partials with the channels exchanged; the bias gradient has Cout entries, so the column-sum scratch is sized for the wider of Cin and Cout.
 extern "C" size_t da_conv_k2s2_wgrad_ws_bytes(int N, int D, int H, int W, int Cin, int Cout) {
-    return da_deconv_k2s2_wgrad_ws_bytes(N, D, H, W, Cout, Cin);
+    return k2s2_wgrad_bytes(N, D, H, W, Cout, Cin, Cin > Cout ? Cin : Cout);
 }
 
 // dw_toi: [8][Cout][Cin] (convert with da_w_tio_to_iok(dw_toi, dw_oik, Cout, Cin, 8)); dbias [Cout] optional
@@ -419,10 +427,10 @@ extern "C" int da_conv_k2s2_wgrad(const float* x, const float* dy, float* dw_toi
     if (!da_pw_supported(Cout, Cin)) return DA_ERR_UNSUPPORTED;
     if (ws_bytes < da_conv_k2s2_wgrad_ws_bytes(N, D, H, W, Cin, Cout)) return DA_ERR_WS_SMALL;
     hipStream_t st = da_stream(stream);
-    const size_t cs_off = ((ws_bytes - da_bn_ws_bytes(0, Cout)) / 256) * 256;
-    const int rc = da_pw_wgrad(dy, x, dw_toi, (long long)N * D * H * W, D, H, W, Cout, Cin, 8, 1, ws, cs_off, st);
+    const DaColsumTail cs = da_colsum_tail(ws, da_conv_k2s2_wgrad_ws_bytes(N, D, H, W, Cin, Cout), Cout);
+    const int rc = da_pw_wgrad(dy, x, dw_toi, (long long)N * D * H * W, D, H, W, Cout, Cin, 8, 1, ws, cs.front, st);
     if (rc) return rc;
-    if (dbias) return da_colsum(dy, (long long)N * D * H * W, Cout, dbias, (char*)ws + cs_off, da_bn_ws_bytes(0, Cout), stream);
+    if (dbias) return da_colsum(dy, (long long)N * D * H * W, Cout, dbias, cs.ws, cs.bytes, stream);
     return 0;
 }
 
@@ -465,11 +473,11 @@ extern "C" int da_deconv_k2s2_wgrad_bf16(const void* in, const void* dy, float* 
     if (!in || !dy || !dw_tio || N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return DA_ERR_BADARG;
     if (!da_pw_supported(Cin, Cout)) return DA_ERR_UNSUPPORTED;
     if (ws_bytes < da_deconv_k2s2_wgrad_ws_bytes(N, D, H, W, Cin, Cout)) return DA_ERR_WS_SMALL;
-    const size_t cs_off = ((ws_bytes - da_bn_ws_bytes(0, Cout)) / 256) * 256;
-    const int rc = da_pw_wgrad((const float*)in, (const float*)dy, dw_tio, (long long)N * D * H * W, D, H, W, Cin, Cout, 8, 1, ws, cs_off, da_stream(stream),
+    const DaColsumTail cs = da_colsum_tail(ws, da_deconv_k2s2_wgrad_ws_bytes(N, D, H, W, Cin, Cout), Cout);
+    const int rc = da_pw_wgrad((const float*)in, (const float*)dy, dw_tio, (long long)N * D * H * W, D, H, W, Cin, Cout, 8, 1, ws, cs.front, da_stream(stream),
                                nullptr, nullptr, -1.f, 1, 1);
     if (rc) return rc;
-    if (dbias) return da_colsum_bf16(dy, (long long)N * D * H * W * 8, Cout, dbias, (char*)ws + cs_off, da_bn_ws_bytes(0, Cout), stream);
+    if (dbias) return da_colsum_bf16(dy, (long long)N * D * H * W * 8, Cout, dbias, cs.ws, cs.bytes, stream);
     return 0;
 }
 
@@ -497,10 +505,10 @@ extern "C" int da_conv1x1_wgrad_bf16(const void* in, const float* dy, float* dw_
     if (!in || !dy || !dw_io || M <= 0 || Cin <= 0 || Cout <= 0) return DA_ERR_BADARG;
     if (!da_pw_supported(Cin, Cout)) return DA_ERR_UNSUPPORTED;
     if (ws_bytes < da_conv1x1_wgrad_ws_bytes(M, Cin, Cout)) return DA_ERR_WS_SMALL;
-    const size_t cs_off = ((ws_bytes - da_bn_ws_bytes(0, Cout)) / 256) * 256;
-    const int rc = da_pw_wgrad((const float*)in, dy, dw_io, M, 1, 1, 1, Cin, Cout, 1, 0, ws, cs_off, da_stream(stream), nullptr, nullptr, -1.f, 1, 0);
+    const DaColsumTail cs = da_colsum_tail(ws, da_conv1x1_wgrad_ws_bytes(M, Cin, Cout), Cout);
+    const int rc = da_pw_wgrad((const float*)in, dy, dw_io, M, 1, 1, 1, Cin, Cout, 1, 0, ws, cs.front, da_stream(stream), nullptr, nullptr, -1.f, 1, 0);
     if (rc) return rc;
-    if (dbias) return da_colsum(dy, M, Cout, dbias, (char*)ws + cs_off, da_bn_ws_bytes(0, Cout), stream);
+    if (dbias) return da_colsum(dy, M, Cout, dbias, cs.ws, cs.bytes, stream);
     return 0;
 }
 extern "C" int da_conv1x1_wgrad_pro_bf16(const void* in, const float* pro_scale, const float* pro_shift, float pro_slope,
@@ -509,9 +517,9 @@ extern "C" int da_conv1x1_wgrad_pro_bf16(const void* in, const float* pro_scale,
     if (!in || !pro_scale || !pro_shift || !dy || !dw_io || M <= 0 || Cin <= 0 || Cout <= 0) return DA_ERR_BADARG;
     if (!da_pw_supported(Cin, Cout)) return DA_ERR_UNSUPPORTED;
     if (ws_bytes < da_conv1x1_wgrad_ws_bytes(M, Cin, Cout)) return DA_ERR_WS_SMALL;
-    const size_t cs_off = ((ws_bytes - da_bn_ws_bytes(0, Cout)) / 256) * 256;
-    const int rc = da_pw_wgrad((const float*)in, dy, dw_io, M, 1, 1, 1, Cin, Cout, 1, 0, ws, cs_off, da_stream(stream), pro_scale, pro_shift, pro_slope, 1, 0);
+    const DaColsumTail cs = da_colsum_tail(ws, da_conv1x1_wgrad_ws_bytes(M, Cin, Cout), Cout);
+    const int rc = da_pw_wgrad((const float*)in, dy, dw_io, M, 1, 1, 1, Cin, Cout, 1, 0, ws, cs.front, da_stream(stream), pro_scale, pro_shift, pro_slope, 1, 0);
     if (rc) return rc;
-    if (dbias) return da_colsum(dy, M, Cout, dbias, (char*)ws + cs_off, da_bn_ws_bytes(0, Cout), stream);
+    if (dbias) return da_colsum(dy, M, Cout, dbias, cs.ws, cs.bytes, stream);
     return 0;
 }

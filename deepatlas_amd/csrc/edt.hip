@@ -704,19 +704,16 @@ sd_finish_kernel(const unsigned* __restrict__ cnt, const unsigned long long* __r
 
 int sd_order(int connectivity) { return connectivity == 6 ? 1 : connectivity == 18 ? 2 : connectivity == 26 ? 3 : 0; }
 
-// the workspace behind the two transform buffers: list | cnt | cursor | maxbits | off | partial
-struct SdWs { size_t list, cnt, cursor, maxbits, off, partial, total; };
-SdWs sd_layout(int N, int Kp, long long V, size_t edt_bytes) {
+// the two buffers the transform's passes alternate between, G site sets of N volumes each
+struct EdtWs { float *a, *b; size_t bytes; };
+EdtWs edt_carve(DaCarve& c, int N, int G, long long V) { return EdtWs{c.take<float>((size_t)N * G * (size_t)V), c.take<float>((size_t)N * G * (size_t)V), c.off}; }
+EdtWs edt_layout(int N, int G, long long V, void* ws) { DaCarve c(ws); return edt_carve(c, N, G, V); }
+// the surface distances' workspace: the transform buffers, then list | cnt | cursor | maxbits | off | partial; cnt, cursor and maxbits are packed: zeroed together
+struct SdWs { EdtWs edt; unsigned *list, *cnt, *cursor, *maxbits; unsigned long long* off; double* partial; size_t total; };
+SdWs sd_layout(int N, int Kp, long long V, void* ws) {
     const size_t S = (size_t)N * Kp;
-    SdWs w;
-    w.list = edt_bytes;
-    w.cnt = w.list + da_align(2 * (size_t)N * (size_t)V * sizeof(unsigned));
-    w.cursor = w.cnt + S * 2 * sizeof(unsigned);                           // cnt, cursor and maxbits are zeroed together
-    w.maxbits = w.cursor + S * sizeof(unsigned);
-    w.off = da_align(w.maxbits + S * 2 * sizeof(unsigned));
-    w.partial = da_align(w.off + S * sizeof(unsigned long long));
-    w.total = da_align(w.partial + S * 2 * kSdBlocks * sizeof(double));
-    return w;
+    DaCarve c(ws); return SdWs{edt_carve(c, N, edt_group(N, V, Kp), V), c.take<unsigned>(2 * (size_t)N * (size_t)V), c.take<unsigned>(S * 2, 1), c.take<unsigned>(S, 1), c.take<unsigned>(S * 2),
+                c.take<unsigned long long>(S), c.take<double>(S * 2 * kSdBlocks), c.off};
 }
 
 }  // namespace
@@ -724,7 +721,7 @@ SdWs sd_layout(int N, int Kp, long long V, size_t edt_bytes) {
 extern "C" size_t da_edt_ws_bytes(int N, int Kp, int D, int H, int W) {
     if (Kp < 1 || edt_extents(N, D, H, W) != 0) return 0;
     const long long V = (long long)D * H * W;
-    return 2 * da_align((size_t)N * edt_group(N, V, Kp) * (size_t)V * sizeof(float));
+    return edt_layout(N, edt_group(N, V, Kp), V, nullptr).bytes;
 }
 
 extern "C" int da_edt_sq(const void* mask, int mask_bytes, int N, int D, int H, int W, float sD, float sH, float sW, int take_sqrt,
@@ -733,8 +730,7 @@ extern "C" int da_edt_sq(const void* mask, int mask_bytes, int N, int D, int H, 
     if (const int rc = edt_extents(N, D, H, W)) return rc;
     if (ws_bytes < da_edt_ws_bytes(N, 1, D, H, W)) return DA_ERR_WS_SMALL;
     const long long V = (long long)D * H * W;
-    float* a = (float*)ws;
-    float* b = (float*)((char*)ws + da_align((size_t)N * (size_t)V * sizeof(float)));
+    const auto [a, b, need] = edt_layout(N, 1, V, ws);
     EdtEpi e{take_sqrt ? 1 : 0, nullptr, 0, nullptr, 0, 0, 1, 1, V};
     return edt_passes(mask, mask_bytes, nullptr, 0, 1, 0, N, D, H, W, sD, sH, sW, a, b, out, e, da_stream(stream));
 }
@@ -747,8 +743,7 @@ extern "C" int da_signed_distance_maps(const void* labels, int label_bytes, cons
     if (ws_bytes < da_edt_ws_bytes(N, Kp, D, H, W)) return DA_ERR_WS_SMALL;
     const long long V = (long long)D * H * W;
     const int G = edt_group(N, V, Kp);
-    float* a = (float*)ws;
-    float* b = (float*)((char*)ws + da_align((size_t)N * G * (size_t)V * sizeof(float)));
+    const auto [a, b, need] = edt_layout(N, G, V, ws);
     for (int g0 = 0; g0 < Kp; g0 += G) {
         const int g = Kp - g0 < G ? Kp - g0 : G;
         for (int complement = 0; complement < 2; ++complement) {
@@ -815,7 +810,7 @@ extern "C" int da_label_surface(const void* labels, int label_bytes, int N, int 
 extern "C" size_t da_surface_dist_ws_bytes(int N, int Kp, int D, int H, int W) {
     const size_t edt_bytes = da_edt_ws_bytes(N, Kp, D, H, W);
     if (!edt_bytes || Kp > 65535 || (long long)N * Kp > 0x7FFFFFFFLL) return 0;
-    return sd_layout(N, Kp, (long long)D * H * W, edt_bytes).total;
+    return sd_layout(N, Kp, (long long)D * H * W, nullptr).total;
 }
 
 extern "C" int da_surface_dist_stats(const void* pred, int pred_bytes, const void* truth, int truth_bytes, const int* classes, int Kp,
@@ -830,16 +825,8 @@ extern "C" int da_surface_dist_stats(const void* pred, int pred_bytes, const voi
     hipStream_t st = da_stream(stream);
     const long long V = (long long)D * H * W;
     const int G = edt_group(N, V, Kp), order = sd_order(connectivity), nb = sd_blocks(V);
-    const SdWs w = sd_layout(N, Kp, V, da_edt_ws_bytes(N, Kp, D, H, W));
-    char* base = (char*)ws;
-    float* a = (float*)base;
-    float* b = (float*)(base + da_align((size_t)N * G * (size_t)V * sizeof(float)));
-    unsigned* list = (unsigned*)(base + w.list);
-    unsigned* cnt = (unsigned*)(base + w.cnt);
-    unsigned* cursor = (unsigned*)(base + w.cursor);
-    unsigned* maxbits = (unsigned*)(base + w.maxbits);
-    unsigned long long* off = (unsigned long long*)(base + w.off);
-    double* partial = (double*)(base + w.partial);
+    const auto [edt, list, cnt, cursor, maxbits, off, partial, need] = sd_layout(N, Kp, V, ws);
+    float *a = edt.a, *b = edt.b;
     const long long S = (long long)N * Kp;
     if (const hipError_t e = hipMemsetAsync(cnt, 0, (size_t)S * 5 * sizeof(unsigned), st)) return (int)e;
     hipLaunchKernelGGL(sd_count_kernel, dim3(nb, Kp, N), dim3(256), 0, st, pred, pred_bytes, truth, truth_bytes, classes, Kp, D, H, W, order, cnt);

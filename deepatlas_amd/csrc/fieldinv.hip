@@ -218,7 +218,7 @@ extern "C" size_t da_field_invert_ws_bytes(int N, int D, int H, int W) {
 
 extern "C" size_t da_field_points_ws_bytes(int N, int P) {
     (void)P;
-    return da_align((size_t)(N > 0 ? N : 1) * kFiBlocks * kFiStats * sizeof(double));
+    return da_field_invert_ws_bytes(N, 0, 0, 0);          // the same per-sample statistics partials
 }
 
 extern "C" int da_field_invert(const float* disp, float* out, unsigned char* iters, int N, int D, int H, int W, int max_iters, float tol_vox,

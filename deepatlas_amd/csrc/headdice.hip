@@ -439,12 +439,18 @@ static bool hd_shape_ok(int K, int C) { return (K == 16 || K == 64) && (C == 16 
 
 }  // namespace
 
+// the packed head weights in front, then the bytes the two phases reuse: forward [Dice partials | isc], backward [dW + dbias partials | their sum]
+static float* hd_pack(DaCarve& c, int Cin, int C) { return c.take<float>((size_t)2 * Cin * C); }
+struct HdFwdWs { float* wp; DaDiceWs dice; };
+static HdFwdWs hd_fwd_layout(int N, int Cin, int C, void* ws) { DaCarve c(ws); return HdFwdWs{hd_pack(c, Cin, C), da_dice_carve(c, N, kHdBlocks, C)}; }
+struct HdBwdWs { float *wp, *wpartial, *folded; size_t bytes; };
+static HdBwdWs hd_bwd_layout(int Cin, int C, void* ws) {
+    DaCarve c(ws); return HdBwdWs{hd_pack(c, Cin, C), c.take<float>((size_t)kHdBlocks * (Cin * C + C)), c.take<float>((size_t)(Cin * C + C)), c.off};
+}
 extern "C" size_t da_head_dice_ws_bytes(int N, long long V, int Cin, int C) {
     (void)V;
-    const size_t pack = da_align((size_t)2 * Cin * C * sizeof(float));
-    const size_t fwd = da_align((size_t)N * kHdBlocks * 3 * C * sizeof(double)) + da_align((size_t)3 * N * C * sizeof(float));
-    const size_t bwd = da_align((size_t)kHdBlocks * (Cin * C + C) * sizeof(float)) + da_align((size_t)(Cin * C + C) * sizeof(float));
-    return pack + (fwd > bwd ? fwd : bwd);
+    const size_t fwd = hd_fwd_layout(N, Cin, C, nullptr).dice.bytes, bwd = hd_bwd_layout(Cin, C, nullptr).bytes;
+    return fwd > bwd ? fwd : bwd;
 }
 
 template <int KC, int NT, typename T>
@@ -469,12 +475,10 @@ static int head_dice_fwd_t(const float* x, const float* pro_scale, const float* 
     if (!hd_shape_ok(Cin, C) || (pro_scale && pro_slope >= 1.f)) return DA_ERR_UNSUPPORTED;
     if (ws_bytes < da_head_dice_ws_bytes(N, V, Cin, C)) return DA_ERR_WS_SMALL;
     hipStream_t st = da_stream(stream);
-    float* wp = (float*)ws;
+    const HdFwdWs l = hd_fwd_layout(N, Cin, C, ws);
+    float* wp = l.wp; double* partial = l.dice.partial; float* isc = l.dice.isc;
     hipLaunchKernelGGL(hd_pack_kernel, dim3(da_grid(Cin * C, 256, 64)), dim3(256), 0, st, w_io, wp, Cin, C, 0);
     DA_LAUNCH_CHECK();
-    char* rest = (char*)ws + da_align((size_t)2 * Cin * C * sizeof(float));
-    double* partial = (double*)rest;
-    float* isc = (float*)(rest + da_align((size_t)N * kHdBlocks * 3 * C * sizeof(double)));
     int nblocks = (int)da_cdiv(V, 256 * 2); if (nblocks > kHdBlocks) nblocks = kHdBlocks; if (nblocks < 1) nblocks = 1;
     HdP p;
     p.x = x; p.ps = pro_scale; p.pt = pro_shift; p.pslope = pro_scale ? (pro_slope < 0.f ? 1.f : pro_slope) : 1.f;
@@ -513,14 +517,11 @@ static int head_dice_bwd_t(const float* x, const float* pro_scale, const float* 
     if (!hd_shape_ok(Cin, C) || (pro_scale && pro_slope >= 1.f)) return DA_ERR_UNSUPPORTED;
     if (ws_bytes < da_head_dice_ws_bytes(N, V, Cin, C)) return DA_ERR_WS_SMALL;
     hipStream_t st = da_stream(stream);
-    float* wpf = (float*)ws;
+    const auto [wpf, wpartial, folded, need] = hd_bwd_layout(Cin, C, ws);
     const float* wpb = w_io;                 // the data-gradient A fragments are read straight from w_io [Cin][C]
     hipLaunchKernelGGL(hd_pack_kernel, dim3(da_grid(Cin * C, 256, 64)), dim3(256), 0, st, w_io, wpf, Cin, C, 0);
     DA_LAUNCH_CHECK();
-    char* rest = (char*)ws + da_align((size_t)2 * Cin * C * sizeof(float));
-    float* wpartial = (float*)rest;
     const int O = Cin * C + C;
-    float* folded = (float*)(rest + da_align((size_t)kHdBlocks * O * sizeof(float)));
     const long long nchunks = da_cdiv(V, 256) * N;
     int nblocks = (int)(nchunks < kHdBlocks ? nchunks : kHdBlocks); if (nblocks < 1) nblocks = 1;
     HdP p;

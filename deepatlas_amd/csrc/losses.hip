@@ -690,7 +690,7 @@ __global__ void label_overlap_counts_kernel(const void* __restrict__ pred, int p
 // ================================================================================================
 extern "C" size_t da_dice_ws_bytes(int N, long long V, int C) {
     (void)V;
-    return da_align((size_t)N * kDiceBlocks * 3 * C * sizeof(double)) + da_align((size_t)3 * N * C * sizeof(float));
+    return da_dice_layout(nullptr, N, kDiceBlocks, C).bytes;
 }
 
 extern "C" int da_dice_fwd(const float* src, const void* labels, int label_bytes, const float* soft_target,
@@ -700,8 +700,7 @@ extern "C" int da_dice_fwd(const float* src, const void* labels, int label_bytes
     if (labels && label_bytes != 1 && label_bytes != 8) return DA_ERR_BADARG;
     if (ws_bytes < da_dice_ws_bytes(N, V, C)) return DA_ERR_WS_SMALL;
     hipStream_t st = da_stream(stream);
-    double* partial = (double*)ws;
-    float* isc = (float*)((char*)ws + da_align((size_t)N * kDiceBlocks * 3 * C * sizeof(double)));
+    const auto [partial, isc, need] = da_dice_layout(ws, N, kDiceBlocks, C);
     const int lpv = lpv_for(C);
     int nblocks = (int)da_cdiv(V, 256); if (nblocks > kDiceBlocks) nblocks = kDiceBlocks;
     if (lpv > 0) {
@@ -730,8 +729,7 @@ extern "C" int da_softmax_dice_fwd(const float* src, const void* labels, int lab
     if (lpv <= 0) return DA_ERR_UNSUPPORTED;                               // callers run da_dice_fwd + da_softmax_fwd
     if (ws_bytes < da_dice_ws_bytes(N, V, C)) return DA_ERR_WS_SMALL;
     hipStream_t st = da_stream(stream);
-    double* partial = (double*)ws;
-    float* isc = (float*)((char*)ws + da_align((size_t)N * kDiceBlocks * 3 * C * sizeof(double)));
+    const auto [partial, isc, need] = da_dice_layout(ws, N, kDiceBlocks, C);
     int nblocks = (int)da_cdiv(V, 256); if (nblocks > kDiceBlocks) nblocks = kDiceBlocks;
     const int slots = 256 / lpv;
     hipLaunchKernelGGL(dice_partial_vec_kernel, dim3(nblocks, N), dim3(256), (size_t)3 * slots * C * sizeof(float), st,

@@ -242,9 +242,12 @@ static int mi_blocks(long long V) {
 
 }  // namespace
 
+// per-workgroup joint histograms [N][blocks][32 x 32], then their sum per sample
+struct MiWs { double *partial, *psum; size_t bytes; };
+static MiWs mi_layout(int N, long long V, void* ws) { DaCarve c(ws); return MiWs{c.take<double>((size_t)N * mi_blocks(V) * 1024), c.take<double>((size_t)N * 1024), c.off}; }
 extern "C" size_t da_mi_ws_bytes(int N, long long V, int bins) {
     if (N <= 0 || V <= 0 || bins < 2 || bins > 32) return 0;
-    return da_align((size_t)N * mi_blocks(V) * 1024 * sizeof(double)) + da_align((size_t)N * 1024 * sizeof(double));
+    return mi_layout(N, V, nullptr).bytes;
 }
 
 extern "C" int da_mi_fwd(const float* x, const float* y, int N, long long V, int bins, float vmin, float vmax, float sigma_ratio,
@@ -254,8 +257,7 @@ extern "C" int da_mi_fwd(const float* x, const float* y, int N, long long V, int
     hipStream_t st = da_stream(stream);
     const MiP p = mi_params(bins, vmin, vmax, sigma_ratio);
     const int nb = mi_blocks(V);
-    double* partial = (double*)ws;
-    double* psum = (double*)((char*)ws + da_align((size_t)N * nb * 1024 * sizeof(double)));
+    const auto [partial, psum, need] = mi_layout(N, V, ws);
     hipLaunchKernelGGL(mi_partial_kernel, dim3(nb, N), dim3(256), 0, st, x, y, V, p, partial);
     DA_LAUNCH_CHECK();
     hipLaunchKernelGGL(mi_reduce_kernel, dim3(16, N), dim3(256), 0, st, (const double*)partial, nb, psum);

@@ -368,9 +368,12 @@ int launch_partial(const RowPlan& p, const T* x, const T* dy, const float* mean,
 
 }  // namespace
 
+// per-workgroup column sums, then cm[2][C], the per-channel constants of the backward's apply pass
+struct BnWs { double* partial; float* cm; size_t bytes; };
+static BnWs bn_layout(int C, void* ws) { DaCarve c(ws); return BnWs{c.take<double>((size_t)kMaxBlocks * 2 * C), c.take<float>((size_t)2 * C), c.off}; }
 extern "C" size_t da_bn_ws_bytes(long long M, int C) {
     (void)M;
-    return da_align((size_t)kMaxBlocks * 2 * C * sizeof(double)) + da_align((size_t)2 * C * sizeof(float));
+    return bn_layout(C, nullptr).bytes;
 }
 
 template <typename T>
@@ -464,8 +467,7 @@ static int bn_act_bwd_impl(const T* dy, const T* x, const float* mean, const flo
     if (!dy || !x || !dx || M <= 0 || C <= 0 || C > 1024) return DA_ERR_BADARG;
     if (ws_bytes < da_bn_ws_bytes(M, C)) return DA_ERR_WS_SMALL;
     const RowPlan p = plan_rows(M, C);
-    double* partial = (double*)ws;
-    float* cm = (float*)((char*)ws + da_align((size_t)kMaxBlocks * 2 * C * sizeof(double)));
+    const auto [partial, cm, need] = bn_layout(C, ws);
     hipStream_t st = da_stream(stream);
     if (pre && pre_n > 0) {
         // the two sums arrive from the kernel that produced dy (sum dz, sum dz (x - mean) per workgroup): no reduction pass over (dy, x)
@@ -507,8 +509,7 @@ int da_bn_bwd_sums(const float* dy, const float* x, const float* mean, const flo
     if (!dy || !x || M <= 0 || C <= 0 || C > 1024) return DA_ERR_BADARG;
     if (ws_bytes < da_bn_ws_bytes(M, C)) return DA_ERR_WS_SMALL;
     const RowPlan p = plan_rows(M, C);
-    double* partial = (double*)ws;
-    float* cm = (float*)((char*)ws + da_align((size_t)kMaxBlocks * 2 * C * sizeof(double)));
+    const auto [partial, cm, need] = bn_layout(C, ws);
     if (pre && pre_n > 0) {
         hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(64), 0, st, pre, pre_n, M, C, dgamma, dbeta, cm, rstd);
     } else {

@@ -786,10 +786,12 @@ static size_t wg_partial_bytes(long long M, int ntaps, int Cin, int Cout) {
     return worst;
 }
 
-size_t da_pw_wgrad_ws_bytes(long long M, int ntaps, int Cin, int Cout) {
-    const size_t O = (size_t)ntaps * (Cin < 64 ? Cin : 64) * (Cout < 64 ? Cout : 64);      // one (<= 64 x 64) slice at a time: its reduced result behind the partials
-    return wg_partial_bytes(M, ntaps, Cin, Cout) + da_align(O * sizeof(float));
+// the block partials of EVERY slice shape of the layer, then the reduced result of one (<= 64 x 64) slice at a time
+struct PwWgWs { float *partial, *tmp; size_t bytes; };
+static PwWgWs pw_wgrad_layout(long long M, int ntaps, int Cin, int Cout, void* ws) {
+    DaCarve c(ws); return PwWgWs{(float*)c.take<char>(wg_partial_bytes(M, ntaps, Cin, Cout)), c.take<float>((size_t)ntaps * (Cin < 64 ? Cin : 64) * (Cout < 64 ? Cout : 64)), c.off};
 }
+size_t da_pw_wgrad_ws_bytes(long long M, int ntaps, int Cin, int Cout) { return pw_wgrad_layout(M, ntaps, Cin, Cout, nullptr).bytes; }
 
 __global__ void pw_place_kernel(const float* __restrict__ src, float* __restrict__ dw, int ntaps, int cic, int coc, int Cin, int Cout, int ci0, int co0) {
     const int total = ntaps * cic * coc;
@@ -826,7 +828,7 @@ int da_pw_wgrad(const float* in, const float* dy, float* dw, long long M, int D,
     if (ws_bytes < da_pw_wgrad_ws_bytes(M, ntaps, Cin, Cout)) return DA_ERR_WS_SMALL;
     if (Cin <= 64 && Cout <= 64) return pw_wgrad_slice(in, dy, dw, M, D, H, W, Cin, Cout, Cin, Cout, ntaps, up, ws, st, pro, 0);
     // wide layers: independent 64 x 64 channel slices, each reduced into a dense scratch and placed into dW
-    float* tmp = (float*)((char*)ws + wg_partial_bytes(M, ntaps, Cin, Cout));      // behind the partials of EVERY slice shape of this layer
+    float* tmp = pw_wgrad_layout(M, ntaps, Cin, Cout, ws).tmp;
     for (int ci0 = 0; ci0 < Cin; ci0 += 64)
         for (int co0 = 0; co0 < Cout; co0 += 64) {
             const int cic = (Cin - ci0) < 64 ? (Cin - ci0) : 64, coc = (Cout - co0) < 64 ? (Cout - co0) : 64;
@@ -900,11 +902,13 @@ static int pw_wgrad_slice(const float* in, const float* dy, float* dw, long long
 // ---- fused BatchNorm-backward + transposed-conv backward (deconv_bn_bwd_kernel) ----
 bool da_deconv_bn_bwd_supported(int Cin, int Cout) { return Cin == 32 && Cout == 32; }      // one (cout, cin) tile pair per wave pair: the full-resolution up-sampler of UNet_light
 static int db_blocks(long long nchunks) { return (int)(nchunks < 512 ? nchunks : 512); }    // two workgroups per CU
-size_t da_deconv_bn_bwd_ws_bytes(long long M, int Cin, int Cout) {
-    const long long nchunks = da_cdiv(M, 32);
-    const int nb = db_blocks(nchunks);
-    return da_pw_packed_bytes(8, Cout, Cin) + da_align((size_t)nb * 8 * Cin * Cout * sizeof(float)) + da_align((size_t)nb * 2 * Cout * sizeof(double));
+// the packed weights, then the per-workgroup dW and column-sum partials
+struct DbWs { float *wp, *dwp; double* colp; size_t bytes; };
+static DbWs db_layout(long long M, int Cin, int Cout, void* ws) {
+    const int nb = db_blocks(da_cdiv(M, 32));
+    DaCarve c(ws); return DbWs{(float*)c.take<char>(da_pw_packed_bytes(8, Cout, Cin)), c.take<float>((size_t)nb * 8 * Cin * Cout), c.take<double>((size_t)nb * 2 * Cout), c.off};
 }
+size_t da_deconv_bn_bwd_ws_bytes(long long M, int Cin, int Cout) { return db_layout(M, Cin, Cout, nullptr).bytes; }
 int da_deconv_bn_bwd(const float* gout, const float* y, const float* mean, const float* rstd, const float* scale, const float* shift, const float* cm, float slope,
                      const float* in, const float* w_tio, float* dx, float* dw_tio, float* dbias,
                      long long M, int D, int H, int W, int Cin, int Cout, void* ws, size_t ws_bytes, hipStream_t st) {
@@ -913,9 +917,7 @@ int da_deconv_bn_bwd(const float* gout, const float* y, const float* mean, const
     if ((unsigned long long)M * 8ull * (unsigned long long)Cout >= (1ull << 62)) return DA_ERR_UNSUPPORTED;
     const long long nchunks = da_cdiv(M, 32);
     const int nb = db_blocks(nchunks);
-    float* wp = (float*)ws;
-    float* dwp = (float*)((char*)ws + da_pw_packed_bytes(8, Cout, Cin));
-    double* colp = (double*)((char*)dwp + da_align((size_t)nb * 8 * Cin * Cout * sizeof(float)));
+    const auto [wp, dwp, colp, need] = db_layout(M, Cin, Cout, ws);
     // B_t[k = cout][j = cin] = w_tio[(t * Cin + cin) * Cout + cout]: the data gradient's packing (da_deconv_k2s2_dgrad)
     hipLaunchKernelGGL(pw_pack_kernel, dim3(da_grid((long long)8 * Cin * Cout, 256, 512)), dim3(256), 0, st, w_tio, wp, 8, Cout, Cin, 1, Cout, Cin, 0, 0);
     DA_LAUNCH_CHECK();

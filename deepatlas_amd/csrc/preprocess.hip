@@ -254,8 +254,9 @@ __global__ void label_lut_kernel(const T* __restrict__ src, T* __restrict__ dst,
 
 constexpr long long PP_MAX_V = 1LL << 31;
 inline int pp_parts(long long n) { return (int)(da_cdiv(n, PP_BLOCK) < PP_MAX_PARTS ? da_cdiv(n, PP_BLOCK) : PP_MAX_PARTS); }
-inline size_t pp_select_hist_off() { return da_align(sizeof(SelectState)); }
-inline size_t pp_select_nan_off() { return pp_select_hist_off() + da_align(sizeof(unsigned) * PP_MAX_RANKS * PP_BINS); }
+// the selection's state, its histograms and the NaN counter in a 256-byte slot of its own; zeroed together
+struct SelectWs { SelectState* state; unsigned *hist, *nan_count; size_t bytes; };
+inline SelectWs pp_select_layout(void* ws) { DaCarve c(ws); return SelectWs{c.take<SelectState>(1), c.take<unsigned>((size_t)PP_MAX_RANKS * PP_BINS), c.take<unsigned>(1), c.off}; }
 
 }  // namespace
 
@@ -308,7 +309,7 @@ extern "C" int da_volume_moments(const void* src, int src_dtype, long long n, do
 
 extern "C" size_t da_volume_percentiles_ws_bytes(long long n) {
     if (n <= 0 || n >= PP_MAX_V) return 0;
-    return pp_select_nan_off() + 256;
+    return pp_select_layout(nullptr).bytes;
 }
 
 extern "C" int da_volume_percentiles(const void* src, int src_dtype, long long n, const double* percentiles, int n_percentiles, double* out8,
@@ -319,10 +320,8 @@ extern "C" int da_volume_percentiles(const void* src, int src_dtype, long long n
     if (n >= PP_MAX_V) return DA_ERR_UNSUPPORTED;
     if (ws_bytes < da_volume_percentiles_ws_bytes(n)) return DA_ERR_WS_SMALL;
     hipStream_t st = da_stream(stream);
-    SelectState* state = (SelectState*)ws;
-    unsigned* hist = (unsigned*)((char*)ws + pp_select_hist_off());
-    unsigned* nan_count = (unsigned*)((char*)ws + pp_select_nan_off());
-    hipError_t e = hipMemsetAsync(ws, 0, da_volume_percentiles_ws_bytes(n), st);
+    const auto [state, hist, nan_count, bytes] = pp_select_layout(ws);
+    hipError_t e = hipMemsetAsync(ws, 0, bytes, st);
     if (e != hipSuccess) return (int)e;
     const long long per_group = (long long)PP_BLOCK * 16;
     const int groups = (int)(da_cdiv(n, per_group) < PP_HIST_GROUPS ? da_cdiv(n, per_group) : PP_HIST_GROUPS);

@@ -515,15 +515,24 @@ __global__ void gradloss_bwd_kernel(const float* __restrict__ disp, const float*
 // ================================================================================================
 static inline int lncc_out(int L, int F, int dil, int stride) { const int span = dil * (F - 1) + 1; return L < span ? 0 : (L - span) / stride + 1; }
 
+// separable form, the two phases reuse the same bytes.  forward: box sums along W, then H, of the 5 fields, and the loss partials;
+// backward: the 7 gradient fields G [7][N][Do][Ho][Wo] and their box adjoints along D, then H
+struct LnccFwdWs { float *t1, *t2; double* partial; size_t bytes; };
+static LnccFwdWs lncc_fwd_layout(size_t N, size_t D, size_t H, size_t Ho, size_t Wo, void* ws) {
+    DaCarve c(ws); return LnccFwdWs{c.take<float>(5 * N * D * H * Wo), c.take<float>(5 * N * D * Ho * Wo), c.take<double>(kBlocks), c.off};
+}
+struct LnccBwdWs { float *G, *g1, *g2; size_t bytes; };
+static LnccBwdWs lncc_bwd_layout(size_t N, size_t D, size_t H, size_t Do, size_t Ho, size_t Wo, void* ws) {
+    DaCarve c(ws); return LnccBwdWs{c.take<float>(7 * N * Do * Ho * Wo), c.take<float>(7 * N * D * Ho * Wo), c.take<float>(7 * N * D * H * Wo), c.off};
+}
+
 extern "C" size_t da_lncc_ws_bytes(int N, int D, int H, int W, int F, int dil, int stride) {
     if (F < 1 || dil < 1 || stride < 1) return 0;
     const size_t Wo = lncc_out(W, F, dil, stride), Ho = lncc_out(H, F, dil, stride), Do = lncc_out(D, F, dil, stride);
     if (!Wo || !Ho || !Do) return 0;
     const MarchGeom mg = lncc_march_geom(N, (int)Do, (int)Ho, (int)Wo, F, lncc_march_ok(D, H, W, F, dil, stride));
     if (mg.ok) return da_align((size_t)mg.ntx * mg.nty * mg.nch * N * sizeof(double));     // marching form: the loss partials only
-    // forward: t1 [5][N][D][H][Wo], t2 [5][N][D][Ho][Wo], partials; backward: G [7][N][Do][Ho][Wo], [7][N][D][Ho][Wo], [7][N][D][H][Wo]
-    const size_t fwd = da_align((size_t)5 * N * D * H * Wo * 4) + da_align((size_t)5 * N * D * Ho * Wo * 4) + da_align((size_t)kBlocks * 8);
-    const size_t bwd = da_align((size_t)7 * N * Do * Ho * Wo * 4) + da_align((size_t)7 * N * D * Ho * Wo * 4) + da_align((size_t)7 * N * D * H * Wo * 4);
+    const size_t fwd = lncc_fwd_layout(N, D, H, Ho, Wo, nullptr).bytes, bwd = lncc_bwd_layout(N, D, H, Do, Ho, Wo, nullptr).bytes;
     return fwd > bwd ? fwd : bwd;
 }
 
@@ -548,9 +557,7 @@ extern "C" int da_lncc_fwd(const float* I, const float* J, int N, int D, int H, 
         DA_LAUNCH_CHECK();
         return 0;
     }
-    float* t1 = (float*)ws;
-    float* t2 = (float*)((char*)ws + da_align((size_t)5 * N * D * H * Wo * 4));
-    double* partial = (double*)((char*)t2 + da_align((size_t)5 * N * D * Ho * Wo * 4));
+    const auto [t1, t2, partial, need] = lncc_fwd_layout(N, D, H, Ho, Wo, ws);
     const long long rows = (long long)N * D * H;
     hipLaunchKernelGGL(lncc_boxw_kernel, dim3(da_grid(rows * Wo, 256)), dim3(256), 0, st, I, J, t1, rows, W, Wo, F, rows * Wo, dil, stride);
     DA_LAUNCH_CHECK();
@@ -585,9 +592,7 @@ extern "C" int da_lncc_bwd(const float* I, const float* J, const float* sums, co
         DA_LAUNCH_CHECK();
         return 0;
     }
-    float* G = (float*)ws;
-    float* g1 = (float*)((char*)ws + da_align((size_t)7 * N * Do * Ho * Wo * 4));
-    float* g2 = (float*)((char*)g1 + da_align((size_t)7 * N * D * Ho * Wo * 4));
+    const auto [G, g1, g2, need] = lncc_bwd_layout(N, D, H, Do, Ho, Wo, ws);
     const long long P = (long long)N * Do * Ho * Wo;
     hipLaunchKernelGGL(lncc_bwd_fields_kernel, dim3(da_grid(P, 256)), dim3(256), 0, st, sums, G, P, (float)((double)F * F * F), eps, dloss, (float)(1.0 / (double)P));
     DA_LAUNCH_CHECK();

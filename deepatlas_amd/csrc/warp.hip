@@ -1163,9 +1163,10 @@ extern "C" int da_warp_labels_bwd(const float* dout, const void* labels, int lab
     return 0;
 }
 
-extern "C" size_t da_warp_bwd_dsrc_det_ws_bytes(int N, int D, int H, int W, int C) {
-    return da_align((size_t)N * D * H * W * C * sizeof(unsigned long long)) + 256;
-}
+// fixed-point accumulators, then the bits of the gradient's largest magnitude in a 256-byte slot of their own; zeroed together
+struct DetWs { unsigned long long* acc; unsigned int* max_bits; size_t bytes; };
+static DetWs det_layout(int N, int D, int H, int W, int C, void* ws) { DaCarve c(ws); return DetWs{c.take<unsigned long long>((size_t)N * D * H * W * C), c.take<unsigned int>(1), c.off}; }
+extern "C" size_t da_warp_bwd_dsrc_det_ws_bytes(int N, int D, int H, int W, int C) { return det_layout(N, D, H, W, C, nullptr).bytes; }
 
 extern "C" int da_warp_bwd_dsrc_det(const float* dout, const float* disp, float* d_src, int N, int D, int H, int W, int C,
                                     void* ws, size_t ws_bytes, void* stream) {
@@ -1173,10 +1174,8 @@ extern "C" int da_warp_bwd_dsrc_det(const float* dout, const float* disp, float*
     if (ws_bytes < da_warp_bwd_dsrc_det_ws_bytes(N, D, H, W, C)) return DA_ERR_WS_SMALL;
     hipStream_t st = da_stream(stream);
     const long long tot = (long long)N * D * H * W * C;
-    const size_t acc_bytes = da_align((size_t)tot * sizeof(unsigned long long));
-    unsigned long long* acc = (unsigned long long*)ws;
-    unsigned int* max_bits = (unsigned int*)((char*)ws + acc_bytes);
-    hipError_t e = hipMemsetAsync(ws, 0, acc_bytes + 256, st);
+    const auto [acc, max_bits, bytes] = det_layout(N, D, H, W, C, ws);
+    hipError_t e = hipMemsetAsync(ws, 0, bytes, st);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(absmax_kernel, dim3(da_grid(tot, 256)), dim3(256), 0, st, dout, tot, max_bits);
     DA_LAUNCH_CHECK();
@@ -1191,7 +1190,7 @@ extern "C" int da_warp_bwd_dsrc_det(const float* dout, const float* disp, float*
 static const int kLwdBlocks = 4096;          // (a gather kernel hides its two dependent memory latencies with waves: 16 workgroups per CU)
 
 extern "C" size_t da_label_warp_dice_ws_bytes(int N, int C) {
-    return da_align((size_t)N * kLwdBlocks * 3 * C * sizeof(double)) + da_align((size_t)3 * N * C * sizeof(float));
+    return da_dice_layout(nullptr, N, kLwdBlocks, C).bytes;
 }
 
 extern "C" int da_label_warp_dice_fwd(const void* lab_m, int lab_m_bytes, const void* lab_t, int lab_t_bytes, const float* disp,
@@ -1202,8 +1201,7 @@ extern "C" int da_label_warp_dice_fwd(const void* lab_m, int lab_m_bytes, const 
     if (C > 64) return DA_ERR_UNSUPPORTED;                               // callers fall back to warp(one-hot) + Dice
     if (ws_bytes < da_label_warp_dice_ws_bytes(N, C)) return DA_ERR_WS_SMALL;
     hipStream_t st = da_stream(stream);
-    double* partial = (double*)ws;
-    float* isc = (float*)((char*)ws + da_align((size_t)N * kLwdBlocks * 3 * C * sizeof(double)));
+    const auto [partial, isc, need] = da_dice_layout(ws, N, kLwdBlocks, C);
     const long long V = (long long)D * H * W;
     int nblocks = (int)da_cdiv(V, 256 * 2); if (nblocks > kLwdBlocks) nblocks = kLwdBlocks; if (nblocks < 1) nblocks = 1;
     hipLaunchKernelGGL(label_warp_dice_partial_kernel, dim3(nblocks, N), dim3(256), 0, st, lab_m, lab_m_bytes, lab_t, lab_t_bytes, disp, D, H, W, C, partial);
@@ -1223,8 +1221,7 @@ extern "C" int da_warp_dice_fwd(const float* src, const float* disp, const void*
     int lpv; if (!vec_ok(C, &lpv) || C > 64) return DA_ERR_UNSUPPORTED;       // callers run da_warp_fwd + da_dice_fwd
     if (ws_bytes < da_warp_dice_ws_bytes(N, C)) return DA_ERR_WS_SMALL;
     hipStream_t st = da_stream(stream);
-    double* partial = (double*)ws;
-    float* isc = (float*)((char*)ws + da_align((size_t)N * kLwdBlocks * 3 * C * sizeof(double)));
+    const auto [partial, isc, need] = da_dice_layout(ws, N, kLwdBlocks, C);
     const long long V = (long long)D * H * W;
     const int slots = 256 / lpv;
     int nblocks = (int)da_cdiv(V, (long long)slots * 4); if (nblocks > kLwdBlocks) nblocks = kLwdBlocks; if (nblocks < 1) nblocks = 1;
@@ -1312,8 +1309,7 @@ extern "C" int da_softwarp_dice_fwd(const void* lab_m, int lab_m_bytes, const fl
     if (!softwarp_classes_ok(C)) return DA_ERR_UNSUPPORTED;             // callers compose da_warp_labels_fwd + da_dice_fwd
     if (ws_bytes < da_softwarp_dice_ws_bytes(N, C)) return DA_ERR_WS_SMALL;
     hipStream_t st = da_stream(stream);
-    double* partial = (double*)ws;
-    float* isc = (float*)((char*)ws + da_align((size_t)N * kLwdBlocks * 3 * C * sizeof(double)));
+    const auto [partial, isc, need] = da_dice_layout(ws, N, kLwdBlocks, C);
     const long long V = (long long)D * H * W;
     int nblocks = (int)da_cdiv(V, 256 * 2); if (nblocks > kLwdBlocks) nblocks = kLwdBlocks; if (nblocks < 1) nblocks = 1;
     const dim3 grid(nblocks, N);

@@ -10,7 +10,9 @@
  *   - every activation tensor is fp32, channels-last 3D ("NDHWC"): [N][D][H][W][C], dense.
  *     (torch side: a N x C x D x H x W tensor with torch.channels_last_3d strides.)
  *   - raw device pointers, explicit dims, no hidden allocation: scratch memory is passed in as
- *     (ws, ws_bytes); da_*_ws_bytes() returns the size a call needs.
+ *     (ws, ws_bytes); da_*_ws_bytes() returns the size a call needs.  A call only checks ws_bytes
+ *     against that size (DA_ERR_WS_SMALL): where it places things inside ws depends on the shape
+ *     alone, never on how much more the caller passed.
  *   - `stream` is a hipStream_t (NULL = default stream).  Calls only enqueue work.
  *   - return value: 0 on success, otherwise a hipError_t, or DA_ERR_* (negative) for bad arguments.
  *   - 3x3x3 conv weights use the "TIO" layout [27 taps (kd,kh,kw)][Cin][Cout]; 2x2x2 transposed-conv
