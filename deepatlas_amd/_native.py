@@ -172,6 +172,8 @@ SIGNATURES = {
     'da_assemble_tiles': (I, [P, P, I, I, I, I, P, P, I, P]),
     'da_blend_accumulate': (I, [P, P, I, I, I, I, P, P, I, I, P, P, P, I, P]),
     'da_blend_finalize': (I, [P, LL, I, P, P, P]),
+    'da_bspline3_prefilter': (I, [P, I, P, I, I, I, I, I, P]),
+    'da_warp_frames': (I, [P, I, P, P, P, I, I, I, I, I, I, I, I, I, I, POINTER(c_double), POINTER(c_double), I, DBL, P]),
     'da_synth_volume': (I, [P, P, I, I, I, I, I, I, F, ctypes.c_uint, I, P]),
     'da_resample_axes': (I, [P, I, P, I, I, I, I, I, I, I, I, P, DBL, P]),
     'da_volume_moments_ws_bytes': (SZ, [LL]),

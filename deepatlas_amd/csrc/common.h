@@ -420,3 +420,39 @@ __device__ __forceinline__ bool da_is_finite_coord(float a, float b, float c) {
     // NaN / huge coordinates -> every tap out of range (int conversion of NaN is undefined)
     return fabsf(a) < 1e9f && fabsf(b) < 1e9f && fabsf(c) < 1e9f;
 }
+
+// B[u]: the displacement field u [D][H][W][3] (normalised units, channels (x, y, z) = (W, H, D) axis) sampled trilinearly with BORDER padding,
+// F.grid_sample(u, p, 'bilinear', 'border', align_corners=True).  One definition for the field inversion and the transport of points
+// (fieldinv.hip) and the native-grid warp (regapply.hip): a point carried through a field and a voxel warped through it sample the same value.
+struct DaFieldDims { int D, H, W; float sx, sy, sz; };
+
+__device__ __forceinline__ DaFieldDims da_field_dims(int D, int H, int W) {
+    DaFieldDims m; m.D = D; m.H = H; m.W = W;
+    m.sx = da_vox_scale(W); m.sy = da_vox_scale(H); m.sz = da_vox_scale(D);
+    return m;
+}
+
+// B[u] at the normalised coordinate (gx, gy, gz), which has passed da_is_finite_coord.  After the clamp 0 <= x0 <= W - 1, so the low tap is
+// always in range; the high tap is read only below the extent (its weight is 0 otherwise).
+__device__ __forceinline__ bool da_field_sample_border(const float* __restrict__ u, const DaFieldDims& m, float gx, float gy, float gz, float& bx, float& by, float& bz) {
+#pragma clang fp contract(off)       // every product and sum rounded on its own: the two kernels that inline this compute the same bits
+    const float wx = (float)(m.W - 1), wy = (float)(m.H - 1), wz = (float)(m.D - 1);
+    const float rx = ((gx + 1.f) / 2.f) * wx, ry = ((gy + 1.f) / 2.f) * wy, rz = ((gz + 1.f) / 2.f) * wz;
+    const bool outside = !(rx >= 0.f && rx <= wx && ry >= 0.f && ry <= wy && rz >= 0.f && rz <= wz);
+    const float ix = fminf(fmaxf(rx, 0.f), wx), iy = fminf(fmaxf(ry, 0.f), wy), iz = fminf(fmaxf(rz, 0.f), wz);
+    const float fx = floorf(ix), fy = floorf(iy), fz = floorf(iz);
+    const int x0 = min(max((int)fx, 0), m.W - 1), y0 = min(max((int)fy, 0), m.H - 1), z0 = min(max((int)fz, 0), m.D - 1);
+    const float ax1 = ix - fx, ax0 = (fx + 1.f) - ix, ay1 = iy - fy, ay0 = (fy + 1.f) - iy, az1 = iz - fz, az0 = (fz + 1.f) - iz;
+    bx = 0.f; by = 0.f; bz = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int cz = k >> 2, cy = (k >> 1) & 1, cx = k & 1;
+        const int x = x0 + cx, y = y0 + cy, z = z0 + cz;
+        if (x < m.W && y < m.H && z < m.D) {
+            const float wgt = (cx ? ax1 : ax0) * (cy ? ay1 : ay0) * (cz ? az1 : az0);
+            const float* b = u + ((z * m.H + y) * m.W + x) * 3;
+            bx += b[0] * wgt; by += b[1] * wgt; bz += b[2] * wgt;
+        }
+    }
+    return outside;
+}

@@ -25,7 +25,7 @@ namespace {
 constexpr int kFiBlocks = 2048;    // partial rows per sample (multiple of 8: XCD-contiguous split), the launch of invcons.hip
 constexpr int kFiStats = 4;
 
-struct FiDims { int D, H, W; float sx, sy, sz; };
+using FiDims = DaFieldDims;      // common.h: B[u] is shared with the native-grid warp (regapply.hip)
 
 struct FiResult {
     float vx, vy, vz;      // v after the last update, normalised units; NaN where `bad`
@@ -34,37 +34,6 @@ struct FiResult {
     bool bad;              // a coordinate failed da_is_finite_coord (no memory was read for it), or the update itself is not finite
     bool outside;          // the last sample point left [0, size - 1] on some axis
 };
-
-__device__ __forceinline__ FiDims fi_dims(int D, int H, int W) {
-    FiDims m; m.D = D; m.H = H; m.W = W;
-    m.sx = da_vox_scale(W); m.sy = da_vox_scale(H); m.sz = da_vox_scale(D);
-    return m;
-}
-
-// B[u] at the normalised coordinate (gx, gy, gz), which has passed da_is_finite_coord.  After the clamp 0 <= x0 <= W - 1, so the low tap is
-// always in range; the high tap is read only below the extent (its weight is 0 otherwise).
-__device__ __forceinline__ bool fi_sample(const float* __restrict__ u, const FiDims& m, float gx, float gy, float gz, float& bx, float& by, float& bz) {
-#pragma clang fp contract(off)       // every product and sum rounded on its own: the two kernels that inline this compute the same bits
-    const float wx = (float)(m.W - 1), wy = (float)(m.H - 1), wz = (float)(m.D - 1);
-    const float rx = ((gx + 1.f) / 2.f) * wx, ry = ((gy + 1.f) / 2.f) * wy, rz = ((gz + 1.f) / 2.f) * wz;
-    const bool outside = !(rx >= 0.f && rx <= wx && ry >= 0.f && ry <= wy && rz >= 0.f && rz <= wz);
-    const float ix = fminf(fmaxf(rx, 0.f), wx), iy = fminf(fmaxf(ry, 0.f), wy), iz = fminf(fmaxf(rz, 0.f), wz);
-    const float fx = floorf(ix), fy = floorf(iy), fz = floorf(iz);
-    const int x0 = min(max((int)fx, 0), m.W - 1), y0 = min(max((int)fy, 0), m.H - 1), z0 = min(max((int)fz, 0), m.D - 1);
-    const float ax1 = ix - fx, ax0 = (fx + 1.f) - ix, ay1 = iy - fy, ay0 = (fy + 1.f) - iy, az1 = iz - fz, az0 = (fz + 1.f) - iz;
-    bx = 0.f; by = 0.f; bz = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const int cz = k >> 2, cy = (k >> 1) & 1, cx = k & 1;
-        const int x = x0 + cx, y = y0 + cy, z = z0 + cz;
-        if (x < m.W && y < m.H && z < m.D) {
-            const float wgt = (cx ? ax1 : ax0) * (cy ? ay1 : ay0) * (cz ? az1 : az0);
-            const float* b = u + ((z * m.H + y) * m.W + x) * 3;
-            bx += b[0] * wgt; by += b[1] * wgt; bz += b[2] * wgt;
-        }
-    }
-    return outside;
-}
 
 // the updates of one element whose normalised base coordinate is (g0x, g0y, g0z); a lane that is not `live` takes part in the loop condition only
 __device__ __forceinline__ FiResult fi_solve(const float* __restrict__ u, const FiDims& m, float g0x, float g0y, float g0z, bool live,
@@ -80,7 +49,7 @@ __device__ __forceinline__ FiResult fi_solve(const float* __restrict__ u, const 
             if (!da_is_finite_coord(gx, gy, gz)) { r.bad = true; done = true; }
             else {
                 float bx, by, bz;
-                r.outside = fi_sample(u, m, gx, gy, gz, bx, by, bz);
+                r.outside = da_field_sample_border(u, m, gx, gy, gz, bx, by, bz);
                 const float nx = 0.f - bx, ny = 0.f - by, nz = 0.f - bz;           // (0 - b: a zero field gives +0)
                 const float ex = m.sx * (nx - r.vx), ey = m.sy * (ny - r.vy), ez = m.sz * (nz - r.vz);
                 r.last = sqrtf(ex * ex + ey * ey + ez * ez);
@@ -135,7 +104,7 @@ fieldinv_dense_kernel(const float* __restrict__ disp, float* __restrict__ out, u
     const int n = blockIdx.y;
     const int V = D * H * W;
     const float* u = disp + (long long)n * V * 3;
-    const FiDims m = fi_dims(D, H, W);
+    const FiDims m = da_field_dims(D, H, W);
     const int lane = threadIdx.x & 63;
     FiAcc acc = {0.0, 0.0, 0.0, 0.0};
     for (DaXcdLoop L = da_xcd_loop(V, 256); L.i - lane < L.end; L.i += L.step) {
@@ -164,7 +133,7 @@ fieldinv_points_kernel(const float* __restrict__ disp, const float* __restrict__
     const int n = blockIdx.y;
     const int V = D * H * W;
     const float* u = disp + (long long)n * V * 3;
-    const FiDims m = fi_dims(D, H, W);
+    const FiDims m = da_field_dims(D, H, W);
     const int lane = threadIdx.x & 63;
     const long long step = (long long)gridDim.x * 256;
     FiAcc acc = {0.0, 0.0, 0.0, 0.0};

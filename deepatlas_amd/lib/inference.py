@@ -6,8 +6,10 @@ probabilities, weighted by a separable window that favours the tile's centre, in
 chunk, the softmax kept in registers, the covering tiles of a voxel added in a fixed order); optionally the same for mirrored copies of the
 tiles (test-time augmentation), the un-mirroring folded into the kernel's index arithmetic.  ops.blend_finalize takes the argmax.
 RecordedPreprocess runs config['preprocess'] and notes what restore_native needs to map a label map back to the grid of the file.
+Registration: frame_of turns such a record into the per-axis map prepared index -> native index, and RegistrationPredictor takes a pair of
+prepared scans to one field and carries the NATIVE moving data onto the fixed file's grid through it (ops.warp_to_grid: one interpolation).
 Out of scope: averaging raw logits instead of probabilities, per-class probability maps, checkpoint ensembling, rotations as test-time
-augmentation, bf16 accumulators, HIP-graph capture, 2-D inputs, registration and joint inference.
+augmentation, bf16 accumulators, HIP-graph capture, 2-D inputs, tiled registration, the inverse direction, joint checkpoints.
 """
 import numpy as np
 import torch
@@ -171,3 +173,87 @@ def restore_native(labels, record, interpolator='nearest', resample=None):
     if tuple(int(s) for s in out.shape[-3:]) != tuple(record['native_size']):
         raise ValueError('the map came back as %s, the file holds %s' % (tuple(out.shape[-3:]), tuple(record['native_size'])))
     return out
+
+
+def prepare(path, name, cfg):
+    """(the file's Volume, image 1 x D x H x W on the device, record for restore_native)."""
+    from . import transforms as T
+    from .nifti import read_nifti
+    from ..models import nifti_data
+    vol = read_nifti(path)
+    sample, record = RecordedPreprocess(cfg.get('preprocess'))({'image': vol.array, 'name': name, 'spacing': vol.spacing})
+    sample = T.SitkToTensor()(sample)
+    if nifti_data.is_nifti(cfg) and cfg.get('crop_size'):
+        before = tuple(int(s) for s in sample['image'].shape[-3:])
+        sample = T.CropTensor(cfg['crop_size'])(sample)
+        record['steps'].append(('crop', before, tuple(int(v) for v in T.CropTensor(cfg['crop_size']).crop_size)))
+    return vol, sample['image'], record
+
+
+# ---- registration: from the prepared grid's field to the files' grids -------------------------------------------------------------------
+def frame_of(record, prepared_size):
+    """The frame of a prepared grid inside its file: per axis, (D, H, W) order, the pair (a, b) of float64 with native index = a * prepared
+    index + b.  Composed from record['steps'], last to first, each step mapping the index after it to the index before it: a resample
+    n = (spacing after / spacing before) p (restore_native's rule), a flip p -> (D - 1) - p along D, a crop p -> p + c.  A negative a is a flip.
+    prepared_size is the (D, H, W) the record's last step left; a record that does not lead from it back to record['native_size'] raises."""
+    size = tuple(int(s) for s in prepared_size)
+    if len(size) != 3:
+        raise ValueError('prepared_size takes three extents (D, H, W), got %r' % (prepared_size,))
+    a = [np.float64(1.0)] * 3
+    b = [np.float64(0.0)] * 3
+    for step in reversed(record['steps']):
+        if step[0] == 'flip':
+            scale, offset = (-1.0, 1.0, 1.0), (float(size[0] - 1), 0.0, 0.0)
+        elif step[0] == 'resample':
+            _, before, sp_before, sp_after = step
+            scale, offset = tuple(sp_after[k] / sp_before[k] for k in (2, 1, 0)), (0.0, 0.0, 0.0)
+            size = tuple(int(s) for s in before)
+        elif step[0] == 'crop':
+            _, before, c = step
+            if len(c) != 6 or any(int(c[k]) < 0 or int(c[k]) + size[k] + int(c[k + 3]) != int(before[k]) for k in range(3)):
+                raise ValueError('the crop %r of %r does not hold a grid of %r' % (tuple(c), tuple(before), size))
+            scale, offset = (1.0, 1.0, 1.0), tuple(float(c[k]) for k in range(3))
+            size = tuple(int(s) for s in before)
+        else:
+            raise ValueError('unknown record step %r' % (step,))
+        a, b = [np.float64(scale[k]) * a[k] for k in range(3)], [np.float64(scale[k]) * b[k] + np.float64(offset[k]) for k in range(3)]
+    if size != tuple(int(s) for s in record['native_size']):
+        raise ValueError('the record leads from %s back to %s, the file holds %s' % (tuple(prepared_size), size, tuple(record['native_size'])))
+    return tuple((a[k], b[k]) for k in range(3))
+
+
+class RegistrationPredictor(object):
+    """A trained registration net on one pair.  field(): the prepared pair -> one displacement field 1 x 3 x D x H x W on the prepared grid
+    (WarpFn's units); with affine_init ('rigid' | 'affine') the pair is pre-aligned first (evalMetrics.affine_align with affine_settings),
+    the net sees (aligned moving, fixed) and its field is composed with the affine by ops.affine_disp, exactly as eval_registration does.
+    apply(): data on the MOVING FILE's grid -> the FIXED FILE's grid through that field (ops.warp_to_grid)."""
+
+    def __init__(self, model, affine_init=None, affine_settings=None):
+        self.model = model
+        self.affine_init = affine_init
+        self.affine_settings = dict(affine_settings or {})
+
+    def field(self, moving_prepared, fixed_prepared):
+        from . import evalMetrics as metrics
+        im_m, im_t = (t.reshape((1, 1) + tuple(t.shape[-3:])) for t in (moving_prepared, fixed_prepared))
+        if tuple(im_m.shape) != tuple(im_t.shape):
+            raise ValueError('the prepared pair differs in shape: %s and %s' % (tuple(im_m.shape[2:]), tuple(im_t.shape[2:])))
+        was_training = self.model.training
+        with torch.no_grad():
+            self.model.eval()
+            if self.affine_init is None:
+                disp = self.model(im_m, im_t)[0]
+            else:
+                theta, im_a = metrics.affine_align(im_m, im_t, mode=self.affine_init, **self.affine_settings)
+                disp = ops.affine_disp(theta, self.model(im_a, im_t)[0])
+        self.model.train(was_training)
+        return disp.detach()
+
+    def apply(self, moving_native, disp, fixed_vol, fixed_record, moving_vol, moving_record, order=1, default=0, prefiltered=False, world=False):
+        """moving_native: D x H x W or C x D x H x W device data on the moving file's grid (its raw intensities, its labels, or with
+        prefiltered=True their B-spline coefficients).  Returns it on the fixed file's grid; with world=True also the displacement in
+        millimetres between the two files' world frames (fixed_vol.affine, moving_vol.affine), 3 x D x H x W."""
+        prepared = tuple(int(s) for s in disp.shape[2:])
+        return ops.warp_to_grid(moving_native, disp, fixed_record['native_size'], frame_of(fixed_record, prepared), frame_of(moving_record, prepared),
+                                order=order, default=default, prefiltered=prefiltered,
+                                world=(fixed_vol.affine, moving_vol.affine) if world else None)

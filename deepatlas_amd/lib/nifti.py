@@ -14,6 +14,9 @@ header / image pairs, RGB and complex data, truncated data) raises a ValueError 
 
 write_nifti(path, array, like=None, spacing=None, affine=None) writes little endian with sform and qform set and vox_offset 352, so a
 prediction can leave the process with its input's geometry (like=the input Volume).
+
+write_nifti_field(path, array (3, nz, ny, nx) float32, like=...) / read_nifti_field(path): a displacement field as a 5-D vector image,
+dim = [5, nx, ny, nz, 1, 3], intent code 1007, the layout ITK and ANTs use; read_nifti and write_nifti keep refusing it.
 """
 import gzip
 import struct
@@ -180,6 +183,59 @@ def read_nifti(path):
     return Volume(arr, spacing, header_affine(h), h)
 
 
+def _resolve_geometry(like, spacing, affine):
+    """write_nifti's geometry rule: (spacing or None, affine 4 x 4 float64)."""
+    if affine is None and like is not None:
+        affine = like.affine
+    if spacing is None and like is not None:
+        spacing = like.spacing
+    if affine is None:
+        affine = np.diag([float(s) for s in (spacing or (1.0, 1.0, 1.0))] + [1.0])
+    affine = np.asarray(affine, dtype=np.float64)
+    if affine.shape != (4, 4):
+        raise ValueError('affine must be 4 x 4')
+    return spacing, affine
+
+
+def _header_bytes(dim8, dtype, spacing, affine, intent_code=0):
+    """The 352 bytes in front of the data: little endian, sform and qform both set (codes 1), vox_offset 352, no scaling."""
+    (qb, qc, qd), qoff, qpix, qfac = affine_quaternion(affine)
+    if spacing is None:
+        spacing = qpix
+    if max(dim8[1:4]) > 32767:
+        raise ValueError('NIfTI-1 extents are 16-bit: shape %s' % (tuple(reversed(dim8[1:4])),))
+    key = np.dtype(dtype).newbyteorder('<').str.lstrip('<|')
+    buf = bytearray(HEADER_BYTES + 4)
+    struct.pack_into('<i', buf, 0, HEADER_BYTES)
+    struct.pack_into('<8h', buf, 40, *dim8)
+    struct.pack_into('<h', buf, 68, intent_code)
+    struct.pack_into('<hh', buf, 70, _CODE_OF[key], np.dtype(dtype).itemsize * 8)
+    struct.pack_into('<8f', buf, 76, qfac, float(spacing[0]), float(spacing[1]), float(spacing[2]), 1.0, 1.0, 1.0, 1.0)
+    struct.pack_into('<f', buf, 108, 352.0)
+    struct.pack_into('<ff', buf, 112, 1.0, 0.0)
+    buf[123] = 2                                                 # NIFTI_UNITS_MM
+    struct.pack_into('<hh', buf, 252, 1, 1)
+    struct.pack_into('<3f', buf, 256, qb, qc, qd)
+    struct.pack_into('<3f', buf, 268, *[float(v) for v in qoff])
+    for row, off in enumerate((280, 296, 312)):
+        struct.pack_into('<4f', buf, off, *[float(v) for v in affine[row]])
+    buf[344:348] = b'n+1\0'
+    return buf
+
+
+def _write_all(path, buf, data):
+    path = str(path)
+    if path.endswith('.gz'):
+        with gzip.open(path, 'wb', compresslevel=1) as f:
+            f.write(bytes(buf))
+            f.write(data)
+    else:
+        with open(path, 'wb') as f:
+            f.write(bytes(buf))
+            f.write(data)
+    return path
+
+
 def write_nifti(path, array, like=None, spacing=None, affine=None):
     """array (nz, ny, nx) in one of the supported dtypes (bool -> uint8, float16 -> float32).  Geometry: `affine` (4 x 4), else `like`'s (a
     Volume), else diag(spacing); `spacing` (x, y, z) defaults to like's, else the affine's column norms, else 1.  Little endian, sform and
@@ -194,43 +250,51 @@ def write_nifti(path, array, like=None, spacing=None, affine=None):
     key = arr.dtype.newbyteorder('<').str.lstrip('<|')
     if key not in _CODE_OF:
         raise ValueError('write_nifti: dtype %s is not a supported NIfTI-1 datatype' % arr.dtype)
-    if affine is None and like is not None:
-        affine = like.affine
-    if spacing is None and like is not None:
-        spacing = like.spacing
-    if affine is None:
-        affine = np.diag([float(s) for s in (spacing or (1.0, 1.0, 1.0))] + [1.0])
-    affine = np.asarray(affine, dtype=np.float64)
-    if affine.shape != (4, 4):
-        raise ValueError('affine must be 4 x 4')
-    (qb, qc, qd), qoff, qpix, qfac = affine_quaternion(affine)
-    if spacing is None:
-        spacing = qpix
+    spacing, affine = _resolve_geometry(like, spacing, affine)
     nz, ny, nx = arr.shape
-    if max(nx, ny, nz) > 32767:
-        raise ValueError('NIfTI-1 extents are 16-bit: shape %s' % (arr.shape,))
-    buf = bytearray(HEADER_BYTES + 4)
-    struct.pack_into('<i', buf, 0, HEADER_BYTES)
-    struct.pack_into('<8h', buf, 40, 3, nx, ny, nz, 1, 1, 1, 1)
-    struct.pack_into('<hh', buf, 70, _CODE_OF[key], arr.dtype.itemsize * 8)
-    struct.pack_into('<8f', buf, 76, qfac, float(spacing[0]), float(spacing[1]), float(spacing[2]), 1.0, 1.0, 1.0, 1.0)
-    struct.pack_into('<f', buf, 108, 352.0)
-    struct.pack_into('<ff', buf, 112, 1.0, 0.0)
-    buf[123] = 2                                                 # NIFTI_UNITS_MM
-    struct.pack_into('<hh', buf, 252, 1, 1)
-    struct.pack_into('<3f', buf, 256, qb, qc, qd)
-    struct.pack_into('<3f', buf, 268, *[float(v) for v in qoff])
-    for row, off in enumerate((280, 296, 312)):
-        struct.pack_into('<4f', buf, off, *[float(v) for v in affine[row]])
-    buf[344:348] = b'n+1\0'
+    buf = _header_bytes((3, nx, ny, nz, 1, 1, 1, 1), arr.dtype, spacing, affine)
     data = np.ascontiguousarray(arr.astype(arr.dtype.newbyteorder('<'), copy=False)).tobytes()
-    path = str(path)
-    if path.endswith('.gz'):
-        with gzip.open(path, 'wb', compresslevel=1) as f:
-            f.write(bytes(buf))
-            f.write(data)
-    else:
-        with open(path, 'wb') as f:
-            f.write(bytes(buf))
-            f.write(data)
-    return path
+    return _write_all(path, buf, data)
+
+
+# ---- displacement fields: a 5-D vector image (dim = [5, nx, ny, nz, 1, 3], intent NIFTI_INTENT_VECTOR), the layout ITK and ANTs write --------
+INTENT_VECTOR = 1007
+
+
+def write_nifti_field(path, array, like=None, spacing=None, affine=None):
+    """array (3, nz, ny, nx) float32: a displacement in millimetres per voxel, component (world x, y, z) first.  Written as dim = [5, nx, ny,
+    nz, 1, 3] with intent code 1007 (vector); the component is the slowest file axis, so the array goes out as it lies.  Geometry as in
+    write_nifti.  read_nifti refuses such a file (more than one volume); read_nifti_field reads it."""
+    arr = np.asarray(array)
+    if arr.ndim != 4 or arr.shape[0] != 3:
+        raise ValueError('write_nifti_field takes a (3, nz, ny, nx) array, got shape %s' % (arr.shape,))
+    if arr.dtype != np.float32:
+        raise ValueError('write_nifti_field takes float32, got %s' % arr.dtype)
+    spacing, affine = _resolve_geometry(like, spacing, affine)
+    _, nz, ny, nx = arr.shape
+    buf = _header_bytes((5, nx, ny, nz, 1, 3, 1, 1), arr.dtype, spacing, affine, intent_code=INTENT_VECTOR)
+    return _write_all(path, buf, np.ascontiguousarray(arr.astype('<f4', copy=False)).tobytes())
+
+
+def read_nifti_field(path):
+    """A file write_nifti_field wrote (or any NIfTI-1 with dim = [5, nx, ny, nz, 1, 3], float32, intent 1007) -> Volume whose array is
+    (3, nz, ny, nx) float32; spacing, affine and header as read_nifti gives them."""
+    name = str(path)
+    raw = _read_all(path)
+    h, order = parse_header(raw, name)
+    dim = h['dim']
+    if dim[0] != 5 or dim[4] != 1 or dim[5] != 3 or min(dim[1:4]) < 1:
+        raise ValueError('%s: dim %s is not a displacement field [5, nx, ny, nz, 1, 3]' % (name, tuple(dim[:6])))
+    if h['intent_code'] != INTENT_VECTOR:
+        raise ValueError('%s: intent code %d, a displacement field has %d (vector)' % (name, h['intent_code'], INTENT_VECTOR))
+    if h['datatype'] != 16:
+        raise ValueError('%s: datatype %d, a displacement field is float32 (16)' % (name, h['datatype']))
+    nx, ny, nz = (int(e) for e in dim[1:4])
+    offset = max(int(h['vox_offset']), HEADER_BYTES + 4)
+    need = 3 * nx * ny * nz * 4
+    if len(raw) < offset + need:
+        raise ValueError('%s: truncated data: %d bytes after offset %d, %d needed' % (name, max(len(raw) - offset, 0), offset, need))
+    arr = np.frombuffer(raw, dtype=np.dtype('f4').newbyteorder(order), count=3 * nx * ny * nz, offset=offset).reshape(3, nz, ny, nx)
+    arr = np.ascontiguousarray(arr.astype(np.float32, copy=True))
+    spacing = tuple(abs(float(p)) or 1.0 for p in h['pixdim'][1:4])
+    return Volume(arr, spacing, header_affine(h), h)

@@ -3607,3 +3607,109 @@ def blend_finalize(acc, return_conf=False):
     with torch.cuda.device(acc.device):
         call('da_blend_finalize', ptr(acc), D * H * W, K, ptr(labels), ptr(conf), stream())
     return (labels, conf) if return_conf else labels
+
+
+# ------------------------------------------------------------------------------------------------
+# applying a registration on the files' own grids (regapply.hip): the cubic B-spline prefilter and the warp through frames.  No autograd.
+# ------------------------------------------------------------------------------------------------
+BSPLINE_HORIZON = 24                # DA_BSPLINE_HORIZON (include/deepatlas_hip.h)
+WARP_ORDERS = (0, 1, 3)
+_PREFILTER_AXES = {0: 4, 1: 2, 2: 1}      # axis of a D x H x W volume -> bit of da_bspline3_prefilter's mask
+
+
+def bspline_prefilter(vol, axes=(0, 1, 2)):
+    """Cubic B-spline coefficients of a D x H x W or C x D x H x W device volume (float32, float64, int16, uint8 or int32), float32 of the same
+    shape: scipy.ndimage.spline_filter(vol, 3, mode='mirror') (da_bspline3_prefilter: pole sqrt(3) - 2, gain 6 per axis, whole-sample mirror
+    boundaries; an axis of extent 1 is left as it is).  axes: the axes of D, H, W (0, 1, 2) to filter, all three by default."""
+    single = _volume4(vol)
+    try:
+        mask = sum(_PREFILTER_AXES[int(a)] for a in set(axes))
+    except (KeyError, TypeError, ValueError):
+        raise ValueError('axes takes a subset of (0, 1, 2) = (D, H, W), got %r' % (axes,))
+    nat.require_cuda(vol)
+    v = (vol.unsqueeze(0) if single else vol).contiguous()
+    C, D, H, W = (int(s) for s in v.shape)
+    out = torch.empty((C, D, H, W), dtype=torch.float32, device=v.device)
+    with torch.cuda.device(v.device):
+        call('da_bspline3_prefilter', ptr(v), PREPROCESS_DTYPE_CODE[v.dtype], ptr(out), C, D, H, W, mask, stream())
+    return out[0] if single else out
+
+
+def _frame3(frame, what):
+    """A frame ((a, b) per axis, (D, H, W) order; lib.inference.frame_of) -> six floats, checked."""
+    import math
+    try:
+        flat = [float(v) for pair in frame for v in pair]
+    except (TypeError, ValueError):
+        flat = []
+    if len(flat) != 6 or len(frame) != 3:
+        raise ValueError('%s must hold three (a, b) pairs in (D, H, W) order, got %r' % (what, frame))
+    if not all(math.isfinite(v) for v in flat) or any(flat[k] == 0.0 for k in (0, 2, 4)):
+        raise ValueError('%s needs finite (a, b) with a != 0, got %r' % (what, frame))
+    return flat
+
+
+def warp_to_grid(moving, disp, out_size, fixed_frame, moving_frame, order=1, default=0, prefiltered=False, world=None):
+    """A moving scan on its own grid carried onto a fixed scan's own grid through a field predicted on the prepared grid, with ONE
+    interpolation (da_warp_frames).  moving: D x H x W or C x Dm x Hm x Wm device volume on the moving file's grid.  disp: 1 x 3 x Dp x Hp x Wp
+    float32 in WarpFn's units (normalised, channel 0 = x).  out_size = (Do, Ho, Wo): the fixed file's grid.  fixed_frame / moving_frame:
+    lib.inference.frame_of's pairs (a, b) per axis, native index = a * prepared index + b.  Output voxel x reads the moving volume at
+    y = a_m (p + u(p)) + b_m with p = (x - b_f) / a_f and u sampled trilinearly under border padding; y outside [-0.5, n - 0.5) on any
+    axis gives `default`.  order 0: nearest, the source dtype bit for bit (labels); 1: linear with edge-clamped taps, float32; 3: cubic
+    B-spline over the coefficients of bspline_prefilter (computed here unless prefiltered=True says `moving` already holds them), float32, not
+    clamped to the input's range.  A non-finite sample position gives NaN in a floating-point output and `default` in an integer one.
+    world = (A_f, A_m), the two files' index-to-world affines (4 x 4 or 3 x 4, acting on (i, j, k) = (W, H, D) index): also returns the
+    displacement in millimetres A_m (y, 1) - A_f (x, 1), float32 3 x Do x Ho x Wo (world x, y, z).  No autograd."""
+    import math
+    import numpy as np
+    single = _volume4(moving, 'moving')
+    if order not in WARP_ORDERS:
+        raise ValueError('order %r: 0 (nearest), 1 (linear) or 3 (cubic B-spline)' % (order,))
+    if not torch.is_tensor(disp) or disp.dim() != 5 or disp.shape[0] != 1 or disp.shape[1] != 3 or disp.dtype != torch.float32:
+        raise ValueError('disp must be a 1 x 3 x D x H x W float32 displacement field, got %s'
+                         % ((tuple(disp.shape), disp.dtype) if torch.is_tensor(disp) else type(disp),))
+    if min(int(s) for s in disp.shape[2:]) < 2:
+        raise ValueError('the displacement field needs >= 2 voxels per axis (align_corners=True), got %s' % (tuple(disp.shape),))
+    if disp[0, 0].numel() >= 2 ** 29:
+        raise ValueError('the displacement field has %d voxels: the warp takes fewer than 2^29' % disp[0, 0].numel())
+    if len(out_size) != 3 or min(int(s) for s in out_size) < 1:
+        raise ValueError('out_size takes three positive extents (D, H, W), got %r' % (out_size,))
+    frames = _frame3(fixed_frame, 'fixed_frame') + _frame3(moving_frame, 'moving_frame')
+    if prefiltered and order != 3:
+        raise ValueError('prefiltered goes with order 3 only')
+    if prefiltered and moving.dtype != torch.float32:
+        raise ValueError('prefiltered coefficients are float32, got %s' % moving.dtype)
+    integer = order == 0 and not moving.dtype.is_floating_point
+    if integer:
+        info = torch.iinfo(moving.dtype)
+        if not math.isfinite(float(default)) or int(default) != default or not info.min <= int(default) <= info.max:
+            raise ValueError('default %r is not a value of %s' % (default, moving.dtype))
+    aff = None
+    if world is not None:
+        try:
+            mats = [np.asarray(A, dtype=np.float64) for A in world]
+        except (TypeError, ValueError):
+            mats = []
+        if len(mats) != 2 or any(A.shape not in ((4, 4), (3, 4)) or not np.isfinite(A).all() for A in mats):
+            raise ValueError('world takes (A_f, A_m), two finite 4 x 4 or 3 x 4 index-to-world matrices')
+        aff = (ctypes.c_double * 24)(*[float(v) for A in mats for v in A[:3].reshape(-1)])
+    v = moving.unsqueeze(0) if single else moving
+    C, Dm, Hm, Wm = (int(s) for s in v.shape)
+    Do, Ho, Wo = (int(s) for s in out_size)
+    if C * Do * Ho * Wo >= PREPROCESS_MAX_VOXELS:
+        raise ValueError('the output has %d elements: the warp takes fewer than 2^31' % (C * Do * Ho * Wo))
+    nat.require_cuda(v, disp)
+    if v.device != disp.device:
+        raise ValueError('moving and disp live on different devices')
+    v = v.contiguous()
+    if order == 3 and not prefiltered:
+        v = bspline_prefilter(v)
+    u = ndhwc(disp.detach())
+    Dp, Hp, Wp = (int(s) for s in u.shape[1:4])
+    out = torch.empty((C, Do, Ho, Wo), dtype=v.dtype if order == 0 else torch.float32, device=v.device)
+    wd = torch.empty((3, Do, Ho, Wo), dtype=torch.float32, device=v.device) if world is not None else None
+    with torch.cuda.device(v.device):
+        call('da_warp_frames', ptr(v), PREPROCESS_DTYPE_CODE[v.dtype], ptr(u), ptr(out), ptr(wd), C, Dm, Hm, Wm, Dp, Hp, Wp, Do, Ho, Wo,
+             (ctypes.c_double * 12)(*frames), aff, int(order), float(default), stream())
+    out = out[0] if single else out
+    return (out, wd) if world is not None else out

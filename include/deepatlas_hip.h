@@ -492,6 +492,51 @@ int da_blend_accumulate(const float* logits, float* acc, int D, int H, int W, in
                         const float* wz, const float* wy, const float* wx, int flip, void* stream);
 int da_blend_finalize(const float* acc, long long V, int K, unsigned char* labels, float* conf, void* stream);
 
+/* ---- applying a registration on the files' own grids (csrc/regapply.hip; the project's own: one interpolation of the native moving data,
+ * cubic B-spline as the reference's resample() defaults to, lib/transforms.py:287) -------------------------------------------------------
+ * Volumes are [C][D][H][W], src_dtype as in the preprocessing section (0 f32, 1 f64, 2 i16, 3 u8, 4 i32).  No workspace, no atomics, every
+ * output element written by one lane from its own inputs: results are bit-identical from run to run.  No autograd.
+ *
+ * da_bspline3_prefilter: dst [C][D][H][W] fp32 = the cubic B-spline coefficients of src, scipy.ndimage.spline_filter(x, 3, mode='mirror'):
+ * per axis the recursive filter with pole z = sqrt(3) - 2 and gain 6 under whole-sample mirror boundaries (x[-k] = x[k], x[n - 1 + k] =
+ * x[n - 1 - k]), c+[k] = 6 x[k] + z c+[k - 1], c[n - 1] = z / (z^2 - 1) (c+[n - 1] + z c+[n - 2]), c[k] = z (c[k + 1] - c+[k]), computed in
+ * fp32.  axes: bit 0 / 1 / 2 = filter along W / H / D (7: the full prefilter; the first launch always converts src to fp32 into dst, so a
+ * mask is the prefilter of the chosen axes alone); an axis of extent 1 is left as it is.  Three launches, W first: along W the combined
+ * causal + anticausal response h_k = sqrt(3) z^|k| is summed directly over mirrored indices from an LDS row segment (lanes along W, Horner
+ * from the outermost tap inwards); along H and D one lane owns one line, neighbouring lanes neighbouring W, and runs the recursion in place
+ * on dst.  Horizon: the direct sum along W takes DA_BSPLINE_HORIZON taps per side and the causal start of the H and D lines
+ * c+[0] = 6 sum_k z^k x[mirror(k)] the same number of terms; |z|^(DA_BSPLINE_HORIZON + 1) = 5e-15, below fp32 rounding of any tap, and no
+ * other truncation is made (a line shorter than the horizon is walked through its mirror images).  src and dst must not be the same buffer
+ * (the W pass reads its neighbours' inputs): DA_ERR_BADARG, as are null pointers, an extent < 1, a src_dtype or axes out of range; 2^31 or more elements: DA_ERR_UNSUPPORTED.
+ *
+ * da_warp_frames: out [C][Do][Ho][Wo] on the fixed scan's native grid, one launch.  For output voxel x = (d, h, w):
+ *   p = (x - b_f) / a_f          continuous index on the prepared fixed grid (double; the reciprocal of a_f is formed once on the host)
+ *   u(p) = s B[u](g(p))          disp [Dp][Hp][Wp][3] fp32, normalised units, channel 0 = x (W axis), sampled trilinearly under border padding
+ *                                at the fp32 normalised coordinate g = p / (size - 1) * 2 - 1 (da_field_sample_border, fieldinv.hip's B[u]),
+ *                                s = (size - 1) / 2 voxels
+ *   q = p + u(p),  y = a_m q + b_m      index on the prepared moving grid, then on the moving scan's native grid (double)
+ *   inside iff -0.5 <= y < n - 0.5 on every axis (ops.resample_axis_table's rule); a voxel outside gets default_value
+ *   order 0: moving[clamp(floor(y + 0.5))], the source dtype copied bit for bit
+ *   order 1: taps f = floor(y), lower clamp(f, 0, n - 1), upper min(lower + 1, n - 1), fraction fp32(y - f), 0 for y < 0; fp32,
+ *            fmaf(t, b - a, a) along W, then H, then D (da_resample_axes' arithmetic)
+ *   order 3: moving = fp32 coefficients of da_bspline3_prefilter (src_dtype 0); sum of 64 taps floor(y) - 1 ... floor(y) + 2 per axis under
+ *            whole-sample mirror indexing (period 2 n - 2; index 0 when n = 1), weights ((1-t)^3, 3t^3 - 6t^2 + 4, -3t^3 + 3t^2 + 3t + 1,
+ *            t^3) / 6 at t = fp32(y - floor(y)); fp32, summed along W, then H, then D; not clamped to the input's range.
+ * frames: 12 host doubles (a, b) per axis in (D, H, W) order, the fixed frame then the moving frame: native index = a * prepared index + b.
+ * A sample position (p, or y after the field) that is NaN, infinite or >= 1e9 in magnitude reads no memory: its voxel gets NaN in a
+ * floating-point output and default_value in an integer one; no other voxel is affected.  No address is formed from a data value.
+ * world (may be NULL) [3][Do][Ho][Wo] fp32 = A_m (y, 1) - A_f (x, 1) in millimetres, for every voxel (inside or not; NaN for a refused
+ * position): affines = 24 host doubles, the 3 x 4 index-to-world matrices A_f then A_m acting on (i, j, k) = (w, h, d); evaluated in
+ * double as M_m y - M_f x + (t_m - t_f) and rounded once.
+ * DA_ERR_BADARG: null pointers, an extent < 1, a prepared extent < 2, order not 0 / 1 / 3, order 3 with src_dtype != 0, an a that is 0 or
+ * not finite, a b that is not finite, world without affines.  DA_ERR_UNSUPPORTED: 2^31 or more elements in moving or out, 2^29 or more
+ * voxels in disp. */
+#define DA_BSPLINE_HORIZON 24
+int da_bspline3_prefilter(const void* src, int src_dtype, float* dst, int C, int D, int H, int W, int axes, void* stream);
+int da_warp_frames(const void* moving, int src_dtype, const float* disp, void* out, float* world, int C, int Dm, int Hm, int Wm,
+                   int Dp, int Hp, int Wp, int Do, int Ho, int Wo, const double* frames, const double* affines, int order,
+                   double default_value, void* stream);
+
 /* synthetic volumes generated on the device (row f4; the structure of the BASELINE configs' synthetic data, the reference's sample
  * convention lib/datasets.py:150-166: image [N][D][H][W] fp32 in [0,1], segmentation uint8).  Counter-based hash: element = f(seed,
  * sample0 + n, voxel), restated bit-exactly in oracle/datapath.py.  mode 0: iid image ~ U[0,1), labels ~ U{0..C-1};

@@ -12,7 +12,7 @@ plain averaging of the overlapping tiles); optionally the connected-component cl
 (lib/inference.py restore_native: the left_to_right flip and the resample are undone, nearest neighbour) and written as <name>_seg.nii.gz
 (uint8) with the input's geometry; --save-confidence adds <name>_conf.nii.gz (float32, restored linearly).  With labels given, Dice per scan
 and its mean are printed on the native grid, with --surface-metrics also HD95 and ASSD at the file's spacing.
-Out of scope: registration and joint inference, writing displacement fields, per-class probability maps, checkpoint ensembling, overlapping
+Out of scope: joint inference (registration and displacement fields: predict_reg.py), per-class probability maps, checkpoint ensembling, overlapping
 the host's gzip with the device."""
 import argparse
 import json
@@ -125,19 +125,9 @@ def postprocess_setting(args):
 
 
 def prepare(path, name, cfg):
-    """(the file's Volume, image 1 x D x H x W on the device, record for restore_native)."""
-    from deepatlas_amd.lib import transforms as T
-    from deepatlas_amd.lib.inference import RecordedPreprocess
-    from deepatlas_amd.lib.nifti import read_nifti
-    from deepatlas_amd.models import nifti_data
-    vol = read_nifti(path)
-    sample, record = RecordedPreprocess(cfg.get('preprocess'))({'image': vol.array, 'name': name, 'spacing': vol.spacing})
-    sample = T.SitkToTensor()(sample)
-    if nifti_data.is_nifti(cfg) and cfg.get('crop_size'):
-        before = tuple(int(s) for s in sample['image'].shape[-3:])
-        sample = T.CropTensor(cfg['crop_size'])(sample)
-        record['steps'].append(('crop', before, tuple(int(v) for v in T.CropTensor(cfg['crop_size']).crop_size)))
-    return vol, sample['image'], record
+    """lib/inference.py prepare (shared with predict_reg.py): (the file's Volume, image 1 x D x H x W on the device, record for restore_native)."""
+    from deepatlas_amd.lib.inference import prepare as shared
+    return shared(path, name, cfg)
 
 
 def predict_volume(model, image, cfg, patch, blend, want_conf):
