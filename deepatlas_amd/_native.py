@@ -144,6 +144,10 @@ SIGNATURES = {
     'da_affine_warp_ws_bytes': (SZ, [I, I, I, I]),
     'da_affine_warp_bwd_theta': (I, [P, P, P, P, I, I, I, I, I, P, SZ, P]),
     'da_affine_compose_disp': (I, [P, P, P, I, I, I, I, P]),
+    'da_refine_moments_ws_bytes': (SZ, [I, I, I, I]),
+    'da_refine_moments': (I, [P, P, P, I, I, I, I, P, P, SZ, P]),
+    'da_refine_host_state': (I, [P, F, F, F, I, F, F, I, P]),
+    'da_refine_step': (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
     'da_label_fusion_vote': (I, [P, I, LL, P, P, P, I, I, I, I, I, P, P, P]),
     'da_local_msd_weights_ws_bytes': (SZ, [I, I, I, I, I]),
     'da_local_msd_weights': (I, [P, P, I, I, I, I, I, I, F, P, P, SZ, P]),

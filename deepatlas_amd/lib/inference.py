@@ -226,18 +226,38 @@ class RegistrationPredictor(object):
     """A trained registration net on one pair.  field(): the prepared pair -> one displacement field 1 x 3 x D x H x W on the prepared grid
     (WarpFn's units); with affine_init ('rigid' | 'affine') the pair is pre-aligned first (evalMetrics.affine_align with affine_settings),
     the net sees (aligned moving, fixed) and its field is composed with the affine by ops.affine_disp, exactly as eval_registration does.
+    With refine (a dict of lib/refine.py refine_field keywords) that field is then refined on this very pair: against the ORIGINAL prepared moving
+    image and the fixed one, so with affine_init it is the composed field that is refined -- the only one that maps the fixed frame onto the
+    original moving image.  net_field() is the field before that step and refined() the step alone, for callers that report both.
     apply(): data on the MOVING FILE's grid -> the FIXED FILE's grid through that field (ops.warp_to_grid)."""
 
-    def __init__(self, model, affine_init=None, affine_settings=None):
+    def __init__(self, model, affine_init=None, affine_settings=None, refine=None):
         self.model = model
         self.affine_init = affine_init
         self.affine_settings = dict(affine_settings or {})
+        self.refine = dict(refine) if refine is not None else None
 
-    def field(self, moving_prepared, fixed_prepared):
-        from . import evalMetrics as metrics
+    @staticmethod
+    def _pair(moving_prepared, fixed_prepared):
         im_m, im_t = (t.reshape((1, 1) + tuple(t.shape[-3:])) for t in (moving_prepared, fixed_prepared))
         if tuple(im_m.shape) != tuple(im_t.shape):
             raise ValueError('the prepared pair differs in shape: %s and %s' % (tuple(im_m.shape[2:]), tuple(im_t.shape[2:])))
+        return im_m, im_t
+
+    def field(self, moving_prepared, fixed_prepared):
+        disp = self.net_field(moving_prepared, fixed_prepared)
+        return disp if self.refine is None else self.refined(moving_prepared, fixed_prepared, disp)
+
+    def refined(self, moving_prepared, fixed_prepared, disp):
+        """`disp` refined on this pair with the predictor's refine settings (lib/refine.py refine_field; the images as float32)."""
+        from .refine import refine_field
+        im_m, im_t = self._pair(moving_prepared, fixed_prepared)
+        return refine_field(im_m.float(), im_t.float(), disp, **self.refine)
+
+    def net_field(self, moving_prepared, fixed_prepared):
+        """The field the net predicts (with affine_init composed with the affine), before any refinement."""
+        from . import evalMetrics as metrics
+        im_m, im_t = self._pair(moving_prepared, fixed_prepared)
         was_training = self.model.training
         with torch.no_grad():
             self.model.eval()

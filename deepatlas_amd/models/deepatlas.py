@@ -33,7 +33,7 @@ from .base import BaseExperiment
 from . import nifti_data
 from .joint import DeepAtlasJointStep
 from .registration import (atlas_fusion_text, check_atlas_fusion, check_jac_penalty, check_sim_loss, dataset_volumes, eval_atlas_fusion,
-                           eval_registration, jac_name_suffix)
+                           eval_registration, jac_name_suffix, refuse_refine)
 from .segmentation import SegmentationExperiment, refuse_patch
 from ..lib.inference import refuse_tile_blend
 from ..lib import datasets as med_data
@@ -63,6 +63,7 @@ class DeepAtlasExperiment(BaseExperiment):
         cfg = self.config
         refuse_patch(cfg, 'joint')
         refuse_tile_blend(cfg, 'joint')
+        refuse_refine(cfg, 'joint')
         if cfg['debug_mode']:
             print("Debug mode")
             cfg['print_batch_period'] = cfg['valid_epoch_period'] = 2

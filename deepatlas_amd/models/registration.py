@@ -24,6 +24,9 @@ image and segmentation a rigid misalignment, the same one in every epoch (seeded
 config['report_tre'] (None default: off | a dict with 'amp_vox' and optionally 'points') makes validation also run the known-deformation
 probe (lib/evalMetrics.py known_deformation_tre) on the fixed image of every pair, one more net forward: the landmark error in voxels against
 the exact inverse of a known smooth field (tre_mean_vox, tre_max_vox, tre_initial_mean_vox).  It takes no part in the experiment's name.
+config['refine'] (None default: off | an iteration count | a dict of lib/refine.py refine_field keywords) makes validation also refine every pair's
+field on that pair (refined_dice_avg, refined_fold_frac, refine_sim_before, refine_sim_after); the regulariser weight and the similarity default to
+the training ones.  It takes no part in the experiment's name, and model selection and best_score stay on the net's own field.
 config['data'] other than 'synthetic' (models/nifti_data.py) trains on the ordered pairs of the NIfTI volumes of a list file; misalign and report_tre
 are synthetic-only and raise with such data.
 """
@@ -43,6 +46,7 @@ from .joint import RegistrationStep, SIM_LOSSES, make_jac_penalty, make_ic_penal
 from .segmentation import SegmentationExperiment, refuse_patch
 from ..lib.inference import refuse_tile_blend
 from ..lib import datasets as med_data
+from ..lib import refine as refine_lib
 from ..lib import evalMetrics as metrics
 from ..lib import affine as affine_lib
 from ..lib.transforms import rigid_index_affine
@@ -88,7 +92,8 @@ def misalign_pairs(im_m, seg_m, names, misalign):
     return ops.spatial_resample(im_m.float(), seg_m, np.stack(mats), interpolator='linear')
 
 
-def eval_registration(model, dataloader, n_classes, device, report_ic=False, affine_init=None, affine_settings=None, misalign=None, tre_probe=None):
+def eval_registration(model, dataloader, n_classes, device, report_ic=False, affine_init=None, affine_settings=None, misalign=None, tre_probe=None,
+                      refine=None):
     """Registration metrics of `model` over a loader of (moving image, fixed image, moving seg, fixed seg, has_moving_seg, name) batches.
     Pairs without a moving segmentation have no registration Dice and are skipped for it; every pair counts for the Jacobian statistics.
     Returns a dict: dice_per_class [C-1] (mean over the pairs that have the class: nanmean), dice_avg (mean over the classes that occur),
@@ -103,8 +108,12 @@ def eval_registration(model, dataloader, n_classes, device, report_ic=False, aff
     affine_dice_per_class / affine_dice_avg, the Dice under the affine's field alone (the inverse-consistency report is then that of the net on the aligned pair).
     tre_probe (a dict amp_vox, points): the known-deformation probe (metrics.known_deformation_tre) runs on the fixed image of every batch, one
     more net forward, and the dict gains tre_mean_vox / tre_initial_mean_vox (means over the pairs of the per-pair mean landmark error against
-    the exact inverse of the known field, and of what no registration would leave) and tre_max_vox (the largest landmark error of any pair)."""
+    the exact inverse of the known field, and of what no registration would leave) and tre_max_vox (the largest landmark error of any pair).
+    refine (a dict of lib/refine.py refine_field keywords): every pair's field -- with affine_init the composed one -- is additionally refined on that
+    pair against the original moving image, and the dict gains refined_dice_per_class / refined_dice_avg, refined_fold_frac and refine_sim_before /
+    refine_sim_after (the means over the pairs of each pair's 1 - NCC under the net's field and under the refined one; batches beyond 64 pairs are refined in chunks); every other entry is the net's own."""
     dice_aff = []
+    dice_ref, fold_ref, sim_ref = [], [], {'before': [], 'after': []}
     tre = {'tre_mean_vox': [], 'tre_max_vox': [], 'tre_initial_mean_vox': []}
     dice, dice_id, jac = [], [], {'nonpos_frac': [], 'mean': [], 'std': []}
     ic = {'mean_vox': [], 'max_vox': [], 'outside_frac': []}
@@ -114,7 +123,7 @@ def eval_registration(model, dataloader, n_classes, device, report_ic=False, aff
             im_m, im_t = im_m.to(device), im_t.to(device)
             if misalign is not None:
                 im_m, seg_m = misalign_pairs(im_m, seg_m.to(device), _name, misalign)
-            disp_aff = None
+            disp_aff, im_m0 = None, im_m
             if affine_init is None:
                 disp = net_disp = model(im_m, im_t)[0]
             else:
@@ -126,6 +135,15 @@ def eval_registration(model, dataloader, n_classes, device, report_ic=False, aff
             js = metrics.jacobian_stats(disp)
             for k in jac:
                 jac[k].append(js[k])
+            if refine is not None:
+                parts = []
+                for k in range(0, im_t.shape[0], ops.REFINE_MAX_BATCH):          # the kernels take 64 samples per call; a sample's statistics are its own
+                    m_k, t_k, d_k = (t[k:k + ops.REFINE_MAX_BATCH] for t in (im_m0.float(), im_t.float(), disp))
+                    parts.append(refine_lib.refine_field(m_k, t_k, d_k, **refine))
+                    sim_ref['before'].append(refine_lib.one_minus_ncc(m_k, t_k, d_k, per_sample=True).cpu().numpy())
+                    sim_ref['after'].append(refine_lib.one_minus_ncc(m_k, t_k, parts[-1], per_sample=True).cpu().numpy())
+                disp_r = parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+                fold_ref.append(metrics.jacobian_stats(disp_r)['nonpos_frac'])
             if report_ic:
                 ics = metrics.inverse_consistency(net_disp, model(im_t, im_m)[0])
                 for k in ic:
@@ -141,8 +159,11 @@ def eval_registration(model, dataloader, n_classes, device, report_ic=False, aff
                 dice_id.append(metrics.registration_dice(sm, st_, torch.zeros_like(dk), n_classes))
                 if disp_aff is not None:
                     dice_aff.append(metrics.registration_dice(sm, st_, disp_aff[keep.to(device)], n_classes))
+                if refine is not None:
+                    dice_ref.append(metrics.registration_dice(sm, st_, disp_r[keep.to(device)], n_classes))
     out = {}
-    for key, rows in (('dice', dice), ('identity_dice', dice_id)) + ((('affine_dice', dice_aff),) if affine_init is not None else ()):
+    for key, rows in ((('dice', dice), ('identity_dice', dice_id)) + ((('affine_dice', dice_aff),) if affine_init is not None else ())
+                      + ((('refined_dice', dice_ref),) if refine is not None else ())):
         per = _nanmean(np.concatenate(rows, 0), axis=0) if rows else np.full(n_classes - 1, np.nan)
         out[key + '_per_class'] = per
         out[key + '_avg'] = float(_nanmean(per)) if np.isfinite(per).any() else float('nan')
@@ -155,6 +176,10 @@ def eval_registration(model, dataloader, n_classes, device, report_ic=False, aff
         for k in tre:
             rows = np.concatenate(tre[k]) if tre[k] else np.full(1, np.nan)
             out[k] = float(np.max(rows) if k == 'tre_max_vox' else np.mean(rows))
+    if refine is not None:
+        out['refined_fold_frac'] = float(np.mean(np.concatenate(fold_ref))) if fold_ref else float('nan')
+        for k in sim_ref:
+            out['refine_sim_' + k] = float(np.mean(np.concatenate(sim_ref[k]))) if sim_ref[k] else float('nan')
     out['n_pairs'] = int(sum(len(a) for a in jac['mean']))
     out['n_dice_pairs'] = int(sum(len(a) for a in dice))
     return out
@@ -298,6 +323,26 @@ def check_report_tre(cfg):
     return {'amp_vox': amp, 'points': int(points)}
 
 
+def check_refine(cfg):
+    """config['refine']: None (off, the default, also when absent), an iteration count or a dict of lib/refine.py refine_field keywords: validation
+    then also refines every pair's field (eval_registration).  What the value leaves open comes from the training config (the regulariser weight,
+    the similarity).  It takes no part in the experiment's name, in model selection or in best_score.  Returns None or the complete dict."""
+    return refine_lib.settings_from_config(cfg, cfg.get('refine'))
+
+
+def refuse_refine(cfg, experiment):
+    """The experiments that do not refine at validation say so instead of ignoring the key."""
+    if cfg.get('refine') is not None:
+        raise ValueError("config['refine'] is not supported by the %s experiment: refine a trained net's fields with the registration experiment or predict_reg.py"
+                         % experiment)
+
+
+def refine_text(res):
+    if 'refined_dice_avg' not in res:
+        return ''
+    return ', refined Dice {:.4f} (folding {:.4f})'.format(res['refined_dice_avg'], res['refined_fold_frac'])
+
+
 def tre_text(res):
     """What a validation or test line adds when the known-deformation probe is on ('' otherwise)."""
     if 'tre_mean_vox' not in res:
@@ -350,6 +395,7 @@ class RegistrationExperiment(BaseExperiment):
         self.affine_init, self.affine_settings = check_affine_init(cfg)
         self.misalign = check_misalign(cfg)
         self.report_tre = check_report_tre(cfg)
+        self.refine = check_refine(cfg)
         nifti_data.refuse_synthetic_only(cfg, ('misalign', 'report_tre'))
         self.exp_name = self.experiment_name(cfg)
         run_dir = "debug_reg" if cfg['debug_mode'] else self.exp_name
@@ -501,7 +547,8 @@ class RegistrationExperiment(BaseExperiment):
 
     def eval(self, dataloader):
         res = eval_registration(self.model, dataloader, self.config['n_classes'], self.device, report_ic=self.report_ic,
-                                affine_init=self.affine_init, affine_settings=self.affine_settings, misalign=self.misalign, tre_probe=self.report_tre)
+                                affine_init=self.affine_init, affine_settings=self.affine_settings, misalign=self.misalign, tre_probe=self.report_tre,
+                                refine=self.refine)
         if self.atlas_fusion:
             # the volumes behind the loader's pairs, each segmented from the training volumes (all labelled here), at most atlas_fusion_max
             if self.training_data_loader is None:
@@ -533,11 +580,12 @@ class RegistrationExperiment(BaseExperiment):
             tag = 'validation_{}/'.format(self.config['data'])
             for k in ('dice_avg', 'identity_dice_avg', 'nonpos_frac', 'det_mean', 'det_std'):
                 self.writer.add_scalar(tag + k, res[k], global_step=self.global_step)
-            for k in ('ic_mean_vox', 'ic_max_vox', 'ic_outside_frac', 'affine_dice_avg', 'tre_mean_vox', 'tre_max_vox', 'tre_initial_mean_vox'):
+            for k in ('ic_mean_vox', 'ic_max_vox', 'ic_outside_frac', 'affine_dice_avg', 'tre_mean_vox', 'tre_max_vox', 'tre_initial_mean_vox',
+                      'refined_dice_avg', 'refined_fold_frac', 'refine_sim_before', 'refine_sim_after'):
                 if k in res:
                     self.writer.add_scalar(tag + k, res[k], global_step=self.global_step)
-        print("Validation: registration Dice Avg: {:.4f} (identity {:.4f}{}){}  det J {:.4f} +- {:.4f}, folding {:.3%}{}{} ({:.3f} sec) {}".format(
-            score, res['identity_dice_avg'], affine_text(res), atlas_fusion_text(res), res['det_mean'], res['det_std'], res['nonpos_frac'], ic_text(res), tre_text(res), time.time() - start_time,
+        print("Validation: registration Dice Avg: {:.4f} (identity {:.4f}{}){}  det J {:.4f} +- {:.4f}, folding {:.3%}{}{}{} ({:.3f} sec) {}".format(
+            score, res['identity_dice_avg'], affine_text(res), atlas_fusion_text(res), res['det_mean'], res['det_std'], res['nonpos_frac'], refine_text(res), ic_text(res), tre_text(res), time.time() - start_time,
             datetime.datetime.now().strftime("%D %H:%M:%S")))
         if self.current_epoch % self.config['save_ckpts_epoch_period'] == 0:
             self.save_checkpoint({'epoch': self.current_epoch,

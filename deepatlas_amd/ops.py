@@ -2411,6 +2411,76 @@ def affine_disp(theta, disp=None, size=None):
     return ncdhw(out)
 
 
+# ------------------------------------------------------------------------------------------------
+# instance refinement of a displacement field (refine.hip); the loop is lib/refine.py refine_field
+# ------------------------------------------------------------------------------------------------
+REFINE_STATE_FLOATS = 12        # DA_REFINE_STATE_FLOATS (include/deepatlas_hip.h)
+REFINE_MAX_BATCH = 64
+
+
+def refine_lr3(lr_vox, size):
+    """Per-channel (x, y, z) step in WarpFn's normalised units of a step of `lr_vox` voxels on a volume of `size` = (D, H, W):
+    lr_vox * 2 / (extent - 1), 0 along an axis of extent 1 (nothing moves there)."""
+    D, H, W = (int(s) for s in size)
+    return tuple(float(lr_vox) * 2.0 / (e - 1) if e > 1 else 0.0 for e in (W, H, D))
+
+
+def refine_host_state(lr3, betas, eps, step, grad_scale, lambda_sim, it):
+    """The REFINE_STATE_FLOATS scalars da_refine_step reads for Adam step `step` (>= 1) and history slot `it`, as a CPU float32 tensor
+    (da_refine_host_state: the bias corrections in double, as da_adam_step forms them).  Needs no device."""
+    out = (ctypes.c_float * REFINE_STATE_FLOATS)()
+    call('da_refine_host_state', (ctypes.c_float * 3)(*[float(v) for v in lr3]), float(betas[0]), float(betas[1]), float(eps), int(step),
+         float(grad_scale), float(lambda_sim), int(it), out)
+    return torch.tensor(list(out), dtype=torch.float32)
+
+
+def refine_args(moving, fixed, disp):
+    """Checks of the refinement entry points -> (moving N x D x H x W x 1, fixed likewise, N, D, H, W); disp N x 3 x D x H x W is only checked."""
+    if moving.dim() != 5 or moving.shape[1] != 1 or tuple(moving.shape) != tuple(fixed.shape):
+        raise ValueError('refinement expects two N x 1 x D x H x W volumes of one shape, got %s and %s' % (tuple(moving.shape), tuple(fixed.shape)))
+    N, _, D, H, W = (int(s) for s in moving.shape)
+    if disp.dim() != 5 or tuple(disp.shape) != (N, 3, D, H, W):
+        raise ValueError('displacement field must be N x 3 x D x H x W matching the volumes, got %s for %s' % (tuple(disp.shape), tuple(moving.shape)))
+    if moving.dtype != torch.float32 or fixed.dtype != torch.float32 or disp.dtype != torch.float32:
+        raise ValueError('refinement expects float32 volumes and a float32 displacement field')
+    if not 1 <= N <= REFINE_MAX_BATCH:
+        raise ValueError('refinement takes 1..%d samples per call, got %d' % (REFINE_MAX_BATCH, N))
+    nat.require_cuda(moving, fixed, disp)
+    return ndhwc(moving.detach()), ndhwc(fixed.detach()), N, D, H, W
+
+
+def refine_moments(mv, fx, u, stats=None, ws=None):
+    """stats N x 8 float64 (NCCFn's layout) of NCC(warp(moving, identity + u), fixed), the warped image never written.  mv, fx, u: dense
+    N x D x H x W x C tensors (refine_args / ndhwc).  ws: (pointer, size) of a workspace the caller owns (a captured loop), else the shared one."""
+    N, D, H, W = (int(s) for s in u.shape[:4])
+    if stats is None:
+        stats = torch.empty((N, 8), dtype=torch.float64, device=u.device)
+    wp, wn = ws if ws is not None else _ws(nat.lib().da_refine_moments_ws_bytes(N, D, H, W), u)
+    call('da_refine_moments', ptr(mv), ptr(fx), ptr(u), N, D, H, W, ptr(stats), wp, wn, stream())
+    return stats
+
+
+def refine_step(mv, fx, u, stats, state, g_extra=None, m=None, v=None, grad_out=None, hist=None, update=False):
+    """da_refine_step on dense N x D x H x W x C tensors: grad_out (if given) = lambda_sim d(1 - NCC)/du + g_extra; update: Adam on u, m, v in place."""
+    N, D, H, W = (int(s) for s in u.shape[:4])
+    call('da_refine_step', ptr(mv), ptr(fx), ptr(u), ptr(g_extra), ptr(stats), ptr(state), ptr(m), ptr(v), ptr(grad_out), ptr(hist),
+         int(hist.numel()) if hist is not None else 0, N, D, H, W, 1 if update else 0, stream())
+
+
+def refine_ncc_grad(moving, fixed, disp, lambda_sim=1.0):
+    """(1 - NCC, gradient) of lambda_sim * NormalizedCrossCorrelationLoss(WarpFn(moving, disp), fixed) with respect to disp, fused: two passes
+    over the volume, neither the warped image nor its cotangent written.  moving, fixed N x 1 x D x H x W, disp N x 3 x D x H x W float32 on
+    the GPU; returns a 0-d tensor (unweighted) and N x 3 x D x H x W.  No autograd."""
+    mv, fx, N, D, H, W = refine_args(moving, fixed, disp)
+    u = ndhwc(disp.detach())
+    with torch.cuda.device(u.device):
+        stats = refine_moments(mv, fx, u)
+        state = refine_host_state((0.0, 0.0, 0.0), (0.9, 0.999), 1e-8, 1, 1.0, lambda_sim, 0).to(u.device)
+        grad, hist = torch.empty_like(u), torch.empty((1,), dtype=torch.float32, device=u.device)
+        refine_step(mv, fx, u, stats, state, grad_out=grad, hist=hist)
+    return hist.reshape(()), ncdhw(grad)
+
+
 class XentFn(Function):
     """Cross-entropy family of the loss registry (lib/loss.py:739-761) on N x C x D x H x W logits: mode 0 nn.CrossEntropyLoss,
     1 FocalLoss.forward (lib/loss.py:181-213), 2 SoftCrossEntropy.forward with a probability target (:115-154)."""

@@ -802,6 +802,31 @@ int da_affine_warp_bwd_theta(const float* g, const float* src, const float* thet
                              int C, void* ws, size_t ws_bytes, void* stream);
 int da_affine_compose_disp(const float* theta, const float* disp /*[N][D][H][W][3] or NULL*/, float* out /*[N][D][H][W][3]*/,
                            int N, int D, int H, int W, void* stream);
+/* Instance refinement of a displacement field (refine.hip): descend on 1 - mean_n NCC(moving_n o (identity + disp_n), fixed_n) for this pair,
+ * the warped image never written.  moving / fixed [N][D][H][W] fp32 (one channel), disp [N][D][H][W][3]; everything else is da_warp_fwd's
+ * convention (normalised units, channels (x, y, z) = (W, H, D), trilinear, zeros outside, align_corners=True; at an integer coordinate the
+ * derivative is da_warp_bwd's).  1 <= N <= 64; an extent of 1 is legal (that axis samples index 0 and has gradient 0); < 2^29 voxels per sample
+ * (DA_ERR_UNSUPPORTED otherwise).  A sample coordinate that is NaN, infinite or >= 1e9 in magnitude makes the sums of its sample NaN (moments) and
+ * its own three gradient / disp / m / v elements NaN (step); nothing is indexed by a data value.
+ * moments: stats [N][8] doubles in da_ncc_fwd's layout {mean_w, mean_f, cov, var_w, var_f, ncc, V, 0} of w = the warped moving image, what
+ * da_ncc_fwd(warp, fixed) returns up to rounding.  Per-workgroup partial sums in double added in workgroup order: two runs are bit-identical.
+ * step: one voxel per lane.  g = lambda_sim d(1 - mean_n NCC_n)/d disp (from stats) + g_extra (the caller's regulariser gradient, already
+ * weighted; NULL: none).  grad_out (or NULL) receives g.  update != 0: Adam on disp, m, v in place (a lane touches them at its own voxel only)
+ * with the scalars of `state`, DA_REFINE_STATE_FLOATS floats in DEVICE memory = {1 / bc1, beta1, beta2, eps, 1 / sqrt(bc2), grad_scale,
+ * lambda_sim, lr_x / bc1, lr_y / bc1, lr_z / bc1, iter, 0}: da_adam_step_dev's state6 for lr = 1, the similarity weight, the per-channel step
+ * sizes (lr_c in normalised units; da_adam_step's own lr / bc1, so a channel updates exactly as da_adam_step with lr = lr_c would) and the slot
+ * of hist this launch fills.  da_refine_host_state fills a HOST array with them for Adam step `step` (>= 1).  update == 0 needs grad_out, update != 0
+ * needs m and v (DA_ERR_BADARG otherwise).  hist (or NULL; hist_len floats): hist[iter] = 1 - mean_n stats[n][5], written by one lane when
+ * 0 <= iter < hist_len.  The launch arguments do not depend on the iteration, so the sequence can be captured in a HIP graph and replayed. */
+#define DA_REFINE_STATE_FLOATS 12
+size_t da_refine_moments_ws_bytes(int N, int D, int H, int W);
+int da_refine_moments(const float* moving, const float* fixed, const float* disp, int N, int D, int H, int W, double* stats /*[N][8]*/,
+                      void* ws, size_t ws_bytes, void* stream);
+int da_refine_host_state(const float* lr3, float beta1, float beta2, float eps, int step, float grad_scale, float lambda_sim, int iter,
+                         float* state_host /*[DA_REFINE_STATE_FLOATS]*/);
+int da_refine_step(const float* moving, const float* fixed, float* disp, const float* g_extra /*[N][D][H][W][3] or NULL*/, const double* stats,
+                   const float* state, float* m, float* v, float* grad_out /*or NULL*/, float* hist /*or NULL*/, int hist_len,
+                   int N, int D, int H, int W, int update, void* stream);
 /* Inverse of a displacement field and transport of points through it (fieldinv.hip).  disp [N][D][H][W][3], units and channel order as above,
  * is the pull-back map x -> x + u(x).  B[u](p) = F.grid_sample(u, p, 'bilinear', padding_mode='border', align_corners=True): the unnormalised
  * coordinate is clamped to [0, size - 1] before the taps are formed, a tap of index `size` has weight 0 and is not read.  With g the

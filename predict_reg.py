@@ -2,6 +2,7 @@
 
     python predict_reg.py --ckpt CKPT --output-dir DIR (--moving FILE... --fixed FILE... | --data-dir DIR --pair-list FILE)
         [--config JSON] [--interp linear|bspline] [--moving-labels FILE...] [--fixed-labels FILE...] [--label-dir DIR] [--save-field]
+        [--refine ITERS [--refine-lr VOX] [--refine-lambda-reg W] [--refine-sim ncc|lncc|mi]]
 
 The config is the train_config.json the experiment wrote beside its checkpoints (--config names another; find_config and load_model are
 predict_seg.py's).  Per pair: lib/nifti.py reads both files; config['preprocess'] (and config['crop_size']) prepares both as training did
@@ -14,6 +15,10 @@ adds ..._seg.nii.gz (nearest neighbour, the labels' dtype, config['preprocess']'
 --save-field ..._field.nii.gz (the displacement in millimetres between the two files' world frames, lib/nifti.py write_nifti_field).
 Per pair the Jacobian statistics of the prepared-grid field are printed; with both label sets also the Dice of the warped labels on the
 fixed file's grid beside the Dice a zero field gives through the same op; at the end their means.
+--refine ITERS refines every pair's field on that pair (lib/refine.py refine_field: ITERS Adam iterations of --refine-lr voxels on the similarity
+under the bending energy; the weight and the similarity default to the checkpoint's train_config.json) and prints
+`refine: 1-NCC a.bcde -> f.ghij (K iterations)`; everything written and the det J line then belong to the refined field, and with both label
+sets the Dice of the unrefined field is printed beside the refined one.
 Out of scope: reorientation by the affine and oblique grids, the inverse direction, tiled registration, joint checkpoints beyond loading
 their reg_ file, clamping the cubic overshoot."""
 import argparse
@@ -41,7 +46,23 @@ def build_parser():
     parser.add_argument('--fixed-labels', nargs='+', default=None, metavar='FILE', help='label files of the fixed scans, one per --fixed, to score against')
     parser.add_argument('--label-dir', default=None, type=str, help='with --pair-list: directory of both scans\' label files, named as the training dataset names them')
     parser.add_argument('--save-field', action='store_true', help='also write <pair>_field.nii.gz: the displacement in millimetres')
+    parser.add_argument('--refine', default=None, type=int, metavar='ITERS', help="refine every pair's field on that pair by ITERS Adam iterations (default: off)")
+    parser.add_argument('--refine-lr', default=None, type=float, metavar='VOX', help='step of --refine in voxels (default 0.1)')
+    parser.add_argument('--refine-lambda-reg', default=None, type=float, metavar='W', help="bending-energy weight of --refine (default: the checkpoint's lambda_reg)")
+    parser.add_argument('--refine-sim', default=None, choices=['ncc', 'lncc', 'mi'], help="similarity of --refine (default: the checkpoint's sim_loss)")
     return parser
+
+
+def refine_settings(args, cfg):
+    """None without --refine, else the refine_field keywords: the flags over the checkpoint's training config (lib/refine.py settings_from_config).
+    The other --refine-* flags need --refine."""
+    from deepatlas_amd.lib.refine import settings_from_config
+    given = {k: v for k, v in (('lr_vox', args.refine_lr), ('lambda_reg', args.refine_lambda_reg), ('sim', args.refine_sim)) if v is not None}
+    if args.refine is None:
+        if given:
+            raise ValueError('--refine-lr / --refine-lambda-reg / --refine-sim go with --refine ITERS')
+        return None
+    return settings_from_config(cfg, dict(given, iters=args.refine))
 
 
 def read_pair_list(path):
@@ -121,11 +142,15 @@ def native_dice(warped, truth, n_class):
     return float(np.nanmean(d)) if np.any(~np.isnan(d)) else float('nan')
 
 
-def format_pair(name, jac, dice=None, identity=None):
+def format_pair(name, jac, dice=None, identity=None, unrefined=None):
     line = 'det J mean %.4f std %.4f folds %d' % (jac['mean'], jac['std'], jac['folds'])
     if dice is not None:
-        line = 'Dice Avg: %.6f (identity %.6f), ' % (dice, identity) + line
+        line = 'Dice Avg: %.6f (identity %.6f%s), ' % (dice, identity, '' if unrefined is None else ', unrefined %.6f' % unrefined) + line
     return '%s: %s' % (name, line)
+
+
+def format_refine(before, after, iters):
+    return 'refine: 1-NCC %.4f -> %.4f (%d iterations)' % (before, after, iters)
 
 
 def main(argv=None):
@@ -134,16 +159,18 @@ def main(argv=None):
     from deepatlas_amd.lib import transforms as T
     from deepatlas_amd.lib.inference import RegistrationPredictor, prepare
     from deepatlas_amd.lib.nifti import write_nifti, write_nifti_field
+    from deepatlas_amd.lib.refine import one_minus_ncc
     from deepatlas_amd.models import nifti_data
     from deepatlas_amd.models.registration import check_affine_init
     from predict_seg import find_config, load_model
     with open(find_config(args.ckpt, args.config)) as f:
         cfg = json.load(f)
     pairs = resolve_pairs(args, cfg)
+    refine = refine_settings(args, cfg)               # (checked before anything is loaded)
     affine_init, affine_settings = check_affine_init(cfg)
     device = torch.device('cuda:{}'.format(args.device) if args.device.isdigit() else args.device)
     torch.cuda.set_device(device)
-    predictor = RegistrationPredictor(load_model(cfg, args.ckpt, device), affine_init, affine_settings)
+    predictor = RegistrationPredictor(load_model(cfg, args.ckpt, device), affine_init, affine_settings, refine=refine)
     n_class = int(cfg.get('n_classes') or 0)
     label_filters = [t for t in T.make_preprocess(cfg.get('preprocess')) if isinstance(t, T.SegmentationLabelFilter)]
     order = INTERP_ORDER[args.interp]
@@ -153,7 +180,12 @@ def main(argv=None):
         vol_m, im_m, rec_m = prepare(m_path, m_name, cfg)
         vol_f, im_f, rec_f = prepare(f_path, f_name, cfg)
         nifti_data.check_shapes([[(im_m, None, m_name), (im_f, None, f_name)]], [cfg['model']])
-        disp = predictor.field(im_m.to(device), im_f.to(device))
+        im_m, im_f = im_m.to(device), im_f.to(device)
+        disp = net_disp = predictor.net_field(im_m, im_f)
+        if refine is not None:
+            disp = predictor.refined(im_m, im_f, net_disp)
+            sim = [float(one_minus_ncc(*(t.reshape((1, 1) + tuple(t.shape[-3:])).float() for t in (im_m, im_f)), d)) for d in (net_disp, disp)]
+            print(format_refine(sim[0], sim[1], refine['iters']))
         out = predictor.apply(native_tensor(vol_m.array, device), disp, vol_f, rec_f, vol_m, rec_m, order=order, world=args.save_field)
         warped, world = out if args.save_field else (out, None)
         stem = os.path.join(args.output_dir, name)
@@ -162,7 +194,7 @@ def main(argv=None):
             write_nifti_field(stem + '_field.nii.gz', world.cpu().numpy(), like=vol_f)
         js = metrics.jacobian_stats(disp)
         jac = {'mean': float(js['mean'][0]), 'std': float(js['std'][0]), 'folds': int(js['n_nonpos'][0])}
-        dice = identity = None
+        dice = identity = unrefined = None
         if m_lab is not None:
             lab_vol, lab = read_labels(m_lab, m_name, label_filters)
             if tuple(lab.shape) != tuple(vol_m.array.shape):
@@ -179,13 +211,16 @@ def main(argv=None):
                 truth_dev = native_tensor(truth, device, labels=True)
                 still = predictor.apply(lab_dev, torch.zeros_like(disp), vol_f, rec_f, vol_m, rec_m, order=0)
                 dice, identity = native_dice(moved, truth_dev, n_class), native_dice(still, truth_dev, n_class)
-        rows.append((jac, dice, identity))
-        print(format_pair(name, jac, dice, identity))
+                if refine is not None:
+                    unrefined = native_dice(predictor.apply(lab_dev, net_disp, vol_f, rec_f, vol_m, rec_m, order=0), truth_dev, n_class)
+        rows.append((jac, dice, identity, unrefined))
+        print(format_pair(name, jac, dice, identity, unrefined))
     mean_jac = {'mean': float(np.mean([r[0]['mean'] for r in rows])), 'std': float(np.mean([r[0]['std'] for r in rows])),
                 'folds': int(round(float(np.mean([r[0]['folds'] for r in rows]))))}
     scored = [r for r in rows if r[1] is not None]
     print(format_pair('mean over %d pairs' % len(rows), mean_jac,
-                      float(np.nanmean([r[1] for r in scored])) if scored else None, float(np.nanmean([r[2] for r in scored])) if scored else None))
+                      float(np.nanmean([r[1] for r in scored])) if scored else None, float(np.nanmean([r[2] for r in scored])) if scored else None,
+                      float(np.nanmean([r[3] for r in scored])) if scored and refine is not None else None))
 
 
 if __name__ == '__main__':

@@ -56,7 +56,16 @@ def build_config(args):
     apply_inverse_consistency_arguments(config)
     apply_affine_arguments(config)
     apply_tre_arguments(config)
+    apply_refine_arguments(config)
     return apply_data_arguments(config)
+
+
+def apply_refine_arguments(config):
+    """--refine-eval ITERS -> config['refine'] = ITERS; an absent flag leaves no key, so a run without it has the config it always had."""
+    iters = config.pop('refine_eval', None)
+    if iters is not None:
+        config['refine'] = int(iters)
+    return config
 
 
 def apply_tre_arguments(config):
@@ -181,8 +190,16 @@ def add_tre_arguments(parser):
     return parser
 
 
+def add_refine_arguments(parser):
+    """Instance refinement at validation (registration experiment only)."""
+    parser.add_argument('--refine-eval', default=None, type=int, metavar='ITERS',
+                        help="validation also refines every pair's field on that pair by ITERS Adam iterations on the similarity under the training "
+                             "regulariser (lib/refine.py) and prints the refined Dice and folding fraction; model selection stays on the net's own field")
+    return parser
+
+
 def main(argv=None):
-    args = add_tre_arguments(add_affine_arguments(add_inverse_consistency_arguments(add_common_arguments(argparse.ArgumentParser())))).parse_args(argv)
+    args = add_refine_arguments(add_tre_arguments(add_affine_arguments(add_inverse_consistency_arguments(add_common_arguments(argparse.ArgumentParser()))))).parse_args(argv)
     exp = RegistrationExperiment(build_config(args))
     if not args.test_only:
         exp.train()
